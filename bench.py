@@ -16,7 +16,15 @@ torch.distributed.run directly (RANK / WORLD_SIZE in the environment) it is simp
 `--workload long` is BASELINE.json configs[4] per GPU: 32,768 pairs of 10 kbp x 10 kbp, banded
 Smith-Waterman (512 diagonals), int32 cells.
 
-Rank 0 prints ONE JSON line.  Extra objects:
+A plain run does only what the headline needs: it sets up, warms up, times `--steps` steps, writes
+the outputs of the last timed step when `--dump-outputs DIR` is given, and prints the line (metric,
+value, unit, higher_is_better, dtype, ms_per_step, config).  `--dump-outputs DIR` writes the scores
+that step handed its caller (all ranks' scores after the all-gather at N > 1) as DIR/scores.npy in
+float64, exact for int16 and int32 scores; above 64 MB a fixed, evenly strided sample of the pairs
+is written instead.  The inputs depend only on the arguments (seeded generator), so two builds
+can be compared output for output.
+
+Rank 0 prints ONE JSON line.  Extra objects, only with `--full`:
   roofline ....... HBM roofline of the dominant kernel from ALGORITHMIC bytes
                    (R + F + 2 per pair) / average launch duration
                    measured with events on the launch stream.
@@ -60,6 +68,7 @@ AFFINE = dict(open_read=-5, ext_read=-1, open_ref=-5, ext_ref=-1)     # SURVEY.m
 HBM_PEAK_GBPS = 8000.0
 PMC_PROFILES = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_final.json")) +
                       glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_long_c5.json")))      # (--workload long's kernel)
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000          # --dump-outputs: the arrays of all files together (under 64 MB with the headers)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -230,6 +239,23 @@ def timed_steps(fn, steps, warmup, world):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     return elapsed
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array (a tensor or ndarray, one row per pair) as out_dir/<name>.npy in float64, DUMP_LIMIT_BYTES
+    in all; an array above its share keeps every k-th row from row 0 (the same rows every run).  Returns {name: rows kept}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    kept = {}
+    for name, a in arrays.items():
+        a = np.asarray(a.cpu().numpy() if hasattr(a, "cpu") else a).astype(np.float64)
+        if a.nbytes > share:
+            stride = (a.nbytes + share - 1) // share          # ceil: at most `share` bytes kept
+            a = a[::stride]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        kept[name] = int(a.shape[0])
+    return kept
 
 
 def kernel_launch_ms(eng, opt, reads, refs, out, reps):
@@ -696,22 +722,27 @@ def selftest_rank(args, world, rank):
     for _ in range(args.steps):
         full = shard.all_gather_scores(local, n_total=n * world)
     elapsed = time.perf_counter() - t0
-    mine = torch.tensor([int(local.to(torch.int64).sum())], dtype=torch.int64)
-    dist.all_reduce(mine)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"scores": full})
+    if args.full:
+        mine = torch.tensor([int(local.to(torch.int64).sum())], dtype=torch.int64)
+        dist.all_reduce(mine)
     if rank == 0:
-        # the CPU leg of a real N > 1 line, on a small synthetic batch: rank 0 runs the oracle while the others wait below
-        from versalignlib_amd import synth
-        h_reads, h_refs = synth.make_pairs(512, R, F, seed=2000)
-        cpu, _ = cpu_baseline(torch.from_numpy(h_reads), torch.from_numpy(h_refs), affine=True, seconds=0.2, simd_seconds=0.1)
-        print(json.dumps({"metric": "launcher self-test (no alignment computed)", "value": 0.0, "unit": "none",
-                          "n_gpus": world, "steps": args.steps, "warmup": 0, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-                          "data": "launcher-selftest", "backend": "gloo",
-                          "roofline": roofline_record(n, R, F, None, "(none: the self-test runs no kernel)", ""),
-                          "cpu_baseline": cpu,
-                          "multi_gpu": {"n_ranks_seen": dist.get_world_size(), "gathered_pairs": int(full.numel()),
-                                        "gather_checksum": int(full.to(torch.int64).sum()),
-                                        "sum_of_rank_checksums": int(mine.item()),
-                                        "checksum_ok": int(full.to(torch.int64).sum()) == int(mine.item())}}), flush=True)
+        line = {"metric": "launcher self-test (no alignment computed)", "value": 0.0, "unit": "none",
+                "n_gpus": world, "steps": args.steps, "warmup": 0, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+                "data": "launcher-selftest", "backend": "gloo"}
+        if args.full:
+            # the CPU leg of a real N > 1 line, on a small synthetic batch: rank 0 runs the oracle while the others wait below
+            from versalignlib_amd import synth
+            h_reads, h_refs = synth.make_pairs(512, R, F, seed=2000)
+            cpu, _ = cpu_baseline(torch.from_numpy(h_reads), torch.from_numpy(h_refs), affine=True, seconds=0.2, simd_seconds=0.1)
+            line.update({"roofline": roofline_record(n, R, F, None, "(none: the self-test runs no kernel)", ""),
+                         "cpu_baseline": cpu,
+                         "multi_gpu": {"n_ranks_seen": dist.get_world_size(), "gathered_pairs": int(full.numel()),
+                                       "gather_checksum": int(full.to(torch.int64).sum()),
+                                       "sum_of_rank_checksums": int(mine.item()),
+                                       "checksum_ok": int(full.to(torch.int64).sum()) == int(mine.item())}})
+        print(json.dumps(line), flush=True)
     dist.barrier()
     dist.destroy_process_group()
 
@@ -728,13 +759,23 @@ def main(argv=None):
                     help="short: BASELINE configs[1]/[3] (150x500 SW affine, default); long: configs[4] per GPU "
                          "(10 kbp x 10 kbp banded SW, int32 cells)")
     ap.add_argument("--pairs", type=int, default=0, help="pairs per GPU (default: the config's size)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline legs")
-    ap.add_argument("--no-abi", action="store_true", help="skip the plugin-ABI (PCIe-inclusive) leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also every figure and check beside the headline: roofline, multi_gpu, half_float, linear_gap, "
+                         "alignments, length_sorted, abi, cpu_baseline, verified (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline legs")
+    ap.add_argument("--no-abi", action="store_true", help="with --full: skip the plugin-ABI (PCIe-inclusive) leg")
     ap.add_argument("--abi-threads", type=int, default=0, help="num_threads of the ABI leg (default: host cores, <= 16)")
     ap.add_argument("--child-in-plugin-shards", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--selftest-launcher", action="store_true",
                     help="CPU/gloo self-test of launcher + all-gather + result relay; computes no alignment")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+        argv += ["--dump-outputs", args.dump_outputs]          # (the last one counts: ranks start in ROOT, not here)
 
     if args.child_in_plugin_shards:
         return child_in_plugin_shards(args.child_in_plugin_shards, args.abi_threads or 16)
@@ -800,10 +841,12 @@ def main(argv=None):
     elapsed = timed_steps(step, args.steps, args.warmup, world)
     total_cells = float(n) * RR * FF * world * args.steps
     value = total_cells / elapsed / 1e9
-    timed_scores = local.clone() if rank == 0 else None       # what the last timed step wrote (later legs reuse `local`)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"scores": gathered[0]})          # what the last timed step handed its caller
+    timed_scores = local.clone() if rank == 0 and args.full else None      # the same, for `verified` (the legs reuse `local`)
 
     multi = None
-    if world > 1:
+    if world > 1 and args.full:
         # evidence that the collective did its job: every rank's shard is in the gathered vector
         mine = local.to(torch.int64).sum().reshape(1)
         dist.all_reduce(mine)
@@ -819,7 +862,6 @@ def main(argv=None):
     rc = 0
     if rank == 0:
         assert gathered[0].numel() == n * world
-        k_ms = kernel_launch_ms(eng, 0, reads, refs, local, max(3, min(args.steps, 10)))
         d = eng.describe(0, n)
         cells = d.get("score_cells", "int16")
         if long_mode:
@@ -846,106 +888,108 @@ def main(argv=None):
             # it); the cells the band actually holds -- what the kernel sweeps -- are far fewer: both rates, side by side
             **({"swept_gcups": round(world * n * d.get("band_cells_per_pair", 0) / elapsed * args.steps / 1e9, 1),
                 "band_cells_per_pair": d.get("band_cells_per_pair"), "full_matrix_cells_per_pair": RR * FF} if long_mode else {}),
-            "roofline": roofline_record(n, RR, FF, k_ms, kernel_name, pmc_key,
-                                        {"band_waves_per_cu": d.get("band_waves_per_cu"), "band_lds_per_wave": d.get("band_lds_per_wave")} if long_mode else None),
         }
-        if multi is not None:
-            line["multi_gpu"] = multi
-            if not multi["checksum_ok"] or multi["n_ranks_seen"] != world:
-                rc = 3
-        if not long_mode:
-            # the half-float-cell kernel (what the plugin picks by itself for this scoring): identical scores
-            eng_f16 = hipkernel.Engine(RR, FF, affine_sc, device=local_rank)
-            f16_scores = eng_f16.score_device(0, reads, refs)
-            torch.cuda.synchronize()
-            f16_ms = kernel_launch_ms(eng_f16, 0, reads, refs, f16_scores, 5)
-            eng.score_device(0, reads, refs, local)
-            torch.cuda.synchronize()
-            line["half_float"] = {"cells": eng_f16.describe(0, n).get("score_cells"),
-                                  "identical_to_int16_kernel": bool(torch.equal(local, f16_scores)),
-                                  "kernel_ms": round(f16_ms, 4), "kernel_gcups": round(n * RR * FF / (f16_ms * 1e-3) / 1e9, 1),
-                                  "note": "v_pk_maximum3_f16 recurrence on integers of magnitude <= 2048 (exact in fp16); "
-                                          "the engine's own choice for this scoring, bit-identical results"}
-            eng_f16.close()
-            del f16_scores
-            eng_lin = hipkernel.Engine(RR, FF, lin_sc, device=local_rank)
-            lin_ms = kernel_launch_ms(eng_lin, 0, reads, refs, local, 5)
-            line["linear_gap"] = {"kernel_ms": round(lin_ms, 4), "kernel_gcups": round(n * RR * FF / (lin_ms * 1e-3) / 1e9, 1),
-                                  "cells": eng_lin.describe(0, n).get("score_cells"),
-                                  "note": "reference's own gap model (bit-exact path), same batch"}
-            # BASELINE config 3 (NW + traceback) on the same batch, device-resident: extra evidence,
-            # never part of `value`
-            try:
-                AL = RR + FF
-                rows = torch.empty((n, 2, AL), dtype=torch.uint8, device=device)
-                idx = torch.empty((n, 4), dtype=torch.int16, device=device)
-                line["alignments"] = {}
-                # (sw_linear: the call the reference's own timing loop makes, src/impl/main.cpp:278-287, device-resident here)
-                for name, e, opt, aff in (("nw_affine_traceback", eng, 1, True), ("nw_linear_traceback", eng_lin, 1, False),
-                                          ("sw_linear_traceback", eng_lin, 0, False)):
-                    e.align_device(opt, reads, refs, rows, idx)
-                    torch.cuda.synchronize()
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    e.align_device(opt, reads, refs, rows, idx)
-                    e1.record()
-                    torch.cuda.synchronize()
-                    ms = e0.elapsed_time(e1)
-                    line["alignments"][name] = {"ms": round(ms, 3), "gcups": round(n * RR * FF / (ms * 1e-3) / 1e9, 1),
-                                                "algorithmic_GBps": round(n * (3 * AL + 8) / (ms * 1e-3) / 1e9, 1),
-                                                "verified": verify_alignments(rows, idx, opt, reads, refs, aff)}
-                    if line["alignments"][name]["verified"]["mismatches"]:
-                        rc = 4
-                del rows, idx
-            except hipkernel.HipKernelError as e:
-                line["alignments"] = {"error": str(e)[:200]}
-            eng_lin.close()
-            # a mixed-length batch of the same size, classified, packed and swept by length class on
-            # the device (ragged_batching = 2) against the padded sweep of the same bytes -- identical scores required
-            try:
-                line["length_sorted"] = length_sorted_leg(reads, refs, affine_sc, local_rank)
-                if not line["length_sorted"]["identical_to_padded_sweep"]:
-                    rc = 4
-            except hipkernel.HipKernelError as e:
-                line["length_sorted"] = {"error": str(e)[:200]}
-            if not args.no_abi:
+        if args.full:
+            k_ms = kernel_launch_ms(eng, 0, reads, refs, local, max(3, min(args.steps, 10)))
+            line["roofline"] = roofline_record(n, RR, FF, k_ms, kernel_name, pmc_key,
+                                               {"band_waves_per_cu": d.get("band_waves_per_cu"), "band_lds_per_wave": d.get("band_lds_per_wave")} if long_mode else None)
+            if multi is not None:
+                line["multi_gpu"] = multi
+                if not multi["checksum_ok"] or multi["n_ranks_seen"] != world:
+                    rc = 3
+            if not long_mode:
+                # the half-float-cell kernel (what the plugin picks by itself for this scoring): identical scores
+                eng_f16 = hipkernel.Engine(RR, FF, affine_sc, device=local_rank)
+                f16_scores = eng_f16.score_device(0, reads, refs)
+                torch.cuda.synchronize()
+                f16_ms = kernel_launch_ms(eng_f16, 0, reads, refs, f16_scores, 5)
+                eng.score_device(0, reads, refs, local)
+                torch.cuda.synchronize()
+                line["half_float"] = {"cells": eng_f16.describe(0, n).get("score_cells"),
+                                      "identical_to_int16_kernel": bool(torch.equal(local, f16_scores)),
+                                      "kernel_ms": round(f16_ms, 4), "kernel_gcups": round(n * RR * FF / (f16_ms * 1e-3) / 1e9, 1),
+                                      "note": "v_pk_maximum3_f16 recurrence on integers of magnitude <= 2048 (exact in fp16); "
+                                              "the engine's own choice for this scoring, bit-identical results"}
+                eng_f16.close()
+                del f16_scores
+                eng_lin = hipkernel.Engine(RR, FF, lin_sc, device=local_rank)
+                lin_ms = kernel_launch_ms(eng_lin, 0, reads, refs, local, 5)
+                line["linear_gap"] = {"kernel_ms": round(lin_ms, 4), "kernel_gcups": round(n * RR * FF / (lin_ms * 1e-3) / 1e9, 1),
+                                      "cells": eng_lin.describe(0, n).get("score_cells"),
+                                      "note": "reference's own gap model (bit-exact path), same batch"}
+                # BASELINE config 3 (NW + traceback) on the same batch, device-resident: extra evidence,
+                # never part of `value`
                 try:
-                    threads = args.abi_threads or min(16, host_cores())
-                    line["abi"] = abi_leg(reads, refs, threads)
-                    # the plugin picks the half-float-cell kernel for this scoring: that is the kernel the call contains
-                    for key in ("score_alignments_sw", "score_alignments_sw_ascii"):
-                        line["abi"][key]["ratio_to_kernel_ms"] = round(line["abi"][key]["ms"] / line["half_float"]["kernel_ms"], 3)
-                except Exception as e:
-                    line["abi"] = {"error": str(e)[:300]}
-                visible = torch.cuda.device_count()
-                if world > 1 and visible > 1:
-                    # one host process driving several devices through the plugin key hip_devices (and the RCCL all-gather
-                    # inside the plugin), on the real devices of this node while the other ranks wait on the host.  In a
-                    # CHILD process: this path has never met more than one real device, and whatever it does there must
-                    # not take the rank that prints the line with it.
-                    line["abi_in_plugin_shards"] = in_plugin_shards_child(min(world, visible), args.abi_threads or min(16, host_cores()))
-        oracle_scores = None
-        if not args.no_cpu:
-            # N == 1: the full CPU legs (10-30 s).  N > 1: the same oracle on a short sample (~1.5 s + ~1 s of the AVX2
-            # sweep) on rank 0's host CPUs while the other ranks wait at the final barrier -- the CPU path timed "in the
-            # same run" at every N, without holding N - 1 GPUs for half a minute
-            short = world > 1
-            if long_mode:
-                line["cpu_baseline"], oracle_scores = cpu_baseline(reads, refs, affine=False, R=RR, F=FF, band=LONG_BAND,
-                                                                   seconds=1.5 if short else 12.0)
-            else:
-                line["cpu_baseline"], oracle_scores = cpu_baseline(reads, refs, affine=True, seconds=1.5 if short else 12.0,
-                                                                   simd_seconds=1.0 if short else 6.0)
-                if not short:
-                    line["linear_gap"]["cpu_port"], _ = cpu_baseline(reads, refs, affine=False, simd_seconds=3.0)
-                    line["linear_gap"]["cpu_reference"] = reference_cpu_kernels(reads, refs)
-        # the timed kernel's own output against the oracle, in this very run: the sample cpu_baseline scored (or a
-        # small fresh one when the CPU legs are off / N > 1); a mismatch fails the run
-        line["verified"] = verify_scores(timed_scores, reads, refs, affine=not long_mode, R=RR, F=FF,
-                                         band=LONG_BAND if long_mode else 0, oracle_scores=oracle_scores,
-                                         pairs=8192 if not long_mode else 16)
-        if line["verified"]["mismatches"]:
-            rc = 4
+                    AL = RR + FF
+                    rows = torch.empty((n, 2, AL), dtype=torch.uint8, device=device)
+                    idx = torch.empty((n, 4), dtype=torch.int16, device=device)
+                    line["alignments"] = {}
+                    # (sw_linear: the call the reference's own timing loop makes, src/impl/main.cpp:278-287, device-resident here)
+                    for name, e, opt, aff in (("nw_affine_traceback", eng, 1, True), ("nw_linear_traceback", eng_lin, 1, False),
+                                              ("sw_linear_traceback", eng_lin, 0, False)):
+                        e.align_device(opt, reads, refs, rows, idx)
+                        torch.cuda.synchronize()
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        e.align_device(opt, reads, refs, rows, idx)
+                        e1.record()
+                        torch.cuda.synchronize()
+                        ms = e0.elapsed_time(e1)
+                        line["alignments"][name] = {"ms": round(ms, 3), "gcups": round(n * RR * FF / (ms * 1e-3) / 1e9, 1),
+                                                    "algorithmic_GBps": round(n * (3 * AL + 8) / (ms * 1e-3) / 1e9, 1),
+                                                    "verified": verify_alignments(rows, idx, opt, reads, refs, aff)}
+                        if line["alignments"][name]["verified"]["mismatches"]:
+                            rc = 4
+                    del rows, idx
+                except hipkernel.HipKernelError as e:
+                    line["alignments"] = {"error": str(e)[:200]}
+                eng_lin.close()
+                # a mixed-length batch of the same size, classified, packed and swept by length class on
+                # the device (ragged_batching = 2) against the padded sweep of the same bytes -- identical scores required
+                try:
+                    line["length_sorted"] = length_sorted_leg(reads, refs, affine_sc, local_rank)
+                    if not line["length_sorted"]["identical_to_padded_sweep"]:
+                        rc = 4
+                except hipkernel.HipKernelError as e:
+                    line["length_sorted"] = {"error": str(e)[:200]}
+                if not args.no_abi:
+                    try:
+                        threads = args.abi_threads or min(16, host_cores())
+                        line["abi"] = abi_leg(reads, refs, threads)
+                        # the plugin picks the half-float-cell kernel for this scoring: that is the kernel the call contains
+                        for key in ("score_alignments_sw", "score_alignments_sw_ascii"):
+                            line["abi"][key]["ratio_to_kernel_ms"] = round(line["abi"][key]["ms"] / line["half_float"]["kernel_ms"], 3)
+                    except Exception as e:
+                        line["abi"] = {"error": str(e)[:300]}
+                    visible = torch.cuda.device_count()
+                    if world > 1 and visible > 1:
+                        # one host process driving several devices through the plugin key hip_devices (and the RCCL all-gather
+                        # inside the plugin), on the real devices of this node while the other ranks wait on the host.  In a
+                        # CHILD process: this path has never met more than one real device, and whatever it does there must
+                        # not take the rank that prints the line with it.
+                        line["abi_in_plugin_shards"] = in_plugin_shards_child(min(world, visible), args.abi_threads or min(16, host_cores()))
+            oracle_scores = None
+            if not args.no_cpu:
+                # N == 1: the full CPU legs (10-30 s).  N > 1: the same oracle on a short sample (~1.5 s + ~1 s of the AVX2
+                # sweep) on rank 0's host CPUs while the other ranks wait at the final barrier -- the CPU path timed "in the
+                # same run" at every N, without holding N - 1 GPUs for half a minute
+                short = world > 1
+                if long_mode:
+                    line["cpu_baseline"], oracle_scores = cpu_baseline(reads, refs, affine=False, R=RR, F=FF, band=LONG_BAND,
+                                                                       seconds=1.5 if short else 12.0)
+                else:
+                    line["cpu_baseline"], oracle_scores = cpu_baseline(reads, refs, affine=True, seconds=1.5 if short else 12.0,
+                                                                       simd_seconds=1.0 if short else 6.0)
+                    if not short:
+                        line["linear_gap"]["cpu_port"], _ = cpu_baseline(reads, refs, affine=False, simd_seconds=3.0)
+                        line["linear_gap"]["cpu_reference"] = reference_cpu_kernels(reads, refs)
+            # the timed kernel's own output against the oracle, in this very run: the sample cpu_baseline scored (or a
+            # small fresh one when the CPU legs are off / N > 1); a mismatch fails the run
+            line["verified"] = verify_scores(timed_scores, reads, refs, affine=not long_mode, R=RR, F=FF,
+                                             band=LONG_BAND if long_mode else 0, oracle_scores=oracle_scores,
+                                             pairs=8192 if not long_mode else 16)
+            if line["verified"]["mismatches"]:
+                rc = 4
         print(json.dumps(line), flush=True)
         if rc == 4:
             print("bench.py: results differ from the oracle (see `verified`)", file=sys.stderr)

@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 from conftest import ROOT
 
 
@@ -20,7 +22,7 @@ def _run(*argv, timeout=300):
 
 
 def test_plain_command_starts_two_ranks_and_relays_one_line():
-    p = _run("--gpus", "2", "--selftest-launcher", "--steps", "2", "--pairs", "1001")
+    p = _run("--gpus", "2", "--selftest-launcher", "--steps", "2", "--pairs", "1001", "--full")
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines                       # ONE line on stdout, everything else on stderr
@@ -36,6 +38,50 @@ def test_plain_command_starts_two_ranks_and_relays_one_line():
     assert cpu["simd"] is None or "error" in cpu["simd"] or (cpu["simd"]["value"] > 0 and cpu["simd"]["identical_to_scalar_oracle"])
     roof = line["roofline"]
     assert {"bound", "achieved", "peak", "unit", "frac", "traffic"} <= set(roof) and roof["peak"] == 8000.0
+
+
+def test_without_full_the_line_is_the_headline_alone():
+    """A plain run prints the headline and takes no runs of its own beside the timed steps: no roofline, CPU baseline or
+    multi_gpu check (those come with --full)."""
+    p = _run("--gpus", "2", "--selftest-launcher", "--steps", "3", "--pairs", "1001")
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == 2 and line["steps"] == 3 and line["ms_per_step"] >= 0
+    assert {"metric", "value", "unit"} <= set(line)
+    assert not {"roofline", "cpu_baseline", "multi_gpu"} & set(line)
+
+
+def test_dump_outputs_writes_the_gathered_scores(tmp_path):
+    """--dump-outputs DIR (relative to the caller's directory, not the repository's): rank 0 writes the all-gathered
+    scores of the last step as float64, the same in every run with the same arguments."""
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    n = 1001
+    for tag in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--selftest-launcher", "--steps", "2",
+                            "--pairs", str(n), "--dump-outputs", tag], env=env, cwd=str(tmp_path), stdout=subprocess.PIPE,
+                           stderr=subprocess.PIPE, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+    a, b = np.load(str(tmp_path / "a" / "scores.npy")), np.load(str(tmp_path / "b" / "scores.npy"))
+    assert a.dtype == np.float64 and np.array_equal(a, b)
+    exp = np.concatenate([((np.arange(n, dtype=np.int64) * 7 + r * 1000003) % 30011).astype(np.int16) for r in range(2)])
+    assert np.array_equal(a, exp.astype(np.float64))
+
+
+def test_dump_outputs_keeps_a_fixed_sample_under_the_limit(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8000)
+    small, big = np.arange(100, dtype=np.int16), np.arange(3000, dtype=np.int32)      # 800 B and 24000 B as float64
+    kept = bench.dump_outputs(str(tmp_path), {"small": small, "big": big})            # 4000 B each: every 6th row of big
+    assert kept == {"small": 100, "big": 500}
+    got = np.load(str(tmp_path / "big.npy"))
+    assert got.dtype == np.float64 and np.array_equal(got, big[::6].astype(np.float64))
+    assert np.array_equal(np.load(str(tmp_path / "small.npy")), small.astype(np.float64))
+    assert sum(os.path.getsize(str(tmp_path / f)) for f in ("small.npy", "big.npy")) <= 8000 + 2 * 128
 
 
 def test_real_line_builds_its_cpu_leg_for_every_world_size():

@@ -162,7 +162,7 @@ def test_bench_on_two_real_gpus():
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
     proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                           "--pairs", "131072", "--no-abi"], env=env, cwd=ROOT, stdout=subprocess.PIPE,
+                           "--pairs", "131072", "--no-abi", "--full"], env=env, cwd=ROOT, stdout=subprocess.PIPE,
                           stderr=subprocess.PIPE, text=True, timeout=900)
     assert proc.returncode == 0, proc.stderr[-2000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
@@ -172,6 +172,36 @@ def test_bench_on_two_real_gpus():
     assert line["multi_gpu"]["n_ranks_seen"] == 2 and line["multi_gpu"]["checksum_ok"]
     assert line["multi_gpu"]["gathered_pairs"] == 2 * 131072
     assert line["verified"]["mismatches"] == 0 and line["verified"]["pairs"] > 0
+
+
+def test_plain_bench_line_and_dumped_scores(tmp_path):
+    """`bench.py --gpus 1` without --full, on a small batch: the headline line alone, and --dump-outputs writes the
+    scores of the last timed step -- the same in two runs, and the oracle's scores of the batch bench.py generates."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    n, dumps = 4096, []
+    for tag in ("a", "b"):
+        proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                               "--pairs", str(n), "--dump-outputs", tag], env=env, cwd=str(tmp_path), stdout=subprocess.PIPE,
+                              stderr=subprocess.PIPE, text=True, timeout=600)
+        assert proc.returncode == 0, proc.stderr[-2000:]
+        lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, proc.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["unit"] == "GCUPS" and line["higher_is_better"] is True and line["dtype"] == "int16"
+        assert not {"roofline", "half_float", "linear_gap", "alignments", "abi", "cpu_baseline", "verified"} & set(line)
+        dumps.append(np.load(str(tmp_path / tag / "scores.npy")))
+    assert dumps[0].dtype == np.float64 and dumps[0].shape == (n,)
+    assert np.array_equal(dumps[0], dumps[1])
+    reads, refs = bench.synth_on_device(n, torch.device("cuda", 0), seed=2000)
+    sc = cpu_ref.Scoring.make(2, -1, -3, -3, **bench.AFFINE)
+    exp = cpu_ref.score(0, reads.cpu().numpy(), refs.cpu().numpy(), sc, threads=8, affine=True)
+    assert np.array_equal(dumps[0], exp.astype(np.float64))
 
 
 _RCCL_REHEARSAL = r"""

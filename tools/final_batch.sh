@@ -13,9 +13,9 @@ export TMPDIR=/tmp
 bash tools/pmc_passes.sh $TAG --modes sw_affine16,sw_affine,sw_linear,nw_linear || exit 1
 python tools/pmc_summary.py $R/gpurun_out/pmc_$TAG > $OUT/pmc_final.json || exit 1
 mkdir -p $R/profiles && cp $OUT/pmc_final.json $R/profiles/${TAG}_pmc_final.json     # on the box: lets the bench below quote it
-python bench.py > $OUT/bench_final.json 2> $OUT/bench_final.err || exit 1
+python bench.py --full > $OUT/bench_final.json 2> $OUT/bench_final.err || exit 1
 echo "bench done"
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu --no-abi > $OUT/prof_bench.log 2>&1) || exit 1
+(cd "$TMPDIR" && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -- python3 $R/bench.py --full --steps 5 --warmup 1 --no-cpu --no-abi > $OUT/prof_bench.log 2>&1) || exit 1
 echo "bench trace done"
 # the long workload's kernel (BASELINE configs[4] per GPU: 32768 pairs of 10 kbp x 10 kbp, band 512, int32 cells): PMC first, so that its bench line can quote it
 bash tools/pmc_long.sh c5 --R 10000 --F 10000 --n 32768 --band 512 --width 32 > $OUT/pmc_long_c5.log 2>&1
@@ -23,8 +23,8 @@ python tools/pmc_summary.py $R/gpurun_out/pmc_c5 32768 > $OUT/pmc_long_c5.json |
 cp $OUT/pmc_long_c5.json $R/profiles/${TAG}_pmc_long_c5.json
 bash tools/pmc_long.sh c5aff --R 10000 --F 10000 --n 32768 --band 512 --width 32 --affine 1 > $OUT/pmc_long_c5_affine.log 2>&1
 python tools/pmc_summary.py $R/gpurun_out/pmc_c5aff 32768 > $OUT/pmc_long_c5_affine.json || exit 1
-python bench.py --workload long --steps 5 --warmup 1 > $OUT/bench_long.json 2> $OUT/bench_long.err || exit 1
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_long -- python3 $R/bench.py --workload long --steps 3 --warmup 1 --no-cpu > $OUT/prof_long.log 2>&1) || exit 1
+python bench.py --full --workload long --steps 5 --warmup 1 > $OUT/bench_long.json 2> $OUT/bench_long.err || exit 1
+(cd "$TMPDIR" && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_long -- python3 $R/bench.py --full --workload long --steps 3 --warmup 1 --no-cpu > $OUT/prof_long.log 2>&1) || exit 1
 echo "long bench done"
 (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_align -- python3 $R/tools/align_bench.py --iters 2 > $OUT/prof_align.log 2>&1) || exit 1
 python tools/align_bench.py --iters 3 2>&1 | grep -v amdgpu.ids > $OUT/align_bench.txt || exit 1
