@@ -31,6 +31,7 @@
 #include <thread>
 #include <vector>
 
+#include "hip_handles.h"
 #include "host_pipeline.h"
 #include "kernel_instances.hip.h"
 #include "band_kernels.hip.h"
@@ -46,11 +47,6 @@ struct Scoring {
     bool affine = false;
     int open_read = -3, ext_read = -3, open_ref = -3, ext_ref = -3;
 };
-
-inline void hip_check(hipError_t e, const char *what) {
-    if (e != hipSuccess)
-        throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
 
 // The per-geometry kernels are compiled in kernel_part.hip (one object per part, in parallel)
 #define VALIGN_DECLARE_FULL(G, K) VALIGN_FAST_KERNELS(extern template, G, K) VALIGN_FALLBACK_KERNELS(extern template, G, K)
@@ -280,7 +276,7 @@ public:
     int read_length() const { return R_; }
     int ref_length() const { return F_; }
     const LaunchPlan &plan() const { return plan_; }
-    hipStream_t own_stream() const { return streams_[0]; }
+    hipStream_t own_stream() const { return streams_[0].get(); }
 
     // Device-resident batch, asynchronous on `stream`.
     // `length_sorted` false: the caller has decided about length-sorted batching itself (the chunk pipeline of score_host)
@@ -389,7 +385,7 @@ public:
         int *min_start;             // device word: the traceback leaves the chunk's smallest readStart there (or nullptr)
         uint8_t *packed;            // ... and the rows, packed to their columns from there on, go here (compact_rows_kernel)
     };
-    hipEvent_t trace_done(int region) const { return trace_done_[region]; }
+    hipEvent_t trace_done(int region) const { return trace_done_[region].get(); }
     struct FillChoice {
         int kernel = 0;                 // FillKernel
         bool affine_tagged = false, tagged = false;
@@ -448,6 +444,19 @@ public:
 private:
     void validate_scoring();
 
+    // the eight scoring fields every kernel argument struct carries under these names
+    template <class A>
+    void put_scoring(A &a) const {
+        a.match = (short)sc_.match;
+        a.mismatch = (short)sc_.mismatch;
+        a.gap_read = (short)sc_.gap_read;
+        a.gap_ref = (short)sc_.gap_ref;
+        a.open_read = (short)sc_.open_read;
+        a.ext_read = (short)sc_.ext_read;
+        a.open_ref = (short)sc_.open_ref;
+        a.ext_ref = (short)sc_.ext_ref;
+    }
+
     // latency: pick for the shortest single sweep (few pairs: every wave has a SIMD to itself and the call takes
     // as long as one wave does) instead of for the most cell updates per second
     LaunchPlan choose_plan(int R, int F, int force_g, int force_k, bool latency = false, bool full_only = false) const;
@@ -495,8 +504,6 @@ private:
     // host-pointer call starts from idle streams and empty slots.
     void reset_pipeline();
 
-    void release_trace_scratch();
-
     // The pointer stream's bytes per pair-of-pairs depend on the fill kernel the call selects (tagged /
     // untagged, 4- or 8-step blocks, one or two code words): capacity is tracked in BYTES, so a call with a
     // wider stream than the one that sized the scratch reallocates instead of writing past it.
@@ -509,8 +516,6 @@ private:
     void scatter(Sink sink, long long cnt, const uint8_t *rows, const short *idx, int threads, size_t first_col = 0) {
         packer_.scatter(sink, cnt, rows, idx, threads, first_col);
     }
-
-    void release_staging();
 
     void ensure_staging(long long pairs);
 
@@ -548,16 +553,16 @@ private:
     // batches (score_device, on the caller's stream).
     struct RaggedCtx {
         long long cap = 0;                     // pairs the buffers hold
-        uint8_t *reads = nullptr, *refs = nullptr;     // the packed groups
-        int16_t *scores = nullptr;             // ... and their scores, packed order
-        uint16_t *bin = nullptr;               // length bin of every pair
-        int *pos = nullptr;                    // packed place of every pair
-        RaggedPlace *place = nullptr;          // ... as byte offsets + strides, for the copy kernel
-        unsigned *counters = nullptr;          // bins' pair counts, then the groups' fill cursors
-        uint8_t *tables = nullptr;             // device: group_of_bin[bins] then RaggedGroupDev[groups]
-        unsigned *h_counts = nullptr;          // pinned: the histogram's way to the host
-        uint8_t *h_tables = nullptr;           // pinned: the tables' way to the device
-        hipEvent_t counted = nullptr;
+        EventHandle counted;                   // (declared before the buffers: they are freed first)
+        DeviceBuffer<uint8_t> reads, refs;     // the packed groups
+        DeviceBuffer<int16_t> scores;          // ... and their scores, packed order
+        DeviceBuffer<uint16_t> bin;            // length bin of every pair
+        DeviceBuffer<int> pos;                 // packed place of every pair
+        DeviceBuffer<RaggedPlace> place;       // ... as byte offsets + strides, for the copy kernel
+        DeviceBuffer<unsigned> counters;       // bins' pair counts, then the groups' fill cursors
+        DeviceBuffer<uint8_t> tables;          // device: group_of_bin[bins] then RaggedGroupDev[groups]
+        PinnedBuffer<unsigned> h_counts;       // pinned: the histogram's way to the host
+        PinnedBuffer<uint8_t> h_tables;        // pinned: the tables' way to the device
         const uint8_t *src_reads = nullptr, *src_refs = nullptr;      // of the chunk between begin and finish
     };
     static constexpr size_t kRaggedTableBytes = sizeof(uint16_t) * kRaggedMaxBins + sizeof(RaggedGroupDev) * kRaggedMaxGroups;
@@ -569,7 +574,6 @@ private:
     }
 
     void ensure_ragged(int c, long long n);
-    void release_ragged();
 
     // first half: trimmed lengths -> bins, the histogram on its way to the host.  Asynchronous on `stream`.
     void ragged_begin(int c, long long n, const uint8_t *d_reads, const uint8_t *d_refs, hipStream_t stream);
@@ -603,11 +607,7 @@ private:
     std::vector<unsigned char> read_class_;
     std::vector<unsigned short> ref_class_;
     std::map<std::pair<int, int>, LaunchPlan> class_plans_;
-    RaggedCtx rag_[kSlots + 1];                                  // one per pipeline slot, the last for device-resident batches
-    hipStream_t ragged_dev_stream_ = nullptr;                    // stream and end of the last device-resident length-sorted call
-    hipEvent_t ragged_dev_done_ = nullptr;
-    uint8_t *d_read_class_ = nullptr;
-    uint16_t *d_ref_class_ = nullptr;
+    hipStream_t ragged_dev_stream_ = nullptr;                    // stream (the caller's) of the last device-resident length-sorted call
     HostPacker packer_{R_, F_};                               // (declared after R_ / F_)
     HostStats host_stats_;
     DebugSwitches dbg_;                                       // VALIGN_HIP_DEBUG (tests and experiments only)
@@ -624,46 +624,52 @@ private:
     bool no_overlap_ = dbg_.on("no_overlap");   // tracebacks in stream order behind their fills
     int strip_k_ = (int)dbg_.value("strip_k", 0);                  // rows per lane of the strip alignment kernels (16 / 12 / 8): tests
     long long scratch_cap_mb_ = dbg_.value("scratch_cap_mb", 0);   // small pointer scratch: chunked alignment batches in tests (key: pointer_scratch_cap_mb)
-    hipStream_t trace_stream_ = nullptr;                          // helper stream of align_device (walks beside the next fill)
     bool chain_regions_busy_[2] = {false, false};                 // WalkChain: the region's last walk may still be running
-    hipEvent_t fill_done_[2] = {nullptr, nullptr}, trace_done_[2] = {nullptr, nullptr}, entry_ev_ = nullptr;
     std::string arch_;
     LaunchPlan plan_, latency_plan_;
     LaunchPlan align_resident_;         // what choose_plan picked before the score path's preferences for the long-read kernels
     LaunchPlan fallback_plan_;          // alignments that need a kernel only the full geometries carry (align_plan_for)
-    hipStream_t streams_[kSlots] = {};
-    hipEvent_t slot_done_[kSlots] = {};
     long long slot_begin_[kSlots] = {}, slot_pending_[kSlots] = {};
-    long long staged_pairs_ = 0;
-    uint8_t *h_reads_[kSlots] = {}, *h_refs_[kSlots] = {};
-    short *h_scores_[kSlots] = {};
-    uint8_t *d_reads_[kSlots] = {}, *d_refs_[kSlots] = {};
-    uint8_t *d_pack_reads_[kSlots] = {}, *d_pack_refs_[kSlots] = {};     // 4-bit classes as they arrive (score path)
+    long long staged_pairs_ = 0, align_staged_pairs_ = 0;
     bool pack_ = true;                                                   // host_packing: 4-bit base classes across PCIe
-    int16_t *d_scores_[kSlots] = {};
-    // compute_alignments: pointer scratch + end cells (device), result staging (both sides)
     BandPlan band_plan_;               // banded linear SW: the block chain's plan for band_plan_width_, its tables on the device
     int band_plan_width_ = -1;
     int band_blocks_per_cu_ = 0, band_lds_ = 0;          // of the last block-chain launch (describe)
     int long_strip_rows_ = 0;                            // rows per strip of the last score_long_kernel launch (describe)
-    BandBlock *d_band_blocks_ = nullptr;
-    int *d_band_fill_ = nullptr;
     int cu_count_ = 0;
     bool no_band_chain_ = dbg_.on("no_band_chain");      // banded scores on score_long_kernel's strips
-    unsigned *d_brow_ = nullptr;       // long-read path: strip boundary rows
-    size_t brow_bytes_ = 0;
-    unsigned *d_ptr_ = nullptr;
-    EndCell *d_ends_ = nullptr;
-    long long trace_pairs_ = 0, align_staged_pairs_ = 0;
-    size_t trace_bytes_ = 0;            // capacity of d_ptr_
-    int *d_first_bad_ = nullptr;        // row strips: first invalid read / ref position per pair
-    size_t first_bad_bytes_ = 0;
-    uint8_t *h_rows_[kSlots] = {}, *d_rows_[kSlots] = {};
-    short *h_idx_[kSlots] = {}, *d_idx_[kSlots] = {};
-    uint8_t *d_packed_rows_[kSlots] = {};                        // the chunk's rows without their all-zero leading columns
-    int *d_min_start_ = nullptr, *h_min_start_ = nullptr;       // per slot: first column of the chunk's rows that holds a string (device / pinned)
-    int start_col_[kSlots] = {};                                 // ... as the copy issuer used it (columns before it were not copied)
-    hipEvent_t in_done_[kSlots] = {}, kernels_done_[kSlots] = {};   // align_host: H2D / kernels of the slot's chunk finished
+    int start_col_[kSlots] = {};                         // per slot: first column of the chunk's rows the copy issuer copied
+
+    // ---- owned HIP objects.  Members are destroyed in reverse order: the streams and events come first here, so that
+    // every buffer is freed before the streams and events it was used on. ----
+    StreamHandle streams_[kSlots];
+    EventHandle slot_done_[kSlots];
+    EventHandle in_done_[kSlots], kernels_done_[kSlots];         // align_host: H2D / kernels of the slot's chunk finished
+    StreamHandle trace_stream_;                                  // helper stream of align_device (walks beside the next fill)
+    EventHandle fill_done_[2], trace_done_[2], entry_ev_;
+    EventHandle ragged_dev_done_;                                // end of the last device-resident length-sorted call
+    PinnedBuffer<uint8_t> h_reads_[kSlots], h_refs_[kSlots];     // score / alignment staging, kSlots slots
+    PinnedBuffer<short> h_scores_[kSlots];
+    DeviceBuffer<uint8_t> d_reads_[kSlots], d_refs_[kSlots];
+    DeviceBuffer<int16_t> d_scores_[kSlots];
+    DeviceBuffer<uint8_t> d_pack_reads_[kSlots], d_pack_refs_[kSlots];     // 4-bit classes as they arrive (score path)
+    // compute_alignments: pointer scratch + end cells (device), result staging (both sides)
+    DeviceBuffer<unsigned> d_ptr_;
+    DeviceBuffer<EndCell> d_ends_;
+    DeviceBuffer<int> d_first_bad_;                              // row strips: first invalid read / ref position per pair
+    PinnedBuffer<uint8_t> h_rows_[kSlots];
+    PinnedBuffer<short> h_idx_[kSlots];
+    DeviceBuffer<uint8_t> d_rows_[kSlots];
+    DeviceBuffer<short> d_idx_[kSlots];
+    DeviceBuffer<uint8_t> d_packed_rows_[kSlots];                // the chunk's rows without their all-zero leading columns
+    DeviceBuffer<int> d_min_start_;                              // per slot: first column of the chunk's rows that holds a string
+    PinnedBuffer<int> h_min_start_;                              // ... on its way to the host
+    DeviceBuffer<unsigned> d_brow_;                              // long-read path: strip boundary rows
+    DeviceBuffer<BandBlock> d_band_blocks_;                      // the block chain's tables (band_plan_)
+    DeviceBuffer<int> d_band_fill_;
+    RaggedCtx rag_[kSlots + 1];                                  // one per pipeline slot, the last for device-resident batches
+    DeviceBuffer<uint8_t> d_read_class_;                         // length -> class tables of the length-sorted batches
+    DeviceBuffer<uint16_t> d_ref_class_;
 };
 
 }  // namespace valign

@@ -155,8 +155,7 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
     // 150 x 500 (43.6 GB) on a 288 GB device -- and half the free HBM.
     size_t free_b = 0, total_b = 0;
     hip_check(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
-    const size_t have = trace_bytes_;
-    size_t cap = std::min<size_t>(64ull << 30, std::max<size_t>((free_b + have) / 2, 256ull << 20));
+    size_t cap = std::min<size_t>(64ull << 30, std::max<size_t>((free_b + d_ptr_.bytes()) / 2, 256ull << 20));
     if (scratch_cap_mb_ > 0) cap = std::min<size_t>(cap, (size_t)scratch_cap_mb_ << 20);
     long long chunk = (long long)(cap / bytes_per_pp) * 2;
     chunk = std::max(ppb, chunk / ppb * ppb);
@@ -200,19 +199,19 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
         // the result rows are zeroed on the helper stream too (1.4 GB per million pairs of 150 x 500: the fills do not
         // touch them), behind whatever the caller's stream was still doing with them
         ensure_trace_stream();
-        hip_check(hipEventRecord(entry_ev_, stream), "hipEventRecord");
-        hip_check(hipStreamWaitEvent(trace_stream_, entry_ev_, 0), "hipStreamWaitEvent");
-        hip_check(hipMemsetAsync(d_rows, 0, (size_t)n * 2 * AL, trace_stream_), "hipMemsetAsync(rows)");
+        hip_check(hipEventRecord(entry_ev_.get(), stream), "hipEventRecord");
+        hip_check(hipStreamWaitEvent(trace_stream_.get(), entry_ev_.get(), 0), "hipStreamWaitEvent");
+        hip_check(hipMemsetAsync(d_rows, 0, (size_t)n * 2 * AL, trace_stream_.get()), "hipMemsetAsync(rows)");
     } else if (!chain) {
         hip_check(hipMemsetAsync(d_rows, 0, (size_t)n * 2 * AL, stream), "hipMemsetAsync(rows)");
     }
     bool region_used[2] = {chain && chain_regions_busy_[0], chain && chain_regions_busy_[1]};
     for (const Part &part : parts) {
         const long long begin = part.begin, cnt = part.cnt;
-        unsigned *part_ptr = reinterpret_cast<unsigned *>(reinterpret_cast<unsigned char *>(d_ptr_) + (size_t)(part.slot / 2) * bytes_per_pp);
-        EndCell *part_ends = d_ends_ + part.slot;
+        unsigned *part_ptr = reinterpret_cast<unsigned *>(reinterpret_cast<unsigned char *>(d_ptr_.get()) + (size_t)(part.slot / 2) * bytes_per_pp);
+        EndCell *part_ends = d_ends_.get() + part.slot;
         if (helper && region_used[part.region])          // the region's previous walk must be over before it is overwritten
-            hip_check(hipStreamWaitEvent(stream, trace_done_[part.region], 0), "hipStreamWaitEvent");
+            hip_check(hipStreamWaitEvent(stream, trace_done_[part.region].get(), 0), "hipStreamWaitEvent");
         FillArgs f;
         f.reads = d_reads + (size_t)begin * R_;
         f.refs = d_refs + (size_t)begin * F_;
@@ -225,14 +224,7 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
         f.refc_stride = plan.lds.refc_stride;
         f.wave_lds = plan.lds.total;
         f.blocks8 = blocks8;
-        f.match = (short)sc_.match;
-        f.mismatch = (short)sc_.mismatch;
-        f.gap_read = (short)sc_.gap_read;
-        f.gap_ref = (short)sc_.gap_ref;
-        f.open_read = (short)sc_.open_read;
-        f.ext_read = (short)sc_.ext_read;
-        f.open_ref = (short)sc_.open_ref;
-        f.ext_ref = (short)sc_.ext_ref;
+        put_scoring(f);
         void *fargs[] = {&f};
         const long long blocks = (cnt + ppb - 1) / ppb;
         hip_check(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(plan.waves_per_block * kWave), fargs,
@@ -253,26 +245,19 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
         t.pad_rows = G * K - R_;
         t.blocks8 = blocks8;
         t.alg = alg;
-        t.match = f.match;
-        t.mismatch = f.mismatch;
-        t.gap_read = f.gap_read;
-        t.gap_ref = f.gap_ref;
+        put_scoring(t);
         t.affine = sc_.affine ? 1 : 0;
         t.sse_policy = sse_policy_ ? 1 : 0;
         t.tagged = affine_tagged ? 2 : ((tagged && !sse_policy_) ? 1 : 0);     // SSE tags are the stored states
-        t.open_read = f.open_read;
-        t.ext_read = f.ext_read;
-        t.open_ref = f.open_ref;
-        t.ext_ref = f.ext_ref;
         void *targs[] = {&t};
         hipStream_t walk_stream = stream;
         if (helper) {
-            hip_check(hipEventRecord(fill_done_[part.region], stream), "hipEventRecord");
-            hip_check(hipStreamWaitEvent(trace_stream_, fill_done_[part.region], 0), "hipStreamWaitEvent");
-            walk_stream = trace_stream_;
-            if (chain) hip_check(hipMemsetAsync(d_rows, 0, (size_t)n * 2 * AL, trace_stream_), "hipMemsetAsync(rows)");
+            hip_check(hipEventRecord(fill_done_[part.region].get(), stream), "hipEventRecord");
+            walk_stream = trace_stream_.get();
+            hip_check(hipStreamWaitEvent(walk_stream, fill_done_[part.region].get(), 0), "hipStreamWaitEvent");
+            if (chain) hip_check(hipMemsetAsync(d_rows, 0, (size_t)n * 2 * AL, walk_stream), "hipMemsetAsync(rows)");
             if (chain && chain->min_start) {
-                hip_check(hipMemsetD32Async((hipDeviceptr_t)chain->min_start, AL, 1, trace_stream_), "hipMemsetD32Async(first column)");
+                hip_check(hipMemsetD32Async((hipDeviceptr_t)chain->min_start, AL, 1, walk_stream), "hipMemsetD32Async(first column)");
                 t.min_start = chain->min_start;
             }
         }
@@ -286,7 +271,7 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
                       "hipLaunchKernel(compact_rows_kernel)");
         }
         if (helper) {
-            hip_check(hipEventRecord(trace_done_[part.region], trace_stream_), "hipEventRecord");
+            hip_check(hipEventRecord(trace_done_[part.region].get(), walk_stream), "hipEventRecord");
             region_used[part.region] = true;
         }
     }
@@ -296,17 +281,17 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
     }
     if (helper)                                        // the call stays asynchronous on `stream`: it ends when the walks have
         for (int r = 0; r < 2; ++r)
-            if (region_used[r]) hip_check(hipStreamWaitEvent(stream, trace_done_[r], 0), "hipStreamWaitEvent");
+            if (region_used[r]) hip_check(hipStreamWaitEvent(stream, trace_done_[r].get(), 0), "hipStreamWaitEvent");
     return false;
 }
 
 void Engine::ensure_trace_stream() {
-    if (trace_stream_) return;
-    hip_check(hipStreamCreateWithFlags(&trace_stream_, hipStreamNonBlocking), "hipStreamCreate(traceback)");
-    hip_check(hipEventCreateWithFlags(&entry_ev_, hipEventDisableTiming), "hipEventCreate");
+    if (trace_done_[1]) return;             // (the last one created: a failure part-way starts over)
+    trace_stream_ = make_stream("traceback");
+    entry_ev_ = make_event(hipEventDisableTiming);
     for (int r = 0; r < 2; ++r) {
-        hip_check(hipEventCreateWithFlags(&fill_done_[r], hipEventDisableTiming), "hipEventCreate");
-        hip_check(hipEventCreateWithFlags(&trace_done_[r], hipEventDisableTiming), "hipEventCreate");
+        fill_done_[r] = make_event(hipEventDisableTiming);
+        trace_done_[r] = make_event(hipEventDisableTiming);
     }
 }
 
@@ -350,10 +335,7 @@ bool Engine::align_fused(int alg, long long n, const uint8_t *d_reads, const uin
     f.refc_stride = best_lds.refc_stride;
     f.wave_lds = best_lds.total;
     f.blocks8 = best_blocks;
-    f.match = (short)sc_.match;
-    f.mismatch = (short)sc_.mismatch;
-    f.gap_read = (short)sc_.gap_read;
-    f.gap_ref = (short)sc_.gap_ref;
+    put_scoring(f);
     f.out_rows = d_rows;
     f.out_idx = d_idx;
     const void *fn = best->kernel[alg];
@@ -405,39 +387,19 @@ void Engine::align_strips_device(int alg, long long n, const uint8_t *d_reads, c
     hip_check(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
     // (the pointer stream of a 10 kbp x 10 kbp pair-of-pairs is 50 MB: what fits the scratch is what runs side by side --
     // 24 GB, the bound until round 4, kept 480 waves on 1 024 SIMDs; half of the free HBM, at most 128 GB, now)
-    size_t cap = std::min<size_t>(128ull << 30, std::max<size_t>((free_b + trace_bytes_) / 2, 256ull << 20));
+    size_t cap = std::min<size_t>(128ull << 30, std::max<size_t>((free_b + d_ptr_.bytes()) / 2, 256ull << 20));
     if (scratch_cap_mb_ > 0) cap = std::min<size_t>(cap, (size_t)scratch_cap_mb_ << 20);
     long long chunk = std::max<long long>(2, (long long)(cap / bytes_per_pp) * 2);
     chunk = std::min(chunk, (n + 1) / 2 * 2);
     const long long waves = chunk / 2;
-    const size_t need = (size_t)waves * bytes_per_pp;
-    if (need > trace_bytes_ || chunk > trace_pairs_ || (size_t)2 * n * sizeof(int) > first_bad_bytes_) {
+    ensure_trace_scratch(chunk, bytes_per_pp, 2, stream);      // (chunk is even: waves * bytes_per_pp bytes, chunk end cells)
+    if ((size_t)2 * n * sizeof(int) > d_first_bad_.bytes()) {
         hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
-        if (need > trace_bytes_) {
-            if (d_ptr_) (void)hipFree(d_ptr_);
-            d_ptr_ = nullptr;
-            trace_bytes_ = 0;
-            hip_check(hipMalloc((void **)&d_ptr_, need), "hipMalloc(pointer scratch)");
-            trace_bytes_ = need;
-        }
-        if (chunk > trace_pairs_) {
-            if (d_ends_) (void)hipFree(d_ends_);
-            d_ends_ = nullptr;
-            trace_pairs_ = 0;
-            hip_check(hipMalloc((void **)&d_ends_, sizeof(EndCell) * (size_t)chunk), "hipMalloc(end cells)");
-            trace_pairs_ = chunk;
-        }
-        if ((size_t)2 * n * sizeof(int) > first_bad_bytes_) {
-            if (d_first_bad_) (void)hipFree(d_first_bad_);
-            d_first_bad_ = nullptr;
-            first_bad_bytes_ = 0;
-            hip_check(hipMalloc((void **)&d_first_bad_, (size_t)2 * n * sizeof(int)), "hipMalloc(first invalid positions)");
-            first_bad_bytes_ = (size_t)2 * n * sizeof(int);
-        }
+        d_first_bad_.reserve((size_t)2 * n * sizeof(int), "first invalid positions");
     }
-    unsigned *boundary = d_ptr_ + (size_t)waves * strip_words * strips;        // two rows per pair-of-pairs behind the pointers
+    unsigned *boundary = d_ptr_.get() + (size_t)waves * strip_words * strips;        // two rows per pair-of-pairs behind the pointers
     hip_check(hipMemsetAsync(d_rows, 0, (size_t)n * 2 * AL, stream), "hipMemsetAsync(rows)");
-    hipLaunchKernelGGL(first_invalid_kernel, dim3((unsigned)n), dim3(kWave), 0, stream, d_reads, d_refs, n, R_, F_, d_first_bad_,
+    hipLaunchKernelGGL(first_invalid_kernel, dim3((unsigned)n), dim3(kWave), 0, stream, d_reads, d_refs, n, R_, F_, d_first_bad_.get(),
                        sse_policy_ ? 1 : 0);
     hip_check(hipGetLastError(), "hipLaunchKernel(first_invalid_kernel)");
     const void *fn = wide ? geo->wide_kernel[alg][wide_mode] : (affine ? geo->affine_kernel[alg] : (sse_policy_ ? geo->sse_kernel[alg] : geo->kernel[alg]));
@@ -450,9 +412,9 @@ void Engine::align_strips_device(int alg, long long n, const uint8_t *d_reads, c
             StripArgs a;
             a.reads = d_reads + (size_t)begin * R_;
             a.refs = d_refs + (size_t)begin * F_;
-            a.ptr = d_ptr_ + (size_t)s * cnt_waves * strip_words;
-            a.ends = d_ends_;
-            a.first_bad = d_first_bad_ + 2 * begin;
+            a.ptr = d_ptr_.get() + (size_t)s * cnt_waves * strip_words;
+            a.ends = d_ends_.get();
+            a.first_bad = d_first_bad_.get() + 2 * begin;
             a.top = boundary + (size_t)((s & 1) ^ 1) * row_sets * waves * row_dwords;
             a.bottom = boundary + (size_t)(s & 1) * row_sets * waves * row_dwords;
             a.top_f = a.top + (size_t)waves * row_dwords;                // (only read / written by the affine kernel)
@@ -467,14 +429,7 @@ void Engine::align_strips_device(int alg, long long n, const uint8_t *d_reads, c
             a.strip = s;
             a.strips = strips;
             a.row_dwords = row_dwords;
-            a.match = (short)sc_.match;
-            a.mismatch = (short)sc_.mismatch;
-            a.gap_read = (short)sc_.gap_read;
-            a.gap_ref = (short)sc_.gap_ref;
-            a.open_read = (short)sc_.open_read;
-            a.ext_read = (short)sc_.ext_read;
-            a.open_ref = (short)sc_.open_ref;
-            a.ext_ref = (short)sc_.ext_ref;
+            put_scoring(a);
             void *kargs[] = {&a};
             hip_check(hipLaunchKernel(fn, dim3((unsigned)cnt_waves), dim3(kWave), kargs, (size_t)lds.total, stream),
                       "hipLaunchKernel(align_strip_kernel)");
@@ -482,8 +437,8 @@ void Engine::align_strips_device(int alg, long long n, const uint8_t *d_reads, c
         TraceArgs t{};
         t.reads = d_reads + (size_t)begin * R_;
         t.refs = d_refs + (size_t)begin * F_;
-        t.ptr = d_ptr_;
-        t.ends = d_ends_;
+        t.ptr = d_ptr_.get();
+        t.ends = d_ends_.get();
         t.rows = d_rows + (size_t)begin * 2 * AL;
         t.idx = d_idx + (size_t)begin * 4;
         t.n = cnt;
@@ -494,16 +449,9 @@ void Engine::align_strips_device(int alg, long long n, const uint8_t *d_reads, c
         t.pad_rows = pad_total;
         t.blocks8 = blocks8;
         t.alg = alg;
-        t.match = (short)sc_.match;
-        t.mismatch = (short)sc_.mismatch;
-        t.gap_read = (short)sc_.gap_read;
-        t.gap_ref = (short)sc_.gap_ref;
+        put_scoring(t);
         t.affine = affine ? 1 : 0;
         t.sse_policy = sse_policy_ ? 1 : 0;
-        t.open_read = (short)sc_.open_read;
-        t.ext_read = (short)sc_.ext_read;
-        t.open_ref = (short)sc_.open_ref;
-        t.ext_ref = (short)sc_.ext_ref;
         t.strip_rows = rows;
         t.strip_words = (long long)(cnt_waves * strip_words);
         t.wide_score = wide ? 1 : 0;
@@ -534,23 +482,23 @@ void Engine::align_host(int opt, int n, const char *const *reads, const char *co
     ensure_align_staging(chunk);
     if (threads < 1) threads = 1;
     threads = std::min(threads, 64);
-    hipStream_t kernels = streams_[0], copy_in = streams_[1], copy_out = streams_[2];
+    hipStream_t kernels = streams_[0].get(), copy_in = streams_[1].get(), copy_out = streams_[2].get();
     host_stats_ = HostStats{};
     if (direct_call(n, (size_t)AL)) {
         // Small call: one stream, no events.  The kernels read the sequences out of the pinned staging; rows
         // and coordinates land next to each other in one device buffer and come back in ONE copy (scattered
         // 4-byte stores over PCIe would cost a bus transaction each).
         auto t0 = std::chrono::steady_clock::now();
-        gather(reads, refs, n, h_reads_[0], h_refs_[0], threads);
+        uint8_t *h_reads = h_reads_[0].get(), *h_refs = h_refs_[0].get(), *h_rows = h_rows_[0].get(), *d_rows = d_rows_[0].get();
+        gather(reads, refs, n, h_reads, h_refs, threads);
         auto t1 = std::chrono::steady_clock::now();
         const size_t rows_bytes = ((size_t)n * 2 * AL + 15) / 16 * 16, all_bytes = rows_bytes + sizeof(short) * 4 * (size_t)n;
-        if (align_fused(alg, n, dev_view(h_reads_[0]), dev_view(h_refs_[0]), dev_view(h_rows_[0]),
-                        (short *)(dev_view(h_rows_[0]) + rows_bytes), kernels)) {
+        if (align_fused(alg, n, dev_view(h_reads), dev_view(h_refs), dev_view(h_rows), (short *)(dev_view(h_rows) + rows_bytes), kernels)) {
             // ONE launch: the wave that fills a pair's pointers (kept in LDS) walks it back and writes the rows
             // straight into the pinned staging
             hip_check(hipStreamSynchronize(kernels), "hipStreamSynchronize");
             auto t2 = std::chrono::steady_clock::now();
-            scatter(alignments, n, h_rows_[0], (const short *)(h_rows_[0] + rows_bytes), threads);
+            scatter(alignments, n, h_rows, (const short *)(h_rows + rows_bytes), threads);
             host_stats_.gather_ms = ms_between(t0, t1);
             host_stats_.wait_ms = ms_between(t1, t2);
             host_stats_.drain_ms = ms_between(t2, std::chrono::steady_clock::now());
@@ -559,12 +507,12 @@ void Engine::align_host(int opt, int n, const char *const *reads, const char *co
         }
         // rows and coordinates sit next to each other in the slot's row buffer (it has room for both) and come
         // back in ONE copy
-        short *d_idx = (short *)(d_rows_[0] + rows_bytes);
-        align_device(opt, n, dev_view(h_reads_[0]), dev_view(h_refs_[0]), d_rows_[0], d_idx, kernels);
-        hip_check(hipMemcpyAsync(h_rows_[0], d_rows_[0], all_bytes, hipMemcpyDeviceToHost, kernels), "D2H rows + idx");
+        short *d_idx = (short *)(d_rows + rows_bytes);
+        align_device(opt, n, dev_view(h_reads), dev_view(h_refs), d_rows, d_idx, kernels);
+        hip_check(hipMemcpyAsync(h_rows, d_rows, all_bytes, hipMemcpyDeviceToHost, kernels), "D2H rows + idx");
         hip_check(hipStreamSynchronize(kernels), "hipStreamSynchronize");
         auto t2 = std::chrono::steady_clock::now();
-        scatter(alignments, n, h_rows_[0], (const short *)(h_rows_[0] + rows_bytes), threads);
+        scatter(alignments, n, h_rows, (const short *)(h_rows + rows_bytes), threads);
         host_stats_.gather_ms = ms_between(t0, t1);
         host_stats_.wait_ms = ms_between(t1, t2);
         host_stats_.drain_ms = ms_between(t2, std::chrono::steady_clock::now());
@@ -584,7 +532,7 @@ void Engine::align_host(int opt, int n, const char *const *reads, const char *co
     auto drain = [&](int s) {
         if (slot_pending_[s] <= 0) return;
         const auto t0 = std::chrono::steady_clock::now();
-        if (!direct_rows) scatter(alignments + slot_begin_[s], slot_pending_[s], h_rows_[s], h_idx_[s], threads, (size_t)start_col_[s]);
+        if (!direct_rows) scatter(alignments + slot_begin_[s], slot_pending_[s], h_rows_[s].get(), h_idx_[s].get(), threads, (size_t)start_col_[s]);
         host_stats_.drain_ms += ms_between(t0, std::chrono::steady_clock::now());
         host_stats_.d2h_row_bytes += (double)slot_pending_[s] * 2 * (AL - start_col_[s]);
         host_stats_.full_row_bytes += (double)slot_pending_[s] * 2 * AL;
@@ -609,8 +557,8 @@ void Engine::align_host(int opt, int n, const char *const *reads, const char *co
                 } catch (...) {
                 }
             }
-            if (e->trace_stream_) (void)hipStreamSynchronize(e->trace_stream_);
-            for (int s = 0; s < kSlots; ++s) (void)hipStreamSynchronize(e->streams_[s]);
+            if (e->trace_stream_) (void)hipStreamSynchronize(e->trace_stream_.get());
+            for (int s = 0; s < kSlots; ++s) (void)hipStreamSynchronize(e->streams_[s].get());
             for (int s = 0; s < kSlots; ++s) e->slot_pending_[s] = 0;
         }
     } quiesce{this};
@@ -618,32 +566,33 @@ void Engine::align_host(int opt, int n, const char *const *reads, const char *co
         const long long cnt = std::min<long long>(chunk, n - begin);
         auto t0 = std::chrono::steady_clock::now();
         copy_issuer->wait_issued(slot);             // (only then is the slot's event the one of its last chunk)
-        hip_check(hipEventSynchronize(slot_done_[slot]), "hipEventSynchronize");   // its last chunk is back on the host
+        hip_check(hipEventSynchronize(slot_done_[slot].get()), "hipEventSynchronize");   // its last chunk is back on the host
         host_stats_.wait_ms += ms_between(t0, std::chrono::steady_clock::now());
         drain(slot);
+        uint8_t *h_reads = h_reads_[slot].get(), *h_refs = h_refs_[slot].get(), *d_reads = d_reads_[slot].get(), *d_refs = d_refs_[slot].get();
         t0 = std::chrono::steady_clock::now();
-        gather(reads + begin, refs + begin, cnt, h_reads_[slot], h_refs_[slot], threads);
+        gather(reads + begin, refs + begin, cnt, h_reads, h_refs, threads);
         host_stats_.gather_ms += ms_between(t0, std::chrono::steady_clock::now());
-        hip_check(hipMemcpyAsync(d_reads_[slot], h_reads_[slot], (size_t)cnt * R_, hipMemcpyHostToDevice, copy_in), "H2D reads");
-        hip_check(hipMemcpyAsync(d_refs_[slot], h_refs_[slot], (size_t)cnt * F_, hipMemcpyHostToDevice, copy_in), "H2D refs");
-        hip_check(hipEventRecord(in_done_[slot], copy_in), "hipEventRecord");
-        hip_check(hipStreamWaitEvent(kernels, in_done_[slot], 0), "hipStreamWaitEvent");
+        hip_check(hipMemcpyAsync(d_reads, h_reads, (size_t)cnt * R_, hipMemcpyHostToDevice, copy_in), "H2D reads");
+        hip_check(hipMemcpyAsync(d_refs, h_refs, (size_t)cnt * F_, hipMemcpyHostToDevice, copy_in), "H2D refs");
+        hip_check(hipEventRecord(in_done_[slot].get(), copy_in), "hipEventRecord");
+        hip_check(hipStreamWaitEvent(kernels, in_done_[slot].get(), 0), "hipStreamWaitEvent");
         // the walk of this chunk runs on the helper stream beside the fill of the next one (two scratch regions)
         const bool packed = !direct_rows && !whole_rows_;
-        const WalkChain chain{(int)(chunk_no & 1), chunk, packed ? d_min_start_ + slot : nullptr, packed ? d_packed_rows_[slot] : nullptr};
-        const bool chained = align_device(opt, cnt, d_reads_[slot], d_refs_[slot], d_rows_[slot], d_idx_[slot], kernels, &chain);
-        hip_check(hipEventRecord(kernels_done_[slot], chained ? trace_stream_ : kernels), "hipEventRecord");      // the chunk's last kernel
+        const WalkChain chain{(int)(chunk_no & 1), chunk, packed ? d_min_start_.get() + slot : nullptr, packed ? d_packed_rows_[slot].get() : nullptr};
+        const bool chained = align_device(opt, cnt, d_reads, d_refs, d_rows_[slot].get(), d_idx_[slot].get(), kernels, &chain);
+        hip_check(hipEventRecord(kernels_done_[slot].get(), chained ? trace_stream_.get() : kernels), "hipEventRecord");      // the chunk's last kernel
         ++chunk_no;
-        uint8_t *rows_to = direct_rows ? direct_rows + (size_t)begin * 2 * AL : h_rows_[slot];
-        short *idx_to = direct_idx ? direct_idx + 4 * begin : h_idx_[slot];
+        uint8_t *rows_to = direct_rows ? direct_rows + (size_t)begin * 2 * AL : h_rows_[slot].get();
+        short *idx_to = direct_idx ? direct_idx + 4 * begin : h_idx_[slot].get();
         // SDMA, not a blit kernel beside the next fill: the copies are issued once the host has seen the kernels end
-        CopyIssuer::Job job{kernels_done_[slot], {rows_to, idx_to}, {d_rows_[slot], d_idx_[slot]},
-                            {(size_t)cnt * 2 * AL, sizeof(short) * 4 * (size_t)cnt}, copy_out, slot_done_[slot], slot};
+        CopyIssuer::Job job{kernels_done_[slot].get(), {rows_to, idx_to}, {d_rows_[slot].get(), d_idx_[slot].get()},
+                            {(size_t)cnt * 2 * AL, sizeof(short) * 4 * (size_t)cnt}, copy_out, slot_done_[slot].get(), slot};
         start_col_[slot] = 0;
         if (chained && packed) {        // (the stream-order fallback -- row strips, a scratch too small for two regions -- copies whole rows)
-            job.src[0] = d_packed_rows_[slot];
-            job.d_min = d_min_start_ + slot;
-            job.h_min = h_min_start_ + slot;
+            job.src[0] = d_packed_rows_[slot].get();
+            job.d_min = d_min_start_.get() + slot;
+            job.h_min = h_min_start_.get() + slot;
             job.row_bytes = AL;
             job.rows = 2 * cnt;
             job.col = &start_col_[slot];
@@ -656,7 +605,7 @@ void Engine::align_host(int opt, int n, const char *const *reads, const char *co
         const int s = (slot + k) % kSlots;
         const auto t0 = std::chrono::steady_clock::now();
         copy_issuer->wait_issued(s);
-        hip_check(hipEventSynchronize(slot_done_[s]), "hipEventSynchronize");
+        hip_check(hipEventSynchronize(slot_done_[s].get()), "hipEventSynchronize");
         host_stats_.wait_ms += ms_between(t0, std::chrono::steady_clock::now());
         drain(s);
     }
@@ -671,90 +620,46 @@ void Engine::prime_copy_engines(hipStream_t copy_in, hipStream_t copy_out, long 
     if (in_bytes < (16u << 20) || out_bytes == 0) return;         // (too short to still be running when the second copy is issued)
     hip_check(hipStreamSynchronize(copy_in), "hipStreamSynchronize");
     hip_check(hipStreamSynchronize(copy_out), "hipStreamSynchronize");
-    hip_check(hipMemcpyAsync(d_refs_[0], h_refs_[0], in_bytes, hipMemcpyHostToDevice, copy_in), "H2D (engine priming)");
+    hip_check(hipMemcpyAsync(d_refs_[0].get(), h_refs_[0].get(), in_bytes, hipMemcpyHostToDevice, copy_in), "H2D (engine priming)");
     // the input copy must have reached its engine before the result stream asks which engines are free: >= 16 MB
     // take >= 0.3 ms on the wire, a tenth of that is plenty for the submission
     for (const auto t0 = std::chrono::steady_clock::now(); ms_between(t0, std::chrono::steady_clock::now()) < 0.1;) {
     }
-    hip_check(hipMemcpyAsync(h_idx_[0], d_idx_[0], out_bytes, hipMemcpyDeviceToHost, copy_out), "D2H (engine priming)");
+    hip_check(hipMemcpyAsync(h_idx_[0].get(), d_idx_[0].get(), out_bytes, hipMemcpyDeviceToHost, copy_out), "D2H (engine priming)");
     hip_check(hipStreamSynchronize(copy_out), "hipStreamSynchronize");
     hip_check(hipStreamSynchronize(copy_in), "hipStreamSynchronize");
 }
 
-void Engine::release_trace_scratch() {
-    if (d_ptr_) (void)hipFree(d_ptr_);
-    if (d_ends_) (void)hipFree(d_ends_);
-    d_ptr_ = nullptr;
-    d_ends_ = nullptr;
-    trace_pairs_ = 0;
-    trace_bytes_ = 0;
-    if (d_first_bad_) (void)hipFree(d_first_bad_);
-    d_first_bad_ = nullptr;
-    first_bad_bytes_ = 0;
-    for (int s = 0; s < kSlots; ++s) {
-        if (h_rows_[s]) (void)hipHostFree(h_rows_[s]);
-        if (h_idx_[s]) (void)hipHostFree(h_idx_[s]);
-        if (d_rows_[s]) (void)hipFree(d_rows_[s]);
-        if (d_idx_[s]) (void)hipFree(d_idx_[s]);
-        if (d_packed_rows_[s]) (void)hipFree(d_packed_rows_[s]);
-        d_packed_rows_[s] = nullptr;
-        h_rows_[s] = nullptr;
-        h_idx_[s] = nullptr;
-        d_rows_[s] = nullptr;
-        d_idx_[s] = nullptr;
-    }
-    align_staged_pairs_ = 0;
-    if (d_min_start_) (void)hipFree(d_min_start_);
-    if (h_min_start_) (void)hipHostFree(h_min_start_);
-    d_min_start_ = nullptr;
-    h_min_start_ = nullptr;
-}
-
 void Engine::ensure_trace_scratch(long long pairs, size_t bytes_per_pp, long long ppw, hipStream_t stream) {
     const long long waves = (pairs + ppw - 1) / ppw;
-    const size_t need = (size_t)(waves * (ppw / 2)) * bytes_per_pp;
-    if (need <= trace_bytes_ && pairs <= trace_pairs_) return;
+    const size_t need = (size_t)(waves * (ppw / 2)) * bytes_per_pp, ends = sizeof(EndCell) * (size_t)(waves * ppw);
+    if (need <= d_ptr_.bytes() && ends <= d_ends_.bytes()) return;
     hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");   // nothing may still read the old scratch
-    if (trace_stream_) hip_check(hipStreamSynchronize(trace_stream_), "hipStreamSynchronize");
+    if (trace_stream_) hip_check(hipStreamSynchronize(trace_stream_.get()), "hipStreamSynchronize");
     chain_regions_busy_[0] = chain_regions_busy_[1] = false;
-    if (need > trace_bytes_) {
-        if (d_ptr_) (void)hipFree(d_ptr_);
-        d_ptr_ = nullptr;
-        trace_bytes_ = 0;
-        hip_check(hipMalloc((void **)&d_ptr_, need), "hipMalloc(pointer scratch)");
-        trace_bytes_ = need;
-    }
-    if (pairs > trace_pairs_) {
-        if (d_ends_) (void)hipFree(d_ends_);
-        d_ends_ = nullptr;
-        trace_pairs_ = 0;
-        hip_check(hipMalloc((void **)&d_ends_, sizeof(EndCell) * (size_t)(waves * ppw)), "hipMalloc(end cells)");
-        trace_pairs_ = pairs;
-    }
+    d_ptr_.reserve(need, "pointer scratch");
+    d_ends_.reserve(ends, "end cells");
 }
 
 void Engine::ensure_align_staging(long long pairs) {
     if (pairs <= align_staged_pairs_) return;
+    align_staged_pairs_ = 0;
     const size_t AL = (size_t)R_ + F_;
     for (int s = 0; s < kSlots; ++s) {
-        if (h_rows_[s]) (void)hipHostFree(h_rows_[s]);
-        if (h_idx_[s]) (void)hipHostFree(h_idx_[s]);
-        if (d_rows_[s]) (void)hipFree(d_rows_[s]);
-        if (d_idx_[s]) (void)hipFree(d_idx_[s]);
+        h_rows_[s].reset();
+        h_idx_[s].reset();
+        d_rows_[s].reset();
+        d_idx_[s].reset();
         // (room for the coordinates behind the rows: small calls bring both back in one piece)
         const size_t rows_cap = (size_t)pairs * 2 * AL + sizeof(short) * 4 * (size_t)pairs + 32;
-        hip_check(hipHostMalloc((void **)&h_rows_[s], rows_cap, hipHostMallocDefault), "hipHostMalloc");
-        hip_check(hipHostMalloc((void **)&h_idx_[s], sizeof(short) * 4 * (size_t)pairs, hipHostMallocDefault), "hipHostMalloc");
-        hip_check(hipMalloc((void **)&d_rows_[s], rows_cap), "hipMalloc");
-        hip_check(hipMalloc((void **)&d_idx_[s], sizeof(short) * 4 * (size_t)pairs), "hipMalloc");
-        if (d_packed_rows_[s]) (void)hipFree(d_packed_rows_[s]);
-        d_packed_rows_[s] = nullptr;
-        hip_check(hipMalloc((void **)&d_packed_rows_[s], (size_t)pairs * 2 * AL + 64), "hipMalloc(packed rows)");
+        h_rows_[s].reserve(rows_cap);
+        h_idx_[s].reserve(sizeof(short) * 4 * (size_t)pairs);
+        d_rows_[s].reserve(rows_cap);
+        d_idx_[s].reserve(sizeof(short) * 4 * (size_t)pairs);
+        d_packed_rows_[s].reserve((size_t)pairs * 2 * AL + 64, "packed rows");
     }
-    if (!d_min_start_) {
-        hip_check(hipMalloc((void **)&d_min_start_, sizeof(int) * kSlots), "hipMalloc(first columns)");
-        hip_check(hipHostMalloc((void **)&h_min_start_, sizeof(int) * kSlots, hipHostMallocDefault), "hipHostMalloc(first columns)");
-    }
+    d_min_start_.reserve(sizeof(int) * kSlots, "first columns");        // (fixed sizes: once)
+    h_min_start_.reserve(sizeof(int) * kSlots, "first columns");
     align_staged_pairs_ = pairs;
 }
 

@@ -45,38 +45,19 @@ Engine::Engine(int device, int R, int F, const Scoring &sc, int force_g, int for
     }
     latency_plan_ = (force_g || force_k || plan_.long_mode) ? plan_ : choose_plan(R_, F_, 0, 0, true);
     build_length_classes();
-    for (int s = 0; s < kSlots; ++s) hip_check(hipStreamCreateWithFlags(&streams_[s], hipStreamNonBlocking), "hipStreamCreate");
+    for (int s = 0; s < kSlots; ++s) streams_[s] = make_stream();
     for (int s = 0; s < kSlots; ++s) {
-        hip_check(hipEventCreateWithFlags(&slot_done_[s], hipEventDisableTiming), "hipEventCreate");
-        hip_check(hipEventCreateWithFlags(&in_done_[s], hipEventDisableTiming), "hipEventCreate");
-        hip_check(hipEventCreateWithFlags(&kernels_done_[s], hipEventDisableTiming | hipEventBlockingSync), "hipEventCreate");     // (the copy issuer sleeps on it)
+        slot_done_[s] = make_event(hipEventDisableTiming);
+        in_done_[s] = make_event(hipEventDisableTiming);
+        kernels_done_[s] = make_event(hipEventDisableTiming | hipEventBlockingSync);     // (the copy issuer sleeps on it)
     }
 }
 
+// The members free the buffers, then destroy the events and streams (engine.hip.h), with this device current.
 Engine::~Engine() {
     copy_issuer_.reset();               // (joins its thread; nothing is queued outside a call)
     (void)hipSetDevice(device_);
-    if (trace_stream_) (void)hipStreamSynchronize(trace_stream_);
-    release_staging();
-    release_trace_scratch();
-    if (d_brow_) (void)hipFree(d_brow_);
-    if (d_band_blocks_) (void)hipFree(d_band_blocks_);
-    if (d_band_fill_) (void)hipFree(d_band_fill_);
-    release_ragged();
-    for (int s = 0; s < kSlots; ++s) {
-        if (slot_done_[s]) (void)hipEventDestroy(slot_done_[s]);
-        if (in_done_[s]) (void)hipEventDestroy(in_done_[s]);
-        if (kernels_done_[s]) (void)hipEventDestroy(kernels_done_[s]);
-        if (streams_[s]) (void)hipStreamDestroy(streams_[s]);
-    }
-    if (trace_stream_) {
-        for (int r = 0; r < 2; ++r) {
-            (void)hipEventDestroy(fill_done_[r]);
-            (void)hipEventDestroy(trace_done_[r]);
-        }
-        (void)hipEventDestroy(entry_ev_);
-        (void)hipStreamDestroy(trace_stream_);
-    }
+    if (trace_stream_) (void)hipStreamSynchronize(trace_stream_.get());
 }
 
 bool Engine::affine_tagged_range_ok(int alg, int geo_rows, int K) const {
@@ -318,48 +299,39 @@ void Engine::reset_pipeline() {
         } catch (...) {
         }
     }
-    if (trace_stream_) (void)hipStreamSynchronize(trace_stream_);
+    if (trace_stream_) (void)hipStreamSynchronize(trace_stream_.get());
     for (int s = 0; s < kSlots; ++s) {
-        (void)hipStreamSynchronize(streams_[s]);
+        (void)hipStreamSynchronize(streams_[s].get());
         slot_pending_[s] = 0;
         slot_begin_[s] = 0;
     }
 }
 
-void Engine::release_staging() {
-    for (int s = 0; s < kSlots; ++s) {
-        if (h_reads_[s]) (void)hipHostFree(h_reads_[s]);
-        if (h_refs_[s]) (void)hipHostFree(h_refs_[s]);
-        if (h_scores_[s]) (void)hipHostFree(h_scores_[s]);
-        if (d_reads_[s]) (void)hipFree(d_reads_[s]);
-        if (d_refs_[s]) (void)hipFree(d_refs_[s]);
-        if (d_scores_[s]) (void)hipFree(d_scores_[s]);
-        if (d_pack_reads_[s]) (void)hipFree(d_pack_reads_[s]);
-        if (d_pack_refs_[s]) (void)hipFree(d_pack_refs_[s]);
-        d_pack_reads_[s] = d_pack_refs_[s] = nullptr;
-        h_reads_[s] = h_refs_[s] = nullptr;
-        h_scores_[s] = nullptr;
-        d_reads_[s] = d_refs_[s] = nullptr;
-        d_scores_[s] = nullptr;
-    }
-    staged_pairs_ = 0;
-}
-
 void Engine::ensure_staging(long long pairs) {
     if (pairs <= staged_pairs_) return;
-    release_staging();
+    staged_pairs_ = 0;
+    for (int s = 0; s < kSlots; ++s) {          // (every old block goes before the first new one is allocated)
+        h_reads_[s].reset();
+        h_refs_[s].reset();
+        h_scores_[s].reset();
+        d_reads_[s].reset();
+        d_refs_[s].reset();
+        d_scores_[s].reset();
+        d_pack_reads_[s].reset();
+        d_pack_refs_[s].reset();
+    }
     for (int s = 0; s < kSlots; ++s) {
         // (write-combined pinned memory for the input staging was tried: no gain -- the call is bound by the H2D
         // copies, 12-14 ms per 650 MB while the host threads gather, and by what else runs on the box)
-        hip_check(hipHostMalloc((void **)&h_reads_[s], std::max<size_t>((size_t)pairs * R_, 16), hipHostMallocDefault), "hipHostMalloc");
-        hip_check(hipHostMalloc((void **)&h_refs_[s], std::max<size_t>((size_t)pairs * F_, 16), hipHostMallocDefault), "hipHostMalloc");
-        hip_check(hipHostMalloc((void **)&h_scores_[s], sizeof(short) * (size_t)pairs, hipHostMallocDefault), "hipHostMalloc");
-        hip_check(hipMalloc((void **)&d_reads_[s], std::max<size_t>((size_t)pairs * R_, 16)), "hipMalloc");
-        hip_check(hipMalloc((void **)&d_refs_[s], std::max<size_t>((size_t)pairs * F_, 16)), "hipMalloc");
-        hip_check(hipMalloc((void **)&d_scores_[s], sizeof(short) * (size_t)pairs), "hipMalloc");
+        h_reads_[s].reserve(std::max<size_t>((size_t)pairs * R_, 16));
+        h_refs_[s].reserve(std::max<size_t>((size_t)pairs * F_, 16));
+        h_scores_[s].reserve(sizeof(short) * (size_t)pairs);
+        d_reads_[s].reserve(std::max<size_t>((size_t)pairs * R_, 16));
+        d_refs_[s].reserve(std::max<size_t>((size_t)pairs * F_, 16));
+        d_scores_[s].reserve(sizeof(short) * (size_t)pairs);
         // (the 4-bit class copies of the score path; the pinned staging above is large enough for them)
-        hip_check(hipMalloc((void **)&d_pack_reads_[s], std::max<size_t>((size_t)pairs * packed_length(R_), 16)), "hipMalloc");
-        hip_check(hipMalloc((void **)&d_pack_refs_[s], std::max<size_t>((size_t)pairs * packed_length(F_), 16)), "hipMalloc");
+        d_pack_reads_[s].reserve(std::max<size_t>((size_t)pairs * packed_length(R_), 16));
+        d_pack_refs_[s].reserve(std::max<size_t>((size_t)pairs * packed_length(F_), 16));
     }
     staged_pairs_ = pairs;
 }

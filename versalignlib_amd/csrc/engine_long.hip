@@ -123,18 +123,16 @@ bool Engine::score_band_device(long long n, const uint8_t *d_reads, const uint8_
     if (no_band_chain_ || band_width_ <= 0) return false;
     if (band_plan_width_ != band_width_) {
         band_plan_ = make_band_plan();
-        band_plan_width_ = band_width_;
         hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
-        if (d_band_blocks_) (void)hipFree(d_band_blocks_);
-        if (d_band_fill_) (void)hipFree(d_band_fill_);
-        d_band_blocks_ = nullptr;
-        d_band_fill_ = nullptr;
+        d_band_blocks_.reset();
+        d_band_fill_.reset();
         if (band_plan_.usable) {
-            hip_check(hipMalloc((void **)&d_band_blocks_, band_plan_.blocks.size() * sizeof(BandBlock)), "hipMalloc(band blocks)");
-            hip_check(hipMalloc((void **)&d_band_fill_, band_plan_.fill_to.size() * sizeof(int)), "hipMalloc(band fill)");
-            hip_check(hipMemcpy(d_band_blocks_, band_plan_.blocks.data(), band_plan_.blocks.size() * sizeof(BandBlock), hipMemcpyHostToDevice), "hipMemcpy");
-            hip_check(hipMemcpy(d_band_fill_, band_plan_.fill_to.data(), band_plan_.fill_to.size() * sizeof(int), hipMemcpyHostToDevice), "hipMemcpy");
+            d_band_blocks_.reserve(band_plan_.blocks.size() * sizeof(BandBlock), "band blocks");
+            d_band_fill_.reserve(band_plan_.fill_to.size() * sizeof(int), "band fill");
+            hip_check(hipMemcpy(d_band_blocks_.get(), band_plan_.blocks.data(), band_plan_.blocks.size() * sizeof(BandBlock), hipMemcpyHostToDevice), "hipMemcpy");
+            hip_check(hipMemcpy(d_band_fill_.get(), band_plan_.fill_to.data(), band_plan_.fill_to.size() * sizeof(int), hipMemcpyHostToDevice), "hipMemcpy");
         }
+        band_plan_width_ = band_width_;         // (only once the tables are on the device)
     }
     if (!band_plan_.usable) return false;
     const BandPlan &p = band_plan_;
@@ -142,8 +140,8 @@ bool Engine::score_band_device(long long n, const uint8_t *d_reads, const uint8_
     a.reads = d_reads;
     a.refs = d_refs;
     a.scores = d_scores;
-    a.blocks = d_band_blocks_;
-    a.fill_to = d_band_fill_;
+    a.blocks = d_band_blocks_.get();
+    a.fill_to = d_band_fill_.get();
     a.n = n;
     a.R = R_;
     a.F = F_;
@@ -153,14 +151,7 @@ bool Engine::score_band_device(long long n, const uint8_t *d_reads, const uint8_
     a.d = p.d;
     a.ring_depth = p.ring_depth;
     a.code_cols = p.code_cols;
-    a.match = (short)sc_.match;
-    a.mismatch = (short)sc_.mismatch;
-    a.gap_read = (short)sc_.gap_read;
-    a.gap_ref = (short)sc_.gap_ref;
-    a.open_read = (short)sc_.open_read;
-    a.ext_read = (short)sc_.ext_read;
-    a.open_ref = (short)sc_.open_ref;
-    a.ext_ref = (short)sc_.ext_ref;
+    put_scoring(a);
     const bool sym = (sc_.affine ? (sc_.open_read == sc_.open_ref && sc_.ext_read == sc_.ext_ref) : sc_.gap_read == sc_.gap_ref) && !no_sym_;
     static const void *const kernels[2][2][2] = {        // [affine][one score both ways][unit delay]
         {{(const void *)&score_band_kernel<kBandK, false, false>, (const void *)&score_band_kernel<kBandK, false, true>},
@@ -208,26 +199,16 @@ void Engine::score_long_device(int alg, long long n, const uint8_t *d_reads, con
     a.strips = std::max(1, (R_ + rows - 1) / rows);
     a.row_dwords = ((F_ + geo.G + kPhase - 1) / kPhase) * kPhase + kPhase;
     a.band_half = (band_width_ > 0 && alg == kAlgSW) ? band_width_ / 2 : -1;
-    a.match = (short)sc_.match;
-    a.mismatch = (short)sc_.mismatch;
-    a.gap_read = (short)sc_.gap_read;
-    a.gap_ref = (short)sc_.gap_ref;
-    a.open_read = (short)sc_.open_read;
-    a.ext_read = (short)sc_.ext_read;
-    a.open_ref = (short)sc_.open_ref;
-    a.ext_ref = (short)sc_.ext_ref;
+    put_scoring(a);
     const int row_sets = (wide ? 2 : 1) * (sc_.affine ? 2 : 1);        // boundary rows per pair-of-pairs: per half (int32), H and F (affine)
     const size_t bytes_per_wave = (size_t)2 * (ppw / 2) * a.row_dwords * 4 * row_sets;
     long long chunk = (long long)((8ull << 30) / bytes_per_wave) * ppw;
     chunk = std::max<long long>(ppw, std::min(chunk, (n + ppw - 1) / ppw * ppw));
     const long long waves = chunk / ppw;
     const bool single_strip = long_single_strip(wide);       // (no boundary rows: nothing to allocate, nothing shared between launches)
-    if (!single_strip && (size_t)waves * bytes_per_wave > brow_bytes_) {
+    if (!single_strip && (size_t)waves * bytes_per_wave > d_brow_.bytes()) {
         hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
-        if (d_brow_) (void)hipFree(d_brow_);
-        d_brow_ = nullptr;
-        brow_bytes_ = (size_t)waves * bytes_per_wave;
-        hip_check(hipMalloc((void **)&d_brow_, brow_bytes_), "hipMalloc(boundary rows)");
+        d_brow_.reserve((size_t)waves * bytes_per_wave, "boundary rows");
     }
     const bool affine_sym = sc_.open_read == sc_.open_ref && sc_.ext_read == sc_.ext_ref && !no_sym_;
     const bool sym = sc_.affine ? affine_sym : (sc_.gap_read == sc_.gap_ref && !no_sym_);
@@ -258,7 +239,7 @@ void Engine::score_long_device(int alg, long long n, const uint8_t *d_reads, con
         a.reads = d_reads + (size_t)begin * R_;
         a.refs = d_refs + (size_t)begin * F_;
         a.scores = d_scores + begin;
-        a.brow = d_brow_;
+        a.brow = d_brow_.get();
         a.n = cnt;
         a.pp_total = waves * (ppw / 2) * row_sets;
         void *kargs[] = {&a};

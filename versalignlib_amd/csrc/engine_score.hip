@@ -27,12 +27,12 @@ void Engine::score_device(int opt, long long n, const uint8_t *d_reads, const ui
         // table copies are through -- otherwise it would rewrite the pinned tables under them.  Calls on one stream are
         // ordered by the stream.
         if (ragged_dev_done_ && ragged_dev_stream_ != stream)
-            hip_check(hipEventSynchronize(ragged_dev_done_), "hipEventSynchronize(previous length-sorted call)");
-        if (!ragged_dev_done_) hip_check(hipEventCreateWithFlags(&ragged_dev_done_, hipEventDisableTiming), "hipEventCreate");
+            hip_check(hipEventSynchronize(ragged_dev_done_.get()), "hipEventSynchronize(previous length-sorted call)");
+        if (!ragged_dev_done_) ragged_dev_done_ = make_event(hipEventDisableTiming);
         ragged_dev_stream_ = stream;
         ragged_begin(kSlots, n, d_reads, d_refs, stream);           // (a context of its own: the pipeline's slots may be busy on the engine's streams)
         const bool swept = ragged_finish(kSlots, alg, n, d_scores, stream, ragged_ == 2);
-        hip_check(hipEventRecord(ragged_dev_done_, stream), "hipEventRecord");
+        hip_check(hipEventRecord(ragged_dev_done_.get(), stream), "hipEventRecord");
         if (swept) return;
     }
     // a batch that leaves most SIMDs with at most one wave is over when its slowest wave is: shortest sweep
@@ -70,14 +70,7 @@ void Engine::launch_score(const LaunchPlan &plan, int alg, int R, int F, long lo
     a.prof_area = plan.lds.prof_area;
     a.refc_stride = plan.lds.refc_stride;
     a.wave_lds = plan.lds.total;
-    a.match = (short)sc_.match;
-    a.mismatch = (short)sc_.mismatch;
-    a.gap_read = (short)sc_.gap_read;
-    a.gap_ref = (short)sc_.gap_ref;
-    a.open_read = (short)sc_.open_read;
-    a.ext_read = (short)sc_.ext_read;
-    a.open_ref = (short)sc_.open_ref;
-    a.ext_ref = (short)sc_.ext_ref;
+    put_scoring(a);
     int gaps;
     if (sc_.affine) {
         gaps = (sc_.open_read == sc_.open_ref && sc_.ext_read == sc_.ext_ref && !no_sym_) ? kGapAffineSym : kGapAffine;
@@ -143,12 +136,13 @@ void Engine::score_host(int opt, int n, const char *const *reads, const char *co
         // three copies, a launch, an event and four event waits.
         host_stats_ = HostStats{};
         auto t0 = std::chrono::steady_clock::now();
-        gather(reads, refs, n, h_reads_[0], h_refs_[0], threads);
+        gather(reads, refs, n, h_reads_[0].get(), h_refs_[0].get(), threads);
         auto t1 = std::chrono::steady_clock::now();
-        score_device(opt, n, dev_view(h_reads_[0]), dev_view(h_refs_[0]), d_dest ? d_dest : (int16_t *)dev_view(h_scores_[0]), streams_[0]);
-        hip_check(hipStreamSynchronize(streams_[0]), "hipStreamSynchronize");
+        score_device(opt, n, dev_view(h_reads_[0].get()), dev_view(h_refs_[0].get()), d_dest ? d_dest : (int16_t *)dev_view(h_scores_[0].get()),
+                     streams_[0].get());
+        hip_check(hipStreamSynchronize(streams_[0].get()), "hipStreamSynchronize");
         auto t2 = std::chrono::steady_clock::now();
-        if (!d_dest) memcpy(scores, h_scores_[0], sizeof(short) * (size_t)n);
+        if (!d_dest) memcpy(scores, h_scores_[0].get(), sizeof(short) * (size_t)n);
         host_stats_.gather_ms = ms_between(t0, t1);
         host_stats_.wait_ms = ms_between(t1, t2);
         host_stats_.drain_ms = ms_between(t2, std::chrono::steady_clock::now());
@@ -170,18 +164,18 @@ void Engine::score_host(int opt, int n, const char *const *reads, const char *co
             slot_pending_[s] = 0;
             return;
         }
-        memcpy(scores + slot_begin_[s], h_scores_[s], sizeof(short) * (size_t)slot_pending_[s]);
+        memcpy(scores + slot_begin_[s], h_scores_[s].get(), sizeof(short) * (size_t)slot_pending_[s]);
         slot_pending_[s] = 0;
     };
     // what follows a chunk's kernels: the scores' way home and the slot's event.  A length-sorted chunk gets there one
     // iteration late: its classification runs on the device while the host gathers the next chunk, and only then does
     // the host read the histogram, lay the groups out and launch the sweeps (ragged_finish) -- no wait in between.
     auto finish_chunk = [&](int s, long long pairs) {
-        hipStream_t cs = streams_[shared_scratch ? 0 : s];
-        if (ragged) (void)ragged_finish(s, alg, pairs, d_scores_[s], cs, true);
+        hipStream_t cs = streams_[shared_scratch ? 0 : s].get();
+        if (ragged) (void)ragged_finish(s, alg, pairs, d_scores_[s].get(), cs, true);
         if (!d_dest)
-            hip_check(hipMemcpyAsync(h_scores_[s], d_scores_[s], sizeof(short) * (size_t)pairs, hipMemcpyDeviceToHost, cs), "D2H scores");
-        hip_check(hipEventRecord(slot_done_[s], cs), "hipEventRecord");
+            hip_check(hipMemcpyAsync(h_scores_[s].get(), d_scores_[s].get(), sizeof(short) * (size_t)pairs, hipMemcpyDeviceToHost, cs), "D2H scores");
+        hip_check(hipEventRecord(slot_done_[s].get(), cs), "hipEventRecord");
     };
     // (two iterations late, in fact: one gather is about as long as a chunk's copy + classification, two leave room)
     struct OpenChunk {
@@ -198,36 +192,37 @@ void Engine::score_host(int opt, int n, const char *const *reads, const char *co
         const long long ramp = (n > 2 * chunk) ? (chunk_no == 0 ? whole_rounds(chunk / 4) : (chunk_no == 1 ? whole_rounds(chunk / 2) : chunk)) : chunk;
         cnt = std::min<long long>(std::max<long long>(ramp, 1024), n - begin);
         auto t0 = std::chrono::steady_clock::now();
-        hip_check(hipEventSynchronize(slot_done_[slot]), "hipEventSynchronize");
+        hip_check(hipEventSynchronize(slot_done_[slot].get()), "hipEventSynchronize");
         auto t1 = std::chrono::steady_clock::now();
         drain(slot);                            // the result of the chunk that used this slot
         auto t2 = std::chrono::steady_clock::now();
         host_stats_.wait_ms += ms_between(t0, t1);
         host_stats_.drain_ms += ms_between(t1, t2);
         // kernels that share a scratch (strip boundary rows) stay on one stream
-        hipStream_t st = streams_[shared_scratch ? 0 : slot];
+        hipStream_t st = streams_[shared_scratch ? 0 : slot].get();
+        uint8_t *h_reads = h_reads_[slot].get(), *h_refs = h_refs_[slot].get(), *d_reads = d_reads_[slot].get(), *d_refs = d_refs_[slot].get();
         const bool sweep_now = !ragged;
         if (pack_) {
             // two base classes per byte across PCIe, expanded in HBM to the canonical byte of each class
             const size_t PR = packed_length(R_), PF = packed_length(F_);
-            packer_.gather_packed(reads + begin, refs + begin, cnt, h_reads_[slot], h_refs_[slot], threads);
+            packer_.gather_packed(reads + begin, refs + begin, cnt, h_reads, h_refs, threads);
             host_stats_.gather_ms += ms_between(t2, std::chrono::steady_clock::now());
-            hip_check(hipMemcpyAsync(d_pack_reads_[slot], h_reads_[slot], (size_t)cnt * PR, hipMemcpyHostToDevice, st), "H2D reads (classes)");
-            hip_check(hipMemcpyAsync(d_pack_refs_[slot], h_refs_[slot], (size_t)cnt * PF, hipMemcpyHostToDevice, st), "H2D refs (classes)");
-            launch_unpack(d_pack_reads_[slot], d_reads_[slot], cnt, R_, st);
-            launch_unpack(d_pack_refs_[slot], d_refs_[slot], cnt, F_, st);
+            hip_check(hipMemcpyAsync(d_pack_reads_[slot].get(), h_reads, (size_t)cnt * PR, hipMemcpyHostToDevice, st), "H2D reads (classes)");
+            hip_check(hipMemcpyAsync(d_pack_refs_[slot].get(), h_refs, (size_t)cnt * PF, hipMemcpyHostToDevice, st), "H2D refs (classes)");
+            launch_unpack(d_pack_reads_[slot].get(), d_reads, cnt, R_, st);
+            launch_unpack(d_pack_refs_[slot].get(), d_refs, cnt, F_, st);
             host_stats_.packed = 1;
         } else {
-            gather(reads + begin, refs + begin, cnt, h_reads_[slot], h_refs_[slot], threads);
+            gather(reads + begin, refs + begin, cnt, h_reads, h_refs, threads);
             host_stats_.gather_ms += ms_between(t2, std::chrono::steady_clock::now());
-            hip_check(hipMemcpyAsync(d_reads_[slot], h_reads_[slot], (size_t)cnt * R_, hipMemcpyHostToDevice, st), "H2D reads");
-            hip_check(hipMemcpyAsync(d_refs_[slot], h_refs_[slot], (size_t)cnt * F_, hipMemcpyHostToDevice, st), "H2D refs");
+            hip_check(hipMemcpyAsync(d_reads, h_reads, (size_t)cnt * R_, hipMemcpyHostToDevice, st), "H2D reads");
+            hip_check(hipMemcpyAsync(d_refs, h_refs, (size_t)cnt * F_, hipMemcpyHostToDevice, st), "H2D refs");
         }
         if (sweep_now) {
-            score_device(opt, cnt, d_reads_[slot], d_refs_[slot], d_dest ? d_dest + begin : d_scores_[slot], st, false);
+            score_device(opt, cnt, d_reads, d_refs, d_dest ? d_dest + begin : d_scores_[slot].get(), st, false);
             finish_chunk(slot, cnt);
         } else {
-            ragged_begin(slot, cnt, d_reads_[slot], d_refs_[slot], st);
+            ragged_begin(slot, cnt, d_reads, d_refs, st);
             open.push_back(OpenChunk{slot, cnt});
             if (open.size() > kOpenChunks) {
                 finish_chunk(open.front().slot, open.front().pairs);
@@ -241,7 +236,7 @@ void Engine::score_host(int opt, int n, const char *const *reads, const char *co
     for (int k = 0; k < kSlots; ++k) {          // oldest chunk first
         const int s = (slot + k) % kSlots;
         auto t0 = std::chrono::steady_clock::now();
-        hip_check(hipEventSynchronize(slot_done_[s]), "hipEventSynchronize");
+        hip_check(hipEventSynchronize(slot_done_[s].get()), "hipEventSynchronize");
         auto t1 = std::chrono::steady_clock::now();
         drain(s);
         host_stats_.wait_ms += ms_between(t0, t1);
@@ -268,52 +263,33 @@ double Engine::sampled_cell_fraction(const char *const *reads, const char *const
 
 void Engine::ensure_ragged(int c, long long n) {
     RaggedCtx &x = rag_[c];
-    if (!d_read_class_) {
-        hip_check(hipMalloc((void **)&d_read_class_, read_class_.size()), "hipMalloc(read classes)");
-        hip_check(hipMalloc((void **)&d_ref_class_, sizeof(uint16_t) * ref_class_.size()), "hipMalloc(ref classes)");
-        hip_check(hipMemcpy(d_read_class_, read_class_.data(), read_class_.size(), hipMemcpyHostToDevice), "hipMemcpy");
-        hip_check(hipMemcpy(d_ref_class_, ref_class_.data(), sizeof(uint16_t) * ref_class_.size(), hipMemcpyHostToDevice), "hipMemcpy");
+    if (!d_ref_class_.get()) {
+        d_read_class_.reserve(read_class_.size(), "read classes");
+        d_ref_class_.reserve(sizeof(uint16_t) * ref_class_.size(), "ref classes");
+        hip_check(hipMemcpy(d_read_class_.get(), read_class_.data(), read_class_.size(), hipMemcpyHostToDevice), "hipMemcpy");
+        hip_check(hipMemcpy(d_ref_class_.get(), ref_class_.data(), sizeof(uint16_t) * ref_class_.size(), hipMemcpyHostToDevice), "hipMemcpy");
     }
-    if (!x.counted) {
-        hip_check(hipEventCreateWithFlags(&x.counted, hipEventDisableTiming), "hipEventCreate");
-        hip_check(hipMalloc((void **)&x.counters, sizeof(unsigned) * (kRaggedMaxBins + kRaggedMaxGroups)), "hipMalloc(ragged counters)");
-        hip_check(hipMalloc((void **)&x.tables, kRaggedTableBytes), "hipMalloc(ragged tables)");
-        hip_check(hipHostMalloc((void **)&x.h_counts, sizeof(unsigned) * kRaggedMaxBins, hipHostMallocDefault), "hipHostMalloc");
-        hip_check(hipHostMalloc((void **)&x.h_tables, kRaggedTableBytes, hipHostMallocDefault), "hipHostMalloc");
-    }
+    if (!x.counted) x.counted = make_event(hipEventDisableTiming);
+    x.counters.reserve(sizeof(unsigned) * (kRaggedMaxBins + kRaggedMaxGroups), "ragged counters");      // (fixed sizes: once)
+    x.tables.reserve(kRaggedTableBytes, "ragged tables");
+    x.h_counts.reserve(sizeof(unsigned) * kRaggedMaxBins);
+    x.h_tables.reserve(kRaggedTableBytes);
     if (x.cap >= n) return;
-    for (void *p : {(void *)x.reads, (void *)x.refs, (void *)x.scores, (void *)x.bin, (void *)x.pos, (void *)x.place})
-        if (p) (void)hipFree(p);                         // (hipFree waits for the device: nothing is still reading them)
-    x.reads = x.refs = nullptr;
-    x.scores = nullptr;
-    x.bin = nullptr;
-    x.pos = nullptr;
-    x.place = nullptr;
     x.cap = 0;
-    hip_check(hipMalloc((void **)&x.reads, std::max<size_t>((size_t)n * R_, 16)), "hipMalloc(ragged reads)");
-    hip_check(hipMalloc((void **)&x.refs, std::max<size_t>((size_t)n * F_, 16)), "hipMalloc(ragged refs)");
-    hip_check(hipMalloc((void **)&x.scores, sizeof(int16_t) * (size_t)n), "hipMalloc(ragged scores)");
-    hip_check(hipMalloc((void **)&x.bin, sizeof(uint16_t) * (size_t)n), "hipMalloc(ragged bins)");
-    hip_check(hipMalloc((void **)&x.pos, sizeof(int) * (size_t)n), "hipMalloc(ragged places)");
-    hip_check(hipMalloc((void **)&x.place, sizeof(RaggedPlace) * (size_t)n), "hipMalloc(ragged place records)");
+    // (hipFree waits for the device: nothing is still reading them)
+    x.reads.reset();
+    x.refs.reset();
+    x.scores.reset();
+    x.bin.reset();
+    x.pos.reset();
+    x.place.reset();
+    x.reads.reserve(std::max<size_t>((size_t)n * R_, 16), "ragged reads");
+    x.refs.reserve(std::max<size_t>((size_t)n * F_, 16), "ragged refs");
+    x.scores.reserve(sizeof(int16_t) * (size_t)n, "ragged scores");
+    x.bin.reserve(sizeof(uint16_t) * (size_t)n, "ragged bins");
+    x.pos.reserve(sizeof(int) * (size_t)n, "ragged places");
+    x.place.reserve(sizeof(RaggedPlace) * (size_t)n, "ragged place records");
     x.cap = n;
-}
-
-void Engine::release_ragged() {
-    if (ragged_dev_done_) (void)hipEventDestroy(ragged_dev_done_);
-    ragged_dev_done_ = nullptr;
-    for (RaggedCtx &x : rag_) {
-        for (void *p : {(void *)x.reads, (void *)x.refs, (void *)x.scores, (void *)x.bin, (void *)x.pos, (void *)x.place, (void *)x.counters, (void *)x.tables})
-            if (p) (void)hipFree(p);
-        if (x.h_counts) (void)hipHostFree(x.h_counts);
-        if (x.h_tables) (void)hipHostFree(x.h_tables);
-        if (x.counted) (void)hipEventDestroy(x.counted);
-        x = RaggedCtx{};
-    }
-    if (d_read_class_) (void)hipFree(d_read_class_);
-    if (d_ref_class_) (void)hipFree(d_ref_class_);
-    d_read_class_ = nullptr;
-    d_ref_class_ = nullptr;
 }
 
 void Engine::ragged_begin(int c, long long n, const uint8_t *d_reads, const uint8_t *d_refs, hipStream_t stream) {
@@ -322,14 +298,14 @@ void Engine::ragged_begin(int c, long long n, const uint8_t *d_reads, const uint
     x.src_reads = d_reads;
     x.src_refs = d_refs;
     const int NG = ragged_bins();
-    hip_check(hipMemsetAsync(x.counters, 0, sizeof(unsigned) * (kRaggedMaxBins + kRaggedMaxGroups), stream), "hipMemsetAsync");
-    RaggedClassifyArgs a{d_reads, d_refs, n, R_, F_, d_read_class_, d_ref_class_, (int)ref_caps_.size(), NG, x.bin, x.counters};
+    hip_check(hipMemsetAsync(x.counters.get(), 0, sizeof(unsigned) * (kRaggedMaxBins + kRaggedMaxGroups), stream), "hipMemsetAsync");
+    RaggedClassifyArgs a{d_reads, d_refs, n, R_, F_, d_read_class_.get(), d_ref_class_.get(), (int)ref_caps_.size(), NG, x.bin.get(), x.counters.get()};
     void *kargs[] = {&a};
     const long long blocks = (n + kRaggedClassifyPairs - 1) / kRaggedClassifyPairs;
     hip_check(hipLaunchKernel((const void *)&ragged_classify_kernel, dim3((unsigned)blocks), dim3(256), kargs, 0, stream),
               "hipLaunchKernel(ragged_classify_kernel)");
-    hip_check(hipMemcpyAsync(x.h_counts, x.counters, sizeof(unsigned) * (size_t)NG, hipMemcpyDeviceToHost, stream), "D2H histogram");
-    hip_check(hipEventRecord(x.counted, stream), "hipEventRecord");
+    hip_check(hipMemcpyAsync(x.h_counts.get(), x.counters.get(), sizeof(unsigned) * (size_t)NG, hipMemcpyDeviceToHost, stream), "D2H histogram");
+    hip_check(hipEventRecord(x.counted.get(), stream), "hipEventRecord");
 }
 
 std::vector<Engine::LengthGroup> Engine::fold_groups(std::vector<long long> &total, std::vector<int> &group_of_bin) const {
@@ -387,12 +363,12 @@ bool Engine::ragged_finish(int c, int alg, long long n, int16_t *d_scores, hipSt
     RaggedCtx &x = rag_[c];
     const int NG = ragged_bins();
     const auto t0 = std::chrono::steady_clock::now();
-    hip_check(hipEventSynchronize(x.counted), "hipEventSynchronize");
+    hip_check(hipEventSynchronize(x.counted.get()), "hipEventSynchronize");
     const auto t_counted = std::chrono::steady_clock::now();
     host_stats_.classify_ms += ms_between(t0, t_counted);
     std::vector<long long> total((size_t)NG);
     long long seen = 0;
-    for (int g = 0; g < NG; ++g) seen += (total[g] = (long long)x.h_counts[g]);
+    for (int g = 0; g < NG; ++g) seen += (total[g] = (long long)x.h_counts.get()[g]);
     if (seen != n) throw std::runtime_error("length classification lost pairs");
     std::vector<int> group_of_bin;
     const std::vector<LengthGroup> groups = fold_groups(total, group_of_bin);
@@ -402,15 +378,15 @@ bool Engine::ragged_finish(int c, int alg, long long n, int16_t *d_scores, hipSt
     if (!always && swept >= 0.67 * padded) return false;
     const int NL = (int)groups.size();
     if (NL > kRaggedMaxGroups) throw std::runtime_error("too many length groups");
-    uint16_t *h_map = reinterpret_cast<uint16_t *>(x.h_tables);
-    RaggedGroupDev *h_groups = reinterpret_cast<RaggedGroupDev *>(x.h_tables + sizeof(uint16_t) * kRaggedMaxBins);
+    uint16_t *h_map = reinterpret_cast<uint16_t *>(x.h_tables.get());
+    RaggedGroupDev *h_groups = reinterpret_cast<RaggedGroupDev *>(x.h_tables.get() + sizeof(uint16_t) * kRaggedMaxBins);
     for (int g = 0; g < NG; ++g) h_map[g] = (uint16_t)group_of_bin[g];
     for (int l = 0; l < NL; ++l)
         h_groups[l] = RaggedGroupDev{groups[l].R, groups[l].F, groups[l].pair_ofs, (long long)groups[l].read_ofs, (long long)groups[l].ref_ofs};
-    hip_check(hipMemcpyAsync(x.tables, x.h_tables, kRaggedTableBytes, hipMemcpyHostToDevice, stream), "H2D length groups");
-    RaggedPermuteArgs pa{x.src_reads, x.src_refs, n, R_, F_, x.bin, reinterpret_cast<const uint16_t *>(x.tables),
-                         reinterpret_cast<const RaggedGroupDev *>(x.tables + sizeof(uint16_t) * kRaggedMaxBins), NL,
-                         x.counters + kRaggedMaxBins, x.reads, x.refs, x.pos, x.place};
+    hip_check(hipMemcpyAsync(x.tables.get(), x.h_tables.get(), kRaggedTableBytes, hipMemcpyHostToDevice, stream), "H2D length groups");
+    RaggedPermuteArgs pa{x.src_reads, x.src_refs, n, R_, F_, x.bin.get(), reinterpret_cast<const uint16_t *>(x.tables.get()),
+                         reinterpret_cast<const RaggedGroupDev *>(x.tables.get() + sizeof(uint16_t) * kRaggedMaxBins), NL,
+                         x.counters.get() + kRaggedMaxBins, x.reads.get(), x.refs.get(), x.pos.get(), x.place.get()};
     void *pargs[] = {&pa};
     hip_check(hipLaunchKernel((const void *)&ragged_place_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), pargs, 0, stream),
               "hipLaunchKernel(ragged_place_kernel)");
@@ -421,12 +397,12 @@ bool Engine::ragged_finish(int c, int alg, long long n, int16_t *d_scores, hipSt
         size_t end = first;
         int widest = 0;
         while (end < groups.size() && groups[end].R == groups[first].R) widest = std::max(widest, groups[end++].F);
-        launch_score(class_plan(groups[first].R, widest), alg, groups[first].R, widest, 0, x.reads, x.refs, x.scores, stream,
+        launch_score(class_plan(groups[first].R, widest), alg, groups[first].R, widest, 0, x.reads.get(), x.refs.get(), x.scores.get(), stream,
                      groups.data() + first, (int)(end - first));
         host_stats_.launches += 1;
         first = end;
     }
-    RaggedUnpermuteArgs ua{x.scores, x.pos, d_scores, n};
+    RaggedUnpermuteArgs ua{x.scores.get(), x.pos.get(), d_scores, n};
     void *uargs[] = {&ua};
     hip_check(hipLaunchKernel((const void *)&ragged_unpermute_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), uargs, 0, stream),
               "hipLaunchKernel(ragged_unpermute_kernel)");

@@ -67,44 +67,44 @@ public:
             throw std::runtime_error("hip_devices_allgather: librccl.so lacks an expected symbol");
         comms_.assign(devices.size(), nullptr);
         check(init_all_(comms_.data(), (int)devices.size(), devices.data()), "ncclCommInitAll");
-        streams_.assign(devices.size(), nullptr);
+        streams_.resize(devices.size());
         for (size_t i = 0; i < devices.size(); ++i) {
             valign::hip_check(hipSetDevice(devices[i]), "hipSetDevice");
-            valign::hip_check(hipStreamCreateWithFlags(&streams_[i], hipStreamNonBlocking), "hipStreamCreate");
+            streams_[i] = valign::make_stream();
         }
-        send_.assign(devices.size(), nullptr);
-        recv_.assign(devices.size(), nullptr);
+        send_.resize(devices.size());
+        recv_.resize(devices.size());
     }
     ~ShardGather() {
         for (size_t i = 0; i < devices_.size(); ++i) {
             (void)hipSetDevice(devices_[i]);
-            if (i < send_.size() && send_[i]) (void)hipFree(send_[i]);
-            if (i < recv_.size() && recv_[i]) (void)hipFree(recv_[i]);
-            if (i < streams_.size() && streams_[i]) (void)hipStreamDestroy(streams_[i]);
+            send_[i].reset();
+            recv_[i].reset();
+            streams_[i].reset();
             if (i < comms_.size() && comms_[i] && destroy_) (void)destroy_(comms_[i]);
         }
         // (librccl.so stays loaded: a collective library with service threads is not something to unmap under them)
     }
     // shard buffer of device i: `per` scores (the all-gather needs equal counts: the last shard's tail is padding)
     void reserve(int per) { ensure(per); }                                   // (before the shard threads start)
-    int16_t *shard(int i) const { return send_[(size_t)i]; }
+    int16_t *shard(int i) const { return send_[(size_t)i].get(); }
     // after every shard's kernels have finished: gather on all devices, copy the first n scores out of device 0's vector
     void gather_to_host(int per, int n, short *scores) {
         check(group_start_(), "ncclGroupStart");
         for (size_t i = 0; i < devices_.size(); ++i)
-            check(all_gather_(send_[i], recv_[i], (size_t)per * 2, 0 /* ncclInt8 */, comms_[i], streams_[i]), "ncclAllGather");
+            check(all_gather_(send_[i].get(), recv_[i].get(), (size_t)per * 2, 0 /* ncclInt8 */, comms_[i], streams_[i].get()), "ncclAllGather");
         check(group_end_(), "ncclGroupEnd");
         valign::hip_check(hipSetDevice(devices_[0]), "hipSetDevice");
-        valign::hip_check(hipMemcpyAsync(scores, recv_[0], sizeof(short) * (size_t)n, hipMemcpyDeviceToHost, streams_[0]), "D2H gathered scores");
+        valign::hip_check(hipMemcpyAsync(scores, recv_[0].get(), sizeof(short) * (size_t)n, hipMemcpyDeviceToHost, streams_[0].get()), "D2H gathered scores");
         for (size_t i = 0; i < devices_.size(); ++i) {
             valign::hip_check(hipSetDevice(devices_[i]), "hipSetDevice");
-            valign::hip_check(hipStreamSynchronize(streams_[i]), "hipStreamSynchronize");
+            valign::hip_check(hipStreamSynchronize(streams_[i].get()), "hipStreamSynchronize");
         }
     }
     // (tests) the gathered vector of device i, first n scores
     void copy_gathered(int i, int n, short *out) {
         valign::hip_check(hipSetDevice(devices_[(size_t)i]), "hipSetDevice");
-        valign::hip_check(hipMemcpy(out, recv_[(size_t)i], sizeof(short) * (size_t)n, hipMemcpyDeviceToHost), "D2H");
+        valign::hip_check(hipMemcpy(out, recv_[(size_t)i].get(), sizeof(short) * (size_t)n, hipMemcpyDeviceToHost), "D2H");
     }
 
 private:
@@ -115,12 +115,11 @@ private:
         if (per <= cap_) return;
         for (size_t i = 0; i < devices_.size(); ++i) {
             valign::hip_check(hipSetDevice(devices_[i]), "hipSetDevice");
-            if (send_[i]) (void)hipFree(send_[i]);
-            if (recv_[i]) (void)hipFree(recv_[i]);
-            send_[i] = recv_[i] = nullptr;
-            valign::hip_check(hipMalloc((void **)&send_[i], sizeof(short) * (size_t)per), "hipMalloc(shard scores)");
-            valign::hip_check(hipMalloc((void **)&recv_[i], sizeof(short) * (size_t)per * devices_.size()), "hipMalloc(gathered scores)");
-            valign::hip_check(hipMemset(send_[i], 0, sizeof(short) * (size_t)per), "hipMemset");
+            send_[i].reset();
+            recv_[i].reset();
+            send_[i].reserve(sizeof(short) * (size_t)per, "shard scores");
+            recv_[i].reserve(sizeof(short) * (size_t)per * devices_.size(), "gathered scores");
+            valign::hip_check(hipMemset(send_[i].get(), 0, sizeof(short) * (size_t)per), "hipMemset");
         }
         cap_ = per;
     }
@@ -133,8 +132,8 @@ private:
     int (*all_gather_)(const void *, void *, size_t, int, void *, hipStream_t) = nullptr;
     const char *(*error_string_)(int) = nullptr;
     std::vector<void *> comms_;
-    std::vector<hipStream_t> streams_;
-    std::vector<int16_t *> send_, recv_;
+    std::vector<valign::StreamHandle> streams_;
+    std::vector<valign::DeviceBuffer<int16_t>> send_, recv_;
     int cap_ = 0;
 };
 
