@@ -216,7 +216,10 @@ int valign_hip_set_host_packing(valign_hip_engine *e, int mode);
  * half_float_cells.                                                                                                      */
 int valign_hip_set_half_float_cells(valign_hip_engine *e, int mode);
 
-/* JSON description of what a call with this opt would launch (geometry, LDS, grid).   */
+/* JSON description of what a call with this opt would launch (geometry, LDS, grid).  "score_cells" is a prediction for a
+ * device-resident call of n pairs; "ran_score_cells" (f16 / int16 / int32, joined with '+' where a length-sorted call
+ * mixed them) and "ran_align_fill" (the alignment path and fill kernel: fused_tag, tag_prof_key, ..., strip, strip_wide)
+ * report what the engine's last score / alignment call actually launched ("none" before any).                         */
 int valign_hip_describe(valign_hip_engine *e, int opt, long long n, char *buf, int cap);
 
 const char *valign_hip_last_error(void);

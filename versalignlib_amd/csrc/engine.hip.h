@@ -326,8 +326,17 @@ public:
     // align_fill_tag_kernel keeps 4 * cell + tag in int16
     bool tagged_range_ok(int alg, int rows) const;
 
-    // what score_alignments computes in for this mode at the engine's full shape
-    const char *score_cell_format(int alg) const;
+    // The cell format score_alignments is PREDICTED to compute in for this mode: a device-resident call of n pairs (n <= 0:
+    // a large call) at the engine's full shape.  What a call really launched is ran_score_cells(): the host pipeline's
+    // chunks may be small enough for the latency plan, and length-sorted batches sweep each length class on a plan of its own.
+    const char *score_cell_format(int alg, long long n = 0) const;
+    // the long-read score kernel of this mode runs on half-float cells (score_long_device; describe predicts with it)
+    bool long_score_f16(int alg, bool wide) const;
+    bool long_tall_strips() const;         // score_long_device sweeps on the 512-row strips (kLongTall)
+    // what the last score / alignment call launched (describe: ran_score_cells, ran_align_fill)
+    std::string ran_score_cells() const;
+    const char *ran_align_fill() const { return ran_align_fill_; }
+    std::string ran_kernels() const;
 
     // Every cell of an R x F sweep and everything added to it stays an integer of magnitude <= 2048:
     // exact in half floats (kGapAffineSymF16 / kGapAffineF16).  SW cells are >= 0; cells of the NW
@@ -636,6 +645,12 @@ private:
     int band_plan_width_ = -1;
     int band_blocks_per_cu_ = 0, band_lds_ = 0;          // of the last block-chain launch (describe)
     int long_strip_rows_ = 0;                            // rows per strip of the last score_long_kernel launch (describe)
+    // Cell formats of the score kernels the last score call launched, one bit each (kRanF16 / kRanInt16 / kRanInt32; a
+    // length-sorted batch may mix them), and the path + fill kernel of the last alignment call ("none": no call yet, or the
+    // call was refused) -- set where the kernel is picked, not re-derived (describe: ran_score_cells, ran_align_fill)
+    static constexpr unsigned kRanF16 = 1, kRanInt16 = 2, kRanInt32 = 4;
+    unsigned ran_score_cells_ = 0;
+    const char *ran_align_fill_ = "none";
     int cu_count_ = 0;
     bool no_band_chain_ = dbg_.on("no_band_chain");      // banded scores on score_long_kernel's strips
     int start_col_[kSlots] = {};                         // per slot: first column of the chunk's rows the copy issuer copied

@@ -93,6 +93,13 @@ Engine::FillChoice Engine::fill_choice(int alg, const Geometry &geo) const {
     return c;
 }
 
+// describe()'s name of a fill kernel (ran_align_fill)
+static const char *fill_kernel_name(int kernel) {
+    static const char *const names[kFillKernels] = {"linear", "linear_sym", "affine", "sse", "tag", "tag_key", "affine_sym",
+                                                            "affine_tag", "affine_tag_sym", "sse_tag", "sse_tag_key", "tag_prof_key"};
+    return kernel >= 0 && kernel < kFillKernels ? names[kernel] : "none";
+}
+
 // The plan an alignment call of this mode runs on: the engine's own where its geometry carries the kernel the call needs;
 // otherwise (a fallback kernel on a geometry compiled with the fast set only, kernel_instances.hip.h) the cheapest FULL
 // geometry that fits the read -- same results, the sweep a few per cent longer.
@@ -110,6 +117,7 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
                   short *d_idx, hipStream_t stream, const WalkChain *chain) {
     const int alg = opt & 0xF;
     if (alg > 1 || n <= 0) return false;
+    ran_align_fill_ = "none";
     // Alignments whose cells leave int16 (the reference's shorts would wrap): int32 cells on the row-strip path, one pair per
     // register (align_strip_wide_kernel) -- every mode; only scores so large that (R + F) * |score| nears 2^28 are refused
     // (column 0 of the NW variant: a gap of the whole read -- linear (R + 1) gap_ref; affine open_ref + R ext_ref, which
@@ -129,6 +137,7 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
             throw std::runtime_error("shape x scoring can leave the int32 range of the DP cells (read_length " + std::to_string(R_) +
                                      ", ref_length " + std::to_string(F_) + ")");
         hip_check(hipSetDevice(device_), "hipSetDevice");
+        ran_align_fill_ = "strip_wide";
         align_strips_device(alg, n, d_reads, d_refs, d_rows, d_idx, stream, true);
         return false;
     }
@@ -137,6 +146,7 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
     // rows, whose resident geometries (64 x 24 / 64 x 32: 34 to 53 KB of LDS) fill at 0.8-2.1 TCUPS where 12- or 16-row
     // strips at eight waves per CU do 1.6-2.3 (1 200 x 3 000: 41 / 74 ms -> 26 / 37 ms, linear / affine)
     if (align_base_plan().long_mode || (!force_g_ && !force_k_ && R_ > 1024)) {
+        ran_align_fill_ = "strip";
         align_strips_device(alg, n, d_reads, d_refs, d_rows, d_idx, stream);
         return false;
     }
@@ -165,6 +175,7 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
     chunk = chain ? 2 * chain_pairs : std::min(chunk, (n + ppb - 1) / ppb * ppb);
     ensure_trace_scratch(chunk, bytes_per_pp, plan.pairs_per_wave, stream);
     const void *fn = plan.geo->fill[alg][fc.kernel];
+    ran_align_fill_ = fill_kernel_name(fc.kernel);
     const int block_lds = plan.lds.total * plan.waves_per_block;
     if (block_lds > kDefaultBlockLds)
         hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, block_lds),
@@ -339,6 +350,7 @@ bool Engine::align_fused(int alg, long long n, const uint8_t *d_reads, const uin
     f.out_rows = d_rows;
     f.out_idx = d_idx;
     const void *fn = best->kernel[alg];
+    ran_align_fill_ = "fused_tag";
     if (best_total > kDefaultBlockLds)
         hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, best_total),
                   "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
@@ -467,6 +479,7 @@ void Engine::align_host(int opt, int n, const char *const *reads, const char *co
     const int alg = opt & 0xF;
     if (alg > 1 || n <= 0) return;
     hip_check(hipSetDevice(device_), "hipSetDevice");
+    ran_align_fill_ = "none";
     const int AL = R_ + F_;
     const size_t per_pair = (size_t)3 * AL + 8;
     // (row strips run chunk after chunk on one pointer scratch: chunks that fill the device -- 2 000 pairs-of-pairs and more --

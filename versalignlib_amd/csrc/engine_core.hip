@@ -89,19 +89,33 @@ bool Engine::tagged_range_ok(int alg, int rows) const {     // rows: padded rows
     return 4 * hi + 4 <= 32000 && 4 * lo - 4 >= -32000 && std::abs(sc_.match) < 2000 && std::abs(sc_.mismatch) < 2000;
 }
 
-const char *Engine::score_cell_format(int alg) const {
+const char *Engine::score_cell_format(int alg, long long n) const {
     if (alg > 1) return "none";
     if (alg == kAlgSW && band_chain_in_use()) return "int32";
     if (score_width_ == 32 || (score_width_ == 0 && !int16_range_ok(alg))) return "int32";
-    if (!plan_.long_mode && sc_.affine && !no_f16_ && half_float_exact(alg, R_, F_, plan_.geo->G * plan_.geo->K)) return "f16";
-    if (!plan_.long_mode && !sc_.affine && ((sc_.gap_read == sc_.gap_ref && !no_sym_) || alg == kAlgNW) && !no_f16_ &&
-        (alg == kAlgNW ? half_float_exact(alg, R_, F_, plan_.geo->G * plan_.geo->K) : half_float_unit_exact(R_, F_)))
-        return "f16";
     // (long-read kernels: Smith-Waterman with one gap score on the 160-row strips, engine_long.hip)
-    if (plan_.long_mode && alg == kAlgSW && !sc_.affine && sc_.gap_read == sc_.gap_ref && !no_sym_ && !no_f16_ && band_width_ == 0 &&
-        R_ <= 1024 && half_float_unit_exact(R_, F_))
+    if (plan_.long_mode) return long_score_f16(alg, false) ? "f16" : "int16";
+    // the plan score_device launches for a call of n pairs: small calls sweep on the latency plan, whose rows enter the
+    // NW variant's tilt
+    const LaunchPlan &plan = (n > 0 && n <= (long long)latency_plan_.pairs_per_wave * 1024 && band_width_ == 0) ? latency_plan_ : plan_;
+    const int rows = plan.geo->G * plan.geo->K;
+    if (sc_.affine && !no_f16_ && half_float_exact(alg, R_, F_, rows)) return "f16";
+    if (!sc_.affine && ((sc_.gap_read == sc_.gap_ref && !no_sym_) || alg == kAlgNW) && !no_f16_ &&
+        (alg == kAlgNW ? half_float_exact(alg, R_, F_, rows) : half_float_unit_exact(R_, F_)))
         return "f16";
     return "int16";
+}
+
+std::string Engine::ran_score_cells() const {
+    if (!ran_score_cells_) return "none";
+    std::string s;
+    for (const auto &f : {std::make_pair(kRanF16, "f16"), std::make_pair(kRanInt16, "int16"), std::make_pair(kRanInt32, "int32")})
+        if (ran_score_cells_ & f.first) s += (s.empty() ? "" : "+") + std::string(f.second);
+    return s;
+}
+
+std::string Engine::ran_kernels() const {
+    return "{\"ran_score_cells\": \"" + ran_score_cells() + "\", \"ran_align_fill\": \"" + ran_align_fill_ + "\"}";
 }
 
 bool Engine::half_float_exact(int alg, int R, int F, int rows) const {
@@ -175,22 +189,22 @@ std::string Engine::host_phases() const {
 
 std::string Engine::describe(int opt, long long n) const {
     const long long ppb = (long long)plan_.pairs_per_wave * plan_.waves_per_block;
-    char buf[1600];
+    char buf[2048];
     snprintf(buf, sizeof buf,
              "{\"arch\": \"%s\", \"device\": %d, \"alg\": %d, \"affine\": %d, \"group_lanes\": %d, "
              "\"rows_per_lane\": %d, \"padded_rows\": %d, \"pairs_per_wave\": %d, \"waves_per_block\": %d, "
              "\"lds_per_wave\": %d, \"lds_per_block\": %d, \"steps\": %d, \"blocks\": %lld, \"long_mode\": %d, "
              "\"band_width\": %d, \"ragged_batching\": %d, \"ragged_launches\": %d, \"ragged_cell_fraction\": %.4f, "
-             "\"score_cells\": \"%s\", \"direct_call\": %d, \"packed_classes\": %d, \"direct_out\": %d, \"band_block_rows\": %d, \"band_col_align\": %d, \"band_waves_per_cu\": %d, \"band_lds_per_wave\": %d, \"band_cells_per_pair\": %lld, \"long_strip_rows\": %d, \"d2h_row_mb\": %.1f, \"full_row_mb\": %.1f, \"host_gather_ms\": %.3f, \"host_classify_ms\": %.3f, \"host_wait_ms\": %.3f, \"host_drain_ms\": %.3f}",
+             "\"score_cells\": \"%s\", \"direct_call\": %d, \"packed_classes\": %d, \"direct_out\": %d, \"band_block_rows\": %d, \"band_col_align\": %d, \"band_waves_per_cu\": %d, \"band_lds_per_wave\": %d, \"band_cells_per_pair\": %lld, \"long_strip_rows\": %d, \"d2h_row_mb\": %.1f, \"full_row_mb\": %.1f, \"host_gather_ms\": %.3f, \"host_classify_ms\": %.3f, \"host_wait_ms\": %.3f, \"host_drain_ms\": %.3f, \"ran_score_cells\": \"%s\", \"ran_align_fill\": \"%s\"}",
              arch_.c_str(), device_, opt & 0xF, sc_.affine ? 1 : 0, plan_.geo->G, plan_.geo->K,
              plan_.geo->G * plan_.geo->K, plan_.pairs_per_wave, plan_.waves_per_block, plan_.lds.total,
              plan_.lds.total * plan_.waves_per_block, F_ + plan_.geo->G - 1, n > 0 ? (n + ppb - 1) / ppb : 0,
              plan_.long_mode ? 1 : 0, band_width_, ragged_, host_stats_.launches,
              host_stats_.cells_padded > 0 ? host_stats_.cells_swept / host_stats_.cells_padded : 1.0,
-             score_cell_format(opt & 0xF), host_stats_.direct, host_stats_.packed, host_stats_.direct_out,
+             score_cell_format(opt & 0xF, n), host_stats_.direct, host_stats_.packed, host_stats_.direct_out,
              ((opt & 0xF) == kAlgSW && band_chain_in_use()) ? kBandK : VALIGN_HIP_BAND_BLOCK_ROWS,
              ((opt & 0xF) == kAlgSW && band_chain_in_use()) ? 1 : VALIGN_HIP_BAND_COL_ALIGN, band_blocks_per_cu_, band_lds_, (band_plan_width_ == band_width_ && band_plan_.usable) ? band_plan_.cells : 0ll, long_strip_rows_, host_stats_.d2h_row_bytes / 1e6, host_stats_.full_row_bytes / 1e6, host_stats_.gather_ms, host_stats_.classify_ms, host_stats_.wait_ms,
-             host_stats_.drain_ms);
+             host_stats_.drain_ms, ran_score_cells().c_str(), ran_align_fill_);
     return buf;
 }
 

@@ -160,6 +160,7 @@ bool Engine::score_band_device(long long n, const uint8_t *d_reads, const uint8_
          {(const void *)&score_band_kernel<kBandK, true, false, true>, (const void *)&score_band_kernel<kBandK, true, true, true>}}};
     const void *fn = kernels[sc_.affine ? 1 : 0][sym ? 1 : 0][p.unit_delay ? 1 : 0];
     const int lds = BandLds<kBandK>::total(p.code_cols, p.ring_depth, sc_.affine);
+    ran_score_cells_ |= kRanInt32;
     // as many one-wave blocks as run side by side; each takes quads of pairs in turn (band_kernels.hip.h)
     int per_cu = 0;
     hip_check(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kWave, (size_t)lds), "hipOccupancyMaxActiveBlocksPerMultiprocessor");
@@ -177,6 +178,18 @@ bool Engine::band_chain_in_use() const {
     return !no_band_chain_ && band_width_ > 0 && (band_plan_width_ == band_width_ ? band_plan_.usable : make_band_plan().usable);
 }
 
+// Unbanded sweeps of reads beyond a few strips take the tall strips; a band is defined on the 160-row blocks.
+bool Engine::long_tall_strips() const {
+    return band_width_ == 0 && R_ > 2 * kLongTall.G * kLongTall.K && !dbg_.on("short_strips");
+}
+
+// Half-float cells (score_long_kernel<..., F16>): Smith-Waterman with one gap score on the 160-row strips while every cell
+// stays below 1024 -- short reads against a reference the resident kernels' LDS cannot hold (150 x 8 000: 8.2 -> ~11 TCUPS).
+bool Engine::long_score_f16(int alg, bool wide) const {
+    const bool sym = sc_.gap_read == sc_.gap_ref && !no_sym_;
+    return !long_tall_strips() && alg == kAlgSW && !sc_.affine && sym && !wide && band_width_ == 0 && !no_f16_ && half_float_unit_exact(R_, F_);
+}
+
 // One 160-row strip, packed cells, no band: the long-read instances that keep nothing in HBM between launches.
 bool Engine::long_single_strip(bool wide) const {
     return R_ <= kLongG * kLongK && !wide && band_width_ == 0 && !dbg_.on("no_single_strip");
@@ -188,8 +201,7 @@ void Engine::score_long_device(int alg, long long n, const uint8_t *d_reads, con
         throw std::runtime_error("band_width applies to Smith-Waterman scores only");
     // linear gaps, banded: the cyclic block chain (int32 cells whatever score_width says: same results in the int16 range)
     if (band_width_ > 0 && alg == kAlgSW && score_band_device(n, d_reads, d_refs, d_scores, stream)) return;
-    // unbanded sweeps of reads beyond a few strips take the tall strips; a band is defined on the 160-row blocks
-    const LongGeometry &geo = (band_width_ == 0 && R_ > 2 * kLongTall.G * kLongTall.K && !dbg_.on("short_strips")) ? kLongTall : kLongStrips;
+    const LongGeometry &geo = long_tall_strips() ? kLongTall : kLongStrips;
     const int rows = geo.G * geo.K;
     const int ppw = 2 * (kWave / geo.G);
     long_strip_rows_ = rows;
@@ -213,10 +225,8 @@ void Engine::score_long_device(int alg, long long n, const uint8_t *d_reads, con
     const bool affine_sym = sc_.open_read == sc_.open_ref && sc_.ext_read == sc_.ext_ref && !no_sym_;
     const bool sym = sc_.affine ? affine_sym : (sc_.gap_read == sc_.gap_ref && !no_sym_);
     const void *fn = geo.kernel[sc_.affine ? 1 : 0][alg][sym ? 1 : 0][wide ? 1 : 0];
-    // half-float cells (score_long_kernel<..., F16>): Smith-Waterman with one gap score on the 160-row strips while every cell
-    // stays below 1024 -- short reads against a reference the resident kernels' LDS cannot hold (150 x 8 000: 8.2 -> ~11 TCUPS)
-    if (&geo == &kLongStrips && alg == kAlgSW && !sc_.affine && sym && !wide && band_width_ == 0 && !no_f16_ && half_float_unit_exact(R_, F_))
-        fn = (const void *)&score_long_kernel<kLongG, kLongK, kAlgSW, true, false, false, true>;
+    if (long_score_f16(alg, wide)) fn = (const void *)&score_long_kernel<kLongG, kLongK, kAlgSW, true, false, false, true>;
+    ran_score_cells_ |= long_score_f16(alg, wide) ? kRanF16 : (wide ? kRanInt32 : kRanInt16);
     int long_lds = geo.lds[sc_.affine ? 1 : 0];
     // a read of ONE strip (short reads sent here for their reference's length): the instances without boundary rings
     if (single_strip) {

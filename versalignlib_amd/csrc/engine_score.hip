@@ -11,7 +11,10 @@ void Engine::score_device(int opt, long long n, const uint8_t *d_reads, const ui
     const int alg = opt & 0xF;
     if (alg > 1 || n <= 0) return;          // reference: unsupported mode is a silent no-op
     hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (length_sorted) host_stats_ = HostStats{};
+    if (length_sorted) {            // (a call of its own, or score_host's direct one)
+        host_stats_ = HostStats{};
+        ran_score_cells_ = 0;
+    }
     if (score_width_ == 16) check_int16_range(alg, true);
     const bool wide = score_width_ == 32 || (score_width_ == 0 && !int16_range_ok(alg));
     if (plan_.long_mode || wide) {      // int32 cells exist on the strip path only
@@ -83,6 +86,7 @@ void Engine::launch_score(const LaunchPlan &plan, int alg, int R, int F, long lo
             gaps = kGapSymF16;
     }
     const void *fn = plan.geo->kernel[alg][gaps];
+    ran_score_cells_ |= (gaps == kGapSymF16 || gaps == kGapAffineSymF16 || gaps == kGapAffineF16) ? kRanF16 : kRanInt16;
     const int block_lds = plan.lds.total * plan.waves_per_block;
     if (block_lds > kDefaultBlockLds)
         hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, block_lds),
@@ -113,6 +117,7 @@ void Engine::score_host(int opt, int n, const char *const *reads, const char *co
     const int alg = opt & 0xF;
     if (alg > 1 || n <= 0) return;
     hip_check(hipSetDevice(device_), "hipSetDevice");
+    ran_score_cells_ = 0;
     const size_t per_pair = (size_t)R_ + F_;
     // Long reads on row strips: their launches follow one another on one stream (the strips' boundary rows are one scratch) and
     // a 48 MB chunk of 10 kbp pairs is 1 200 waves for 3 500 resident ones -- each launch runs at a third of the device.

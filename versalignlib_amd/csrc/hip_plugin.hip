@@ -278,13 +278,13 @@ public:
                 });
                 gather_->gather_to_host(per, aln_number, scores);
                 log_line(0, "HIPKernel score done (RCCL all-gather of " + std::to_string(shards) + " shard(s) of " + std::to_string(per) +
-                                " scores), host phases " + engine_->host_phases());
+                                " scores), ran " + engine_->ran_kernels() + ", host phases " + engine_->host_phases());
                 return;
             }
             sharded(aln_number, threads, [&](valign::Engine &e, int begin, int count, int th) {
                 e.score_host(opt, count, reads + begin, refs + begin, scores + begin, th);
             });
-            log_line(0, "HIPKernel score done, host phases " + engine_->host_phases());
+            log_line(0, "HIPKernel score done, ran " + engine_->ran_kernels() + ", host phases " + engine_->host_phases());
         } catch (const std::exception &e) {
             rethrow_for_host(e.what());
         }
@@ -300,7 +300,7 @@ public:
             sharded(aln_number, threads, [&](valign::Engine &e, int begin, int count, int th) {
                 e.align_host(opt, count, reads + begin, refs + begin, alignments + begin, th);
             });
-            log_line(0, "HIPKernel align done, host phases " + engine_->host_phases());
+            log_line(0, "HIPKernel align done, ran " + engine_->ran_kernels() + ", host phases " + engine_->host_phases());
         } catch (const std::exception &e) {
             rethrow_for_host(e.what());
         }

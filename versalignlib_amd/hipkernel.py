@@ -256,7 +256,7 @@ class Engine:
         return rows, idx
 
     def describe(self, opt=0, n=0):
-        buf = ctypes.create_string_buffer(2048)
+        buf = ctypes.create_string_buffer(4096)
         lib().valign_hip_describe(self._h, int(opt), int(n), buf, len(buf))
         return json.loads(buf.value.decode())
 

@@ -191,6 +191,16 @@ class Plugin:
         lib().vh_drain_log(self._h, buf, len(buf))
         return buf.value.decode(errors="replace")
 
+    def last_ran(self):
+        """What the plugin's last score / alignment call launched, from its log line ("... done, ran {...}"):
+        {"ran_score_cells": "f16" | "int16" | "int32" | ..., "ran_align_fill": "fused_tag" | "tag_key" | "strip_wide" | ...}.
+        Drains the log; None when no call has logged since the last drain.  With several device shares (hip_devices) the
+        values are those of the first share's engine: every share runs the same shape and scoring, so the same kernels."""
+        import json
+        import re
+        found = re.findall(r"done(?: \([^)]*\))?, ran (\{[^}]*\})", self.drain_log())
+        return json.loads(found[-1]) if found else None
+
     def log_to_stderr(self, on=True):
         lib().vh_log_to_stderr(self._h, 1 if on else 0)
 
