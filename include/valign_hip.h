@@ -21,6 +21,10 @@
  *                                                         1 SSE2/AVX2 tie-breaks (linear gaps)
  *       band_width ...................................... > 0: banded Smith-Waterman scores, that
  *                                                         many diagonals around the main one (strip band)
+ *       band_alignments ................................. 1: compute_alignments under band_width > 0 returns banded
+ *                                                         Smith-Waterman alignments on the scores' block band;
+ *                                                         0 (default): every cell whatever band_width says
+ *                                                         (opt-in: existing calls return what they did)
  *       score_width ..................................... DP cells of score_alignments: 0 auto (int16,
  *                                                         int32 where int16 could overflow), 16, 32
  *       ragged_batching ................................. length-sorted score calls, both modes
@@ -134,12 +138,23 @@ int valign_hip_set_traceback_policy(valign_hip_engine *e, int policy);
  *   B = 160, A = 4   row strips (long_kernels.hip.h): every other banded case; VALIGN_HIP_BAND_BLOCK_ROWS /
  *                    VALIGN_HIP_BAND_COL_ALIGN.
  * The chain's band is the tighter superset of the per-cell band.  0 (default) computes every cell; a band wider
- * than the matrix gives the unbanded result.                                                                   */
+ * than the matrix gives the unbanded result.
+ *
+ * Alignments use the SAME block band once valign_hip_set_band_alignments(e, 1) (key band_alignments = 1) is set:
+ * the reference's Default SW fill and traceback (DefaultKernel.cpp:204-280, 391-456) on int32 semantics, every cell
+ * outside the band 0 with pointer START (affine gaps: H = E = F = 0), the end cell the row-major first strict maximum
+ * over in-band cells, the walk ending at START or at a step that leaves the band.  So the score of every returned
+ * alignment is the banded score of the same pair, and a band of at least 2 * max(R, F) gives the unbanded alignments.
+ * Smith-Waterman with linear or affine gaps and traceback_policy = 0 only: NW alignments and traceback_policy = 1 are
+ * refused under band_alignments = 1.                                                                             */
 #define VALIGN_HIP_BAND_BLOCK_ROWS 160
 #define VALIGN_HIP_BAND_COL_ALIGN 4
 #define VALIGN_HIP_BAND_CHAIN_BLOCK_ROWS 16
 #define VALIGN_HIP_BAND_CHAIN_COL_ALIGN 1
 int valign_hip_set_band_width(valign_hip_engine *e, int diagonals);
+/* 1: valign_hip_align_device / _align_host return banded SW alignments when band_width > 0 (above); 0 (default):
+ * unbanded alignments whatever band_width says.  Other values are refused.                                       */
+int valign_hip_set_band_alignments(valign_hip_engine *e, int on);
 
 /* Cap (MiB) of the internal pointer scratch compute_alignments keeps in device memory (2 bits per cell and pair,
  * 4 with affine gaps: 20.8 / 41.6 KB per pair at 150 x 500).  0 (default): up to 64 GiB or half the free HBM,

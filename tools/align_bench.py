@@ -20,6 +20,7 @@ def main():
     ap.add_argument("--models", default="linear,affine", help="gap models to time (affine: open -5, extend -1; BASELINE config 3)")
     ap.add_argument("--R", type=int, default=bench.R)
     ap.add_argument("--F", type=int, default=bench.F)
+    ap.add_argument("--band", type=int, default=0, help="> 0: banded SW alignments of that many diagonals (band_alignments = 1; NW skipped)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     bench.R, bench.F = a.R, a.F                     # (other shapes: reads beyond 2048 rows take the row strips)
@@ -35,7 +36,10 @@ def main():
         eng = hipkernel.Engine(bench.R, bench.F, sc, group_lanes=G, rows_per_lane=K)
         if a.policy:
             eng.set_traceback_policy(a.policy)
-        for opt, name in ((0, "sw_" + model), (1, "nw_" + model)):
+        if a.band > 0:
+            eng.set_band_width(a.band)
+            eng.set_band_alignments(1)
+        for opt, name in ((0, "sw_" + model),) + (((1, "nw_" + model),) if a.band <= 0 else ()):
             eng.align_device(opt, reads, refs, rows, idx)
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -46,7 +50,8 @@ def main():
             torch.cuda.synchronize()
             ms = e0.elapsed_time(e1) / a.iters
             d = eng.describe(opt, a.pairs)
-            print(json.dumps({"mode": name + "_align", "geom": "%dx%d" % (d["group_lanes"], d["rows_per_lane"]),
+            print(json.dumps({"mode": name + "_align", "band": a.band, "fill": d["ran_align_fill"],
+                              "ptr_bytes_per_pair": d["align_ptr_bytes_per_pair"], "geom": "%dx%d" % (d["group_lanes"], d["rows_per_lane"]),
                               "ms": round(ms, 3), "gcups": round(a.pairs * bench.R * bench.F / ms / 1e6, 1),
                               "start_checksum": int(idx[:, 0].to(torch.int64).sum().item())}))
         eng.close()

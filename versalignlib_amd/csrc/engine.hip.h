@@ -235,6 +235,16 @@ public:
         if (diagonals > 0 && !plan_.long_mode) plan_ = long_plan();
     }
     int band_width() const { return band_width_; }
+    // Alignments under band_width (opt-in, so that band_width keeps its meaning for existing callers): 1 = compute_alignments
+    // returns banded Smith-Waterman alignments on the block band of the scores (band_block_shape; linear and affine gaps,
+    // traceback_policy 0), 0 = every cell whatever band_width says (default)
+    void set_band_alignments(int on) {
+        if (on != 0 && on != 1) throw std::runtime_error("band_alignments must be 0 or 1");
+        band_alignments_ = on == 1;
+    }
+    int band_alignments() const { return band_alignments_ ? 1 : 0; }
+    // The block band of banded SW scores and alignments: (16, 1) on the block chain, else (160, 4) (valign_hip.h)
+    void band_block_shape(int &block_rows, int &col_align) const;
     // DP cell width of score_alignments: 0 = int16 unless the shape could overflow it (default),
     // 16 = int16 or refuse, 32 = always int32 (strip path, half the throughput)
     void set_score_width(int bits) {
@@ -427,8 +437,10 @@ public:
     // rows ping-pong through HBM, one pointer region per strip, then the same traceback kernel (strip_kernels.hip.h).
     // Linear or affine gaps, Default tie-breaks, int16 cells (the reference's; where they would wrap the call is refused
     // by check_int16_range above instead of wrapping silently).
+    // band: banded SW alignments (align_strip_kernel<..., BAND>: each strip sweeps its rows' band windows only).
     void align_strips_device(int alg, long long n, const uint8_t *d_reads, const uint8_t *d_refs, uint8_t *d_rows,
-                             short *d_idx, hipStream_t stream, bool wide = false);
+                             short *d_idx, hipStream_t stream, bool wide = false, bool band = false);
+    bool align_banded() const { return band_alignments_ && band_width_ > 0; }
 
     // Host pointers in, Alignment[] out: the rows of every pair are fresh operator new[] blocks
     // (the host's ~Alignment delete[]s them, include/AlignmentKernel.h:20-23).
@@ -606,6 +618,7 @@ private:
     Scoring sc_;
     bool sse_policy_ = false;
     int band_width_ = 0;
+    bool band_alignments_ = false;
     int score_width_ = 0;
     int ragged_ = 0, force_g_ = 0, force_k_ = 0;
     size_t score_chunk_bytes_ = 48u << 20;                   // staging chunk of score_host (debug switch chunk_bytes)
@@ -651,6 +664,7 @@ private:
     static constexpr unsigned kRanF16 = 1, kRanInt16 = 2, kRanInt32 = 4;
     unsigned ran_score_cells_ = 0;
     const char *ran_align_fill_ = "none";
+    long long align_ptr_bytes_per_pair_ = 0;             // pointer-stream bytes per pair of the last alignment call's plan (describe)
     int cu_count_ = 0;
     bool no_band_chain_ = dbg_.on("no_band_chain");      // banded scores on score_long_kernel's strips
     int start_col_[kSlots] = {};                         // per slot: first column of the chunk's rows the copy issuer copied

@@ -15,6 +15,7 @@ struct StripGeometry {
     const void *affine_kernel[2];      // nullptr: too many rows per lane for the affine kernel's registers
     const void *sse_kernel[2];         // traceback_policy = 1 (linear gaps)
     const void *wide_kernel[2][3];     // int32 cells, [alg][0 linear gaps, 1 affine, 2 SSE tie-breaks]; nullptr: no such instance
+    const void *band_kernel[2][2];     // banded SW (BAND), [0 int16 / 1 int32 cells][0 linear gaps, 1 affine]; nullptr: no such instance
 };
 // int32 cells are the rare path: every mode at 8 rows per lane, the NW variant with linear gaps (the reference's model: long
 // reads whose column-0 border leaves int16) at 16 / 12 as well
@@ -26,6 +27,13 @@ struct StripGeometry {
 #define VALIGN_STRIP_WIDE_NW(K) {{nullptr, nullptr, nullptr}, {(const void *)&align_strip_wide_kernel<K, kAlgNW>, nullptr, nullptr}}
 #define VALIGN_STRIP_WIDE_NONE {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}
 #define VALIGN_STRIP_SSE(K) {(const void *)&align_strip_kernel<K, kAlgSW, false, true>, (const void *)&align_strip_kernel<K, kAlgNW, false, true>}
+// banded SW alignments: int16 cells at 16 and 8 rows per lane, int32 cells at 8
+#define VALIGN_STRIP_BAND(K)                                                                                                 \
+    {{(const void *)&align_strip_kernel<K, kAlgSW, false, false, true>, (const void *)&align_strip_kernel<K, kAlgSW, true, false, true>}, \
+     {nullptr, nullptr}}
+#define VALIGN_STRIP_BAND_WIDE(K)                                                                                            \
+    {{(const void *)&align_strip_kernel<K, kAlgSW, false, false, true>, (const void *)&align_strip_kernel<K, kAlgSW, true, false, true>}, \
+     {(const void *)&align_strip_wide_kernel<K, kAlgSW, false, false, true>, (const void *)&align_strip_wide_kernel<K, kAlgSW, true, false, true>}}
 template <int K>
 static WaveLds strip_lds(int, int) {            // the profile of 64 K rows and the ring of slab numbers: no term in F
     return WaveLds{StripLds<K>::kRing, 0, StripLds<K>::kTotal};
@@ -33,15 +41,17 @@ static WaveLds strip_lds(int, int) {            // the profile of 64 K rows and 
 static const StripGeometry kStripGeometries[] = {
     {16, &strip_lds<16>, {(const void *)&align_strip_kernel<16, kAlgSW>, (const void *)&align_strip_kernel<16, kAlgNW>},
      {(const void *)&align_strip_kernel<16, kAlgSW, true>, (const void *)&align_strip_kernel<16, kAlgNW, true>}, VALIGN_STRIP_SSE(16),
-     VALIGN_STRIP_WIDE_NW(16)},
+     VALIGN_STRIP_WIDE_NW(16), VALIGN_STRIP_BAND(16)},
     {12, &strip_lds<12>, {(const void *)&align_strip_kernel<12, kAlgSW>, (const void *)&align_strip_kernel<12, kAlgNW>},
      {(const void *)&align_strip_kernel<12, kAlgSW, true>, (const void *)&align_strip_kernel<12, kAlgNW, true>}, VALIGN_STRIP_SSE(12),
-     VALIGN_STRIP_WIDE_NW(12)},
+     VALIGN_STRIP_WIDE_NW(12), {{nullptr, nullptr}, {nullptr, nullptr}}},
     {8, &strip_lds<8>, {(const void *)&align_strip_kernel<8, kAlgSW>, (const void *)&align_strip_kernel<8, kAlgNW>},
      {(const void *)&align_strip_kernel<8, kAlgSW, true>, (const void *)&align_strip_kernel<8, kAlgNW, true>}, VALIGN_STRIP_SSE(8),
-     VALIGN_STRIP_WIDE_ALL(8)},
+     VALIGN_STRIP_WIDE_ALL(8), VALIGN_STRIP_BAND_WIDE(8)},
 };
 #undef VALIGN_STRIP_SSE
+#undef VALIGN_STRIP_BAND
+#undef VALIGN_STRIP_BAND_WIDE
 #undef VALIGN_STRIP_WIDE_ALL
 #undef VALIGN_STRIP_WIDE_NW
 #undef VALIGN_STRIP_WIDE_NONE
@@ -118,6 +128,10 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
     const int alg = opt & 0xF;
     if (alg > 1 || n <= 0) return false;
     ran_align_fill_ = "none";
+    const bool band = align_banded();
+    if (band && alg != kAlgSW) throw std::runtime_error("band_alignments applies to Smith-Waterman alignments only");
+    if (band && sse_policy_)
+        throw std::runtime_error("band_alignments needs traceback_policy = 0 (no banded SSE/AVX tie-breaks)");
     // Alignments whose cells leave int16 (the reference's shorts would wrap): int32 cells on the row-strip path, one pair per
     // register (align_strip_wide_kernel) -- every mode; only scores so large that (R + F) * |score| nears 2^28 are refused
     // (column 0 of the NW variant: a gap of the whole read -- linear (R + 1) gap_ref; affine open_ref + R ext_ref, which
@@ -137,11 +151,18 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
             throw std::runtime_error("shape x scoring can leave the int32 range of the DP cells (read_length " + std::to_string(R_) +
                                      ", ref_length " + std::to_string(F_) + ")");
         hip_check(hipSetDevice(device_), "hipSetDevice");
-        ran_align_fill_ = "strip_wide";
-        align_strips_device(alg, n, d_reads, d_refs, d_rows, d_idx, stream, true);
+        ran_align_fill_ = band ? "strip_wide_band" : "strip_wide";
+        align_strips_device(alg, n, d_reads, d_refs, d_rows, d_idx, stream, true, band);
         return false;
     }
     hip_check(hipSetDevice(device_), "hipSetDevice");
+    // banded SW alignments: row strips that sweep the band windows (banded cells never exceed unbanded ones: the range
+    // decision above stands)
+    if (band) {
+        ran_align_fill_ = "strip_band";
+        align_strips_device(alg, n, d_reads, d_refs, d_rows, d_idx, stream, false, true);
+        return false;
+    }
     // row strips: reads beyond one register sweep, and -- measured, profiles/r04_rate_sweep.txt -- reads of more than 1 024
     // rows, whose resident geometries (64 x 24 / 64 x 32: 34 to 53 KB of LDS) fill at 0.8-2.1 TCUPS where 12- or 16-row
     // strips at eight waves per CU do 1.6-2.3 (1 200 x 3 000: 41 / 74 ms -> 26 / 37 ms, linear / affine)
@@ -174,6 +195,7 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
     if (!chain) chain_regions_busy_[0] = chain_regions_busy_[1] = false;
     chunk = chain ? 2 * chain_pairs : std::min(chunk, (n + ppb - 1) / ppb * ppb);
     ensure_trace_scratch(chunk, bytes_per_pp, plan.pairs_per_wave, stream);
+    align_ptr_bytes_per_pair_ = (long long)(bytes_per_pp / 2);
     const void *fn = plan.geo->fill[alg][fc.kernel];
     ran_align_fill_ = fill_kernel_name(fc.kernel);
     const int block_lds = plan.lds.total * plan.waves_per_block;
@@ -309,7 +331,7 @@ void Engine::ensure_trace_stream() {
 bool Engine::align_fused(int alg, long long n, const uint8_t *d_reads, const uint8_t *d_refs, uint8_t *d_rows, short *d_idx,
                  hipStream_t stream) {
     if (no_fused_ || sc_.affine || sse_policy_ || no_tag_ || align_base_plan().long_mode || force_g_ || force_k_ || !tagged_range_ok(alg, 256)) return false;     // (256: the tallest fused geometry)
-    if (wide_align_) return false;
+    if (wide_align_ || align_banded()) return false;       // (banded alignments: the strip kernels)
     try {
         check_int16_range(alg);
     } catch (const std::runtime_error &) {
@@ -351,6 +373,7 @@ bool Engine::align_fused(int alg, long long n, const uint8_t *d_reads, const uin
     f.out_idx = d_idx;
     const void *fn = best->kernel[alg];
     ran_align_fill_ = "fused_tag";
+    align_ptr_bytes_per_pair_ = (long long)best->G * best_blocks * best->K * 4 / 2;
     if (best_total > kDefaultBlockLds)
         hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, best_total),
                   "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
@@ -362,7 +385,7 @@ bool Engine::align_fused(int alg, long long n, const uint8_t *d_reads, const uin
 }
 
 void Engine::align_strips_device(int alg, long long n, const uint8_t *d_reads, const uint8_t *d_refs, uint8_t *d_rows,
-                         short *d_idx, hipStream_t stream, bool wide) {
+                         short *d_idx, hipStream_t stream, bool wide, bool band) {
     const bool affine = sc_.affine;
     if (sse_policy_ && affine)
         throw std::runtime_error("traceback_policy = 1 (SSE/AVX tie-breaks) exists for the linear gap model only");
@@ -377,6 +400,7 @@ void Engine::align_strips_device(int alg, long long n, const uint8_t *d_reads, c
         if (affine && !g.affine_kernel[alg]) continue;
         if (sse_policy_ && !g.sse_kernel[alg]) continue;
         if (wide && !g.wide_kernel[alg][wide_mode]) continue;
+        if (band && !g.band_kernel[wide ? 1 : 0][affine ? 1 : 0]) continue;
         if (strip_k_ && g.K != strip_k_) continue;
         const int rows_g = 64 * g.K;
         const double cost = (double)((R_ + rows_g - 1) / rows_g) * rows_g * (g.K == 16 ? 1.0 : (g.K == 12 ? 1.115 : 1.147));
@@ -389,12 +413,27 @@ void Engine::align_strips_device(int alg, long long n, const uint8_t *d_reads, c
     if (!geo) throw std::runtime_error("no strip alignment kernel for this mode");
     const int K = geo->K, rows = 64 * K, AL = R_ + F_;
     const int strips = std::max(1, (R_ + rows - 1) / rows), pad_total = strips * rows - R_;
-    const int blocks8 = (F_ + 63 + 7) / 8;
+    // band: every strip's pointer region is sized by the widest strip window (the block band, band_window.h)
+    BandShape bs{-1, 1, 1, 0};
+    int max_cols = F_;
+    if (band) {
+        band_block_shape(bs.block_rows, bs.col_align);
+        bs.half = band_width_ / 2;
+        bs.pad = (R_ + bs.block_rows - 1) / bs.block_rows * bs.block_rows - R_;
+        max_cols = 0;
+        for (int s = 0; s < strips; ++s) {
+            int c_lo, cols;
+            band_rows_window(bs, s * rows - pad_total, (s + 1) * rows - pad_total - 1, R_, F_, c_lo, cols);
+            max_cols = std::max(max_cols, cols);
+        }
+    }
+    const int blocks8 = (max_cols + 63 + 7) / 8;
     const int row_dwords = ((F_ + 71) / 64 + 2) * 64;
     const size_t strip_words = (size_t)blocks8 * 64 * K * (affine ? 2 : 1);    // per wave (= pair-of-pairs) and strip
     // boundary row sets: H, and F beside it (affine); int32 cells: those per pair
     const int row_sets = (affine ? 2 : 1) * (wide ? 2 : 1);
     const size_t bytes_per_pp = strip_words * 4 * strips + (size_t)2 * row_sets * row_dwords * 4;
+    align_ptr_bytes_per_pair_ = (long long)(strip_words * 4 * strips / 2);
     size_t free_b = 0, total_b = 0;
     hip_check(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
     // (the pointer stream of a 10 kbp x 10 kbp pair-of-pairs is 50 MB: what fits the scratch is what runs side by side --
@@ -414,7 +453,8 @@ void Engine::align_strips_device(int alg, long long n, const uint8_t *d_reads, c
     hipLaunchKernelGGL(first_invalid_kernel, dim3((unsigned)n), dim3(kWave), 0, stream, d_reads, d_refs, n, R_, F_, d_first_bad_.get(),
                        sse_policy_ ? 1 : 0);
     hip_check(hipGetLastError(), "hipLaunchKernel(first_invalid_kernel)");
-    const void *fn = wide ? geo->wide_kernel[alg][wide_mode] : (affine ? geo->affine_kernel[alg] : (sse_policy_ ? geo->sse_kernel[alg] : geo->kernel[alg]));
+    const void *fn = band ? geo->band_kernel[wide ? 1 : 0][affine ? 1 : 0]
+                          : wide ? geo->wide_kernel[alg][wide_mode] : (affine ? geo->affine_kernel[alg] : (sse_policy_ ? geo->sse_kernel[alg] : geo->kernel[alg]));
     if (lds.total > kDefaultBlockLds)
         hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds.total),
                   "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
@@ -441,6 +481,7 @@ void Engine::align_strips_device(int alg, long long n, const uint8_t *d_reads, c
             a.strip = s;
             a.strips = strips;
             a.row_dwords = row_dwords;
+            a.band = bs;
             put_scoring(a);
             void *kargs[] = {&a};
             hip_check(hipLaunchKernel(fn, dim3((unsigned)cnt_waves), dim3(kWave), kargs, (size_t)lds.total, stream),
@@ -467,8 +508,10 @@ void Engine::align_strips_device(int alg, long long n, const uint8_t *d_reads, c
         t.strip_rows = rows;
         t.strip_words = (long long)(cnt_waves * strip_words);
         t.wide_score = wide ? 1 : 0;
+        t.band = bs;
         void *targs[] = {&t};
-        hip_check(hipLaunchKernel((const void *)&traceback_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), targs, 0, stream),
+        hip_check(hipLaunchKernel(band ? (const void *)&traceback_band_kernel : (const void *)&traceback_kernel, dim3((unsigned)((cnt + 255) / 256)),
+                                  dim3(256), targs, 0, stream),
                   "hipLaunchKernel(traceback_kernel)");
     }
 }
@@ -484,7 +527,7 @@ void Engine::align_host(int opt, int n, const char *const *reads, const char *co
     const size_t per_pair = (size_t)3 * AL + 8;
     // (row strips run chunk after chunk on one pointer scratch: chunks that fill the device -- 2 000 pairs-of-pairs and more --
     // instead of 128 MB of staging, which is 1 100 of them at 10 kbp x 10 kbp: 253 -> ~190 ms per 4 096 pairs through the ABI)
-    const bool by_strips = align_base_plan().long_mode || (!force_g_ && !force_k_ && R_ > 1024);
+    const bool by_strips = align_base_plan().long_mode || (!force_g_ && !force_k_ && R_ > 1024) || align_banded();
     const size_t chunk_bytes = by_strips && !dbg_.on("align_chunk_bytes") ? std::max<size_t>(align_chunk_bytes_, 384u << 20) : align_chunk_bytes_;
     long long chunk = per_pair ? (long long)(chunk_bytes / per_pair) : n;
     chunk = whole_rounds(chunk);

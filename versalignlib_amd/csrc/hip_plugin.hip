@@ -202,6 +202,7 @@ public:
                                                                      opt_param("hip_group_lanes", 0), opt_param("hip_rows_per_lane", 0)));
                 e->set_traceback_policy(opt_param("traceback_policy", 0));
                 e->set_band_width(opt_param("band_width", 0));
+                e->set_band_alignments(opt_param("band_alignments", 0));
                 e->set_score_width(opt_param("score_width", 0));
                 e->set_ragged_batching(opt_param("ragged_batching", 0));
                 // pointer scratch of compute_alignments (device memory, internal): capped at 64 GiB / half the free HBM
@@ -437,6 +438,14 @@ VALIGN_EXPORT int valign_hip_set_band_width(valign_hip_engine *e, int diagonals)
         return 1;
     }
     return flat_guard([&] { e->impl->set_band_width(diagonals); });
+}
+
+VALIGN_EXPORT int valign_hip_set_band_alignments(valign_hip_engine *e, int on) {
+    if (!e) {
+        g_last_error = "null engine";
+        return 1;
+    }
+    return flat_guard([&] { e->impl->set_band_alignments(on); });
 }
 
 VALIGN_EXPORT int valign_hip_set_score_width(valign_hip_engine *e, int bits) {

@@ -24,6 +24,7 @@
 
 #include "dp_kernels.hip.h"
 #include "valign_hip.h"
+#include "band_window.h"
 
 namespace valign {
 
@@ -89,26 +90,6 @@ struct LongLds {
     static constexpr int kOutF = kInF + geo::kGroups * kRing * 4;
     static constexpr int kTotal = SINGLE ? kIn : (AFFINE ? kOutF + geo::kGroups * kRing * 4 : kInF);      // (LDS bounds the waves per CU: 9 at 16.7 KB, 12 at 12.6)
 };
-
-// Columns [c_lo, c_hi] swept by strip s.  c_lo is a multiple of 4 (16-byte ring accesses).
-template <int G, int K>
-__host__ __device__ inline void strip_columns(int s, int R, int F, int pad_rows, int band_half, int &c_lo, int &c_hi) {
-    constexpr int rows = G * K;
-    // (a band is only ever swept with the geometry whose strips are the API's blocks: Engine::score_long_device checks
-    // G * K == VALIGN_HIP_BAND_BLOCK_ROWS there; taller strips exist for unbanded sweeps)
-    static_assert(VALIGN_HIP_BAND_COL_ALIGN == 4, "c_lo is rounded down to a multiple of 4 below");
-    if (band_half < 0 || R <= 0) {
-        c_lo = 0;
-        c_hi = F - 1;
-        return;
-    }
-    int r_lo = s * rows - pad_rows, r_hi = (s + 1) * rows - pad_rows - 1;
-    r_lo = r_lo < 0 ? 0 : r_lo;
-    r_hi = r_hi > R - 1 ? R - 1 : r_hi;
-    const long long lo = (long long)r_lo * F / R - band_half, hi = (long long)r_hi * F / R + band_half;
-    c_lo = (int)(lo < 0 ? 0 : lo) & ~3;
-    c_hi = (int)(hi > F - 1 ? F - 1 : hi);
-}
 
 // AFFINE: Gotoh recurrence (E along the row in registers like H; F down the column -- through the lanes by DPP
 // and from strip to strip through a second boundary row next to H's).  SYM then means open_read == open_ref and

@@ -43,6 +43,7 @@ struct StripArgs {
     short match, mismatch;
     short gap_read, gap_ref;
     short open_read, ext_read, open_ref, ext_ref;     // affine
+    BandShape band;             // BAND kernels: the block band (band_window.h)
 };
 
 #ifdef VALIGN_TU_ALIGN      // not a template: defined once, in engine_align.hip
@@ -157,10 +158,18 @@ __device__ __forceinline__ StripRefBytes strip_ring_request(const uint8_t *ref_a
 // SSE: the tie-breaks of the reference's SSE2 / AVX2 kernels (traceback_policy = 1; linear gaps): stored states 3 DIAG
 // (only between two ACGT bases) > 2 LEFT > 1 UP > 0 START, no zero-floor arithmetic on the gap terms (a floored cell
 // whose neighbours lie below zero is START), as align_fill_sse_kernel (src/Kernels/AVX-SSE/SSEKernel.cpp:366-379, 646-659).
-template <int K, int ALG, bool AFFINE = false, bool SSE = false>
+//
+// BAND (Smith-Waterman, default tie-breaks): banded alignments on the block band StripArgs.band (band_window.h).  The strip
+// sweeps only the union [c_lo, c_lo + cols) of its rows' windows: the reference, the boundary rows and the column count are
+// taken from c_lo on, so step t is column c_lo + t - lane and the sweep is the unbanded one on a narrower matrix, and the
+// pointer region starts at c_lo.  A cell outside its own row's window is forced to H = E = F = 0 (the walk never reads its code:
+// it stops on reaching 0 and at the window's edge, traceback_band_kernel); the row above reads as 0 outside the columns
+// [p_lo, p_lo + p_w) the previous strip swept.
+template <int K, int ALG, bool AFFINE = false, bool SSE = false, bool BAND = false>
 __global__ void __launch_bounds__(64)
 align_strip_kernel(const StripArgs args) {
     static_assert(!(AFFINE && SSE), "the SSE / AVX kernels have linear gaps only");
+    static_assert(!BAND || (ALG == kAlgSW && !SSE), "bands: Smith-Waterman with the default tie-breaks");
     constexpr int W = AFFINE ? 2 * K : K;                             // pointer words per lane and block
     constexpr int G = 64;
     using geo = Geo<G, K>;
@@ -172,13 +181,20 @@ align_strip_kernel(const StripArgs args) {
 
     WaveTables w;
     if (!strip_ring_setup<K>(args.reads, args.n, R, args.F, args.match, args.mismatch, row0, w)) return;
-    const int F = args.F;
+    // BAND: columns [c_lo, c_lo + cols) of this strip, [p_lo, p_lo + p_w) of the previous one (relative to c_lo)
+    int c_lo = 0, cols = args.F, p_lo = 0, p_w = 0;
+    if constexpr (BAND) {
+        band_rows_window(args.band, row0, row0 + geo::kRows - 1, R, args.F, c_lo, cols);
+        if (args.strip > 0) band_rows_window(args.band, row0 - geo::kRows, row0 - 1, R, args.F, p_lo, p_w);
+        p_lo -= c_lo;
+    }
+    const int F = args.F - c_lo;                        // (columns from c_lo on)
 
     const unsigned lane_base = lds_offset(w.prof) + l * geo::kLaneBytes;
     // slab numbers of this lane's column: ring entry (j mod 128), two bytes (pair A, pair B)
     const unsigned ring_base = lds_offset(w.refc);
     unsigned code_addr = ring_base | ((unsigned)(-2 * l) & (2u * kStripRingCols - 1u));
-    const uint8_t *ref_a = args.refs + w.pair0 * args.F, *ref_b = args.refs + (w.pair0 + (w.last >= 1 ? 1 : 0)) * args.F;
+    const uint8_t *ref_a = args.refs + w.pair0 * args.F + c_lo, *ref_b = args.refs + (w.pair0 + (w.last >= 1 ? 1 : 0)) * args.F + c_lo;
     StripRefBytes ref_raw = strip_ring_request(ref_a, ref_b, lane, F);         // columns [0, 64)
 
     const s16x2 g_read = pk(ALG == kAlgSW ? (short)-args.gap_read : args.gap_read);
@@ -206,11 +222,16 @@ align_strip_kernel(const StripArgs args) {
     s16x2 El[AFFINE ? K : 1], code_g[AFFINE ? K : 1], acc_g[AFFINE ? K : 1];
     s16x2 rb[ALG == kAlgSW ? K : 1], fc[ALG == kAlgSW ? K : 1], sel[ALG == kAlgNW ? K : 1];
     s16x2 rinv[SSE ? K : 1];                           // SSE policy: 1 where the row's read base is not one of ACGT (no DIAG there)
+    int win_lo[BAND ? K : 1], win_w[BAND ? K : 1];     // BAND: each row's window, relative to c_lo
     short nw_seed[2] = {0, 0};
     const uint8_t *read_a = args.reads + (w.pair0 + 0) * R, *read_b = args.reads + (w.pair0 + (w.last >= 1 ? 1 : 0)) * R;
 #pragma unroll
     for (int q = 0; q < K; ++q) {
         const int pos = row0 + l * K + q;              // read position of the row (negative: padding)
+        if constexpr (BAND) {
+            band_row_window(args.band, pos, R, args.F, win_lo[q], win_w[q]);
+            win_lo[q] -= c_lo;
+        }
         if (SSE) {
             const int ca = (pos >= 0 && pos < R) ? base_class(read_a[pos]) : 0, cb = (pos >= 0 && pos < R) ? base_class(read_b[pos]) : 0;
             rinv[q] = s16x2{(short)((ca >= 1 && ca <= 4) ? 0 : 1), (short)((cb >= 1 && cb <= 4) ? 0 : 1)};
@@ -248,36 +269,42 @@ align_strip_kernel(const StripArgs args) {
 
     unsigned *ptr_lane = pointer_stream_lane<G, K, W>(args.ptr, w.pair0, args.blocks8, lane);
     const long long pp = w.pair0 / 2;
-    const unsigned *top = args.top + pp * args.row_dwords, *top_f = args.top_f + pp * args.row_dwords;
-    unsigned *bottom = args.bottom + pp * args.row_dwords, *bottom_f = args.bottom_f + pp * args.row_dwords;
+    const unsigned *top = args.top + pp * args.row_dwords + c_lo, *top_f = args.top_f + pp * args.row_dwords + c_lo;
+    unsigned *bottom = args.bottom + pp * args.row_dwords + c_lo, *bottom_f = args.bottom_f + pp * args.row_dwords + c_lo;
+    const int row_dwords = args.row_dwords - c_lo;
     const bool has_top = args.strip > 0, has_bottom = args.strip + 1 < args.strips;
+    // BAND: the row above at column c_lo - 1 (the diagonal of lane 0's first cell), where the previous strip swept it
+    if (BAND && l == 0 && has_top && (unsigned)(-1 - p_lo) < (unsigned)p_w) up0 = as_pk(top[-1]);
     // 64 columns of the row above per lane-register, fetched 64 steps ahead (row_dwords covers the reads)
     const unsigned border_f_bits = as_u32(border_f);
     unsigned top_cur = 0u, top_next = has_top ? top[lane] : 0u;
     unsigned topf_cur = border_f_bits, topf_next = (AFFINE && has_top) ? top_f[lane] : border_f_bits;
     unsigned bot_acc = 0u, botf_acc = 0u;
 
-    const int steps = (ALG == kAlgSW) ? ((F + G - 1 + 7) / 8) * 8 : args.blocks8 * 8;   // whole 8-step blocks
+    const int steps = (ALG == kAlgSW) ? (((BAND ? cols : F) + G - 1 + 7) / 8) * 8 : args.blocks8 * 8;   // whole 8-step blocks
     for (int t = 0; t < steps; ++t) {
         if ((t & 63) == 0) {
             top_cur = top_next;
-            top_next = (has_top && t + 64 + lane < args.row_dwords) ? top[t + 64 + lane] : 0u;
+            top_next = (has_top && t + 64 + lane < row_dwords) ? top[t + 64 + lane] : 0u;
             if (AFFINE) {
                 topf_cur = topf_next;
-                topf_next = (has_top && t + 64 + lane < args.row_dwords) ? top_f[t + 64 + lane] : border_f_bits;
+                topf_next = (has_top && t + 64 + lane < row_dwords) ? top_f[t + 64 + lane] : border_f_bits;
             }
             strip_ring_commit<K>(w.refc, t + lane, F, ref_raw);                // columns [t, t + 64): lane 0 needs column t now
             ref_raw = strip_ring_request(ref_a, ref_b, t + 64 + lane, F);
         }
         const s16x2 diag0 = up0;
-        const unsigned above = (unsigned)__builtin_amdgcn_readlane((int)top_cur, t & 63);      // H(row above, column t)
+        unsigned above = (unsigned)__builtin_amdgcn_readlane((int)top_cur, t & 63);      // H(row above, column t)
+        const bool above_out = BAND && (unsigned)(t - p_lo) >= (unsigned)p_w;           // BAND: not swept by the previous strip
+        if constexpr (BAND) above = above_out ? 0u : above;
         // every lane takes part in the DPP move: a lane masked off by the select would be read as 0 by its neighbour
         unsigned from_lane = from_prev_lane(as_u32(h_last));
         asm volatile("" : "+v"(from_lane));
         up0 = as_pk(l == 0 ? above : from_lane);
         s16x2 fup0 = border_f;
         if (AFFINE) {
-            const unsigned above_f = (unsigned)__builtin_amdgcn_readlane((int)topf_cur, t & 63);
+            unsigned above_f = (unsigned)__builtin_amdgcn_readlane((int)topf_cur, t & 63);
+            if constexpr (BAND) above_f = above_out ? 0u : above_f;
             unsigned f_lane = from_prev_lane(as_u32(f_last));
             asm volatile("" : "+v"(f_lane));
             fup0 = as_pk(l == 0 ? above_f : f_lane);
@@ -305,6 +332,9 @@ align_strip_kernel(const StripArgs args) {
                 const s16x2 f_open = gap_add(h, o_ref), f_extd = gap_add(f, e_ref);
                 f = pk_max(f_extd, f_open);
                 h = pk_max(m[q], f);
+                if constexpr (BAND) {
+                    if ((unsigned)(j - win_lo[q]) >= (unsigned)win_w[q]) h = f = El[q] = pk(0);     // outside the row's window
+                }
                 Hl[q] = h;
                 const s16x2 nd = pk_min_u(h - d[q], one), nf = pk_min_u(h - f, one);
                 code[q] = (s16x2)((u16x2)nd << (u16x2)nf);
@@ -383,6 +413,7 @@ align_strip_kernel(const StripArgs args) {
             for (int q = 0; q < K; ++q) {
                 const s16x2 ug = (ALG == kAlgSW) ? pk_sub_floor0(h, g_ref) : h + g_ref;
                 h = pk_max(m[q], ug);
+                if constexpr (BAND) h = (unsigned)(j - win_lo[q]) < (unsigned)win_w[q] ? h : pk(0);     // outside the row's window: 0
                 const s16x2 nu = pk_min_u(h - ug, one);
                 Hl[q] = h;
                 // back pointer: 0 if h == diag + S, else 1 if it came from above, else 2 (DIAG > UP > LEFT)
@@ -471,7 +502,7 @@ align_strip_kernel(const StripArgs args) {
             out.pad = 0;
             out.score = (short)(kmax >> 16);
             out.read_pos = (short)(strip_pad + p - pad_total);
-            out.ref_pos = (short)(col_t - win_lane);
+            out.ref_pos = (short)(c_lo + col_t - win_lane);
             if (out.score <= 0) {
                 out.read_pos = 0;
                 out.ref_pos = 0;
@@ -513,10 +544,12 @@ align_strip_kernel(const StripArgs args) {
 // both algorithms, linear / affine gaps (the same recurrences and equality-test pointers, plain int32 arithmetic; "minus
 // infinity" is -2^29, the host bounds (R + F) * |score| below 2^28), default / SSE tie-breaks.  The Smith-Waterman end
 // value does not fit EndCell.score: its high half travels in EndCell.pad (TraceArgs.wide_score).
-template <int K, int ALG = kAlgNW, bool AFFINE = false, bool SSE = false>
+// BAND: the banded strips of align_strip_kernel<..., BAND> on int32 cells.
+template <int K, int ALG = kAlgNW, bool AFFINE = false, bool SSE = false, bool BAND = false>
 __global__ void __launch_bounds__(64)
 align_strip_wide_kernel(const StripArgs args) {
     static_assert(!(AFFINE && SSE), "the SSE / AVX kernels have linear gaps only");
+    static_assert(!BAND || (ALG == kAlgSW && !SSE), "bands: Smith-Waterman with the default tie-breaks");
     constexpr int W = AFFINE ? 2 * K : K;                 // pointer words per lane and block
     constexpr int G = 64;
     constexpr int kNinf = -(1 << 29);
@@ -531,10 +564,24 @@ align_strip_wide_kernel(const StripArgs args) {
 
     WaveTables w;
     if (!strip_ring_setup<K>(args.reads, args.n, R, args.F, args.match, args.mismatch, row0, w)) return;
-    const int F = args.F;
+    // BAND: columns [c_lo, c_lo + cols) of this strip, [p_lo, p_lo + p_w) of the previous one (relative to c_lo), each row's
+    // window (relative to c_lo)
+    int c_lo = 0, cols = args.F, p_lo = 0, p_w = 0;
+    int win_lo[BAND ? K : 1], win_w[BAND ? K : 1];
+    if constexpr (BAND) {
+        band_rows_window(args.band, row0, row0 + geo::kRows - 1, R, args.F, c_lo, cols);
+        if (args.strip > 0) band_rows_window(args.band, row0 - geo::kRows, row0 - 1, R, args.F, p_lo, p_w);
+        p_lo -= c_lo;
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+            band_row_window(args.band, row0 + l * K + q, R, args.F, win_lo[q], win_w[q]);
+            win_lo[q] -= c_lo;
+        }
+    }
+    const int F = args.F - c_lo;                        // (columns from c_lo on)
     const unsigned lane_base = lds_offset(w.prof) + l * geo::kLaneBytes;
     const unsigned ring_base = lds_offset(w.refc);
-    const uint8_t *ref_a = args.refs + w.pair0 * args.F, *ref_b = args.refs + (w.pair0 + (w.last >= 1 ? 1 : 0)) * args.F;
+    const uint8_t *ref_a = args.refs + w.pair0 * args.F + c_lo, *ref_b = args.refs + (w.pair0 + (w.last >= 1 ? 1 : 0)) * args.F + c_lo;
     // Smith-Waterman: magnitudes for the floor-at-zero subtract (as align_strip_kernel); NW variant: signed addends
     const int g_read = ALG == kAlgSW && !SSE ? -args.gap_read : args.gap_read, g_ref = ALG == kAlgSW && !SSE ? -args.gap_ref : args.gap_ref;
     const int o_read = ALG == kAlgSW ? -args.open_read : args.open_read, e_read = ALG == kAlgSW ? -args.ext_read : args.ext_read;
@@ -547,14 +594,15 @@ align_strip_wide_kernel(const StripArgs args) {
     const long long pp = w.pair0 / 2;
     const size_t set_dwords = (size_t)(args.top_f - args.top);
     const bool has_top = args.strip > 0, has_bottom = args.strip + 1 < args.strips;
-    const int steps = (ALG == kAlgSW) ? ((F + G - 1 + 7) / 8) * 8 : args.blocks8 * 8;
+    const int steps = (ALG == kAlgSW) ? (((BAND ? cols : F) + G - 1 + 7) / 8) * 8 : args.blocks8 * 8;
+    const int row_dwords = args.row_dwords - c_lo;
 
     for (int half = 0; half < 2; ++half) {
         const long long pair = w.pair0 + half;
         const long long p_src = w.pair0 + (half > w.last ? w.last : half);
         const int ir = args.first_bad[2 * p_src], jr = args.first_bad[2 * p_src + 1];
-        const unsigned *top = args.top + (size_t)(kSets * half) * set_dwords + pp * args.row_dwords;
-        unsigned *bottom = args.bottom + (size_t)(kSets * half) * set_dwords + pp * args.row_dwords;
+        const unsigned *top = args.top + (size_t)(kSets * half) * set_dwords + pp * args.row_dwords + c_lo;
+        unsigned *bottom = args.bottom + (size_t)(kSets * half) * set_dwords + pp * args.row_dwords + c_lo;
         const unsigned *top_f = top + set_dwords;             // (affine only)
         unsigned *bottom_f = bottom + set_dwords;
         // NW variant: the one row whose arg-max the end-cell rule needs is the last valid read row
@@ -594,6 +642,7 @@ align_strip_wide_kernel(const StripArgs args) {
         int h_last = Hl[K - 1], f_last = border_f;
         int up0 = 0;                                        // row above the strip at column -1
         if (ALG == kAlgNW && l == 0 && row0 - 1 >= 0) up0 = AFFINE ? args.open_ref + (row0 - 1) * args.ext_ref : row0 * args.gap_ref;
+        if (BAND && l == 0 && has_top && (unsigned)(-1 - p_lo) < (unsigned)p_w) up0 = (int)top[-1];     // BAND: column c_lo - 1
         int j = -l;
         unsigned code_addr = ring_base | ((unsigned)(-2 * l) & (2u * kStripRingCols - 1u));
         StripRefBytes ref_raw = strip_ring_request(ref_a, ref_b, lane, F);     // columns [0, 64) (each pass starts the ring over)
@@ -604,22 +653,25 @@ align_strip_wide_kernel(const StripArgs args) {
         for (int t = 0; t < steps; ++t) {
             if ((t & 63) == 0) {
                 top_cur = top_next;
-                top_next = (has_top && t + 64 + lane < args.row_dwords) ? top[t + 64 + lane] : 0u;
+                top_next = (has_top && t + 64 + lane < row_dwords) ? top[t + 64 + lane] : 0u;
                 if (AFFINE) {
                     topf_cur = topf_next;
-                    topf_next = (has_top && t + 64 + lane < args.row_dwords) ? top_f[t + 64 + lane] : (unsigned)border_f;
+                    topf_next = (has_top && t + 64 + lane < row_dwords) ? top_f[t + 64 + lane] : (unsigned)border_f;
                 }
                 strip_ring_commit<K>(w.refc, t + lane, F, ref_raw);
                 ref_raw = strip_ring_request(ref_a, ref_b, t + 64 + lane, F);
             }
             const int diag0 = up0;
-            const int above = __builtin_amdgcn_readlane((int)top_cur, t & 63);
+            int above = __builtin_amdgcn_readlane((int)top_cur, t & 63);
+            const bool above_out = BAND && (unsigned)(t - p_lo) >= (unsigned)p_w;       // BAND: not swept by the previous strip
+            if constexpr (BAND) above = above_out ? 0 : above;
             int from_lane = __builtin_amdgcn_update_dpp(0, h_last, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
             asm volatile("" : "+v"(from_lane));
             up0 = l == 0 ? above : from_lane;
             int fup0 = border_f;
             if (AFFINE) {
-                const int above_f = __builtin_amdgcn_readlane((int)topf_cur, t & 63);
+                int above_f = __builtin_amdgcn_readlane((int)topf_cur, t & 63);
+                if constexpr (BAND) above_f = above_out ? 0 : above_f;
                 int f_lane = __builtin_amdgcn_update_dpp(0, f_last, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
                 asm volatile("" : "+v"(f_lane));
                 fup0 = l == 0 ? above_f : f_lane;
@@ -660,6 +712,12 @@ align_strip_wide_kernel(const StripArgs args) {
                         m = lg > ug ? lg : ug;
                         m = d > m ? d : m;
                         code[q] = m == d ? 0u : (m == ug ? 1u : 2u);          // DIAG > UP > LEFT
+                    }
+                    if constexpr (BAND) {
+                        if ((unsigned)(j - win_lo[q]) >= (unsigned)win_w[q]) {      // outside the row's window: H = E = F = 0
+                            m = 0;
+                            if constexpr (AFFINE) f = El[q] = 0;
+                        }
                     }
                     h = m;
                     Hl[q] = m;
@@ -741,7 +799,7 @@ align_strip_wide_kernel(const StripArgs args) {
             out.score = (short)(vmax & 0xFFFF);
             out.pad = (short)((unsigned)vmax >> 16);
             out.read_pos = (short)(strip_pad + p - pad_total);
-            out.ref_pos = (short)(col_t - win_lane);
+            out.ref_pos = (short)(c_lo + col_t - win_lane);
             if (vmax <= 0) {
                 out.read_pos = 0;
                 out.ref_pos = 0;

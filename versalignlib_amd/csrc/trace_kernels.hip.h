@@ -22,6 +22,7 @@
 // reference's "cell == 0 -> START" rule; for NW START is row 0 and column 0 is UP.
 #pragma once
 
+#include "band_window.h"
 #include "dp_kernels.hip.h"
 
 namespace valign {
@@ -80,6 +81,8 @@ struct TraceArgs {
     int wide_score;           // 1: int32 cells -- the end value is EndCell.score (low half) and EndCell.pad (high half)
     int *min_start;           // not null: receives the smallest readStart of the launch (atomicMin; the caller presets R + F) --
                               // the host then copies only the columns from there on out of every row (Engine::align_host)
+    BandShape band;           // traceback_band_kernel: the block band of the strips (band_window.h); each strip's pointer region
+                              // starts at its window's first column, and a step out of the row's window ends the walk (START)
 };
 
 typedef unsigned __attribute__((aligned(1))) u32_any_align;   // global dword access at any byte address
@@ -91,8 +94,9 @@ typedef unsigned __attribute__((aligned(1))) u32_any_align;   // global dword ac
 // (block 0), `ptr_words` the words from there to the end of the group's last block; `half` selects pair A / B of
 // the group.  Pointers may be global or LDS (generic): traceback_kernel walks the HBM scratch, the fused small-batch
 // kernel (align_fill_tag_kernel<..., FUSED>) the copy it keeps in LDS.
-template <bool BYTE_ROWS = false>      // BYTE_ROWS: everything the walk touches sits in LDS (fused kernel) -- explicit LDS reads,
+template <bool BYTE_ROWS = false,     // BYTE_ROWS: everything the walk touches sits in LDS (fused kernel) -- explicit LDS reads,
                                        // one byte store per step (no dword at an odd LDS address)
+          bool BAND = false>           // BAND: banded strips (TraceArgs.band)
 __device__ __forceinline__ int trace_walk(const TraceArgs &a, const unsigned *ptr_pair, long long ptr_words, int half,
                                           const EndCell e, const uint8_t *read, const uint8_t *ref,
                                           uint8_t *row_read, uint8_t *row_ref, short *out) {
@@ -110,6 +114,8 @@ __device__ __forceinline__ int trace_walk(const TraceArgs &a, const unsigned *pt
     unsigned out_r = 0, out_f = 0;         // up to 4 pending output bytes per row, newest in the low byte
     int pending = 0;
     int state = 0;                         // affine only: 0 at H, 1 inside F (gap in the ref), 2 inside E
+    // BAND: the window of the rows from band_row0 on (one block) and the first column of strip band_strip's region
+    int band_row0 = 0x7FFFFFFF, band_lo = 0, band_width = 0, band_strip = -1, strip_lo = 0;
 
     auto base_at = [](const uint8_t *seq, int len, int pos, int &at, unsigned &w) -> unsigned {
         if ((pos >> 2) != at) {
@@ -167,13 +173,28 @@ __device__ __forceinline__ int trace_walk(const TraceArgs &a, const unsigned *pt
         } else {
             int p = i + a.pad_rows;
             long long region = 0;
+            int t = j;
             if (a.strip_rows > 0) {                     // row strips: each has its own pointer region
                 const int strip = p / a.strip_rows;
                 p -= strip * a.strip_rows;
                 region = strip * a.strip_words;
+                if constexpr (BAND) {
+                    if (i < band_row0) {                // (rows only decrease: a new block)
+                        band_row0 = (i + a.band.pad) / a.band.block_rows * a.band.block_rows - a.band.pad;
+                        band_row_window(a.band, i, R, F, band_lo, band_width);
+                    }
+                    if ((unsigned)(j - band_lo) >= (unsigned)band_width) break;     // out of the band: START
+                    if (strip != band_strip) {
+                        int strip_width;
+                        band_strip = strip;
+                        band_rows_window(a.band, strip * a.strip_rows - a.pad_rows, (strip + 1) * a.strip_rows - a.pad_rows - 1, R, F,
+                                         strip_lo, strip_width);
+                    }
+                    t -= strip_lo;
+                }
             }
             const int l = p / K, q = p - l * K;
-            const int t = j + l;
+            t += l;
             const long long wi = region + ((long long)(a.tagged == 2 ? (t >> 2) : (t >> 3)) * kWave + l) * wpb + q;
             if (a.tagged == 2) {
                 const int f4 = code_at(wi, t);          // [3:2] source of H (2 DIAG, 1 F, 0 E), [1] E opened, [0] F opened
@@ -260,10 +281,10 @@ __device__ __forceinline__ int trace_walk(const TraceArgs &a, const unsigned *pt
     return k + 1;                                       // readStart = refStart: where both rows' strings begin
 }
 
-#ifdef VALIGN_TU_ALIGN      // not a template: defined once, in engine_align.hip
+#ifdef VALIGN_TU_ALIGN      // not templates: defined once, in engine_align.hip
 // One lane per pair over the HBM pointer scratch.
-__global__ void __launch_bounds__(256)
-traceback_kernel(const TraceArgs a) {
+template <bool BAND>
+__device__ __forceinline__ void traceback_pairs(const TraceArgs &a) {
     const long long pair = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int R = a.R, F = a.F, AL = R + F, K = a.K, G = a.G;
     int start = AL;
@@ -275,7 +296,7 @@ traceback_kernel(const TraceArgs a) {
         long long ptr_words = ((long long)(a.blocks8 - 1) * kWave + G) * wpb;   // words from there to the end of the group's last block
         if (a.strip_rows > 0) ptr_words += (long long)((R + a.pad_rows) / a.strip_rows - 1) * a.strip_words;   // ... of the last strip
         uint8_t *row_read = a.rows + pair * 2 * AL;
-        start = trace_walk(a, ptr_pair, ptr_words, (int)(pair & 1), a.ends[pair], a.reads + pair * R, a.refs + pair * F, row_read,
+        start = trace_walk<false, BAND>(a, ptr_pair, ptr_words, (int)(pair & 1), a.ends[pair], a.reads + pair * R, a.refs + pair * F, row_read,
                            row_read + AL, a.idx + pair * 4);
     }
     if (a.min_start) {                                  // (uniform) the launch's smallest start: one atomic per wave
@@ -286,6 +307,15 @@ traceback_kernel(const TraceArgs a) {
         }
         if ((threadIdx.x & (kWave - 1)) == 0 && start < AL) atomicMin(a.min_start, start);
     }
+}
+__global__ void __launch_bounds__(256)
+traceback_kernel(const TraceArgs a) {
+    traceback_pairs<false>(a);
+}
+// ... of the banded strips (align_strip_kernel<..., BAND>)
+__global__ void __launch_bounds__(256)
+traceback_band_kernel(const TraceArgs a) {
+    traceback_pairs<true>(a);
 }
 
 // Result rows are right-justified strings behind zeros (650-byte rows whose strings are ~160 bytes for Smith-Waterman
