@@ -1,14 +1,16 @@
 """Every cell-format range rule walked to its edge, and both sides of the edge judged exactly.
 
 Each score and alignment call picks its cell format (f16 / int16 / int32) and its fill kernel from closed-form bounds
-(engine_core.hip: half_float_exact, half_float_unit_exact, check_int16_range, tagged_range_ok, affine_tagged_range_ok;
-engine_align.hip: fill_choice's lane / profile keys, border_bad, the int32 refusal).  A bound one term too loose does not
+(versalignlib_amd/csrc/cell_rules.h: half_float_exact, half_float_unit_exact, int16_range_ok, tagged_range_ok,
+affine_tagged_range_ok, lane_key_ok, prof_key_ok, border_bad, int32_refused; score_gap_form, fill_choice and align_route choose
+with them).  A bound one term too loose does not
 fail: it returns a rounded half or a wrapped short for some inputs only.  So each row of ROWS walks one parameter of one
 rule at a fixed shape and mode, reads what the engine REPORTS it launched (describe / the plugin's log: ran_score_cells,
 ran_align_fill -- not the prediction), finds the last value that runs the narrow form and the first that does not, and
 runs a batch built to reach the bound's extremes at both values against the int32 oracle (cpu_ref ..., wide=True; where
 the reference's int16 would wrap, the score is the value saturated to a short).  Tiny shapes with extreme scorings are
-judged by exhaustive enumeration (tests/enumerate_alignments.py), which shares no code with the oracle."""
+judged by exhaustive enumeration (tests/enumerate_alignments.py), which shares no code with the oracle.
+tests/cell_rules_check.cpp walks the same families over the rules alone, on the CPU, value by value: one transition each."""
 import numpy as np
 import pytest
 
@@ -145,7 +147,7 @@ ROWS = [
     R_("half_float_unit_exact", "score", SW, 150, 500, 1, 12, lambda v: S(v, -1, -3), ("f16",)),
     R_("half_float_unit_exact_slack", "score", SW, 150, 500, 100, 600, lambda v: S(2, -v, -3), ("f16",)),
     R_("half_float_unit_exact_long", "score", SW, 150, 8000, 1, 12, lambda v: S(v, -1, -3), ("f16",), n=24),
-    # check_int16_range: scores (int16 or f16 vs int32 strips), alignments (anything vs the int32 strips)
+    # int16_range_ok: scores (int16 or f16 vs int32 strips), alignments (anything vs the int32 strips)
     R_("int16_range_score", "score", SW, 150, 500, 150, 300, lambda v: S(v, -1, -3), NOT_INT32),
     R_("int16_range_score_abi", "score", SW, 150, 500, 150, 300, lambda v: S(v, -1, -3), NOT_INT32, api="plugin"),
     # ... by read length at match 200: hi = 200 R + 1 > 32000 from R = 160, one unit of the bound visible
@@ -160,7 +162,7 @@ ROWS = [
     R_("int16_range_align_affine_nw_lo", "align", NW, 150, 500, 60, 200, lambda v: S(2, -1, -v, aff=(-v, -v, -v, -v)), NOT_WIDE),
     # border_bad: column 0 of the NW variant, a gap of the whole read (binds where the reference is the short side)
     R_("border_bad", "align", NW, 400, 50, 40, 120, lambda v: S(2, -1, -1, -v), NOT_WIDE),
-    # tagged_range_ok (4 x range, 2-bit tag) and the SW keys: profile key, lane key (4 bits), plain tags
+    # tagged_range_ok (4 x range, 2-bit tag) and the SW keys: prof_key_ok, lane_key_ok (4 bits), plain tags
     R_("prof_key", "align", SW, 150, 500, 1, 20, lambda v: S(v, -1, -3), ("tag_prof_key",)),
     R_("prof_key_mismatch", "align", SW, 150, 500, 200, 300, lambda v: S(1, -v, -3), ("tag_prof_key",)),
     R_("prof_key_gap", "align", SW, 150, 500, 450, 550, lambda v: S(1, -1, -v), ("tag_prof_key",)),
@@ -190,7 +192,7 @@ ROWS = [
     R_("affine_tagged_5bit", "align", SW, 150, 500, 1, 40, lambda v: S(v, -1, -5, aff=(-5, -1, -5, -1)), ("affine_tag_sym",), G=64, K=32),
     # ... |mismatch| < 1000 (SW: the lower bound is one mismatch, 8 lo - 8 >= -28000 allows 3 499)
     R_("affine_tagged_mismatch", "align", SW, 150, 500, 900, 1100, lambda v: S(2, -v, -5, aff=(-5, -1, -5, -1)), ("affine_tag_sym",)),
-    # the fused small-call kernel on both sides of tagged_range_ok(alg, 256): 1 000 pairs of 64 x 128 through the ABI
+    # the fused small-call kernel (align_route: Fused) on both sides of tagged_range_ok(alg, 256): 1 000 pairs of 64 x 128 through the ABI
     R_("fused", "align", SW, 64, 128, 60, 200, lambda v: S(v, -1, -3), ("fused_tag",), n=1000, api="plugin"),
     R_("fused", "align", NW, 64, 128, 60, 200, lambda v: S(v, -1, -1), ("fused_tag",), n=1000, api="plugin"),
 ]
@@ -199,12 +201,12 @@ ROWS = [
 # The transitions each rule puts at its row's shape (last narrow value, first other one), worked out from the bound:
 # a rule whose edge moves -- loosened or tightened by one unit where the shape makes that unit visible -- fails its row.
 #
-# Clauses with no row, and why:
+# Clauses (of the rules in cell_rules.h, by function name) with no row, and why:
 #   unreachable -- implied by a stricter clause of the same rule for every input:
 #     half_float_exact SW  slack <= 1024          (top + 2 slack <= 2048, top >= 0)
 #     half_float_exact NW  span < 30000           (centre + 3 slack <= 2048 keeps span <= 4096)
 #     half_float_unit_exact  slack < 512          (top + 2 slack < 1024)
-#     affine_tagged_range_ok SW  8 hi + 8 <= 32000 (the lane key (hi + 1) << 4 binds first)
+#     affine_tagged_range_ok SW  8 hi + 8 <= 32000 (its own lane-key clause (hi + 1) << 4 binds first)
 #     affine_tagged_range_ok NW  |ext_read| (F + 1) <= 3500  (the lower bound's (R + F + 2) |ext| binds first)
 #   reachable, not walked -- they bind only at shapes of at most a few rows:
 #     tagged_range_ok |match| < 2000 (min(R, F) <= 3), affine_tagged_range_ok |match| < 1000 (min(R, F) <= 1 for SW,

@@ -2,6 +2,8 @@
 # CPU-side sanitizer run ("race detection / sanitizers"; the GPU pool offers none):
 #   1. the host-only half of the plugin's host-pointer path (versalignlib_amd/csrc/host_pipeline.h: worker pool,
 #      gather, scatter) as a stand-alone program under -fsanitize=thread and under -fsanitize=address,undefined;
+#      and the engine's cell-range rules and path choice (versalignlib_amd/csrc/cell_rules.h, tests/cell_rules_check.cpp)
+#      under -fsanitize=address,undefined;
 #   2. libvalignhost.so, valign-bench and the oracle (oracle/cpu_ref.c) built with -fsanitize=address,undefined
 #      into build/sanitize/, and the whole CPU test-suite run against THOSE (python gets the runtimes preloaded).
 # Usage: tools/sanitize.sh [pytest args...]      (also: make sanitize)
@@ -18,6 +20,9 @@ TSAN_OPTIONS="halt_on_error=1 second_deadlock_stack=1" "$OUT/host_pipeline_tsan"
 echo "== host_pipeline.h under AddressSanitizer + UBSan"
 g++ -std=c++17 $SAN -pthread -I"$CS" "$R/tests/host_pipeline_check.cpp" -o "$OUT/host_pipeline_asan"
 ASAN_OPTIONS="detect_leaks=1" "$OUT/host_pipeline_asan"
+echo "== cell_rules.h under AddressSanitizer + UBSan"
+g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/cell_rules_check.cpp" -o "$OUT/cell_rules_asan"
+"$OUT/cell_rules_asan"
 
 echo "== libvalignhost.so, valign-bench, libcpuref.so with $SAN"
 g++ -std=c++14 $SAN -fPIC -shared -Wall -pthread -I"$R/include" "$CS/valign_host.cpp" -o "$OUT/libvalignhost.so" -ldl

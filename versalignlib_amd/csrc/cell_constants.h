@@ -1,0 +1,37 @@
+// cell_constants.h -- what the kernels' template arguments and the host's choice of them (cell_rules.h) both name: the scoring
+// of an engine, the algorithms, the gap forms of the score kernels and the fill kernels of a geometry.  No HIP here.
+#pragma once
+
+namespace valign {
+
+struct Scoring {
+    int match = 2, mismatch = -1, gap_read = -3, gap_ref = -3;
+    bool affine = false;
+    int open_read = -3, ext_read = -3, open_ref = -3, ext_ref = -3;
+};
+
+constexpr int kAlgSW = 0;
+constexpr int kAlgNW = 1;
+
+// GAPS of score_kernel selects the recurrence (dp_kernels.hip.h describes each form)
+constexpr int kGapLinear = 0, kGapSym = 1, kGapAffine = 2, kGapAffineSym = 3;       // int16 cells
+constexpr int kGapAffineSymF16 = 4, kGapAffineF16 = 5, kGapSymF16 = 6;              // the same recurrences on half floats
+
+// alignment fill kernels of a geometry, by what the engine selects (fill_choice, cell_rules.h)
+enum FillKernel {
+    kFillLinear = 0,        // equality-test pointers, two gap scores            (full geometries only)
+    kFillLinearSym,         // ... one shared gap score                           (full)
+    kFillAffine,            // affine, equality tests                             (full)
+    kFillSse,               // SSE2 / AVX2 tie-breaks, equality tests             (full)
+    kFillTag,               // pointer tagged into the cell; SW: per-row arg-max  (NW: every geometry; SW: full)
+    kFillTagKey,            // ... SW with one end-cell key per lane              (every geometry)
+    kFillAffineSym,         // affine with symmetric scores, equality tests       (full)
+    kFillAffineTag,         // affine, tagged cells, different scores per direction (full)
+    kFillAffineTagSym,      // ... symmetric scores                               (every geometry)
+    kFillSseTag,            // SSE tie-breaks, tagged; SW: per-row arg-max        (full)
+    kFillSseTagKey,         // ... SW with the lane key                           (full)
+    kFillTagProfKey,        // SW, the end-cell key rides in the query profile    (every geometry)
+    kFillKernels
+};
+
+}  // namespace valign

@@ -1,0 +1,239 @@
+// cell_rules.h -- the closed-form bounds that pick the cell format (f16 / int16 / int32), the fill kernel and the path of a
+// score or alignment call, each defined once; integer arithmetic on (scoring, shape, a few switches), no HIP.  The engine
+// units include it and tests/cell_rules_check.cpp exercises it on the CPU (as band_window.h and host_pipeline.h are).  A bound
+// one term too loose does not fail: it returns a wrapped short or a rounded half for some inputs only
+// (tests/test_gpu_range_edges.py walks each rule to its edge on the GPU).
+#pragma once
+
+#include <algorithm>
+#include <cstdlib>
+#include <stdexcept>
+#include <string>
+
+#include "cell_constants.h"
+
+namespace valign {
+
+// What every rule reads of an engine (Engine::rule_inputs): the scoring, the shape, traceback_policy = 1 and the debug switches
+struct RuleInputs {
+    Scoring sc;
+    int R = 0, F = 0;
+    bool sse_policy = false;
+    bool no_sym = false, no_tag = false, no_f16 = false, no_prof_key = false;
+};
+
+// int16 DP cells: the reference wraps silently.  Scores and alignments switch to int32 cells on the strip path where they could.
+// The NW score kernels keep cell (p, j) plus -g_ref * p - g_read * j (g: gap / extension scores, <= 0): the most that
+// adds over a sweep of `rows` padded rows and F columns.
+inline long long nw_tilt_span(const Scoring &sc, int rows, int F) {
+    const long long per_row = -(long long)(sc.affine ? sc.ext_ref : sc.gap_ref);
+    const long long per_col = -(long long)(sc.affine ? sc.ext_read : sc.gap_read);
+    return per_row * (rows + 1) + per_col * (F + 1);
+}
+
+// Every cell of an R x F sweep and everything added to it stays an integer of magnitude <= 2048:
+// exact in half floats (kGapAffineSymF16 / kGapAffineF16).  SW cells are >= 0; cells of the NW
+// variant are bounded below by the cheaper border path (as in int16_range_ok).
+// NW: plus what the kernels' tilted frame adds to a cell of a sweep of `rows` padded rows (score_kernel).
+inline bool half_float_exact(const Scoring &sc, int alg, int R, int F, int rows) {
+    const long long top = (long long)std::min(R, F) * std::max({sc.match, sc.mismatch, 0});
+    long long slack = std::max({std::abs(sc.match), std::abs(sc.mismatch), std::abs(sc.open_read),
+                                std::abs(sc.ext_read), std::abs(sc.open_ref), std::abs(sc.ext_ref)});
+    if (alg == kAlgSW) return top + 2 * slack <= 2048 && slack <= 1024;
+    // NW frame: H' of cell (p, j) is at least what its row or its column adds (the border path along the other axis
+    // is free there) less one opening, at most top + the far corner's tilt; E' / F' sit at most one opening below H'.
+    // The kernel centres that range on zero (nw_frame_centre, same formula).
+    if (!sc.affine) slack = std::max<long long>(slack, std::max(std::abs(sc.gap_read), std::abs(sc.gap_ref)));
+    const long long span = nw_tilt_span(sc, rows, F);
+    const long long centre = (top + span) / 2;
+    return span < 30000 && (top + span - centre) + 3 * slack <= 2048 && centre + 3 * slack <= 2048 && slack <= 512;
+}
+
+// kGapSymF16 for Smith-Waterman scales every value by 2^-10 and floors with the [0, 1] clamp of the
+// packed add: cells must stay below 1024, scores be integers of magnitude < 1024
+inline bool half_float_unit_exact(const Scoring &sc, int R, int F) {
+    const long long top = (long long)std::min(R, F) * std::max({sc.match, sc.mismatch, 0});
+    const long long slack = std::max({std::abs(sc.match), std::abs(sc.mismatch), std::abs(sc.gap_read), std::abs(sc.gap_ref)});
+    return top + 2 * slack < 1024 && slack < 512;
+}
+
+// Every cell of the call stays inside int16.  score_path: score_alignments (the NW variant's tilted frame counts on the
+// register sweep: `tilt_rows` padded rows, the tallest plan a call may take); long_mode: the engine's plan is the long-read one
+inline bool int16_range_ok(const RuleInputs &in, int alg, bool score_path, bool long_mode, int tilt_rows) {
+    const Scoring &sc = in.sc;
+    long long hi = (long long)std::min(in.R, in.F) * std::max(sc.match, 0) + 1;
+    if (score_path && alg == kAlgNW && !long_mode) hi += nw_tilt_span(sc, tilt_rows, in.F);
+    const int worst_gap = std::min({sc.gap_read, sc.gap_ref, sc.open_read, sc.open_ref, sc.ext_read, sc.ext_ref, 0});
+    // SW cells are >= 0; NW-variant score cells are bounded below by the cheaper border path
+    long long lo = alg == kAlgSW ? (long long)std::min(sc.mismatch, 0) + worst_gap
+                                 : (long long)(std::min(in.R, in.F) + 2) * std::min(worst_gap, std::min(sc.mismatch, 0));
+    // NW-variant alignments with affine gaps (plain frame, "minus infinity" = -16384): row 0 is free, so every H is at least a
+    // gap straight down from it -- open_ref + (R - 1) ext_ref -- and E / F lie at most one opening below an H; a candidate
+    // adds one mismatch.  (The product above charged every step an opening: -50 010 for 10 kbp reads at -5 / -1, whose cells
+    // never go below -10 010.)
+    if ((!score_path || long_mode) && sc.affine && alg == kAlgNW)       // (the long-read score kernels: the same plain frame)
+        lo = (long long)std::min(sc.open_ref, 0) + (long long)in.R * std::min(sc.ext_ref, 0) + std::min({sc.open_read, sc.open_ref, 0}) +
+             std::min(sc.mismatch, 0);
+    return !(hi > 32000 || lo < -32000 || (sc.affine && alg == kAlgNW && lo < -15000));
+}
+
+// Column 0 of the NW variant with linear gaps leaves int16: a gap of the whole read, (R + 1) gap_ref (affine: open_ref +
+// R ext_ref, which int16_range_ok covers)
+inline bool border_bad(const RuleInputs &in, int alg) {
+    return alg == kAlgNW && !in.sc.affine && (long long)(in.R + 1) * std::min(in.sc.gap_ref, 0) < -32000;
+}
+
+// int32 cells (align_strip_wide_kernel) serve every mode; only scores so large that (R + F) * |score| nears 2^28 are refused
+inline bool int32_refused(const RuleInputs &in) {
+    const Scoring &sc = in.sc;
+    const long long worst = std::max({std::abs((long long)sc.match), std::abs((long long)sc.mismatch),
+                                      std::abs((long long)(sc.affine ? sc.open_read : sc.gap_read)), std::abs((long long)(sc.affine ? sc.open_ref : sc.gap_ref)),
+                                      sc.affine ? std::abs((long long)sc.ext_read) : 0ll, sc.affine ? std::abs((long long)sc.ext_ref) : 0ll});
+    return (long long)(in.R + in.F + 2) * worst >= (1ll << 28);
+}
+
+// align_fill_tag_kernel keeps 4 * cell + tag in int16.  rows: padded rows of the sweep that would run
+inline bool tagged_range_ok(const RuleInputs &in, int alg, int rows) {
+    const Scoring &sc = in.sc;
+    long long hi = (long long)std::min(in.R, in.F) * std::max(sc.match, 0) + 1;
+    if (alg == kAlgNW && !in.sse_policy)           // the kernel's tilted frame: every cell plus -gap_ref * p - gap_read * j
+        hi += (long long)-sc.gap_ref * (rows + 1) + (long long)-sc.gap_read * (in.F + 1);
+    const int worst = std::min({sc.gap_read, sc.gap_ref, sc.mismatch, 0});
+    const long long lo = alg == kAlgSW ? worst : (long long)(in.R + in.F + 2) * worst;      // H(i,j) >= i gf + j gr
+    if (alg == kAlgSW && !in.sse_policy && sc.gap_ref >= 0) return false;
+    return 4 * hi + 4 <= 32000 && 4 * lo - 4 >= -32000 && std::abs(sc.match) < 2000 && std::abs(sc.mismatch) < 2000;
+}
+
+// align_fill_affine_tag_kernel keeps 8 * cell + tag in int16; SW needs open scores < 0 (the tag rides on the
+// open constant) and, for the lane key, value << 4 (5) in range
+inline bool affine_tagged_range_ok(const RuleInputs &in, int alg, int geo_rows, int K) {
+    const Scoring &sc = in.sc;
+    long long hi = (long long)std::min(in.R, in.F) * std::max(sc.match, 0) + 1;
+    const int worst = std::min({sc.open_read, sc.open_ref, sc.ext_read, sc.ext_ref, sc.mismatch, 0});
+    // NW: every cell is at least the path "one gap up, one gap left"; E / F sit one open below H
+    long long lo = alg == kAlgSW ? worst
+                                 : 2ll * (std::min(sc.open_read, 0) + std::min(sc.open_ref, 0)) +
+                                       (long long)(in.R + in.F + 2) * std::min({sc.ext_read, sc.ext_ref, 0}) + worst;
+    if (alg == kAlgNW) {        // the kernel's tilted frame: cell (p, j) carries - ext_ref * p - ext_read * j on top
+        const long long rows = (long long)geo_rows + 1, cols = in.F + 1;
+        hi += std::max(0, -sc.ext_ref) * rows + std::max(0, -sc.ext_read) * cols;
+        lo += std::min(0, -sc.ext_ref) * rows + std::min(0, -sc.ext_read) * cols;
+        if (std::abs((long long)sc.ext_ref) * rows > 3500 || std::abs((long long)sc.ext_read) * cols > 3500) return false;
+    }
+    if (alg == kAlgSW && (sc.open_read >= 0 || sc.open_ref >= 0)) return false;
+    const int key_bits = K <= 16 ? 4 : 5;
+    if (alg == kAlgSW && ((hi + 1) << key_bits) > 32000) return false;
+    return 8 * hi + 8 <= 32000 && 8 * lo - 8 >= -28000 && std::abs(sc.match) < 1000 && std::abs(sc.mismatch) < 1000;
+}
+
+// SW, tagged cells: one (value, row) key per lane instead of a first-arg-max per row where value << 4 (5 bits of row for more
+// than 16 rows per lane) still fits int16
+inline bool lane_key_ok(const RuleInputs &in, int K) {
+    return (((long long)std::min(in.R, in.F) * std::max(in.sc.match, 0) + 1) << (K <= 16 ? 4 : 5)) <= 32000;
+}
+// ... and where 64x the cell range fits (K <= 16), the key rides in the query profile instead of being computed
+inline bool prof_key_ok(const RuleInputs &in, int K) {
+    const Scoring &sc = in.sc;
+    return !in.sse_policy && !in.no_prof_key && K <= 16 && (((long long)std::min(in.R, in.F) * std::max(sc.match, 0) + 2) << 6) <= 32000 &&
+           64ll * std::max(std::abs(sc.gap_read), std::abs(sc.gap_ref)) < 32000 && 64ll * std::abs(sc.mismatch) < 16000;
+}
+
+// The gap form (kGap*) a register-sweep score launch of R x F on `rows` padded rows runs: what launch_score launches and what
+// describe() predicts (score_cells).
+inline int score_gap_form(const RuleInputs &in, int alg, int R, int F, int rows) {
+    const Scoring &sc = in.sc;
+    if (sc.affine) {
+        const bool sym = sc.open_read == sc.open_ref && sc.ext_read == sc.ext_ref && !in.no_sym;
+        if (!in.no_f16 && half_float_exact(sc, alg, R, F, rows)) return sym ? kGapAffineSymF16 : kGapAffineF16;
+        return sym ? kGapAffineSym : kGapAffine;
+    }
+    const int gaps = (sc.gap_read == sc.gap_ref && !in.no_sym) ? kGapSym : kGapLinear;
+    // (the NW variant's tilted frame has no gap constants left: its half-float kernel serves gap_read != gap_ref too)
+    if ((gaps == kGapSym || alg == kAlgNW) && !in.no_f16 &&
+        (alg == kAlgNW ? half_float_exact(sc, alg, R, F, rows) : half_float_unit_exact(sc, R, F)))
+        return kGapSymF16;
+    return gaps;
+}
+inline bool gap_form_f16(int gaps) { return gaps == kGapSymF16 || gaps == kGapAffineSymF16 || gaps == kGapAffineF16; }
+
+// Which fill kernel an alignment call of this mode takes on a G x K geometry, and what its pointer stream looks like.
+struct FillChoice {
+    int kernel = 0;                 // FillKernel
+    bool affine_tagged = false, tagged = false;
+};
+inline FillChoice fill_choice(const RuleInputs &in, int alg, int G, int K) {
+    const Scoring &sc = in.sc;
+    FillChoice c;
+    const int rows = G * K;
+    // affine gaps with the traceback information tagged into the cells (4-bit codes, 4-step blocks)
+    c.affine_tagged = sc.affine && !in.sse_policy && !in.no_tag && affine_tagged_range_ok(in, alg, rows, K);
+    // linear gaps: the pointer rides in the low bits of the cell where 4x the cell range still fits int16 (and, for SW,
+    // gap_ref < 0); otherwise the equality-test kernels (both tie-break policies)
+    c.tagged = !sc.affine && !in.no_tag && tagged_range_ok(in, alg, rows);
+    const bool lane_key = c.tagged && alg == kAlgSW && lane_key_ok(in, K);
+    const bool prof_key = lane_key && prof_key_ok(in, K);
+    const bool affine_sym = sc.affine && sc.open_read == sc.open_ref && sc.ext_read == sc.ext_ref && !in.no_sym;
+    if (prof_key) c.kernel = kFillTagProfKey;
+    else if (c.tagged) c.kernel = in.sse_policy ? (lane_key ? kFillSseTagKey : kFillSseTag) : (lane_key ? kFillTagKey : kFillTag);
+    else if (in.sse_policy) c.kernel = kFillSse;
+    else if (sc.affine) c.kernel = c.affine_tagged ? (affine_sym ? kFillAffineTagSym : kFillAffineTag) : (affine_sym ? kFillAffineSym : kFillAffine);
+    else c.kernel = (sc.gap_read == sc.gap_ref && !in.no_sym) ? kFillLinearSym : kFillLinear;
+    return c;
+}
+
+// ---- the path of an alignment call ----
+enum class AlignRoute { Fused, Register, Strip, StripBand, StripWide, StripWideBand };
+
+// What the route reads of the engine beyond the rule inputs (Engine::align_route)
+struct RouteFacts {
+    bool banded = false;            // band_alignments with a band_width
+    bool wide_align = false;        // debug switch: int32 cells always
+    bool read_strips = false;       // the alignment plan is the long-read one, or an unforced read of more than 1 024 rows
+    bool fused_off = false;         // debug switch no_fused, or a forced geometry
+    bool small_call = false;        // align_host's direct call: the one place the fused kernel is tried
+    int fused_rows = 0;             // padded rows of the tallest fused geometry
+};
+
+// The cascade, once: refusals, then int32 cells, the band, row strips, the fused kernel for a small call, the register sweep.
+// tagged_range_ok is asked about two different sweeps on purpose: Fused is decided before a fused geometry is picked, so it
+// tests `fused_rows` (the tallest one: whichever geometry align_fused then takes is in range); the register path tests the
+// rows of the plan it launches (fill_choice).
+inline AlignRoute align_route(const RuleInputs &in, int alg, const RouteFacts &f) {
+    if (f.banded && alg != kAlgSW) throw std::runtime_error("band_alignments applies to Smith-Waterman alignments only");
+    if (f.banded && in.sse_policy)
+        throw std::runtime_error("band_alignments needs traceback_policy = 0 (no banded SSE/AVX tie-breaks)");
+    // Alignments whose cells leave int16 (the reference's shorts would wrap): int32 cells on the row-strip path, one pair per
+    // register (align_strip_wide_kernel) -- every mode
+    if (border_bad(in, alg) || !int16_range_ok(in, alg, false, false, 0) || f.wide_align) {
+        if (int32_refused(in))
+            throw std::runtime_error("shape x scoring can leave the int32 range of the DP cells (read_length " + std::to_string(in.R) +
+                                     ", ref_length " + std::to_string(in.F) + ")");
+        return f.banded ? AlignRoute::StripWideBand : AlignRoute::StripWide;
+    }
+    // banded SW alignments: row strips that sweep the band windows (banded cells never exceed unbanded ones: the range
+    // decision above stands)
+    if (f.banded) return AlignRoute::StripBand;
+    if (f.read_strips) return AlignRoute::Strip;
+    if (in.sse_policy && in.sc.affine)
+        throw std::runtime_error("traceback_policy = 1 (SSE/AVX tie-breaks) exists for the linear gap model only");
+    // fill + traceback in one launch: linear gaps, default tie-breaks, plain tagged cells
+    if (f.small_call && !f.fused_off && !in.sc.affine && !in.sse_policy && !in.no_tag && tagged_range_ok(in, alg, f.fused_rows)) return AlignRoute::Fused;
+    return AlignRoute::Register;
+}
+
+// align_host sizes its chunks for strips where the read or the band asks for them; int32 cells alone (a short read whose
+// cells leave int16) keep the register path's chunks
+inline bool strip_chunks(AlignRoute r, const RouteFacts &f) {
+    return r == AlignRoute::Strip || r == AlignRoute::StripBand || r == AlignRoute::StripWideBand || (r == AlignRoute::StripWide && f.read_strips);
+}
+
+// describe()'s name of what an alignment call launched (ran_align_fill); fill_kernel: the register path's FillKernel
+inline const char *ran_fill_name(AlignRoute r, int fill_kernel = -1) {
+    static const char *const names[kFillKernels] = {"linear", "linear_sym", "affine", "sse", "tag", "tag_key", "affine_sym",
+                                                    "affine_tag", "affine_tag_sym", "sse_tag", "sse_tag_key", "tag_prof_key"};
+    static const char *const routes[] = {"fused_tag", nullptr, "strip", "strip_band", "strip_wide", "strip_wide_band"};     // by AlignRoute
+    if (r != AlignRoute::Register) return routes[(int)r];
+    return fill_kernel >= 0 && fill_kernel < kFillKernels ? names[fill_kernel] : "none";
+}
+
+}  // namespace valign

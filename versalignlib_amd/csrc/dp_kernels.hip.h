@@ -49,6 +49,8 @@
 
 #include <type_traits>
 
+#include "cell_constants.h"
+
 namespace valign {
 
 typedef short s16x2 __attribute__((ext_vector_type(2)));
@@ -57,8 +59,6 @@ typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kWave = 64;
 constexpr int kWaveLanes = 64;
-constexpr int kAlgSW = 0;
-constexpr int kAlgNW = 1;
 constexpr int kCodePad = 72;          // columns of zero-slab codes before column 0 and after column F-1
 constexpr short kNegInf = -16384;   // "minus infinity" of the affine NW borders (oracle: NEG_INF)
 
@@ -431,26 +431,21 @@ __device__ __forceinline__ void fetch_profile(unsigned addr_a, unsigned addr_b, 
 // 13.54 ms, half-float affine 11.47 -> 12.14 ms, linear 7.19 -> 8.66 ms: every LDS return writes a full wave of VGPRs
 // whatever its width.  The code is gone; DESIGN.md section 3 keeps the numbers.)
 
-// GAPS selects the recurrence: kGapLinear (two gap scores), kGapSym (linear with
-// gap_read == gap_ref: one subtract serves both neighbours), kGapAffine (Gotoh extension).
-constexpr int kGapLinear = 0;
-constexpr int kGapSym = 1;
-constexpr int kGapAffine = 2;
-constexpr int kGapAffineSym = 3;   // affine with open_read == open_ref and ext_read == ext_ref
-// The same recurrence as kGapAffineSym on packed half floats: every value is an
+// GAPS selects the recurrence (the constants: cell_constants.h): kGapLinear (two gap scores), kGapSym (linear with
+// gap_read == gap_ref: one subtract serves both neighbours), kGapAffine (Gotoh extension), kGapAffineSym (affine with
+// open_read == open_ref and ext_read == ext_ref).
+// kGapAffineSymF16: the same recurrence as kGapAffineSym on packed half floats: every value is an
 // integer of magnitude <= 2048, which fp16 represents exactly, and gfx950's v_pk_maximum3_f16
 // takes three operands -- h = max3(diag + S, E, F), E = max3(E - ext, H - open, 0) (which floors the
 // whole SW cell at zero) and the SW maximum tracking two rows at a time: 8.5 instead of 10 packed
 // instructions per register (NW variant, tilted frame: 6 instead of 7, gap matrices start at a real -inf).  The
 // engine picks it when shape x scoring stays inside +-2048.
-constexpr int kGapAffineSymF16 = 4;
-constexpr int kGapAffineF16 = 5;      // half floats with four different open / extend scores: 9.5 instead of 11
-// Linear gaps with gap_read == gap_ref on half floats.  NW variant: h = max3(diag + S', left, up) in the tilted
+// kGapAffineF16: half floats with four different open / extend scores: 9.5 instead of 11
+// kGapSymF16: linear gaps with gap_read == gap_ref on half floats.  NW variant: h = max3(diag + S', left, up) in the tilted
 // frame (score_kernel) -- perm, add, max3: 3 packed instructions per register.  Smith-Waterman needs the zero
 // floor: there every value is scaled by 2^-10 (exact for integers below 1024), which turns the floor into the
 // hardware clamp of v_pk_add_f16 -- max(h + g, 0) is ONE instruction, and a register pair (h, max(h + g, 0))
 // per cell gives h = max3(diag + S, left', up'), left' / up' being the clamped registers: 4 per register.
-constexpr int kGapSymF16 = 6;
 
 constexpr int kTrackAll = 0, kTrackNone = 1, kTrackPair = 2;   // see score_kernel's step
 

@@ -1,7 +1,8 @@
 // engine.hip.h -- the host side of libHIPKernel.so: one Engine per (device, read_length, ref_length, scoring).
 //
 // The class is declared here; its parts are separate translation units, compiled in parallel and testable apart:
-//   engine_core.hip ..... construction, launch-plan selection (cost model), cell-range checks, staging, describe()
+//   engine_core.hip ..... construction, launch-plan selection (cost model), staging, describe()
+//   cell_rules.h ........ the cell-range rules and the choice of gap form, fill kernel and alignment path (pure, CPU-tested)
 //   engine_score.hip .... score_alignments: register-sweep launches, the host-pointer chunk pipeline, 4-bit class
 //                         unpacking, length-sorted batches (reference: DefaultKernel.cpp:52-202)
 //   engine_long.hip ..... long reads: row strips (score_long_kernel) and the banded block chain (score_band_kernel)
@@ -31,6 +32,8 @@
 #include <thread>
 #include <vector>
 
+#include "align_parts.h"
+#include "cell_rules.h"
 #include "hip_handles.h"
 #include "host_pipeline.h"
 #include "kernel_instances.hip.h"
@@ -42,35 +45,12 @@
 
 namespace valign {
 
-struct Scoring {
-    int match = 2, mismatch = -1, gap_read = -3, gap_ref = -3;
-    bool affine = false;
-    int open_read = -3, ext_read = -3, open_ref = -3, ext_ref = -3;
-};
-
 // The per-geometry kernels are compiled in kernel_part.hip (one object per part, in parallel)
 #define VALIGN_DECLARE_FULL(G, K) VALIGN_FAST_KERNELS(extern template, G, K) VALIGN_FALLBACK_KERNELS(extern template, G, K)
 #define VALIGN_DECLARE_FAST(G, K) VALIGN_FAST_KERNELS(extern template, G, K)
 VALIGN_ALL_PARTS(VALIGN_DECLARE_FULL, VALIGN_DECLARE_FAST)
 #undef VALIGN_DECLARE_FULL
 #undef VALIGN_DECLARE_FAST
-
-// alignment fill kernels of a geometry, by what the engine selects (Engine::fill_kernel_index)
-enum FillKernel {
-    kFillLinear = 0,        // equality-test pointers, two gap scores            (full geometries only)
-    kFillLinearSym,         // ... one shared gap score                           (full)
-    kFillAffine,            // affine, equality tests                             (full)
-    kFillSse,               // SSE2 / AVX2 tie-breaks, equality tests             (full)
-    kFillTag,               // pointer tagged into the cell; SW: per-row arg-max  (NW: every geometry; SW: full)
-    kFillTagKey,            // ... SW with one end-cell key per lane              (every geometry)
-    kFillAffineSym,         // affine with symmetric scores, equality tests       (full)
-    kFillAffineTag,         // affine, tagged cells, different scores per direction (full)
-    kFillAffineTagSym,      // ... symmetric scores                               (every geometry)
-    kFillSseTag,            // SSE tie-breaks, tagged; SW: per-row arg-max        (full)
-    kFillSseTagKey,         // ... SW with the lane key                           (full)
-    kFillTagProfKey,        // SW, the end-cell key rides in the query profile    (every geometry)
-    kFillKernels
-};
 
 // One compiled (G, K) geometry with its kernel variants.
 struct Geometry {
@@ -329,13 +309,6 @@ public:
     void score_long_device(int alg, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int16_t *d_scores,
                            hipStream_t stream, bool wide);
 
-    // align_fill_affine_tag_kernel keeps 8 * cell + tag in int16; SW needs open scores < 0 (the tag rides on the
-    // open constant) and, for the lane key, value << 4 (5) in range
-    bool affine_tagged_range_ok(int alg, int rows, int K) const;
-
-    // align_fill_tag_kernel keeps 4 * cell + tag in int16
-    bool tagged_range_ok(int alg, int rows) const;
-
     // The cell format score_alignments is PREDICTED to compute in for this mode: a device-resident call of n pairs (n <= 0:
     // a large call) at the engine's full shape.  What a call really launched is ran_score_cells(): the host pipeline's
     // chunks may be small enough for the latency plan, and length-sorted batches sweep each length class on a plan of its own.
@@ -348,27 +321,12 @@ public:
     const char *ran_align_fill() const { return ran_align_fill_; }
     std::string ran_kernels() const;
 
-    // Every cell of an R x F sweep and everything added to it stays an integer of magnitude <= 2048:
-    // exact in half floats (kGapAffineSymF16 / kGapAffineF16).  SW cells are >= 0; cells of the NW
-    // variant are bounded below by the cheaper border path (as in check_int16_range).
-    // NW: plus what the kernels' tilted frame adds to a cell of a sweep of `rows` padded rows (score_kernel).
-    bool half_float_exact(int alg, int R, int F, int rows) const;
-
-    // kGapSymF16 for Smith-Waterman scales every value by 2^-10 and floors with the [0, 1] clamp of the
-    // packed add: cells must stay below 1024, scores be integers of magnitude < 1024
-    bool half_float_unit_exact(int R, int F) const;
-
-    // int16 DP cells: the reference wraps silently.  Scores switch to int32 cells on the strip path
-    // where they could; alignments (int16 only) are refused.
-    // The NW score kernels keep cell (p, j) plus -g_ref * p - g_read * j (g: gap / extension scores, <= 0): the most that
-    // adds over a sweep of `rows` padded rows and F columns.
-    long long nw_tilt_span(int rows, int F) const;
-    int widest_sweep_rows() const;
-
-    bool int16_range_ok(int alg) const;
-
-    // score_path: score_alignments' register sweep (the NW variant's tilted frame counts)
-    void check_int16_range(int alg, bool score_path = false) const;
+    // What the pure rules of cell_rules.h read of this engine
+    RuleInputs rule_inputs() const { return RuleInputs{sc_, R_, F_, sse_policy_, no_sym_, no_tag_, no_f16_, no_prof_key_}; }
+    // score_alignments at the engine's full shape stays inside int16 cells (int16_range_ok with this engine's plans: the
+    // NW variant's tilt over the tallest register sweep a call may take)
+    bool score_int16_ok(int alg) const;
+    bool score_wide_cells(int alg) const { return score_width_ == 32 || (score_width_ == 0 && !score_int16_ok(alg)); }
 
     // Host pointers in, host scores out.  Chunked over kSlots pinned slots, each with its own
     // stream: while the kernel of chunk c runs, chunk c+1 crosses PCIe and the host threads gather
@@ -405,11 +363,6 @@ public:
         uint8_t *packed;            // ... and the rows, packed to their columns from there on, go here (compact_rows_kernel)
     };
     hipEvent_t trace_done(int region) const { return trace_done_[region].get(); }
-    struct FillChoice {
-        int kernel = 0;                 // FillKernel
-        bool affine_tagged = false, tagged = false;
-    };
-    FillChoice fill_choice(int alg, const Geometry &geo) const;
     const LaunchPlan &align_plan_for(int alg, FillChoice &choice);
     // The plan compute_alignments starts from: the engine's own -- unless that is the long-read one only because the score
     // kernels prefer it (a reference that starves LDS) while the read fits a register sweep with two waves per CU or so:
@@ -428,15 +381,19 @@ public:
 
     void ensure_trace_stream();
 
-    // Fill + traceback of a small batch in one launch (linear gaps, default tie-breaks, tagged cells): false when the
-    // shape / scoring has no fused kernel (the caller takes the three-kernel path).
+    // What align_route (cell_rules.h: the path of an alignment call) reads of this engine.  small_call: the direct call of
+    // align_host, which may take the fused kernel
+    RouteFacts route_facts(bool small_call) const;
+
+    // Fill + traceback of a small batch in one launch (AlignRoute::Fused): false when no fused geometry holds the shape's
+    // pointer stream in LDS (the caller takes the three-kernel path).
     bool align_fused(int alg, long long n, const uint8_t *d_reads, const uint8_t *d_refs, uint8_t *d_rows, short *d_idx,
                      hipStream_t stream);
 
     // Reads beyond one register sweep: row strips of 64 * K rows, one launch per strip in stream order, boundary
     // rows ping-pong through HBM, one pointer region per strip, then the same traceback kernel (strip_kernels.hip.h).
-    // Linear or affine gaps, Default tie-breaks, int16 cells (the reference's; where they would wrap the call is refused
-    // by check_int16_range above instead of wrapping silently).
+    // Linear or affine gaps, Default tie-breaks, int16 cells (the reference's; where they would wrap, align_route
+    // takes the int32 cells instead of wrapping silently).
     // band: banded SW alignments (align_strip_kernel<..., BAND>: each strip sweeps its rows' band windows only).
     void align_strips_device(int alg, long long n, const uint8_t *d_reads, const uint8_t *d_refs, uint8_t *d_rows,
                              short *d_idx, hipStream_t stream, bool wide = false, bool band = false);

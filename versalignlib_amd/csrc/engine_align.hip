@@ -77,50 +77,27 @@ constexpr FusedGeometry make_fused() {
 static const FusedGeometry kFusedGeometries[] = {make_fused<8, 4>(), make_fused<16, 4>(), make_fused<32, 2>(), make_fused<16, 8>(),
                                                  make_fused<32, 4>(), make_fused<16, 10>(), make_fused<32, 8>(), make_fused<64, 4>()};
 
-// Which fill kernel a call of this mode takes on geometry `geo`, and what its pointer stream looks like.
-Engine::FillChoice Engine::fill_choice(int alg, const Geometry &geo) const {
-    FillChoice c;
-    const int rows = geo.G * geo.K;
-    // affine gaps with the traceback information tagged into the cells (4-bit codes, 4-step blocks)
-    c.affine_tagged = sc_.affine && !sse_policy_ && !no_tag_ && affine_tagged_range_ok(alg, rows, geo.K);
-    // linear gaps: the pointer rides in the low bits of the cell where 4x the cell range still fits int16 (and, for SW,
-    // gap_ref < 0); otherwise the equality-test kernels (both tie-break policies)
-    c.tagged = !sc_.affine && !no_tag_ && tagged_range_ok(alg, rows);
-    // SW: one (value, row) key per lane instead of a first-arg-max per row where value << 4 (5 bits of row for more than
-    // 16 rows per lane) still fits int16
-    const long long key_top = ((long long)std::min(R_, F_) * std::max(sc_.match, 0) + 1) << (geo.K <= 16 ? 4 : 5);
-    const bool lane_key = c.tagged && alg == kAlgSW && key_top <= 32000;
-    // ... and where 64x the cell range fits (K <= 16), the key rides in the query profile instead of being computed
-    const bool prof_key = lane_key && !sse_policy_ && !no_prof_key_ && geo.K <= 16 &&
-                          (((long long)std::min(R_, F_) * std::max(sc_.match, 0) + 2) << 6) <= 32000 &&
-                          64ll * std::max(std::abs(sc_.gap_read), std::abs(sc_.gap_ref)) < 32000 && 64ll * std::abs(sc_.mismatch) < 16000;
-    const bool affine_sym = sc_.affine && sc_.open_read == sc_.open_ref && sc_.ext_read == sc_.ext_ref && !no_sym_;
-    if (prof_key) c.kernel = kFillTagProfKey;
-    else if (c.tagged) c.kernel = sse_policy_ ? (lane_key ? kFillSseTagKey : kFillSseTag) : (lane_key ? kFillTagKey : kFillTag);
-    else if (sse_policy_) c.kernel = kFillSse;
-    else if (sc_.affine) c.kernel = c.affine_tagged ? (affine_sym ? kFillAffineTagSym : kFillAffineTag) : (affine_sym ? kFillAffineSym : kFillAffine);
-    else c.kernel = (sc_.gap_read == sc_.gap_ref && !no_sym_) ? kFillLinearSym : kFillLinear;
-    return c;
-}
-
-// describe()'s name of a fill kernel (ran_align_fill)
-static const char *fill_kernel_name(int kernel) {
-    static const char *const names[kFillKernels] = {"linear", "linear_sym", "affine", "sse", "tag", "tag_key", "affine_sym",
-                                                            "affine_tag", "affine_tag_sym", "sse_tag", "sse_tag_key", "tag_prof_key"};
-    return kernel >= 0 && kernel < kFillKernels ? names[kernel] : "none";
-}
-
 // The plan an alignment call of this mode runs on: the engine's own where its geometry carries the kernel the call needs;
 // otherwise (a fallback kernel on a geometry compiled with the fast set only, kernel_instances.hip.h) the cheapest FULL
 // geometry that fits the read -- same results, the sweep a few per cent longer.
 const LaunchPlan &Engine::align_plan_for(int alg, FillChoice &choice) {
     const LaunchPlan &base = align_base_plan();
-    choice = fill_choice(alg, *base.geo);
+    choice = fill_choice(rule_inputs(), alg, base.geo->G, base.geo->K);
     if (base.geo->fill[alg][choice.kernel]) return base;
     if (!fallback_plan_.geo) fallback_plan_ = choose_plan(R_, F_, 0, 0, false, true);
-    choice = fill_choice(alg, *fallback_plan_.geo);
+    choice = fill_choice(rule_inputs(), alg, fallback_plan_.geo->G, fallback_plan_.geo->K);
     if (!fallback_plan_.geo->fill[alg][choice.kernel]) throw std::runtime_error("no alignment kernel for this mode");
     return fallback_plan_;
+}
+
+RouteFacts Engine::route_facts(bool small_call) const {
+    int fused_rows = 0;
+    for (const FusedGeometry &g : kFusedGeometries) fused_rows = std::max(fused_rows, g.G * g.K);
+    // row strips: reads beyond one register sweep, and -- measured, profiles/r04_rate_sweep.txt -- reads of more than 1 024
+    // rows, whose resident geometries (64 x 24 / 64 x 32: 34 to 53 KB of LDS) fill at 0.8-2.1 TCUPS where 12- or 16-row
+    // strips at eight waves per CU do 1.6-2.3 (1 200 x 3 000: 41 / 74 ms -> 26 / 37 ms, linear / affine)
+    const bool read_strips = align_base_plan().long_mode || (!force_g_ && !force_k_ && R_ > 1024);
+    return RouteFacts{align_banded(), wide_align_, read_strips, no_fused_ || force_g_ || force_k_, small_call, fused_rows};
 }
 
 bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, uint8_t *d_rows,
@@ -128,101 +105,38 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
     const int alg = opt & 0xF;
     if (alg > 1 || n <= 0) return false;
     ran_align_fill_ = "none";
-    const bool band = align_banded();
-    if (band && alg != kAlgSW) throw std::runtime_error("band_alignments applies to Smith-Waterman alignments only");
-    if (band && sse_policy_)
-        throw std::runtime_error("band_alignments needs traceback_policy = 0 (no banded SSE/AVX tie-breaks)");
-    // Alignments whose cells leave int16 (the reference's shorts would wrap): int32 cells on the row-strip path, one pair per
-    // register (align_strip_wide_kernel) -- every mode; only scores so large that (R + F) * |score| nears 2^28 are refused
-    // (column 0 of the NW variant: a gap of the whole read -- linear (R + 1) gap_ref; affine open_ref + R ext_ref, which
-    // check_int16_range covers)
-    const bool border_bad = alg == kAlgNW && !sc_.affine && (long long)(R_ + 1) * std::min(sc_.gap_ref, 0) < -32000;
-    bool in_range = true;
-    try {
-        check_int16_range(alg);
-    } catch (const std::runtime_error &) {
-        in_range = false;
-    }
-    if (border_bad || !in_range || wide_align_) {
-        const long long worst = std::max({std::abs((long long)sc_.match), std::abs((long long)sc_.mismatch),
-                                          std::abs((long long)(sc_.affine ? sc_.open_read : sc_.gap_read)), std::abs((long long)(sc_.affine ? sc_.open_ref : sc_.gap_ref)),
-                                          sc_.affine ? std::abs((long long)sc_.ext_read) : 0ll, sc_.affine ? std::abs((long long)sc_.ext_ref) : 0ll});
-        if ((long long)(R_ + F_ + 2) * worst >= (1ll << 28))
-            throw std::runtime_error("shape x scoring can leave the int32 range of the DP cells (read_length " + std::to_string(R_) +
-                                     ", ref_length " + std::to_string(F_) + ")");
-        hip_check(hipSetDevice(device_), "hipSetDevice");
-        ran_align_fill_ = band ? "strip_wide_band" : "strip_wide";
-        align_strips_device(alg, n, d_reads, d_refs, d_rows, d_idx, stream, true, band);
-        return false;
-    }
+    const AlignRoute route = valign::align_route(rule_inputs(), alg, route_facts(false));       // (throws what the mode refuses)
     hip_check(hipSetDevice(device_), "hipSetDevice");
-    // banded SW alignments: row strips that sweep the band windows (banded cells never exceed unbanded ones: the range
-    // decision above stands)
-    if (band) {
-        ran_align_fill_ = "strip_band";
-        align_strips_device(alg, n, d_reads, d_refs, d_rows, d_idx, stream, false, true);
+    if (route != AlignRoute::Register) {
+        ran_align_fill_ = ran_fill_name(route);
+        align_strips_device(alg, n, d_reads, d_refs, d_rows, d_idx, stream, route == AlignRoute::StripWide || route == AlignRoute::StripWideBand,
+                            route == AlignRoute::StripBand || route == AlignRoute::StripWideBand);
         return false;
     }
-    // row strips: reads beyond one register sweep, and -- measured, profiles/r04_rate_sweep.txt -- reads of more than 1 024
-    // rows, whose resident geometries (64 x 24 / 64 x 32: 34 to 53 KB of LDS) fill at 0.8-2.1 TCUPS where 12- or 16-row
-    // strips at eight waves per CU do 1.6-2.3 (1 200 x 3 000: 41 / 74 ms -> 26 / 37 ms, linear / affine)
-    if (align_base_plan().long_mode || (!force_g_ && !force_k_ && R_ > 1024)) {
-        ran_align_fill_ = "strip";
-        align_strips_device(alg, n, d_reads, d_refs, d_rows, d_idx, stream);
-        return false;
-    }
-    if (sse_policy_ && sc_.affine)
-        throw std::runtime_error("traceback_policy = 1 (SSE/AVX tie-breaks) exists for the linear gap model only");
     // the fill kernel of this mode -- and the geometry that has it: the plan's own, or the next full one (fallback kernels)
     FillChoice fc;
     const LaunchPlan &plan = align_plan_for(alg, fc);
     const bool affine_tagged = fc.affine_tagged, tagged = fc.tagged;
     const int G = plan.geo->G, K = plan.geo->K, AL = R_ + F_;
-    int blocks8 = affine_tagged ? (F_ + G - 1 + 3) / 4 : (F_ + G - 1 + 7) / 8;            // blocks of steps per lane
     const long long ppb = (long long)plan.pairs_per_wave * plan.waves_per_block;
-    const size_t bytes_per_pp = (size_t)G * blocks8 * K * 4 * ((sc_.affine && !affine_tagged) ? 2 : 1);
-    // Pointer scratch: as much of the batch per launch as memory allows (a 1 M-pair launch keeps
-    // the traceback kernel at full occupancy), capped at 64 GiB -- one launch for a million affine pairs of
-    // 150 x 500 (43.6 GB) on a 288 GB device -- and half the free HBM.
     size_t free_b = 0, total_b = 0;
     hip_check(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
-    size_t cap = std::min<size_t>(64ull << 30, std::max<size_t>((free_b + d_ptr_.bytes()) / 2, 256ull << 20));
-    if (scratch_cap_mb_ > 0) cap = std::min<size_t>(cap, (size_t)scratch_cap_mb_ << 20);
-    long long chunk = (long long)(cap / bytes_per_pp) * 2;
-    chunk = std::max(ppb, chunk / ppb * ppb);
-    const long long chain_pairs = chain ? (std::max(chain->chunk_pairs, n) + ppb - 1) / ppb * ppb : 0;
-    if (chain && (2 * chain_pairs > chunk || no_overlap_)) chain = nullptr;        // two regions do not fit: stream order
+    const TraceScratch ts = size_trace_scratch(G, K, F_, sc_.affine, affine_tagged, ppb, free_b + d_ptr_.bytes(), scratch_cap_mb_, n,
+                                               chain ? chain->chunk_pairs : 0, no_overlap_);
+    const int blocks8 = ts.blocks8;
+    const size_t bytes_per_pp = ts.bytes_per_pp;
+    if (!ts.chained) chain = nullptr;                    // two regions do not fit: stream order
     if (!chain) chain_regions_busy_[0] = chain_regions_busy_[1] = false;
-    chunk = chain ? 2 * chain_pairs : std::min(chunk, (n + ppb - 1) / ppb * ppb);
-    ensure_trace_scratch(chunk, bytes_per_pp, plan.pairs_per_wave, stream);
+    ensure_trace_scratch(ts.chunk, bytes_per_pp, plan.pairs_per_wave, stream);
     align_ptr_bytes_per_pair_ = (long long)(bytes_per_pp / 2);
     const void *fn = plan.geo->fill[alg][fc.kernel];
-    ran_align_fill_ = fill_kernel_name(fc.kernel);
+    ran_align_fill_ = ran_fill_name(route, fc.kernel);
     const int block_lds = plan.lds.total * plan.waves_per_block;
     if (block_lds > kDefaultBlockLds)
         hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, block_lds),
                   "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-    // Parts of the batch: the traceback of one part runs on a helper stream beside the fill of the next (the walk
-    // waits on memory at 17 % VALU issue, the fill owns the VALU).  A batch that fits the scratch in one piece is cut
-    // 7/8 + 1/8 -- the short fill covers the long walk, what stays exposed is the walk of the last eighth (cuts between
-    // 3/4 and 7/8 measure the same, finer ones lose to the second fill's own tail); a batch
-    // that needs several chunks alternates between the two halves of the scratch.
-    struct Part { long long begin, cnt, slot; int region; };
-    std::vector<Part> parts;
     const bool overlap = !no_overlap_ && (double)n * R_ * F_ >= 1e10 && !chain;
-    if (chain) {
-        parts.push_back(Part{0, n, chain->region * chain_pairs, chain->region});
-    } else if (overlap && chunk >= n && n >= 16 * ppb) {
-        const long long big = std::max(ppb, n * 7 / 8 / ppb * ppb);
-        parts.push_back(Part{0, big, 0, 0});
-        parts.push_back(Part{big, n - big, big, 1});
-    } else if (overlap && chunk < n && chunk >= 4 * ppb) {
-        const long long half = chunk / 2 / ppb * ppb;
-        for (long long begin = 0, i = 0; begin < n; begin += half, ++i)
-            parts.push_back(Part{begin, std::min(half, n - begin), (i & 1) * half, (int)(i & 1)});
-    } else {
-        for (long long begin = 0; begin < n; begin += chunk) parts.push_back(Part{begin, std::min(chunk, n - begin), 0, 0});
-    }
+    const std::vector<Part> parts = cut_parts(n, ts, chain ? chain->region : -1, overlap);      // (align_parts.h)
     const bool helper = (parts.size() > 1 && overlap) || chain;
     if (chain) {
         // rows are zeroed on the helper stream right before the walk that writes them (the caller has made sure the
@@ -330,14 +244,6 @@ void Engine::ensure_trace_stream() {
 
 bool Engine::align_fused(int alg, long long n, const uint8_t *d_reads, const uint8_t *d_refs, uint8_t *d_rows, short *d_idx,
                  hipStream_t stream) {
-    if (no_fused_ || sc_.affine || sse_policy_ || no_tag_ || align_base_plan().long_mode || force_g_ || force_k_ || !tagged_range_ok(alg, 256)) return false;     // (256: the tallest fused geometry)
-    if (wide_align_ || align_banded()) return false;       // (banded alignments: the strip kernels)
-    try {
-        check_int16_range(alg);
-    } catch (const std::runtime_error &) {
-        return false;                           // let the regular path raise its error
-    }
-    if (alg == kAlgNW && (long long)(R_ + 1) * std::min(sc_.gap_ref, 0) < -32000) return false;
     const FusedGeometry *best = nullptr;
     WaveLds best_lds{};
     int best_total = 0, best_blocks = 0;
@@ -372,7 +278,7 @@ bool Engine::align_fused(int alg, long long n, const uint8_t *d_reads, const uin
     f.out_rows = d_rows;
     f.out_idx = d_idx;
     const void *fn = best->kernel[alg];
-    ran_align_fill_ = "fused_tag";
+    ran_align_fill_ = ran_fill_name(AlignRoute::Fused);
     align_ptr_bytes_per_pair_ = (long long)best->G * best_blocks * best->K * 4 / 2;
     if (best_total > kDefaultBlockLds)
         hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, best_total),
@@ -527,7 +433,9 @@ void Engine::align_host(int opt, int n, const char *const *reads, const char *co
     const size_t per_pair = (size_t)3 * AL + 8;
     // (row strips run chunk after chunk on one pointer scratch: chunks that fill the device -- 2 000 pairs-of-pairs and more --
     // instead of 128 MB of staging, which is 1 100 of them at 10 kbp x 10 kbp: 253 -> ~190 ms per 4 096 pairs through the ABI)
-    const bool by_strips = align_base_plan().long_mode || (!force_g_ && !force_k_ && R_ > 1024) || align_banded();
+    const RouteFacts facts = route_facts(true);
+    const AlignRoute route = valign::align_route(rule_inputs(), alg, facts);       // (of a direct call; refusals leave here)
+    const bool by_strips = strip_chunks(route, facts);
     const size_t chunk_bytes = by_strips && !dbg_.on("align_chunk_bytes") ? std::max<size_t>(align_chunk_bytes_, 384u << 20) : align_chunk_bytes_;
     long long chunk = per_pair ? (long long)(chunk_bytes / per_pair) : n;
     chunk = whole_rounds(chunk);
@@ -549,7 +457,7 @@ void Engine::align_host(int opt, int n, const char *const *reads, const char *co
         gather(reads, refs, n, h_reads, h_refs, threads);
         auto t1 = std::chrono::steady_clock::now();
         const size_t rows_bytes = ((size_t)n * 2 * AL + 15) / 16 * 16, all_bytes = rows_bytes + sizeof(short) * 4 * (size_t)n;
-        if (align_fused(alg, n, dev_view(h_reads), dev_view(h_refs), dev_view(h_rows), (short *)(dev_view(h_rows) + rows_bytes), kernels)) {
+        if (route == AlignRoute::Fused && align_fused(alg, n, dev_view(h_reads), dev_view(h_refs), dev_view(h_rows), (short *)(dev_view(h_rows) + rows_bytes), kernels)) {
             // ONE launch: the wave that fills a pair's pointers (kept in LDS) walks it back and writes the rows
             // straight into the pinned staging
             hip_check(hipStreamSynchronize(kernels), "hipStreamSynchronize");

@@ -1,4 +1,4 @@
-// engine_core.hip -- Engine: construction, launch-plan selection, cell-range checks, staging, describe().
+// engine_core.hip -- Engine: construction, launch-plan selection, staging, describe().
 #include "engine.hip.h"
 
 namespace valign {
@@ -60,50 +60,16 @@ Engine::~Engine() {
     if (trace_stream_) (void)hipStreamSynchronize(trace_stream_.get());
 }
 
-bool Engine::affine_tagged_range_ok(int alg, int geo_rows, int K) const {
-    long long hi = (long long)std::min(R_, F_) * std::max(sc_.match, 0) + 1;
-    const int worst = std::min({sc_.open_read, sc_.open_ref, sc_.ext_read, sc_.ext_ref, sc_.mismatch, 0});
-    // NW: every cell is at least the path "one gap up, one gap left"; E / F sit one open below H
-    long long lo = alg == kAlgSW ? worst
-                                 : 2ll * (std::min(sc_.open_read, 0) + std::min(sc_.open_ref, 0)) +
-                                       (long long)(R_ + F_ + 2) * std::min({sc_.ext_read, sc_.ext_ref, 0}) + worst;
-    if (alg == kAlgNW) {        // the kernel's tilted frame: cell (p, j) carries - ext_ref * p - ext_read * j on top
-        const long long rows = (long long)geo_rows + 1, cols = F_ + 1;
-        hi += std::max(0, -sc_.ext_ref) * rows + std::max(0, -sc_.ext_read) * cols;
-        lo += std::min(0, -sc_.ext_ref) * rows + std::min(0, -sc_.ext_read) * cols;
-        if (std::abs((long long)sc_.ext_ref) * rows > 3500 || std::abs((long long)sc_.ext_read) * cols > 3500) return false;
-    }
-    if (alg == kAlgSW && (sc_.open_read >= 0 || sc_.open_ref >= 0)) return false;
-    const int key_bits = K <= 16 ? 4 : 5;
-    if (alg == kAlgSW && ((hi + 1) << key_bits) > 32000) return false;
-    return 8 * hi + 8 <= 32000 && 8 * lo - 8 >= -28000 && std::abs(sc_.match) < 1000 && std::abs(sc_.mismatch) < 1000;
-}
-
-bool Engine::tagged_range_ok(int alg, int rows) const {     // rows: padded rows of the sweep that would run
-    long long hi = (long long)std::min(R_, F_) * std::max(sc_.match, 0) + 1;
-    if (alg == kAlgNW && !sse_policy_)           // the kernel's tilted frame: every cell plus -gap_ref * p - gap_read * j
-        hi += (long long)-sc_.gap_ref * (rows + 1) + (long long)-sc_.gap_read * (F_ + 1);
-    const int worst = std::min({sc_.gap_read, sc_.gap_ref, sc_.mismatch, 0});
-    const long long lo = alg == kAlgSW ? worst : (long long)(R_ + F_ + 2) * worst;      // H(i,j) >= i gf + j gr
-    if (alg == kAlgSW && !sse_policy_ && sc_.gap_ref >= 0) return false;
-    return 4 * hi + 4 <= 32000 && 4 * lo - 4 >= -32000 && std::abs(sc_.match) < 2000 && std::abs(sc_.mismatch) < 2000;
-}
-
 const char *Engine::score_cell_format(int alg, long long n) const {
     if (alg > 1) return "none";
     if (alg == kAlgSW && band_chain_in_use()) return "int32";
-    if (score_width_ == 32 || (score_width_ == 0 && !int16_range_ok(alg))) return "int32";
+    if (score_wide_cells(alg)) return "int32";
     // (long-read kernels: Smith-Waterman with one gap score on the 160-row strips, engine_long.hip)
     if (plan_.long_mode) return long_score_f16(alg, false) ? "f16" : "int16";
     // the plan score_device launches for a call of n pairs: small calls sweep on the latency plan, whose rows enter the
     // NW variant's tilt
     const LaunchPlan &plan = (n > 0 && n <= (long long)latency_plan_.pairs_per_wave * 1024 && band_width_ == 0) ? latency_plan_ : plan_;
-    const int rows = plan.geo->G * plan.geo->K;
-    if (sc_.affine && !no_f16_ && half_float_exact(alg, R_, F_, rows)) return "f16";
-    if (!sc_.affine && ((sc_.gap_read == sc_.gap_ref && !no_sym_) || alg == kAlgNW) && !no_f16_ &&
-        (alg == kAlgNW ? half_float_exact(alg, R_, F_, rows) : half_float_unit_exact(R_, F_)))
-        return "f16";
-    return "int16";
+    return gap_form_f16(score_gap_form(rule_inputs(), alg, R_, F_, plan.geo->G * plan.geo->K)) ? "f16" : "int16";
 }
 
 std::string Engine::ran_score_cells() const {
@@ -118,65 +84,11 @@ std::string Engine::ran_kernels() const {
     return "{\"ran_score_cells\": \"" + ran_score_cells() + "\", \"ran_align_fill\": \"" + ran_align_fill_ + "\"}";
 }
 
-bool Engine::half_float_exact(int alg, int R, int F, int rows) const {
-    const long long top = (long long)std::min(R, F) * std::max({sc_.match, sc_.mismatch, 0});
-    long long slack = std::max({std::abs(sc_.match), std::abs(sc_.mismatch), std::abs(sc_.open_read),
-                                std::abs(sc_.ext_read), std::abs(sc_.open_ref), std::abs(sc_.ext_ref)});
-    if (alg == kAlgSW) return top + 2 * slack <= 2048 && slack <= 1024;
-    // NW frame: H' of cell (p, j) is at least what its row or its column adds (the border path along the other axis
-    // is free there) less one opening, at most top + the far corner's tilt; E' / F' sit at most one opening below H'.
-    // The kernel centres that range on zero (nw_frame_centre, same formula).
-    if (!sc_.affine) slack = std::max<long long>(slack, std::max(std::abs(sc_.gap_read), std::abs(sc_.gap_ref)));
-    const long long span = nw_tilt_span(rows, F);
-    const long long centre = (top + span) / 2;
-    return span < 30000 && (top + span - centre) + 3 * slack <= 2048 && centre + 3 * slack <= 2048 && slack <= 512;
-}
-
-bool Engine::half_float_unit_exact(int R, int F) const {
-    const long long top = (long long)std::min(R, F) * std::max({sc_.match, sc_.mismatch, 0});
-    const long long slack = std::max({std::abs(sc_.match), std::abs(sc_.mismatch), std::abs(sc_.gap_read), std::abs(sc_.gap_ref)});
-    return top + 2 * slack < 1024 && slack < 512;
-}
-
-long long Engine::nw_tilt_span(int rows, int F) const {
-    const long long per_row = -(long long)(sc_.affine ? sc_.ext_ref : sc_.gap_ref);
-    const long long per_col = -(long long)(sc_.affine ? sc_.ext_read : sc_.gap_read);
-    return per_row * (rows + 1) + per_col * (F + 1);
-}
-
-int Engine::widest_sweep_rows() const {
+bool Engine::score_int16_ok(int alg) const {
     int rows = 0;
     if (!plan_.long_mode && plan_.geo) rows = plan_.geo->G * plan_.geo->K;
     if (latency_plan_.geo && !latency_plan_.long_mode) rows = std::max(rows, latency_plan_.geo->G * latency_plan_.geo->K);
-    return rows;
-}
-
-bool Engine::int16_range_ok(int alg) const {
-    try {
-        check_int16_range(alg, true);
-        return true;
-    } catch (const std::runtime_error &) {
-        return false;
-    }
-}
-
-void Engine::check_int16_range(int alg, bool score_path) const {
-    long long hi = (long long)std::min(R_, F_) * std::max(sc_.match, 0) + 1;
-    if (score_path && alg == kAlgNW && !plan_.long_mode) hi += nw_tilt_span(widest_sweep_rows(), F_);
-    const int worst_gap = std::min({sc_.gap_read, sc_.gap_ref, sc_.open_read, sc_.open_ref, sc_.ext_read, sc_.ext_ref, 0});
-    // SW cells are >= 0; NW-variant score cells are bounded below by the cheaper border path
-    long long lo = alg == kAlgSW ? (long long)std::min(sc_.mismatch, 0) + worst_gap
-                                 : (long long)(std::min(R_, F_) + 2) * std::min(worst_gap, std::min(sc_.mismatch, 0));
-    // NW-variant alignments with affine gaps (plain frame, "minus infinity" = -16384): row 0 is free, so every H is at least a
-    // gap straight down from it -- open_ref + (R - 1) ext_ref -- and E / F lie at most one opening below an H; a candidate
-    // adds one mismatch.  (The product above charged every step an opening: -50 010 for 10 kbp reads at -5 / -1, whose cells
-    // never go below -10 010.)
-    if ((!score_path || plan_.long_mode) && sc_.affine && alg == kAlgNW)       // (the long-read score kernels: the same plain frame)
-        lo = (long long)std::min(sc_.open_ref, 0) + (long long)R_ * std::min(sc_.ext_ref, 0) + std::min({sc_.open_read, sc_.open_ref, 0}) +
-             std::min(sc_.mismatch, 0);
-    if (hi > 32000 || lo < -32000 || (sc_.affine && alg == kAlgNW && lo < -15000))
-        throw std::runtime_error("shape x scoring can leave the int16 range of the DP cells (read_length " +
-                                 std::to_string(R_) + ", ref_length " + std::to_string(F_) + ")");
+    return int16_range_ok(rule_inputs(), alg, true, plan_.long_mode, rows);
 }
 
 std::string Engine::host_phases() const {

@@ -187,7 +187,7 @@ bool Engine::long_tall_strips() const {
 // stays below 1024 -- short reads against a reference the resident kernels' LDS cannot hold (150 x 8 000: 8.2 -> ~11 TCUPS).
 bool Engine::long_score_f16(int alg, bool wide) const {
     const bool sym = sc_.gap_read == sc_.gap_ref && !no_sym_;
-    return !long_tall_strips() && alg == kAlgSW && !sc_.affine && sym && !wide && band_width_ == 0 && !no_f16_ && half_float_unit_exact(R_, F_);
+    return !long_tall_strips() && alg == kAlgSW && !sc_.affine && sym && !wide && band_width_ == 0 && !no_f16_ && half_float_unit_exact(sc_, R_, F_);
 }
 
 // One 160-row strip, packed cells, no band: the long-read instances that keep nothing in HBM between launches.

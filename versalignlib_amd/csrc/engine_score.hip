@@ -15,8 +15,10 @@ void Engine::score_device(int opt, long long n, const uint8_t *d_reads, const ui
         host_stats_ = HostStats{};
         ran_score_cells_ = 0;
     }
-    if (score_width_ == 16) check_int16_range(alg, true);
-    const bool wide = score_width_ == 32 || (score_width_ == 0 && !int16_range_ok(alg));
+    if (score_width_ == 16 && !score_int16_ok(alg))
+        throw std::runtime_error("shape x scoring can leave the int16 range of the DP cells (read_length " +
+                                 std::to_string(R_) + ", ref_length " + std::to_string(F_) + ")");
+    const bool wide = score_wide_cells(alg);
     if (plan_.long_mode || wide) {      // int32 cells exist on the strip path only
         score_long_device(alg, n, d_reads, d_refs, d_scores, stream, wide);
         return;
@@ -74,19 +76,9 @@ void Engine::launch_score(const LaunchPlan &plan, int alg, int R, int F, long lo
     a.refc_stride = plan.lds.refc_stride;
     a.wave_lds = plan.lds.total;
     put_scoring(a);
-    int gaps;
-    if (sc_.affine) {
-        gaps = (sc_.open_read == sc_.open_ref && sc_.ext_read == sc_.ext_ref && !no_sym_) ? kGapAffineSym : kGapAffine;
-        if (!no_f16_ && half_float_exact(alg, R, F, plan.geo->G * plan.geo->K)) gaps = gaps == kGapAffineSym ? kGapAffineSymF16 : kGapAffineF16;
-    } else {
-        gaps = (sc_.gap_read == sc_.gap_ref && !no_sym_) ? kGapSym : kGapLinear;
-        // (the NW variant's tilted frame has no gap constants left: its half-float kernel serves gap_read != gap_ref too)
-        if ((gaps == kGapSym || alg == kAlgNW) && !no_f16_ &&
-            (alg == kAlgNW ? half_float_exact(alg, R, F, plan.geo->G * plan.geo->K) : half_float_unit_exact(R, F)))
-            gaps = kGapSymF16;
-    }
+    const int gaps = score_gap_form(rule_inputs(), alg, R, F, plan.geo->G * plan.geo->K);
     const void *fn = plan.geo->kernel[alg][gaps];
-    ran_score_cells_ |= (gaps == kGapSymF16 || gaps == kGapAffineSymF16 || gaps == kGapAffineF16) ? kRanF16 : kRanInt16;
+    ran_score_cells_ |= gap_form_f16(gaps) ? kRanF16 : kRanInt16;
     const int block_lds = plan.lds.total * plan.waves_per_block;
     if (block_lds > kDefaultBlockLds)
         hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, block_lds),
@@ -122,7 +114,7 @@ void Engine::score_host(int opt, int n, const char *const *reads, const char *co
     // Long reads on row strips: their launches follow one another on one stream (the strips' boundary rows are one scratch) and
     // a 48 MB chunk of 10 kbp pairs is 1 200 waves for 3 500 resident ones -- each launch runs at a third of the device.
     // Chunks of up to 192 MB there (the banded block chain needs no scratch: its small chunks run side by side instead).
-    const bool wide_cells = score_width_ == 32 || (score_width_ == 0 && !int16_range_ok(alg));
+    const bool wide_cells = score_wide_cells(alg);
     const bool scratch_free = (band_width_ > 0 && alg == kAlgSW && band_chain_in_use()) || (plan_.long_mode && long_single_strip(wide_cells));
     const bool strips_in_turn = plan_.long_mode && !scratch_free;
     const size_t chunk_bytes = strips_in_turn && !dbg_.on("chunk_bytes") ? std::max<size_t>(score_chunk_bytes_, 192u << 20) : score_chunk_bytes_;
@@ -161,7 +153,7 @@ void Engine::score_host(int opt, int n, const char *const *reads, const char *co
     // (the banded block chain keeps nothing in HBM between its steps: its chunks may run side by side on the slots' streams --
     // a chunk of 2 400 pairs of 10 kbp fills 600 of the 4 096 resident waves and takes a launch's latency whatever its size)
     // ... and so do the single-strip instances of the long-read kernel (short reads against a long reference)
-    const bool shared_scratch = !scratch_free && (plan_.long_mode || score_width_ == 32 || !int16_range_ok(alg));
+    const bool shared_scratch = !scratch_free && (plan_.long_mode || score_width_ == 32 || !score_int16_ok(alg));
     host_stats_ = HostStats{};
     auto drain = [&](int s) {
         if (slot_pending_[s] <= 0) return;
@@ -251,7 +243,7 @@ void Engine::score_host(int opt, int n, const char *const *reads, const char *co
 
 bool Engine::ragged_applies(int alg) const {
     return ragged_ && alg <= kAlgNW && !plan_.long_mode && !force_g_ && !force_k_ && score_width_ != 32 &&
-           R_ > 0 && F_ > 0 && int16_range_ok(alg);
+           R_ > 0 && F_ > 0 && score_int16_ok(alg);
 }
 
 double Engine::sampled_cell_fraction(const char *const *reads, const char *const *refs, long long n) const {
