@@ -25,6 +25,11 @@
  *                                                         Smith-Waterman alignments on the scores' block band;
  *                                                         0 (default): every cell whatever band_width says
  *                                                         (opt-in: existing calls return what they did)
+ *       trace_checkpoints ............................... 1: compute_alignments of long reads (the plain row strips: unbanded,
+ *                                                         int16 cells, traceback_policy 0) keeps one boundary row per strip
+ *                                                         and ONE strip's pointers and re-fills strip after strip along the
+ *                                                         walk: identical alignments, 5.5 instead of 51.5 MB of scratch per
+ *                                                         pair of pairs at 10 kbp x 10 kbp; 0 (default): every pointer
  *       score_width ..................................... DP cells of score_alignments: 0 auto (int16,
  *                                                         int32 where int16 could overflow), 16, 32
  *       ragged_batching ................................. length-sorted score calls, both modes
@@ -156,6 +161,28 @@ int valign_hip_set_band_width(valign_hip_engine *e, int diagonals);
  * unbanded alignments whatever band_width says.  Other values are refused.                                       */
 int valign_hip_set_band_alignments(valign_hip_engine *e, int on);
 
+/* Checkpointed traceback for long-read alignments in bounded memory (key trace_checkpoints).  Reads beyond one register sweep
+ * are filled in row strips of 64 K rows, and by default (0) every strip streams 2 bits per cell and pair (4 with affine gaps) to
+ * a pointer region of its own: S regions, memory that grows with R x F.  With 1, calls that take the plain row strips --
+ * unbanded, int16 cells, traceback_policy = 0; Smith-Waterman and the NW variant, linear and affine gaps, both entry paths and
+ * every hip_devices shard -- run a forward pass that stores NO pointers and keeps every strip's bottom row (S - 1 boundary rows
+ * per pair of pairs instead of the two that ping-pong), then walk back strip by strip, last to first: the strip is filled again,
+ * with pointers, into ONE strip-sized region that every round reuses (from the checkpoint row above it, and only up to the
+ * column the walk has reached), and the walk crosses it and leaves its state for the next round.  The alignments are
+ * bit-identical; the scratch per pair of pairs is one region + (S - 1) rows + 48 bytes of walk state (10 kbp x 10 kbp at 16
+ * rows per lane: 5.5 MB instead of 51.5 MB, linear gaps), so a given pointer_scratch_cap_mb holds nine times the pairs.
+ * Not covered, and run exactly as with 0: int32 cells (strip_wide), bands (strip_band, strip_wide_band), traceback_policy = 1
+ * and the register and fused paths of short reads -- the key saves memory and changes no result, so nothing is refused;
+ * "ran_align_fill" of valign_hip_describe says which path ran ("strip_ckpt" for this one), "align_ptr_bytes_per_pair" and
+ * "align_ckpt_bytes_per_pair" what a pair holds (pointers; checkpoint rows + walk state), "align_scratch_bytes" what the
+ * engine holds after the call.  Values other than 0 and 1 are refused.
+ * Time, measured at 10 kbp x 10 kbp against the full-pointer path (profiles/r07_trace_checkpoints.txt): with linear gaps a
+ * call whose full pointer scratch fits the device in one piece is SLOWER with the key -- 4,096 pairs: 143.7 against 137.6 ms
+ * (SW), 131.1 against 120.6 ms (NW variant), 1.04 x / 1.09 x -- because every cell is filled one and a half times; the key is
+ * there for the memory bound.  Where the full-pointer path has to run in chunks it is faster: affine gaps 201 against 329 ms
+ * (4,096 pairs), 16,384 pairs 661 against 835 ms (linear) and 903 against 1,322 ms (affine).                                 */
+int valign_hip_set_trace_checkpoints(valign_hip_engine *e, int on);
+
 /* Cap (MiB) of the internal pointer scratch compute_alignments keeps in device memory (2 bits per cell and pair,
  * 4 with affine gaps: 20.8 / 41.6 KB per pair at 150 x 500).  0 (default): up to 64 GiB or half the free HBM,
  * whichever is smaller; batches that need more than the cap run in chunks -- same results, more launches.
@@ -195,8 +222,8 @@ int valign_hip_score_device(valign_hip_engine *e, int opt, long long n, const vo
  * (readStart, readEnd, refStart, refEnd), i.e. the contents of the ABI's `Alignment`
  * (include/AlignmentKernel.h:12-18) flattened.  Tie-breaks follow the Default kernel.
  * Asynchronous on `hip_stream`; uses an internal pointer scratch (20.8 KB per pair at
- * 150x500, 25 MB at 10 kbp x 10 kbp; up to half the free HBM per launch -- at most 64 GiB for
- * reads of up to 2048 rows, 128 GiB for row strips --, larger batches run in chunks).                */
+ * 150x500, 25 MB at 10 kbp x 10 kbp -- 2.8 MB with valign_hip_set_trace_checkpoints(e, 1); up to half the free HBM per
+ * launch -- at most 64 GiB for reads of up to 2048 rows, 128 GiB for row strips --, larger batches run in chunks).   */
 int valign_hip_align_device(valign_hip_engine *e, int opt, long long n, const void *d_reads,
                             const void *d_refs, void *d_rows, void *d_idx, void *hip_stream);
 
@@ -233,8 +260,10 @@ int valign_hip_set_half_float_cells(valign_hip_engine *e, int mode);
 
 /* JSON description of what a call with this opt would launch (geometry, LDS, grid).  "score_cells" is a prediction for a
  * device-resident call of n pairs; "ran_score_cells" (f16 / int16 / int32, joined with '+' where a length-sorted call
- * mixed them) and "ran_align_fill" (the alignment path and fill kernel: fused_tag, tag_prof_key, ..., strip, strip_wide)
- * report what the engine's last score / alignment call actually launched ("none" before any).                         */
+ * mixed them) and "ran_align_fill" (the alignment path and fill kernel: fused_tag, tag_prof_key, ..., strip, strip_wide,
+ * strip_ckpt) report what the engine's last score / alignment call actually launched ("none" before any);
+ * "align_ptr_bytes_per_pair" / "align_ckpt_bytes_per_pair" are the pointer-stream and checkpoint bytes a pair holds in the plan
+ * of the last alignment call, "align_scratch_bytes" the pointer scratch the engine holds after it.                     */
 int valign_hip_describe(valign_hip_engine *e, int opt, long long n, char *buf, int cap);
 
 const char *valign_hip_last_error(void);

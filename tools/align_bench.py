@@ -21,6 +21,7 @@ def main():
     ap.add_argument("--R", type=int, default=bench.R)
     ap.add_argument("--F", type=int, default=bench.F)
     ap.add_argument("--band", type=int, default=0, help="> 0: banded SW alignments of that many diagonals (band_alignments = 1; NW skipped)")
+    ap.add_argument("--trace-checkpoints", type=int, default=0, help="1: checkpointed traceback of long reads (trace_checkpoints = 1)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     bench.R, bench.F = a.R, a.F                     # (other shapes: reads beyond 2048 rows take the row strips)
@@ -39,6 +40,8 @@ def main():
         if a.band > 0:
             eng.set_band_width(a.band)
             eng.set_band_alignments(1)
+        if a.trace_checkpoints:
+            eng.set_trace_checkpoints(a.trace_checkpoints)
         for opt, name in ((0, "sw_" + model),) + (((1, "nw_" + model),) if a.band <= 0 else ()):
             eng.align_device(opt, reads, refs, rows, idx)
             torch.cuda.synchronize()
@@ -51,7 +54,8 @@ def main():
             ms = e0.elapsed_time(e1) / a.iters
             d = eng.describe(opt, a.pairs)
             print(json.dumps({"mode": name + "_align", "band": a.band, "fill": d["ran_align_fill"],
-                              "ptr_bytes_per_pair": d["align_ptr_bytes_per_pair"], "geom": "%dx%d" % (d["group_lanes"], d["rows_per_lane"]),
+                              "ptr_bytes_per_pair": d["align_ptr_bytes_per_pair"], "ckpt_bytes_per_pair": d["align_ckpt_bytes_per_pair"],
+                              "scratch_mb": round(d["align_scratch_bytes"] / 1e6, 1), "geom": "%dx%d" % (d["group_lanes"], d["rows_per_lane"]),
                               "ms": round(ms, 3), "gcups": round(a.pairs * bench.R * bench.F / ms / 1e6, 1),
                               "start_checksum": int(idx[:, 0].to(torch.int64).sum().item())}))
         eng.close()

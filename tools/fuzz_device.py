@@ -51,7 +51,7 @@ def draw(rng):
                 band=int(rng.integers(8, 300)) * 2 if (rng.random() < 0.12 and R >= 64) else 0,
                 stream=bool(rng.random() < 0.5), policy=1 if (not affine and rng.random() < 0.2) else 0,
                 cap_mb=int(rng.integers(1, 64)) if rng.random() < 0.15 else 0, host=bool(rng.random() < 0.3),
-                threads=int(rng.integers(1, 9)))
+                threads=int(rng.integers(1, 9)), ckpt=bool(kind == "long" and rng.random() < 0.5))     # long reads: checkpointed traceback
 
 
 def run(c):
@@ -67,6 +67,8 @@ def run(c):
             eng.set_traceback_policy(1)
         if c["cap_mb"]:
             eng.set_pointer_scratch_cap_mb(c["cap_mb"])
+        if c.get("ckpt"):
+            eng.set_trace_checkpoints(1)
         stream = torch.cuda.Stream() if c["stream"] else None
         d_reads, d_refs = torch.from_numpy(reads).cuda(), torch.from_numpy(refs).cuda()
         torch.cuda.synchronize()

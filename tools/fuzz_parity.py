@@ -79,6 +79,8 @@ def draw_case(rng, big=False, kinds=None):
         keys["half_float_cells"] = int(rng.integers(0, 2))
     if rng.random() < 0.1:
         keys["hip_devices"] = 1                           # the in-plugin shard path with one shard
+    if kind == "long" and rng.random() < 0.5:
+        keys["trace_checkpoints"] = 1                     # long reads: checkpointed traceback (same results)
     data = dict(seed=int(rng.integers(1, 1 << 30)), sub_rate=float(rng.choice([0.02, 0.1, 0.3])), indel_rate=float(rng.choice([0.0, 0.02])) if n * R < 400_000 else 0.0,
                 n_run_frac=float(rng.choice([0.0, 0.1])), short_frac=float(rng.choice([0.0, 0.2, 0.6])), lowercase_frac=0.05, junk_frac=0.05)
     return dict(R=R, F=F, n=n, keys=keys, aff=aff, affine=affine, policy=policy, data=data, gaps=(gr, gf), match=match, mismatch=mismatch, band=band)

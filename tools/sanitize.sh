@@ -3,6 +3,7 @@
 #   1. the host-only half of the plugin's host-pointer path (versalignlib_amd/csrc/host_pipeline.h: worker pool,
 #      gather, scatter) as a stand-alone program under -fsanitize=thread and under -fsanitize=address,undefined;
 #      and the engine's cell-range rules and path choice (versalignlib_amd/csrc/cell_rules.h, tests/cell_rules_check.cpp)
+#      and the plan of the checkpointed traceback (versalignlib_amd/csrc/ckpt_plan.h, tests/ckpt_plan_check.cpp)
 #      under -fsanitize=address,undefined;
 #   2. libvalignhost.so, valign-bench and the oracle (oracle/cpu_ref.c) built with -fsanitize=address,undefined
 #      into build/sanitize/, and the whole CPU test-suite run against THOSE (python gets the runtimes preloaded).
@@ -22,6 +23,9 @@ g++ -std=c++17 $SAN -pthread -I"$CS" "$R/tests/host_pipeline_check.cpp" -o "$OUT
 ASAN_OPTIONS="detect_leaks=1" "$OUT/host_pipeline_asan"
 echo "== cell_rules.h under AddressSanitizer + UBSan"
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/cell_rules_check.cpp" -o "$OUT/cell_rules_asan"
+echo "== ckpt_plan.h under AddressSanitizer + UBSan"
+g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/ckpt_plan_check.cpp" -o "$OUT/ckpt_plan_asan"
+"$OUT/ckpt_plan_asan"
 "$OUT/cell_rules_asan"
 
 echo "== libvalignhost.so, valign-bench, libcpuref.so with $SAN"

@@ -182,7 +182,7 @@ inline FillChoice fill_choice(const RuleInputs &in, int alg, int G, int K) {
 }
 
 // ---- the path of an alignment call ----
-enum class AlignRoute { Fused, Register, Strip, StripBand, StripWide, StripWideBand };
+enum class AlignRoute { Fused, Register, Strip, StripBand, StripWide, StripWideBand, StripCkpt };
 
 // What the route reads of the engine beyond the rule inputs (Engine::align_route)
 struct RouteFacts {
@@ -192,9 +192,12 @@ struct RouteFacts {
     bool fused_off = false;         // debug switch no_fused, or a forced geometry
     bool small_call = false;        // align_host's direct call: the one place the fused kernel is tried
     int fused_rows = 0;             // padded rows of the tallest fused geometry
+    bool checkpoints = false;       // trace_checkpoints = 1: plain row strips keep checkpoint rows instead of every pointer
 };
 
 // The cascade, once: refusals, then int32 cells, the band, row strips, the fused kernel for a small call, the register sweep.
+// trace_checkpoints changes the memory of one path and nothing else: where the call would take the plain int16 row strips with
+// the default tie-breaks it takes StripCkpt (same results); every other call runs as without the key.
 // tagged_range_ok is asked about two different sweeps on purpose: Fused is decided before a fused geometry is picked, so it
 // tests `fused_rows` (the tallest one: whichever geometry align_fused then takes is in range); the register path tests the
 // rows of the plan it launches (fill_choice).
@@ -213,7 +216,7 @@ inline AlignRoute align_route(const RuleInputs &in, int alg, const RouteFacts &f
     // banded SW alignments: row strips that sweep the band windows (banded cells never exceed unbanded ones: the range
     // decision above stands)
     if (f.banded) return AlignRoute::StripBand;
-    if (f.read_strips) return AlignRoute::Strip;
+    if (f.read_strips) return (f.checkpoints && !in.sse_policy) ? AlignRoute::StripCkpt : AlignRoute::Strip;
     if (in.sse_policy && in.sc.affine)
         throw std::runtime_error("traceback_policy = 1 (SSE/AVX tie-breaks) exists for the linear gap model only");
     // fill + traceback in one launch: linear gaps, default tie-breaks, plain tagged cells
@@ -224,14 +227,14 @@ inline AlignRoute align_route(const RuleInputs &in, int alg, const RouteFacts &f
 // align_host sizes its chunks for strips where the read or the band asks for them; int32 cells alone (a short read whose
 // cells leave int16) keep the register path's chunks
 inline bool strip_chunks(AlignRoute r, const RouteFacts &f) {
-    return r == AlignRoute::Strip || r == AlignRoute::StripBand || r == AlignRoute::StripWideBand || (r == AlignRoute::StripWide && f.read_strips);
+    return r == AlignRoute::Strip || r == AlignRoute::StripCkpt || r == AlignRoute::StripBand || r == AlignRoute::StripWideBand || (r == AlignRoute::StripWide && f.read_strips);
 }
 
 // describe()'s name of what an alignment call launched (ran_align_fill); fill_kernel: the register path's FillKernel
 inline const char *ran_fill_name(AlignRoute r, int fill_kernel = -1) {
     static const char *const names[kFillKernels] = {"linear", "linear_sym", "affine", "sse", "tag", "tag_key", "affine_sym",
                                                     "affine_tag", "affine_tag_sym", "sse_tag", "sse_tag_key", "tag_prof_key"};
-    static const char *const routes[] = {"fused_tag", nullptr, "strip", "strip_band", "strip_wide", "strip_wide_band"};     // by AlignRoute
+    static const char *const routes[] = {"fused_tag", nullptr, "strip", "strip_band", "strip_wide", "strip_wide_band", "strip_ckpt"};     // by AlignRoute
     if (r != AlignRoute::Register) return routes[(int)r];
     return fill_kernel >= 0 && fill_kernel < kFillKernels ? names[fill_kernel] : "none";
 }

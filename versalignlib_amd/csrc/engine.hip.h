@@ -223,6 +223,16 @@ public:
         band_alignments_ = on == 1;
     }
     int band_alignments() const { return band_alignments_ ? 1 : 0; }
+    // Checkpointed traceback of long-read alignments (opt-in; ckpt_plan.h): 1 = calls that take the plain row strips (unbanded,
+    // int16 cells, traceback_policy 0; both algorithms, linear and affine gaps) keep one boundary row per strip and ONE strip's
+    // pointer region instead of every pointer, and re-fill strip after strip along the walk -- identical results, a scratch that
+    // grows with R + F instead of R x F.  Every other call (int32 cells, bands, traceback_policy 1, the register and fused
+    // paths) runs exactly as with 0 (default); ran_align_fill says which path ran.
+    void set_trace_checkpoints(int on) {
+        if (on != 0 && on != 1) throw std::runtime_error("trace_checkpoints must be 0 or 1");
+        trace_checkpoints_ = on == 1;
+    }
+    int trace_checkpoints() const { return trace_checkpoints_ ? 1 : 0; }
     // The block band of banded SW scores and alignments: (16, 1) on the block chain, else (160, 4) (valign_hip.h)
     void band_block_shape(int &block_rows, int &col_align) const;
     // DP cell width of score_alignments: 0 = int16 unless the shape could overflow it (default),
@@ -395,8 +405,10 @@ public:
     // Linear or affine gaps, Default tie-breaks, int16 cells (the reference's; where they would wrap, align_route
     // takes the int32 cells instead of wrapping silently).
     // band: banded SW alignments (align_strip_kernel<..., BAND>: each strip sweeps its rows' band windows only).
+    // ckpt: checkpointed traceback (AlignRoute::StripCkpt; ckpt_plan.h has the schedule): a forward pass without pointers that
+    // keeps every strip's bottom row, then per strip, last to first, a re-fill into one pointer region and a resumable walk.
     void align_strips_device(int alg, long long n, const uint8_t *d_reads, const uint8_t *d_refs, uint8_t *d_rows,
-                             short *d_idx, hipStream_t stream, bool wide = false, bool band = false);
+                             short *d_idx, hipStream_t stream, bool wide = false, bool band = false, bool ckpt = false);
     bool align_banded() const { return band_alignments_ && band_width_ > 0; }
 
     // Host pointers in, Alignment[] out: the rows of every pair are fresh operator new[] blocks
@@ -576,6 +588,7 @@ private:
     bool sse_policy_ = false;
     int band_width_ = 0;
     bool band_alignments_ = false;
+    bool trace_checkpoints_ = false;
     int score_width_ = 0;
     int ragged_ = 0, force_g_ = 0, force_k_ = 0;
     size_t score_chunk_bytes_ = 48u << 20;                   // staging chunk of score_host (debug switch chunk_bytes)
@@ -622,6 +635,7 @@ private:
     unsigned ran_score_cells_ = 0;
     const char *ran_align_fill_ = "none";
     long long align_ptr_bytes_per_pair_ = 0;             // pointer-stream bytes per pair of the last alignment call's plan (describe)
+    long long align_ckpt_bytes_per_pair_ = 0;            // ... and what StripCkpt keeps beside it: checkpoint rows + walk state
     int cu_count_ = 0;
     bool no_band_chain_ = dbg_.on("no_band_chain");      // banded scores on score_long_kernel's strips
     int start_col_[kSlots] = {};                         // per slot: first column of the chunk's rows the copy issuer copied

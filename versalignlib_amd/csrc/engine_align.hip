@@ -16,6 +16,7 @@ struct StripGeometry {
     const void *sse_kernel[2];         // traceback_policy = 1 (linear gaps)
     const void *wide_kernel[2][3];     // int32 cells, [alg][0 linear gaps, 1 affine, 2 SSE tie-breaks]; nullptr: no such instance
     const void *band_kernel[2][2];     // banded SW (BAND), [0 int16 / 1 int32 cells][0 linear gaps, 1 affine]; nullptr: no such instance
+    const void *ckpt_kernel[2][2][2];  // checkpointed traceback, [alg][0 linear gaps, 1 affine][0 forward pass, 1 re-fill]
 };
 // int32 cells are the rare path: every mode at 8 rows per lane, the NW variant with linear gaps (the reference's model: long
 // reads whose column-0 border leaves int16) at 16 / 12 as well
@@ -34,6 +35,12 @@ struct StripGeometry {
 #define VALIGN_STRIP_BAND_WIDE(K)                                                                                            \
     {{(const void *)&align_strip_kernel<K, kAlgSW, false, false, true>, (const void *)&align_strip_kernel<K, kAlgSW, true, false, true>}, \
      {(const void *)&align_strip_wide_kernel<K, kAlgSW, false, false, true>, (const void *)&align_strip_wide_kernel<K, kAlgSW, true, false, true>}}
+#define VALIGN_STRIP_CKPT_ALG(K, ALG)                                                                                   \
+    {{(const void *)&align_strip_kernel<K, ALG, false, false, false, kCkptForward>,                                    \
+      (const void *)&align_strip_kernel<K, ALG, false, false, false, kCkptRefill>},                                    \
+     {(const void *)&align_strip_kernel<K, ALG, true, false, false, kCkptForward>,                                     \
+      (const void *)&align_strip_kernel<K, ALG, true, false, false, kCkptRefill>}}
+#define VALIGN_STRIP_CKPT(K) {VALIGN_STRIP_CKPT_ALG(K, kAlgSW), VALIGN_STRIP_CKPT_ALG(K, kAlgNW)}
 template <int K>
 static WaveLds strip_lds(int, int) {            // the profile of 64 K rows and the ring of slab numbers: no term in F
     return WaveLds{StripLds<K>::kRing, 0, StripLds<K>::kTotal};
@@ -41,14 +48,16 @@ static WaveLds strip_lds(int, int) {            // the profile of 64 K rows and 
 static const StripGeometry kStripGeometries[] = {
     {16, &strip_lds<16>, {(const void *)&align_strip_kernel<16, kAlgSW>, (const void *)&align_strip_kernel<16, kAlgNW>},
      {(const void *)&align_strip_kernel<16, kAlgSW, true>, (const void *)&align_strip_kernel<16, kAlgNW, true>}, VALIGN_STRIP_SSE(16),
-     VALIGN_STRIP_WIDE_NW(16), VALIGN_STRIP_BAND(16)},
+     VALIGN_STRIP_WIDE_NW(16), VALIGN_STRIP_BAND(16), VALIGN_STRIP_CKPT(16)},
     {12, &strip_lds<12>, {(const void *)&align_strip_kernel<12, kAlgSW>, (const void *)&align_strip_kernel<12, kAlgNW>},
      {(const void *)&align_strip_kernel<12, kAlgSW, true>, (const void *)&align_strip_kernel<12, kAlgNW, true>}, VALIGN_STRIP_SSE(12),
-     VALIGN_STRIP_WIDE_NW(12), {{nullptr, nullptr}, {nullptr, nullptr}}},
+     VALIGN_STRIP_WIDE_NW(12), {{nullptr, nullptr}, {nullptr, nullptr}}, VALIGN_STRIP_CKPT(12)},
     {8, &strip_lds<8>, {(const void *)&align_strip_kernel<8, kAlgSW>, (const void *)&align_strip_kernel<8, kAlgNW>},
      {(const void *)&align_strip_kernel<8, kAlgSW, true>, (const void *)&align_strip_kernel<8, kAlgNW, true>}, VALIGN_STRIP_SSE(8),
-     VALIGN_STRIP_WIDE_ALL(8), VALIGN_STRIP_BAND_WIDE(8)},
+     VALIGN_STRIP_WIDE_ALL(8), VALIGN_STRIP_BAND_WIDE(8), VALIGN_STRIP_CKPT(8)},
 };
+#undef VALIGN_STRIP_CKPT
+#undef VALIGN_STRIP_CKPT_ALG
 #undef VALIGN_STRIP_SSE
 #undef VALIGN_STRIP_BAND
 #undef VALIGN_STRIP_BAND_WIDE
@@ -97,7 +106,7 @@ RouteFacts Engine::route_facts(bool small_call) const {
     // rows, whose resident geometries (64 x 24 / 64 x 32: 34 to 53 KB of LDS) fill at 0.8-2.1 TCUPS where 12- or 16-row
     // strips at eight waves per CU do 1.6-2.3 (1 200 x 3 000: 41 / 74 ms -> 26 / 37 ms, linear / affine)
     const bool read_strips = align_base_plan().long_mode || (!force_g_ && !force_k_ && R_ > 1024);
-    return RouteFacts{align_banded(), wide_align_, read_strips, no_fused_ || force_g_ || force_k_, small_call, fused_rows};
+    return RouteFacts{align_banded(), wide_align_, read_strips, no_fused_ || force_g_ || force_k_, small_call, fused_rows, trace_checkpoints_};
 }
 
 bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, uint8_t *d_rows,
@@ -105,12 +114,13 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
     const int alg = opt & 0xF;
     if (alg > 1 || n <= 0) return false;
     ran_align_fill_ = "none";
+    align_ckpt_bytes_per_pair_ = 0;
     const AlignRoute route = valign::align_route(rule_inputs(), alg, route_facts(false));       // (throws what the mode refuses)
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (route != AlignRoute::Register) {
         ran_align_fill_ = ran_fill_name(route);
         align_strips_device(alg, n, d_reads, d_refs, d_rows, d_idx, stream, route == AlignRoute::StripWide || route == AlignRoute::StripWideBand,
-                            route == AlignRoute::StripBand || route == AlignRoute::StripWideBand);
+                            route == AlignRoute::StripBand || route == AlignRoute::StripWideBand, route == AlignRoute::StripCkpt);
         return false;
     }
     // the fill kernel of this mode -- and the geometry that has it: the plan's own, or the next full one (fallback kernels)
@@ -291,8 +301,9 @@ bool Engine::align_fused(int alg, long long n, const uint8_t *d_reads, const uin
 }
 
 void Engine::align_strips_device(int alg, long long n, const uint8_t *d_reads, const uint8_t *d_refs, uint8_t *d_rows,
-                         short *d_idx, hipStream_t stream, bool wide, bool band) {
+                         short *d_idx, hipStream_t stream, bool wide, bool band, bool ckpt) {
     const bool affine = sc_.affine;
+    if (ckpt && (wide || band || sse_policy_)) throw std::runtime_error("checkpointed traceback: plain int16 row strips only");
     if (sse_policy_ && affine)
         throw std::runtime_error("traceback_policy = 1 (SSE/AVX tie-breaks) exists for the linear gap model only");
     const int wide_mode = affine ? 1 : (sse_policy_ ? 2 : 0);
@@ -338,43 +349,57 @@ void Engine::align_strips_device(int alg, long long n, const uint8_t *d_reads, c
     const size_t strip_words = (size_t)blocks8 * 64 * K * (affine ? 2 : 1);    // per wave (= pair-of-pairs) and strip
     // boundary row sets: H, and F beside it (affine); int32 cells: those per pair
     const int row_sets = (affine ? 2 : 1) * (wide ? 2 : 1);
-    const size_t bytes_per_pp = strip_words * 4 * strips + (size_t)2 * row_sets * row_dwords * 4;
-    align_ptr_bytes_per_pair_ = (long long)(strip_words * 4 * strips / 2);
+    // checkpointed traceback: ONE region, a boundary row set per strip but the last, the walk state of the two pairs (ckpt_plan.h)
+    const CkptPlan cp = ckpt_plan(R_, F_, K, affine);
+    if (ckpt && (cp.strips != strips || cp.blocks8 != blocks8 || cp.row_dwords != row_dwords || cp.region_bytes != strip_words * 4 || cp.row_sets != row_sets))
+        throw std::runtime_error("checkpointed traceback: the plan and the strips disagree");
+    const size_t bytes_per_pp = ckpt ? cp.bytes_per_pp : strip_words * 4 * strips + (size_t)2 * row_sets * row_dwords * 4;
+    align_ptr_bytes_per_pair_ = (long long)(strip_words * 4 * (ckpt ? 1 : strips) / 2);
+    align_ckpt_bytes_per_pair_ = ckpt ? (long long)((cp.row_bytes + cp.state_bytes) / 2) : 0;
     size_t free_b = 0, total_b = 0;
     hip_check(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
     // (the pointer stream of a 10 kbp x 10 kbp pair-of-pairs is 50 MB: what fits the scratch is what runs side by side --
     // 24 GB, the bound until round 4, kept 480 waves on 1 024 SIMDs; half of the free HBM, at most 128 GB, now)
     size_t cap = std::min<size_t>(128ull << 30, std::max<size_t>((free_b + d_ptr_.bytes()) / 2, 256ull << 20));
     if (scratch_cap_mb_ > 0) cap = std::min<size_t>(cap, (size_t)scratch_cap_mb_ << 20);
-    long long chunk = std::max<long long>(2, (long long)(cap / bytes_per_pp) * 2);
-    chunk = std::min(chunk, (n + 1) / 2 * 2);
+    const long long chunk = strip_chunk_pairs(cap, bytes_per_pp, n);
     const long long waves = chunk / 2;
     ensure_trace_scratch(chunk, bytes_per_pp, 2, stream);      // (chunk is even: waves * bytes_per_pp bytes, chunk end cells)
     if ((size_t)2 * n * sizeof(int) > d_first_bad_.bytes()) {
         hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
         d_first_bad_.reserve((size_t)2 * n * sizeof(int), "first invalid positions");
     }
-    unsigned *boundary = d_ptr_.get() + (size_t)waves * strip_words * strips;        // two rows per pair-of-pairs behind the pointers
+    // two rows per pair-of-pairs behind the pointers; ckpt: strips - 1 row sets behind the one region, the walk states behind those
+    unsigned *boundary = d_ptr_.get() + (size_t)waves * strip_words * (ckpt ? 1 : strips);
+    WalkState *walk = reinterpret_cast<WalkState *>(boundary + (size_t)(strips - 1) * row_sets * waves * row_dwords);      // (ckpt only)
     hip_check(hipMemsetAsync(d_rows, 0, (size_t)n * 2 * AL, stream), "hipMemsetAsync(rows)");
     hipLaunchKernelGGL(first_invalid_kernel, dim3((unsigned)n), dim3(kWave), 0, stream, d_reads, d_refs, n, R_, F_, d_first_bad_.get(),
                        sse_policy_ ? 1 : 0);
     hip_check(hipGetLastError(), "hipLaunchKernel(first_invalid_kernel)");
-    const void *fn = band ? geo->band_kernel[wide ? 1 : 0][affine ? 1 : 0]
+    const void *refill_fn = ckpt ? geo->ckpt_kernel[alg][affine ? 1 : 0][1] : nullptr;
+    const void *fn = ckpt ? geo->ckpt_kernel[alg][affine ? 1 : 0][0]
+                     : band ? geo->band_kernel[wide ? 1 : 0][affine ? 1 : 0]
                           : wide ? geo->wide_kernel[alg][wide_mode] : (affine ? geo->affine_kernel[alg] : (sse_policy_ ? geo->sse_kernel[alg] : geo->kernel[alg]));
-    if (lds.total > kDefaultBlockLds)
+    if (lds.total > kDefaultBlockLds) {
         hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds.total),
                   "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+        if (refill_fn)
+            hip_check(hipFuncSetAttribute(refill_fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds.total),
+                      "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+    }
     for (long long begin = 0; begin < n; begin += chunk) {
         const long long cnt = std::min(chunk, n - begin), cnt_waves = (cnt + 1) / 2;
-        for (int s = 0; s < strips; ++s) {
+        // the boundary row set below strip s: the two that ping-pong -- or, checkpointed, strip s's own (the last strip has none)
+        auto row_set = [&](int s) { return boundary + (size_t)(ckpt ? std::min(s, std::max(strips - 2, 0)) : (s & 1)) * row_sets * waves * row_dwords; };
+        auto strip_args = [&](int s) {
             StripArgs a;
             a.reads = d_reads + (size_t)begin * R_;
             a.refs = d_refs + (size_t)begin * F_;
-            a.ptr = d_ptr_.get() + (size_t)s * cnt_waves * strip_words;
+            a.ptr = d_ptr_.get() + (ckpt ? 0 : (size_t)s * cnt_waves * strip_words);
             a.ends = d_ends_.get();
             a.first_bad = d_first_bad_.get() + 2 * begin;
-            a.top = boundary + (size_t)((s & 1) ^ 1) * row_sets * waves * row_dwords;
-            a.bottom = boundary + (size_t)(s & 1) * row_sets * waves * row_dwords;
+            a.top = row_set(s > 0 ? s - 1 : 0);                          // (unused for strip 0)
+            a.bottom = row_set(s);                                       // (not written by the last strip)
             a.top_f = a.top + (size_t)waves * row_dwords;                // (only read / written by the affine kernel)
             a.bottom_f = a.bottom + (size_t)waves * row_dwords;
             a.n = cnt;
@@ -388,7 +413,12 @@ void Engine::align_strips_device(int alg, long long n, const uint8_t *d_reads, c
             a.strips = strips;
             a.row_dwords = row_dwords;
             a.band = bs;
+            a.walk = walk;
             put_scoring(a);
+            return a;
+        };
+        for (int s = 0; s < strips; ++s) {
+            StripArgs a = strip_args(s);
             void *kargs[] = {&a};
             hip_check(hipLaunchKernel(fn, dim3((unsigned)cnt_waves), dim3(kWave), kargs, (size_t)lds.total, stream),
                       "hipLaunchKernel(align_strip_kernel)");
@@ -415,6 +445,20 @@ void Engine::align_strips_device(int alg, long long n, const uint8_t *d_reads, c
         t.strip_words = (long long)(cnt_waves * strip_words);
         t.wide_score = wide ? 1 : 0;
         t.band = bs;
+        if (ckpt) {
+            // the backward pass: per strip, last to first, re-fill it into the one region and let the walks cross it
+            hipLaunchKernelGGL(walk_init_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, (const EndCell *)d_ends_.get(), walk, cnt, AL);
+            hip_check(hipGetLastError(), "hipLaunchKernel(walk_init_kernel)");
+            for (int s : ckpt_rounds(strips)) {
+                StripArgs a = strip_args(s);
+                void *kargs[] = {&a};
+                hip_check(hipLaunchKernel(refill_fn, dim3((unsigned)cnt_waves), dim3(kWave), kargs, (size_t)lds.total, stream),
+                          "hipLaunchKernel(align_strip_kernel, re-fill)");
+                hipLaunchKernelGGL(traceback_ckpt_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, t, walk, s);
+                hip_check(hipGetLastError(), "hipLaunchKernel(traceback_ckpt_kernel)");
+            }
+            continue;
+        }
         void *targs[] = {&t};
         hip_check(hipLaunchKernel(band ? (const void *)&traceback_band_kernel : (const void *)&traceback_kernel, dim3((unsigned)((cnt + 255) / 256)),
                                   dim3(256), targs, 0, stream),

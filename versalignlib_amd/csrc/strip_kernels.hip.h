@@ -44,7 +44,19 @@ struct StripArgs {
     short gap_read, gap_ref;
     short open_read, ext_read, open_ref, ext_ref;     // affine
     BandShape band;             // BAND kernels: the block band (band_window.h)
+    const WalkState *walk;      // kCkptRefill: the walk state of the call's pairs (which waves re-fill, and up to which column)
 };
+
+// Checkpointed traceback (trace_checkpoints = 1; ckpt_plan.h): the two extra passes are instances of align_strip_kernel, so
+// that the forward pass, the re-fill and the full-pointer path compute the same cells with the same instructions.
+//   kCkptForward: no pointer stream (its stores and the code arithmetic are compiled out); the host hands every strip a
+//                 boundary row of its own to keep (StripArgs.bottom), the end cell is found as ever.
+//   kCkptRefill:  strip `strip` once more, WITH pointers, into the one region (StripArgs.ptr) from checkpoint row strip - 1
+//                 (StripArgs.top).  A wave reads the walk state of its two pairs: a pair is active when its walk has not ended
+//                 and its current row lies in this strip; a wave with no active pair returns at once, otherwise it sweeps the
+//                 columns [0, c] only, c the larger current column of its active pairs -- a path never moves right, and the
+//                 cells left of and above a cell do not depend on cells to its right.  No end cell, no bottom row.
+constexpr int kCkptNone = 0, kCkptForward = 1, kCkptRefill = 2;
 
 #ifdef VALIGN_TU_ALIGN      // not a template: defined once, in engine_align.hip
 // First position of each read / ref whose base class is 0 (else R / F): one wave per pair.
@@ -165,11 +177,14 @@ __device__ __forceinline__ StripRefBytes strip_ring_request(const uint8_t *ref_a
 // pointer region starts at c_lo.  A cell outside its own row's window is forced to H = E = F = 0 (the walk never reads its code:
 // it stops on reaching 0 and at the window's edge, traceback_band_kernel); the row above reads as 0 outside the columns
 // [p_lo, p_lo + p_w) the previous strip swept.
-template <int K, int ALG, bool AFFINE = false, bool SSE = false, bool BAND = false>
+template <int K, int ALG, bool AFFINE = false, bool SSE = false, bool BAND = false, int CKPT = kCkptNone>
 __global__ void __launch_bounds__(64)
 align_strip_kernel(const StripArgs args) {
     static_assert(!(AFFINE && SSE), "the SSE / AVX kernels have linear gaps only");
     static_assert(!BAND || (ALG == kAlgSW && !SSE), "bands: Smith-Waterman with the default tie-breaks");
+    static_assert(CKPT == kCkptNone || (!SSE && !BAND), "checkpointed traceback: unbanded strips with the default tie-breaks");
+    constexpr bool kPointers = CKPT != kCkptForward;                  // the pass stores a pointer stream
+    constexpr bool kEndCell = CKPT != kCkptRefill;                    // the pass tracks and writes the end cell
     constexpr int W = AFFINE ? 2 * K : K;                             // pointer words per lane and block
     constexpr int G = 64;
     using geo = Geo<G, K>;
@@ -178,6 +193,20 @@ align_strip_kernel(const StripArgs args) {
     const int R = args.R;
     const int pad_total = args.strips * geo::kRows - R;             // padding rows above row 0, all in strip 0
     const int row0 = args.strip * geo::kRows - pad_total;           // read position of this strip's first row
+
+    // kCkptRefill: columns [0, col_limit) -- up to the current column of the wave's active walks (uniform: before any barrier)
+    int col_limit = 0;
+    if constexpr (CKPT == kCkptRefill) {
+        const long long p0 = (long long)blockIdx.x * geo::kPairs;
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            if (p0 + half >= args.n) continue;
+            const WalkState st = args.walk[p0 + half];
+            if (st.done || ckpt_strip_of_row(st.i, pad_total, geo::kRows) != args.strip) continue;
+            col_limit = st.j + 1 > col_limit ? st.j + 1 : col_limit;
+        }
+        if (col_limit <= 0) return;
+    }
 
     WaveTables w;
     if (!strip_ring_setup<K>(args.reads, args.n, R, args.F, args.match, args.mismatch, row0, w)) return;
@@ -188,7 +217,7 @@ align_strip_kernel(const StripArgs args) {
         if (args.strip > 0) band_rows_window(args.band, row0 - geo::kRows, row0 - 1, R, args.F, p_lo, p_w);
         p_lo -= c_lo;
     }
-    const int F = args.F - c_lo;                        // (columns from c_lo on)
+    const int F = CKPT == kCkptRefill ? col_limit : args.F - c_lo;      // (columns from c_lo on)
 
     const unsigned lane_base = lds_offset(w.prof) + l * geo::kLaneBytes;
     // slab numbers of this lane's column: ring entry (j mod 128), two bytes (pair A, pair B)
@@ -272,7 +301,7 @@ align_strip_kernel(const StripArgs args) {
     const unsigned *top = args.top + pp * args.row_dwords + c_lo, *top_f = args.top_f + pp * args.row_dwords + c_lo;
     unsigned *bottom = args.bottom + pp * args.row_dwords + c_lo, *bottom_f = args.bottom_f + pp * args.row_dwords + c_lo;
     const int row_dwords = args.row_dwords - c_lo;
-    const bool has_top = args.strip > 0, has_bottom = args.strip + 1 < args.strips;
+    const bool has_top = args.strip > 0, has_bottom = CKPT != kCkptRefill && args.strip + 1 < args.strips;
     // BAND: the row above at column c_lo - 1 (the diagonal of lane 0's first cell), where the previous strip swept it
     if (BAND && l == 0 && has_top && (unsigned)(-1 - p_lo) < (unsigned)p_w) up0 = as_pk(top[-1]);
     // 64 columns of the row above per lane-register, fetched 64 steps ahead (row_dwords covers the reads)
@@ -281,7 +310,7 @@ align_strip_kernel(const StripArgs args) {
     unsigned topf_cur = border_f_bits, topf_next = (AFFINE && has_top) ? top_f[lane] : border_f_bits;
     unsigned bot_acc = 0u, botf_acc = 0u;
 
-    const int steps = (ALG == kAlgSW) ? (((BAND ? cols : F) + G - 1 + 7) / 8) * 8 : args.blocks8 * 8;   // whole 8-step blocks
+    const int steps = (ALG == kAlgSW || CKPT == kCkptRefill) ? (((BAND ? cols : F) + G - 1 + 7) / 8) * 8 : args.blocks8 * 8;   // whole 8-step blocks
     for (int t = 0; t < steps; ++t) {
         if ((t & 63) == 0) {
             top_cur = top_next;
@@ -323,7 +352,7 @@ align_strip_kernel(const StripArgs args) {
                 const s16x2 e_open = gap_add(Hl[q], o_read), e_extd = gap_add(El[q], e_read);
                 const s16x2 e = pk_max(e_extd, e_open);
                 El[q] = e;
-                code_g[q] = pk_min_u(e - e_open, one);
+                if constexpr (kPointers) code_g[q] = pk_min_u(e - e_open, one);
                 m[q] = pk_max(d[q], e);
             }
             s16x2 h = up0, f = fup0, hs = pk(0);
@@ -336,10 +365,13 @@ align_strip_kernel(const StripArgs args) {
                     if ((unsigned)(j - win_lo[q]) >= (unsigned)win_w[q]) h = f = El[q] = pk(0);     // outside the row's window
                 }
                 Hl[q] = h;
-                const s16x2 nd = pk_min_u(h - d[q], one), nf = pk_min_u(h - f, one);
-                code[q] = (s16x2)((u16x2)nd << (u16x2)nf);
-                code_g[q] = pk_mad_u(code_g[q], two, pk_min_u(f - f_open, one));
-                if (ALG == kAlgSW) {
+                if constexpr (kPointers) {
+                    const s16x2 nd = pk_min_u(h - d[q], one), nf = pk_min_u(h - f, one);
+                    code[q] = (s16x2)((u16x2)nd << (u16x2)nf);
+                    code_g[q] = pk_mad_u(code_g[q], two, pk_min_u(f - f_open, one));
+                }
+                if constexpr (!kEndCell) {              // (the re-fill tracks no end cell)
+                } else if (ALG == kAlgSW) {
                     const s16x2 changed = (rb[q] - h) >> fifteen;
                     fc[q] = as_pk((as_u32(changed) & as_u32(tt)) | (~as_u32(changed) & as_u32(fc[q])));
                     rb[q] = pk_max(rb[q], h);
@@ -347,7 +379,7 @@ align_strip_kernel(const StripArgs args) {
                     hs = pk_mad_u(h, sel[q], hs);
                 }
             }
-            if (ALG == kAlgNW) {
+            if (ALG == kAlgNW && kEndCell) {
                 const s16x2 nb = pk_max(rb[0], hs);
                 const s16x2 changed = (rb[0] - nb) >> fifteen;
                 fc[0] = as_pk((as_u32(changed) & as_u32(tt)) | (~as_u32(changed) & as_u32(fc[0])));
@@ -414,12 +446,15 @@ align_strip_kernel(const StripArgs args) {
                 const s16x2 ug = (ALG == kAlgSW) ? pk_sub_floor0(h, g_ref) : h + g_ref;
                 h = pk_max(m[q], ug);
                 if constexpr (BAND) h = (unsigned)(j - win_lo[q]) < (unsigned)win_w[q] ? h : pk(0);     // outside the row's window: 0
-                const s16x2 nu = pk_min_u(h - ug, one);
                 Hl[q] = h;
-                // back pointer: 0 if h == diag + S, else 1 if it came from above, else 2 (DIAG > UP > LEFT)
-                const s16x2 nd = pk_min_u(h - d[q], one);
-                code[q] = (s16x2)((u16x2)nd << (u16x2)nu);
-                if (ALG == kAlgSW) {
+                if constexpr (kPointers) {
+                    // back pointer: 0 if h == diag + S, else 1 if it came from above, else 2 (DIAG > UP > LEFT)
+                    const s16x2 nu = pk_min_u(h - ug, one);
+                    const s16x2 nd = pk_min_u(h - d[q], one);
+                    code[q] = (s16x2)((u16x2)nd << (u16x2)nu);
+                }
+                if constexpr (!kEndCell) {              // (the re-fill tracks no end cell)
+                } else if (ALG == kAlgSW) {
                     const s16x2 changed = (rb[q] - h) >> fifteen;          // 0xFFFF where h beats the row best
                     fc[q] = as_pk((as_u32(changed) & as_u32(tt)) | (~as_u32(changed) & as_u32(fc[q])));
                     rb[q] = pk_max(rb[q], h);
@@ -427,7 +462,7 @@ align_strip_kernel(const StripArgs args) {
                     hs = pk_mad_u(h, sel[q], hs);                          // picks the cell of the one tracked row
                 }
             }
-            if (ALG == kAlgNW) {
+            if (ALG == kAlgNW && kEndCell) {
                 const s16x2 nb = pk_max(rb[0], hs);
                 const s16x2 changed = (rb[0] - nb) >> fifteen;
                 fc[0] = as_pk((as_u32(changed) & as_u32(tt)) | (~as_u32(changed) & as_u32(fc[0])));
@@ -435,13 +470,15 @@ align_strip_kernel(const StripArgs args) {
             }
             h_last = h;
         }
+        if constexpr (kPointers) {
 #pragma unroll
-        for (int q = 0; q < K; ++q) acc[q] = pk_mad_u(acc[q], four, code[q]);
-        if (AFFINE) {
+            for (int q = 0; q < K; ++q) acc[q] = pk_mad_u(acc[q], four, code[q]);
+        }
+        if (AFFINE && kPointers) {
 #pragma unroll
             for (int q = 0; q < K; ++q) acc_g[q] = pk_mad_u(acc_g[q], four, code_g[q]);
         }
-        if ((t & 7) == 7) {
+        if (kPointers && (t & 7) == 7) {
             if constexpr (AFFINE) {               // K words of H codes followed by K words of gap codes
                 unsigned w8[2 * K];
 #pragma unroll
@@ -472,6 +509,7 @@ align_strip_kernel(const StripArgs args) {
     }
 
     // ---- end cell ----
+    if constexpr (!kEndCell) return;
     const int strip_pad = args.strip * geo::kRows;          // padded row of this strip's first row
 #pragma unroll
     for (int half = 0; half < 2; ++half) {

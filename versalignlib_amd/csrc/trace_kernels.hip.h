@@ -23,6 +23,7 @@
 #pragma once
 
 #include "band_window.h"
+#include "ckpt_plan.h"
 #include "dp_kernels.hip.h"
 
 namespace valign {
@@ -85,6 +86,16 @@ struct TraceArgs {
                               // starts at its window's first column, and a step out of the row's window ends the walk (START)
 };
 
+// Checkpointed traceback (trace_checkpoints = 1; ckpt_plan.h): what a pair's walk carries from one strip's round to the next.
+struct WalkState {
+    int i, j;                 // current cell: read / ref position
+    int h;                    // its value (Smith-Waterman: the walk stops where it reaches 0)
+    int k;                    // next output position of the two rows
+    int state;                // affine: 0 at H, 1 inside F (gap in the ref), 2 inside E
+    int done;                 // 1: the walk has ended and the coordinates are written
+};
+static_assert(sizeof(WalkState) == kWalkStateBytes, "ckpt_plan.h sizes the scratch with kWalkStateBytes per pair");
+
 typedef unsigned __attribute__((aligned(1))) u32_any_align;   // global dword access at any byte address
 
 // The walk of ONE pair (one lane): from the end cell back along the stored pointers, writing the two right-justified
@@ -96,10 +107,14 @@ typedef unsigned __attribute__((aligned(1))) u32_any_align;   // global dword ac
 // kernel (align_fill_tag_kernel<..., FUSED>) the copy it keeps in LDS.
 template <bool BYTE_ROWS = false,     // BYTE_ROWS: everything the walk touches sits in LDS (fused kernel) -- explicit LDS reads,
                                        // one byte store per step (no dword at an odd LDS address)
-          bool BAND = false>           // BAND: banded strips (TraceArgs.band)
+          bool BAND = false,           // BAND: banded strips (TraceArgs.band)
+          bool RESUME = false>         // RESUME: one round of the checkpointed traceback -- the walk starts from *ws instead of the end
+                                       // cell, reads the ONE pointer region (that of the strip whose first read row is `row_lo`), stops
+                                       // where its row leaves that strip's top and leaves its state in *ws; the coordinates are written
+                                       // by the round in which the walk ends (ws->done)
 __device__ __forceinline__ int trace_walk(const TraceArgs &a, const unsigned *ptr_pair, long long ptr_words, int half,
                                           const EndCell e, const uint8_t *read, const uint8_t *ref,
-                                          uint8_t *row_read, uint8_t *row_ref, short *out) {
+                                          uint8_t *row_read, uint8_t *row_ref, short *out, WalkState *ws = nullptr, int row_lo = 0) {
     const int R = a.R, F = a.F, AL = R + F, K = a.K;
     const int wpb = (a.affine && a.tagged != 2) ? 2 * K : K;      // words per lane and block of steps
     const int half_shift = half * 16;
@@ -114,6 +129,14 @@ __device__ __forceinline__ int trace_walk(const TraceArgs &a, const unsigned *pt
     unsigned out_r = 0, out_f = 0;         // up to 4 pending output bytes per row, newest in the low byte
     int pending = 0;
     int state = 0;                         // affine only: 0 at H, 1 inside F (gap in the ref), 2 inside E
+    bool paused = false;                   // RESUME: the row left the strip before the walk ended
+    if constexpr (RESUME) {
+        i = ws->i;
+        j = ws->j;
+        h = ws->h;
+        k = ws->k;
+        state = ws->state;
+    }
     // BAND: the window of the rows from band_row0 on (one block) and the first column of strip band_strip's region
     int band_row0 = 0x7FFFFFFF, band_lo = 0, band_width = 0, band_strip = -1, strip_lo = 0;
 
@@ -166,6 +189,14 @@ __device__ __forceinline__ int trace_walk(const TraceArgs &a, const unsigned *pt
                 if (i < 0) break;                       // row 0: START
             }
         }
+        if constexpr (RESUME) {
+            // the next cell lies in the strip above: its pointers are the next round's (column 0 of the NW variant, j < 0,
+            // needs none and is finished here)
+            if (i < row_lo && i >= 0 && j >= 0) {
+                paused = true;
+                break;
+            }
+        }
         int move;                                       // 0 DIAG, 1 UP (emit read, '-'), 2 LEFT
         if (j < 0) {
             move = 1;                                   // column 0 of the NW variant: UP all the way
@@ -177,7 +208,7 @@ __device__ __forceinline__ int trace_walk(const TraceArgs &a, const unsigned *pt
             if (a.strip_rows > 0) {                     // row strips: each has its own pointer region
                 const int strip = p / a.strip_rows;
                 p -= strip * a.strip_rows;
-                region = strip * a.strip_words;
+                if constexpr (!RESUME) region = strip * a.strip_words;
                 if constexpr (BAND) {
                     if (i < band_row0) {                // (rows only decrease: a new block)
                         band_row0 = (i + a.band.pad) / a.band.block_rows * a.band.block_rows - a.band.pad;
@@ -273,6 +304,15 @@ __device__ __forceinline__ int trace_walk(const TraceArgs &a, const unsigned *pt
         row_read[k + 1 + x] = (uint8_t)(out_r >> (8 * x));
         row_ref[k + 1 + x] = (uint8_t)(out_f >> (8 * x));
     }
+    if constexpr (RESUME) {
+        ws->i = i;
+        ws->j = j;
+        ws->h = h;
+        ws->k = k;
+        ws->state = state;
+        ws->done = paused ? 0 : 1;
+        if (paused) return R + F;
+    }
 
     out[0] = (short)(k + 1);
     out[1] = (short)(AL - 1);
@@ -316,6 +356,30 @@ traceback_kernel(const TraceArgs a) {
 __global__ void __launch_bounds__(256)
 traceback_band_kernel(const TraceArgs a) {
     traceback_pairs<true>(a);
+}
+
+// ---- checkpointed traceback (trace_checkpoints = 1): the walk in rounds, one strip's pointer region at a time ----
+// Before the first round: every pair's walk starts at its end cell.
+__global__ void __launch_bounds__(256)
+walk_init_kernel(const EndCell *ends, WalkState *ws, long long n, int AL) {
+    const long long pair = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pair >= n) return;
+    const EndCell e = ends[pair];
+    ws[pair] = WalkState{e.read_pos, e.ref_pos, e.score, AL - 2, 0, 0};
+}
+// Round `strip`: one lane per pair whose walk has not ended and whose current row lies in this strip (a pair whose end cell
+// lies in an earlier strip starts in that strip's round) walks a.ptr -- the one region, just re-filled for this strip -- until
+// its row leaves the strip's top.  a.strip_rows: rows per strip; a.strip_words is not used.
+__global__ void __launch_bounds__(256)
+traceback_ckpt_kernel(const TraceArgs a, WalkState *ws, int strip) {
+    const long long pair = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pair >= a.n) return;
+    if (ws[pair].done || ckpt_strip_of_row(ws[pair].i, a.pad_rows, a.strip_rows) != strip) return;
+    const int AL = a.R + a.F, wpb = a.affine ? 2 * a.K : a.K;
+    const long long ptr_words = (long long)a.blocks8 * kWave * wpb;           // one wave's region: a pair-of-pairs
+    uint8_t *row_read = a.rows + pair * 2 * AL;
+    trace_walk<false, false, true>(a, a.ptr + (pair / 2) * ptr_words, ptr_words, (int)(pair & 1), EndCell{}, a.reads + pair * a.R,
+                                   a.refs + pair * a.F, row_read, row_read + AL, a.idx + pair * 4, ws + pair, strip * a.strip_rows - a.pad_rows);
 }
 
 // Result rows are right-justified strings behind zeros (650-byte rows whose strings are ~160 bytes for Smith-Waterman

@@ -85,6 +85,7 @@ def lib():
         L.valign_hip_set_traceback_policy.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_band_width.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_band_alignments.argtypes = [vp, ctypes.c_int]
+        L.valign_hip_set_trace_checkpoints.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_pointer_scratch_cap_mb.argtypes = [vp, ctypes.c_longlong]
         L.valign_hip_set_host_packing.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_half_float_cells.argtypes = [vp, ctypes.c_int]
@@ -106,7 +107,7 @@ def lib():
 EXPORTED_SYMBOLS = (
     "spawn_alignment_kernel", "set_parameters", "set_logger", "delete_alignment_kernel",
     "valign_hip_device_count", "valign_hip_shard_range", "valign_hip_engine_create", "valign_hip_engine_destroy",
-    "valign_hip_set_traceback_policy", "valign_hip_set_pointer_scratch_cap_mb", "valign_hip_set_host_packing", "valign_hip_set_half_float_cells", "valign_hip_host_register", "valign_hip_host_unregister", "valign_hip_set_band_width", "valign_hip_set_band_alignments", "valign_hip_set_score_width", "valign_hip_set_ragged_batching", "valign_hip_score_device", "valign_hip_align_device", "valign_hip_score_host", "valign_hip_align_host", "valign_hip_describe",
+    "valign_hip_set_traceback_policy", "valign_hip_set_pointer_scratch_cap_mb", "valign_hip_set_host_packing", "valign_hip_set_half_float_cells", "valign_hip_host_register", "valign_hip_host_unregister", "valign_hip_set_band_width", "valign_hip_set_band_alignments", "valign_hip_set_trace_checkpoints", "valign_hip_set_score_width", "valign_hip_set_ragged_batching", "valign_hip_score_device", "valign_hip_align_device", "valign_hip_score_host", "valign_hip_align_host", "valign_hip_describe",
     "valign_hip_last_error",
 )
 
@@ -183,6 +184,13 @@ class Engine:
         """1: alignments (align_device / align_host) are banded Smith-Waterman alignments on the same block band as the
         scores when band_width > 0; 0 (default): every cell whatever band_width says."""
         if lib().valign_hip_set_band_alignments(self._h, int(on)) != 0:
+            raise HipKernelError(_err())
+
+    def set_trace_checkpoints(self, on):
+        """1: long-read alignments on the plain row strips keep one boundary row per strip and one strip's pointers, and
+        re-fill strip after strip along the walk (identical results, a scratch that grows with R + F instead of R x F);
+        0 (default): every pointer of every strip.  Other paths run as ever (describe: ran_align_fill)."""
+        if lib().valign_hip_set_trace_checkpoints(self._h, int(on)) != 0:
             raise HipKernelError(_err())
 
     def score_device(self, opt, reads, refs, scores=None, stream=None):
