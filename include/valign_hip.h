@@ -239,6 +239,51 @@ int valign_hip_score_host(valign_hip_engine *e, int opt, int n, const char *cons
 int valign_hip_align_host(valign_hip_engine *e, int opt, int n, const char *const *reads,
                           const char *const *refs, void *rows, short *idx, int threads);
 
+/* ---- compact alignment results: placed CIGARs from the device ----
+ * A second result format beside the rows: per pair one fixed record and a run of 32-bit ops, encoded ON THE DEVICE behind the
+ * traceback, so every alignment path feeds it (fused small calls, the register geometries, row strips, int32 strips, banded
+ * strips, checkpointed strips; both traceback policies) and every key of the alignment path applies unchanged.  The rows stay
+ * in an engine-owned device scratch (a chunk of the call at a time: "cigar_rows_scratch_bytes") and never cross PCIe.
+ *   op ......... length << 4 | code, BAM codes M 0, I 1, D 2, = 7, X 8, in reading order.  Columns are classified exactly as
+ *                vh_cigar does (valign_host.h): '-' in the read row is D, '-' in the ref row is I, otherwise M -- or, with
+ *                extended = 1, '=' where the two bytes are equal ignoring case and X where not.  The ops rendered as text are
+ *                vh_cigar's string of the rows valign_hip_align_device returns for the same pair.  No soft clips and no
+ *                N / S / H / P ops: read_begin / read_end say what part of the read is aligned.
+ *   coordinates  0-based, half-open, in the read / reference as passed in: the ends are the fill's end cell + 1, the
+ *                begins the ends minus the non-gap bases of the rows.  This is what the rows cannot say: WHERE in the
+ *                reference a Smith-Waterman alignment lies.
+ *   score ...... the returned alignment re-scored under the engine's scoring: match / mismatch between two ACGT bases of
+ *                either case, 0 for any other pair of bytes; linear gaps gap_read per '-' in the read row and gap_ref per '-'
+ *                in the ref row; affine gaps open + (k - 1) * extend per maximal run of k and direction.  int32, defined for
+ *                both algorithms and every path.
+ *   empty ...... an empty alignment (Smith-Waterman maximum 0; an NW-variant read that starts with an invalid byte) is
+ *                n_ops = 0 with all four coordinates and the score 0.                                                       */
+typedef struct {                     /* 24 bytes */
+    int32_t read_begin, read_end;
+    int32_t ref_begin, ref_end;
+    int32_t score;
+    uint32_t n_ops;                  /* ops this alignment has (may exceed what was stored, below) */
+} valign_hip_aln;
+
+/* Device-resident: asynchronous on hip_stream like valign_hip_align_device, no host round trip.  d_recs = n records,
+ * d_ops = n * ops_stride uint32.  A pair stores its first min(n_ops, ops_stride) ops at d_ops + pair * ops_stride; n_ops
+ * always says how many there are, so the caller sees an overflow per pair (words past a pair's ops are not written).
+ * extended: 0 = M, 1 = '=' / X.  opt & 0xF > 1 does nothing.                                                               */
+int valign_hip_align_cigar_device(valign_hip_engine *e, int opt, long long n, const void *d_reads,
+                                  const void *d_refs, int extended, void *d_recs, void *d_ops,
+                                  int ops_stride, void *hip_stream);
+
+/* Host pointers in, packed results out: recs[n], offsets[n + 1] (offsets[0] = 0), pair p's ops are
+ * ops[offsets[p] .. offsets[p + 1]).  The gather -> H2D -> fill -> walk pipeline of valign_hip_align_host with the copy-back
+ * replaced: per chunk the device counts, scans and packs, and ONE copy brings the records and the ops back (24 bytes + 4 per op
+ * and pair instead of the rows; "cigar_d2h_bytes" of valign_hip_describe).  If the call needs more than ops_cap ops it returns
+ * non-zero, *ops_needed holds the total and recs / offsets are complete, so the caller can size the retry exactly (on success
+ * *ops_needed = offsets[n]).  n = 0 sets offsets[0] = 0; opt & 0xF > 1 writes nothing.                                      */
+int valign_hip_align_cigar_host(valign_hip_engine *e, int opt, int n, const char *const *reads,
+                                const char *const *refs, int extended, valign_hip_aln *recs,
+                                uint32_t *ops, long long ops_cap, long long *offsets,
+                                long long *ops_needed, int threads);
+
 /* Page-lock a host range and map it for the device (hipHostRegister behind a C symbol, so that an FFI caller needs no
  * HIP binding).  valign_hip_align_host into result buffers that lie inside a registered range -- or inside memory the
  * caller page-locked itself -- skips the library's pinned staging and its host-side copy: the device's copy engine
@@ -263,7 +308,9 @@ int valign_hip_set_half_float_cells(valign_hip_engine *e, int mode);
  * mixed them) and "ran_align_fill" (the alignment path and fill kernel: fused_tag, tag_prof_key, ..., strip, strip_wide,
  * strip_ckpt) report what the engine's last score / alignment call actually launched ("none" before any);
  * "align_ptr_bytes_per_pair" / "align_ckpt_bytes_per_pair" are the pointer-stream and checkpoint bytes a pair holds in the plan
- * of the last alignment call, "align_scratch_bytes" the pointer scratch the engine holds after it.                     */
+ * of the last alignment call, "align_scratch_bytes" the pointer scratch the engine holds after it.
+ * "ran_result_format" is "rows" or "cigar" for the last alignment call, "cigar_d2h_bytes" what the last
+ * valign_hip_align_cigar_host call copied back, "cigar_rows_scratch_bytes" the rows scratch of the compact format.       */
 int valign_hip_describe(valign_hip_engine *e, int opt, long long n, char *buf, int cap);
 
 const char *valign_hip_last_error(void);

@@ -19,6 +19,7 @@
  *   vh_pad ................... pad()                   (src/util/versalignUtil.cpp:17-33)
  *   vh_parse_fasta ........... FastaProvider           (src/util/versalignUtil.h:52-92)
  *   vh_cigar ................. (none; the rows main.cpp:147-189 prints, run-length encoded)
+ *   vh_cigar_ops / _text ..... (none; the same runs as 32-bit ops, the format valign_hip_align_cigar_* return)
  *
  * All functions return 0 on success and a negative value on failure unless stated
  * otherwise; vh_last_error() gives the message of the most recent failure on the
@@ -130,6 +131,17 @@ int vh_pad(const char *blob, int count, char fill, uint8_t **out, int *length);
  * An empty alignment gives "".                                                                   */
 int vh_cigar(const uint8_t *read_row, const uint8_t *ref_row, int start, int end, int extended,
              char *buf, int cap);
+
+/* The same alignment as 32-bit ops, the compact result format of libHIPKernel.so (valign_hip.h, valign_hip_aln): one op per
+ * run, length << 4 | code with the BAM codes M 0, I 1, D 2, = 7, X 8, in reading order; columns are classified exactly as
+ * vh_cigar does.  For hosts that stay on the plugin ABI, and the CPU statement of what the device encoder writes.  Returns the
+ * number of ops, or -1 on bad input or when there are more than cap of them (an error, nothing is truncated).              */
+int vh_cigar_ops(const uint8_t *read_row, const uint8_t *ref_row, int start, int end, int extended,
+                 uint32_t *ops, int cap);
+
+/* Ops -> text ("3=2I5="): vh_cigar's string for the rows the ops came from.  Returns the length, -1 when cap is too small or
+ * an op's code is none of BAM's.                                                                                           */
+int vh_cigar_text(const uint32_t *ops, int n_ops, char *buf, int cap);
 
 void vh_free(void *ptr);
 

@@ -8,6 +8,7 @@
 //   engine_long.hip ..... long reads: row strips (score_long_kernel) and the banded block chain (score_band_kernel)
 //   engine_align.hip .... compute_alignments: fill + traceback launches, row strips, the fused small-batch launch, the
 //                         host-pointer pipeline with its copy-issuing thread (reference: DefaultKernel.cpp:21-50, 204-525)
+//   engine_cigar.hip .... the compact result format: records + CIGAR ops encoded on the device behind the walks (cigar_kernels.hip.h)
 //   hip_plugin.hip ...... the plugin ABI and the flat C API over it
 // The closest reference precedent for the staging loops is the OpenCL backend's gather / copy / launch / collect loop
 // (src/Kernels/OpenCL/OpenCLKernel.cpp:57-108); unlike it, chunks here are large, asynchronous and overlapped.
@@ -38,6 +39,7 @@
 #include "host_pipeline.h"
 #include "kernel_instances.hip.h"
 #include "band_kernels.hip.h"
+#include "cigar_kernels.hip.h"
 #include "long_kernels.hip.h"
 #include "pack_kernels.hip.h"
 #include "ragged_kernels.hip.h"
@@ -153,7 +155,7 @@ public:
         if (!env) return;
         static const char *const known[] = {"no_sym", "no_tag", "no_f16", "no_fused", "no_prof_key", "no_overlap", "no_band_chain",
                                             "force_long", "wide_align", "strip_k", "no_single_strip", "no_direct_out", "ragged_min", "chunk_bytes",
-                                            "align_chunk_bytes", "direct_bytes", "scratch_cap_mb", "whole_rows", "short_strips"};
+                                            "align_chunk_bytes", "direct_bytes", "scratch_cap_mb", "whole_rows", "short_strips", "cigar_rows_mb", "cigar_lanes"};
         std::string s(env);
         for (size_t at = 0; at <= s.size();) {
             const size_t end = std::min(s.find(',', at), s.size());
@@ -426,6 +428,18 @@ public:
     void align_host(int opt, int n, const char *const *reads, const char *const *refs, Sink alignments,
                     int threads);
 
+    // ---- the compact result format (valign_hip.h: valign_hip_aln + ops; engine_cigar.hip) ----
+    // Both run the alignment paths above unchanged, into an engine-owned rows scratch (a chunk of the call at a time), and
+    // encode each part's rows behind its walk, on the walk's stream, while the part's end cells are still in d_ends_.
+    // Device-resident: records and ops at a fixed stride, asynchronous on `stream`.
+    void align_cigar_device(int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int extended, CigarRec *d_recs,
+                            unsigned *d_ops, int ops_stride, hipStream_t stream);
+    // Host pointers: per chunk records on the device (count), an exclusive scan of n_ops, then ops packed at their offsets
+    // beside the records (emit) and ONE copy back.  false: the call needs more than ops_cap ops (*ops_needed; recs and
+    // offsets are complete).
+    bool align_cigar_host(int opt, int n, const char *const *reads, const char *const *refs, int extended, CigarRec *recs,
+                          unsigned *ops, long long ops_cap, long long *offsets, long long *ops_needed, int threads);
+
     // host-side phases of the last score_host / align_host call
     std::string host_phases() const;
 
@@ -500,6 +514,18 @@ private:
     void ensure_trace_scratch(long long pairs, size_t bytes_per_pp, long long ppw, hipStream_t stream);
 
     void ensure_align_staging(long long pairs);
+
+    // Where the records (and, device API, the ops) of the alignment call in progress go: set by the two cigar entry points
+    // around their align_device / align_fused calls, null otherwise.  Pair 0 of the call is recs[0].
+    struct CigarSink {
+        CigarRec *recs;
+        unsigned *ops;              // null: records only (host path: the ops follow the chunk's scan)
+        int ops_stride, extended;
+    };
+    // encode `cnt` pairs from pair `begin` of the call on `stream`: rows / idx / ends are those of pair `begin`
+    void launch_cigar(hipStream_t stream, const uint8_t *rows, const short *idx, const EndCell *ends, long long begin, long long cnt);
+    void launch_cigar_args(hipStream_t stream, CigarArgs &a);
+    void ensure_cigar_scratch(int slots, long long pairs, hipStream_t stream);
 
     // gather / scatter between the caller's scattered blocks and the staging: host_pipeline.h (host-only, sanitizer-tested)
     template <typename Sink>
@@ -634,6 +660,10 @@ private:
     static constexpr unsigned kRanF16 = 1, kRanInt16 = 2, kRanInt32 = 4;
     unsigned ran_score_cells_ = 0;
     const char *ran_align_fill_ = "none";
+    const char *ran_result_format_ = "rows";             // of the last alignment call: rows / cigar (describe)
+    long long cigar_d2h_bytes_ = 0;                      // what the last align_cigar_host call copied back
+    const CigarSink *cigar_ = nullptr;
+    long long cigar_pairs_[2] = {0, 0};                  // pairs the cigar scratch of each slot holds
     long long align_ptr_bytes_per_pair_ = 0;             // pointer-stream bytes per pair of the last alignment call's plan (describe)
     long long align_ckpt_bytes_per_pair_ = 0;            // ... and what StripCkpt keeps beside it: checkpoint rows + walk state
     int cu_count_ = 0;
@@ -662,6 +692,15 @@ private:
     DeviceBuffer<uint8_t> d_rows_[kSlots];
     DeviceBuffer<short> d_idx_[kSlots];
     DeviceBuffer<uint8_t> d_packed_rows_[kSlots];                // the chunk's rows without their all-zero leading columns
+    // compact result format: the rows the walks write (never copied out), per chunk parity; host path: count-pass records,
+    // scanned offsets, the packed records + ops as they cross PCIe
+    DeviceBuffer<uint8_t> d_cig_rows_[2];
+    DeviceBuffer<short> d_cig_idx_[2];
+    DeviceBuffer<CigarRec> d_cig_recs_[2];
+    DeviceBuffer<long long> d_cig_offsets_[2];
+    DeviceBuffer<uint8_t> d_cig_out_[2];
+    PinnedBuffer<uint8_t> h_cig_out_[2];
+    PinnedBuffer<long long> h_cig_total_;
     DeviceBuffer<int> d_min_start_;                              // per slot: first column of the chunk's rows that holds a string
     PinnedBuffer<int> h_min_start_;                              // ... on its way to the host
     DeviceBuffer<unsigned> d_brow_;                              // long-read path: strip boundary rows

@@ -114,6 +114,7 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
     const int alg = opt & 0xF;
     if (alg > 1 || n <= 0) return false;
     ran_align_fill_ = "none";
+    ran_result_format_ = cigar_ ? "cigar" : "rows";
     align_ckpt_bytes_per_pair_ = 0;
     const AlignRoute route = valign::align_route(rule_inputs(), alg, route_facts(false));       // (throws what the mode refuses)
     hip_check(hipSetDevice(device_), "hipSetDevice");
@@ -227,6 +228,8 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
             hip_check(hipLaunchKernel((const void *)&compact_rows_kernel, dim3((unsigned)(2 * cnt)), dim3(256), cargs, 0, walk_stream),
                       "hipLaunchKernel(compact_rows_kernel)");
         }
+        // records (and ops) of the part, behind its walk and before the part's end cells and region are reused
+        if (cigar_) launch_cigar(walk_stream, t.rows, t.idx, part_ends, begin, cnt);
         if (helper) {
             hip_check(hipEventRecord(trace_done_[part.region].get(), walk_stream), "hipEventRecord");
             region_used[part.region] = true;
@@ -287,8 +290,17 @@ bool Engine::align_fused(int alg, long long n, const uint8_t *d_reads, const uin
     put_scoring(f);
     f.out_rows = d_rows;
     f.out_idx = d_idx;
+    if (cigar_) {                          // the end cells leave the wave's LDS too: the encoder places the alignment with them
+        if (sizeof(EndCell) * (size_t)n > d_ends_.bytes()) {
+            hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+            if (trace_stream_) hip_check(hipStreamSynchronize(trace_stream_.get()), "hipStreamSynchronize");
+            d_ends_.reserve(sizeof(EndCell) * (size_t)n, "end cells");
+        }
+        f.ends = d_ends_.get();
+    }
     const void *fn = best->kernel[alg];
     ran_align_fill_ = ran_fill_name(AlignRoute::Fused);
+    ran_result_format_ = cigar_ ? "cigar" : "rows";
     align_ptr_bytes_per_pair_ = (long long)best->G * best_blocks * best->K * 4 / 2;
     if (best_total > kDefaultBlockLds)
         hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, best_total),
@@ -297,6 +309,7 @@ bool Engine::align_fused(int alg, long long n, const uint8_t *d_reads, const uin
     void *fargs[] = {&f};
     hip_check(hipLaunchKernel(fn, dim3((unsigned)((n + ppw - 1) / ppw)), dim3(kWave), fargs, (size_t)best_total, stream),
               "hipLaunchKernel(align_fill_tag_kernel, fused)");
+    if (cigar_) launch_cigar(stream, d_rows, d_idx, d_ends_.get(), 0, n);
     return true;
 }
 
@@ -457,12 +470,14 @@ void Engine::align_strips_device(int alg, long long n, const uint8_t *d_reads, c
                 hipLaunchKernelGGL(traceback_ckpt_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, t, walk, s);
                 hip_check(hipGetLastError(), "hipLaunchKernel(traceback_ckpt_kernel)");
             }
+            if (cigar_) launch_cigar(stream, t.rows, t.idx, d_ends_.get(), begin, cnt);
             continue;
         }
         void *targs[] = {&t};
         hip_check(hipLaunchKernel(band ? (const void *)&traceback_band_kernel : (const void *)&traceback_kernel, dim3((unsigned)((cnt + 255) / 256)),
                                   dim3(256), targs, 0, stream),
                   "hipLaunchKernel(traceback_kernel)");
+        if (cigar_) launch_cigar(stream, t.rows, t.idx, d_ends_.get(), begin, cnt);      // (before the next chunk's fill reuses d_ends_)
     }
 }
 

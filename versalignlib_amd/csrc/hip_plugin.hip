@@ -558,6 +558,38 @@ VALIGN_EXPORT int valign_hip_align_host(valign_hip_engine *e, int opt, int n, co
     });
 }
 
+static_assert(sizeof(valign_hip_aln) == sizeof(valign::CigarRec) && sizeof(valign_hip_aln) == 24, "valign_hip_aln is the encoder's record");
+
+VALIGN_EXPORT int valign_hip_align_cigar_device(valign_hip_engine *e, int opt, long long n, const void *d_reads, const void *d_refs,
+                                                int extended, void *d_recs, void *d_ops, int ops_stride, void *hip_stream) {
+    if (!e) {
+        g_last_error = "null engine";
+        return 1;
+    }
+    return flat_guard([&] {
+        e->impl->align_cigar_device(opt, n, (const uint8_t *)d_reads, (const uint8_t *)d_refs, extended, (valign::CigarRec *)d_recs,
+                                    (unsigned *)d_ops, ops_stride, (hipStream_t)hip_stream);
+    });
+}
+
+VALIGN_EXPORT int valign_hip_align_cigar_host(valign_hip_engine *e, int opt, int n, const char *const *reads, const char *const *refs,
+                                              int extended, valign_hip_aln *recs, uint32_t *ops, long long ops_cap, long long *offsets,
+                                              long long *ops_needed, int threads) {
+    if (!e) {
+        g_last_error = "null engine";
+        return 1;
+    }
+    bool fits = true;
+    const int rc = flat_guard([&] {
+        fits = e->impl->align_cigar_host(opt, n, reads, refs, extended, (valign::CigarRec *)recs, ops, ops_cap, offsets, ops_needed, threads);
+    });
+    if (rc == 0 && !fits) {
+        g_last_error = "ops_cap is too small: the call needs " + std::to_string(*ops_needed) + " ops";
+        return 2;
+    }
+    return rc;
+}
+
 VALIGN_EXPORT int valign_hip_describe(valign_hip_engine *e, int opt, long long n, char *buf, int cap) {
     if (!e || !buf || cap <= 0) return 1;
     const std::string s = e->impl->describe(opt, n);

@@ -39,7 +39,7 @@ struct FillArgs {
     const uint8_t *reads;
     const uint8_t *refs;
     unsigned *ptr;            // pointer scratch: [wave][block of steps][lane of the wave][words per block] dwords
-    EndCell *ends;            // n
+    EndCell *ends;            // n (fused kernel: null, or where the end cells go beside the rows)
     long long n;
     int R, F;
     int prof_area, refc_stride, wave_lds;
@@ -509,8 +509,12 @@ __device__ __forceinline__ void write_end_cells(const FillArgs &args, const Wave
             out.ref_pos = (short)(last_ref < arg_col ? last_ref : arg_col);
         }
         if (l == 0 && pair < args.n) {
-            if (wave_ends) wave_ends[2 * grp + half] = out;
-            else args.ends[pair] = out;
+            if (wave_ends) {
+                wave_ends[2 * grp + half] = out;
+                if (args.ends) args.ends[pair] = out;      // (a caller that places the alignment: cigar_kernels.hip.h)
+            } else {
+                args.ends[pair] = out;
+            }
         }
     }
 }

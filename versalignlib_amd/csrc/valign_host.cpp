@@ -483,6 +483,69 @@ int vh_cigar(const uint8_t *read_row, const uint8_t *ref_row, int start, int end
     return len;
 }
 
+// The compact format's ops (valign_hip.h) on the CPU: vh_cigar's column rule and run lengths, 32 bits per run
+int vh_cigar_ops(const uint8_t *read_row, const uint8_t *ref_row, int start, int end, int extended, uint32_t *ops, int cap) {
+    if (!read_row || !ref_row || cap < 0 || (!ops && cap > 0) || start < 0 || end < start) {
+        fail("bad argument");
+        return -1;
+    }
+    int n = 0;
+    uint32_t run = 0, op = 0;
+    for (int c = start; c < end; ++c) {
+        const uint8_t a = read_row[c], b = ref_row[c];
+        if (a == 0 && b == 0) break;                      // the terminating NUL column
+        uint32_t now;
+        if (a == '-' && b != '-') now = 2;                // D
+        else if (b == '-' && a != '-') now = 1;           // I
+        else if (!extended) now = 0;                      // M
+        else now = ((a | 0x20) == (b | 0x20)) ? 7 : 8;    // = / X
+        if (run > 0 && now != op) {
+            if (n >= cap) {
+                fail("CIGAR op buffer too small");
+                return -1;
+            }
+            ops[n++] = (run << 4) | op;
+            run = 0;
+        }
+        op = now;
+        ++run;                                            // (end - start < 2^28: a run always fits its 28 bits)
+    }
+    if (run > 0) {
+        if (n >= cap) {
+            fail("CIGAR op buffer too small");
+            return -1;
+        }
+        ops[n++] = (run << 4) | op;
+    }
+    return n;
+}
+
+int vh_cigar_text(const uint32_t *ops, int n_ops, char *buf, int cap) {
+    if ((!ops && n_ops > 0) || n_ops < 0 || !buf || cap <= 0) {
+        fail("bad argument");
+        return -1;
+    }
+    static const char letters[] = "MIDNSHP=X";
+    int len = 0;
+    for (int i = 0; i < n_ops; ++i) {
+        const uint32_t code = ops[i] & 15u;
+        if (code > 8) {
+            fail("bad CIGAR op code");
+            return -1;
+        }
+        char tmp[16];
+        const int w = snprintf(tmp, sizeof tmp, "%u%c", ops[i] >> 4, letters[code]);
+        if (len + w >= cap) {
+            fail("CIGAR buffer too small");
+            return -1;
+        }
+        memcpy(buf + len, tmp, (size_t)w);
+        len += w;
+    }
+    buf[len] = 0;
+    return len;
+}
+
 void vh_free(void *ptr) { free(ptr); }
 
 }  // extern "C"

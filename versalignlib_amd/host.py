@@ -73,6 +73,9 @@ def lib():
                              ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int)]
         L.vh_cigar.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                ctypes.c_char_p, ctypes.c_int]
+        L.vh_cigar_ops.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                   ctypes.c_void_p, ctypes.c_int]
+        L.vh_cigar_text.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
         L.vh_free.restype = None
         L.vh_free.argtypes = [ctypes.c_void_p]
         _lib = L
@@ -264,6 +267,33 @@ def cigars(rows, idx, extended=False):
             raise PluginError(_err())
         out.append(buf.value.decode())
     return out
+
+
+def cigar_ops(rows, idx, extended=False, cap=None):
+    """The same alignments as 32-bit ops (vh_cigar_ops: length << 4 | BAM code), the compact result format of
+    Engine.align_cigar_device / align_cigar_host: -> a list of uint32 arrays.  `cap` (default: every column its own op)
+    smaller than an alignment's op count is an error."""
+    rows = np.ascontiguousarray(rows, dtype=np.uint8)
+    n, AL = rows.shape[0], rows.shape[2]
+    buf = np.zeros(AL if cap is None else max(int(cap), 0), dtype=np.uint32)
+    out = []
+    for i in range(n):
+        base = rows.ctypes.data + i * 2 * AL
+        got = lib().vh_cigar_ops(base, base + AL, int(idx[i, 0]), int(idx[i, 1]), 1 if extended else 0,
+                                 buf.ctypes.data, len(buf))
+        if got < 0:
+            raise PluginError(_err())
+        out.append(buf[:got].copy())
+    return out
+
+
+def cigar_text(ops):
+    """One alignment's ops (uint32: length << 4 | BAM code) -> its CIGAR string (vh_cigar_text)."""
+    ops = np.ascontiguousarray(ops, dtype=np.uint32)
+    buf = ctypes.create_string_buffer(12 * len(ops) + 16)
+    if lib().vh_cigar_text(ops.ctypes.data, len(ops), buf, len(buf)) < 0:
+        raise PluginError(_err())
+    return buf.value.decode()
 
 
 def pad(seqs, fill=b"\0"):
