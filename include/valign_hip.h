@@ -25,6 +25,10 @@
  *                                                         Smith-Waterman alignments on the scores' block band;
  *                                                         0 (default): every cell whatever band_width says
  *                                                         (opt-in: existing calls return what they did)
+ *       band_nw ......................................... 1: band_width > 0 also applies to the scores of the NW variant
+ *                                                         and, with band_alignments = 1, to its alignments (definition at
+ *                                                         valign_hip_set_band_nw); 0 (default): both are refused under a
+ *                                                         band.  Smith-Waterman calls are untouched.  Other values are refused
  *       trace_checkpoints ............................... 1: compute_alignments of long reads (the plain row strips: unbanded,
  *                                                         int16 cells, traceback_policy 0) keeps one boundary row per strip
  *                                                         and ONE strip's pointers and re-fills strip after strip along the
@@ -160,6 +164,34 @@ int valign_hip_set_band_width(valign_hip_engine *e, int diagonals);
 /* 1: valign_hip_align_device / _align_host return banded SW alignments when band_width > 0 (above); 0 (default):
  * unbanded alignments whatever band_width says.  Other values are refused.                                       */
 int valign_hip_set_band_alignments(valign_hip_engine *e, int on);
+
+/* The band for the reference's Needleman-Wunsch variant (key band_nw; the mode that places a whole read inside a reference
+ * window: the read is consumed end to end, the reference ends are free).  0 (default): NW-variant scores under band_width > 0
+ * and NW-variant alignments under band_alignments = 1 are refused, as ever.  1: band_width > 0 also applies to NW-variant
+ * scores and, together with band_alignments = 1, to NW-variant alignments (linear and affine gaps; traceback_policy = 1 stays
+ * refused under a band).  Smith-Waterman calls do not read the key.  DEFINITION -- windows exactly those of the Smith-Waterman
+ * band: row i (0-based read position) has the inclusive column window [lo_i, hi_i] of its block, on the (B, A) that
+ * valign_hip_describe reports after valign_hip_set_band_width ((16, 1) on the chain, (160, 4) on strips; band_window.h):
+ *   - a cell (i, j) with j outside [lo_i, hi_i] is ABSENT: never a candidate of a neighbour, never part of a maximum or an
+ *     arg-max; with affine gaps H, E and F are all absent there;
+ *   - the border row above read row 0 is present at every column, value 0, pointer START; the border column left of ref
+ *     column 0 is present at row i only where lo_i == 0, with the unbanded values: scores 0; alignments (i + 1) * gap_ref with
+ *     pointer UP (linear gaps), open_ref + i * ext_ref entered from F (affine gaps);
+ *   - present cells use the unbanded NW-variant recurrence and tie-breaks: DIAG > UP > LEFT (linear gaps); Gotoh with
+ *     DIAG > F > E and a gap opened rather than extended on ties (affine gaps);
+ *   - the score is max(0, present cells of the last read row, present cells of the last ref column);
+ *   - the alignment's end cell follows the reference's rule on present cells: end_i is the last row before the first invalid
+ *     read byte, end_j = min(last_ref, arg), arg the first strict arg-max over the present cells of row end_i, the running
+ *     best starting at the border column's value where lo == 0 and at absent otherwise.  Where that start cell is absent
+ *     (say last_ref < lo) the alignment is empty: all-zero rows, the four coordinates R + F - 1, an all-zero CIGAR record;
+ *   - calls with 2 * (band_width / 2) + 1 < ceil(F / R) are refused: the windows of consecutive blocks would not connect.  In
+ *     every accepted call each in-band cell has a present candidate, so a pointer never leads out of the band.
+ * Hence a band of at least 2 * max(R, F) gives exactly the unbanded NW-variant scores and alignments, and for scores
+ * per-cell band <= block band <= unbanded.  Scores run on int32 cells; alignments on the packed int16 strips where the
+ * sentinel that stands for "absent" is provably safe (band_nw_int16_ok, cell_rules.h), else on int32 cells
+ * ("ran_align_fill": strip_band / strip_wide_band).  tests/band_nw_ref.py restates the definition in numpy.  Other values
+ * than 0 / 1 are refused.                                                                                         */
+int valign_hip_set_band_nw(valign_hip_engine *e, int on);
 
 /* Checkpointed traceback for long-read alignments in bounded memory (key trace_checkpoints).  Reads beyond one register sweep
  * are filled in row strips of 64 K rows, and by default (0) every strip streams 2 bits per cell and pair (4 with affine gaps) to

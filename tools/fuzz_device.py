@@ -15,11 +15,16 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))     # band_nw_ref: the restated banded NW variant
 
 import torch                                                       # noqa: E402
 
 from oracle import cpu_ref                                          # noqa: E402
 from versalignlib_amd import hipkernel, synth                      # noqa: E402
+import band_nw_ref                                                 # noqa: E402
+
+
+NW_BAND_CASES = [0]             # cases that also ran the NW variant under the band
 
 
 def draw(rng):
@@ -81,6 +86,26 @@ def run(c):
             exp = cpu_ref.score_banded_sw(reads, refs, c["band"], osc, threads=8, block_rows=d["band_block_rows"], col_align=d["band_col_align"], affine=c["affine"])
             if not np.array_equal(got.cpu().numpy(), exp):
                 return "banded score_device differs"
+            # every other banded case also runs the NW variant under the band (band_nw = 1) against tests/band_nw_ref.py
+            # (decided by the seed: no further draw, so the sequence of cases is the one it was)
+            if c["seed"] % 2 and not c["policy"] and 2 * (c["band"] // 2) + 1 >= -(-F // R):
+                NW_BAND_CASES[0] += 1
+                eng.set_band_nw(1)
+                eng.set_band_alignments(1)
+                shape = (d["band_block_rows"], d["band_col_align"])
+                got = eng.score_device(1, d_reads, d_refs, stream=stream)
+                if stream is not None:
+                    stream.synchronize()
+                exp = np.minimum(band_nw_ref.score_banded_nw(reads, refs, c["band"], osc, *shape, affine=c["affine"]), 32767)
+                if not np.array_equal(got.cpu().numpy().astype(np.int64), exp):
+                    return "banded NW score_device differs"
+                if R * F * n <= 30_000_000:
+                    rows, idx = eng.align_device(1, d_reads, d_refs, stream=stream)
+                    if stream is not None:
+                        stream.synchronize()
+                    e_rows, e_idx = band_nw_ref.align_banded_nw(reads, refs, c["band"], osc, *shape, affine=c["affine"])
+                    if not (np.array_equal(rows.cpu().numpy(), e_rows) and np.array_equal(idx.cpu().numpy(), e_idx)):
+                        return "banded NW align_device differs"
             return None
         for opt in (0, 1):
             exp = cpu_ref.score(opt, reads, refs, osc, threads=8, affine=c["affine"], wide=True)
@@ -141,7 +166,7 @@ def main():
             if done % 25 == 0:
                 print("%d cases, %.0f s" % (done, time.time() - t0), flush=True)
         i += 1
-    print("ok: %d cases in %.0f s (seed %d)" % (done, time.time() - t0, a.seed))
+    print("ok: %d cases in %.0f s (seed %d), %d of them with the banded NW variant" % (done, time.time() - t0, a.seed, NW_BAND_CASES[0]))
     return 0
 
 

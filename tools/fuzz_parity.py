@@ -17,9 +17,14 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))     # band_nw_ref: the restated banded NW variant
 
 from oracle import cpu_ref                                          # noqa: E402
 from versalignlib_amd import build, host, synth                    # noqa: E402
+import band_nw_ref                                                 # noqa: E402
+
+
+NW_BAND_CASES = [0]             # cases that also ran the NW variant under the band
 
 
 def draw_case(rng, big=False, kinds=None):
@@ -110,6 +115,20 @@ def run_case(c, verbose=False):
         if not np.array_equal(got, exp):
             bad = np.nonzero(got != exp)[0]
             return "banded score (blocks %d / %d): %d of %d differ, first %s got %s exp %s" % (rows_, align_, bad.size, n, bad[:4], got[bad[:4]], exp[bad[:4]])
+        # every other banded case also runs the NW variant under the band (band_nw = 1; traceback_policy 0) against
+        # tests/band_nw_ref.py -- decided by the data seed, so the sequence of cases is the one it was
+        if c["data"].get("seed", 0) % 2 and c["policy"] != "sse" and 2 * (c["band"] // 2) + 1 >= -(-F // R):
+            NW_BAND_CASES[0] += 1
+            with host.Plugin(build.HIP_PLUGIN, R, F, band_width=c["band"], band_alignments=1, band_nw=1, **c["keys"]) as hip:
+                got = hip.score_alignments(host.NW, reads, refs)
+                exp = np.minimum(band_nw_ref.score_banded_nw(reads, refs, c["band"], sc, rows_, align_, affine=c["affine"]), 32767)
+                if not np.array_equal(got.astype(np.int64), exp):
+                    return "banded NW score (blocks %d / %d) differs" % (rows_, align_)
+                if R * F * n <= 40_000_000:
+                    rows, idx = hip.compute_alignments(host.NW, reads, refs)
+                    e_rows, e_idx = band_nw_ref.align_banded_nw(reads, refs, c["band"], sc, rows_, align_, affine=c["affine"])
+                    if not (np.array_equal(rows, e_rows) and np.array_equal(idx, e_idx)):
+                        return "banded NW alignments (blocks %d / %d) differ" % (rows_, align_)
         return None
     with host.Plugin(build.HIP_PLUGIN, R, F, **c["keys"]) as hip:
         for opt in (host.SW, host.NW):
@@ -169,7 +188,7 @@ def main():
             if i == a.only:
                 break
         i += 1
-    print("ok: %d cases in %.0f s (seed %d)" % (done, time.time() - t0, a.seed))
+    print("ok: %d cases in %.0f s (seed %d), %d of them with the banded NW variant" % (done, time.time() - t0, a.seed, NW_BAND_CASES[0]))
     return 0
 
 

@@ -27,6 +27,9 @@ echo "== ckpt_plan.h under AddressSanitizer + UBSan"
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/ckpt_plan_check.cpp" -o "$OUT/ckpt_plan_asan"
 "$OUT/ckpt_plan_asan"
 "$OUT/cell_rules_asan"
+echo "== the band_nw rules of cell_rules.h under AddressSanitizer + UBSan"
+g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/band_nw_rules_check.cpp" -o "$OUT/band_nw_rules_asan"
+"$OUT/band_nw_rules_asan"
 
 echo "== libvalignhost.so, valign-bench, libcpuref.so with $SAN"
 g++ -std=c++14 $SAN -fPIC -shared -Wall -pthread -I"$R/include" "$CS/valign_host.cpp" -o "$OUT/libvalignhost.so" -ldl

@@ -109,9 +109,21 @@ static_assert(((band_class_table() >> (3 * ('A' - 'A'))) & 7) == 0 && ((band_cla
                   ((band_class_table() >> (3 * ('N' - 'A'))) & 7) == 4 && ((band_class_table() >> (3 * 20)) & 7) == 4,
               "classes of the profile's slabs: A, T, C, G; N and everything else: none");
 
-template <int K, bool SYM, bool UNIT, bool AFFINE = false>
+// NW (band_nw = 1): the reference's Needleman-Wunsch variant on the same chain (definition: include/valign_hip.h).  No zero
+// floor -- the gap terms are plain subtractions; a cell outside its block's window is ABSENT: the sentinel -2^29, which loses
+// every comparison (every in-band cell has a present candidate: the engine refuses bands whose windows do not connect).  An
+// inactive lane hands the sentinel on instead of 0 and a lane starts its block from it; where the window starts at column 0
+// the border column (0) is present instead -- the block's own cells start at 0 and the cell it receives for column -1 is
+// replaced by 0 -- and the first block's row above is the border row, 0 at every column.  No running maximum: the result is
+// the best of the last row (the last block's last row, every step) and of the last column (the cells of every block whose
+// window ends at column F - 1, at that step), floored at 0.
+template <int K, bool SYM, bool UNIT, bool AFFINE = false, bool NW = false>
 __global__ void __launch_bounds__(64)
 score_band_kernel(const BandArgs args) {
+    constexpr int kOut = NW ? kBandNwAbsent32 : 0;            // what the band gives a cell outside its window
+    auto gsub = [](int v, unsigned mag) __attribute__((always_inline)) -> int {
+        return NW ? v - (int)mag : (int)__builtin_elementwise_sub_sat((unsigned)v, mag);
+    };
     static_assert(K % 8 == 0, "rows per lane come in chunks of eight int16 scores");
     using lay = BandLds<K>;
     const int lane = threadIdx.x;
@@ -159,7 +171,7 @@ score_band_kernel(const BandArgs args) {
     for (int i = lane; i < kBandGroups * args.code_cols; i += kWave) codes[i] = (unsigned char)zero_slab;
     if (!UNIT)
         for (int i = lane; i < kWave * args.ring_depth * (AFFINE ? 2 : 1); i += kWave)
-            reinterpret_cast<unsigned *>(valign_smem + lay::ring(args.code_cols, args.ring_depth))[i] = 0u;
+            reinterpret_cast<unsigned *>(valign_smem + lay::ring(args.code_cols, args.ring_depth))[i] = (unsigned)kOut;
 
     // per row: H of the previous column; linear gaps: max(H - g, 0) beside it (shared-gap form); affine: E of the previous
     // column and, with symmetric scores, max(H - open, 0)
@@ -173,11 +185,14 @@ score_band_kernel(const BandArgs args) {
     auto put_hg = [&](int q, int h, int g) __attribute__((always_inline)) { HG[q] = ((u64)(unsigned)g << 32) | (u64)(unsigned)h; };
     auto put_h = [&](int q, int h) __attribute__((always_inline)) { HG[q] = (HG[q] & 0xFFFFFFFF00000000ull) | (u64)(unsigned)h; };
 #pragma unroll
-    for (int q = 0; q < K; ++q) HG[q] = 0;
+    for (int q = 0; q < K; ++q) put_hg(q, kOut, kOut);
 #pragma unroll
-    for (int q = 0; q < (AFFINE ? K : 1); ++q) El[q] = 0;
-    int up0 = 0, up_in = 0, best = 0;      // up_in: the predecessor's cell for the coming step (read one step ahead)
-    int fup_in = 0;                        // affine: the predecessor's F beside it
+    for (int q = 0; q < (AFFINE ? K : 1); ++q) El[q] = kOut;
+    int up0 = kOut, up_in = kOut, best = 0;      // up_in: the predecessor's cell for the coming step (read one step ahead)
+    int fup_in = kOut;                     // affine: the predecessor's F beside it
+    // NW: the lane's block is the first one (its row above: the border row), starts at column 0 (the border column is present),
+    // holds the last row, reaches the last column
+    bool first_blk = false, lo0 = false, last_blk = false, to_end = false;
     // u: the lane's column minus the first column of its window (inside the window while 0 <= u <= span);
     // ca: LDS address of the ring entry two columns ahead of the lane's
     int u = -0x20000000, span = 0;
@@ -294,28 +309,30 @@ score_band_kernel(const BandArgs args) {
             asm volatile("ds_read_u8 %0, %1" : "=v"(code) : "v"(ca));    // step t + 2
         }
         ca = ((ca + 1u) & code_mask) | codes_lds;
-        int h_out = 0, f_out = 0;
+        if constexpr (NW) up0 = (first_blk || (u == -1 && lo0)) ? 0 : up0;          // the border row / the border column
+        int h_out = kOut, f_out = kOut;
         if (AFFINE) {
             if ((unsigned)u <= (unsigned)span) {
                 int f = fup_cur;
-                int ho = (int)__builtin_elementwise_sub_sat((unsigned)up0, omag_ref);          // H - open of the row above
+                int ho = gsub(up0, omag_ref);          // H - open of the row above
                 int d_cur = diag0 + score_of(S, 0), d_prev = 0, h = 0;
 #pragma unroll
                 for (int q = 0; q < K; ++q) {
                     int d_next = 0;
                     if (q + 1 < K) d_next = h_of(q) + score_of(S, q + 1);  // before H of the row is overwritten
-                    const int ex = (int)__builtin_elementwise_sub_sat((unsigned)El[q], emag_read);
-                    const int eo = SYM ? g_of(q) : (int)__builtin_elementwise_sub_sat((unsigned)h_of(q), omag_read);
+                    const int ex = gsub(El[q], emag_read);
+                    const int eo = SYM ? g_of(q) : gsub(h_of(q), omag_read);
                     const int e = ex > eo ? ex : eo;
-                    const int fx = (int)__builtin_elementwise_sub_sat((unsigned)f, emag_ref);
+                    const int fx = gsub(f, emag_ref);
                     f = fx > ho ? fx : ho;
                     int m = d_cur > e ? d_cur : e;
                     m = m > f ? m : f;
                     h = m;
                     El[q] = e;
-                    ho = (int)__builtin_elementwise_sub_sat((unsigned)m, omag_ref);
+                    ho = gsub(m, omag_ref);
                     if (SYM) put_hg(q, m, ho); else put_h(q, m);
-                    if (q & 1) {
+                    if constexpr (NW) {
+                    } else if (q & 1) {
                         int b2 = best > d_prev ? best : d_prev;
                         best = b2 > d_cur ? b2 : d_cur;
                     } else if (q == K - 1) {
@@ -326,23 +343,31 @@ score_band_kernel(const BandArgs args) {
                 }
                 h_out = h;
                 f_out = f;
+                if constexpr (NW) {
+                    if (last_blk) best = best > h ? best : h;
+                    if (to_end && u == span) {
+#pragma unroll
+                        for (int q = 0; q < K; ++q) best = best > h_of(q) ? best : h_of(q);
+                    }
+                }
             }
         } else if ((unsigned)u <= (unsigned)span) {
             int h = up0;
-            int up_c = (int)__builtin_elementwise_sub_sat((unsigned)up0, gmag_ref);
+            int up_c = gsub(up0, gmag_ref);
             int d_cur = diag0 + score_of(S, 0), d_prev = 0;
 #pragma unroll
             for (int q = 0; q < K; ++q) {
                 int d_next = 0;
                 if (q + 1 < K) d_next = h_of(q) + score_of(S, q + 1);    // before H of the row is overwritten
                 int left_c = g_of(q);
-                if (!SYM) left_c = (int)__builtin_elementwise_sub_sat((unsigned)h_of(q), gmag_read);
+                if (!SYM) left_c = gsub(h_of(q), gmag_read);
                 int m = d_cur > left_c ? d_cur : left_c;
                 m = m > up_c ? m : up_c;
                 h = m;
-                up_c = (int)__builtin_elementwise_sub_sat((unsigned)m, gmag_ref);
+                up_c = gsub(m, gmag_ref);
                 if (SYM) put_hg(q, m, up_c); else put_h(q, m);
-                if (q & 1) {
+                if constexpr (NW) {
+                } else if (q & 1) {
                     int b2 = best > d_prev ? best : d_prev;
                     best = b2 > d_cur ? b2 : d_cur;
                 } else if (q == K - 1) {
@@ -352,6 +377,13 @@ score_band_kernel(const BandArgs args) {
                 d_cur = d_next;
             }
             h_out = h;
+            if constexpr (NW) {
+                if (last_blk) best = best > h ? best : h;
+                if (to_end && u == span) {
+#pragma unroll
+                    for (int q = 0; q < K; ++q) best = best > h_of(q) ? best : h_of(q);
+                }
+            }
         }
         if (!UNIT) {
             *(__attribute__((address_space(3))) unsigned *)(my_ring + (t4 & ring_mask)) = (unsigned)h_out;
@@ -397,11 +429,19 @@ score_band_kernel(const BandArgs args) {
         commit_codes(pre_first, pre_limit, pre_ref0, pre_ref1);           // (first: the new block's columns may be among them)
         filled = pre_limit > filled ? pre_limit : filled;
         if (l == ls) {
+            // (NW: the cells left of the window -- the border column, 0, where the window starts at column 0, else absent)
+            const int left = (NW && blk.lo != 0) ? kOut : 0;
 #pragma unroll
-            for (int q = 0; q < K; ++q) HG[q] = 0;
+            for (int q = 0; q < K; ++q) put_hg(q, left, NW ? gsub(left, AFFINE ? omag_ref : gmag_ref) : 0);
 #pragma unroll
-            for (int q = 0; q < (AFFINE ? K : 1); ++q) El[q] = 0;
-            up0 = 0;
+            for (int q = 0; q < (AFFINE ? K : 1); ++q) El[q] = kOut;
+            up0 = kOut;
+            if constexpr (NW) {
+                first_blk = b == args.first_block;
+                lo0 = blk.lo == 0;
+                last_blk = b == args.nb - 1;
+                to_end = blk.lo + blk.span == F - 1;
+            }
             u = blk.start - blk.lo;             // (an empty block: lo = 0x3FFFFFFF -- never inside)
             span = blk.span;
             addr_next = lane_prof + (unsigned)*(lds_cu8 *)(codes_lds | ((unsigned)(blk.start + 1) & code_mask)) * kSlabStride;

@@ -17,6 +17,11 @@ constexpr int kAlgNW = 1;
 constexpr int kGapLinear = 0, kGapSym = 1, kGapAffine = 2, kGapAffineSym = 3;       // int16 cells
 constexpr int kGapAffineSymF16 = 4, kGapAffineF16 = 5, kGapSymF16 = 6;              // the same recurrences on half floats
 
+// band_nw: what an ABSENT cell holds on the packed int16 strips (= kNegInf, the "minus infinity" of the affine NW borders;
+// band_nw_int16_ok, cell_rules.h, says where it is safe) and on int32 cells (chain, strips: -2^29)
+constexpr int kBandNwAbsent16 = -16384;
+constexpr int kBandNwAbsent32 = -(1 << 29);
+
 // alignment fill kernels of a geometry, by what the engine selects (fill_choice, cell_rules.h)
 enum FillKernel {
     kFillLinear = 0,        // equality-test pointers, two gap scores            (full geometries only)

@@ -181,6 +181,37 @@ inline FillChoice fill_choice(const RuleInputs &in, int alg, int G, int K) {
     return c;
 }
 
+// ---- band_nw = 1: the NW variant under the block band (include/valign_hip.h) ----
+// Consecutive blocks' windows connect -- every in-band cell has a present candidate -- once 2 * (band_width / 2) + 1 columns
+// cover the most a window start advances per row, ceil(F / R).  Narrower bands are refused.
+inline bool band_nw_connects(int R, int F, int band_width) {
+    return R > 0 && 2ll * (band_width / 2) + 1 >= ((long long)F + R - 1) / R;
+}
+inline void band_nw_check(int R, int F, int band_width) {
+    if (!band_nw_connects(R, F, band_width))
+        throw std::runtime_error("band_nw: band_width " + std::to_string(band_width) + " is too narrow for read_length " + std::to_string(R) +
+                                 ", ref_length " + std::to_string(F) + " (the windows of consecutive blocks do not connect: 2 * (band_width / 2) + 1 "
+                                 "must be at least ceil(ref_length / read_length))");
+}
+
+// Banded NW-variant alignments on the packed int16 strips: an absent cell is the finite sentinel kBandNwAbsent16, forced at
+// every cell outside its row's window, so it never drifts.  The sentinel is safe where
+//   * sentinel + the largest addend (a profile value or a gap score) stays below every legitimate cell: a present cell is at
+//     least the worst monotone in-band path to it from a border -- at most R + F + 2 steps, each the worst step score (affine:
+//     E and F lie one more opening below an H);
+//   * sentinel + the smallest addend does not wrap (the linear strips add without saturation);
+//   * no legitimate cell exceeds 16000: the tracked row's first-arg-max test takes (running best - cell) in int16, and the
+//     running best starts at the sentinel where the border column is absent.
+inline bool band_nw_int16_ok(const RuleInputs &in) {
+    const Scoring &sc = in.sc;
+    const long long worst = sc.affine ? std::min({sc.open_read, sc.open_ref, sc.ext_read, sc.ext_ref, sc.mismatch, sc.match, 0})
+                                      : std::min({sc.gap_read, sc.gap_ref, sc.mismatch, sc.match, 0});
+    const long long top_add = std::max({sc.match, sc.mismatch, 0});
+    const long long hi = (long long)std::min(in.R, in.F) * std::max(sc.match, 0) + 1;
+    const long long lo = (long long)(in.R + in.F + 2) * worst + (sc.affine ? std::min({sc.open_read, sc.open_ref, 0}) : 0);
+    return kBandNwAbsent16 + top_add < lo && kBandNwAbsent16 + worst >= -32768 && hi <= 16000;
+}
+
 // ---- the path of an alignment call ----
 enum class AlignRoute { Fused, Register, Strip, StripBand, StripWide, StripWideBand, StripCkpt };
 
@@ -193,6 +224,8 @@ struct RouteFacts {
     bool small_call = false;        // align_host's direct call: the one place the fused kernel is tried
     int fused_rows = 0;             // padded rows of the tallest fused geometry
     bool checkpoints = false;       // trace_checkpoints = 1: plain row strips keep checkpoint rows instead of every pointer
+    bool band_nw = false;           // band_nw = 1: the band also applies to the NW variant
+    int band_width = 0;             // ... whose calls are refused where the windows would not connect (band_nw_check)
 };
 
 // The cascade, once: refusals, then int32 cells, the band, row strips, the fused kernel for a small call, the register sweep.
@@ -202,18 +235,21 @@ struct RouteFacts {
 // tests `fused_rows` (the tallest one: whichever geometry align_fused then takes is in range); the register path tests the
 // rows of the plan it launches (fill_choice).
 inline AlignRoute align_route(const RuleInputs &in, int alg, const RouteFacts &f) {
-    if (f.banded && alg != kAlgSW) throw std::runtime_error("band_alignments applies to Smith-Waterman alignments only");
+    if (f.banded && alg != kAlgSW && !f.band_nw) throw std::runtime_error("band_alignments applies to Smith-Waterman alignments only");
     if (f.banded && in.sse_policy)
         throw std::runtime_error("band_alignments needs traceback_policy = 0 (no banded SSE/AVX tie-breaks)");
+    const bool nw_band = f.banded && alg == kAlgNW;
+    if (nw_band) band_nw_check(in.R, in.F, f.band_width);
     // Alignments whose cells leave int16 (the reference's shorts would wrap): int32 cells on the row-strip path, one pair per
     // register (align_strip_wide_kernel) -- every mode
-    if (border_bad(in, alg) || !int16_range_ok(in, alg, false, false, 0) || f.wide_align) {
+    // (the banded NW variant also where its int16 sentinel is not safe: band_nw_int16_ok)
+    if (border_bad(in, alg) || !int16_range_ok(in, alg, false, false, 0) || f.wide_align || (nw_band && !band_nw_int16_ok(in))) {
         if (int32_refused(in))
             throw std::runtime_error("shape x scoring can leave the int32 range of the DP cells (read_length " + std::to_string(in.R) +
                                      ", ref_length " + std::to_string(in.F) + ")");
         return f.banded ? AlignRoute::StripWideBand : AlignRoute::StripWide;
     }
-    // banded SW alignments: row strips that sweep the band windows (banded cells never exceed unbanded ones: the range
+    // banded alignments: row strips that sweep the band windows (banded cells never exceed unbanded ones: the range
     // decision above stands)
     if (f.banded) return AlignRoute::StripBand;
     if (f.read_strips) return (f.checkpoints && !in.sse_policy) ? AlignRoute::StripCkpt : AlignRoute::Strip;

@@ -225,6 +225,13 @@ public:
         band_alignments_ = on == 1;
     }
     int band_alignments() const { return band_alignments_ ? 1 : 0; }
+    // The band for the NW variant too (opt-in; include/valign_hip.h has the definition): 1 = band_width > 0 also applies to
+    // NW-variant scores and, with band_alignments = 1, to NW-variant alignments; 0 = both are refused under a band (default)
+    void set_band_nw(int on) {
+        if (on != 0 && on != 1) throw std::runtime_error("band_nw must be 0 or 1");
+        band_nw_ = on == 1;
+    }
+    int band_nw() const { return band_nw_ ? 1 : 0; }
     // Checkpointed traceback of long-read alignments (opt-in; ckpt_plan.h): 1 = calls that take the plain row strips (unbanded,
     // int16 cells, traceback_policy 0; both algorithms, linear and affine gaps) keep one boundary row per strip and ONE strip's
     // pointer region instead of every pointer, and re-fill strip after strip along the walk -- identical results, a scratch that
@@ -312,8 +319,9 @@ public:
     // calls plan().  `usable` is false where the chain does not pay or does not fit (then score_long_kernel's strips run).
     BandPlan make_band_plan() const;
 
-    // score_alignments(SW, linear gaps, band_width > 0) on the block chain; false: not applicable here (strips run instead)
-    bool score_band_device(long long n, const uint8_t *d_reads, const uint8_t *d_refs, int16_t *d_scores, hipStream_t stream);
+    // score_alignments(band_width > 0) on the block chain (alg: SW, or the NW variant under band_nw); false: not applicable
+    // here (strips run instead)
+    bool score_band_device(int alg, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int16_t *d_scores, hipStream_t stream);
     bool band_chain_in_use() const;
     bool long_single_strip(bool wide) const;
 
@@ -614,6 +622,7 @@ private:
     bool sse_policy_ = false;
     int band_width_ = 0;
     bool band_alignments_ = false;
+    bool band_nw_ = false;
     bool trace_checkpoints_ = false;
     int score_width_ = 0;
     int ragged_ = 0, force_g_ = 0, force_k_ = 0;

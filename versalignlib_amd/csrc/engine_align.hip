@@ -15,7 +15,7 @@ struct StripGeometry {
     const void *affine_kernel[2];      // nullptr: too many rows per lane for the affine kernel's registers
     const void *sse_kernel[2];         // traceback_policy = 1 (linear gaps)
     const void *wide_kernel[2][3];     // int32 cells, [alg][0 linear gaps, 1 affine, 2 SSE tie-breaks]; nullptr: no such instance
-    const void *band_kernel[2][2];     // banded SW (BAND), [0 int16 / 1 int32 cells][0 linear gaps, 1 affine]; nullptr: no such instance
+    const void *band_kernel[2][2][2];  // banded (BAND), [alg][0 int16 / 1 int32 cells][0 linear gaps, 1 affine]; nullptr: no such instance
     const void *ckpt_kernel[2][2][2];  // checkpointed traceback, [alg][0 linear gaps, 1 affine][0 forward pass, 1 re-fill]
 };
 // int32 cells are the rare path: every mode at 8 rows per lane, the NW variant with linear gaps (the reference's model: long
@@ -28,13 +28,15 @@ struct StripGeometry {
 #define VALIGN_STRIP_WIDE_NW(K) {{nullptr, nullptr, nullptr}, {(const void *)&align_strip_wide_kernel<K, kAlgNW>, nullptr, nullptr}}
 #define VALIGN_STRIP_WIDE_NONE {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}
 #define VALIGN_STRIP_SSE(K) {(const void *)&align_strip_kernel<K, kAlgSW, false, true>, (const void *)&align_strip_kernel<K, kAlgNW, false, true>}
-// banded SW alignments: int16 cells at 16 and 8 rows per lane, int32 cells at 8
-#define VALIGN_STRIP_BAND(K)                                                                                                 \
-    {{(const void *)&align_strip_kernel<K, kAlgSW, false, false, true>, (const void *)&align_strip_kernel<K, kAlgSW, true, false, true>}, \
+// banded alignments (SW; the NW variant under band_nw): int16 cells at 16 and 8 rows per lane, int32 cells at 8
+#define VALIGN_STRIP_BAND_ALG(K, ALG)                                                                                        \
+    {{(const void *)&align_strip_kernel<K, ALG, false, false, true>, (const void *)&align_strip_kernel<K, ALG, true, false, true>}, \
      {nullptr, nullptr}}
-#define VALIGN_STRIP_BAND_WIDE(K)                                                                                            \
-    {{(const void *)&align_strip_kernel<K, kAlgSW, false, false, true>, (const void *)&align_strip_kernel<K, kAlgSW, true, false, true>}, \
-     {(const void *)&align_strip_wide_kernel<K, kAlgSW, false, false, true>, (const void *)&align_strip_wide_kernel<K, kAlgSW, true, false, true>}}
+#define VALIGN_STRIP_BAND_WIDE_ALG(K, ALG)                                                                                   \
+    {{(const void *)&align_strip_kernel<K, ALG, false, false, true>, (const void *)&align_strip_kernel<K, ALG, true, false, true>}, \
+     {(const void *)&align_strip_wide_kernel<K, ALG, false, false, true>, (const void *)&align_strip_wide_kernel<K, ALG, true, false, true>}}
+#define VALIGN_STRIP_BAND(K) {VALIGN_STRIP_BAND_ALG(K, kAlgSW), VALIGN_STRIP_BAND_ALG(K, kAlgNW)}
+#define VALIGN_STRIP_BAND_WIDE(K) {VALIGN_STRIP_BAND_WIDE_ALG(K, kAlgSW), VALIGN_STRIP_BAND_WIDE_ALG(K, kAlgNW)}
 #define VALIGN_STRIP_CKPT_ALG(K, ALG)                                                                                   \
     {{(const void *)&align_strip_kernel<K, ALG, false, false, false, kCkptForward>,                                    \
       (const void *)&align_strip_kernel<K, ALG, false, false, false, kCkptRefill>},                                    \
@@ -51,7 +53,7 @@ static const StripGeometry kStripGeometries[] = {
      VALIGN_STRIP_WIDE_NW(16), VALIGN_STRIP_BAND(16), VALIGN_STRIP_CKPT(16)},
     {12, &strip_lds<12>, {(const void *)&align_strip_kernel<12, kAlgSW>, (const void *)&align_strip_kernel<12, kAlgNW>},
      {(const void *)&align_strip_kernel<12, kAlgSW, true>, (const void *)&align_strip_kernel<12, kAlgNW, true>}, VALIGN_STRIP_SSE(12),
-     VALIGN_STRIP_WIDE_NW(12), {{nullptr, nullptr}, {nullptr, nullptr}}, VALIGN_STRIP_CKPT(12)},
+     VALIGN_STRIP_WIDE_NW(12), {{{nullptr, nullptr}, {nullptr, nullptr}}, {{nullptr, nullptr}, {nullptr, nullptr}}}, VALIGN_STRIP_CKPT(12)},
     {8, &strip_lds<8>, {(const void *)&align_strip_kernel<8, kAlgSW>, (const void *)&align_strip_kernel<8, kAlgNW>},
      {(const void *)&align_strip_kernel<8, kAlgSW, true>, (const void *)&align_strip_kernel<8, kAlgNW, true>}, VALIGN_STRIP_SSE(8),
      VALIGN_STRIP_WIDE_ALL(8), VALIGN_STRIP_BAND_WIDE(8), VALIGN_STRIP_CKPT(8)},
@@ -61,6 +63,8 @@ static const StripGeometry kStripGeometries[] = {
 #undef VALIGN_STRIP_SSE
 #undef VALIGN_STRIP_BAND
 #undef VALIGN_STRIP_BAND_WIDE
+#undef VALIGN_STRIP_BAND_ALG
+#undef VALIGN_STRIP_BAND_WIDE_ALG
 #undef VALIGN_STRIP_WIDE_ALL
 #undef VALIGN_STRIP_WIDE_NW
 #undef VALIGN_STRIP_WIDE_NONE
@@ -106,7 +110,8 @@ RouteFacts Engine::route_facts(bool small_call) const {
     // rows, whose resident geometries (64 x 24 / 64 x 32: 34 to 53 KB of LDS) fill at 0.8-2.1 TCUPS where 12- or 16-row
     // strips at eight waves per CU do 1.6-2.3 (1 200 x 3 000: 41 / 74 ms -> 26 / 37 ms, linear / affine)
     const bool read_strips = align_base_plan().long_mode || (!force_g_ && !force_k_ && R_ > 1024);
-    return RouteFacts{align_banded(), wide_align_, read_strips, no_fused_ || force_g_ || force_k_, small_call, fused_rows, trace_checkpoints_};
+    return RouteFacts{align_banded(), wide_align_, read_strips, no_fused_ || force_g_ || force_k_, small_call, fused_rows, trace_checkpoints_,
+                      band_nw_, band_width_};
 }
 
 bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, uint8_t *d_rows,
@@ -330,7 +335,7 @@ void Engine::align_strips_device(int alg, long long n, const uint8_t *d_reads, c
         if (affine && !g.affine_kernel[alg]) continue;
         if (sse_policy_ && !g.sse_kernel[alg]) continue;
         if (wide && !g.wide_kernel[alg][wide_mode]) continue;
-        if (band && !g.band_kernel[wide ? 1 : 0][affine ? 1 : 0]) continue;
+        if (band && !g.band_kernel[alg][wide ? 1 : 0][affine ? 1 : 0]) continue;
         if (strip_k_ && g.K != strip_k_) continue;
         const int rows_g = 64 * g.K;
         const double cost = (double)((R_ + rows_g - 1) / rows_g) * rows_g * (g.K == 16 ? 1.0 : (g.K == 12 ? 1.115 : 1.147));
@@ -391,7 +396,7 @@ void Engine::align_strips_device(int alg, long long n, const uint8_t *d_reads, c
     hip_check(hipGetLastError(), "hipLaunchKernel(first_invalid_kernel)");
     const void *refill_fn = ckpt ? geo->ckpt_kernel[alg][affine ? 1 : 0][1] : nullptr;
     const void *fn = ckpt ? geo->ckpt_kernel[alg][affine ? 1 : 0][0]
-                     : band ? geo->band_kernel[wide ? 1 : 0][affine ? 1 : 0]
+                     : band ? geo->band_kernel[alg][wide ? 1 : 0][affine ? 1 : 0]
                           : wide ? geo->wide_kernel[alg][wide_mode] : (affine ? geo->affine_kernel[alg] : (sse_policy_ ? geo->sse_kernel[alg] : geo->kernel[alg]));
     if (lds.total > kDefaultBlockLds) {
         hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds.total),

@@ -119,7 +119,7 @@ Engine::BandPlan Engine::make_band_plan() const {
     return p;
 }
 
-bool Engine::score_band_device(long long n, const uint8_t *d_reads, const uint8_t *d_refs, int16_t *d_scores, hipStream_t stream) {
+bool Engine::score_band_device(int alg, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int16_t *d_scores, hipStream_t stream) {
     if (no_band_chain_ || band_width_ <= 0) return false;
     if (band_plan_width_ != band_width_) {
         band_plan_ = make_band_plan();
@@ -158,7 +158,12 @@ bool Engine::score_band_device(long long n, const uint8_t *d_reads, const uint8_
          {(const void *)&score_band_kernel<kBandK, true, false>, (const void *)&score_band_kernel<kBandK, true, true>}},
         {{(const void *)&score_band_kernel<kBandK, false, false, true>, (const void *)&score_band_kernel<kBandK, false, true, true>},
          {(const void *)&score_band_kernel<kBandK, true, false, true>, (const void *)&score_band_kernel<kBandK, true, true, true>}}};
-    const void *fn = kernels[sc_.affine ? 1 : 0][sym ? 1 : 0][p.unit_delay ? 1 : 0];
+    static const void *const nw_kernels[2][2][2] = {     // the NW variant (band_nw)
+        {{(const void *)&score_band_kernel<kBandK, false, false, false, true>, (const void *)&score_band_kernel<kBandK, false, true, false, true>},
+         {(const void *)&score_band_kernel<kBandK, true, false, false, true>, (const void *)&score_band_kernel<kBandK, true, true, false, true>}},
+        {{(const void *)&score_band_kernel<kBandK, false, false, true, true>, (const void *)&score_band_kernel<kBandK, false, true, true, true>},
+         {(const void *)&score_band_kernel<kBandK, true, false, true, true>, (const void *)&score_band_kernel<kBandK, true, true, true, true>}}};
+    const void *fn = (alg == kAlgNW ? nw_kernels : kernels)[sc_.affine ? 1 : 0][sym ? 1 : 0][p.unit_delay ? 1 : 0];
     const int lds = BandLds<kBandK>::total(p.code_cols, p.ring_depth, sc_.affine);
     ran_score_cells_ |= kRanInt32;
     // as many one-wave blocks as run side by side; each takes quads of pairs in turn (band_kernels.hip.h)
@@ -177,6 +182,13 @@ bool Engine::score_band_device(long long n, const uint8_t *d_reads, const uint8_
 bool Engine::band_chain_in_use() const {
     return !no_band_chain_ && band_width_ > 0 && (band_plan_width_ == band_width_ ? band_plan_.usable : make_band_plan().usable);
 }
+
+// The banded NW strips of score_long_kernel (band_nw): int32 cells, [affine][same scores both ways]
+static const void *const kLongNwBand[2][2] = {
+    {(const void *)&score_long_kernel<kLongG, kLongK, kAlgNW, false, true, false, false, false, true>,
+     (const void *)&score_long_kernel<kLongG, kLongK, kAlgNW, true, true, false, false, false, true>},
+    {(const void *)&score_long_kernel<kLongG, kLongK, kAlgNW, false, true, true, false, false, true>,
+     (const void *)&score_long_kernel<kLongG, kLongK, kAlgNW, true, true, true, false, false, true>}};
 
 // Unbanded sweeps of reads beyond a few strips take the tall strips; a band is defined on the 160-row blocks.
 bool Engine::long_tall_strips() const {
@@ -197,10 +209,18 @@ bool Engine::long_single_strip(bool wide) const {
 
 void Engine::score_long_device(int alg, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int16_t *d_scores,
                        hipStream_t stream, bool wide) {
-    if (band_width_ > 0 && alg != kAlgSW)
+    if (band_width_ > 0 && alg != kAlgSW && !band_nw_)
         throw std::runtime_error("band_width applies to Smith-Waterman scores only");
-    // linear gaps, banded: the cyclic block chain (int32 cells whatever score_width says: same results in the int16 range)
-    if (band_width_ > 0 && alg == kAlgSW && score_band_device(n, d_reads, d_refs, d_scores, stream)) return;
+    const bool nw_band = band_width_ > 0 && alg == kAlgNW;
+    if (nw_band) {
+        band_nw_check(R_, F_, band_width_);
+        if (int32_refused(rule_inputs()))
+            throw std::runtime_error("shape x scoring can leave the int32 range of the DP cells (read_length " + std::to_string(R_) +
+                                     ", ref_length " + std::to_string(F_) + ")");
+        wide = true;                    // (the banded NW strips: int32 cells, whose sentinel needs no range rule)
+    }
+    // banded: the cyclic block chain (int32 cells whatever score_width says: same results in the int16 range)
+    if (band_width_ > 0 && score_band_device(alg, n, d_reads, d_refs, d_scores, stream)) return;
     const LongGeometry &geo = long_tall_strips() ? kLongTall : kLongStrips;
     const int rows = geo.G * geo.K;
     const int ppw = 2 * (kWave / geo.G);
@@ -210,7 +230,7 @@ void Engine::score_long_device(int alg, long long n, const uint8_t *d_reads, con
     a.F = F_;
     a.strips = std::max(1, (R_ + rows - 1) / rows);
     a.row_dwords = ((F_ + geo.G + kPhase - 1) / kPhase) * kPhase + kPhase;
-    a.band_half = (band_width_ > 0 && alg == kAlgSW) ? band_width_ / 2 : -1;
+    a.band_half = band_width_ > 0 ? band_width_ / 2 : -1;
     put_scoring(a);
     const int row_sets = (wide ? 2 : 1) * (sc_.affine ? 2 : 1);        // boundary rows per pair-of-pairs: per half (int32), H and F (affine)
     const size_t bytes_per_wave = (size_t)2 * (ppw / 2) * a.row_dwords * 4 * row_sets;
@@ -226,6 +246,7 @@ void Engine::score_long_device(int alg, long long n, const uint8_t *d_reads, con
     const bool sym = sc_.affine ? affine_sym : (sc_.gap_read == sc_.gap_ref && !no_sym_);
     const void *fn = geo.kernel[sc_.affine ? 1 : 0][alg][sym ? 1 : 0][wide ? 1 : 0];
     if (long_score_f16(alg, wide)) fn = (const void *)&score_long_kernel<kLongG, kLongK, kAlgSW, true, false, false, true>;
+    if (nw_band) fn = kLongNwBand[sc_.affine ? 1 : 0][sym ? 1 : 0];
     ran_score_cells_ |= long_score_f16(alg, wide) ? kRanF16 : (wide ? kRanInt32 : kRanInt16);
     int long_lds = geo.lds[sc_.affine ? 1 : 0];
     // a read of ONE strip (short reads sent here for their reference's length): the instances without boundary rings

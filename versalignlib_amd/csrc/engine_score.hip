@@ -115,7 +115,7 @@ void Engine::score_host(int opt, int n, const char *const *reads, const char *co
     // a 48 MB chunk of 10 kbp pairs is 1 200 waves for 3 500 resident ones -- each launch runs at a third of the device.
     // Chunks of up to 192 MB there (the banded block chain needs no scratch: its small chunks run side by side instead).
     const bool wide_cells = score_wide_cells(alg);
-    const bool scratch_free = (band_width_ > 0 && alg == kAlgSW && band_chain_in_use()) || (plan_.long_mode && long_single_strip(wide_cells));
+    const bool scratch_free = (band_width_ > 0 && (alg == kAlgSW || band_nw_) && band_chain_in_use()) || (plan_.long_mode && long_single_strip(wide_cells));
     const bool strips_in_turn = plan_.long_mode && !scratch_free;
     const size_t chunk_bytes = strips_in_turn && !dbg_.on("chunk_bytes") ? std::max<size_t>(score_chunk_bytes_, 192u << 20) : score_chunk_bytes_;
     long long chunk = per_pair ? (long long)(chunk_bytes / per_pair) : n;

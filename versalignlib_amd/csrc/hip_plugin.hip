@@ -203,6 +203,7 @@ public:
                 e->set_traceback_policy(opt_param("traceback_policy", 0));
                 e->set_band_width(opt_param("band_width", 0));
                 e->set_band_alignments(opt_param("band_alignments", 0));
+                e->set_band_nw(opt_param("band_nw", 0));
                 e->set_trace_checkpoints(opt_param("trace_checkpoints", 0));
                 e->set_score_width(opt_param("score_width", 0));
                 e->set_ragged_batching(opt_param("ragged_batching", 0));
@@ -447,6 +448,14 @@ VALIGN_EXPORT int valign_hip_set_band_alignments(valign_hip_engine *e, int on) {
         return 1;
     }
     return flat_guard([&] { e->impl->set_band_alignments(on); });
+}
+
+VALIGN_EXPORT int valign_hip_set_band_nw(valign_hip_engine *e, int on) {
+    if (!e) {
+        g_last_error = "null engine";
+        return 1;
+    }
+    return flat_guard([&] { e->impl->set_band_nw(on); });
 }
 
 VALIGN_EXPORT int valign_hip_set_trace_checkpoints(valign_hip_engine *e, int on) {

@@ -102,9 +102,15 @@ struct LongLds {
 // long for the resident kernels' LDS.
 // SINGLE (the read fits ONE strip: short reads routed here for their reference's length): nothing crosses strips -- no
 // boundary rings in LDS (16.7 -> 12.6 KB per wave: 12 waves per CU instead of 9), no ring read / write per step.
-template <int G, int K, int ALG, bool SYM, bool WIDE, bool AFFINE = false, bool F16 = false, bool SINGLE = false>
+// NWBAND (band_nw = 1: the NW variant under the strip band, int32 cells): a cell outside its strip's columns is ABSENT -- the
+// sentinel -2^29, which loses every comparison (every swept cell has a present candidate: the engine refuses bands whose
+// windows do not connect) -- instead of 0: what enters from the row above outside the previous strip's columns, and what
+// stands left of the first swept column unless that is column 0 (the border column, 0).  The border row above strip 0 stays
+// 0 at every column.  The score collects the last row (last strip) and the last column -- of the strips that reach it.
+template <int G, int K, int ALG, bool SYM, bool WIDE, bool AFFINE = false, bool F16 = false, bool SINGLE = false, bool NWBAND = false>
 __global__ void __launch_bounds__(64, G == 64 ? 3 : 1)
 score_long_kernel(const LongArgs args) {
+    static_assert(!NWBAND || (ALG == kAlgNW && WIDE && !SINGLE && !F16), "the banded NW variant: int32 cells on the boundary-row strips");
     static_assert(!F16 || (ALG == kAlgSW && SYM && !WIDE && !AFFINE), "half-float cells: Smith-Waterman, one gap score, packed");
     using geo = Geo<G, K>;
     using lay = LongLds<G, K, AFFINE, SINGLE>;
@@ -185,10 +191,14 @@ score_long_kernel(const LongArgs args) {
         const unsigned *brow_prev = args.brow + (long long)((s & 1) ^ 1) * args.pp_total * args.row_dwords;
         unsigned *brow_cur = args.brow + (long long)(s & 1) * args.pp_total * args.row_dwords;
 
+        // NWBAND: what stands left of the first swept column (the border column, 0, or nothing), what the row above holds
+        // outside the previous strip's columns
+        const cell_t left_init = (NWBAND && c_lo > 0) ? ops::ninf() : ops::bc(0);
+        const unsigned above_out = (NWBAND && s > 0) ? ops::bits(ops::ninf()) : 0u;
         cell_t Hl[K];
         int Gl[(SYM && WIDE && ALG == kAlgSW) ? K : 1];       // int32 SW: max(h - g, 0) of the previous column
 #pragma unroll
-        for (int q = 0; q < K; ++q) Hl[q] = ops::bc(0);
+        for (int q = 0; q < K; ++q) Hl[q] = left_init;
 #pragma unroll
         for (int q = 0; q < ((SYM && WIDE && ALG == kAlgSW) ? K : 1); ++q) Gl[q] = 0;
         cell_t El[(AFFINE || F16) ? K : 1];     // affine: E of the previous column; F16: max(h + g, 0) of it
@@ -199,9 +209,9 @@ score_long_kernel(const LongArgs args) {
         cell_t HOl[(AFFINE && SYM) ? K : 1];
 #pragma unroll
         for (int q = 0; q < ((AFFINE && SYM) ? K : 1); ++q)
-            HOl[q] = (ALG == kAlgSW) ? ops::sub0(ops::bc(0), o_ref) : ops::adds(ops::bc(0), o_ref);
+            HOl[q] = (ALG == kAlgSW) ? ops::sub0(ops::bc(0), o_ref) : ops::adds(left_init, o_ref);
         cell_t f_last = border_f;
-        cell_t up0 = ops::bc(0), h_last = ops::bc(0);
+        cell_t up0 = left_init, h_last = left_init;
         if (l == 0 && c_lo - 1 >= p_lo && c_lo - 1 <= p_hi)     // diagonal neighbour of the first swept column
             up0 = ops::from_bits(__builtin_nontemporal_load(brow_prev + brow_slot * args.row_dwords + (c_lo - 1)));
         int j = c_lo - l;
@@ -440,12 +450,12 @@ score_long_kernel(const LongArgs args) {
                 if constexpr (SINGLE) return;
                 const int g = lane / 16, col = c_lo + kLead + t0 + (lane % 16) * 4;
                 if (g >= geo::kGroups) return;
-                uint4 v = make_uint4(0u, 0u, 0u, 0u);
+                uint4 v = make_uint4(above_out, above_out, above_out, above_out);
                 if (pre_brow_valid) {
-                    v.x = (col + 0 >= p_lo && col + 0 <= p_hi) ? pre_brow.x : 0u;      // outside the previous strip's
-                    v.y = (col + 1 >= p_lo && col + 1 <= p_hi) ? pre_brow.y : 0u;      // columns the row above is 0
-                    v.z = (col + 2 >= p_lo && col + 2 <= p_hi) ? pre_brow.z : 0u;
-                    v.w = (col + 3 >= p_lo && col + 3 <= p_hi) ? pre_brow.w : 0u;
+                    v.x = (col + 0 >= p_lo && col + 0 <= p_hi) ? pre_brow.x : above_out;      // outside the previous strip's
+                    v.y = (col + 1 >= p_lo && col + 1 <= p_hi) ? pre_brow.y : above_out;      // columns the row above is 0
+                    v.z = (col + 2 >= p_lo && col + 2 <= p_hi) ? pre_brow.z : above_out;      // (NWBAND: absent)
+                    v.w = (col + 3 >= p_lo && col + 3 <= p_hi) ? pre_brow.w : above_out;
                 }
                 *reinterpret_cast<uint4 *>(ring_in + g * kRing + (col & (kRing - 1))) = v;
                 if constexpr (AFFINE) {                                  // F of the row above: the border value where there is none
@@ -480,7 +490,7 @@ score_long_kernel(const LongArgs args) {
             }
             if (!SINGLE && lane < geo::kGroups * kLead) {
                 const int g = lane / kLead, bc = c_lo + (lane % kLead);
-                unsigned v = 0u, vf = border_f_bits;
+                unsigned v = above_out, vf = border_f_bits;
                 if (s > 0 && bc < args.row_dwords && bc >= p_lo && bc <= p_hi) {
                     v = __builtin_nontemporal_load(brow_prev + brow_slot_of(g, half, 0) * args.row_dwords + bc);
                     if constexpr (AFFINE) vf = __builtin_nontemporal_load(brow_prev + brow_slot_of(g, half, 1) * args.row_dwords + bc);
@@ -540,7 +550,7 @@ score_long_kernel(const LongArgs args) {
         }
         if (ALG == kAlgNW) {                    // every lane froze at the last column: this strip's rows
 #pragma unroll
-            for (int q = 0; q < K; ++q) col_best = ops::mx(col_best, Hl[q]);
+            for (int q = 0; q < K; ++q) col_best = ops::mx(col_best, (!NWBAND || c_hi == F - 1) ? Hl[q] : ops::bc(0));
             if (s + 1 < args.strips) row_best = ops::bc(0);  // only the last strip holds the last row
         }
     }

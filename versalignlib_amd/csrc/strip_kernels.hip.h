@@ -181,8 +181,10 @@ template <int K, int ALG, bool AFFINE = false, bool SSE = false, bool BAND = fal
 __global__ void __launch_bounds__(64)
 align_strip_kernel(const StripArgs args) {
     static_assert(!(AFFINE && SSE), "the SSE / AVX kernels have linear gaps only");
-    static_assert(!BAND || (ALG == kAlgSW && !SSE), "bands: Smith-Waterman with the default tie-breaks");
+    static_assert(!BAND || !SSE, "bands: the default tie-breaks");
+    static_assert(kNegInf == kBandNwAbsent16, "the sentinel band_nw_int16_ok (cell_rules.h) reasons about");
     static_assert(CKPT == kCkptNone || (!SSE && !BAND), "checkpointed traceback: unbanded strips with the default tie-breaks");
+    constexpr bool NWBAND = BAND && ALG == kAlgNW;      // band_nw: cells outside a row's window are ABSENT (the sentinel kNegInf)
     constexpr bool kPointers = CKPT != kCkptForward;                  // the pass stores a pointer stream
     constexpr bool kEndCell = CKPT != kCkptRefill;                    // the pass tracks and writes the end cell
     constexpr int W = AFFINE ? 2 * K : K;                             // pointer words per lane and block
@@ -257,9 +259,15 @@ align_strip_kernel(const StripArgs args) {
 #pragma unroll
     for (int q = 0; q < K; ++q) {
         const int pos = row0 + l * K + q;              // read position of the row (negative: padding)
+        bool border_present = true;                    // NWBAND: the border column exists where the row's window starts at column 0
         if constexpr (BAND) {
             band_row_window(args.band, pos, R, args.F, win_lo[q], win_w[q]);
+            border_present = win_lo[q] == 0;
             win_lo[q] -= c_lo;
+            if (NWBAND && pos < 0) {                   // padding rows are the border row: present at every column
+                win_lo[q] = 0;
+                win_w[q] = 0x7FFFFFFF;
+            }
         }
         if (SSE) {
             const int ca = (pos >= 0 && pos < R) ? base_class(read_a[pos]) : 0, cb = (pos >= 0 && pos < R) ? base_class(read_b[pos]) : 0;
@@ -268,6 +276,7 @@ align_strip_kernel(const StripArgs args) {
         short border = 0;
         if (ALG == kAlgNW)                             // column 0 of the NW variant: a gap of pos + 1 read bases
             border = pos < 0 ? (short)0 : (AFFINE ? (short)(args.open_ref + pos * args.ext_ref) : (short)((pos + 1) * args.gap_ref));
+        if (NWBAND && pos >= 0 && !border_present) border = kNegInf;
         Hl[q] = pk(border);
         code[q] = pk(0);
         acc[q] = pk(0);
@@ -294,6 +303,7 @@ align_strip_kernel(const StripArgs args) {
     s16x2 up0 = pk(0);
     if (ALG == kAlgNW && l == 0 && row0 - 1 >= 0)
         up0 = pk(AFFINE ? (short)(args.open_ref + (row0 - 1) * args.ext_ref) : (short)(row0 * args.gap_ref));
+    if (NWBAND && c_lo > 0) up0 = pk(kNegInf);         // (no border column left of this strip's windows)
     int j = -l;
 
     unsigned *ptr_lane = pointer_stream_lane<G, K, W>(args.ptr, w.pair0, args.blocks8, lane);
@@ -310,7 +320,7 @@ align_strip_kernel(const StripArgs args) {
     unsigned topf_cur = border_f_bits, topf_next = (AFFINE && has_top) ? top_f[lane] : border_f_bits;
     unsigned bot_acc = 0u, botf_acc = 0u;
 
-    const int steps = (ALG == kAlgSW || CKPT == kCkptRefill) ? (((BAND ? cols : F) + G - 1 + 7) / 8) * 8 : args.blocks8 * 8;   // whole 8-step blocks
+    const int steps = (ALG == kAlgSW || BAND || CKPT == kCkptRefill) ? (((BAND ? cols : F) + G - 1 + 7) / 8) * 8 : args.blocks8 * 8;   // whole 8-step blocks
     for (int t = 0; t < steps; ++t) {
         if ((t & 63) == 0) {
             top_cur = top_next;
@@ -325,7 +335,8 @@ align_strip_kernel(const StripArgs args) {
         const s16x2 diag0 = up0;
         unsigned above = (unsigned)__builtin_amdgcn_readlane((int)top_cur, t & 63);      // H(row above, column t)
         const bool above_out = BAND && (unsigned)(t - p_lo) >= (unsigned)p_w;           // BAND: not swept by the previous strip
-        if constexpr (BAND) above = above_out ? 0u : above;
+        constexpr unsigned kOut = NWBAND ? 0xC000C000u : 0u;                            // (NWBAND: absent; strip 0: the border row, 0)
+        if constexpr (BAND) above = (above_out && (!NWBAND || has_top)) ? kOut : above;
         // every lane takes part in the DPP move: a lane masked off by the select would be read as 0 by its neighbour
         unsigned from_lane = from_prev_lane(as_u32(h_last));
         asm volatile("" : "+v"(from_lane));
@@ -333,7 +344,7 @@ align_strip_kernel(const StripArgs args) {
         s16x2 fup0 = border_f;
         if (AFFINE) {
             unsigned above_f = (unsigned)__builtin_amdgcn_readlane((int)topf_cur, t & 63);
-            if constexpr (BAND) above_f = above_out ? 0u : above_f;
+            if constexpr (BAND) above_f = (above_out && (!NWBAND || has_top)) ? kOut : above_f;
             unsigned f_lane = from_prev_lane(as_u32(f_last));
             asm volatile("" : "+v"(f_lane));
             fup0 = as_pk(l == 0 ? above_f : f_lane);
@@ -362,7 +373,7 @@ align_strip_kernel(const StripArgs args) {
                 f = pk_max(f_extd, f_open);
                 h = pk_max(m[q], f);
                 if constexpr (BAND) {
-                    if ((unsigned)(j - win_lo[q]) >= (unsigned)win_w[q]) h = f = El[q] = pk(0);     // outside the row's window
+                    if ((unsigned)(j - win_lo[q]) >= (unsigned)win_w[q]) h = f = El[q] = pk(NWBAND ? kNegInf : (short)0);     // outside the row's window
                 }
                 Hl[q] = h;
                 if constexpr (kPointers) {
@@ -445,7 +456,7 @@ align_strip_kernel(const StripArgs args) {
             for (int q = 0; q < K; ++q) {
                 const s16x2 ug = (ALG == kAlgSW) ? pk_sub_floor0(h, g_ref) : h + g_ref;
                 h = pk_max(m[q], ug);
-                if constexpr (BAND) h = (unsigned)(j - win_lo[q]) < (unsigned)win_w[q] ? h : pk(0);     // outside the row's window: 0
+                if constexpr (BAND) h = (unsigned)(j - win_lo[q]) < (unsigned)win_w[q] ? h : pk(NWBAND ? kNegInf : (short)0);     // outside the row's window: 0 / absent
                 Hl[q] = h;
                 if constexpr (kPointers) {
                     // back pointer: 0 if h == diag + S, else 1 if it came from above, else 2 (DIAG > UP > LEFT)
@@ -561,11 +572,17 @@ align_strip_kernel(const StripArgs args) {
                 arg_col = __shfl(mine, src_l, kWave);
             }
             const int last_ref = jr[half] - 1;
+            arg_col += c_lo;
             EndCell out;
             out.pad = 0;
             out.score = 0;
             out.read_pos = (short)i_end;
             out.ref_pos = (short)(last_ref < arg_col ? last_ref : arg_col);
+            if (NWBAND && i_end >= 0) {               // a start cell outside its row's window is absent: the empty alignment
+                int e_lo, e_w;
+                band_row_window(args.band, i_end, R, args.F, e_lo, e_w);
+                if (out.ref_pos < (e_lo == 0 ? -1 : e_lo)) out.read_pos = out.ref_pos = -1;
+            }
             if (l == 0 && pair < args.n) args.ends[pair] = out;
         }
     }
@@ -587,7 +604,8 @@ template <int K, int ALG = kAlgNW, bool AFFINE = false, bool SSE = false, bool B
 __global__ void __launch_bounds__(64)
 align_strip_wide_kernel(const StripArgs args) {
     static_assert(!(AFFINE && SSE), "the SSE / AVX kernels have linear gaps only");
-    static_assert(!BAND || (ALG == kAlgSW && !SSE), "bands: Smith-Waterman with the default tie-breaks");
+    static_assert(!BAND || !SSE, "bands: the default tie-breaks");
+    constexpr bool NWBAND = BAND && ALG == kAlgNW;        // band_nw: cells outside a row's window are ABSENT (kNinf)
     constexpr int W = AFFINE ? 2 * K : K;                 // pointer words per lane and block
     constexpr int G = 64;
     constexpr int kNinf = -(1 << 29);
@@ -606,6 +624,7 @@ align_strip_wide_kernel(const StripArgs args) {
     // window (relative to c_lo)
     int c_lo = 0, cols = args.F, p_lo = 0, p_w = 0;
     int win_lo[BAND ? K : 1], win_w[BAND ? K : 1];
+    bool border_present[NWBAND ? K : 1];                // NWBAND: the border column exists where the row's window starts at column 0
     if constexpr (BAND) {
         band_rows_window(args.band, row0, row0 + geo::kRows - 1, R, args.F, c_lo, cols);
         if (args.strip > 0) band_rows_window(args.band, row0 - geo::kRows, row0 - 1, R, args.F, p_lo, p_w);
@@ -613,7 +632,12 @@ align_strip_wide_kernel(const StripArgs args) {
 #pragma unroll
         for (int q = 0; q < K; ++q) {
             band_row_window(args.band, row0 + l * K + q, R, args.F, win_lo[q], win_w[q]);
+            border_present[q] = win_lo[q] == 0;
             win_lo[q] -= c_lo;
+            if (NWBAND && row0 + l * K + q < 0) {       // padding rows are the border row: present at every column
+                win_lo[q] = 0;
+                win_w[q] = 0x7FFFFFFF;
+            }
         }
     }
     const int F = args.F - c_lo;                        // (columns from c_lo on)
@@ -632,7 +656,7 @@ align_strip_wide_kernel(const StripArgs args) {
     const long long pp = w.pair0 / 2;
     const size_t set_dwords = (size_t)(args.top_f - args.top);
     const bool has_top = args.strip > 0, has_bottom = args.strip + 1 < args.strips;
-    const int steps = (ALG == kAlgSW) ? (((BAND ? cols : F) + G - 1 + 7) / 8) * 8 : args.blocks8 * 8;
+    const int steps = (ALG == kAlgSW || BAND) ? (((BAND ? cols : F) + G - 1 + 7) / 8) * 8 : args.blocks8 * 8;
     const int row_dwords = args.row_dwords - c_lo;
 
     for (int half = 0; half < 2; ++half) {
@@ -664,6 +688,7 @@ align_strip_wide_kernel(const StripArgs args) {
             int border = 0;
             if (ALG == kAlgNW)                              // column 0: a gap of pos + 1 read bases
                 border = pos < 0 ? 0 : (AFFINE ? args.open_ref + pos * args.ext_ref : (pos + 1) * args.gap_ref);
+            if constexpr (NWBAND) border = (pos >= 0 && !border_present[q]) ? kNinf : border;
             Hl[q] = border;
             code[q] = acc[q] = 0u;
             if (AFFINE) {
@@ -680,6 +705,7 @@ align_strip_wide_kernel(const StripArgs args) {
         int h_last = Hl[K - 1], f_last = border_f;
         int up0 = 0;                                        // row above the strip at column -1
         if (ALG == kAlgNW && l == 0 && row0 - 1 >= 0) up0 = AFFINE ? args.open_ref + (row0 - 1) * args.ext_ref : row0 * args.gap_ref;
+        if (NWBAND && c_lo > 0) up0 = kNinf;                // (no border column left of this strip's windows)
         if (BAND && l == 0 && has_top && (unsigned)(-1 - p_lo) < (unsigned)p_w) up0 = (int)top[-1];     // BAND: column c_lo - 1
         int j = -l;
         unsigned code_addr = ring_base | ((unsigned)(-2 * l) & (2u * kStripRingCols - 1u));
@@ -702,14 +728,15 @@ align_strip_wide_kernel(const StripArgs args) {
             const int diag0 = up0;
             int above = __builtin_amdgcn_readlane((int)top_cur, t & 63);
             const bool above_out = BAND && (unsigned)(t - p_lo) >= (unsigned)p_w;       // BAND: not swept by the previous strip
-            if constexpr (BAND) above = above_out ? 0 : above;
+            constexpr int kOut = NWBAND ? kNinf : 0;                                    // (NWBAND: absent; strip 0: the border row, 0)
+            if constexpr (BAND) above = (above_out && (!NWBAND || has_top)) ? kOut : above;
             int from_lane = __builtin_amdgcn_update_dpp(0, h_last, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
             asm volatile("" : "+v"(from_lane));
             up0 = l == 0 ? above : from_lane;
             int fup0 = border_f;
             if (AFFINE) {
                 int above_f = __builtin_amdgcn_readlane((int)topf_cur, t & 63);
-                if constexpr (BAND) above_f = above_out ? 0 : above_f;
+                if constexpr (BAND) above_f = (above_out && (!NWBAND || has_top)) ? kOut : above_f;
                 int f_lane = __builtin_amdgcn_update_dpp(0, f_last, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
                 asm volatile("" : "+v"(f_lane));
                 fup0 = l == 0 ? above_f : f_lane;
@@ -752,9 +779,9 @@ align_strip_wide_kernel(const StripArgs args) {
                         code[q] = m == d ? 0u : (m == ug ? 1u : 2u);          // DIAG > UP > LEFT
                     }
                     if constexpr (BAND) {
-                        if ((unsigned)(j - win_lo[q]) >= (unsigned)win_w[q]) {      // outside the row's window: H = E = F = 0
-                            m = 0;
-                            if constexpr (AFFINE) f = El[q] = 0;
+                        if ((unsigned)(j - win_lo[q]) >= (unsigned)win_w[q]) {      // outside the row's window: H = E = F = 0 / absent
+                            m = kOut;
+                            if constexpr (AFFINE) f = El[q] = kOut;
                         }
                     }
                     h = m;
@@ -855,11 +882,17 @@ align_strip_wide_kernel(const StripArgs args) {
                 int arg_col = 0;
                 if (i_end >= 0) arg_col = __shfl(row_col - l, tr_lane, kWave);
                 const int last_ref = jr - 1;
+                arg_col += c_lo;
                 EndCell out;
                 out.pad = 0;
                 out.score = 0;
                 out.read_pos = (short)i_end;
                 out.ref_pos = (short)(last_ref < arg_col ? last_ref : arg_col);
+                if (NWBAND && i_end >= 0) {           // a start cell outside its row's window is absent: the empty alignment
+                    int e_lo, e_w;
+                    band_row_window(args.band, i_end, R, args.F, e_lo, e_w);
+                    if (out.ref_pos < (e_lo == 0 ? -1 : e_lo)) out.read_pos = out.ref_pos = -1;
+                }
                 if (l == 0 && pair < args.n) args.ends[pair] = out;
             }
         }

@@ -214,6 +214,10 @@ __device__ __forceinline__ int trace_walk(const TraceArgs &a, const unsigned *pt
                         band_row0 = (i + a.band.pad) / a.band.block_rows * a.band.block_rows - a.band.pad;
                         band_row_window(a.band, i, R, F, band_lo, band_width);
                     }
+                    // Smith-Waterman: a step out of the band is START, the defined end of the walk.  NW variant (band_nw): only an
+                    // absent START CELL arrives here -- the fill's end-cell rule turns it into the empty alignment; from a
+                    // present cell no pointer leads out of the band, because band_nw_check (cell_rules.h) only admits bands
+                    // in which every in-band cell has a present candidate (tests/band_nw_ref.py asserts it on its own walk)
                     if ((unsigned)(j - band_lo) >= (unsigned)band_width) break;     // out of the band: START
                     if (strip != band_strip) {
                         int strip_width;
