@@ -21,7 +21,7 @@ def test_cell_rules_check(tmp_path):
 
 def test_engine_uses_the_checked_rules():
     """The engine units must run THESE rules: no member copy of one, and no exception used to ask a rule a question."""
-    for header in ("cell_rules.h", "cell_constants.h", "align_parts.h"):
+    for header in ("cell_rules.h", "cell_constants.h", "align_parts.h", "strip_plan.h", "band_window.h"):
         assert "#include <hip" not in open(os.path.join(CSRC, header)).read(), header
     assert '#include "cell_rules.h"' in open(os.path.join(CSRC, "engine.hip.h")).read()
     for unit in ("engine.hip.h", "engine_core.hip", "engine_score.hip", "engine_long.hip", "engine_align.hip"):

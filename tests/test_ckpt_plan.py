@@ -20,8 +20,11 @@ def test_ckpt_plan_check(tmp_path):
 
 
 def test_the_engine_runs_the_checked_plan():
-    """The header is pure, and the engine sizes its scratch with it rather than with arithmetic of its own."""
-    assert "#include <hip" not in open(os.path.join(CSRC, "ckpt_plan.h")).read()
+    """The headers are pure, and the engine sizes its scratch with them rather than with arithmetic of its own: the one plan of
+    the strip path (strip_plan.h), of which ckpt_plan() is the checkpointed view."""
+    for header in ("ckpt_plan.h", "strip_plan.h"):
+        assert "#include <hip" not in open(os.path.join(CSRC, header)).read(), header
+    assert "strip_plan(" in open(os.path.join(CSRC, "ckpt_plan.h")).read()
     text = open(os.path.join(CSRC, "engine_align.hip")).read()
-    for name in ("ckpt_plan(", "strip_chunk_pairs(", "ckpt_rounds("):
+    for name in ("strip_plan(", "strip_chunk_pairs(", "ckpt_rounds("):
         assert name in text, name

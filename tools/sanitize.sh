@@ -3,7 +3,8 @@
 #   1. the host-only half of the plugin's host-pointer path (versalignlib_amd/csrc/host_pipeline.h: worker pool,
 #      gather, scatter) as a stand-alone program under -fsanitize=thread and under -fsanitize=address,undefined;
 #      and the engine's cell-range rules and path choice (versalignlib_amd/csrc/cell_rules.h, tests/cell_rules_check.cpp)
-#      and the plan of the checkpointed traceback (versalignlib_amd/csrc/ckpt_plan.h, tests/ckpt_plan_check.cpp)
+#      and the plans of the strip path and of its checkpointed traceback (versalignlib_amd/csrc/strip_plan.h, ckpt_plan.h;
+#      tests/strip_plan_check.cpp, tests/ckpt_plan_check.cpp)
 #      under -fsanitize=address,undefined;
 #   2. libvalignhost.so, valign-bench and the oracle (oracle/cpu_ref.c) built with -fsanitize=address,undefined
 #      into build/sanitize/, and the whole CPU test-suite run against THOSE (python gets the runtimes preloaded).
@@ -27,6 +28,9 @@ echo "== ckpt_plan.h under AddressSanitizer + UBSan"
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/ckpt_plan_check.cpp" -o "$OUT/ckpt_plan_asan"
 "$OUT/ckpt_plan_asan"
 "$OUT/cell_rules_asan"
+echo "== strip_plan.h under AddressSanitizer + UBSan"
+g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/strip_plan_check.cpp" -o "$OUT/strip_plan_asan"
+"$OUT/strip_plan_asan"
 echo "== the band_nw rules of cell_rules.h under AddressSanitizer + UBSan"
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/band_nw_rules_check.cpp" -o "$OUT/band_nw_rules_asan"
 "$OUT/band_nw_rules_asan"

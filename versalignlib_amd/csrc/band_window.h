@@ -8,7 +8,12 @@
 // traceback_kernel finds a strip's column offset from the same function.
 #pragma once
 
-#include "valign_hip.h"
+#include "../../include/valign_hip.h"
+
+#ifndef __HIPCC__       // plain g++ (the CPU checks of the plans that read the band): the functions below are host functions
+#define __host__
+#define __device__
+#endif
 
 namespace valign {
 

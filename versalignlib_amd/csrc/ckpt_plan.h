@@ -1,6 +1,7 @@
 // ckpt_plan.h -- checkpointed traceback of long-read alignments (trace_checkpoints = 1, AlignRoute::StripCkpt) before its
 // launches: what a pair-of-pairs holds in the scratch, how much of the batch the scratch takes at a time, and the order of the
 // backward rounds.  Integers in, integers out; no HIP (tests/ckpt_plan_check.cpp exercises it on the CPU, as align_parts.h).
+// The sizes are those of strip_plan.h -- the one plan of the strip path -- under the names this schedule gives them.
 //
 // The schedule (Engine::align_strips_device): the read is swept in S strips of 64 K rows.  The forward pass stores no
 // pointers and keeps EVERY strip's bottom row -- S - 1 boundary-row sets (H; F beside it with affine gaps) instead of the two
@@ -14,9 +15,9 @@
 #include <algorithm>
 #include <vector>
 
-namespace valign {
+#include "strip_plan.h"
 
-constexpr int kWalkStateBytes = 24;         // sizeof(WalkState) (trace_kernels.hip.h), per pair
+namespace valign {
 
 struct CkptPlan {
     int rows = 0;                   // rows per strip: 64 K
@@ -33,21 +34,11 @@ struct CkptPlan {
     size_t full_bytes = 0;          // what the full-pointer path holds instead: S regions
 };
 
-// Strips and boundary rows exactly as the full-pointer path sizes them (align_strips_device), unbanded int16 cells
+// The checkpointed strip plan (strip_plan.h) of unbanded int16 cells, and what the full-pointer path holds beside it
 inline CkptPlan ckpt_plan(int R, int F, int K, bool affine) {
-    CkptPlan p;
-    p.rows = 64 * K;
-    p.strips = std::max(1, (R + p.rows - 1) / p.rows);
-    p.pad_total = p.strips * p.rows - R;
-    p.blocks8 = (F + 63 + 7) / 8;
-    p.row_dwords = ((F + 71) / 64 + 2) * 64;
-    p.row_sets = affine ? 2 : 1;
-    p.region_bytes = (size_t)p.blocks8 * 64 * K * 4 * (affine ? 2 : 1);
-    p.row_bytes = (size_t)(p.strips - 1) * p.row_sets * p.row_dwords * 4;
-    p.state_bytes = (size_t)2 * kWalkStateBytes;
-    p.bytes_per_pp = p.region_bytes + p.row_bytes + p.state_bytes;
-    p.full_bytes = p.region_bytes * p.strips;
-    return p;
+    const StripPlan s = strip_plan(R, F, K, StripMode{kAlgSW, affine, false, false, false, true}, kNoBand);
+    return CkptPlan{s.rows,     s.strips,      s.pad_total,    s.blocks8,      s.row_dwords,
+                    s.row_sets, s.strip_words * 4, s.row_bytes, s.state_bytes, s.bytes_per_pp, s.strip_words * 4 * s.strips};
 }
 
 // Pairs (an even number: whole waves) a scratch of at most `cap` bytes takes at a time -- at least one wave, at most the batch.

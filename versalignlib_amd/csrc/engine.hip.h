@@ -31,6 +31,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "align_parts.h"
@@ -44,6 +45,7 @@
 #include "pack_kernels.hip.h"
 #include "ragged_kernels.hip.h"
 #include "strip_kernels.hip.h"
+#include "strip_plan.h"
 
 namespace valign {
 
@@ -413,12 +415,11 @@ public:
     // Reads beyond one register sweep: row strips of 64 * K rows, one launch per strip in stream order, boundary
     // rows ping-pong through HBM, one pointer region per strip, then the same traceback kernel (strip_kernels.hip.h).
     // Linear or affine gaps, Default tie-breaks, int16 cells (the reference's; where they would wrap, align_route
-    // takes the int32 cells instead of wrapping silently).
-    // band: banded SW alignments (align_strip_kernel<..., BAND>: each strip sweeps its rows' band windows only).
-    // ckpt: checkpointed traceback (AlignRoute::StripCkpt; ckpt_plan.h has the schedule): a forward pass without pointers that
+    // takes the int32 cells instead of wrapping silently).  mode (strip_plan.h, from the route) -- band: each strip sweeps its
+    // rows' band windows only; ckpt: checkpointed traceback (ckpt_plan.h has the schedule): a forward pass without pointers that
     // keeps every strip's bottom row, then per strip, last to first, a re-fill into one pointer region and a resumable walk.
-    void align_strips_device(int alg, long long n, const uint8_t *d_reads, const uint8_t *d_refs, uint8_t *d_rows,
-                             short *d_idx, hipStream_t stream, bool wide = false, bool band = false, bool ckpt = false);
+    void align_strips_device(const StripMode &mode, long long n, const uint8_t *d_reads, const uint8_t *d_refs, uint8_t *d_rows, short *d_idx,
+                             hipStream_t stream);
     bool align_banded() const { return band_alignments_ && band_width_ > 0; }
 
     // Host pointers in, Alignment[] out: the rows of every pair are fresh operator new[] blocks
@@ -468,6 +469,28 @@ private:
         a.open_ref = (short)sc_.open_ref;
         a.ext_ref = (short)sc_.ext_ref;
     }
+
+    // what FillArgs, StripArgs and TraceArgs share: the sequences and the size of the launch's part of the batch, the blocks of
+    // its sweep, the scoring -- and, for the two that fill (lds given), the LDS layout of a wave
+    template <class A>
+    void put_sweep(A &a, const uint8_t *d_reads, const uint8_t *d_refs, long long n, int blocks8) const {
+        a.reads = d_reads;
+        a.refs = d_refs;
+        a.n = n;
+        a.R = R_;
+        a.F = F_;
+        a.blocks8 = blocks8;
+        put_scoring(a);
+    }
+    template <class A>
+    void put_sweep(A &a, const uint8_t *d_reads, const uint8_t *d_refs, long long n, int blocks8, const WaveLds &lds) const {
+        put_sweep(a, d_reads, d_refs, n, blocks8);
+        a.prof_area = lds.prof_area;
+        a.refc_stride = lds.refc_stride;
+        a.wave_lds = lds.total;
+    }
+    TraceArgs trace_args(int alg, const uint8_t *d_reads, const uint8_t *d_refs, long long n, const unsigned *ptr, const EndCell *ends, uint8_t *rows,
+                         short *idx, int G, int K, int pad_rows, int blocks8) const;
 
     // latency: pick for the shortest single sweep (few pairs: every wave has a SIMD to itself and the call takes
     // as long as one wave does) instead of for the most cell updates per second

@@ -7,67 +7,39 @@
 
 namespace valign {
 
-// compute_alignments for reads beyond one register sweep (strip_kernels.hip.h): a wave per pair-of-pairs, K rows per lane
+// compute_alignments for reads beyond one register sweep (strip_kernels.hip.h): a wave per pair-of-pairs, K rows per lane.
+// The one place a strip kernel is instantiated: the instance of (mode, pass) number I -- bit 0 the algorithm, then int32
+// cells, affine gaps, SSE tie-breaks, the band; above them the checkpointed pass (kCkptNone / kCkptForward / kCkptRefill) --
+// where strip_instance_exists (strip_plan.h) says it is compiled, null elsewhere.
+constexpr int kStripModeBits = 5, kStripInstances = 3 << kStripModeBits;
+template <int K, int I>
+const void *strip_instance() {
+    constexpr int ALG = I & 1, CKPT = I >> kStripModeBits;
+    constexpr bool WIDE = (I & 2) != 0, AFFINE = (I & 4) != 0, SSE = (I & 8) != 0, BAND = (I & 16) != 0;
+    if constexpr (!strip_instance_exists(K, StripMode{ALG, AFFINE, SSE, WIDE, BAND, CKPT != kCkptNone})) return nullptr;
+    else if constexpr (WIDE) return (const void *)&align_strip_wide_kernel<K, ALG, AFFINE, SSE, BAND>;
+    else return (const void *)&align_strip_kernel<K, ALG, AFFINE, SSE, BAND, CKPT>;
+}
+// ckpt_pass (checkpointed modes): 0 the forward pass, 1 the re-fill
+template <int K, int... I>
+const void *strip_kernel_in(const StripMode &m, int ckpt_pass, std::integer_sequence<int, I...>) {
+    static const void *const instances[] = {strip_instance<K, I>()...};
+    const int pass = m.ckpt ? (ckpt_pass ? kCkptRefill : kCkptForward) : kCkptNone;
+    return instances[m.alg | m.wide << 1 | m.affine << 2 | m.sse << 3 | m.band << 4 | pass << kStripModeBits];
+}
+template <int K>
+const void *strip_kernel(const StripMode &m, int ckpt_pass) {
+    return strip_kernel_in<K>(m, ckpt_pass, std::make_integer_sequence<int, kStripInstances>());
+}
 struct StripGeometry {
     int K;
-    WaveLds (*lds)(int R, int F);
-    const void *kernel[2];
-    const void *affine_kernel[2];      // nullptr: too many rows per lane for the affine kernel's registers
-    const void *sse_kernel[2];         // traceback_policy = 1 (linear gaps)
-    const void *wide_kernel[2][3];     // int32 cells, [alg][0 linear gaps, 1 affine, 2 SSE tie-breaks]; nullptr: no such instance
-    const void *band_kernel[2][2][2];  // banded (BAND), [alg][0 int16 / 1 int32 cells][0 linear gaps, 1 affine]; nullptr: no such instance
-    const void *ckpt_kernel[2][2][2];  // checkpointed traceback, [alg][0 linear gaps, 1 affine][0 forward pass, 1 re-fill]
+    WaveLds lds;            // the profile of 64 K rows and the ring of slab numbers: no term in the shape
+    const void *(*kernel)(const StripMode &, int ckpt_pass);
 };
-// int32 cells are the rare path: every mode at 8 rows per lane, the NW variant with linear gaps (the reference's model: long
-// reads whose column-0 border leaves int16) at 16 / 12 as well
-#define VALIGN_STRIP_WIDE_ALL(K)                                                                                       \
-    {{(const void *)&align_strip_wide_kernel<K, kAlgSW>, (const void *)&align_strip_wide_kernel<K, kAlgSW, true>,      \
-      (const void *)&align_strip_wide_kernel<K, kAlgSW, false, true>},                                                 \
-     {(const void *)&align_strip_wide_kernel<K, kAlgNW>, (const void *)&align_strip_wide_kernel<K, kAlgNW, true>,      \
-      (const void *)&align_strip_wide_kernel<K, kAlgNW, false, true>}}
-#define VALIGN_STRIP_WIDE_NW(K) {{nullptr, nullptr, nullptr}, {(const void *)&align_strip_wide_kernel<K, kAlgNW>, nullptr, nullptr}}
-#define VALIGN_STRIP_WIDE_NONE {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}
-#define VALIGN_STRIP_SSE(K) {(const void *)&align_strip_kernel<K, kAlgSW, false, true>, (const void *)&align_strip_kernel<K, kAlgNW, false, true>}
-// banded alignments (SW; the NW variant under band_nw): int16 cells at 16 and 8 rows per lane, int32 cells at 8
-#define VALIGN_STRIP_BAND_ALG(K, ALG)                                                                                        \
-    {{(const void *)&align_strip_kernel<K, ALG, false, false, true>, (const void *)&align_strip_kernel<K, ALG, true, false, true>}, \
-     {nullptr, nullptr}}
-#define VALIGN_STRIP_BAND_WIDE_ALG(K, ALG)                                                                                   \
-    {{(const void *)&align_strip_kernel<K, ALG, false, false, true>, (const void *)&align_strip_kernel<K, ALG, true, false, true>}, \
-     {(const void *)&align_strip_wide_kernel<K, ALG, false, false, true>, (const void *)&align_strip_wide_kernel<K, ALG, true, false, true>}}
-#define VALIGN_STRIP_BAND(K) {VALIGN_STRIP_BAND_ALG(K, kAlgSW), VALIGN_STRIP_BAND_ALG(K, kAlgNW)}
-#define VALIGN_STRIP_BAND_WIDE(K) {VALIGN_STRIP_BAND_WIDE_ALG(K, kAlgSW), VALIGN_STRIP_BAND_WIDE_ALG(K, kAlgNW)}
-#define VALIGN_STRIP_CKPT_ALG(K, ALG)                                                                                   \
-    {{(const void *)&align_strip_kernel<K, ALG, false, false, false, kCkptForward>,                                    \
-      (const void *)&align_strip_kernel<K, ALG, false, false, false, kCkptRefill>},                                    \
-     {(const void *)&align_strip_kernel<K, ALG, true, false, false, kCkptForward>,                                     \
-      (const void *)&align_strip_kernel<K, ALG, true, false, false, kCkptRefill>}}
-#define VALIGN_STRIP_CKPT(K) {VALIGN_STRIP_CKPT_ALG(K, kAlgSW), VALIGN_STRIP_CKPT_ALG(K, kAlgNW)}
 template <int K>
-static WaveLds strip_lds(int, int) {            // the profile of 64 K rows and the ring of slab numbers: no term in F
-    return WaveLds{StripLds<K>::kRing, 0, StripLds<K>::kTotal};
-}
-static const StripGeometry kStripGeometries[] = {
-    {16, &strip_lds<16>, {(const void *)&align_strip_kernel<16, kAlgSW>, (const void *)&align_strip_kernel<16, kAlgNW>},
-     {(const void *)&align_strip_kernel<16, kAlgSW, true>, (const void *)&align_strip_kernel<16, kAlgNW, true>}, VALIGN_STRIP_SSE(16),
-     VALIGN_STRIP_WIDE_NW(16), VALIGN_STRIP_BAND(16), VALIGN_STRIP_CKPT(16)},
-    {12, &strip_lds<12>, {(const void *)&align_strip_kernel<12, kAlgSW>, (const void *)&align_strip_kernel<12, kAlgNW>},
-     {(const void *)&align_strip_kernel<12, kAlgSW, true>, (const void *)&align_strip_kernel<12, kAlgNW, true>}, VALIGN_STRIP_SSE(12),
-     VALIGN_STRIP_WIDE_NW(12), {{{nullptr, nullptr}, {nullptr, nullptr}}, {{nullptr, nullptr}, {nullptr, nullptr}}}, VALIGN_STRIP_CKPT(12)},
-    {8, &strip_lds<8>, {(const void *)&align_strip_kernel<8, kAlgSW>, (const void *)&align_strip_kernel<8, kAlgNW>},
-     {(const void *)&align_strip_kernel<8, kAlgSW, true>, (const void *)&align_strip_kernel<8, kAlgNW, true>}, VALIGN_STRIP_SSE(8),
-     VALIGN_STRIP_WIDE_ALL(8), VALIGN_STRIP_BAND_WIDE(8), VALIGN_STRIP_CKPT(8)},
-};
-#undef VALIGN_STRIP_CKPT
-#undef VALIGN_STRIP_CKPT_ALG
-#undef VALIGN_STRIP_SSE
-#undef VALIGN_STRIP_BAND
-#undef VALIGN_STRIP_BAND_WIDE
-#undef VALIGN_STRIP_BAND_ALG
-#undef VALIGN_STRIP_BAND_WIDE_ALG
-#undef VALIGN_STRIP_WIDE_ALL
-#undef VALIGN_STRIP_WIDE_NW
-#undef VALIGN_STRIP_WIDE_NONE
+constexpr StripGeometry strip_geometry{K, {StripLds<K>::kRing, 0, StripLds<K>::kTotal}, &strip_kernel<K>};
+constexpr StripGeometry kStripGeometries[] = {strip_geometry<kStripKs[0]>, strip_geometry<kStripKs[1]>, strip_geometry<kStripKs[2]>};
+static_assert(sizeof(kStripKs) == 3 * sizeof(int), "a row per K that strip_plan.h chooses among");
 
 // Small batches: fill + traceback in one launch, pointer stream in LDS (align_fill_tag_kernel<..., FUSED>)
 struct FusedGeometry {
@@ -125,8 +97,7 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (route != AlignRoute::Register) {
         ran_align_fill_ = ran_fill_name(route);
-        align_strips_device(alg, n, d_reads, d_refs, d_rows, d_idx, stream, route == AlignRoute::StripWide || route == AlignRoute::StripWideBand,
-                            route == AlignRoute::StripBand || route == AlignRoute::StripWideBand, route == AlignRoute::StripCkpt);
+        align_strips_device(strip_mode(route, rule_inputs(), alg), n, d_reads, d_refs, d_rows, d_idx, stream);
         return false;
     }
     // the fill kernel of this mode -- and the geometry that has it: the plan's own, or the next full one (fallback kernels)
@@ -175,42 +146,16 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
         EndCell *part_ends = d_ends_.get() + part.slot;
         if (helper && region_used[part.region])          // the region's previous walk must be over before it is overwritten
             hip_check(hipStreamWaitEvent(stream, trace_done_[part.region].get(), 0), "hipStreamWaitEvent");
-        FillArgs f;
-        f.reads = d_reads + (size_t)begin * R_;
-        f.refs = d_refs + (size_t)begin * F_;
+        FillArgs f{};
+        put_sweep(f, d_reads + (size_t)begin * R_, d_refs + (size_t)begin * F_, cnt, blocks8, plan.lds);
         f.ptr = part_ptr;
         f.ends = part_ends;
-        f.n = cnt;
-        f.R = R_;
-        f.F = F_;
-        f.prof_area = plan.lds.prof_area;
-        f.refc_stride = plan.lds.refc_stride;
-        f.wave_lds = plan.lds.total;
-        f.blocks8 = blocks8;
-        put_scoring(f);
         void *fargs[] = {&f};
         const long long blocks = (cnt + ppb - 1) / ppb;
         hip_check(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(plan.waves_per_block * kWave), fargs,
                                   (size_t)block_lds, stream),
                   "hipLaunchKernel(align_fill_kernel)");
-        TraceArgs t{};
-        t.reads = f.reads;
-        t.refs = f.refs;
-        t.ptr = part_ptr;
-        t.ends = part_ends;
-        t.rows = d_rows + (size_t)begin * 2 * AL;
-        t.idx = d_idx + (size_t)begin * 4;
-        t.n = cnt;
-        t.R = R_;
-        t.F = F_;
-        t.G = G;
-        t.K = K;
-        t.pad_rows = G * K - R_;
-        t.blocks8 = blocks8;
-        t.alg = alg;
-        put_scoring(t);
-        t.affine = sc_.affine ? 1 : 0;
-        t.sse_policy = sse_policy_ ? 1 : 0;
+        TraceArgs t = trace_args(alg, f.reads, f.refs, cnt, part_ptr, part_ends, d_rows + (size_t)begin * 2 * AL, d_idx + (size_t)begin * 4, G, K, G * K - R_, blocks8);
         t.tagged = affine_tagged ? 2 : ((tagged && !sse_policy_) ? 1 : 0);     // SSE tags are the stored states
         void *targs[] = {&t};
         hipStream_t walk_stream = stream;
@@ -283,16 +228,7 @@ bool Engine::align_fused(int alg, long long n, const uint8_t *d_reads, const uin
     }
     if (!best) return false;
     FillArgs f{};
-    f.reads = d_reads;
-    f.refs = d_refs;
-    f.n = n;
-    f.R = R_;
-    f.F = F_;
-    f.prof_area = best_lds.prof_area;
-    f.refc_stride = best_lds.refc_stride;
-    f.wave_lds = best_lds.total;
-    f.blocks8 = best_blocks;
-    put_scoring(f);
+    put_sweep(f, d_reads, d_refs, n, best_blocks, best_lds);
     f.out_rows = d_rows;
     f.out_idx = d_idx;
     if (cigar_) {                          // the end cells leave the wave's LDS too: the encoder places the alignment with them
@@ -318,170 +254,105 @@ bool Engine::align_fused(int alg, long long n, const uint8_t *d_reads, const uin
     return true;
 }
 
-void Engine::align_strips_device(int alg, long long n, const uint8_t *d_reads, const uint8_t *d_refs, uint8_t *d_rows,
-                         short *d_idx, hipStream_t stream, bool wide, bool band, bool ckpt) {
-    const bool affine = sc_.affine;
-    if (ckpt && (wide || band || sse_policy_)) throw std::runtime_error("checkpointed traceback: plain int16 row strips only");
-    if (sse_policy_ && affine)
-        throw std::runtime_error("traceback_policy = 1 (SSE/AVX tie-breaks) exists for the linear gap model only");
-    const int wide_mode = affine ? 1 : (sse_policy_ ? 2 : 0);
-    // 16 rows per lane unless fewer leave less padding: 1 024-row strips cost 136 ms where 768-row strips cost 152 and 512-row
-    // strips 156 (10 kbp x 10 kbp, 4 096 pairs; 24 and 32 rows per lane -- 218 / 221 ms, two waves per SIMD by their
-    // registers -- are gone).  LDS no longer depends on the shape: the profile of the strip's rows and a 256-byte ring.
-    const StripGeometry *geo = nullptr;
-    WaveLds lds{};
-    double best_cost = 0.0;
-    for (const StripGeometry &g : kStripGeometries) {
-        if (affine && !g.affine_kernel[alg]) continue;
-        if (sse_policy_ && !g.sse_kernel[alg]) continue;
-        if (wide && !g.wide_kernel[alg][wide_mode]) continue;
-        if (band && !g.band_kernel[alg][wide ? 1 : 0][affine ? 1 : 0]) continue;
-        if (strip_k_ && g.K != strip_k_) continue;
-        const int rows_g = 64 * g.K;
-        const double cost = (double)((R_ + rows_g - 1) / rows_g) * rows_g * (g.K == 16 ? 1.0 : (g.K == 12 ? 1.115 : 1.147));
-        if (!geo || cost < best_cost) {
-            geo = &g;
-            lds = g.lds(rows_g, F_);
-            best_cost = cost;
-        }
+// what the two walks' TraceArgs share (register sweep: G x K is the geometry; strips: 64 x K and the padding of all strips)
+TraceArgs Engine::trace_args(int alg, const uint8_t *d_reads, const uint8_t *d_refs, long long n, const unsigned *ptr, const EndCell *ends,
+                             uint8_t *rows, short *idx, int G, int K, int pad_rows, int blocks8) const {
+    TraceArgs t{};
+    put_sweep(t, d_reads, d_refs, n, blocks8);
+    t.ptr = ptr;
+    t.ends = ends;
+    t.rows = rows;
+    t.idx = idx;
+    t.G = G;
+    t.K = K;
+    t.pad_rows = pad_rows;
+    t.alg = alg;
+    t.affine = sc_.affine ? 1 : 0;
+    t.sse_policy = sse_policy_ ? 1 : 0;
+    return t;
+}
+
+void Engine::align_strips_device(const StripMode &mode, long long n, const uint8_t *d_reads, const uint8_t *d_refs, uint8_t *d_rows,
+                         short *d_idx, hipStream_t stream) {
+    // ---- the plan (strip_plan.h): rows per lane, strips, what a pair-of-pairs holds in the scratch, the chunk ----
+    const int K = strip_rows_per_lane(R_, mode, strip_k_);
+    if (!K) throw std::runtime_error("no strip alignment kernel for this mode");
+    const StripGeometry &geo = *std::find_if(std::begin(kStripGeometries), std::end(kStripGeometries), [&](const StripGeometry &g) { return g.K == K; });
+    const WaveLds &lds = geo.lds;
+    BandShape band = kNoBand;           // every strip's pointer region is sized by the widest strip window (the block band, band_window.h)
+    if (mode.band) {
+        int block_rows, col_align;
+        band_block_shape(block_rows, col_align);
+        band = strip_band_shape(R_, band_width_, block_rows, col_align);
     }
-    if (!geo) throw std::runtime_error("no strip alignment kernel for this mode");
-    const int K = geo->K, rows = 64 * K, AL = R_ + F_;
-    const int strips = std::max(1, (R_ + rows - 1) / rows), pad_total = strips * rows - R_;
-    // band: every strip's pointer region is sized by the widest strip window (the block band, band_window.h)
-    BandShape bs{-1, 1, 1, 0};
-    int max_cols = F_;
-    if (band) {
-        band_block_shape(bs.block_rows, bs.col_align);
-        bs.half = band_width_ / 2;
-        bs.pad = (R_ + bs.block_rows - 1) / bs.block_rows * bs.block_rows - R_;
-        max_cols = 0;
-        for (int s = 0; s < strips; ++s) {
-            int c_lo, cols;
-            band_rows_window(bs, s * rows - pad_total, (s + 1) * rows - pad_total - 1, R_, F_, c_lo, cols);
-            max_cols = std::max(max_cols, cols);
-        }
-    }
-    const int blocks8 = (max_cols + 63 + 7) / 8;
-    const int row_dwords = ((F_ + 71) / 64 + 2) * 64;
-    const size_t strip_words = (size_t)blocks8 * 64 * K * (affine ? 2 : 1);    // per wave (= pair-of-pairs) and strip
-    // boundary row sets: H, and F beside it (affine); int32 cells: those per pair
-    const int row_sets = (affine ? 2 : 1) * (wide ? 2 : 1);
-    // checkpointed traceback: ONE region, a boundary row set per strip but the last, the walk state of the two pairs (ckpt_plan.h)
-    const CkptPlan cp = ckpt_plan(R_, F_, K, affine);
-    if (ckpt && (cp.strips != strips || cp.blocks8 != blocks8 || cp.row_dwords != row_dwords || cp.region_bytes != strip_words * 4 || cp.row_sets != row_sets))
-        throw std::runtime_error("checkpointed traceback: the plan and the strips disagree");
-    const size_t bytes_per_pp = ckpt ? cp.bytes_per_pp : strip_words * 4 * strips + (size_t)2 * row_sets * row_dwords * 4;
-    align_ptr_bytes_per_pair_ = (long long)(strip_words * 4 * (ckpt ? 1 : strips) / 2);
-    align_ckpt_bytes_per_pair_ = ckpt ? (long long)((cp.row_bytes + cp.state_bytes) / 2) : 0;
+    const StripPlan plan = strip_plan(R_, F_, K, mode, band);
+    const int strips = plan.strips, AL = R_ + F_;
+    align_ptr_bytes_per_pair_ = plan.ptr_bytes_per_pair;
+    align_ckpt_bytes_per_pair_ = plan.ckpt_bytes_per_pair;
     size_t free_b = 0, total_b = 0;
     hip_check(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
-    // (the pointer stream of a 10 kbp x 10 kbp pair-of-pairs is 50 MB: what fits the scratch is what runs side by side --
-    // 24 GB, the bound until round 4, kept 480 waves on 1 024 SIMDs; half of the free HBM, at most 128 GB, now)
-    size_t cap = std::min<size_t>(128ull << 30, std::max<size_t>((free_b + d_ptr_.bytes()) / 2, 256ull << 20));
-    if (scratch_cap_mb_ > 0) cap = std::min<size_t>(cap, (size_t)scratch_cap_mb_ << 20);
-    const long long chunk = strip_chunk_pairs(cap, bytes_per_pp, n);
+    const long long chunk = strip_chunk_pairs(strip_scratch_cap(free_b + d_ptr_.bytes(), scratch_cap_mb_), plan.bytes_per_pp, n);
     const long long waves = chunk / 2;
-    ensure_trace_scratch(chunk, bytes_per_pp, 2, stream);      // (chunk is even: waves * bytes_per_pp bytes, chunk end cells)
+    // ---- reserve ----
+    ensure_trace_scratch(chunk, plan.bytes_per_pp, 2, stream);      // (chunk is even: waves * bytes_per_pp bytes, chunk end cells)
     if ((size_t)2 * n * sizeof(int) > d_first_bad_.bytes()) {
         hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
         d_first_bad_.reserve((size_t)2 * n * sizeof(int), "first invalid positions");
     }
-    // two rows per pair-of-pairs behind the pointers; ckpt: strips - 1 row sets behind the one region, the walk states behind those
-    unsigned *boundary = d_ptr_.get() + (size_t)waves * strip_words * (ckpt ? 1 : strips);
-    WalkState *walk = reinterpret_cast<WalkState *>(boundary + (size_t)(strips - 1) * row_sets * waves * row_dwords);      // (ckpt only)
+    WalkState *walk = mode.ckpt ? reinterpret_cast<WalkState *>(d_ptr_.get() + plan.walk_at(waves)) : nullptr;
+    const void *fn = geo.kernel(mode, 0), *refill_fn = mode.ckpt ? geo.kernel(mode, 1) : fn;
+    if (lds.total > kDefaultBlockLds)
+        for (const void *f : {fn, refill_fn})
+            hip_check(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds.total), "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+    // ---- launches: the rows zeroed and the first invalid positions once, then chunk after chunk its strips and its walk ----
     hip_check(hipMemsetAsync(d_rows, 0, (size_t)n * 2 * AL, stream), "hipMemsetAsync(rows)");
     hipLaunchKernelGGL(first_invalid_kernel, dim3((unsigned)n), dim3(kWave), 0, stream, d_reads, d_refs, n, R_, F_, d_first_bad_.get(),
                        sse_policy_ ? 1 : 0);
     hip_check(hipGetLastError(), "hipLaunchKernel(first_invalid_kernel)");
-    const void *refill_fn = ckpt ? geo->ckpt_kernel[alg][affine ? 1 : 0][1] : nullptr;
-    const void *fn = ckpt ? geo->ckpt_kernel[alg][affine ? 1 : 0][0]
-                     : band ? geo->band_kernel[alg][wide ? 1 : 0][affine ? 1 : 0]
-                          : wide ? geo->wide_kernel[alg][wide_mode] : (affine ? geo->affine_kernel[alg] : (sse_policy_ ? geo->sse_kernel[alg] : geo->kernel[alg]));
-    if (lds.total > kDefaultBlockLds) {
-        hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds.total),
-                  "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-        if (refill_fn)
-            hip_check(hipFuncSetAttribute(refill_fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds.total),
-                      "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-    }
     for (long long begin = 0; begin < n; begin += chunk) {
         const long long cnt = std::min(chunk, n - begin), cnt_waves = (cnt + 1) / 2;
-        // the boundary row set below strip s: the two that ping-pong -- or, checkpointed, strip s's own (the last strip has none)
-        auto row_set = [&](int s) { return boundary + (size_t)(ckpt ? std::min(s, std::max(strips - 2, 0)) : (s & 1)) * row_sets * waves * row_dwords; };
-        auto strip_args = [&](int s) {
-            StripArgs a;
-            a.reads = d_reads + (size_t)begin * R_;
-            a.refs = d_refs + (size_t)begin * F_;
-            a.ptr = d_ptr_.get() + (ckpt ? 0 : (size_t)s * cnt_waves * strip_words);
+        const uint8_t *reads = d_reads + (size_t)begin * R_, *refs = d_refs + (size_t)begin * F_;
+        const unsigned walk_blocks = (unsigned)((cnt + 255) / 256);
+        auto launch_strip = [&](const void *kernel, int s, const char *what) {
+            StripArgs a{};
+            put_sweep(a, reads, refs, cnt, plan.blocks8, lds);
+            a.ptr = d_ptr_.get() + plan.region_at(cnt_waves, s);
             a.ends = d_ends_.get();
             a.first_bad = d_first_bad_.get() + 2 * begin;
-            a.top = row_set(s > 0 ? s - 1 : 0);                          // (unused for strip 0)
-            a.bottom = row_set(s);                                       // (not written by the last strip)
-            a.top_f = a.top + (size_t)waves * row_dwords;                // (only read / written by the affine kernel)
-            a.bottom_f = a.bottom + (size_t)waves * row_dwords;
-            a.n = cnt;
-            a.R = R_;
-            a.F = F_;
-            a.prof_area = lds.prof_area;
-            a.refc_stride = lds.refc_stride;
-            a.wave_lds = lds.total;
-            a.blocks8 = blocks8;
+            a.top = d_ptr_.get() + plan.top_at(waves, s);
+            a.bottom = d_ptr_.get() + plan.bottom_at(waves, s);
+            a.top_f = a.top + plan.f_rows_at(waves);      // (only read / written by the affine kernel)
+            a.bottom_f = a.bottom + plan.f_rows_at(waves);
             a.strip = s;
             a.strips = strips;
-            a.row_dwords = row_dwords;
-            a.band = bs;
+            a.row_dwords = plan.row_dwords;
+            a.band = plan.band;
             a.walk = walk;
-            put_scoring(a);
-            return a;
-        };
-        for (int s = 0; s < strips; ++s) {
-            StripArgs a = strip_args(s);
             void *kargs[] = {&a};
-            hip_check(hipLaunchKernel(fn, dim3((unsigned)cnt_waves), dim3(kWave), kargs, (size_t)lds.total, stream),
-                      "hipLaunchKernel(align_strip_kernel)");
-        }
-        TraceArgs t{};
-        t.reads = d_reads + (size_t)begin * R_;
-        t.refs = d_refs + (size_t)begin * F_;
-        t.ptr = d_ptr_.get();
-        t.ends = d_ends_.get();
-        t.rows = d_rows + (size_t)begin * 2 * AL;
-        t.idx = d_idx + (size_t)begin * 4;
-        t.n = cnt;
-        t.R = R_;
-        t.F = F_;
-        t.G = 64;
-        t.K = K;
-        t.pad_rows = pad_total;
-        t.blocks8 = blocks8;
-        t.alg = alg;
-        put_scoring(t);
-        t.affine = affine ? 1 : 0;
-        t.sse_policy = sse_policy_ ? 1 : 0;
-        t.strip_rows = rows;
-        t.strip_words = (long long)(cnt_waves * strip_words);
-        t.wide_score = wide ? 1 : 0;
-        t.band = bs;
-        if (ckpt) {
+            hip_check(hipLaunchKernel(kernel, dim3((unsigned)cnt_waves), dim3(kWave), kargs, (size_t)lds.total, stream), what);
+        };
+        for (int s = 0; s < strips; ++s) launch_strip(fn, s, "hipLaunchKernel(align_strip_kernel)");
+        TraceArgs t = trace_args(mode.alg, reads, refs, cnt, d_ptr_.get(), d_ends_.get(), d_rows + (size_t)begin * 2 * AL, d_idx + (size_t)begin * 4, 64, K,
+                                 plan.pad_total, plan.blocks8);
+        t.strip_rows = plan.rows;
+        t.strip_words = (long long)plan.region_stride(cnt_waves);
+        t.wide_score = mode.wide ? 1 : 0;
+        t.band = plan.band;
+        if (mode.ckpt) {
             // the backward pass: per strip, last to first, re-fill it into the one region and let the walks cross it
-            hipLaunchKernelGGL(walk_init_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, (const EndCell *)d_ends_.get(), walk, cnt, AL);
+            hipLaunchKernelGGL(walk_init_kernel, dim3(walk_blocks), dim3(256), 0, stream, (const EndCell *)d_ends_.get(), walk, cnt, AL);
             hip_check(hipGetLastError(), "hipLaunchKernel(walk_init_kernel)");
             for (int s : ckpt_rounds(strips)) {
-                StripArgs a = strip_args(s);
-                void *kargs[] = {&a};
-                hip_check(hipLaunchKernel(refill_fn, dim3((unsigned)cnt_waves), dim3(kWave), kargs, (size_t)lds.total, stream),
-                          "hipLaunchKernel(align_strip_kernel, re-fill)");
-                hipLaunchKernelGGL(traceback_ckpt_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, t, walk, s);
+                launch_strip(refill_fn, s, "hipLaunchKernel(align_strip_kernel, re-fill)");
+                hipLaunchKernelGGL(traceback_ckpt_kernel, dim3(walk_blocks), dim3(256), 0, stream, t, walk, s);
                 hip_check(hipGetLastError(), "hipLaunchKernel(traceback_ckpt_kernel)");
             }
-            if (cigar_) launch_cigar(stream, t.rows, t.idx, d_ends_.get(), begin, cnt);
-            continue;
+        } else {
+            void *targs[] = {&t};
+            hip_check(hipLaunchKernel(mode.band ? (const void *)&traceback_band_kernel : (const void *)&traceback_kernel, dim3(walk_blocks), dim3(256), targs, 0,
+                                      stream),
+                      "hipLaunchKernel(traceback_kernel)");
         }
-        void *targs[] = {&t};
-        hip_check(hipLaunchKernel(band ? (const void *)&traceback_band_kernel : (const void *)&traceback_kernel, dim3((unsigned)((cnt + 255) / 256)),
-                                  dim3(256), targs, 0, stream),
-                  "hipLaunchKernel(traceback_kernel)");
         if (cigar_) launch_cigar(stream, t.rows, t.idx, d_ends_.get(), begin, cnt);      // (before the next chunk's fill reuses d_ends_)
     }
 }
