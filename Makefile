@@ -13,7 +13,7 @@ test:
 test-gpu:
 	$(PY) -m pytest tests -q -m gpu
 
-# CPU sanitizers: host_pipeline.h under TSan and ASan/UBSan, cell_rules.h, strip_plan.h and ckpt_plan.h under ASan/UBSan, then the CPU suite against -fsanitize builds of
+# CPU sanitizers: host_pipeline.h under TSan and ASan/UBSan, cell_rules.h, strip_plan.h, long_plan.h and ckpt_plan.h under ASan/UBSan, then the CPU suite against -fsanitize builds of
 # libvalignhost.so, valign-bench and oracle/cpu_ref.c (tools/sanitize.sh)
 sanitize:
 	tools/sanitize.sh

@@ -24,4 +24,6 @@ def test_engine_uses_the_checked_rules():
         text = open(os.path.join(CSRC, unit)).read()
         for rule in ("band_nw_int16_ok", "band_nw_connects", "band_nw_check"):
             assert "Engine::" + rule not in text and "bool " + rule + "(" not in text, (unit, rule)
-    assert "band_nw_check(" in open(os.path.join(CSRC, "engine_long.hip")).read()
+    # (the score path's refusals are thrown where its route is decoded: long_plan.h, which engine_long.hip asks)
+    assert "band_nw_check(" in open(os.path.join(CSRC, "long_plan.h")).read()
+    assert "long_mode(alg, true)" in open(os.path.join(CSRC, "engine_long.hip")).read()

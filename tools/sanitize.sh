@@ -4,7 +4,7 @@
 #      gather, scatter) as a stand-alone program under -fsanitize=thread and under -fsanitize=address,undefined;
 #      and the engine's cell-range rules and path choice (versalignlib_amd/csrc/cell_rules.h, tests/cell_rules_check.cpp)
 #      and the plans of the strip path and of its checkpointed traceback (versalignlib_amd/csrc/strip_plan.h, ckpt_plan.h;
-#      tests/strip_plan_check.cpp, tests/ckpt_plan_check.cpp)
+#      tests/strip_plan_check.cpp, tests/ckpt_plan_check.cpp) and of the long-read score path (long_plan.h; tests/long_plan_check.cpp)
 #      under -fsanitize=address,undefined;
 #   2. libvalignhost.so, valign-bench and the oracle (oracle/cpu_ref.c) built with -fsanitize=address,undefined
 #      into build/sanitize/, and the whole CPU test-suite run against THOSE (python gets the runtimes preloaded).
@@ -31,6 +31,9 @@ g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/ckpt_plan_check.cpp" -o "$OU
 echo "== strip_plan.h under AddressSanitizer + UBSan"
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/strip_plan_check.cpp" -o "$OUT/strip_plan_asan"
 "$OUT/strip_plan_asan"
+echo "== long_plan.h under AddressSanitizer + UBSan"
+g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/long_plan_check.cpp" -o "$OUT/long_plan_asan"
+"$OUT/long_plan_asan"
 echo "== the band_nw rules of cell_rules.h under AddressSanitizer + UBSan"
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/band_nw_rules_check.cpp" -o "$OUT/band_nw_rules_asan"
 "$OUT/band_nw_rules_asan"

@@ -32,19 +32,12 @@
 #pragma once
 
 #include "dp_kernels.hip.h"
+#include "long_plan.h"
 
 namespace valign {
 
-constexpr int kBandG = 32;                 // lanes per group: two groups (= two pairs at a time) per wave
-constexpr int kBandGroups = kWave / kBandG;
-constexpr int kBandSlabs = 4 * kBandGroups + 1;                // (class, group) + one all-zero slab (both groups)
-
-struct BandBlock {          // per row block, computed once on the host (Engine::band_plan)
-    int start;              // column of the block's first step (its window's first column - 1: the warm-up column)
-    int lo;                 // first column of the window, clipped to the matrix (0x3FFFFFFF: nothing to compute)
-    int span;               // last column - first column
-    int delay;              // steps between the predecessor's write and this block's read of the same column
-};
+// kBandG, kBandGroups, kBandSlabs, BandBlock and the LDS layout BandLds<K>: long_plan.h (the host plans with them, on the CPU too)
+static_assert(kPlanWave == kWave, "long_plan.h sizes the rings for this wave");
 
 struct BandArgs {
     const uint8_t *reads;
@@ -63,25 +56,6 @@ struct BandArgs {
     short match, mismatch;
     short gap_read, gap_ref;
     short open_read, ext_read, open_ref, ext_ref;     // AFFINE instantiations (all <= 0)
-};
-
-template <int K>
-struct BandLds {
-    static constexpr int kRowChunks = K / 8;
-    static constexpr int kChunkBytes = kBandSlabs * kBandG * 16;          // one 8-row chunk (int16 scores) of every slab
-    static constexpr int kProf = 0;
-    static constexpr int kProfBytes = kRowChunks * kChunkBytes;
-    // (the reference rings are addressed as base | column: aligned to their own size, code_cols a power of two)
-    __host__ __device__ static int codes(int code_cols) { return (kProfBytes + code_cols - 1) / code_cols * code_cols; }
-    // (the delay rings are addressed as base | offset: aligned to one lane's ring)
-    __host__ __device__ static int ring(int code_cols, int ring_depth) {
-        const int at = codes(code_cols) + kBandGroups * code_cols, a = ring_depth * 4;
-        return (at + a - 1) / a * a;
-    }
-    // (ring_depth 0: the unit-delay kernel, no ring; affine: a second ring, for F, behind the first)
-    __host__ __device__ static int total(int code_cols, int ring_depth, bool affine = false) {
-        return ring(code_cols, ring_depth ? ring_depth : 1) + kWave * ring_depth * 4 * (affine ? 2 : 1);
-    }
 };
 
 // SYM: gap_read == gap_ref (one saturating subtract per cell serves both neighbours).

@@ -6,6 +6,7 @@
 //   engine_score.hip .... score_alignments: register-sweep launches, the host-pointer chunk pipeline, 4-bit class
 //                         unpacking, length-sorted batches (reference: DefaultKernel.cpp:52-202)
 //   engine_long.hip ..... long reads: row strips (score_long_kernel) and the banded block chain (score_band_kernel)
+//   long_plan.h ......... the route of a long-read score call, its compiled instances, strip sizes and the chain's plan (pure, CPU-tested)
 //   engine_align.hip .... compute_alignments: fill + traceback launches, row strips, the fused small-batch launch, the
 //                         host-pointer pipeline with its copy-issuing thread (reference: DefaultKernel.cpp:21-50, 204-525)
 //   engine_cigar.hip .... the compact result format: records + CIGAR ops encoded on the device behind the walks (cigar_kernels.hip.h)
@@ -42,6 +43,7 @@
 #include "band_kernels.hip.h"
 #include "cigar_kernels.hip.h"
 #include "long_kernels.hip.h"
+#include "long_plan.h"
 #include "pack_kernels.hip.h"
 #include "ragged_kernels.hip.h"
 #include "strip_kernels.hip.h"
@@ -137,9 +139,6 @@ constexpr int kMaxBlockLds = 160 * 1024;       // gfx950: 160 KiB per CU, one bl
 constexpr int kSlots = 4;                      // staging slots of the host-pointer pipeline
 constexpr int kDefaultBlockLds = 64 * 1024;    // above this the kernel attribute must be raised
 
-// Long-read path (row strips + column phases, long_kernels.hip.h): one geometry.
-constexpr int kLongG = 16, kLongK = 10;
-
 struct LaunchPlan {
     bool long_mode = false;        // sequences too long for one register sweep / LDS-resident reference
     const Geometry *geo = nullptr;
@@ -217,6 +216,7 @@ public:
         if (diagonals < 0) throw std::runtime_error("band_width must be >= 0");
         band_width_ = diagonals;
         if (diagonals > 0 && !plan_.long_mode) plan_ = long_plan();
+        band_plan_ = band_chain_plan(R_, F_, band_width_, sc_.affine);      // (once per band_width: shape and scoring are the engine's)
     }
     int band_width() const { return band_width_; }
     // Alignments under band_width (opt-in, so that band_width keeps its meaning for existing callers): 1 = compute_alignments
@@ -306,38 +306,25 @@ public:
     // n sequences of `len` 4-bit classes -> n * len canonical bytes (pack_kernels.hip.h)
     void launch_unpack(const uint8_t *d_packed, uint8_t *d_out, long long n, int len, hipStream_t stream);
 
-    // ---- banded Smith-Waterman scores, linear gaps: the cyclic block chain of band_kernels.hip.h ----
-    static constexpr int kBandK = VALIGN_HIP_BAND_CHAIN_BLOCK_ROWS;              // rows per block = the band definition's block (describe: band_block_rows)
+    // ---- long reads (engine_long.hip; long_plan.h decodes the route, sizes the strips and plans the chain) ----
+    // What long_score_mode reads of this engine beyond the rule inputs, and the route of a score call of `alg` that takes the
+    // long-read path.  refuse: throw what the call refuses; false: the route it would have taken (describe, score_host)
+    LongFacts long_facts(int alg) const {
+        return LongFacts{band_width_, band_nw_, score_wide_cells(alg), dbg_.on("short_strips"), dbg_.on("no_single_strip"), no_band_chain_, band_plan_.usable};
+    }
+    LongScoreMode long_mode(int alg, bool refuse) const { return long_score_mode(rule_inputs(), alg, long_facts(alg), refuse); }
 
-    struct BandPlan {
-        bool usable = false, unit_delay = false;
-        int nb = 0, first_block = 0, pad_rows = 0, d = 0, ring_depth = 0, code_cols = 0, events = 0;
-        long long cells = 0;                // DP cells one pair's band windows hold (what the chain actually sweeps)
-        std::vector<BandBlock> blocks;
-        std::vector<int> fill_to;
-    };
-
-    // Windows, start distance, delays and ring sizes of the block chain for (R, F, band): what tools/band_schedule_model.py
-    // calls plan().  `usable` is false where the chain does not pay or does not fit (then score_long_kernel's strips run).
-    BandPlan make_band_plan() const;
-
-    // score_alignments(band_width > 0) on the block chain (alg: SW, or the NW variant under band_nw); false: not applicable
-    // here (strips run instead)
-    bool score_band_device(int alg, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int16_t *d_scores, hipStream_t stream);
-    bool band_chain_in_use() const;
-    bool long_single_strip(bool wide) const;
-
-    // Long sequences: strips of kLongG*kLongK rows, boundary rows through an HBM scratch.
-    void score_long_device(int alg, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int16_t *d_scores,
-                           hipStream_t stream, bool wide);
+    // Row strips of the mode's G * K rows, boundary rows through an HBM scratch -- or, banded, the block chain.
+    void score_long_device(int alg, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int16_t *d_scores, hipStream_t stream);
+    // Banded scores (SW and, under band_nw, the NW variant; linear and affine gaps) on the cyclic block chain of
+    // band_kernels.hip.h, for a mode whose route is the chain; its tables follow band_width_ (sync_band_tables)
+    void sync_band_tables(hipStream_t stream);
+    void score_band_device(const LongScoreMode &mode, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int16_t *d_scores, hipStream_t stream);
 
     // The cell format score_alignments is PREDICTED to compute in for this mode: a device-resident call of n pairs (n <= 0:
     // a large call) at the engine's full shape.  What a call really launched is ran_score_cells(): the host pipeline's
     // chunks may be small enough for the latency plan, and length-sorted batches sweep each length class on a plan of its own.
     const char *score_cell_format(int alg, long long n = 0) const;
-    // the long-read score kernel of this mode runs on half-float cells (score_long_device; describe predicts with it)
-    bool long_score_f16(int alg, bool wide) const;
-    bool long_tall_strips() const;         // score_long_device sweeps on the 512-row strips (kLongTall)
     // what the last score / alignment call launched (describe: ran_score_cells, ran_align_fill)
     std::string ran_score_cells() const;
     const char *ran_align_fill() const { return ran_align_fill_; }
@@ -682,8 +669,8 @@ private:
     long long slot_begin_[kSlots] = {}, slot_pending_[kSlots] = {};
     long long staged_pairs_ = 0, align_staged_pairs_ = 0;
     bool pack_ = true;                                                   // host_packing: 4-bit base classes across PCIe
-    BandPlan band_plan_;               // banded linear SW: the block chain's plan for band_plan_width_, its tables on the device
-    int band_plan_width_ = -1;
+    BandPlan band_plan_;               // the block chain's plan for band_width_ (set_band_width)
+    int band_tables_width_ = -1;       // ... and the band_width whose tables are on the device
     int band_blocks_per_cu_ = 0, band_lds_ = 0;          // of the last block-chain launch (describe)
     int long_strip_rows_ = 0;                            // rows per strip of the last score_long_kernel launch (describe)
     // Cell formats of the score kernels the last score call launched, one bit each (kRanF16 / kRanInt16 / kRanInt32; a

@@ -62,11 +62,8 @@ Engine::~Engine() {
 
 const char *Engine::score_cell_format(int alg, long long n) const {
     if (alg > 1) return "none";
-    if ((alg == kAlgSW || band_nw_) && band_chain_in_use()) return "int32";
-    if (alg == kAlgNW && band_nw_ && band_width_ > 0) return "int32";          // (the banded NW strips: int32 cells)
-    if (score_wide_cells(alg)) return "int32";
-    // (long-read kernels: Smith-Waterman with one gap score on the 160-row strips, engine_long.hip)
-    if (plan_.long_mode) return long_score_f16(alg, false) ? "f16" : "int16";
+    // the long-read kernels (a band takes them; int32 cells exist there only): the route's cells (long_plan.h)
+    if (plan_.long_mode || band_width_ > 0 || score_wide_cells(alg)) return long_cells_name(long_mode(alg, false).cells);
     // the plan score_device launches for a call of n pairs: small calls sweep on the latency plan, whose rows enter the
     // NW variant's tilt
     const LaunchPlan &plan = (n > 0 && n <= (long long)latency_plan_.pairs_per_wave * 1024 && band_width_ == 0) ? latency_plan_ : plan_;
@@ -121,7 +118,7 @@ std::string Engine::describe(int opt, long long n) const {
              host_stats_.cells_padded > 0 ? host_stats_.cells_swept / host_stats_.cells_padded : 1.0,
              score_cell_format(opt & 0xF, n), host_stats_.direct, host_stats_.packed, host_stats_.direct_out,
              ((opt & 0xF) == kAlgSW || band_nw_) ? band_rows : VALIGN_HIP_BAND_BLOCK_ROWS, ((opt & 0xF) == kAlgSW || band_nw_) ? band_align : VALIGN_HIP_BAND_COL_ALIGN,
-             band_blocks_per_cu_, band_lds_, (band_plan_width_ == band_width_ && band_plan_.usable) ? band_plan_.cells : 0ll, long_strip_rows_, host_stats_.d2h_row_bytes / 1e6, host_stats_.full_row_bytes / 1e6, host_stats_.gather_ms, host_stats_.classify_ms, host_stats_.wait_ms,
+             band_blocks_per_cu_, band_lds_, (band_tables_width_ == band_width_ && band_plan_.usable) ? band_plan_.cells : 0ll, long_strip_rows_, host_stats_.d2h_row_bytes / 1e6, host_stats_.full_row_bytes / 1e6, host_stats_.gather_ms, host_stats_.classify_ms, host_stats_.wait_ms,
              host_stats_.drain_ms, ran_score_cells().c_str(), ran_align_fill_, band_alignments(), band_nw(), align_ptr_bytes_per_pair_, trace_checkpoints(),
              align_ckpt_bytes_per_pair_, (long long)d_ptr_.bytes(), ran_result_format_, cigar_d2h_bytes_,
              (long long)(d_cig_rows_[0].bytes() + d_cig_rows_[1].bytes()));
@@ -129,7 +126,7 @@ std::string Engine::describe(int opt, long long n) const {
 }
 
 void Engine::band_block_shape(int &block_rows, int &col_align) const {
-    const bool chain = band_chain_in_use();
+    const bool chain = long_mode(kAlgSW, false).chain;       // (of a Smith-Waterman call: describe() names the API's blocks for a refused NW one)
     block_rows = chain ? kBandK : VALIGN_HIP_BAND_BLOCK_ROWS;
     col_align = chain ? VALIGN_HIP_BAND_CHAIN_COL_ALIGN : VALIGN_HIP_BAND_COL_ALIGN;
 }

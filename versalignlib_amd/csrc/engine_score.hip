@@ -20,7 +20,7 @@ void Engine::score_device(int opt, long long n, const uint8_t *d_reads, const ui
                                  std::to_string(R_) + ", ref_length " + std::to_string(F_) + ")");
     const bool wide = score_wide_cells(alg);
     if (plan_.long_mode || wide) {      // int32 cells exist on the strip path only
-        score_long_device(alg, n, d_reads, d_refs, d_scores, stream, wide);
+        score_long_device(alg, n, d_reads, d_refs, d_scores, stream);
         return;
     }
     // ragged_batching on a device-resident batch: classify, pack and sweep by length class (ragged_kernels.hip.h).  The
@@ -113,10 +113,13 @@ void Engine::score_host(int opt, int n, const char *const *reads, const char *co
     const size_t per_pair = (size_t)R_ + F_;
     // Long reads on row strips: their launches follow one another on one stream (the strips' boundary rows are one scratch) and
     // a 48 MB chunk of 10 kbp pairs is 1 200 waves for 3 500 resident ones -- each launch runs at a third of the device.
-    // Chunks of up to 192 MB there (the banded block chain needs no scratch: its small chunks run side by side instead).
-    const bool wide_cells = score_wide_cells(alg);
-    const bool scratch_free = (band_width_ > 0 && (alg == kAlgSW || band_nw_) && band_chain_in_use()) || (plan_.long_mode && long_single_strip(wide_cells));
-    const bool strips_in_turn = plan_.long_mode && !scratch_free;
+    // Chunks of up to 192 MB there.  The route says which calls these are (long_plan.h): what score_device sends to the long-read
+    // kernels (int32 cells exist there only) and whose launches hand boundary rows on through the scratch.  The banded block
+    // chain keeps nothing in HBM between its steps: its chunks may run side by side on the slots' streams -- a chunk of 2 400
+    // pairs of 10 kbp fills 600 of the 4 096 resident waves and takes a launch's latency whatever its size -- and so do the
+    // single-strip instances (short reads against a long reference).
+    const bool shared_scratch = (plan_.long_mode || score_wide_cells(alg)) && long_mode(alg, false).brow;
+    const bool strips_in_turn = plan_.long_mode && shared_scratch;
     const size_t chunk_bytes = strips_in_turn && !dbg_.on("chunk_bytes") ? std::max<size_t>(score_chunk_bytes_, 192u << 20) : score_chunk_bytes_;
     long long chunk = per_pair ? (long long)(chunk_bytes / per_pair) : n;
     chunk = whole_rounds(chunk);
@@ -150,10 +153,6 @@ void Engine::score_host(int opt, int n, const char *const *reads, const char *co
     // is classified, packed by length class and swept class by class in HBM (ragged_kernels.hip.h)
     const bool ragged = !d_dest && ragged_applies(alg) && ragged_fits(chunk) &&
                         (ragged_ == 2 || sampled_cell_fraction(reads, refs, n) < 0.67);
-    // (the banded block chain keeps nothing in HBM between its steps: its chunks may run side by side on the slots' streams --
-    // a chunk of 2 400 pairs of 10 kbp fills 600 of the 4 096 resident waves and takes a launch's latency whatever its size)
-    // ... and so do the single-strip instances of the long-read kernel (short reads against a long reference)
-    const bool shared_scratch = !scratch_free && (plan_.long_mode || score_width_ == 32 || !score_int16_ok(alg));
     host_stats_ = HostStats{};
     auto drain = [&](int s) {
         if (slot_pending_[s] <= 0) return;

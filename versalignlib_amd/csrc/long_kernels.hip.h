@@ -25,10 +25,11 @@
 #include "dp_kernels.hip.h"
 #include "valign_hip.h"
 #include "band_window.h"
+#include "long_plan.h"
 
 namespace valign {
 
-constexpr int kPhase = 64;                 // steps between ring refills; must be >= G - 1
+// kPhase (long_plan.h): steps between ring refills; must be >= G - 1
 constexpr int kRing = 2 * kPhase;          // ring slots per lane group
 constexpr int kLead = 8;                   // columns the ring refill runs ahead of the phase (the sweep prefetches two)
 
