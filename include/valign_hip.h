@@ -316,6 +316,43 @@ int valign_hip_align_cigar_host(valign_hip_engine *e, int opt, int n, const char
                                 uint32_t *ops, long long ops_cap, long long *offsets,
                                 long long *ops_needed, int threads);
 
+/* ---- placed Smith-Waterman scores: score and end cell without a traceback ----
+ * What a mapper asks before it asks for an alignment: how good is the best local alignment of a pair, and WHERE in the
+ * reference does it end?  The score sweep answers both -- no pointer stream, no pointer scratch, no walk.
+ * For Smith-Waterman (opt & 0xF == 0):
+ *   score ....... the value valign_hip_score_device returns for the pair.
+ *   read_end, ref_end
+ *                 (read_end - 1, ref_end - 1) is the reference's end cell under the Default rules
+ *                 (src/Kernels/default/DefaultKernel.cpp:252-256): the first cell in row-major order whose value is strictly
+ *                 greater than every earlier one -- of all cells that hold the maximum the one in the earliest read row and,
+ *                 within that row, the earliest reference column.  So both are 0-based and half-open, and equal
+ *                 valign_hip_aln.read_end / .ref_end of valign_hip_align_cigar_device for the same pair.
+ *   empty ....... a pair whose maximum is 0 returns {0, 0, 0}.
+ * Placed scores run on int16 cells; ragged_batching and half_float_cells are not read by these calls.  opt & 0xF > 1 does
+ * nothing, as everywhere.  NOT BUILT HERE -- each is refused with a non-zero return and a message in valign_hip_last_error:
+ *   opt & 0xF == 1 ........ the NW variant's score (the maximum over the last row AND the last column) and its alignment's end
+ *                           cell (the arg-max of one row) are different cells in the reference: "placed" has no single meaning
+ *   band_width > 0 ........ banded scores
+ *   traceback_policy = 1 .. the SSE/AVX tie-breaks
+ *   score_width = 32, or a shape x scoring whose Smith-Waterman cells could leave int16 (the rule of the score path)
+ * "ran_placed" of valign_hip_describe says what the last call ran: "key" (register sweep, one end-cell key per lane), "rows"
+ * (register sweep, a first-arg-max per row: more than 16 rows per lane, or scores too large for the key), "strip" (reads of
+ * more than 1 024 rows or shapes no register geometry holds: the row strips' pointer-free forward pass), "none".          */
+typedef struct {                     /* 12 bytes */
+    int32_t score, read_end, ref_end;
+} valign_hip_placed;
+
+/* Device-resident: d_placed = n records.  Asynchronous on hip_stream, uses no pointer scratch and writes nothing but d_placed
+ * (the strip path keeps its boundary rows and end cells in an engine-owned scratch: calls of one engine that take it belong
+ * on one stream).                                                                                                            */
+int valign_hip_score_placed_device(valign_hip_engine *e, int opt, long long n, const void *d_reads,
+                                   const void *d_refs, void *d_placed, void *hip_stream);
+
+/* Host pointers in, records out: the gather -> pinned staging -> H2D -> kernel -> D2H chunk pipeline of
+ * valign_hip_score_host (4-bit classes under host_packing), 12 bytes per pair on the way back.                             */
+int valign_hip_score_placed_host(valign_hip_engine *e, int opt, int n, const char *const *reads,
+                                 const char *const *refs, valign_hip_placed *placed, int threads);
+
 /* Page-lock a host range and map it for the device (hipHostRegister behind a C symbol, so that an FFI caller needs no
  * HIP binding).  valign_hip_align_host into result buffers that lie inside a registered range -- or inside memory the
  * caller page-locked itself -- skips the library's pinned staging and its host-side copy: the device's copy engine
@@ -342,7 +379,8 @@ int valign_hip_set_half_float_cells(valign_hip_engine *e, int mode);
  * "align_ptr_bytes_per_pair" / "align_ckpt_bytes_per_pair" are the pointer-stream and checkpoint bytes a pair holds in the plan
  * of the last alignment call, "align_scratch_bytes" the pointer scratch the engine holds after it.
  * "ran_result_format" is "rows" or "cigar" for the last alignment call, "cigar_d2h_bytes" what the last
- * valign_hip_align_cigar_host call copied back, "cigar_rows_scratch_bytes" the rows scratch of the compact format.       */
+ * valign_hip_align_cigar_host call copied back, "cigar_rows_scratch_bytes" the rows scratch of the compact format.
+ * "ran_placed" is what the last placed-score call ran: key / rows / strip ("none" before any, or when it was refused).    */
 int valign_hip_describe(valign_hip_engine *e, int opt, long long n, char *buf, int cap);
 
 const char *valign_hip_last_error(void);

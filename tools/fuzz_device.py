@@ -2,7 +2,7 @@
 """Randomised sweep of the flat device / host API (developer tool; run on the GPU box): hipkernel.Engine objects created and
 destroyed by the hundred, score_device / align_device on torch tensors and random streams, score_host / align_host on numpy
 arrays (with and without a registered destination), length-sorted batching, bands, pointer-scratch caps -- every result
-against oracle/cpu_ref.  What tools/fuzz_parity.py does for the plugin ABI, for the entry points the tests of the device path
+against oracle/cpu_ref; placed Smith-Waterman scores (score_placed_device / _host) against tests/placed_ref.py.  What tools/fuzz_parity.py does for the plugin ABI, for the entry points the tests of the device path
 use; a process that runs it for minutes also exercises the library's set-up and tear-down far more often than the suite.
 
     python -X faulthandler tools/fuzz_device.py --seconds 300 --seed 1
@@ -22,9 +22,11 @@ import torch                                                       # noqa: E402
 from oracle import cpu_ref                                          # noqa: E402
 from versalignlib_amd import hipkernel, synth                      # noqa: E402
 import band_nw_ref                                                 # noqa: E402
+import placed_ref                                                  # noqa: E402
 
 
 NW_BAND_CASES = [0]             # cases that also ran the NW variant under the band
+PLACED_CASES = [0]              # cases that also ran placed Smith-Waterman scores
 
 
 def draw(rng):
@@ -117,6 +119,29 @@ def run(c):
             if c["host"]:
                 if not np.array_equal(eng.score_host(opt, reads, refs, threads=c["threads"]), exp):
                     return "score_host opt %d differs" % opt
+            # placed scores: every case that runs Smith-Waterman scores unbanded under traceback_policy 0, against the numpy
+            # restatement (tests/placed_ref.py: int64 cells -- a case whose cells could leave int16 must be refused instead)
+            if opt == 0 and not c["policy"] and R * F * n <= 60_000_000:
+                fits = min(R, F) * max(c["match"], 0) + 1 <= 32000
+                try:
+                    got = eng.score_placed_device(0, d_reads, d_refs, stream=stream)
+                except hipkernel.HipKernelError:
+                    if fits:
+                        raise
+                    got = None
+                if got is not None:
+                    if stream is not None:
+                        stream.synchronize()
+                    if not fits:
+                        return "score_placed_device ran where the cells can leave int16"
+                    PLACED_CASES[0] += 1
+                    pexp = placed_ref.placed(reads, refs, osc, affine=c["affine"])
+                    if not np.array_equal(got.cpu().numpy().astype(np.int64), pexp):
+                        return "score_placed_device differs (%s)" % eng.describe(0, n)["ran_placed"]
+                    if c["host"]:
+                        h = eng.score_placed_host(0, reads, refs, threads=c["threads"])
+                        if not np.array_equal(np.stack([h["score"], h["read_end"], h["ref_end"]], axis=1).astype(np.int64), pexp):
+                            return "score_placed_host differs"
         if R * F * n <= 30_000_000:
             akw = dict(affine=True) if c["affine"] else dict(policy="sse" if c["policy"] else "default")
             for opt in (0, 1):
@@ -166,7 +191,8 @@ def main():
             if done % 25 == 0:
                 print("%d cases, %.0f s" % (done, time.time() - t0), flush=True)
         i += 1
-    print("ok: %d cases in %.0f s (seed %d), %d of them with the banded NW variant" % (done, time.time() - t0, a.seed, NW_BAND_CASES[0]))
+    print("ok: %d cases in %.0f s (seed %d), %d of them with the banded NW variant, %d with placed scores" %
+          (done, time.time() - t0, a.seed, NW_BAND_CASES[0], PLACED_CASES[0]))
     return 0
 
 

@@ -36,7 +36,13 @@ g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/long_plan_check.cpp" -o "$OU
 "$OUT/long_plan_asan"
 echo "== the band_nw rules of cell_rules.h under AddressSanitizer + UBSan"
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/band_nw_rules_check.cpp" -o "$OUT/band_nw_rules_asan"
+echo "== placed_choice of cell_rules.h under AddressSanitizer + UBSan"
+g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/placed_rules_check.cpp" -o "$OUT/placed_rules_asan"
+"$OUT/placed_rules_asan"
 "$OUT/band_nw_rules_asan"
+echo "== placed_choice of cell_rules.h under AddressSanitizer + UBSan"
+g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/placed_rules_check.cpp" -o "$OUT/placed_rules_asan"
+"$OUT/placed_rules_asan"
 
 echo "== libvalignhost.so, valign-bench, libcpuref.so with $SAN"
 g++ -std=c++14 $SAN -fPIC -shared -Wall -pthread -I"$R/include" "$CS/valign_host.cpp" -o "$OUT/libvalignhost.so" -ldl

@@ -181,6 +181,67 @@ inline FillChoice fill_choice(const RuleInputs &in, int alg, int G, int K) {
     return c;
 }
 
+// ---- placed scores (valign_hip_score_placed_*): the Smith-Waterman score and its end cell from the score sweep alone ----
+// Bits of the lane key below the value: enough for the K rows of a lane.  The key form exists for K <= 16.
+constexpr int placed_key_bits(int K) { return K <= 4 ? 2 : (K <= 8 ? 3 : 4); }
+constexpr int kPlacedKeyMaxK = 16;
+// Reads of more rows than this take the row strips, as alignments do (Engine::route_facts)
+constexpr int kPlacedStripRows = 1024;
+
+enum class PlacedRoute { Refused, Key, Rows, Strip };
+
+// What the rule reads of the engine beyond the rule inputs (Engine::placed_facts)
+struct PlacedFacts {
+    int band_width = 0;
+    int score_width = 0;            // the score_width key: 0, 16 or 32
+    bool forced = false;            // a forced geometry stays on the register path whatever the read length
+    bool long_plan = false;         // no register geometry holds the shape (the alignment plan is the long-read one)
+};
+
+struct PlacedChoice {
+    PlacedRoute route = PlacedRoute::Refused;
+    int key_bits = 0;               // Key: the bits of the row below the value
+    const char *reason = "";        // Refused: why
+};
+
+// `G x K`: the register geometry the call would run on (ignored where the read takes the strips).  Key: one
+// `value << key_bits | (2^key_bits - 1 - row)` per lane, where the largest possible value keeps it inside int16 (the bound of
+// lane_key_ok, with this form's bits); Rows: a first-arg-max per row -- more than 16 rows per lane, or larger scores.
+inline PlacedChoice placed_choice(const RuleInputs &in, int alg, const PlacedFacts &f, int G, int K) {
+    PlacedChoice c;
+    (void)G;
+    if (alg != kAlgSW)
+        c.reason = "placed scores exist for Smith-Waterman only (the NW variant's score and its alignment's end cell are different cells)";
+    else if (f.band_width > 0)
+        c.reason = "placed scores are not built for band_width > 0";
+    else if (in.sse_policy)
+        c.reason = "placed scores are not built for traceback_policy = 1 (SSE/AVX tie-breaks)";
+    else if (f.score_width == 32)
+        c.reason = "placed scores are not built for score_width = 32 (int32 cells)";
+    else if (!int16_range_ok(in, kAlgSW, true, false, 0))
+        c.reason = "placed scores run on int16 cells: shape x scoring can leave their range";
+    if (c.reason[0]) return c;
+    if (f.long_plan || (!f.forced && in.R > kPlacedStripRows)) {
+        c.route = PlacedRoute::Strip;
+        return c;
+    }
+    const int bits = placed_key_bits(K);
+    const long long top = (long long)std::min(in.R, in.F) * std::max(in.sc.match, 0);
+    if (K <= kPlacedKeyMaxK && ((top + 1) << bits) <= 32000) {
+        c.route = PlacedRoute::Key;
+        c.key_bits = bits;
+    } else {
+        c.route = PlacedRoute::Rows;
+    }
+    return c;
+}
+
+// describe()'s name of what the last placed call ran (ran_placed)
+inline const char *ran_placed_name(PlacedRoute r) {
+    static const char *const names[] = {"none", "key", "rows", "strip"};
+    return names[(int)r];
+}
+
 // ---- band_nw = 1: the NW variant under the block band (include/valign_hip.h) ----
 // Consecutive blocks' windows connect -- every in-band cell has a present candidate -- once 2 * (band_width / 2) + 1 columns
 // cover the most a window start advances per row, ceil(F / R).  Narrower bands are refused.

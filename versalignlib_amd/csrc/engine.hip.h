@@ -9,6 +9,7 @@
 //   long_plan.h ......... the route of a long-read score call, its compiled instances, strip sizes and the chain's plan (pure, CPU-tested)
 //   engine_align.hip .... compute_alignments: fill + traceback launches, row strips, the fused small-batch launch, the
 //                         host-pointer pipeline with its copy-issuing thread (reference: DefaultKernel.cpp:21-50, 204-525)
+//   engine_placed.hip ... placed Smith-Waterman scores: score + end cell from the score sweep (placed_kernels.hip.h)
 //   engine_cigar.hip .... the compact result format: records + CIGAR ops encoded on the device behind the walks (cigar_kernels.hip.h)
 //   hip_plugin.hip ...... the plugin ABI and the flat C API over it
 // The closest reference precedent for the staging loops is the OpenCL backend's gather / copy / launch / collect loop
@@ -66,6 +67,7 @@ struct Geometry {
     const void *kernel[2][7];      // score kernels [alg][linear, symmetric linear, affine, symmetric affine,
                                    //                     symmetric affine / affine / symmetric linear on half floats]
     const void *fill[2][kFillKernels];      // alignment fill kernels [alg][FillKernel]; nullptr: not compiled for this geometry
+    const void *(*placed)(int track, int gaps);      // placed-score kernels (placed_kernels.hip.h); returns nullptr where none is compiled
 };
 
 template <int G, int K>
@@ -93,14 +95,14 @@ constexpr void set_fast_kernels(Geometry &g) {
 
 template <int G, int K>
 constexpr Geometry fast_geometry() {
-    Geometry g{G, K, false, &wave_lds<G, K>, {}, {}};
+    Geometry g{G, K, false, &wave_lds<G, K>, {}, {}, &placed_kernel<G, K, false>};
     set_fast_kernels<G, K>(g);
     return g;
 }
 
 template <int G, int K>
 constexpr Geometry full_geometry() {
-    Geometry g{G, K, true, &wave_lds<G, K>, {}, {}};
+    Geometry g{G, K, true, &wave_lds<G, K>, {}, {}, &placed_kernel<G, K, true>};
     set_fast_kernels<G, K>(g);
     g.fill[0][kFillLinear] = (const void *)&align_fill_kernel<G, K, kAlgSW, false>;
     g.fill[0][kFillLinearSym] = (const void *)&align_fill_kernel<G, K, kAlgSW, true>;
@@ -436,6 +438,19 @@ public:
     bool align_cigar_host(int opt, int n, const char *const *reads, const char *const *refs, int extended, CigarRec *recs,
                           unsigned *ops, long long ops_cap, long long *offsets, long long *ops_needed, int threads);
 
+    // ---- placed Smith-Waterman scores (valign_hip.h: valign_hip_placed; engine_placed.hip) ----
+    // Score and end cell of every pair, no traceback: the register sweep with end-cell tracking (placed_kernels.hip.h) or, for
+    // reads that take the row strips, the pointer-free forward pass of the checkpointed traceback.  placed_choice
+    // (cell_rules.h) decides; what it refuses is thrown.  Device-resident: asynchronous on `stream`, writes d_placed only (the
+    // strips keep two boundary row sets and the end cells in an engine-owned scratch between their launches).
+    void score_placed_device(int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, PlacedRec *d_placed, hipStream_t stream);
+    void score_placed_host(int opt, int n, const char *const *reads, const char *const *refs, PlacedRec *placed, int threads);
+    PlacedFacts placed_facts() const;
+    const LaunchPlan &placed_plan_for(int alg, PlacedChoice &choice, int &gaps);
+    void score_placed_strips(long long n, const uint8_t *d_reads, const uint8_t *d_refs, PlacedRec *d_placed, hipStream_t stream);
+    void launch_placed_records(const EndCell *d_ends, PlacedRec *d_placed, long long n, hipStream_t stream);
+    const char *ran_placed() const { return ran_placed_; }
+
     // host-side phases of the last score_host / align_host call
     std::string host_phases() const;
 
@@ -552,6 +567,7 @@ private:
     }
 
     void ensure_staging(long long pairs);
+    void ensure_placed_staging(long long pairs);
 
     // ---- length-sorted batching (score_host, Smith-Waterman) ----
 
@@ -667,7 +683,7 @@ private:
     LaunchPlan align_resident_;         // what choose_plan picked before the score path's preferences for the long-read kernels
     LaunchPlan fallback_plan_;          // alignments that need a kernel only the full geometries carry (align_plan_for)
     long long slot_begin_[kSlots] = {}, slot_pending_[kSlots] = {};
-    long long staged_pairs_ = 0, align_staged_pairs_ = 0;
+    long long staged_pairs_ = 0, align_staged_pairs_ = 0, placed_staged_pairs_ = 0;
     bool pack_ = true;                                                   // host_packing: 4-bit base classes across PCIe
     BandPlan band_plan_;               // the block chain's plan for band_width_ (set_band_width)
     int band_tables_width_ = -1;       // ... and the band_width whose tables are on the device
@@ -679,6 +695,7 @@ private:
     static constexpr unsigned kRanF16 = 1, kRanInt16 = 2, kRanInt32 = 4;
     unsigned ran_score_cells_ = 0;
     const char *ran_align_fill_ = "none";
+    const char *ran_placed_ = "none";                    // what the last placed-score call ran: key / rows / strip (describe)
     const char *ran_result_format_ = "rows";             // of the last alignment call: rows / cigar (describe)
     long long cigar_d2h_bytes_ = 0;                      // what the last align_cigar_host call copied back
     const CigarSink *cigar_ = nullptr;
@@ -722,6 +739,12 @@ private:
     PinnedBuffer<long long> h_cig_total_;
     DeviceBuffer<int> d_min_start_;                              // per slot: first column of the chunk's rows that holds a string
     PinnedBuffer<int> h_min_start_;                              // ... on its way to the host
+    // placed scores: record staging of the host path; the strips' boundary rows, end cells and (unread) first-invalid table
+    PinnedBuffer<PlacedRec> h_placed_[kSlots];
+    DeviceBuffer<PlacedRec> d_placed_[kSlots];
+    DeviceBuffer<unsigned> d_placed_rows_;
+    DeviceBuffer<EndCell> d_placed_ends_;
+    DeviceBuffer<int> d_placed_bad_;
     DeviceBuffer<unsigned> d_brow_;                              // long-read path: strip boundary rows
     DeviceBuffer<BandBlock> d_band_blocks_;                      // the block chain's tables (band_plan_)
     DeviceBuffer<int> d_band_fill_;

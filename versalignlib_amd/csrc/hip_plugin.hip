@@ -599,6 +599,29 @@ VALIGN_EXPORT int valign_hip_align_cigar_host(valign_hip_engine *e, int opt, int
     return rc;
 }
 
+static_assert(sizeof(valign_hip_placed) == sizeof(valign::PlacedRec) && sizeof(valign_hip_placed) == 12, "valign_hip_placed is the kernels' record");
+
+VALIGN_EXPORT int valign_hip_score_placed_device(valign_hip_engine *e, int opt, long long n, const void *d_reads, const void *d_refs,
+                                                 void *d_placed, void *hip_stream) {
+    if (!e) {
+        g_last_error = "null engine";
+        return 1;
+    }
+    return flat_guard([&] {
+        e->impl->score_placed_device(opt, n, (const uint8_t *)d_reads, (const uint8_t *)d_refs, (valign::PlacedRec *)d_placed,
+                                     (hipStream_t)hip_stream);
+    });
+}
+
+VALIGN_EXPORT int valign_hip_score_placed_host(valign_hip_engine *e, int opt, int n, const char *const *reads, const char *const *refs,
+                                               valign_hip_placed *placed, int threads) {
+    if (!e) {
+        g_last_error = "null engine";
+        return 1;
+    }
+    return flat_guard([&] { e->impl->score_placed_host(opt, n, reads, refs, (valign::PlacedRec *)placed, threads); });
+}
+
 VALIGN_EXPORT int valign_hip_describe(valign_hip_engine *e, int opt, long long n, char *buf, int cap) {
     if (!e || !buf || cap <= 0) return 1;
     const std::string s = e->impl->describe(opt, n);

@@ -13,10 +13,14 @@
 //     alignments with different scores per direction -- exists for SIX geometries only, one per row capacity (64, 160,
 //     320, 512, 1024, 2048); a call that needs one of them on another geometry is re-planned onto the next full one
 //     (Engine::align_plan_for): same results, a sweep a few per cent longer.
+// Placed scores (placed_kernels.hip.h) add 68 instances, listed by placed_kernel<G, K, FULL> there: the symmetric gap forms with
+// the lane key on the 15 geometries of up to 16 rows per lane, the asymmetric ones on the five full geometries among them, and
+// the four per-row forms on the six full geometries and 64 x 24.  VALIGN_PLACED_KERNELS instantiates a geometry's table.
 #pragma once
 
 #include "dp_kernels.hip.h"
 #include "trace_kernels.hip.h"
+#include "placed_kernels.hip.h"
 
 // X(G, K): geometries with every kernel;  Y(G, K): geometries with the fast set only.  Parts are balanced by rows per
 // lane (compile time grows with K).
@@ -70,3 +74,6 @@
     PREFIX __global__ void align_fill_tag_kernel<G, K, kAlgNW, false, true>(const FillArgs);         \
     PREFIX __global__ void align_fill_affine_tag_kernel<G, K, kAlgSW, false>(const FillArgs);        \
     PREFIX __global__ void align_fill_affine_tag_kernel<G, K, kAlgNW, false>(const FillArgs);
+
+// The placed-score kernels of a geometry: defined where its table is (FULL: the geometry is a full one)
+#define VALIGN_PLACED_KERNELS(PREFIX, G, K, FULL) PREFIX const void *placed_kernel<G, K, FULL>(int, int);
