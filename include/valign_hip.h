@@ -332,15 +332,42 @@ int valign_hip_align_cigar_host(valign_hip_engine *e, int opt, int n, const char
  * nothing, as everywhere.  NOT BUILT HERE -- each is refused with a non-zero return and a message in valign_hip_last_error:
  *   opt & 0xF == 1 ........ the NW variant's score (the maximum over the last row AND the last column) and its alignment's end
  *                           cell (the arg-max of one row) are different cells in the reference: "placed" has no single meaning
- *   band_width > 0 ........ banded scores
+ *   band_width > 0 ........ banded scores -- unless valign_hip_set_band_placed(e, 1) asks for them, below
  *   traceback_policy = 1 .. the SSE/AVX tie-breaks
  *   score_width = 32, or a shape x scoring whose Smith-Waterman cells could leave int16 (the rule of the score path)
  * "ran_placed" of valign_hip_describe says what the last call ran: "key" (register sweep, one end-cell key per lane), "rows"
  * (register sweep, a first-arg-max per row: more than 16 rows per lane, or scores too large for the key), "strip" (reads of
- * more than 1 024 rows or shapes no register geometry holds: the row strips' pointer-free forward pass), "none".          */
+ * more than 1 024 rows or shapes no register geometry holds: the row strips' pointer-free forward pass), "chain" (band_placed,
+ * below), "none".                                                                                                            */
 typedef struct {                     /* 12 bytes */
     int32_t score, read_end, ref_end;
 } valign_hip_placed;
+
+/* Placed scores under the band (key band_placed; flat API only).  0 (default): placed scores are refused with band_width > 0, as
+ * ever.  1: with band_width > 0 valign_hip_score_placed_device / _host run the banded score sweep of the block chain with
+ * end-cell tracking ("ran_placed": "chain") -- what a banded mapper asks: the banded score and where it ends, at a few tens of
+ * percent over the sweep instead of a banded alignment.  With band_width == 0 the key is not read: the unbanded routes run as
+ * before.  DEFINITION:
+ *   band ........ the chain's block band, exactly as valign_hip_score_device computes it: row i has the inclusive column
+ *                 window of its block on (B, A) = (16, 1), which valign_hip_describe reports after valign_hip_set_band_width
+ *                 ("band_block_rows", "band_col_align"); every cell outside its row's window holds 0.
+ *   score ....... the banded Smith-Waterman score of the pair as int32: valign_hip_score_device's value wherever that is
+ *                 below 32767, where the short saturates -- the record does not.
+ *   read_end, ref_end
+ *                 (read_end - 1, ref_end - 1) is the first IN-BAND cell in row-major order that holds the maximum: the
+ *                 earliest read row and, within it, the earliest reference column -- the rule of
+ *                 src/Kernels/default/DefaultKernel.cpp:252-256 restricted to in-band cells.  0-based, half-open.
+ *   empty ....... a pair whose banded maximum is 0 returns {0, 0, 0}.
+ *   wide bands .. a band of at least 2 * max(R, F) gives exactly the unbanded placed records (where the chain plans a band
+ *                 that wide: its rings must fit, below).
+ *   read length . the route is the chain whatever the read length (banded scores already go there for short reads).
+ * The chain runs on int32 cells whatever score_width says: score_width and the int16 range rule are not read on this route.
+ * REFUSED under band_placed = 1 with a band: opt & 0xF == 1 and traceback_policy = 1, as above; a (shape, band, scoring) for
+ * which the chain has no usable plan -- there is no fall-back to the row strips: their band is the (160, 4) one, a different
+ * definition --; scores so large that the int32 cells ((R + F + 2) x |score| >= 2^28) or the end-cell key
+ * ((min(R, F) x match + 1) << 4 beyond int32) could overflow.  tests/placed_band_ref.py restates the definition in numpy.
+ * Other values than 0 / 1 are refused.                                                                                      */
+int valign_hip_set_band_placed(valign_hip_engine *e, int on);
 
 /* Device-resident: d_placed = n records.  Asynchronous on hip_stream, uses no pointer scratch and writes nothing but d_placed
  * (the strip path keeps its boundary rows and end cells in an engine-owned scratch: calls of one engine that take it belong
@@ -380,7 +407,8 @@ int valign_hip_set_half_float_cells(valign_hip_engine *e, int mode);
  * of the last alignment call, "align_scratch_bytes" the pointer scratch the engine holds after it.
  * "ran_result_format" is "rows" or "cigar" for the last alignment call, "cigar_d2h_bytes" what the last
  * valign_hip_align_cigar_host call copied back, "cigar_rows_scratch_bytes" the rows scratch of the compact format.
- * "ran_placed" is what the last placed-score call ran: key / rows / strip ("none" before any, or when it was refused).    */
+ * "ran_placed" is what the last placed-score call ran: key / rows / strip / chain ("none" before any, or when it was
+ * refused); "band_placed" is the key of valign_hip_set_band_placed.                                                           */
 int valign_hip_describe(valign_hip_engine *e, int opt, long long n, char *buf, int cap);
 
 const char *valign_hip_last_error(void);

@@ -2,7 +2,8 @@
 """Randomised sweep of the flat device / host API (developer tool; run on the GPU box): hipkernel.Engine objects created and
 destroyed by the hundred, score_device / align_device on torch tensors and random streams, score_host / align_host on numpy
 arrays (with and without a registered destination), length-sorted batching, bands, pointer-scratch caps -- every result
-against oracle/cpu_ref; placed Smith-Waterman scores (score_placed_device / _host) against tests/placed_ref.py.  What tools/fuzz_parity.py does for the plugin ABI, for the entry points the tests of the device path
+against oracle/cpu_ref; placed Smith-Waterman scores (score_placed_device / _host) against tests/placed_ref.py and, under a band with
+band_placed = 1, against tests/placed_band_ref.py.  What tools/fuzz_parity.py does for the plugin ABI, for the entry points the tests of the device path
 use; a process that runs it for minutes also exercises the library's set-up and tear-down far more often than the suite.
 
     python -X faulthandler tools/fuzz_device.py --seconds 300 --seed 1
@@ -22,11 +23,13 @@ import torch                                                       # noqa: E402
 from oracle import cpu_ref                                          # noqa: E402
 from versalignlib_amd import hipkernel, synth                      # noqa: E402
 import band_nw_ref                                                 # noqa: E402
+import placed_band_ref                                             # noqa: E402
 import placed_ref                                                  # noqa: E402
 
 
 NW_BAND_CASES = [0]             # cases that also ran the NW variant under the band
 PLACED_CASES = [0]              # cases that also ran placed Smith-Waterman scores
+BAND_PLACED_CASES = [0]         # banded cases that also ran placed scores on the chain (band_placed = 1)
 
 
 def draw(rng):
@@ -88,6 +91,27 @@ def run(c):
             exp = cpu_ref.score_banded_sw(reads, refs, c["band"], osc, threads=8, block_rows=d["band_block_rows"], col_align=d["band_col_align"], affine=c["affine"])
             if not np.array_equal(got.cpu().numpy(), exp):
                 return "banded score_device differs"
+            # banded placed scores where the chain runs: refused with the key off, as ever; with band_placed = 1 against the
+            # numpy restatement on the chain's band (tests/placed_band_ref.py: int64 cells, the record does not saturate)
+            if d["band_block_rows"] == 16 and not c["policy"] and R * F * n <= 60_000_000:
+                try:
+                    eng.score_placed_device(0, d_reads, d_refs, stream=stream)
+                    return "score_placed_device ran under a band with band_placed = 0"
+                except hipkernel.HipKernelError as err:
+                    if "band_width" not in str(err):
+                        raise
+                eng.set_band_placed(1)
+                BAND_PLACED_CASES[0] += 1
+                got = eng.score_placed_device(0, d_reads, d_refs, stream=stream)
+                if stream is not None:
+                    stream.synchronize()
+                pexp = placed_band_ref.placed_banded(reads, refs, c["band"], osc, affine=c["affine"])
+                if eng.describe(0, n)["ran_placed"] != "chain" or not np.array_equal(got.cpu().numpy().astype(np.int64), pexp):
+                    return "banded score_placed_device differs (%s)" % eng.describe(0, n)["ran_placed"]
+                if c["host"]:
+                    h = eng.score_placed_host(0, reads, refs, threads=c["threads"])
+                    if not np.array_equal(np.stack([h["score"], h["read_end"], h["ref_end"]], axis=1).astype(np.int64), pexp):
+                        return "banded score_placed_host differs"
             # every other banded case also runs the NW variant under the band (band_nw = 1) against tests/band_nw_ref.py
             # (decided by the seed: no further draw, so the sequence of cases is the one it was)
             if c["seed"] % 2 and not c["policy"] and 2 * (c["band"] // 2) + 1 >= -(-F // R):
@@ -191,8 +215,8 @@ def main():
             if done % 25 == 0:
                 print("%d cases, %.0f s" % (done, time.time() - t0), flush=True)
         i += 1
-    print("ok: %d cases in %.0f s (seed %d), %d of them with the banded NW variant, %d with placed scores" %
-          (done, time.time() - t0, a.seed, NW_BAND_CASES[0], PLACED_CASES[0]))
+    print("ok: %d cases in %.0f s (seed %d), %d of them with the banded NW variant, %d with placed scores, %d with banded placed scores" %
+          (done, time.time() - t0, a.seed, NW_BAND_CASES[0], PLACED_CASES[0], BAND_PLACED_CASES[0]))
     return 0
 
 

@@ -33,6 +33,7 @@
 
 #include "dp_kernels.hip.h"
 #include "long_plan.h"
+#include "placed_kernels.hip.h"
 
 namespace valign {
 
@@ -42,7 +43,10 @@ static_assert(kPlanWave == kWave, "long_plan.h sizes the rings for this wave");
 struct BandArgs {
     const uint8_t *reads;
     const uint8_t *refs;
-    int16_t *scores;
+    union {
+        int16_t *scores;        // n shorts
+        PlacedRec *placed;      // PLACED instantiations: n records instead (one slot: the argument layout is the same for all)
+    };
     const BandBlock *blocks;    // nb + kBandG + 2 entries (the tail: empty blocks)
     const int *fill_to;         // per event: the reference ring must hold every column below this one
     long long n;
@@ -91,9 +95,22 @@ static_assert(((band_class_table() >> (3 * ('A' - 'A'))) & 7) == 0 && ((band_cla
 // replaced by 0 -- and the first block's row above is the border row, 0 at every column.  No running maximum: the result is
 // the best of the last row (the last block's last row, every step) and of the last column (the cells of every block whose
 // window ends at column F - 1, at that step), floored at 0.
-template <int K, bool SYM, bool UNIT, bool AFFINE = false, bool NW = false>
+//
+// PLACED (band_placed = 1, Smith-Waterman only): the score AND the first in-band cell in row-major order that holds it
+// (include/valign_hip.h), a PlacedRec per pair instead of the short.  A cell is the first to hold the maximum only through its
+// diagonal candidate -- a gap candidate is at most an earlier cell's value -- so the candidates the bare maximum folds are the
+// ones to track: per cell `d_cur << 4 | (15 - q)` (q: the row of the lane's block) goes into the same tree of three-operand
+// maxima, per step one compare and one select remember the step at which the lane's key last grew (a greater value, or the
+// same value in an earlier row of the block: within a block the columns only grow, so the first step wins a tie of one row).
+// The event that starts a lane's next block -- 512 rows further down: it may only win with a strictly greater value -- turns
+// the lane's record into (row, column) and fills the key's row bits.  Behind the sweep five __shfl_xor rounds reduce the
+// group's records on (value descending, row ascending, column ascending).  No LDS operation is added: the counts of the two
+// hand-written wait blocks stand.  Range: (min(R, F) * match + 1) << 4 inside int32 (band_placed_key_ok, cell_rules.h).
+template <int K, bool SYM, bool UNIT, bool AFFINE = false, bool NW = false, bool PLACED = false>
 __global__ void __launch_bounds__(64)
 score_band_kernel(const BandArgs args) {
+    static_assert(!(PLACED && NW), "placed scores exist for Smith-Waterman only");
+    static_assert(!PLACED || K == (1 << kBandPlacedKeyBits), "the key's row bits hold the rows of a block");
     constexpr int kOut = NW ? kBandNwAbsent32 : 0;            // what the band gives a cell outside its window
     auto gsub = [](int v, unsigned mag) __attribute__((always_inline)) -> int {
         return NW ? v - (int)mag : (int)__builtin_elementwise_sub_sat((unsigned)v, mag);
@@ -173,6 +190,21 @@ score_band_kernel(const BandArgs args) {
     unsigned ca = codes_lds;
     unsigned rd4 = 0;                      // 256 * (t + 1 - delay): the predecessor's slot of the column this lane reaches NEXT step
     unsigned t4 = 0;                       // 256 * t
+    // PLACED: the lane's key and the step it last grew at; the lane's current block -- the step of its event, its first row,
+    // its column minus the step --; the record of the lane's finished blocks
+    int lane_key = (1 << kBandPlacedKeyBits) - 1, rec_t = -1;
+    int blk_t = 0, blk_row = 0, blk_col = 0;
+    int rec_row = 0x7FFFFFFF, rec_col = 0;
+    auto key_of = [](int v, int q) __attribute__((always_inline)) -> int {
+        return (int)(((unsigned)v << kBandPlacedKeyBits) | (unsigned)(K - 1 - q));
+    };
+    // a record made in the lane's current block, as (row, column)
+    auto settle = [&]() __attribute__((always_inline)) {
+        if (rec_t >= blk_t) {
+            rec_row = blk_row + (K - 1) - (lane_key & (K - 1));
+            rec_col = blk_col + rec_t;
+        }
+    };
 
     // ---- what the events prefetch ----
     // Read bases of the NEXT block's rows: this lane rewrites the profile entry (row my_q, class my_c) of group 0 and
@@ -249,8 +281,9 @@ score_band_kernel(const BandArgs args) {
     };
 
     // one step: every lane moves one column on.  `S` holds this step's scores, the loads of the next step's go to Snext.
-    auto step = [&](u32x4 (&S)[K / 8], u32x4 (&Snext)[K / 8]) __attribute__((always_inline)) {
+    auto step = [&](u32x4 (&S)[K / 8], u32x4 (&Snext)[K / 8], const int t) __attribute__((always_inline)) {
         const int diag0 = up0;
+        const int key_in = lane_key;
         int fup_cur = 0;
         if (!(UNIT && K == 16)) {
             up0 = up_in;                                                 // the cell above this block's first row
@@ -290,6 +323,7 @@ score_band_kernel(const BandArgs args) {
                 int f = fup_cur;
                 int ho = gsub(up0, omag_ref);          // H - open of the row above
                 int d_cur = diag0 + score_of(S, 0), d_prev = 0, h = 0;
+                [[maybe_unused]] int k_prev = 0;
 #pragma unroll
                 for (int q = 0; q < K; ++q) {
                     int d_next = 0;
@@ -306,6 +340,15 @@ score_band_kernel(const BandArgs args) {
                     ho = gsub(m, omag_ref);
                     if (SYM) put_hg(q, m, ho); else put_h(q, m);
                     if constexpr (NW) {
+                    } else if constexpr (PLACED) {
+                        const int k_cur = key_of(d_cur, q);
+                        if (q & 1) {
+                            int b2 = lane_key > k_prev ? lane_key : k_prev;
+                            lane_key = b2 > k_cur ? b2 : k_cur;
+                        } else if (q == K - 1) {
+                            lane_key = lane_key > k_cur ? lane_key : k_cur;
+                        }
+                        k_prev = k_cur;
                     } else if (q & 1) {
                         int b2 = best > d_prev ? best : d_prev;
                         best = b2 > d_cur ? b2 : d_cur;
@@ -317,6 +360,7 @@ score_band_kernel(const BandArgs args) {
                 }
                 h_out = h;
                 f_out = f;
+                if constexpr (PLACED) rec_t = lane_key != key_in ? t : rec_t;
                 if constexpr (NW) {
                     if (last_blk) best = best > h ? best : h;
                     if (to_end && u == span) {
@@ -329,6 +373,7 @@ score_band_kernel(const BandArgs args) {
             int h = up0;
             int up_c = gsub(up0, gmag_ref);
             int d_cur = diag0 + score_of(S, 0), d_prev = 0;
+            [[maybe_unused]] int k_prev = 0;
 #pragma unroll
             for (int q = 0; q < K; ++q) {
                 int d_next = 0;
@@ -341,6 +386,15 @@ score_band_kernel(const BandArgs args) {
                 up_c = gsub(m, gmag_ref);
                 if (SYM) put_hg(q, m, up_c); else put_h(q, m);
                 if constexpr (NW) {
+                } else if constexpr (PLACED) {
+                    const int k_cur = key_of(d_cur, q);
+                    if (q & 1) {
+                        int b2 = lane_key > k_prev ? lane_key : k_prev;
+                        lane_key = b2 > k_cur ? b2 : k_cur;
+                    } else if (q == K - 1) {
+                        lane_key = lane_key > k_cur ? lane_key : k_cur;
+                    }
+                    k_prev = k_cur;
                 } else if (q & 1) {
                     int b2 = best > d_prev ? best : d_prev;
                     best = b2 > d_cur ? b2 : d_cur;
@@ -351,6 +405,7 @@ score_band_kernel(const BandArgs args) {
                 d_cur = d_next;
             }
             h_out = h;
+            if constexpr (PLACED) rec_t = lane_key != key_in ? t : rec_t;
             if constexpr (NW) {
                 if (last_blk) best = best > h ? best : h;
                 if (to_end && u == span) {
@@ -397,7 +452,7 @@ score_band_kernel(const BandArgs args) {
     // The switching lane's first step is its warm-up column (inactive: the scores in flight for it may be anything);
     // what must be right is the slab of the step after, read here.  Nobody else's pipeline is touched.
     int b = b0;
-    auto event = [&]() __attribute__((always_inline)) {
+    auto event = [&](const int t) __attribute__((always_inline)) {
         const int ls = b % kBandG;
         const BandBlock blk = args.blocks[b];                             // (uniform: scalar loads)
         commit_codes(pre_first, pre_limit, pre_ref0, pre_ref1);           // (first: the new block's columns may be among them)
@@ -410,6 +465,13 @@ score_band_kernel(const BandArgs args) {
 #pragma unroll
             for (int q = 0; q < (AFFINE ? K : 1); ++q) El[q] = kOut;
             up0 = kOut;
+            if constexpr (PLACED) {
+                settle();
+                lane_key |= (1 << kBandPlacedKeyBits) - 1;
+                blk_t = t;
+                blk_row = b * K - args.pad_rows;
+                blk_col = blk.start - t;
+            }
             if constexpr (NW) {
                 first_blk = b == args.first_block;
                 lo0 = blk.lo == 0;
@@ -450,15 +512,34 @@ score_band_kernel(const BandArgs args) {
     int next_event = 0;
     for (int t = 0; t < total_steps; t += 2) {
         if (t == next_event) {
-            event();
+            event(t);
             next_event += d;
         }
-        step(S0, S1);
+        step(S0, S1, t);
         if (t + 1 == next_event) {
-            event();
+            event(t + 1);
             next_event += d;
         }
-        step(S1, S0);
+        step(S1, S0, t + 1);
+    }
+
+    if constexpr (PLACED) {
+        settle();
+        int val = lane_key >> kBandPlacedKeyBits, row = rec_row, col = rec_col;       // (no record: 0 in row 2^31 - 1)
+#pragma unroll
+        for (int dd = kBandG / 2; dd >= 1; dd >>= 1) {
+            const int oval = __shfl_xor(val, dd, kWave), orow = __shfl_xor(row, dd, kWave), ocol = __shfl_xor(col, dd, kWave);
+            const bool take = oval > val || (oval == val && (orow < row || (orow == row && ocol < col)));
+            val = take ? oval : val;
+            row = take ? orow : row;
+            col = take ? ocol : col;
+        }
+        if (l == 0) {
+            const long long pa = pair0 + 2 * grp + half;
+            const bool hit = val > 0;
+            if (pa < args.n) args.placed[pa] = PlacedRec{hit ? val : 0, hit ? row + 1 : 0, hit ? col + 1 : 0};
+        }
+        continue;
     }
 
     int res = best;

@@ -188,7 +188,17 @@ constexpr int kPlacedKeyMaxK = 16;
 // Reads of more rows than this take the row strips, as alignments do (Engine::route_facts)
 constexpr int kPlacedStripRows = 1024;
 
-enum class PlacedRoute { Refused, Key, Rows, Strip };
+enum class PlacedRoute { Refused, Key, Rows, Strip, Chain };
+
+// band_placed = 1 under a band: the banded block chain (band_kernels.hip.h) tracks one key per lane on its int32 cells,
+// `diagonal candidate << kBandPlacedKeyBits | (15 - row of the lane's 16-row block)`, compared as signed integers: the largest
+// possible value plus one, shifted, must stay inside int32.  (int32_refused is the tighter bound wherever both apply -- (R + F +
+// 2) / 2 > min(R, F) -- so placed_choice never refuses through this rule today: it becomes live only if int32_refused is relaxed
+// or the key takes more bits, and is kept, and tested at its own edge, so that either change meets it.)
+constexpr int kBandPlacedKeyBits = 4;
+inline bool band_placed_key_ok(const RuleInputs &in) {
+    return (((long long)std::min(in.R, in.F) * std::max(in.sc.match, 0) + 1) << kBandPlacedKeyBits) <= 0x7FFFFFFFll;
+}
 
 // What the rule reads of the engine beyond the rule inputs (Engine::placed_facts)
 struct PlacedFacts {
@@ -196,6 +206,8 @@ struct PlacedFacts {
     int score_width = 0;            // the score_width key: 0, 16 or 32
     bool forced = false;            // a forced geometry stays on the register path whatever the read length
     bool long_plan = false;         // no register geometry holds the shape (the alignment plan is the long-read one)
+    bool band_placed = false;       // band_placed = 1: under a band the call runs on the block chain, on the chain's band
+    bool chain_usable = false;      // band_chain_plan(...).usable for this band_width (long_plan.h)
 };
 
 struct PlacedChoice {
@@ -204,19 +216,36 @@ struct PlacedChoice {
     const char *reason = "";        // Refused: why
 };
 
-// `G x K`: the register geometry the call would run on (ignored where the read takes the strips).  Key: one
+// `G x K`: the register geometry the call would run on (ignored where the read takes the strips or the chain).  Key: one
 // `value << key_bits | (2^key_bits - 1 - row)` per lane, where the largest possible value keeps it inside int16 (the bound of
-// lane_key_ok, with this form's bits); Rows: a first-arg-max per row -- more than 16 rows per lane, or larger scores.
+// lane_key_ok, with this form's bits); Rows: a first-arg-max per row -- more than 16 rows per lane, or larger scores.  Chain:
+// the banded block chain under band_placed = 1 (above), whatever the read length -- refused where the chain has no plan,
+// never sent to the strips.
 inline PlacedChoice placed_choice(const RuleInputs &in, int alg, const PlacedFacts &f, int G, int K) {
     PlacedChoice c;
     (void)G;
     if (alg != kAlgSW)
         c.reason = "placed scores exist for Smith-Waterman only (the NW variant's score and its alignment's end cell are different cells)";
-    else if (f.band_width > 0)
+    else if (f.band_width > 0 && !f.band_placed)
         c.reason = "placed scores are not built for band_width > 0";
     else if (in.sse_policy)
         c.reason = "placed scores are not built for traceback_policy = 1 (SSE/AVX tie-breaks)";
-    else if (f.score_width == 32)
+    else if (f.band_width > 0) {
+        // band_placed = 1: the chain or nothing -- the strips' band is the (160, 4) one, a different definition.  int32 cells
+        // whatever score_width says, as for banded scores: neither score_width nor the int16 range rule is read here.
+        if (!f.chain_usable)
+            c.reason = "band_placed: the block chain has no usable plan for this read_length, ref_length, band_width and scoring (band_chain_plan); "
+                       "placed scores under a band run nowhere else";
+        else if (int32_refused(in))
+            c.reason = "band_placed: shape x scoring can leave the int32 range of the DP cells";
+        else if (!band_placed_key_ok(in))
+            c.reason = "band_placed: min(read_length, ref_length) x match leaves the range of the chain's end-cell key (value << 4 in int32)";
+        else {
+            c.route = PlacedRoute::Chain;
+            c.key_bits = kBandPlacedKeyBits;
+        }
+        return c;
+    } else if (f.score_width == 32)
         c.reason = "placed scores are not built for score_width = 32 (int32 cells)";
     else if (!int16_range_ok(in, kAlgSW, true, false, 0))
         c.reason = "placed scores run on int16 cells: shape x scoring can leave their range";
@@ -238,7 +267,7 @@ inline PlacedChoice placed_choice(const RuleInputs &in, int alg, const PlacedFac
 
 // describe()'s name of what the last placed call ran (ran_placed)
 inline const char *ran_placed_name(PlacedRoute r) {
-    static const char *const names[] = {"none", "key", "rows", "strip"};
+    static const char *const names[] = {"none", "key", "rows", "strip", "chain"};
     return names[(int)r];
 }
 

@@ -236,6 +236,14 @@ public:
         band_nw_ = on == 1;
     }
     int band_nw() const { return band_nw_ ? 1 : 0; }
+    // Placed scores under the band (opt-in; include/valign_hip.h has the definition): 1 = with band_width > 0
+    // valign_hip_score_placed_* run on the block chain and return the banded score and its first in-band end cell; 0 = placed
+    // scores are refused under a band (default).  Not read without a band.
+    void set_band_placed(int on) {
+        if (on != 0 && on != 1) throw std::runtime_error("band_placed must be 0 or 1");
+        band_placed_ = on == 1;
+    }
+    int band_placed() const { return band_placed_ ? 1 : 0; }
     // Checkpointed traceback of long-read alignments (opt-in; ckpt_plan.h): 1 = calls that take the plain row strips (unbanded,
     // int16 cells, traceback_policy 0; both algorithms, linear and affine gaps) keep one boundary row per strip and ONE strip's
     // pointer region instead of every pointer, and re-fill strip after strip along the walk -- identical results, a scratch that
@@ -319,9 +327,12 @@ public:
     // Row strips of the mode's G * K rows, boundary rows through an HBM scratch -- or, banded, the block chain.
     void score_long_device(int alg, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int16_t *d_scores, hipStream_t stream);
     // Banded scores (SW and, under band_nw, the NW variant; linear and affine gaps) on the cyclic block chain of
-    // band_kernels.hip.h, for a mode whose route is the chain; its tables follow band_width_ (sync_band_tables)
+    // band_kernels.hip.h, for a mode whose route is the chain; its tables follow band_width_ (sync_band_tables).  d_placed:
+    // placed scores under band_placed = 1 (engine_placed.hip) -- the same launch with the kernel's PLACED form, records
+    // instead of d_scores
     void sync_band_tables(hipStream_t stream);
-    void score_band_device(const LongScoreMode &mode, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int16_t *d_scores, hipStream_t stream);
+    void score_band_device(const LongScoreMode &mode, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int16_t *d_scores, PlacedRec *d_placed,
+                           hipStream_t stream);
 
     // The cell format score_alignments is PREDICTED to compute in for this mode: a device-resident call of n pairs (n <= 0:
     // a large call) at the engine's full shape.  What a call really launched is ran_score_cells(): the host pipeline's
@@ -649,6 +660,7 @@ private:
     int band_width_ = 0;
     bool band_alignments_ = false;
     bool band_nw_ = false;
+    bool band_placed_ = false;
     bool trace_checkpoints_ = false;
     int score_width_ = 0;
     int ragged_ = 0, force_g_ = 0, force_k_ = 0;
@@ -695,7 +707,7 @@ private:
     static constexpr unsigned kRanF16 = 1, kRanInt16 = 2, kRanInt32 = 4;
     unsigned ran_score_cells_ = 0;
     const char *ran_align_fill_ = "none";
-    const char *ran_placed_ = "none";                    // what the last placed-score call ran: key / rows / strip (describe)
+    const char *ran_placed_ = "none";                    // what the last placed-score call ran: key / rows / strip / chain (describe)
     const char *ran_result_format_ = "rows";             // of the last alignment call: rows / cigar (describe)
     long long cigar_d2h_bytes_ = 0;                      // what the last align_cigar_host call copied back
     const CigarSink *cigar_ = nullptr;

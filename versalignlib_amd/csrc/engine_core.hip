@@ -108,7 +108,7 @@ std::string Engine::describe(int opt, long long n) const {
              "\"lds_per_wave\": %d, \"lds_per_block\": %d, \"steps\": %d, \"blocks\": %lld, \"long_mode\": %d, "
              "\"band_width\": %d, \"ragged_batching\": %d, \"ragged_launches\": %d, \"ragged_cell_fraction\": %.4f, "
              "\"score_cells\": \"%s\", \"direct_call\": %d, \"packed_classes\": %d, \"direct_out\": %d, \"band_block_rows\": %d, \"band_col_align\": %d, \"band_waves_per_cu\": %d, \"band_lds_per_wave\": %d, \"band_cells_per_pair\": %lld, \"long_strip_rows\": %d, \"d2h_row_mb\": %.1f, \"full_row_mb\": %.1f, \"host_gather_ms\": %.3f, \"host_classify_ms\": %.3f, \"host_wait_ms\": %.3f, \"host_drain_ms\": %.3f, \"ran_score_cells\": \"%s\", \"ran_align_fill\": \"%s\", "
-             "\"band_alignments\": %d, \"band_nw\": %d, \"align_ptr_bytes_per_pair\": %lld, \"trace_checkpoints\": %d, "
+             "\"band_alignments\": %d, \"band_nw\": %d, \"band_placed\": %d, \"align_ptr_bytes_per_pair\": %lld, \"trace_checkpoints\": %d, "
              "\"align_ckpt_bytes_per_pair\": %lld, \"align_scratch_bytes\": %lld, \"ran_result_format\": \"%s\", "
              "\"cigar_d2h_bytes\": %lld, \"cigar_rows_scratch_bytes\": %lld, \"ran_placed\": \"%s\"}",
              arch_.c_str(), device_, opt & 0xF, sc_.affine ? 1 : 0, plan_.geo->G, plan_.geo->K,
@@ -119,7 +119,7 @@ std::string Engine::describe(int opt, long long n) const {
              score_cell_format(opt & 0xF, n), host_stats_.direct, host_stats_.packed, host_stats_.direct_out,
              ((opt & 0xF) == kAlgSW || band_nw_) ? band_rows : VALIGN_HIP_BAND_BLOCK_ROWS, ((opt & 0xF) == kAlgSW || band_nw_) ? band_align : VALIGN_HIP_BAND_COL_ALIGN,
              band_blocks_per_cu_, band_lds_, (band_tables_width_ == band_width_ && band_plan_.usable) ? band_plan_.cells : 0ll, long_strip_rows_, host_stats_.d2h_row_bytes / 1e6, host_stats_.full_row_bytes / 1e6, host_stats_.gather_ms, host_stats_.classify_ms, host_stats_.wait_ms,
-             host_stats_.drain_ms, ran_score_cells().c_str(), ran_align_fill_, band_alignments(), band_nw(), align_ptr_bytes_per_pair_, trace_checkpoints(),
+             host_stats_.drain_ms, ran_score_cells().c_str(), ran_align_fill_, band_alignments(), band_nw(), band_placed(), align_ptr_bytes_per_pair_, trace_checkpoints(),
              align_ckpt_bytes_per_pair_, (long long)d_ptr_.bytes(), ran_result_format_, cigar_d2h_bytes_,
              (long long)(d_cig_rows_[0].bytes() + d_cig_rows_[1].bytes()), ran_placed_);
     return buf;

@@ -47,6 +47,18 @@ const void *band_kernel_in(const LongScoreMode &m, bool unit, std::integer_seque
 }
 static const void *band_kernel(const LongScoreMode &m, bool unit) { return band_kernel_in(m, unit, std::make_integer_sequence<int, 16>()); }
 
+// ... and its PLACED form (band_placed = 1; Smith-Waterman only): [affine][same scores both ways], unit-delay and delay ring
+template <int I>
+const void *band_placed_instance() {
+    return (const void *)&score_band_kernel<kBandK, (I & 2) != 0, (I & 1) != 0, (I & 4) != 0, false, true>;
+}
+template <int... I>
+const void *band_placed_kernel_in(const LongScoreMode &m, bool unit, std::integer_sequence<int, I...>) {
+    static const void *const instances[] = {band_placed_instance<I>()...};
+    return instances[unit | m.sym << 1 | m.affine << 2];
+}
+static const void *band_placed_kernel(const LongScoreMode &m, bool unit) { return band_placed_kernel_in(m, unit, std::make_integer_sequence<int, 8>()); }
+
 // The plan's tables on the device, for the band_width of the call: a width whose plan is not usable holds none
 void Engine::sync_band_tables(hipStream_t stream) {
     const BandPlan &p = band_plan_;
@@ -63,11 +75,14 @@ void Engine::sync_band_tables(hipStream_t stream) {
     band_tables_width_ = band_width_;       // (only once the tables are on the device)
 }
 
-void Engine::score_band_device(const LongScoreMode &mode, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int16_t *d_scores, hipStream_t stream) {
+void Engine::score_band_device(const LongScoreMode &mode, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int16_t *d_scores, PlacedRec *d_placed,
+                               hipStream_t stream) {
     const BandPlan &p = band_plan_;
     BandArgs a{d_reads, d_refs, d_scores, d_band_blocks_.get(), d_band_fill_.get(), n, R_, F_, p.nb, p.first_block, p.pad_rows, p.d, p.ring_depth, p.code_cols};
     put_scoring(a);
-    const void *fn = band_kernel(mode, p.unit_delay);
+    if (d_placed) a.placed = d_placed;
+    if (d_placed && mode.alg != kAlgSW) throw std::runtime_error("no placed-score kernel for this mode");
+    const void *fn = d_placed ? band_placed_kernel(mode, p.unit_delay) : band_kernel(mode, p.unit_delay);
     const int lds = BandLds<kBandK>::total(p.code_cols, p.ring_depth, mode.affine);
     // as many one-wave blocks as run side by side; each takes quads of pairs in turn (band_kernels.hip.h)
     int per_cu = 0;
@@ -86,7 +101,7 @@ void Engine::score_long_device(int alg, long long n, const uint8_t *d_reads, con
     ran_score_cells_ |= mode.cells == LongCells::F16 ? kRanF16 : (mode.cells == LongCells::Int32 ? kRanInt32 : kRanInt16);
     if (band_width_ > 0 && !no_band_chain_) sync_band_tables(stream);
     if (mode.chain) {
-        score_band_device(mode, n, d_reads, d_refs, d_scores, stream);
+        score_band_device(mode, n, d_reads, d_refs, d_scores, nullptr, stream);
         return;
     }
     const LongSizes sz = long_strip_sizes(R_, F_, n, mode);

@@ -9,7 +9,7 @@
 namespace valign {
 
 PlacedFacts Engine::placed_facts() const {
-    return PlacedFacts{band_width_, score_width_, force_g_ != 0 || force_k_ != 0, align_base_plan().long_mode};
+    return PlacedFacts{band_width_, score_width_, force_g_ != 0 || force_k_ != 0, align_base_plan().long_mode, band_placed_, band_plan_.usable && !no_band_chain_};
 }
 
 // The plan a placed call runs on: the one alignments start from where its geometry carries the kernel the rule asks for;
@@ -23,7 +23,7 @@ const LaunchPlan &Engine::placed_plan_for(int alg, PlacedChoice &choice, int &ga
     choice = placed_choice(in, alg, facts, base.geo->G, base.geo->K);
     if (choice.route == PlacedRoute::Refused) throw std::runtime_error(choice.reason);
     gaps = score_gap_form(in, kAlgSW, R_, F_, base.geo->G * base.geo->K);
-    if (choice.route == PlacedRoute::Strip) return base;
+    if (choice.route == PlacedRoute::Strip || choice.route == PlacedRoute::Chain) return base;      // (neither launches on the plan)
     auto track_of = [](const PlacedChoice &c) { return c.route == PlacedRoute::Key ? kPlacedKey : kPlacedRows; };
     if (base.geo->placed(track_of(choice), gaps)) return base;
     if (!fallback_plan_.geo) fallback_plan_ = choose_plan(R_, F_, 0, 0, false, true);
@@ -42,6 +42,13 @@ void Engine::score_placed_device(int opt, long long n, const uint8_t *d_reads, c
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (choice.route == PlacedRoute::Strip) {
         score_placed_strips(n, d_reads, d_refs, d_placed, stream);
+        ran_placed_ = ran_placed_name(choice.route);
+        return;
+    }
+    if (choice.route == PlacedRoute::Chain) {
+        // the banded score sweep's launch (engine_long.hip) with the kernel's PLACED form: int32 cells, nothing kept in HBM
+        sync_band_tables(stream);
+        score_band_device(long_mode(kAlgSW, false), n, d_reads, d_refs, nullptr, d_placed, stream);
         ran_placed_ = ran_placed_name(choice.route);
         return;
     }
@@ -99,6 +106,8 @@ void Engine::score_placed_host(int opt, int n, const char *const *reads, const c
     PlacedChoice choice;
     int gaps = 0;
     (void)placed_plan_for(alg, choice, gaps);          // (refusals leave here, before anything is staged)
+    // (the chain keeps nothing between launches: its chunks run on the slots' own streams; its tables go up once, here)
+    if (choice.route == PlacedRoute::Chain) sync_band_tables(streams_[0].get());
     const bool strips = choice.route == PlacedRoute::Strip;      // their launches share the boundary rows: one stream, large chunks
     const size_t per_pair = (size_t)R_ + F_;
     const size_t chunk_bytes = strips && !dbg_.on("chunk_bytes") ? std::max<size_t>(score_chunk_bytes_, 192u << 20) : score_chunk_bytes_;

@@ -86,6 +86,7 @@ def lib():
         L.valign_hip_set_band_width.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_band_alignments.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_band_nw.argtypes = [vp, ctypes.c_int]
+        L.valign_hip_set_band_placed.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_trace_checkpoints.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_pointer_scratch_cap_mb.argtypes = [vp, ctypes.c_longlong]
         L.valign_hip_set_host_packing.argtypes = [vp, ctypes.c_int]
@@ -114,7 +115,7 @@ def lib():
 EXPORTED_SYMBOLS = (
     "spawn_alignment_kernel", "set_parameters", "set_logger", "delete_alignment_kernel",
     "valign_hip_device_count", "valign_hip_shard_range", "valign_hip_engine_create", "valign_hip_engine_destroy",
-    "valign_hip_set_traceback_policy", "valign_hip_set_pointer_scratch_cap_mb", "valign_hip_set_host_packing", "valign_hip_set_half_float_cells", "valign_hip_host_register", "valign_hip_host_unregister", "valign_hip_set_band_width", "valign_hip_set_band_alignments", "valign_hip_set_band_nw", "valign_hip_set_trace_checkpoints", "valign_hip_set_score_width", "valign_hip_set_ragged_batching", "valign_hip_score_device", "valign_hip_align_device", "valign_hip_score_host", "valign_hip_align_host", "valign_hip_align_cigar_device", "valign_hip_align_cigar_host", "valign_hip_score_placed_device", "valign_hip_score_placed_host", "valign_hip_describe",
+    "valign_hip_set_traceback_policy", "valign_hip_set_pointer_scratch_cap_mb", "valign_hip_set_host_packing", "valign_hip_set_half_float_cells", "valign_hip_host_register", "valign_hip_host_unregister", "valign_hip_set_band_width", "valign_hip_set_band_alignments", "valign_hip_set_band_nw", "valign_hip_set_band_placed", "valign_hip_set_trace_checkpoints", "valign_hip_set_score_width", "valign_hip_set_ragged_batching", "valign_hip_score_device", "valign_hip_align_device", "valign_hip_score_host", "valign_hip_align_host", "valign_hip_align_cigar_device", "valign_hip_align_cigar_host", "valign_hip_score_placed_device", "valign_hip_score_placed_host", "valign_hip_describe",
     "valign_hip_last_error",
 )
 
@@ -210,6 +211,13 @@ class Engine:
         """1: band_width > 0 also applies to NW-variant scores and, with set_band_alignments(1), to NW-variant alignments
         (include/valign_hip.h has the definition); 0 (default): both are refused under a band."""
         if lib().valign_hip_set_band_nw(self._h, int(on)) != 0:
+            raise HipKernelError(_err())
+
+    def set_band_placed(self, on):
+        """1: with band_width > 0 score_placed_device / score_placed_host return the banded Smith-Waterman score and its first
+        in-band end cell from the block chain (describe: ran_placed "chain"; include/valign_hip.h has the definition);
+        0 (default): placed scores are refused under a band.  Not read without a band."""
+        if lib().valign_hip_set_band_placed(self._h, int(on)) != 0:
             raise HipKernelError(_err())
 
     def set_trace_checkpoints(self, on):
