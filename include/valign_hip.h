@@ -380,6 +380,55 @@ int valign_hip_score_placed_device(valign_hip_engine *e, int opt, long long n, c
 int valign_hip_score_placed_host(valign_hip_engine *e, int opt, int n, const char *const *reads,
                                  const char *const *refs, valign_hip_placed *placed, int threads);
 
+/* ---- spanned Smith-Waterman scores: begin and end cell without a traceback ----
+ * A mapper reports where an alignment BEGINS (SAM's POS is ref_begin, the soft clip is read_begin).  Spanned scores give the
+ * placed record plus the begin cell from TWO score sweeps: no pointer stream, no pointer scratch, no walk, no host round trip.
+ * DEFINITION, for Smith-Waterman (opt & 0xF == 0), per pair:
+ *   score, read_end, ref_end
+ *                 exactly what valign_hip_score_placed_device returns for the pair.
+ *   read_begin, ref_begin
+ *                 Let P be the prefix rectangle read[0, read_end) x ref[0, ref_end).  The end cell is the first cell in row-major
+ *                 order that holds the maximum, so it is the only cell of P that holds `score`, and every local alignment
+ *                 inside P with that score ends in it.  Reverse both prefixes and run the same Smith-Waterman recurrence
+ *                 (same scoring, same gap model, read steps and reference steps keeping their roles): that reversed matrix
+ *                 has maximum `score`, in exactly the cells where an optimal alignment ending in the end cell can begin.
+ *                 (read_begin, ref_begin) come from the FIRST cell in row-major order of the reversed matrix that holds
+ *                 `score`: if that cell is (i', j'), 0-based, read_begin = read_end - 1 - i' and ref_begin = ref_end - 1 - j'.
+ *                 In forward terms: of all optimal alignments that end in the end cell, the one that begins in the latest read
+ *                 row and, within that row, the latest reference column.  0-based and half-open, as in valign_hip_aln.
+ *   empty ....... a pair whose maximum is 0 returns five zeros.
+ * GUARANTEED: the global alignment score of read[read_begin, read_end) against ref[ref_begin, ref_end) under the engine's
+ * scoring equals `score`.
+ * NOT GUARANTEED: equality with valign_hip_aln.read_begin / .ref_begin of valign_hip_align_cigar_device.  The walk follows the
+ * fill's pointer tie-breaks; where two optimal alignments share the end cell it may begin elsewhere (on random pairs with the
+ * CPU oracle's walk about one pair in 200 differed).  The two are not interchangeable.
+ * The reverse sweep looks back span_ref_length = min(ref_length, read_length + (read_length x max(match, mismatch, 0) - 1) /
+ * c) reference columns, c the cheapest price of one reference base against a gap in the read (|gap_read|; affine: min(|open_read|,
+ * |ext_read|); c = 0: ref_length): no alignment of a positive score covers more, so the clipped sweep gives exactly the
+ * unclipped records.  tests/span_ref.py restates the definition in numpy, unclipped.
+ * REFUSED with a non-zero return and a message in valign_hip_last_error: everything valign_hip_score_placed_device refuses
+ * without a band, with the same texts (opt & 0xF == 1, traceback_policy = 1, score_width = 32, a shape x scoring whose cells
+ * could leave int16) -- and band_width > 0 WHATEVER band_placed says: the chain's block windows are not symmetric under
+ * reversal, so a reversed banded sweep would be another band.  opt & 0xF > 1 does nothing, as everywhere.
+ * "ran_span" of valign_hip_describe names the forward and the reverse route of the last call, joined ("key/key", "strip/strip",
+ * ...; "none" before any, or when it was refused); "ran_placed" then reports the forward route; "span_ref_length" is the bound
+ * above and "span_scratch_bytes" the scratch device-resident calls hold.                                                     */
+typedef struct {                     /* 20 bytes */
+    int32_t score, read_begin, read_end, ref_begin, ref_end;
+} valign_hip_span;
+
+/* Device-resident: d_spans = n records.  Asynchronous on hip_stream, no host synchronisation once the scratch exists.  The call
+ * is cut into chunks so that the reversed prefixes and the two record buffers stay inside an engine-owned scratch of at most
+ * 256 MiB (whole rounds of the forward sweep's waves); that scratch is reused chunk after chunk in stream order: calls of one
+ * engine that use it belong on one stream.                                                                                   */
+int valign_hip_score_span_device(valign_hip_engine *e, int opt, long long n, const void *d_reads,
+                                 const void *d_refs, void *d_spans, void *hip_stream);
+
+/* Host pointers in, records out: the chunk pipeline of valign_hip_score_placed_host (gather, 4-bit classes under
+ * host_packing, H2D, kernels, D2H; small calls run on the pinned staging directly), 20 bytes per pair on the way back.       */
+int valign_hip_score_span_host(valign_hip_engine *e, int opt, int n, const char *const *reads,
+                               const char *const *refs, valign_hip_span *spans, int threads);
+
 /* Page-lock a host range and map it for the device (hipHostRegister behind a C symbol, so that an FFI caller needs no
  * HIP binding).  valign_hip_align_host into result buffers that lie inside a registered range -- or inside memory the
  * caller page-locked itself -- skips the library's pinned staging and its host-side copy: the device's copy engine
@@ -408,7 +457,8 @@ int valign_hip_set_half_float_cells(valign_hip_engine *e, int mode);
  * "ran_result_format" is "rows" or "cigar" for the last alignment call, "cigar_d2h_bytes" what the last
  * valign_hip_align_cigar_host call copied back, "cigar_rows_scratch_bytes" the rows scratch of the compact format.
  * "ran_placed" is what the last placed-score call ran: key / rows / strip / chain ("none" before any, or when it was
- * refused); "band_placed" is the key of valign_hip_set_band_placed.                                                           */
+ * refused); "band_placed" is the key of valign_hip_set_band_placed.  "ran_span", "span_ref_length" and "span_scratch_bytes"
+ * belong to the spanned scores, above.                                                                                         */
 int valign_hip_describe(valign_hip_engine *e, int opt, long long n, char *buf, int cap);
 
 const char *valign_hip_last_error(void);

@@ -3,7 +3,8 @@
 destroyed by the hundred, score_device / align_device on torch tensors and random streams, score_host / align_host on numpy
 arrays (with and without a registered destination), length-sorted batching, bands, pointer-scratch caps -- every result
 against oracle/cpu_ref; placed Smith-Waterman scores (score_placed_device / _host) against tests/placed_ref.py and, under a band with
-band_placed = 1, against tests/placed_band_ref.py.  What tools/fuzz_parity.py does for the plugin ABI, for the entry points the tests of the device path
+band_placed = 1, against tests/placed_band_ref.py; spanned scores (score_span_device / _host) against tests/span_ref.py wherever the
+unbanded placed scores run, and refused under every band.  What tools/fuzz_parity.py does for the plugin ABI, for the entry points the tests of the device path
 use; a process that runs it for minutes also exercises the library's set-up and tear-down far more often than the suite.
 
     python -X faulthandler tools/fuzz_device.py --seconds 300 --seed 1
@@ -25,10 +26,12 @@ from versalignlib_amd import hipkernel, synth                      # noqa: E402
 import band_nw_ref                                                 # noqa: E402
 import placed_band_ref                                             # noqa: E402
 import placed_ref                                                  # noqa: E402
+import span_ref                                                    # noqa: E402
 
 
 NW_BAND_CASES = [0]             # cases that also ran the NW variant under the band
 PLACED_CASES = [0]              # cases that also ran placed Smith-Waterman scores
+SPAN_CASES = [0]                # ... and spanned scores
 BAND_PLACED_CASES = [0]         # banded cases that also ran placed scores on the chain (band_placed = 1)
 
 
@@ -102,6 +105,12 @@ def run(c):
                         raise
                 eng.set_band_placed(1)
                 BAND_PLACED_CASES[0] += 1
+                try:
+                    eng.score_span_device(0, d_reads, d_refs, stream=stream)
+                    return "score_span_device ran under a band"
+                except hipkernel.HipKernelError as err:
+                    if "band_width" not in str(err):
+                        raise
                 got = eng.score_placed_device(0, d_reads, d_refs, stream=stream)
                 if stream is not None:
                     stream.synchronize()
@@ -166,6 +175,18 @@ def run(c):
                         h = eng.score_placed_host(0, reads, refs, threads=c["threads"])
                         if not np.array_equal(np.stack([h["score"], h["read_end"], h["ref_end"]], axis=1).astype(np.int64), pexp):
                             return "score_placed_host differs"
+                    # spanned scores wherever placed scores ran: the numpy restatement, unclipped (tests/span_ref.py)
+                    SPAN_CASES[0] += 1
+                    sexp = span_ref.spans(reads, refs, osc, affine=c["affine"])
+                    got = eng.score_span_device(0, d_reads, d_refs, stream=stream)
+                    if stream is not None:
+                        stream.synchronize()
+                    if not np.array_equal(got.cpu().numpy().astype(np.int64), sexp):
+                        return "score_span_device differs (%s)" % eng.describe(0, n)["ran_span"]
+                    if c["host"]:
+                        h = eng.score_span_host(0, reads, refs, threads=c["threads"])
+                        if not np.array_equal(np.stack([h[k] for k in hipkernel.span_dtype().names], axis=1).astype(np.int64), sexp):
+                            return "score_span_host differs"
         if R * F * n <= 30_000_000:
             akw = dict(affine=True) if c["affine"] else dict(policy="sse" if c["policy"] else "default")
             for opt in (0, 1):
@@ -215,8 +236,8 @@ def main():
             if done % 25 == 0:
                 print("%d cases, %.0f s" % (done, time.time() - t0), flush=True)
         i += 1
-    print("ok: %d cases in %.0f s (seed %d), %d of them with the banded NW variant, %d with placed scores, %d with banded placed scores" %
-          (done, time.time() - t0, a.seed, NW_BAND_CASES[0], PLACED_CASES[0], BAND_PLACED_CASES[0]))
+    print("ok: %d cases in %.0f s (seed %d), %d of them with the banded NW variant, %d with placed scores, %d with spanned scores, "
+          "%d with banded placed scores" % (done, time.time() - t0, a.seed, NW_BAND_CASES[0], PLACED_CASES[0], SPAN_CASES[0], BAND_PLACED_CASES[0]))
     return 0
 
 

@@ -48,6 +48,10 @@ echo "== placed_choice under band_placed (cell_rules.h + long_plan.h) under Addr
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" -I"$R/include" "$R/tests/placed_band_rules_check.cpp" -o "$OUT/placed_band_rules_asan"
 "$OUT/placed_band_rules_asan"
 
+echo "== span_ref_length and span_choice of cell_rules.h under AddressSanitizer + UBSan"
+g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/span_rules_check.cpp" -o "$OUT/span_rules_asan"
+"$OUT/span_rules_asan"
+
 echo "== libvalignhost.so, valign-bench, libcpuref.so with $SAN"
 g++ -std=c++14 $SAN -fPIC -shared -Wall -pthread -I"$R/include" "$CS/valign_host.cpp" -o "$OUT/libvalignhost.so" -ldl
 g++ -std=c++14 $SAN -Wall -I"$R/include" "$CS/valign_bench.cpp" -o "$OUT/valign-bench" -L"$OUT" -lvalignhost -Wl,-rpath,'$ORIGIN' -ldl -pthread

@@ -271,6 +271,37 @@ inline const char *ran_placed_name(PlacedRoute r) {
     return names[(int)r];
 }
 
+// ---- spanned scores (valign_hip_score_span_*): a placed score plus the begin cell, from a second sweep over the reversed
+// prefixes that end in the end cell ----
+// Reference columns the reverse sweep has to look back.  An alignment of score S >= 1 on a <= R read bases has d <= R diagonal
+// columns and l columns that put a reference base against a gap in the read; with m = max(match, mismatch, 0) and c the
+// cheapest price of one such gap base, S <= d m - l c, so l <= (R m - 1) / c and the alignment covers at most R + l columns.
+// c = 0: no bound, F.  m = 0: no alignment scores at all, and min(R, F) columns hold every diagonal.
+inline long long span_ref_length(const RuleInputs &in) {
+    const Scoring &sc = in.sc;
+    const long long R = in.R, F = in.F;
+    const long long m = std::max({sc.match, sc.mismatch, 0});
+    const long long c = sc.affine ? std::min(std::abs((long long)sc.open_read), std::abs((long long)sc.ext_read)) : std::abs((long long)sc.gap_read);
+    if (c == 0) return F;
+    const long long gap_cols = R * m >= 1 ? (R * m - 1) / c : 0;
+    return std::min(F, R + gap_cols);
+}
+
+// A spanned call is two unbanded placed calls: refused exactly where placed_choice refuses one of those, with its texts -- and
+// under a band whatever band_placed says: the chain's block windows are not symmetric under reversal, so the reverse sweep would
+// run on another band than the forward one.  Otherwise the choice is the forward sweep's (the reverse sweep asks for its own
+// shape, (R, span_ref_length)).  `G x K` as in placed_choice; without them only Refused or not, and the reason, mean anything.
+inline PlacedChoice span_choice(const RuleInputs &in, int alg, const PlacedFacts &f, int G = 0, int K = 0) {
+    PlacedFacts unbanded = f;
+    unbanded.band_width = 0;
+    PlacedChoice c = placed_choice(in, alg, unbanded, G, K);
+    if (c.route != PlacedRoute::Refused && f.band_width > 0) {
+        c = PlacedChoice{};
+        c.reason = "spanned scores are not built for band_width > 0";
+    }
+    return c;
+}
+
 // ---- band_nw = 1: the NW variant under the block band (include/valign_hip.h) ----
 // Consecutive blocks' windows connect -- every in-band cell has a present candidate -- once 2 * (band_width / 2) + 1 columns
 // cover the most a window start advances per row, ceil(F / R).  Narrower bands are refused.

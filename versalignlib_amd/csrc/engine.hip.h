@@ -10,6 +10,8 @@
 //   engine_align.hip .... compute_alignments: fill + traceback launches, row strips, the fused small-batch launch, the
 //                         host-pointer pipeline with its copy-issuing thread (reference: DefaultKernel.cpp:21-50, 204-525)
 //   engine_placed.hip ... placed Smith-Waterman scores: score + end cell from the score sweep (placed_kernels.hip.h)
+//   engine_span.hip ..... spanned Smith-Waterman scores: a placed score plus the begin cell, from a second placed sweep over the
+//                         reversed prefixes (span_kernels.hip.h)
 //   engine_cigar.hip .... the compact result format: records + CIGAR ops encoded on the device behind the walks (cigar_kernels.hip.h)
 //   hip_plugin.hip ...... the plugin ABI and the flat C API over it
 // The closest reference precedent for the staging loops is the OpenCL backend's gather / copy / launch / collect loop
@@ -47,6 +49,7 @@
 #include "long_plan.h"
 #include "pack_kernels.hip.h"
 #include "ragged_kernels.hip.h"
+#include "span_kernels.hip.h"
 #include "strip_kernels.hip.h"
 #include "strip_plan.h"
 
@@ -158,7 +161,8 @@ public:
         if (!env) return;
         static const char *const known[] = {"no_sym", "no_tag", "no_f16", "no_fused", "no_prof_key", "no_overlap", "no_band_chain",
                                             "force_long", "wide_align", "strip_k", "no_single_strip", "no_direct_out", "ragged_min", "chunk_bytes",
-                                            "align_chunk_bytes", "direct_bytes", "scratch_cap_mb", "whole_rows", "short_strips", "cigar_rows_mb", "cigar_lanes"};
+                                            "align_chunk_bytes", "direct_bytes", "scratch_cap_mb", "whole_rows", "short_strips", "cigar_rows_mb", "cigar_lanes",
+                                            "span_scratch_bytes"};
         std::string s(env);
         for (size_t at = 0; at <= s.size();) {
             const size_t end = std::min(s.find(',', at), s.size());
@@ -462,6 +466,16 @@ public:
     void launch_placed_records(const EndCell *d_ends, PlacedRec *d_placed, long long n, hipStream_t stream);
     const char *ran_placed() const { return ran_placed_; }
 
+    // ---- spanned Smith-Waterman scores (valign_hip.h: valign_hip_span; engine_span.hip) ----
+    // The placed record plus the begin cell: score_placed_device as it stands, the reversal of the prefixes that end in the end
+    // cell (span_kernels.hip.h), score_placed_device of a child engine of shape (R, span_ref_length) on the reversed buffers,
+    // and the records.  span_choice (cell_rules.h) decides what is refused.  Device-resident: asynchronous on `stream`, in
+    // chunks that keep the reversed buffers and the two record buffers inside span_scratch_bytes_; calls of one engine belong
+    // on one stream.  Host pointers: score_placed_host's chunk pipeline, 20 bytes per pair on the way back.
+    void score_span_device(int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, SpanRec *d_spans, hipStream_t stream);
+    void score_span_host(int opt, int n, const char *const *reads, const char *const *refs, SpanRec *spans, int threads);
+    const char *ran_span() const { return ran_span_.c_str(); }
+
     // host-side phases of the last score_host / align_host call
     std::string host_phases() const;
 
@@ -579,6 +593,23 @@ private:
 
     void ensure_staging(long long pairs);
     void ensure_placed_staging(long long pairs);
+
+    // ---- spanned scores (engine_span.hip) ----
+    // One context per pipeline slot (chunks of different slots are in flight side by side) and one for device-resident calls
+    struct SpanCtx {
+        long long cap = 0;                     // pairs the buffers hold
+        DeviceBuffer<uint8_t> rev_reads, rev_refs;
+        DeviceBuffer<PlacedRec> fwd, rev;
+        size_t bytes() const { return rev_reads.bytes() + rev_refs.bytes() + fwd.bytes() + rev.bytes(); }
+    };
+    // refusals (thrown), then the child engine of the reverse sweep, created on the first call; strips: either sweep takes the
+    // row strips, whose launches share an engine-owned scratch (one stream)
+    Engine &span_prepare(int alg, bool &strips);
+    long long span_chunk_pairs(long long n) const;
+    void ensure_span_scratch(int c, long long pairs, hipStream_t stream);
+    void ensure_span_staging(long long pairs);
+    // one chunk, all of it on `stream`: forward sweep, reversal, reverse sweep, records
+    void span_chunk(int c, int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, SpanRec *d_spans, hipStream_t stream);
 
     // ---- length-sorted batching (score_host, Smith-Waterman) ----
 
@@ -708,6 +739,9 @@ private:
     unsigned ran_score_cells_ = 0;
     const char *ran_align_fill_ = "none";
     const char *ran_placed_ = "none";                    // what the last placed-score call ran: key / rows / strip / chain (describe)
+    std::string ran_span_ = "none";                      // what the last spanned call ran: forward route / reverse route (describe)
+    size_t span_scratch_bytes_ = (size_t)dbg_.value("span_scratch_bytes", 256ll << 20);      // device-resident spanned calls: scratch of one chunk
+    long long span_staged_pairs_ = 0;
     const char *ran_result_format_ = "rows";             // of the last alignment call: rows / cigar (describe)
     long long cigar_d2h_bytes_ = 0;                      // what the last align_cigar_host call copied back
     const CigarSink *cigar_ = nullptr;
@@ -757,6 +791,11 @@ private:
     DeviceBuffer<unsigned> d_placed_rows_;
     DeviceBuffer<EndCell> d_placed_ends_;
     DeviceBuffer<int> d_placed_bad_;
+    // spanned scores: record staging of the host path, the reversal scratch, the engine of the reverse sweep
+    PinnedBuffer<SpanRec> h_span_[kSlots];
+    DeviceBuffer<SpanRec> d_span_[kSlots];
+    SpanCtx span_[kSlots + 1];                                   // one per pipeline slot, the last for device-resident calls
+    std::unique_ptr<Engine> span_child_;
     DeviceBuffer<unsigned> d_brow_;                              // long-read path: strip boundary rows
     DeviceBuffer<BandBlock> d_band_blocks_;                      // the block chain's tables (band_plan_)
     DeviceBuffer<int> d_band_fill_;

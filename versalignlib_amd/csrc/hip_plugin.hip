@@ -630,6 +630,28 @@ VALIGN_EXPORT int valign_hip_score_placed_host(valign_hip_engine *e, int opt, in
     return flat_guard([&] { e->impl->score_placed_host(opt, n, reads, refs, (valign::PlacedRec *)placed, threads); });
 }
 
+static_assert(sizeof(valign_hip_span) == sizeof(valign::SpanRec) && sizeof(valign_hip_span) == 20, "valign_hip_span is the kernels' record");
+
+VALIGN_EXPORT int valign_hip_score_span_device(valign_hip_engine *e, int opt, long long n, const void *d_reads, const void *d_refs,
+                                               void *d_spans, void *hip_stream) {
+    if (!e) {
+        g_last_error = "null engine";
+        return 1;
+    }
+    return flat_guard([&] {
+        e->impl->score_span_device(opt, n, (const uint8_t *)d_reads, (const uint8_t *)d_refs, (valign::SpanRec *)d_spans, (hipStream_t)hip_stream);
+    });
+}
+
+VALIGN_EXPORT int valign_hip_score_span_host(valign_hip_engine *e, int opt, int n, const char *const *reads, const char *const *refs,
+                                             valign_hip_span *spans, int threads) {
+    if (!e) {
+        g_last_error = "null engine";
+        return 1;
+    }
+    return flat_guard([&] { e->impl->score_span_host(opt, n, reads, refs, (valign::SpanRec *)spans, threads); });
+}
+
 VALIGN_EXPORT int valign_hip_describe(valign_hip_engine *e, int opt, long long n, char *buf, int cap) {
     if (!e || !buf || cap <= 0) return 1;
     const std::string s = e->impl->describe(opt, n);
