@@ -6,7 +6,9 @@
 compiles versalignlib_amd/csrc/kernel_part.hip (-DVALIGN_PART=n), engine_long.hip (--part main: band / long-read kernels) or
 engine_align.hip (--part align: strip / fused / traceback kernels) for gfx950 with
 --cuda-device-only -S, finds the largest innermost loop of the first kernel whose mangled name contains --kernel, and
-counts its instructions by issue class.  Classes follow the measured rates of profiles/r02_valu_rate_microbench.txt and
+counts its instructions by issue class; --all-loops prints every innermost loop of that kernel in program order (the fixed
+part of a sweep -- set-up, fill, drain -- sits in the small ones).  Classes follow the measured rates of
+profiles/r02_valu_rate_microbench.txt and
 r02_valu_rate_bitops.txt: "full" (2.3-2.7 cycles per wave64 instruction per SIMD from two waves per SIMD up) and
 "half" (4.1-4.5: every VOP3P packed instruction, maxima wider than 16 bits, v_perm, v_mad_u24, shifts-with-or, DPP)."""
 import argparse
@@ -44,6 +46,7 @@ def main():
     ap.add_argument("--part", default="5")
     ap.add_argument("--kernel", required=True)
     ap.add_argument("--asm", default="", help="an existing .s file instead of compiling")
+    ap.add_argument("--all-loops", action="store_true", help="every innermost loop of the kernel, not only the largest")
     a = ap.parse_args()
     asm = a.asm
     if not asm:
@@ -66,7 +69,15 @@ def main():
         if m and m.group(1) in labels and labels[m.group(1)] < i:
             loops.append((labels[m.group(1)], i))
     inner = [lp for lp in loops if not any(o != lp and lp[0] <= o[0] and o[1] <= lp[1] for o in loops)]
-    lo, hi = max(inner, key=lambda lp: lp[1] - lp[0])
+    if a.all_loops:          # every innermost loop of the kernel, in program order (the set-up loops and the step loops)
+        for lo, hi in sorted(inner):
+            report(body, lo, hi, "loop")
+    else:
+        lo, hi = max(inner, key=lambda lp: lp[1] - lp[0])
+        report(body, lo, hi, "hot loop")
+
+
+def report(body, lo, hi, what):
     ops = [ln.split()[0] for ln in body[lo:hi + 1] if ln.startswith("\t") and not ln.startswith("\t.") and not ln.strip().startswith(";")]
     counts = collections.Counter()
     detail = collections.Counter()
@@ -83,7 +94,7 @@ def main():
             counts["salu / control"] += 1
         else:
             counts[op] += 1
-    print("hot loop: %d instructions (lines %d-%d of the kernel)" % (len(ops), lo, hi))
+    print("%s: %d instructions (lines %d-%d of the kernel)" % (what, len(ops), lo, hi))
     for k in ("half", "full", "other valu", "lds", "vmem", "salu / control"):
         print("  %-16s %4d" % (k, counts.get(k, 0)))
     valu = counts["half"] + counts["full"] + counts["other valu"]

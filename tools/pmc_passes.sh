@@ -1,6 +1,7 @@
 #!/bin/bash
 # rocprofv3 PMC passes over tools/prof_kernel.py, one counter group per run (no trace domains
 # mixed in).  Usage: tools/pmc_passes.sh <tag> [prof_kernel args...]   (run on the GPU box)
+# PMC_GROUPS="1 5" runs only those passes (e.g. the instruction counts and the cycles of another build, for a comparison).
 set -u
 TAG=$1; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}
@@ -14,6 +15,7 @@ for group in \
   "WRITE_SIZE" \
   "GRBM_GUI_ACTIVE GRBM_COUNT" ; do
   i=$((i+1))
+  case " ${PMC_GROUPS:-1 2 3 4 5} " in *" $i "*) ;; *) continue ;; esac
   rocprofv3 --pmc $group --output-format csv -d $R/gpurun_out/pmc_${TAG}/p$i -- python3 $R/tools/prof_kernel.py "$@" > $R/gpurun_out/pmc_${TAG}_p$i.log 2>&1 || echo "pass $i failed"
   echo "pass $i done"
 done

@@ -39,9 +39,12 @@
 //     V - g_ref * p - g_read * j: gap steps (affine: extensions) cost nothing, the diagonal pays for
 //     both through the query profile -- linear 3 packed instructions per register on half floats
 //     (perm, add, max3), 4 on int16; symmetric affine 6 / 7.  See score_kernel.
-//   * Pipeline fill/drain steps EXEC-mask lanes outside columns [0, F) (finished lanes keep
-//     the values of the last column, needed by the NW-variant result); the steady phase
-//     runs unmasked.
+//   * Smith-Waterman sweeps run unmasked from the first step to the last: a lane outside columns [0, F) reads
+//     zero-slab codes from the pads of the code array, stays zero before column 0 and can only repeat values that
+//     exist already after column F-1, so no step needs a mask and the whole sweep is one loop of two-step trips,
+//     started at the first lane that owns a real row.  The NW variant keeps EXEC-masked fill / drain steps: its
+//     result reads every lane's registers frozen at the last column.  The set-up before a sweep (wave_setup) works
+//     a dword at a time: four reference columns, four read rows per lane and trip (base_classes.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -49,6 +52,7 @@
 
 #include <type_traits>
 
+#include "base_classes.h"
 #include "cell_constants.h"
 
 namespace valign {
@@ -113,18 +117,6 @@ template <int G>
 __device__ __forceinline__ unsigned group_prev_or_zero(unsigned v, unsigned lmask) {
     if (G == 16) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111 /* row_shr:1 */, 0xF, 0xF, true);
     return from_prev_lane(v) & lmask;
-}
-
-// base class of one input byte: A/a 1, T/t 2, C/c 3, G/g 4, N/n 5, else 0
-__device__ __forceinline__ int base_class(unsigned ch) {
-    const unsigned u = ch & 0xDFu;            // fold case; bytes >= 0x80 never match
-    int c = 0;
-    c = (u == 'A') ? 1 : c;
-    c = (u == 'T') ? 2 : c;
-    c = (u == 'C') ? 3 : c;
-    c = (u == 'G') ? 4 : c;
-    c = (u == 'N') ? 5 : c;
-    return c;
 }
 
 // LDS bank conflicts of one profile fetch, modelled per MI355X_MICROARCH.md section LDS: every lane of
@@ -196,6 +188,18 @@ struct Geo {
     __host__ __device__ static constexpr int row_offset(int l, int q) { return l * kLaneBytes + q * 2; }
 };
 
+typedef __attribute__((address_space(3))) const unsigned lds_cu32;
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) const u32x2 lds_cu32x2;
+typedef __attribute__((address_space(3))) const u32x4 lds_cu32x4;
+typedef __attribute__((address_space(3))) const unsigned char lds_cu8;
+
+// LDS byte offset of a pointer into the dynamic shared array
+__device__ __forceinline__ unsigned lds_offset(const void *p) {
+    return (unsigned)(size_t)(__attribute__((address_space(3))) const void *)p;
+}
+
 // Copy global bytes [begin, end) of `src` into LDS so that byte x lands at
 // dst[x - (begin & ~15)] : 16-byte coalesced loads for the interior, bytes at the rims.
 __device__ __forceinline__ void stage_span(unsigned char *dst, const uint8_t *src, long long begin,
@@ -214,6 +218,14 @@ __device__ __forceinline__ void stage_span(unsigned char *dst, const uint8_t *sr
     }
 }
 
+// The four LDS bytes that start at `p`, whatever its alignment: the two aligned dwords around them, one v_alignbyte_b32
+// (reads up to 7 bytes past p: callers keep that inside the wave's LDS)
+__device__ __forceinline__ unsigned lds_dword_at(const unsigned char *p) {
+    const unsigned a = lds_offset(p), base = a & ~3u;
+    const unsigned lo = *(lds_cu32 *)(base), hi = *(lds_cu32 *)(base + 4);
+    return __builtin_amdgcn_alignbyte(hi, lo, a & 3u);
+}
+
 extern __shared__ __align__(16) unsigned char valign_smem[];
 
 // Per-wave LDS tables shared by the score and the alignment-fill kernels.
@@ -227,9 +239,13 @@ struct WaveTables {
 };
 
 // Stage the wave's raw refs with coalesced 16-byte loads, then build the per-column slab
-// numbers and the query profile (read bases come straight from HBM, one coalesced byte
-// per lane and row).  Returns false for a wave past the end of the batch (it still takes
-// part in the block barriers).
+// numbers and the query profile.  Both go a dword at a time (base_classes.h: base_class4): a lane turns four
+// reference columns of pair A and of pair B into four interleaved slab-number pairs (the rim F % 4 goes byte-wise),
+// and four rows of a read into the 4 x 4 scores of the four class slabs, looked up with v_perm_b32 from eight-entry
+// tables indexed by the class.  The wave's reads are one contiguous span when one sweep covers the read: it is staged
+// beside the references where both fit the profile area; otherwise (row strips, long references) the read bases
+// come straight from HBM, one coalesced byte per lane and row.  Returns false for a wave past the end of the
+// batch (it still takes part in the block barriers).
 template <int G, int K, bool FIND_BAD>
 __device__ __forceinline__ bool wave_setup(const uint8_t *reads, const uint8_t *refs, long long n, int R, int F,
                                            int prof_area, int refc_stride, int wave_lds, short match,
@@ -255,11 +271,21 @@ __device__ __forceinline__ bool wave_setup(const uint8_t *reads, const uint8_t *
     if (pair_end > n) pair_end = n;
     const int last = (int)(pair_end - pair0) - 1;
 
-    // ---- read bases of this lane's 2K (pair, padded row) items, straight from HBM ----
+    // (where all the wave's references fit the profile area anyway -- 8 x 500 bytes in 11.6 KB -- they are staged in one go:
+    // one barrier instead of two per lane group, 1.5 % of the 150 x 500 sweep)
+    const bool whole = geo::kPairs * F + 32 <= prof_area;
+    // ... and the wave's reads behind them (8 x 150 bytes), when one sweep covers the read
+    const int rd_off = ((geo::kPairs * F + 32 + 15) / 16) * 16;
+    const bool rd_staged = whole && strip_row0 == kOneSweep && rd_off + geo::kPairs * R + 32 <= prof_area;
+
+    // ---- otherwise: read bases of this lane's 2K (pair, padded row) items, straight from HBM ----
     // kPairs * kRows == 128 * K for every geometry, so each lane owns exactly 2K items.
     unsigned char rd[2 * K];
-    long long ref_lo = 0;
-    if (live) {
+    if (live && FIND_BAD && lane < geo::kPairs) {
+        first_bad[2 * lane] = R;
+        first_bad[2 * lane + 1] = F;
+    }
+    if (live && !rd_staged) {
 #pragma unroll
         for (int i = 0; i < 2 * K; ++i) {
             const int idx = lane + kWave * i;
@@ -267,10 +293,6 @@ __device__ __forceinline__ bool wave_setup(const uint8_t *reads, const uint8_t *
             const int ps = p > last ? last : p;
             const int pos = row0 + rr;
             rd[i] = (pos >= 0 && pos < R) ? reads[(pair0 + ps) * R + pos] : (unsigned char)0;
-        }
-        if (FIND_BAD && lane < geo::kPairs) {
-            first_bad[2 * lane] = R;
-            first_bad[2 * lane + 1] = F;
         }
     }
 
@@ -288,13 +310,12 @@ __device__ __forceinline__ bool wave_setup(const uint8_t *reads, const uint8_t *
             dst[0] = dst[1] = (unsigned char)geo::kZeroSlab;
         }
     }
-    // (where all the wave's references fit the profile area anyway -- 8 x 500 bytes in 11.6 KB -- they are staged in one go:
-    // one barrier instead of two per lane group, 1.5 % of the 150 x 500 sweep)
-    const bool whole = geo::kPairs * F + 32 <= prof_area;
     if (whole) {
         if (live) stage_span(prof, refs, pair0 * F, pair_end * F, lane);
+        if (live && rd_staged) stage_span(prof + rd_off, reads, pair0 * R, pair_end * R, lane);
         __syncthreads();
     }
+    constexpr unsigned kZero4 = (unsigned)geo::kZeroSlab * 0x01010101u;
 #pragma unroll
     for (int g = 0; g < geo::kGroups; ++g) {
         int pa = 2 * g, pb = 2 * g + 1;
@@ -309,7 +330,33 @@ __device__ __forceinline__ bool wave_setup(const uint8_t *reads, const uint8_t *
             const int ref_skew = (int)((unsigned long long)(refs + ref_lo) & 15ull);
             const unsigned char *raw_a = prof + ref_skew + (whole ? pa * F : 0), *raw_b = raw_a + (pb - pa) * F;
             unsigned char *codes_g = refc + g * refc_stride + 2 * kCodePad;
-            for (int j = lane; j < F; j += kWave) {
+            // slab number by class, pair A / pair B of this group: classes 1..4 their slab, 0 and 5..7 the zero slab
+            const unsigned slab_a_lo = geo::kZeroSlab | (unsigned)(2 * g) << 8 | (unsigned)(geo::kPairs + 2 * g) << 16 |
+                                       (unsigned)(2 * geo::kPairs + 2 * g) << 24;
+            const unsigned slab_a_hi = (unsigned)(3 * geo::kPairs + 2 * g) | (kZero4 & 0xFFFFFF00u);
+            const unsigned slab_b_lo = slab_a_lo + 0x01010100u, slab_b_hi = slab_a_hi + 1u;
+            const int F4 = F & ~3;
+            for (int j = 4 * lane; j < F4; j += 4 * kWave) {            // four columns per lane and trip
+                const unsigned ca = base_class4(lds_dword_at(raw_a + j)), cb = base_class4(lds_dword_at(raw_b + j));
+                const unsigned sa = select_bytes8(slab_a_hi, slab_a_lo, ca), sb = select_bytes8(slab_b_hi, slab_b_lo, cb);
+                uint2 codes;                                            // (sa | sb << 8) of columns j, j + 1 | j + 2, j + 3
+                codes.x = __builtin_amdgcn_perm(sb, sa, 0x05010400u);
+                codes.y = __builtin_amdgcn_perm(sb, sa, 0x07030602u);
+                *reinterpret_cast<uint2 *>(codes_g + 2 * j) = codes;
+                const unsigned used = (sa ^ kZero4) | (sb ^ kZero4);    // a byte is non-zero where a pair has an ACGT base
+                if (used) {
+                    const int end = j + 4 - (__builtin_clz(used) >> 3);
+                    cols_used = end > cols_used ? end : cols_used;
+                }
+                if (FIND_BAD) {
+                    // "invalid" for the NW end cell: class 0 (Default kernel) or anything but ACGT (SSE kernel)
+                    const unsigned bad_a = ~nonzero_bytes(bad_is_non_acgt ? sa ^ kZero4 : ca) & 0x80808080u;
+                    const unsigned bad_b = ~nonzero_bytes(bad_is_non_acgt ? sb ^ kZero4 : cb) & 0x80808080u;
+                    if (bad_a) atomicMin(&first_bad[2 * (2 * g) + 1], j + (__builtin_ctz(bad_a) >> 3));
+                    if (bad_b) atomicMin(&first_bad[2 * (2 * g + 1) + 1], j + (__builtin_ctz(bad_b) >> 3));
+                }
+            }
+            for (int j = F4 + lane; j < F; j += kWave) {                // the rim
                 const int ca = base_class(raw_a[j]);
                 const int cb = base_class(raw_b[j]);
                 const bool va = ca >= 1 && ca <= 4, vb = cb >= 1 && cb <= 4;
@@ -326,10 +373,78 @@ __device__ __forceinline__ bool wave_setup(const uint8_t *reads, const uint8_t *
         }
         if (!whole) __syncthreads();
     }
+    // Staged reads: kPairs * kRows / 4 == 32 K four-row items, K / 2 per lane.  Item `it` holds the classes of padded rows
+    // rr .. rr + 3 of pair p (kRows is a multiple of 4: an item never straddles two pairs); (p, rr) walk on by 256 rows
+    // per item.  The classes leave the staging area before the barrier, the profile overwrites it after.
+    unsigned rd4[K / 2];
+    constexpr int kItemPairs = 256 / geo::kRows, kItemRows = 256 % geo::kRows;
+    const int item_p0 = (4 * lane) / geo::kRows, item_rr0 = (4 * lane) % geo::kRows;
+    if (live && rd_staged) {
+        const unsigned char *raw = prof + rd_off + (int)((unsigned long long)(reads + pair0 * R) & 15ull);
+        int p = item_p0, rr = item_rr0;
+#pragma unroll
+        for (int it = 0; it < K / 2; ++it) {
+            const int ps = p > last ? last : p;
+            const int pos = row0 + rr;                          // (row0 + kRows == R: pos + 3 < R always)
+            const int at = pos < -3 ? -3 : pos;
+            unsigned w4 = lds_dword_at(raw + ps * R + at);
+            if (pos < 0) w4 = pos < -3 ? 0u : w4 & (0xFFFFFFFFu << (8 * -pos));      // rows before the read: class 0
+            rd4[it] = base_class4(w4);
+            p += kItemPairs; rr += kItemRows;
+            if (rr >= geo::kRows) { rr -= geo::kRows; ++p; }
+        }
+    }
     if (whole) __syncthreads();
 
     // ---- query profile: slab[class * kPairs + pair][lane rows] = S(read base of the row, class) ----
-    if (live) {
+    if (live && rd_staged) {
+        // scores by class, low and high bytes apart, of slab c: class c + 1 match, the other three of 1..4 mismatch,
+        // classes 0 and 5..7 zero_score
+        auto table = [&](int c, int shift, unsigned &lo, unsigned &hi) __attribute__((always_inline)) {
+            unsigned b[8];
+#pragma unroll
+            for (int a = 0; a < 8; ++a)
+                b[a] = ((unsigned)(unsigned short)(a >= 1 && a <= 4 ? (a == c + 1 ? match : mismatch) : zero_score) >> shift) & 0xFFu;
+            lo = b[0] | b[1] << 8 | b[2] << 16 | b[3] << 24;
+            hi = b[4] | b[5] << 8 | b[6] << 16 | b[7] << 24;
+        };
+        int p = item_p0, rr = item_rr0;
+#pragma unroll
+        for (int it = 0; it < K / 2; ++it) {
+            const unsigned cls = rd4[it];
+            const int pos = row0 + rr;
+            if (FIND_BAD) {
+                // a byte of `good` is zero where the row is a read base of class 0 (or, bad_is_non_acgt, of class 5 too)
+                unsigned good = bad_is_non_acgt ? select_bytes8(0x00000001u, 0x01010100u, cls) : cls;
+                if (pos < 0) good |= pos < -3 ? 0xFFFFFFFFu : ~(0xFFFFFFFFu << (8 * -pos));
+                const unsigned bad = ~nonzero_bytes(good) & 0x80808080u;
+                if (bad) atomicMin(&first_bad[2 * p], pos + (__builtin_ctz(bad) >> 3));
+            }
+            // row_key_step: every score of row q of a lane also carries (15 - q) * step (see below)
+            u16x2 key01 = u16x2{0, 0}, key23 = u16x2{0, 0};
+            if (row_key_step != 0) {
+                const int q0 = rr % K, q1 = (rr + 1) % K, q2 = (rr + 2) % K, q3 = (rr + 3) % K;
+                key01 = u16x2{(unsigned short)(row_key_step * (15 - q0)), (unsigned short)(row_key_step * (15 - q1))};
+                key23 = u16x2{(unsigned short)(row_key_step * (15 - q2)), (unsigned short)(row_key_step * (15 - q3))};
+            }
+            unsigned char *dst = prof + p * geo::kPairStride + 2 * rr;          // row_offset(rr / K, rr % K) == 2 rr
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                unsigned lo_lo, lo_hi, hi_lo, hi_hi;
+                table(c, 0, lo_lo, lo_hi);
+                table(c, 8, hi_lo, hi_hi);
+                const unsigned lows = select_bytes8(lo_hi, lo_lo, cls), highs = select_bytes8(hi_hi, hi_lo, cls);
+                const u16x2 s01 = __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(highs, lows, 0x05010400u)) + key01;
+                const u16x2 s23 = __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(highs, lows, 0x07030602u)) + key23;
+                unsigned *out = reinterpret_cast<unsigned *>(dst + c * geo::kPairs * geo::kPairStride);
+                out[0] = __builtin_bit_cast(unsigned, s01);
+                out[1] = __builtin_bit_cast(unsigned, s23);
+            }
+            p += kItemPairs; rr += kItemRows;
+            if (rr >= geo::kRows) { rr -= geo::kRows; ++p; }
+        }
+    }
+    if (live && !rd_staged) {
 #pragma unroll
         for (int i = 0; i < 2 * K; ++i) {
             const int idx = lane + kWave * i;
@@ -350,6 +465,8 @@ __device__ __forceinline__ bool wave_setup(const uint8_t *reads, const uint8_t *
                 *reinterpret_cast<short *>(prof + c * geo::kPairs * geo::kPairStride + off) = sc;
             }
         }
+    }
+    if (live) {
         for (int idx = lane; idx < geo::kPairStride / 4; idx += kWave) {          // dword idx: rows 2 idx, 2 idx + 1
             const unsigned lo = (unsigned short)(zero_score + row_key_step * (15 - (2 * idx) % K));
             const unsigned hi = (unsigned short)(zero_score + row_key_step * (15 - (2 * idx + 1) % K));
@@ -369,18 +486,6 @@ __device__ __forceinline__ bool wave_setup(const uint8_t *reads, const uint8_t *
     w.pair0 = pair0;
     w.last = last;
     return live;
-}
-
-typedef __attribute__((address_space(3))) const unsigned lds_cu32;
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) const u32x2 lds_cu32x2;
-typedef __attribute__((address_space(3))) const u32x4 lds_cu32x4;
-typedef __attribute__((address_space(3))) const unsigned char lds_cu8;
-
-// LDS byte offset of a pointer into the dynamic shared array
-__device__ __forceinline__ unsigned lds_offset(const void *p) {
-    return (unsigned)(size_t)(__attribute__((address_space(3))) const void *)p;
 }
 
 // K/2 dwords starting at LDS byte offset `addr`, with the widest loads the lane stride allows
@@ -537,7 +642,11 @@ score_kernel(const ScoreArgs args) {
     // ---- per-lane constants (LDS byte offsets) ----
     const unsigned lmask = l == 0 ? 0u : 0xFFFFFFFFu;            // group leader: row-0 border
     const unsigned lane_base = lds_offset(w.prof) + l * geo::kLaneBytes;     // + slab * kPairStride
-    unsigned code_addr = lds_offset(w.refc) + grp * args.refc_stride - 2 * l;   // + 2 per step
+    // Smith-Waterman starts the sweep at the first lane that owns a row of the read: the `lead` lanes above it hold
+    // padding rows only, whose cells are zero at every column, so every lane simply works `lead` columns further right
+    // (lane l at step t: column t - l + lead) and the sweep is `lead` steps shorter.
+    const int lead = (ALG == kAlgSW && G * K > args.R) ? (G * K - args.R) / K : 0;
+    unsigned code_addr = lds_offset(w.refc) + grp * args.refc_stride - 2 * (l - lead);   // + 2 per step
 
     s16x2 g_read, g_ref, o_read, e_read, o_ref, e_ref;
     if (ALG == kAlgSW) {           // magnitudes for the unsigned floor-at-zero subtract
@@ -602,7 +711,7 @@ score_kernel(const ScoreArgs args) {
         cb_next = *(lds_cu8 *)(code_addr + 3);
     }
 
-    // One step of the skewed sweep.  MASKED steps EXEC-mask lanes whose column is outside
+    // One step of the skewed sweep.  MASKED steps (NW variant only) EXEC-mask lanes whose column is outside
     // [0, F) (pipeline fill and drain); in the steady phase every lane is inside.
     // TRACK selects how a step feeds the running SW maximum: kTrackAll = every diag+S of the step;
     // in the steady phase of the shared-gap kernel steps go in pairs -- the first adds nothing
@@ -811,23 +920,44 @@ score_kernel(const ScoreArgs args) {
         code_addr += 2;
     };
 
-    const int steps = F + G - 1;
-    const int fill_end = G - 1 < steps ? G - 1 : steps;
-    const int steady_end = F > fill_end ? F : fill_end;
-    int t = 0;
     using all_t = std::integral_constant<int, kTrackAll>;
     using first_t = std::integral_constant<int, (SYM && ALG == kAlgSW) ? kTrackNone : kTrackAll>;
     using second_t = std::integral_constant<int, (SYM && ALG == kAlgSW) ? kTrackPair : kTrackAll>;
-    auto single = [&](auto masked_tag) __attribute__((always_inline)) { step(masked_tag, all_t{}, S0, S1); };
-    for (; t < fill_end; ++t) single(std::true_type{});
-    {                                          // two steps per trip: loop-carried registers swap roles
-        for (; t + 1 < steady_end; t += 2) {   // instead of being copied (+4 % SW, +10 % NW linear,
-            step(std::false_type{}, first_t{}, S0, S1);    // +4 % affine together with the pipelined fetch)
-            step(std::false_type{}, second_t{}, S1, S0);
+    if constexpr (ALG == kAlgSW) {
+        // Smith-Waterman needs no mask, from the first step to the last.  A lane left of column 0 reads zero-slab codes
+        // (the pad), starts from all-zero registers and is handed zeros by the lane above, which is at the same column
+        // one step earlier: its cells stay zero (half-float affine forms: its gap registers go negative, which the zero
+        // floor of E hides exactly as at column 0).  A lane right of column F-1 reads zero-slab codes again -- padding
+        // or N bases up to the batch's F, then the pad: every diag + S it offers the maximum is an H that exists
+        // already, and it hands values only to lanes that are past the end as well.  So the whole sweep is ONE loop of
+        // two-step trips and, where the step count is odd, one more step (a step rounded up instead would do as well,
+        // but the compiler schedules the loop two VALU instructions per trip dearer without the step behind it).
+        // Codes are read at most (last step) + 2 (prefetch) columns past F-1 and G-1 columns before column 0.
+        static_assert(G - 1 + 1 + 2 <= kCodePad, "the unmasked sweep and its prefetch stay inside the code pad");
+        const int steps = F + G - 1 - lead;
+        int t = 0;
+        for (; t + 1 < steps; t += 2) {        // two steps per trip: loop-carried registers swap roles
+            step(std::false_type{}, first_t{}, S0, S1);    // instead of being copied (+4 % SW, +4 % affine
+            step(std::false_type{}, second_t{}, S1, S0);   // together with the pipelined fetch)
         }
+        if (t < steps) step(std::false_type{}, all_t{}, S0, S1);
+    } else {
+        // The NW variant's result needs every lane frozen at the last column: its fill and drain steps stay masked
+        const int steps = F + G - 1;
+        const int fill_end = G - 1 < steps ? G - 1 : steps;
+        const int steady_end = F > fill_end ? F : fill_end;
+        int t = 0;
+        auto single = [&](auto masked_tag) __attribute__((always_inline)) { step(masked_tag, all_t{}, S0, S1); };
+        for (; t < fill_end; ++t) single(std::true_type{});
+        {                                          // two steps per trip (+10 % NW linear)
+            for (; t + 1 < steady_end; t += 2) {
+                step(std::false_type{}, first_t{}, S0, S1);
+                step(std::false_type{}, second_t{}, S1, S0);
+            }
+        }
+        for (; t < steady_end; ++t) single(std::false_type{});
+        for (; t < steps; ++t) single(std::true_type{});
     }
-    for (; t < steady_end; ++t) single(std::false_type{});
-    for (; t < steps; ++t) single(std::true_type{});
 
     // ---- result ----
     s16x2 res;
