@@ -452,6 +452,9 @@ int valign_hip_set_half_float_cells(valign_hip_engine *e, int mode);
  * device-resident call of n pairs; "ran_score_cells" (f16 / int16 / int32, joined with '+' where a length-sorted call
  * mixed them) and "ran_align_fill" (the alignment path and fill kernel: fused_tag, tag_prof_key, ..., strip, strip_wide,
  * strip_ckpt) report what the engine's last score / alignment call actually launched ("none" before any);
+ * "ran_score_geometry" / "ran_align_geometry" name the compiled geometry, "GxK" (group lanes x rows per lane), whose kernel
+ * the last register-sweep score launch / the last register-path fill launch ran -- the engine's own, its latency plan's or the
+ * full geometry a fallback kernel moved the call to -- and are "none" before any and for every other route;
  * "align_ptr_bytes_per_pair" / "align_ckpt_bytes_per_pair" are the pointer-stream and checkpoint bytes a pair holds in the plan
  * of the last alignment call, "align_scratch_bytes" the pointer scratch the engine holds after it.
  * "ran_result_format" is "rows" or "cigar" for the last alignment call, "cigar_d2h_bytes" what the last

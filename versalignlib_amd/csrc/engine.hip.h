@@ -342,9 +342,11 @@ public:
     // a large call) at the engine's full shape.  What a call really launched is ran_score_cells(): the host pipeline's
     // chunks may be small enough for the latency plan, and length-sorted batches sweep each length class on a plan of its own.
     const char *score_cell_format(int alg, long long n = 0) const;
-    // what the last score / alignment call launched (describe: ran_score_cells, ran_align_fill)
+    // what the last score / alignment call launched (describe: ran_score_cells, ran_align_fill, ran_score_geometry,
+    // ran_align_geometry)
     std::string ran_score_cells() const;
     const char *ran_align_fill() const { return ran_align_fill_; }
+    static std::string ran_geometry(const Geometry *g) { return g ? std::to_string(g->G) + "x" + std::to_string(g->K) : "none"; }
     std::string ran_kernels() const;
 
     // What the pure rules of cell_rules.h read of this engine
@@ -738,6 +740,9 @@ private:
     static constexpr unsigned kRanF16 = 1, kRanInt16 = 2, kRanInt32 = 4;
     unsigned ran_score_cells_ = 0;
     const char *ran_align_fill_ = "none";
+    // ... and the (G, K) geometry whose table the kernel pointer was taken from: of the last register-sweep score launch and
+    // of the last AlignRoute::Register fill launch (null -- "none" -- before any, and for every other route)
+    const Geometry *ran_score_geo_ = nullptr, *ran_align_geo_ = nullptr;
     const char *ran_placed_ = "none";                    // what the last placed-score call ran: key / rows / strip / chain (describe)
     std::string ran_span_ = "none";                      // what the last spanned call ran: forward route / reverse route (describe)
     size_t span_scratch_bytes_ = (size_t)dbg_.value("span_scratch_bytes", 256ll << 20);      // device-resident spanned calls: scratch of one chunk

@@ -91,6 +91,7 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
     const int alg = opt & 0xF;
     if (alg > 1 || n <= 0) return false;
     ran_align_fill_ = "none";
+    ran_align_geo_ = nullptr;
     ran_result_format_ = cigar_ ? "cigar" : "rows";
     align_ckpt_bytes_per_pair_ = 0;
     const AlignRoute route = valign::align_route(rule_inputs(), alg, route_facts(false));       // (throws what the mode refuses)
@@ -118,6 +119,7 @@ bool Engine::align_device(int opt, long long n, const uint8_t *d_reads, const ui
     align_ptr_bytes_per_pair_ = (long long)(bytes_per_pp / 2);
     const void *fn = plan.geo->fill[alg][fc.kernel];
     ran_align_fill_ = ran_fill_name(route, fc.kernel);
+    ran_align_geo_ = plan.geo;
     const int block_lds = plan.lds.total * plan.waves_per_block;
     if (block_lds > kDefaultBlockLds)
         hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, block_lds),
@@ -241,6 +243,7 @@ bool Engine::align_fused(int alg, long long n, const uint8_t *d_reads, const uin
     }
     const void *fn = best->kernel[alg];
     ran_align_fill_ = ran_fill_name(AlignRoute::Fused);
+    ran_align_geo_ = nullptr;
     ran_result_format_ = cigar_ ? "cigar" : "rows";
     align_ptr_bytes_per_pair_ = (long long)best->G * best_blocks * best->K * 4 / 2;
     if (best_total > kDefaultBlockLds)
@@ -414,6 +417,7 @@ void Engine::align_host(int opt, int n, const char *const *reads, const char *co
     if (alg > 1 || n <= 0) return;
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ran_align_fill_ = "none";
+    ran_align_geo_ = nullptr;
     const int AL = R_ + F_;
     const size_t per_pair = (size_t)3 * AL + 8;
     // (row strips run chunk after chunk on one pointer scratch: chunks that fill the device -- 2 000 pairs-of-pairs and more --

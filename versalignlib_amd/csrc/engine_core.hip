@@ -111,7 +111,8 @@ std::string Engine::describe(int opt, long long n) const {
              "\"band_alignments\": %d, \"band_nw\": %d, \"band_placed\": %d, \"align_ptr_bytes_per_pair\": %lld, \"trace_checkpoints\": %d, "
              "\"align_ckpt_bytes_per_pair\": %lld, \"align_scratch_bytes\": %lld, \"ran_result_format\": \"%s\", "
              "\"cigar_d2h_bytes\": %lld, \"cigar_rows_scratch_bytes\": %lld, \"ran_placed\": \"%s\", "
-             "\"ran_span\": \"%s\", \"span_ref_length\": %lld, \"span_scratch_bytes\": %lld}",
+             "\"ran_span\": \"%s\", \"span_ref_length\": %lld, \"span_scratch_bytes\": %lld, "
+             "\"ran_score_geometry\": \"%s\", \"ran_align_geometry\": \"%s\"}",
              arch_.c_str(), device_, opt & 0xF, sc_.affine ? 1 : 0, plan_.geo->G, plan_.geo->K,
              plan_.geo->G * plan_.geo->K, plan_.pairs_per_wave, plan_.waves_per_block, plan_.lds.total,
              plan_.lds.total * plan_.waves_per_block, F_ + plan_.geo->G - 1, n > 0 ? (n + ppb - 1) / ppb : 0,
@@ -123,7 +124,8 @@ std::string Engine::describe(int opt, long long n) const {
              host_stats_.drain_ms, ran_score_cells().c_str(), ran_align_fill_, band_alignments(), band_nw(), band_placed(), align_ptr_bytes_per_pair_, trace_checkpoints(),
              align_ckpt_bytes_per_pair_, (long long)d_ptr_.bytes(), ran_result_format_, cigar_d2h_bytes_,
              (long long)(d_cig_rows_[0].bytes() + d_cig_rows_[1].bytes()), ran_placed_,
-             ran_span_.c_str(), span_ref_length(rule_inputs()), (long long)span_[kSlots].bytes());
+             ran_span_.c_str(), span_ref_length(rule_inputs()), (long long)span_[kSlots].bytes(),
+             ran_geometry(ran_score_geo_).c_str(), ran_geometry(ran_align_geo_).c_str());
     return buf;
 }
 

@@ -14,6 +14,7 @@ void Engine::score_device(int opt, long long n, const uint8_t *d_reads, const ui
     if (length_sorted) {            // (a call of its own, or score_host's direct one)
         host_stats_ = HostStats{};
         ran_score_cells_ = 0;
+        ran_score_geo_ = nullptr;
     }
     if (score_width_ == 16 && !score_int16_ok(alg))
         throw std::runtime_error("shape x scoring can leave the int16 range of the DP cells (read_length " +
@@ -79,6 +80,7 @@ void Engine::launch_score(const LaunchPlan &plan, int alg, int R, int F, long lo
     const int gaps = score_gap_form(rule_inputs(), alg, R, F, plan.geo->G * plan.geo->K);
     const void *fn = plan.geo->kernel[alg][gaps];
     ran_score_cells_ |= gap_form_f16(gaps) ? kRanF16 : kRanInt16;
+    ran_score_geo_ = plan.geo;
     const int block_lds = plan.lds.total * plan.waves_per_block;
     if (block_lds > kDefaultBlockLds)
         hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, block_lds),
@@ -110,6 +112,7 @@ void Engine::score_host(int opt, int n, const char *const *reads, const char *co
     if (alg > 1 || n <= 0) return;
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ran_score_cells_ = 0;
+    ran_score_geo_ = nullptr;
     const size_t per_pair = (size_t)R_ + F_;
     // Long reads on row strips: their launches follow one another on one stream (the strips' boundary rows are one scratch) and
     // a 48 MB chunk of 10 kbp pairs is 1 200 waves for 3 500 resident ones -- each launch runs at a third of the device.

@@ -16,6 +16,7 @@
 // Placed scores (placed_kernels.hip.h) add 68 instances, listed by placed_kernel<G, K, FULL> there: the symmetric gap forms with
 // the lane key on the 15 geometries of up to 16 rows per lane, the asymmetric ones on the five full geometries among them, and
 // the four per-row forms on the six full geometries and 64 x 24.  VALIGN_PLACED_KERNELS instantiates a geometry's table.
+// Two instances are compiled but unselectable: SW tag_prof_key on 64 x 24 and 64 x 32 (prof_key_ok, cell_rules.h, needs K <= 16).
 #pragma once
 
 #include "dp_kernels.hip.h"
