@@ -29,7 +29,8 @@
 //     byte loads.
 //   * Recurrence variants (GAPS), packed instructions per register (= per two cells) incl. the
 //     profile merge: two linear gap scores 6 + maximum tracking, one shared gap score 5 +
-//     tracking, affine 10, affine with the same open/extend for both directions 9.  Where every
+//     tracking, affine 10 + tracking, affine with the same open/extend for both directions 9 + tracking (Smith-Waterman:
+//     9 on gap SOURCES, tracked once per two steps -- 9 + (K + 1) / 2K; see score_kernel's step).  Where every
 //     cell provably stays a small integer the same recurrences run on packed HALF FLOATS, which
 //     gfx950 gives a three-operand maximum (v_pk_maximum3_f16) and a free [0, 1] clamp on the
 //     add: shared-gap linear SW 4 (keeps (h, max(h + g, 0)) scaled by 2^-10), symmetric affine 8,
@@ -572,6 +573,7 @@ score_kernel(const ScoreArgs args) {
     constexpr bool SYM = GAPS == kGapSym;
     constexpr bool LINF16 = GAPS == kGapSymF16;
     constexpr bool AFFSYM = GAPS == kGapAffineSym;
+    constexpr bool SOURCES = AFFSYM && ALG == kAlgSW;      // int16 symmetric affine SW carries gap sources (see the step)
     const int lane = threadIdx.x & (kWave - 1);
     const int grp = lane / G;
     const int l = lane % G;
@@ -666,9 +668,10 @@ score_kernel(const ScoreArgs args) {
     const f16x2 o_half = f16x2{open_h, open_h}, e_half = f16x2{ext_h, ext_h}, zero_half = f16x2{(_Float16)0, (_Float16)0};
     const f16x2 o_read_half = f16x2{open_rd, open_rd}, e_read_half = f16x2{ext_rd, ext_rd};
 
-    // Hl: H of the previous column; El: E of the previous column; HOl (symmetric affine only):
+    // Hl: H of the previous column; El: E of the previous column; HOl (symmetric affine, NW variant and half floats):
     // H - open of the previous column, which feeds E of this column (and, within a column, F of
-    // the next row), so the subtract is done once per cell instead of twice.
+    // the next row), so the subtract is done once per cell instead of twice.  Int16 symmetric affine Smith-Waterman
+    // (SOURCES) keeps the best gap SOURCE of the row in El instead and has no HOl.
     s16x2 Hl[K], El[K], HOl[K];
 #pragma unroll
     for (int q = 0; q < K; ++q) {
@@ -717,7 +720,8 @@ score_kernel(const ScoreArgs args) {
     // in the steady phase of the shared-gap kernel steps go in pairs -- the first adds nothing
     // (kTrackNone), the second adds every max(left, up) plus its last row (kTrackPair): the "left"s
     // are all cells of the first step, the "up"s all cells of the second but the last row.  K + 1
-    // maxima per two steps instead of 2K.
+    // maxima per two steps instead of 2K.  The gap-source form of symmetric affine Smith-Waterman (SOURCES) does the
+    // same with its max(XE, XF).
     auto step = [&](auto masked_tag, auto track_tag, s16x2 (&S)[K], s16x2 (&Snext)[K]) __attribute__((always_inline)) {
         constexpr bool MASKED = decltype(masked_tag)::value;
         constexpr int TRACK = decltype(track_tag)::value;
@@ -729,7 +733,7 @@ score_kernel(const ScoreArgs args) {
         }
         if (TILT) up0 = as_pk(as_u32(up0) | as_u32(top_row));         // (zero in every lane but the group leader)
         s16x2 fup0 = border_f;
-        if (AFFINE) {
+        if (AFFINE && !SOURCES) {          // (the gap-source form fetches its own, behind its first diag + S)
             if (G == 16 && ALG == kAlgSW) {      // (row_shr:1: the group's first lane reads 0, the Smith-Waterman border)
                 fup0 = as_pk((unsigned)__builtin_amdgcn_update_dpp(0, (int)as_u32(f_last), 0x111, 0xF, 0xF, true));
             } else if (G != 16) {
@@ -835,6 +839,40 @@ score_kernel(const ScoreArgs args) {
                 best = bits(bestf);
                 h_last = bits(h);
                 f_last = bits(f);
+            } else if (SOURCES) {
+                // Gap SOURCES instead of gap scores: El[q] holds XE, the best source of a horizontal gap in row q so
+                // far (max over earlier columns k of H(q, k) - (j - 1 - k) ext), xf the same thing down the column (XF),
+                // so E = XE - open and F = XF - open share one maximum and one subtract:
+                //   g = max(XE, XF);  h = max(diag + S, g - open);  XE' = max(XE - ext, h);  XF' = max(XF - ext, h)
+                // -- perm, add, 3 sub, 4 max: 9 packed instructions per register.  g is at least the cell to the left and
+                // the cell above and never more than a cell that exists, so it feeds the running maximum as max(left, up)
+                // does in the shared-gap kernel: kTrackNone / kTrackPair.  The chain xf -> g -> y -> h -> xf down the
+                // column is strictly dependent; the next row's diag + S (which reads the OLD Hl[q]), the two extension
+                // subtracts and the tracking are written between its links.
+                s16x2 d_cur = diag0 + S[0];
+                // XF of the lane above, 0 in the group's first lane.  Fetched here, behind the first add: at the head of
+                // the step the DPP move follows the register's initialisation before the loop too closely, and the wait
+                // state that costs lands inside the loop.
+                s16x2 xf = as_pk(group_prev_or_zero<G>(as_u32(f_last), lmask)), h = pk(0);
+#pragma unroll
+                for (int q = 0; q < K; ++q) {
+                    const s16x2 g = pk_max(El[q], xf);
+                    s16x2 d_next = pk(0);
+                    if (q + 1 < K) d_next = Hl[q] + S[q + 1];
+                    const s16x2 y = pk_sub_floor0(g, o_ref);
+                    const s16x2 a = pk_sub_floor0(El[q], e_ref);
+                    if (TRACK == kTrackAll) best = pk_max(best, d_cur);   // max = a diagonal arrival
+                    if (TRACK == kTrackPair) best = pk_max(best, g);
+                    h = pk_max(d_cur, y);
+                    const s16x2 b = pk_sub_floor0(xf, e_ref);
+                    Hl[q] = h;
+                    El[q] = pk_max(a, h);
+                    xf = pk_max(b, h);
+                    d_cur = d_next;
+                }
+                if (TRACK == kTrackPair) best = pk_max(best, h);
+                h_last = h;
+                f_last = xf;
             } else if (SYM) {
                 // h = max(diag + S, max(left, up) - g): one subtract for both gap directions.  The chain
                 // max -> sub -> max down the column is strictly dependent; the next row's diag + S (which
@@ -921,8 +959,8 @@ score_kernel(const ScoreArgs args) {
     };
 
     using all_t = std::integral_constant<int, kTrackAll>;
-    using first_t = std::integral_constant<int, (SYM && ALG == kAlgSW) ? kTrackNone : kTrackAll>;
-    using second_t = std::integral_constant<int, (SYM && ALG == kAlgSW) ? kTrackPair : kTrackAll>;
+    using first_t = std::integral_constant<int, ((SYM && ALG == kAlgSW) || SOURCES) ? kTrackNone : kTrackAll>;
+    using second_t = std::integral_constant<int, ((SYM && ALG == kAlgSW) || SOURCES) ? kTrackPair : kTrackAll>;
     if constexpr (ALG == kAlgSW) {
         // Smith-Waterman needs no mask, from the first step to the last.  A lane left of column 0 reads zero-slab codes
         // (the pad), starts from all-zero registers and is handed zeros by the lane above, which is at the same column
