@@ -334,11 +334,12 @@ int valign_hip_align_cigar_host(valign_hip_engine *e, int opt, int n, const char
  *                           cell (the arg-max of one row) are different cells in the reference: "placed" has no single meaning
  *   band_width > 0 ........ banded scores -- unless valign_hip_set_band_placed(e, 1) asks for them, below
  *   traceback_policy = 1 .. the SSE/AVX tie-breaks
- *   score_width = 32, or a shape x scoring whose Smith-Waterman cells could leave int16 (the rule of the score path)
+ *   score_width = 32, or a shape x scoring whose Smith-Waterman cells could leave int16 (the rule of the score path) --
+ *                           unless valign_hip_set_placed_wide(e, 1) asks for them, below
  * "ran_placed" of valign_hip_describe says what the last call ran: "key" (register sweep, one end-cell key per lane), "rows"
  * (register sweep, a first-arg-max per row: more than 16 rows per lane, or scores too large for the key), "strip" (reads of
  * more than 1 024 rows or shapes no register geometry holds: the row strips' pointer-free forward pass), "chain" (band_placed,
- * below), "none".                                                                                                            */
+ * below), "wide" (placed_wide, below), "none".                                                                               */
 typedef struct {                     /* 12 bytes */
     int32_t score, read_end, ref_end;
 } valign_hip_placed;
@@ -368,6 +369,33 @@ typedef struct {                     /* 12 bytes */
  * ((min(R, F) x match + 1) << 4 beyond int32) could overflow.  tests/placed_band_ref.py restates the definition in numpy.
  * Other values than 0 / 1 are refused.                                                                                      */
 int valign_hip_set_band_placed(valign_hip_engine *e, int on);
+
+/* Placed and spanned scores on int32 cells (key placed_wide; flat API only).  0 (default): every call runs or is refused exactly
+ * as above.  1: valign_hip_score_placed_device / _host and valign_hip_score_span_device / _host also accept the two kinds of
+ * unbanded Smith-Waterman call the list above refuses for their cells -- calls with score_width = 32, and calls with
+ * score_width = 0 whose shape x scoring could leave int16 (min(R, F) x match + 1 > 32000: 20 kbp x 20 kbp at match 2, 10 kbp x
+ * 10 kbp at match 5) -- and runs them on a pointer-free int32 sweep of row strips ("ran_placed": "wide"): one int32 boundary
+ * row per pair (two with affine gaps) and 8 bytes per pair of end cell between its launches, nothing else -- no pointer
+ * stream, no walk.  DEFINITION: the record is the one defined above, unchanged --
+ *   score ....... the Smith-Waterman maximum of the pair as int32.  The record does NOT saturate at 32767: it equals
+ *                 valign_hip_score_device's value wherever that is below 32767 and valign_hip_aln.score of
+ *                 valign_hip_align_cigar_device everywhere.
+ *   read_end, ref_end
+ *                 (read_end - 1, ref_end - 1) is the row-major first cell that holds the maximum
+ *                 (src/Kernels/default/DefaultKernel.cpp:252-256); 0-based, half-open.
+ *   empty ....... a pair whose maximum is 0 returns {0, 0, 0} (spanned: five zeros).
+ *   spanned ..... the placed record plus the begin cell by the reversed-sweep rule below; the reverse sweep's engine of shape
+ *                 (read_length, span_ref_length) carries the key and decides its own route.
+ * WHAT THE KEY DOES NOT CHANGE: calls inside the int16 range with score_width 0 or 16 keep their routes ("key", "rows",
+ * "strip") and kernels; score_width = 16 means "int16 or refuse" and stays refused, with the text above, on a shape x scoring
+ * that can leave int16; opt & 0xF == 1, traceback_policy = 1 and band_width > 0 are refused (or run on the chain under
+ * band_placed) as above -- the key is not read under a band.
+ * REFUSED under placed_wide = 1: scores so large that the int32 cells could overflow, (R + F + 2) x |score| >= 2^28, with a
+ * message that begins "placed_wide:".  Other values than 0 / 1 are refused.
+ * "ran_placed" reads "wide" after such a call; "ran_span" joins the forward and the reverse route, so it may read "wide/wide",
+ * "wide/key", ...; "placed_wide" of valign_hip_describe is the key and "placed_scratch_bytes" the boundary rows and end cells
+ * the engine holds for the strip and wide routes.  Calls of one engine that take the route belong on one stream.            */
+int valign_hip_set_placed_wide(valign_hip_engine *e, int on);
 
 /* Device-resident: d_placed = n records.  Asynchronous on hip_stream, uses no pointer scratch and writes nothing but d_placed
  * (the strip path keeps its boundary rows and end cells in an engine-owned scratch: calls of one engine that take it belong
@@ -408,7 +436,7 @@ int valign_hip_score_placed_host(valign_hip_engine *e, int opt, int n, const cha
  * unclipped records.  tests/span_ref.py restates the definition in numpy, unclipped.
  * REFUSED with a non-zero return and a message in valign_hip_last_error: everything valign_hip_score_placed_device refuses
  * without a band, with the same texts (opt & 0xF == 1, traceback_policy = 1, score_width = 32, a shape x scoring whose cells
- * could leave int16) -- and band_width > 0 WHATEVER band_placed says: the chain's block windows are not symmetric under
+ * could leave int16; the last two unless placed_wide = 1, above) -- and band_width > 0 WHATEVER band_placed says: the chain's block windows are not symmetric under
  * reversal, so a reversed banded sweep would be another band.  opt & 0xF > 1 does nothing, as everywhere.
  * "ran_span" of valign_hip_describe names the forward and the reverse route of the last call, joined ("key/key", "strip/strip",
  * ...; "none" before any, or when it was refused); "ran_placed" then reports the forward route; "span_ref_length" is the bound
@@ -459,8 +487,8 @@ int valign_hip_set_half_float_cells(valign_hip_engine *e, int mode);
  * of the last alignment call, "align_scratch_bytes" the pointer scratch the engine holds after it.
  * "ran_result_format" is "rows" or "cigar" for the last alignment call, "cigar_d2h_bytes" what the last
  * valign_hip_align_cigar_host call copied back, "cigar_rows_scratch_bytes" the rows scratch of the compact format.
- * "ran_placed" is what the last placed-score call ran: key / rows / strip / chain ("none" before any, or when it was
- * refused); "band_placed" is the key of valign_hip_set_band_placed.  "ran_span", "span_ref_length" and "span_scratch_bytes"
+ * "ran_placed" is what the last placed-score call ran: key / rows / strip / chain / wide ("none" before any, or when it was
+ * refused); "band_placed" is the key of valign_hip_set_band_placed, "placed_wide" that of valign_hip_set_placed_wide.  "ran_span", "span_ref_length" and "span_scratch_bytes"
  * belong to the spanned scores, above.                                                                                         */
 int valign_hip_describe(valign_hip_engine *e, int opt, long long n, char *buf, int cap);
 

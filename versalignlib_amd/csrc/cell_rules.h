@@ -188,7 +188,7 @@ constexpr int kPlacedKeyMaxK = 16;
 // Reads of more rows than this take the row strips, as alignments do (Engine::route_facts)
 constexpr int kPlacedStripRows = 1024;
 
-enum class PlacedRoute { Refused, Key, Rows, Strip, Chain };
+enum class PlacedRoute { Refused, Key, Rows, Strip, Chain, Wide };
 
 // band_placed = 1 under a band: the banded block chain (band_kernels.hip.h) tracks one key per lane on its int32 cells,
 // `diagonal candidate << kBandPlacedKeyBits | (15 - row of the lane's 16-row block)`, compared as signed integers: the largest
@@ -208,6 +208,7 @@ struct PlacedFacts {
     bool long_plan = false;         // no register geometry holds the shape (the alignment plan is the long-read one)
     bool band_placed = false;       // band_placed = 1: under a band the call runs on the block chain, on the chain's band
     bool chain_usable = false;      // band_chain_plan(...).usable for this band_width (long_plan.h)
+    bool placed_wide = false;       // placed_wide = 1: unbanded calls on int32 cells run on the pointer-free int32 sweep
 };
 
 struct PlacedChoice {
@@ -220,7 +221,9 @@ struct PlacedChoice {
 // `value << key_bits | (2^key_bits - 1 - row)` per lane, where the largest possible value keeps it inside int16 (the bound of
 // lane_key_ok, with this form's bits); Rows: a first-arg-max per row -- more than 16 rows per lane, or larger scores.  Chain:
 // the banded block chain under band_placed = 1 (above), whatever the read length -- refused where the chain has no plan,
-// never sent to the strips.
+// never sent to the strips.  Wide: placed_wide = 1, unbanded -- the int32 sweep (placed_wide_kernels.hip.h) exactly where the rule
+// would otherwise refuse for score_width = 32 or because the cells can leave int16 under score_width = 0 (16 means "int16 or
+// refuse" and stays refused); whatever the read length, one pair per register.  Refused only where int32 cells could overflow.
 inline PlacedChoice placed_choice(const RuleInputs &in, int alg, const PlacedFacts &f, int G, int K) {
     PlacedChoice c;
     (void)G;
@@ -249,6 +252,15 @@ inline PlacedChoice placed_choice(const RuleInputs &in, int alg, const PlacedFac
         c.reason = "placed scores are not built for score_width = 32 (int32 cells)";
     else if (!int16_range_ok(in, kAlgSW, true, false, 0))
         c.reason = "placed scores run on int16 cells: shape x scoring can leave their range";
+    if (c.reason[0] && alg == kAlgSW && f.band_width <= 0 && !in.sse_policy && f.placed_wide && f.score_width != 16) {
+        // one of the two int16 refusals just above, with the key on: int32 cells instead
+        c.reason = "";
+        if (int32_refused(in))
+            c.reason = "placed_wide: shape x scoring can leave the int32 range of the DP cells";
+        else
+            c.route = PlacedRoute::Wide;
+        return c;
+    }
     if (c.reason[0]) return c;
     if (f.long_plan || (!f.forced && in.R > kPlacedStripRows)) {
         c.route = PlacedRoute::Strip;
@@ -267,7 +279,7 @@ inline PlacedChoice placed_choice(const RuleInputs &in, int alg, const PlacedFac
 
 // describe()'s name of what the last placed call ran (ran_placed)
 inline const char *ran_placed_name(PlacedRoute r) {
-    static const char *const names[] = {"none", "key", "rows", "strip", "chain"};
+    static const char *const names[] = {"none", "key", "rows", "strip", "chain", "wide"};
     return names[(int)r];
 }
 

@@ -248,6 +248,14 @@ public:
         band_placed_ = on == 1;
     }
     int band_placed() const { return band_placed_ ? 1 : 0; }
+    // Placed and spanned scores on int32 cells (opt-in; include/valign_hip.h has the definition): 1 = unbanded Smith-Waterman
+    // calls that score_width = 32 or the int16 range rule would refuse run on the pointer-free int32 sweep
+    // (placed_wide_kernels.hip.h); 0 = they are refused (default).  Calls inside the int16 range keep their routes.
+    void set_placed_wide(int on) {
+        if (on != 0 && on != 1) throw std::runtime_error("placed_wide must be 0 or 1");
+        placed_wide_ = on == 1;
+    }
+    int placed_wide() const { return placed_wide_ ? 1 : 0; }
     // Checkpointed traceback of long-read alignments (opt-in; ckpt_plan.h): 1 = calls that take the plain row strips (unbanded,
     // int16 cells, traceback_policy 0; both algorithms, linear and affine gaps) keep one boundary row per strip and ONE strip's
     // pointer region instead of every pointer, and re-fill strip after strip along the walk -- identical results, a scratch that
@@ -466,6 +474,9 @@ public:
     const LaunchPlan &placed_plan_for(int alg, PlacedChoice &choice, int &gaps);
     void score_placed_strips(long long n, const uint8_t *d_reads, const uint8_t *d_refs, PlacedRec *d_placed, hipStream_t stream);
     void launch_placed_records(const EndCell *d_ends, PlacedRec *d_placed, long long n, hipStream_t stream);
+    // placed_wide = 1 (PlacedRoute::Wide): the int32 sweep strip after strip, then the records -- score_placed_strips' scratch,
+    // sized for one int32 row set per pair
+    void score_placed_wide(long long n, const uint8_t *d_reads, const uint8_t *d_refs, PlacedRec *d_placed, hipStream_t stream);
     const char *ran_placed() const { return ran_placed_; }
 
     // ---- spanned Smith-Waterman scores (valign_hip.h: valign_hip_span; engine_span.hip) ----
@@ -694,6 +705,7 @@ private:
     bool band_alignments_ = false;
     bool band_nw_ = false;
     bool band_placed_ = false;
+    bool placed_wide_ = false;
     bool trace_checkpoints_ = false;
     int score_width_ = 0;
     int ragged_ = 0, force_g_ = 0, force_k_ = 0;
@@ -743,7 +755,7 @@ private:
     // ... and the (G, K) geometry whose table the kernel pointer was taken from: of the last register-sweep score launch and
     // of the last AlignRoute::Register fill launch (null -- "none" -- before any, and for every other route)
     const Geometry *ran_score_geo_ = nullptr, *ran_align_geo_ = nullptr;
-    const char *ran_placed_ = "none";                    // what the last placed-score call ran: key / rows / strip / chain (describe)
+    const char *ran_placed_ = "none";                    // what the last placed-score call ran: key / rows / strip / chain / wide (describe)
     std::string ran_span_ = "none";                      // what the last spanned call ran: forward route / reverse route (describe)
     size_t span_scratch_bytes_ = (size_t)dbg_.value("span_scratch_bytes", 256ll << 20);      // device-resident spanned calls: scratch of one chunk
     long long span_staged_pairs_ = 0;

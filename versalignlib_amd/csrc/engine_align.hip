@@ -376,7 +376,8 @@ void Engine::score_placed_strips(long long n, const uint8_t *d_reads, const uint
     hip_check(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
     const long long chunk = strip_chunk_pairs(strip_scratch_cap(free_b + d_placed_rows_.bytes(), scratch_cap_mb_), bytes_per_pp, n);
     const long long waves = chunk / 2;
-    if ((size_t)waves * bytes_per_pp > d_placed_rows_.bytes() || sizeof(EndCell) * (size_t)chunk > d_placed_ends_.bytes()) {
+    if ((size_t)waves * bytes_per_pp > d_placed_rows_.bytes() || sizeof(EndCell) * (size_t)chunk > d_placed_ends_.bytes() ||
+        sizeof(int) * 2 * (size_t)chunk > d_placed_bad_.bytes()) {       // (score_placed_wide grows the first two only)
         hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");          // nothing may still read the old scratch
         d_placed_rows_.reserve((size_t)waves * bytes_per_pp, "placed-score boundary rows");
         d_placed_ends_.reserve(sizeof(EndCell) * (size_t)chunk, "placed-score end cells");

@@ -110,7 +110,7 @@ std::string Engine::describe(int opt, long long n) const {
              "\"score_cells\": \"%s\", \"direct_call\": %d, \"packed_classes\": %d, \"direct_out\": %d, \"band_block_rows\": %d, \"band_col_align\": %d, \"band_waves_per_cu\": %d, \"band_lds_per_wave\": %d, \"band_cells_per_pair\": %lld, \"long_strip_rows\": %d, \"d2h_row_mb\": %.1f, \"full_row_mb\": %.1f, \"host_gather_ms\": %.3f, \"host_classify_ms\": %.3f, \"host_wait_ms\": %.3f, \"host_drain_ms\": %.3f, \"ran_score_cells\": \"%s\", \"ran_align_fill\": \"%s\", "
              "\"band_alignments\": %d, \"band_nw\": %d, \"band_placed\": %d, \"align_ptr_bytes_per_pair\": %lld, \"trace_checkpoints\": %d, "
              "\"align_ckpt_bytes_per_pair\": %lld, \"align_scratch_bytes\": %lld, \"ran_result_format\": \"%s\", "
-             "\"cigar_d2h_bytes\": %lld, \"cigar_rows_scratch_bytes\": %lld, \"ran_placed\": \"%s\", "
+             "\"cigar_d2h_bytes\": %lld, \"cigar_rows_scratch_bytes\": %lld, \"ran_placed\": \"%s\", \"placed_wide\": %d, \"placed_scratch_bytes\": %lld, "
              "\"ran_span\": \"%s\", \"span_ref_length\": %lld, \"span_scratch_bytes\": %lld, "
              "\"ran_score_geometry\": \"%s\", \"ran_align_geometry\": \"%s\"}",
              arch_.c_str(), device_, opt & 0xF, sc_.affine ? 1 : 0, plan_.geo->G, plan_.geo->K,
@@ -123,7 +123,7 @@ std::string Engine::describe(int opt, long long n) const {
              band_blocks_per_cu_, band_lds_, (band_tables_width_ == band_width_ && band_plan_.usable) ? band_plan_.cells : 0ll, long_strip_rows_, host_stats_.d2h_row_bytes / 1e6, host_stats_.full_row_bytes / 1e6, host_stats_.gather_ms, host_stats_.classify_ms, host_stats_.wait_ms,
              host_stats_.drain_ms, ran_score_cells().c_str(), ran_align_fill_, band_alignments(), band_nw(), band_placed(), align_ptr_bytes_per_pair_, trace_checkpoints(),
              align_ckpt_bytes_per_pair_, (long long)d_ptr_.bytes(), ran_result_format_, cigar_d2h_bytes_,
-             (long long)(d_cig_rows_[0].bytes() + d_cig_rows_[1].bytes()), ran_placed_,
+             (long long)(d_cig_rows_[0].bytes() + d_cig_rows_[1].bytes()), ran_placed_, placed_wide(), (long long)(d_placed_rows_.bytes() + d_placed_ends_.bytes()),
              ran_span_.c_str(), span_ref_length(rule_inputs()), (long long)span_[kSlots].bytes(),
              ran_geometry(ran_score_geo_).c_str(), ran_geometry(ran_align_geo_).c_str());
     return buf;

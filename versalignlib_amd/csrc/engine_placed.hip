@@ -1,15 +1,16 @@
 // engine_placed.hip -- Engine: placed Smith-Waterman scores (include/valign_hip.h: valign_hip_score_placed_*): score and end
 // cell of every pair from the score sweep alone.  placed_choice (cell_rules.h) decides what a call is -- refused, the register
-// sweep with the lane key or the per-row arg-max (placed_kernels.hip.h), or the row strips (engine_align.hip) -- and this unit
-// launches it; the host-pointer path is score_host's chunk pipeline with 12-byte records on the way back.
-// placed_records_kernel (not a template) is defined in this translation unit.
+// sweep with the lane key or the per-row arg-max (placed_kernels.hip.h), the row strips (engine_align.hip), the banded chain
+// (engine_long.hip) or, under placed_wide = 1, the int32 sweep (placed_wide_kernels.hip.h) -- and this unit launches it; the host-pointer path is score_host's chunk pipeline with 12-byte records on the way back.
+// placed_records_kernel and placed_wide_records_kernel (not templates) are defined in this translation unit.
 #define VALIGN_TU_PLACED 1
 #include "engine.hip.h"
+#include "placed_wide_kernels.hip.h"
 
 namespace valign {
 
 PlacedFacts Engine::placed_facts() const {
-    return PlacedFacts{band_width_, score_width_, force_g_ != 0 || force_k_ != 0, align_base_plan().long_mode, band_placed_, band_plan_.usable && !no_band_chain_};
+    return PlacedFacts{band_width_, score_width_, force_g_ != 0 || force_k_ != 0, align_base_plan().long_mode, band_placed_, band_plan_.usable && !no_band_chain_, placed_wide_};
 }
 
 // The plan a placed call runs on: the one alignments start from where its geometry carries the kernel the rule asks for;
@@ -23,7 +24,7 @@ const LaunchPlan &Engine::placed_plan_for(int alg, PlacedChoice &choice, int &ga
     choice = placed_choice(in, alg, facts, base.geo->G, base.geo->K);
     if (choice.route == PlacedRoute::Refused) throw std::runtime_error(choice.reason);
     gaps = score_gap_form(in, kAlgSW, R_, F_, base.geo->G * base.geo->K);
-    if (choice.route == PlacedRoute::Strip || choice.route == PlacedRoute::Chain) return base;      // (neither launches on the plan)
+    if (choice.route == PlacedRoute::Strip || choice.route == PlacedRoute::Chain || choice.route == PlacedRoute::Wide) return base;      // (none launches on the plan)
     auto track_of = [](const PlacedChoice &c) { return c.route == PlacedRoute::Key ? kPlacedKey : kPlacedRows; };
     if (base.geo->placed(track_of(choice), gaps)) return base;
     if (!fallback_plan_.geo) fallback_plan_ = choose_plan(R_, F_, 0, 0, false, true);
@@ -42,6 +43,11 @@ void Engine::score_placed_device(int opt, long long n, const uint8_t *d_reads, c
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (choice.route == PlacedRoute::Strip) {
         score_placed_strips(n, d_reads, d_refs, d_placed, stream);
+        ran_placed_ = ran_placed_name(choice.route);
+        return;
+    }
+    if (choice.route == PlacedRoute::Wide) {
+        score_placed_wide(n, d_reads, d_refs, d_placed, stream);
         ran_placed_ = ran_placed_name(choice.route);
         return;
     }
@@ -82,6 +88,53 @@ void Engine::launch_placed_records(const EndCell *d_ends, PlacedRec *d_placed, l
     hip_check(hipGetLastError(), "hipLaunchKernel(placed_records_kernel)");
 }
 
+// placed_wide = 1: score_placed_strips with the int32 sweep.  8 rows per lane, the K of the int32 Smith-Waterman alignment strips;
+// per pair-of-pairs two row sets that ping-pong, each one int32 row per pair (and an F row beside it, affine) -- the wide strip
+// plan's row_bytes -- and no pointer region.  The scratch is score_placed_strips' own (a call of the other kind regrows it).
+void Engine::score_placed_wide(long long n, const uint8_t *d_reads, const uint8_t *d_refs, PlacedRec *d_placed, hipStream_t stream) {
+    constexpr int K = 8;
+    const StripMode mode{kAlgSW, sc_.affine, false, true, false, false};
+    const StripPlan plan = strip_plan(R_, F_, K, mode, kNoBand);
+    const size_t bytes_per_pp = plan.row_bytes;             // 2 slots x row_sets x row_dwords dwords
+    size_t free_b = 0, total_b = 0;
+    hip_check(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
+    const long long chunk = strip_chunk_pairs(strip_scratch_cap(free_b + d_placed_rows_.bytes(), scratch_cap_mb_), bytes_per_pp, n);
+    const long long waves = chunk / 2;
+    if ((size_t)waves * bytes_per_pp > d_placed_rows_.bytes() || sizeof(EndCell) * (size_t)chunk > d_placed_ends_.bytes()) {
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");          // nothing may still read the old scratch
+        d_placed_rows_.reserve((size_t)waves * bytes_per_pp, "placed-score boundary rows (int32)");
+        d_placed_ends_.reserve(sizeof(EndCell) * (size_t)chunk, "placed-score end cells");
+    }
+    const void *fn = sc_.affine ? (const void *)&score_placed_wide_kernel<K, true> : (const void *)&score_placed_wide_kernel<K, false>;
+    const WaveLds lds{StripLds<K>::kRing, 0, StripLds<K>::kTotal};
+    if (lds.total > kDefaultBlockLds)
+        hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds.total), "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+    const size_t set_dwords = (size_t)waves * plan.row_dwords;                    // one row of every wave
+    const size_t slot_dwords = (size_t)plan.row_sets * set_dwords;
+    for (long long begin = 0; begin < n; begin += chunk) {
+        const long long cnt = std::min(chunk, n - begin), cnt_waves = (cnt + 1) / 2;
+        for (int s = 0; s < plan.strips; ++s) {
+            StripArgs a{};
+            put_sweep(a, d_reads + (size_t)begin * R_, d_refs + (size_t)begin * F_, cnt, plan.blocks8, lds);
+            a.ends = d_placed_ends_.get();
+            a.bottom = d_placed_rows_.get() + (size_t)(s & 1) * slot_dwords;
+            a.top = d_placed_rows_.get() + (size_t)((s + 1) & 1) * slot_dwords;
+            a.top_f = a.top + set_dwords;           // (the distance is the kernel's set stride, linear gaps too)
+            a.bottom_f = a.bottom + set_dwords;
+            a.strip = s;
+            a.strips = plan.strips;
+            a.row_dwords = plan.row_dwords;
+            a.band = kNoBand;
+            void *kargs[] = {&a};
+            hip_check(hipLaunchKernel(fn, dim3((unsigned)cnt_waves), dim3(kWave), kargs, (size_t)lds.total, stream),
+                      "hipLaunchKernel(score_placed_wide_kernel)");
+        }
+        hipLaunchKernelGGL(placed_wide_records_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, (const EndCell *)d_placed_ends_.get(),
+                           d_placed + begin, cnt);
+        hip_check(hipGetLastError(), "hipLaunchKernel(placed_wide_records_kernel)");
+    }
+}
+
 void Engine::ensure_placed_staging(long long pairs) {
     if (pairs <= placed_staged_pairs_) return;
     placed_staged_pairs_ = 0;
@@ -108,7 +161,7 @@ void Engine::score_placed_host(int opt, int n, const char *const *reads, const c
     (void)placed_plan_for(alg, choice, gaps);          // (refusals leave here, before anything is staged)
     // (the chain keeps nothing between launches: its chunks run on the slots' own streams; its tables go up once, here)
     if (choice.route == PlacedRoute::Chain) sync_band_tables(streams_[0].get());
-    const bool strips = choice.route == PlacedRoute::Strip;      // their launches share the boundary rows: one stream, large chunks
+    const bool strips = choice.route == PlacedRoute::Strip || choice.route == PlacedRoute::Wide;      // their launches share the boundary rows: one stream, large chunks
     const size_t per_pair = (size_t)R_ + F_;
     const size_t chunk_bytes = strips && !dbg_.on("chunk_bytes") ? std::max<size_t>(score_chunk_bytes_, 192u << 20) : score_chunk_bytes_;
     long long chunk = per_pair ? (long long)(chunk_bytes / per_pair) : n;

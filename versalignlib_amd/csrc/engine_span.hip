@@ -17,11 +17,13 @@ Engine &Engine::span_prepare(int alg, bool &strips) {
     if (refusal.route == PlacedRoute::Refused) throw std::runtime_error(refusal.reason);
     if (!span_child_) span_child_ = std::make_unique<Engine>(device_, R_, (int)span_ref_length(in), sc_, force_g_, force_k_);
     span_child_->set_score_width(score_width_);
+    span_child_->set_placed_wide(placed_wide());
     PlacedChoice fwd, rev;
     int gaps = 0;
     (void)placed_plan_for(alg, fwd, gaps);                      // (what either sweep still refuses leaves here, before anything runs)
     (void)span_child_->placed_plan_for(alg, rev, gaps);         // the reverse sweep's rule is asked for its own shape
-    strips = fwd.route == PlacedRoute::Strip || rev.route == PlacedRoute::Strip;
+    auto shared_rows = [](const PlacedChoice &c) { return c.route == PlacedRoute::Strip || c.route == PlacedRoute::Wide; };
+    strips = shared_rows(fwd) || shared_rows(rev);
     return *span_child_;
 }
 

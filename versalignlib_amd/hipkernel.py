@@ -87,6 +87,7 @@ def lib():
         L.valign_hip_set_band_alignments.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_band_nw.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_band_placed.argtypes = [vp, ctypes.c_int]
+        L.valign_hip_set_placed_wide.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_trace_checkpoints.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_pointer_scratch_cap_mb.argtypes = [vp, ctypes.c_longlong]
         L.valign_hip_set_host_packing.argtypes = [vp, ctypes.c_int]
@@ -117,7 +118,7 @@ def lib():
 EXPORTED_SYMBOLS = (
     "spawn_alignment_kernel", "set_parameters", "set_logger", "delete_alignment_kernel",
     "valign_hip_device_count", "valign_hip_shard_range", "valign_hip_engine_create", "valign_hip_engine_destroy",
-    "valign_hip_set_traceback_policy", "valign_hip_set_pointer_scratch_cap_mb", "valign_hip_set_host_packing", "valign_hip_set_half_float_cells", "valign_hip_host_register", "valign_hip_host_unregister", "valign_hip_set_band_width", "valign_hip_set_band_alignments", "valign_hip_set_band_nw", "valign_hip_set_band_placed", "valign_hip_set_trace_checkpoints", "valign_hip_set_score_width", "valign_hip_set_ragged_batching", "valign_hip_score_device", "valign_hip_align_device", "valign_hip_score_host", "valign_hip_align_host", "valign_hip_align_cigar_device", "valign_hip_align_cigar_host", "valign_hip_score_placed_device", "valign_hip_score_placed_host", "valign_hip_score_span_device", "valign_hip_score_span_host", "valign_hip_describe",
+    "valign_hip_set_traceback_policy", "valign_hip_set_pointer_scratch_cap_mb", "valign_hip_set_host_packing", "valign_hip_set_half_float_cells", "valign_hip_host_register", "valign_hip_host_unregister", "valign_hip_set_band_width", "valign_hip_set_band_alignments", "valign_hip_set_band_nw", "valign_hip_set_band_placed", "valign_hip_set_placed_wide", "valign_hip_set_trace_checkpoints", "valign_hip_set_score_width", "valign_hip_set_ragged_batching", "valign_hip_score_device", "valign_hip_align_device", "valign_hip_score_host", "valign_hip_align_host", "valign_hip_align_cigar_device", "valign_hip_align_cigar_host", "valign_hip_score_placed_device", "valign_hip_score_placed_host", "valign_hip_score_span_device", "valign_hip_score_span_host", "valign_hip_describe",
     "valign_hip_last_error",
 )
 
@@ -226,6 +227,14 @@ class Engine:
         in-band end cell from the block chain (describe: ran_placed "chain"; include/valign_hip.h has the definition);
         0 (default): placed scores are refused under a band.  Not read without a band."""
         if lib().valign_hip_set_band_placed(self._h, int(on)) != 0:
+            raise HipKernelError(_err())
+
+    def set_placed_wide(self, on):
+        """1: unbanded Smith-Waterman score_placed_* / score_span_* calls with score_width = 32, or whose cells can leave int16
+        under score_width = 0, run on the pointer-free int32 sweep (describe: ran_placed "wide"; the score does not saturate;
+        include/valign_hip.h has the definition); 0 (default): such calls are refused.  Calls inside the int16 range run as
+        ever; not read under a band."""
+        if lib().valign_hip_set_placed_wide(self._h, int(on)) != 0:
             raise HipKernelError(_err())
 
     def set_trace_checkpoints(self, on):
