@@ -431,6 +431,101 @@ def test_strip_and_wide_calls_share_one_engine():
     eng.close()
 
 
+# ---- 9b. a strip sweep cut into several scratch chunks, the last one short and odd: the scratch is laid out for the waves of a
+# full chunk, the last launch runs fewer ----
+CR, CF, CAP_MB = 1025, 700, 1
+CHUNKED = {"strip": (0, 299), "wide": (32, 151)}           # route: score_width, pairs
+
+
+def _chunk_pairs(width):
+    """pairs of one scratch chunk under the cap (strip_plan.h, ckpt_plan.h, restated): per pair-of-pairs two row sets that
+    ping-pong, each an H and an F row (affine) of row_dwords dwords, and on int32 cells one such row per pair"""
+    row_dwords = ((CF + 71) // 64 + 2) * 64
+    row_sets = 2 * (2 if width == 32 else 1)
+    return (CAP_MB << 20) // (2 * row_sets * row_dwords * 4) * 2
+
+
+def _chunked_engine(width, capped):
+    eng = _engine(CR, CF, _scoring("aff"), width=width)
+    if capped:
+        eng.set_pointer_scratch_cap_mb(CAP_MB)
+    return eng
+
+
+def _records(host):
+    return np.stack([host[k] for k in host.dtype.names], axis=1).astype(np.int64)
+
+
+@functools.lru_cache(maxsize=None)
+def _chunked_case():
+    """the batch, the reference of its first 16 pairs and the uncapped engines' records of every route, computed once (read-only)"""
+    reads, refs = _pairs(299, CR, CF, 1616)
+    out = {"reads": reads, "refs": refs, "ref16": placed_ref.placed(reads[:16], refs[:16], _scoring("aff"), affine=True)}
+    for route, (width, n) in CHUNKED.items():
+        eng = _chunked_engine(width, capped=False)
+        out[route] = _run(eng, reads[:n], refs[:n])
+        out[route, "scratch"] = eng.describe(0, n)["placed_scratch_bytes"]
+        eng.close()
+    for a in out.values():
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    return out
+
+
+def test_chunk_counts_of_the_capped_sweeps():
+    assert CF + 135 <= ((CF + 71) // 64 + 2) * 64 == 896 and (_chunk_pairs(0), _chunk_pairs(32)) == (146, 72)
+    for width, n in CHUNKED.values():
+        chunk = _chunk_pairs(width)
+        assert -(-n // chunk) >= 3 and n % chunk == 7              # a short last chunk with a last wave of one pair
+
+
+@pytest.mark.parametrize("route", list(CHUNKED))
+def test_sweep_in_several_scratch_chunks(route):
+    width, n = CHUNKED[route]
+    case = _chunked_case()
+    eng = _chunked_engine(width, capped=True)
+    got = _run(eng, case["reads"][:n], case["refs"][:n])
+    d = eng.describe(0, n)
+    eng.close()
+    assert d["ran_placed"] == route and -(-n // _chunk_pairs(width)) >= 3
+    assert 0 < d["placed_scratch_bytes"] < case[route, "scratch"]              # the cap held: the rows of one chunk, not of the call
+    _check(got, case[route], (route, "capped against uncapped"))
+    _check(got[:16], case["ref16"], (route, "capped against the reference"))
+    _check(case[route][:16], case["ref16"], (route, "uncapped against the reference"))
+
+
+@pytest.mark.parametrize("route", list(CHUNKED))
+def test_sweep_in_several_scratch_chunks_host_path(route):
+    width, n = CHUNKED[route]
+    case = _chunked_case()
+    got = {}
+    for capped in (True, False):
+        eng = _chunked_engine(width, capped)
+        got[capped] = _records(eng.score_placed_host(0, case["reads"][:n], case["refs"][:n], threads=2))
+        d = eng.describe(0, n)
+        assert d["ran_placed"] == route and -(-n // _chunk_pairs(width)) >= 3
+        # (half a megabyte of sequence: the host call's direct small call -- the sweep's scratch chunks are what this checks, the
+        # pipeline's slot loop is test_host_path_equals_device_path's)
+        assert d["direct_call"] == 1
+        eng.close()
+    _check(got[True], got[False], (route, "host path, capped against uncapped"))
+    _check(got[True], case[route], (route, "host path against device path"))
+    _check(got[True][:16], case["ref16"], (route, "host path against the reference"))
+
+
+def test_spanned_sweep_in_several_scratch_chunks():
+    width, n = CHUNKED["strip"]
+    case = _chunked_case()
+    got = {}
+    for capped in (True, False):
+        eng = _chunked_engine(width, capped)
+        got[capped] = _span(eng, case["reads"][:n], case["refs"][:n])
+        assert eng.describe(0, n)["ran_span"].startswith("strip/") and -(-n // _chunk_pairs(width)) >= 3
+        eng.close()
+    _check(got[True], got[False], "spanned, capped against uncapped")
+    _check(got[True][:, [0, 2, 4]], case["strip"], "spanned against placed records")
+
+
 # ---- 10. seeded differential block ----
 def _predict(R, F, sc, width, K):
     """placed_choice with the key on, unbanded, default tie-breaks (cell_rules.h), restated"""

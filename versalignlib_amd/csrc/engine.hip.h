@@ -4,14 +4,18 @@
 //   engine_core.hip ..... construction, launch-plan selection (cost model), staging, describe()
 //   cell_rules.h ........ the cell-range rules and the choice of gap form, fill kernel and alignment path (pure, CPU-tested)
 //   engine_score.hip .... score_alignments: register-sweep launches, the host-pointer chunk pipeline, 4-bit class
-//                         unpacking, length-sorted batches (reference: DefaultKernel.cpp:52-202)
+//                         unpacking, length-sorted batches (reference: DefaultKernel.cpp:52-202).  The pipeline's pieces are
+//                         defined here once -- host_chunk_pairs, stage_chunk, wait_slot -- and so is record_pipeline, the
+//                         whole pipeline of the calls that bring fixed-size records back (placed and spanned scores)
 //   engine_long.hip ..... long reads: row strips (score_long_kernel) and the banded block chain (score_band_kernel)
 //   long_plan.h ......... the route of a long-read score call, its compiled instances, strip sizes and the chain's plan (pure, CPU-tested)
 //   engine_align.hip .... compute_alignments: fill + traceback launches, row strips, the fused small-batch launch, the
 //                         host-pointer pipeline with its copy-issuing thread (reference: DefaultKernel.cpp:21-50, 204-525)
-//   engine_placed.hip ... placed Smith-Waterman scores: score + end cell from the score sweep (placed_kernels.hip.h)
+//   engine_placed.hip ... placed Smith-Waterman scores: score + end cell from the score sweep (placed_kernels.hip.h); owns
+//                         score_placed_strips, the ONE pointer-free strip sweep (int16 strips and the int32 sweep are two
+//                         PlacedSweep descriptions of it); its host call is record_pipeline with a one-line launch
 //   engine_span.hip ..... spanned Smith-Waterman scores: a placed score plus the begin cell, from a second placed sweep over the
-//                         reversed prefixes (span_kernels.hip.h)
+//                         reversed prefixes (span_kernels.hip.h); its host call is record_pipeline too
 //   engine_cigar.hip .... the compact result format: records + CIGAR ops encoded on the device behind the walks (cigar_kernels.hip.h)
 //   hip_plugin.hip ...... the plugin ABI and the flat C API over it
 // The closest reference precedent for the staging loops is the OpenCL backend's gather / copy / launch / collect loop
@@ -472,11 +476,6 @@ public:
     void score_placed_host(int opt, int n, const char *const *reads, const char *const *refs, PlacedRec *placed, int threads);
     PlacedFacts placed_facts() const;
     const LaunchPlan &placed_plan_for(int alg, PlacedChoice &choice, int &gaps);
-    void score_placed_strips(long long n, const uint8_t *d_reads, const uint8_t *d_refs, PlacedRec *d_placed, hipStream_t stream);
-    void launch_placed_records(const EndCell *d_ends, PlacedRec *d_placed, long long n, hipStream_t stream);
-    // placed_wide = 1 (PlacedRoute::Wide): the int32 sweep strip after strip, then the records -- score_placed_strips' scratch,
-    // sized for one int32 row set per pair
-    void score_placed_wide(long long n, const uint8_t *d_reads, const uint8_t *d_refs, PlacedRec *d_placed, hipStream_t stream);
     const char *ran_placed() const { return ran_placed_; }
 
     // ---- spanned Smith-Waterman scores (valign_hip.h: valign_hip_span; engine_span.hip) ----
@@ -484,7 +483,7 @@ public:
     // cell (span_kernels.hip.h), score_placed_device of a child engine of shape (R, span_ref_length) on the reversed buffers,
     // and the records.  span_choice (cell_rules.h) decides what is refused.  Device-resident: asynchronous on `stream`, in
     // chunks that keep the reversed buffers and the two record buffers inside span_scratch_bytes_; calls of one engine belong
-    // on one stream.  Host pointers: score_placed_host's chunk pipeline, 20 bytes per pair on the way back.
+    // on one stream.  Host pointers: record_pipeline, 20 bytes per pair on the way back.
     void score_span_device(int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, SpanRec *d_spans, hipStream_t stream);
     void score_span_host(int opt, int n, const char *const *reads, const char *const *refs, SpanRec *spans, int threads);
     const char *ran_span() const { return ran_span_.c_str(); }
@@ -523,11 +522,52 @@ private:
         put_scoring(a);
     }
     template <class A>
-    void put_sweep(A &a, const uint8_t *d_reads, const uint8_t *d_refs, long long n, int blocks8, const WaveLds &lds) const {
-        put_sweep(a, d_reads, d_refs, n, blocks8);
+    void put_lds(A &a, const WaveLds &lds) const {
         a.prof_area = lds.prof_area;
         a.refc_stride = lds.refc_stride;
         a.wave_lds = lds.total;
+    }
+    template <class A>
+    void put_sweep(A &a, const uint8_t *d_reads, const uint8_t *d_refs, long long n, int blocks8, const WaveLds &lds) const {
+        put_sweep(a, d_reads, d_refs, n, blocks8);
+        put_lds(a, lds);
+    }
+    // What every strip launch shares (align_strips_device adds ptr and walk): `n` pairs of a chunk, strip `s` of the plan, the
+    // boundary row sets it reads (top) and writes (bottom) at dword offsets into `scratch`, the F rows f_rows behind the H rows
+    StripArgs strip_args(const uint8_t *d_reads, const uint8_t *d_refs, long long n, const StripPlan &plan, const WaveLds &lds, int s, unsigned *scratch,
+                         size_t top, size_t bottom, size_t f_rows, EndCell *ends, const int *first_bad) const {
+        StripArgs a{};
+        put_sweep(a, d_reads, d_refs, n, plan.blocks8, lds);
+        a.ends = ends;
+        a.first_bad = first_bad;
+        a.top = scratch + top;
+        a.bottom = scratch + bottom;
+        a.top_f = a.top + f_rows;           // (only read / written by the affine kernel)
+        a.bottom_f = a.bottom + f_rows;
+        a.strip = s;
+        a.strips = plan.strips;
+        a.row_dwords = plan.row_dwords;
+        a.band = plan.band;
+        return a;
+    }
+    // The pointer-free strip sweep of PlacedRoute::Strip and PlacedRoute::Wide: what differs between the two is this description.
+    struct PlacedSweep {
+        const void *fn;             // the strip kernel
+        WaveLds lds;
+        StripPlan plan;
+        bool first_bad;             // the kernel takes a first-invalid table (int16 strips: zeros, read by the NW variant only)
+        bool wide_records;          // placed_wide_records_kernel closes a chunk, else placed_records_kernel
+        const char *rows_label, *what;      // names of the boundary-row allocation and of the launch, in errors
+    };
+    PlacedSweep placed_strip_sweep() const;         // int16 cells: the forward pass of the checkpointed traceback (engine_align.hip)
+    PlacedSweep placed_wide_sweep() const;          // placed_wide = 1: the int32 sweep, 8 rows per lane (engine_placed.hip)
+    // Chunk after chunk of what the scratch cap holds: strip after strip through two boundary row sets that ping-pong, the end
+    // cell merged on the way, then one record per end cell.  The scratch is the engine's, shared by both descriptions.
+    void score_placed_strips(const PlacedSweep &sweep, long long n, const uint8_t *d_reads, const uint8_t *d_refs, PlacedRec *d_placed, hipStream_t stream);
+    // a block of more than the default LDS: the kernel's attribute first
+    static void raise_block_lds(const void *fn, int bytes) {
+        if (bytes > kDefaultBlockLds)
+            hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
     }
     TraceArgs trace_args(int alg, const uint8_t *d_reads, const uint8_t *d_refs, long long n, const unsigned *ptr, const EndCell *ends, uint8_t *rows,
                          short *idx, int G, int K, int pad_rows, int blocks8) const;
@@ -605,7 +645,27 @@ private:
     }
 
     void ensure_staging(long long pairs);
-    void ensure_placed_staging(long long pairs);
+
+    // ---- the pieces of the host-pointer chunk pipeline (engine_score.hip), shared by score_host and record_pipeline ----
+    // Pairs of one chunk: score_chunk_bytes_ of sequences -- at least 192 MB where the chunks' launches share a scratch and
+    // follow one another on one stream (not under the chunk_bytes debug switch) --, in whole rounds, at least 1024, at most n
+    long long host_chunk_pairs(bool shared_scratch, long long n) const;
+    // gather (4-bit classes where host_packing is on), H2D and unpacking on `stream`: the chunk lies in d_reads_ / d_refs_[slot]
+    void stage_chunk(int slot, hipStream_t stream, const char *const *reads, const char *const *refs, long long cnt, int threads);
+    // the slot's event, then drain(slot): the result of the chunk that used the slot last
+    void wait_slot(int slot, const std::function<void(int)> &drain);
+    // A host-pointer call that brings one fixed-size record per pair back (placed and spanned scores): the direct small call
+    // on the pinned staging, else chunks over the kSlots slots -- wait_slot, stage_chunk, launch, D2H, the slot's event -- on
+    // streams_[one_stream ? 0 : slot], and the oldest-first tail.  launch: the kernels of one chunk, all of them on `stream`.
+    struct RecordKind {
+        size_t bytes;
+        const char *label, *d2h;            // names of the device staging and of the copy back, in errors
+    };
+    using ChunkLaunch = std::function<void(int slot, long long cnt, const uint8_t *d_reads, const uint8_t *d_refs, uint8_t *d_records, hipStream_t stream)>;
+    // chunk: host_chunk_pairs(one_stream, n), the caller's, which may have sized a scratch of its own by it
+    void record_pipeline(long long n, const char *const *reads, const char *const *refs, void *out, const RecordKind &kind, long long chunk, bool one_stream,
+                         int threads, const ChunkLaunch &launch);
+    void ensure_record_staging(long long pairs, const RecordKind &kind);
 
     // ---- spanned scores (engine_span.hip) ----
     // One context per pipeline slot (chunks of different slots are in flight side by side) and one for device-resident calls
@@ -620,7 +680,6 @@ private:
     Engine &span_prepare(int alg, bool &strips);
     long long span_chunk_pairs(long long n) const;
     void ensure_span_scratch(int c, long long pairs, hipStream_t stream);
-    void ensure_span_staging(long long pairs);
     // one chunk, all of it on `stream`: forward sweep, reversal, reverse sweep, records
     void span_chunk(int c, int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, SpanRec *d_spans, hipStream_t stream);
 
@@ -740,7 +799,8 @@ private:
     LaunchPlan align_resident_;         // what choose_plan picked before the score path's preferences for the long-read kernels
     LaunchPlan fallback_plan_;          // alignments that need a kernel only the full geometries carry (align_plan_for)
     long long slot_begin_[kSlots] = {}, slot_pending_[kSlots] = {};
-    long long staged_pairs_ = 0, align_staged_pairs_ = 0, placed_staged_pairs_ = 0;
+    long long staged_pairs_ = 0, align_staged_pairs_ = 0;
+    size_t record_staged_bytes_ = 0;                                     // bytes each slot of the record staging holds
     bool pack_ = true;                                                   // host_packing: 4-bit base classes across PCIe
     BandPlan band_plan_;               // the block chain's plan for band_width_ (set_band_width)
     int band_tables_width_ = -1;       // ... and the band_width whose tables are on the device
@@ -758,7 +818,6 @@ private:
     const char *ran_placed_ = "none";                    // what the last placed-score call ran: key / rows / strip / chain / wide (describe)
     std::string ran_span_ = "none";                      // what the last spanned call ran: forward route / reverse route (describe)
     size_t span_scratch_bytes_ = (size_t)dbg_.value("span_scratch_bytes", 256ll << 20);      // device-resident spanned calls: scratch of one chunk
-    long long span_staged_pairs_ = 0;
     const char *ran_result_format_ = "rows";             // of the last alignment call: rows / cigar (describe)
     long long cigar_d2h_bytes_ = 0;                      // what the last align_cigar_host call copied back
     const CigarSink *cigar_ = nullptr;
@@ -802,15 +861,14 @@ private:
     PinnedBuffer<long long> h_cig_total_;
     DeviceBuffer<int> d_min_start_;                              // per slot: first column of the chunk's rows that holds a string
     PinnedBuffer<int> h_min_start_;                              // ... on its way to the host
-    // placed scores: record staging of the host path; the strips' boundary rows, end cells and (unread) first-invalid table
-    PinnedBuffer<PlacedRec> h_placed_[kSlots];
-    DeviceBuffer<PlacedRec> d_placed_[kSlots];
+    // record_pipeline: record staging (placed or spanned records: one host call runs on an engine at a time)
+    PinnedBuffer<uint8_t> h_records_[kSlots];
+    DeviceBuffer<uint8_t> d_records_[kSlots];
+    // placed scores: the strips' boundary rows, end cells and (unread) first-invalid table
     DeviceBuffer<unsigned> d_placed_rows_;
     DeviceBuffer<EndCell> d_placed_ends_;
     DeviceBuffer<int> d_placed_bad_;
-    // spanned scores: record staging of the host path, the reversal scratch, the engine of the reverse sweep
-    PinnedBuffer<SpanRec> h_span_[kSlots];
-    DeviceBuffer<SpanRec> d_span_[kSlots];
+    // spanned scores: the reversal scratch, the engine of the reverse sweep
     SpanCtx span_[kSlots + 1];                                   // one per pipeline slot, the last for device-resident calls
     std::unique_ptr<Engine> span_child_;
     DeviceBuffer<unsigned> d_brow_;                              // long-read path: strip boundary rows

@@ -304,9 +304,7 @@ void Engine::align_strips_device(const StripMode &mode, long long n, const uint8
     }
     WalkState *walk = mode.ckpt ? reinterpret_cast<WalkState *>(d_ptr_.get() + plan.walk_at(waves)) : nullptr;
     const void *fn = geo.kernel(mode, 0), *refill_fn = mode.ckpt ? geo.kernel(mode, 1) : fn;
-    if (lds.total > kDefaultBlockLds)
-        for (const void *f : {fn, refill_fn})
-            hip_check(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds.total), "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+    for (const void *f : {fn, refill_fn}) raise_block_lds(f, lds.total);
     // ---- launches: the rows zeroed and the first invalid positions once, then chunk after chunk its strips and its walk ----
     hip_check(hipMemsetAsync(d_rows, 0, (size_t)n * 2 * AL, stream), "hipMemsetAsync(rows)");
     hipLaunchKernelGGL(first_invalid_kernel, dim3((unsigned)n), dim3(kWave), 0, stream, d_reads, d_refs, n, R_, F_, d_first_bad_.get(),
@@ -317,19 +315,9 @@ void Engine::align_strips_device(const StripMode &mode, long long n, const uint8
         const uint8_t *reads = d_reads + (size_t)begin * R_, *refs = d_refs + (size_t)begin * F_;
         const unsigned walk_blocks = (unsigned)((cnt + 255) / 256);
         auto launch_strip = [&](const void *kernel, int s, const char *what) {
-            StripArgs a{};
-            put_sweep(a, reads, refs, cnt, plan.blocks8, lds);
+            StripArgs a = strip_args(reads, refs, cnt, plan, lds, s, d_ptr_.get(), plan.top_at(waves, s), plan.bottom_at(waves, s), plan.f_rows_at(waves),
+                                     d_ends_.get(), d_first_bad_.get() + 2 * begin);
             a.ptr = d_ptr_.get() + plan.region_at(cnt_waves, s);
-            a.ends = d_ends_.get();
-            a.first_bad = d_first_bad_.get() + 2 * begin;
-            a.top = d_ptr_.get() + plan.top_at(waves, s);
-            a.bottom = d_ptr_.get() + plan.bottom_at(waves, s);
-            a.top_f = a.top + plan.f_rows_at(waves);      // (only read / written by the affine kernel)
-            a.bottom_f = a.bottom + plan.f_rows_at(waves);
-            a.strip = s;
-            a.strips = strips;
-            a.row_dwords = plan.row_dwords;
-            a.band = plan.band;
             a.walk = walk;
             void *kargs[] = {&a};
             hip_check(hipLaunchKernel(kernel, dim3((unsigned)cnt_waves), dim3(kWave), kargs, (size_t)lds.total, stream), what);
@@ -360,55 +348,15 @@ void Engine::align_strips_device(const StripMode &mode, long long n, const uint8
     }
 }
 
-// Placed scores of reads that take the row strips (engine_placed.hip): the forward pass of the checkpointed traceback -- the
-// strips' sweep without a pointer stream, the Smith-Waterman end cell merged strip after strip, earlier strips winning ties --
-// and nothing else.  The pass hands its bottom rows on; nobody walks back, so two row sets that ping-pong stand in for the
-// checkpoint rows: (2 or 4) x row_dwords dwords per pair-of-pairs, no pointer region.  Then one record per end cell.
-void Engine::score_placed_strips(long long n, const uint8_t *d_reads, const uint8_t *d_refs, PlacedRec *d_placed, hipStream_t stream) {
-    StripMode mode{kAlgSW, sc_.affine, false, false, false, true};
+// Placed scores of reads that take the row strips (Engine::score_placed_strips, engine_placed.hip): the forward pass of the
+// checkpointed traceback at the K the strip rule picks, with a first-invalid table (zeros: read by the NW variant only).
+Engine::PlacedSweep Engine::placed_strip_sweep() const {
+    const StripMode mode{kAlgSW, sc_.affine, false, false, false, true};
     const int K = strip_rows_per_lane(R_, mode, strip_k_);
     if (!K) throw std::runtime_error("no strip kernel for placed scores");
     const StripGeometry &geo = *std::find_if(std::begin(kStripGeometries), std::end(kStripGeometries), [&](const StripGeometry &g) { return g.K == K; });
-    const StripPlan plan = strip_plan(R_, F_, K, mode, kNoBand);
-    const size_t set_dwords = (size_t)plan.row_sets * plan.row_dwords;          // one row set of one pair-of-pairs
-    const size_t bytes_per_pp = 2 * set_dwords * 4;
-    size_t free_b = 0, total_b = 0;
-    hip_check(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
-    const long long chunk = strip_chunk_pairs(strip_scratch_cap(free_b + d_placed_rows_.bytes(), scratch_cap_mb_), bytes_per_pp, n);
-    const long long waves = chunk / 2;
-    if ((size_t)waves * bytes_per_pp > d_placed_rows_.bytes() || sizeof(EndCell) * (size_t)chunk > d_placed_ends_.bytes() ||
-        sizeof(int) * 2 * (size_t)chunk > d_placed_bad_.bytes()) {       // (score_placed_wide grows the first two only)
-        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");          // nothing may still read the old scratch
-        d_placed_rows_.reserve((size_t)waves * bytes_per_pp, "placed-score boundary rows");
-        d_placed_ends_.reserve(sizeof(EndCell) * (size_t)chunk, "placed-score end cells");
-        d_placed_bad_.reserve(sizeof(int) * 2 * (size_t)chunk, "placed-score first invalid positions");
-        hip_check(hipMemsetAsync(d_placed_bad_.get(), 0, sizeof(int) * 2 * (size_t)chunk, stream), "hipMemsetAsync");     // (read by the NW variant only)
-    }
-    const void *fn = geo.kernel(mode, 0);
-    if (geo.lds.total > kDefaultBlockLds)
-        hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, geo.lds.total), "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-    const size_t slot_dwords = (size_t)waves * set_dwords, f_rows = (size_t)waves * plan.row_dwords;
-    for (long long begin = 0; begin < n; begin += chunk) {
-        const long long cnt = std::min(chunk, n - begin), cnt_waves = (cnt + 1) / 2;
-        for (int s = 0; s < plan.strips; ++s) {
-            StripArgs a{};
-            put_sweep(a, d_reads + (size_t)begin * R_, d_refs + (size_t)begin * F_, cnt, plan.blocks8, geo.lds);
-            a.ends = d_placed_ends_.get();
-            a.first_bad = d_placed_bad_.get();
-            a.bottom = d_placed_rows_.get() + (size_t)(s & 1) * slot_dwords;
-            a.top = d_placed_rows_.get() + (size_t)((s + 1) & 1) * slot_dwords;
-            a.top_f = a.top + f_rows;               // (only read / written by the affine kernel)
-            a.bottom_f = a.bottom + f_rows;
-            a.strip = s;
-            a.strips = plan.strips;
-            a.row_dwords = plan.row_dwords;
-            a.band = kNoBand;
-            void *kargs[] = {&a};
-            hip_check(hipLaunchKernel(fn, dim3((unsigned)cnt_waves), dim3(kWave), kargs, (size_t)geo.lds.total, stream),
-                      "hipLaunchKernel(align_strip_kernel, placed scores)");
-        }
-        launch_placed_records(d_placed_ends_.get(), d_placed + begin, cnt, stream);
-    }
+    return PlacedSweep{geo.kernel(mode, 0), geo.lds, strip_plan(R_, F_, K, mode, kNoBand), true, false, "placed-score boundary rows",
+                       "hipLaunchKernel(align_strip_kernel, placed scores)"};
 }
 
 template <typename Sink>

@@ -1,6 +1,7 @@
 // engine_score.hip -- Engine: score_alignments (reference: src/Kernels/default/DefaultKernel.cpp:52-202) -- the register-sweep
-// launches, the host-pointer chunk pipeline, 4-bit class unpacking and length-sorted batches.  The non-template kernels of
-// pack_kernels.hip.h / ragged_kernels.hip.h are defined in this translation unit.
+// launches, the host-pointer chunk pipeline, 4-bit class unpacking and length-sorted batches.  The pipeline's pieces
+// (host_chunk_pairs, stage_chunk, wait_slot) and record_pipeline, the pipeline of the placed and spanned host calls, are defined
+// here.  The non-template kernels of pack_kernels.hip.h / ragged_kernels.hip.h are defined in this translation unit.
 #define VALIGN_TU_SCORE 1
 #include "engine.hip.h"
 
@@ -106,6 +107,103 @@ void Engine::launch_unpack(const uint8_t *d_packed, uint8_t *d_out, long long n,
               "hipLaunchKernel(unpack_kernel)");
 }
 
+long long Engine::host_chunk_pairs(bool shared_scratch, long long n) const {
+    const size_t per_pair = (size_t)R_ + F_;
+    const size_t chunk_bytes = shared_scratch && !dbg_.on("chunk_bytes") ? std::max<size_t>(score_chunk_bytes_, 192u << 20) : score_chunk_bytes_;
+    long long chunk = per_pair ? (long long)(chunk_bytes / per_pair) : n;
+    chunk = whole_rounds(chunk);
+    chunk = std::max<long long>(chunk, 1024);
+    return std::min<long long>(chunk, n);
+}
+
+void Engine::stage_chunk(int slot, hipStream_t st, const char *const *reads, const char *const *refs, long long cnt, int threads) {
+    const auto t0 = std::chrono::steady_clock::now();
+    uint8_t *h_reads = h_reads_[slot].get(), *h_refs = h_refs_[slot].get(), *d_reads = d_reads_[slot].get(), *d_refs = d_refs_[slot].get();
+    if (pack_) {
+        // two base classes per byte across PCIe, expanded in HBM to the canonical byte of each class
+        const size_t PR = packed_length(R_), PF = packed_length(F_);
+        packer_.gather_packed(reads, refs, cnt, h_reads, h_refs, threads);
+        host_stats_.gather_ms += ms_between(t0, std::chrono::steady_clock::now());
+        hip_check(hipMemcpyAsync(d_pack_reads_[slot].get(), h_reads, (size_t)cnt * PR, hipMemcpyHostToDevice, st), "H2D reads (classes)");
+        hip_check(hipMemcpyAsync(d_pack_refs_[slot].get(), h_refs, (size_t)cnt * PF, hipMemcpyHostToDevice, st), "H2D refs (classes)");
+        launch_unpack(d_pack_reads_[slot].get(), d_reads, cnt, R_, st);
+        launch_unpack(d_pack_refs_[slot].get(), d_refs, cnt, F_, st);
+        host_stats_.packed = 1;
+    } else {
+        gather(reads, refs, cnt, h_reads, h_refs, threads);
+        host_stats_.gather_ms += ms_between(t0, std::chrono::steady_clock::now());
+        hip_check(hipMemcpyAsync(d_reads, h_reads, (size_t)cnt * R_, hipMemcpyHostToDevice, st), "H2D reads");
+        hip_check(hipMemcpyAsync(d_refs, h_refs, (size_t)cnt * F_, hipMemcpyHostToDevice, st), "H2D refs");
+    }
+}
+
+void Engine::wait_slot(int slot, const std::function<void(int)> &drain) {
+    const auto t0 = std::chrono::steady_clock::now();
+    hip_check(hipEventSynchronize(slot_done_[slot].get()), "hipEventSynchronize");
+    const auto t1 = std::chrono::steady_clock::now();
+    drain(slot);
+    host_stats_.wait_ms += ms_between(t0, t1);
+    host_stats_.drain_ms += ms_between(t1, std::chrono::steady_clock::now());
+}
+
+void Engine::ensure_record_staging(long long pairs, const RecordKind &kind) {
+    const size_t bytes = kind.bytes * (size_t)pairs;
+    if (bytes <= record_staged_bytes_) return;
+    record_staged_bytes_ = 0;
+    for (int s = 0; s < kSlots; ++s) {          // (every old block goes before the first new one is allocated)
+        h_records_[s].reset();
+        d_records_[s].reset();
+    }
+    for (int s = 0; s < kSlots; ++s) {
+        h_records_[s].reserve(bytes);
+        d_records_[s].reserve(bytes, kind.label);
+    }
+    record_staged_bytes_ = bytes;
+}
+
+void Engine::record_pipeline(long long n, const char *const *reads, const char *const *refs, void *out, const RecordKind &kind, long long chunk,
+                             bool one_stream, int threads, const ChunkLaunch &launch) {
+    const size_t per_pair = (size_t)R_ + F_;
+    reset_pipeline();
+    ensure_staging(chunk);
+    ensure_record_staging(chunk, kind);
+    threads = std::min(std::max(threads, 1), 64);
+    host_stats_ = HostStats{};
+    if (direct_call(n, per_pair)) {
+        // small call: the kernels read the gathered sequences out of the pinned staging and write their records there
+        auto t0 = std::chrono::steady_clock::now();
+        gather(reads, refs, n, h_reads_[0].get(), h_refs_[0].get(), threads);
+        auto t1 = std::chrono::steady_clock::now();
+        launch(0, n, dev_view(h_reads_[0].get()), dev_view(h_refs_[0].get()), dev_view(h_records_[0].get()), streams_[0].get());
+        hip_check(hipStreamSynchronize(streams_[0].get()), "hipStreamSynchronize");
+        auto t2 = std::chrono::steady_clock::now();
+        memcpy(out, h_records_[0].get(), kind.bytes * (size_t)n);
+        host_stats_.gather_ms = ms_between(t0, t1);
+        host_stats_.wait_ms = ms_between(t1, t2);
+        host_stats_.drain_ms = ms_between(t2, std::chrono::steady_clock::now());
+        host_stats_.direct = 1;
+        return;
+    }
+    const std::function<void(int)> drain = [&](int s) {
+        if (slot_pending_[s] <= 0) return;
+        memcpy((uint8_t *)out + kind.bytes * (size_t)slot_begin_[s], h_records_[s].get(), kind.bytes * (size_t)slot_pending_[s]);
+        slot_pending_[s] = 0;
+    };
+    int slot = 0;
+    for (long long begin = 0; begin < n; begin += chunk, slot = (slot + 1) % kSlots) {
+        const long long cnt = std::min<long long>(chunk, n - begin);
+        wait_slot(slot, drain);                 // the result of the chunk that used this slot
+        hipStream_t st = streams_[one_stream ? 0 : slot].get();
+        stage_chunk(slot, st, reads + begin, refs + begin, cnt, threads);
+        launch(slot, cnt, d_reads_[slot].get(), d_refs_[slot].get(), d_records_[slot].get(), st);
+        hip_check(hipMemcpyAsync(h_records_[slot].get(), d_records_[slot].get(), kind.bytes * (size_t)cnt, hipMemcpyDeviceToHost, st), kind.d2h);
+        hip_check(hipEventRecord(slot_done_[slot].get(), st), "hipEventRecord");
+        slot_begin_[slot] = begin;
+        slot_pending_[slot] = cnt;
+    }
+    for (int k = 0; k < kSlots; ++k) wait_slot((slot + k) % kSlots, drain);          // oldest chunk first
+}
+
 void Engine::score_host(int opt, int n, const char *const *reads, const char *const *refs, short *scores,
                 int threads, int16_t *d_dest) {
     const int alg = opt & 0xF;
@@ -123,11 +221,7 @@ void Engine::score_host(int opt, int n, const char *const *reads, const char *co
     // single-strip instances (short reads against a long reference).
     const bool shared_scratch = (plan_.long_mode || score_wide_cells(alg)) && long_mode(alg, false).brow;
     const bool strips_in_turn = plan_.long_mode && shared_scratch;
-    const size_t chunk_bytes = strips_in_turn && !dbg_.on("chunk_bytes") ? std::max<size_t>(score_chunk_bytes_, 192u << 20) : score_chunk_bytes_;
-    long long chunk = per_pair ? (long long)(chunk_bytes / per_pair) : n;
-    chunk = whole_rounds(chunk);
-    chunk = std::max<long long>(chunk, 1024);
-    chunk = std::min<long long>(chunk, n);
+    const long long chunk = host_chunk_pairs(strips_in_turn, n);
     reset_pipeline();
     ensure_staging(chunk);
     if (threads < 1) threads = 1;
@@ -157,7 +251,7 @@ void Engine::score_host(int opt, int n, const char *const *reads, const char *co
     const bool ragged = !d_dest && ragged_applies(alg) && ragged_fits(chunk) &&
                         (ragged_ == 2 || sampled_cell_fraction(reads, refs, n) < 0.67);
     host_stats_ = HostStats{};
-    auto drain = [&](int s) {
+    const std::function<void(int)> drain = [&](int s) {
         if (slot_pending_[s] <= 0) return;
         if (d_dest) {                          // (the kernels wrote the device destination themselves)
             slot_pending_[s] = 0;
@@ -190,34 +284,12 @@ void Engine::score_host(int opt, int n, const char *const *reads, const char *co
     for (long long begin = 0; begin < n; begin += cnt, slot = (slot + 1) % kSlots, ++chunk_no) {
         const long long ramp = (n > 2 * chunk) ? (chunk_no == 0 ? whole_rounds(chunk / 4) : (chunk_no == 1 ? whole_rounds(chunk / 2) : chunk)) : chunk;
         cnt = std::min<long long>(std::max<long long>(ramp, 1024), n - begin);
-        auto t0 = std::chrono::steady_clock::now();
-        hip_check(hipEventSynchronize(slot_done_[slot].get()), "hipEventSynchronize");
-        auto t1 = std::chrono::steady_clock::now();
-        drain(slot);                            // the result of the chunk that used this slot
-        auto t2 = std::chrono::steady_clock::now();
-        host_stats_.wait_ms += ms_between(t0, t1);
-        host_stats_.drain_ms += ms_between(t1, t2);
+        wait_slot(slot, drain);                 // the result of the chunk that used this slot
         // kernels that share a scratch (strip boundary rows) stay on one stream
         hipStream_t st = streams_[shared_scratch ? 0 : slot].get();
-        uint8_t *h_reads = h_reads_[slot].get(), *h_refs = h_refs_[slot].get(), *d_reads = d_reads_[slot].get(), *d_refs = d_refs_[slot].get();
-        const bool sweep_now = !ragged;
-        if (pack_) {
-            // two base classes per byte across PCIe, expanded in HBM to the canonical byte of each class
-            const size_t PR = packed_length(R_), PF = packed_length(F_);
-            packer_.gather_packed(reads + begin, refs + begin, cnt, h_reads, h_refs, threads);
-            host_stats_.gather_ms += ms_between(t2, std::chrono::steady_clock::now());
-            hip_check(hipMemcpyAsync(d_pack_reads_[slot].get(), h_reads, (size_t)cnt * PR, hipMemcpyHostToDevice, st), "H2D reads (classes)");
-            hip_check(hipMemcpyAsync(d_pack_refs_[slot].get(), h_refs, (size_t)cnt * PF, hipMemcpyHostToDevice, st), "H2D refs (classes)");
-            launch_unpack(d_pack_reads_[slot].get(), d_reads, cnt, R_, st);
-            launch_unpack(d_pack_refs_[slot].get(), d_refs, cnt, F_, st);
-            host_stats_.packed = 1;
-        } else {
-            gather(reads + begin, refs + begin, cnt, h_reads, h_refs, threads);
-            host_stats_.gather_ms += ms_between(t2, std::chrono::steady_clock::now());
-            hip_check(hipMemcpyAsync(d_reads, h_reads, (size_t)cnt * R_, hipMemcpyHostToDevice, st), "H2D reads");
-            hip_check(hipMemcpyAsync(d_refs, h_refs, (size_t)cnt * F_, hipMemcpyHostToDevice, st), "H2D refs");
-        }
-        if (sweep_now) {
+        stage_chunk(slot, st, reads + begin, refs + begin, cnt, threads);
+        const uint8_t *d_reads = d_reads_[slot].get(), *d_refs = d_refs_[slot].get();
+        if (!ragged) {
             score_device(opt, cnt, d_reads, d_refs, d_dest ? d_dest + begin : d_scores_[slot].get(), st, false);
             finish_chunk(slot, cnt);
         } else {
@@ -232,15 +304,7 @@ void Engine::score_host(int opt, int n, const char *const *reads, const char *co
         slot_pending_[slot] = cnt;
     }
     for (const OpenChunk &c : open) finish_chunk(c.slot, c.pairs);
-    for (int k = 0; k < kSlots; ++k) {          // oldest chunk first
-        const int s = (slot + k) % kSlots;
-        auto t0 = std::chrono::steady_clock::now();
-        hip_check(hipEventSynchronize(slot_done_[s].get()), "hipEventSynchronize");
-        auto t1 = std::chrono::steady_clock::now();
-        drain(s);
-        host_stats_.wait_ms += ms_between(t0, t1);
-        host_stats_.drain_ms += ms_between(t1, std::chrono::steady_clock::now());
-    }
+    for (int k = 0; k < kSlots; ++k) wait_slot((slot + k) % kSlots, drain);          // oldest chunk first
 }
 
 bool Engine::ragged_applies(int alg) const {

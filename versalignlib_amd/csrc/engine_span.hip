@@ -2,7 +2,7 @@
 // BEGIN cell of every pair from two score sweeps -- no pointer stream, no walk, no host round trip.  span_choice (cell_rules.h)
 // decides what is refused and span_ref_length how many reference columns the reverse sweep looks back; this unit launches:
 // score_placed_device as it stands, span_reverse_kernel, score_placed_device of a child engine of the reverse sweep's shape,
-// span_records_kernel.  The host-pointer path is score_placed_host's chunk pipeline with 20-byte records on the way back.
+// span_records_kernel.  The host-pointer path is record_pipeline (engine_score.hip) with 20-byte records on the way back.
 // span_reverse_kernel and span_records_kernel (not templates) are defined in this translation unit.
 #define VALIGN_TU_SPAN 1
 #include "engine.hip.h"
@@ -95,22 +95,8 @@ void Engine::score_span_device(int opt, long long n, const uint8_t *d_reads, con
         span_chunk(kSlots, opt, std::min(chunk, n - begin), d_reads + (size_t)begin * R_, d_refs + (size_t)begin * F_, d_spans + begin, stream);
 }
 
-void Engine::ensure_span_staging(long long pairs) {
-    if (pairs <= span_staged_pairs_) return;
-    span_staged_pairs_ = 0;
-    for (int s = 0; s < kSlots; ++s) {
-        h_span_[s].reset();
-        d_span_[s].reset();
-    }
-    for (int s = 0; s < kSlots; ++s) {
-        h_span_[s].reserve(sizeof(SpanRec) * (size_t)pairs);
-        d_span_[s].reserve(sizeof(SpanRec) * (size_t)pairs, "spanned records");
-    }
-    span_staged_pairs_ = pairs;
-}
-
-// Host pointers in, host records out: score_placed_host's pipeline -- gather, pinned staging (4-bit classes where host_packing
-// is on), H2D, the four launches of a chunk, D2H -- over kSlots slots, each with a reversal scratch of its own.
+// Host pointers in, host records out: record_pipeline, each slot with a reversal scratch of its own, the four launches of a
+// chunk on the chunk's stream, 20 bytes per pair on the way back.
 void Engine::score_span_host(int opt, int n, const char *const *reads, const char *const *refs, SpanRec *spans, int threads) {
     const int alg = opt & 0xF;
     if (alg > 1 || n <= 0) return;
@@ -120,80 +106,13 @@ void Engine::score_span_host(int opt, int n, const char *const *reads, const cha
     bool strips = false;                                        // their launches share the boundary rows: one stream, large chunks
     (void)span_prepare(alg, strips);                            // (refusals leave here, before anything is staged)
     hip_check(hipSetDevice(device_), "hipSetDevice");
-    const size_t per_pair = (size_t)R_ + F_;
-    const size_t chunk_bytes = strips && !dbg_.on("chunk_bytes") ? std::max<size_t>(score_chunk_bytes_, 192u << 20) : score_chunk_bytes_;
-    long long chunk = per_pair ? (long long)(chunk_bytes / per_pair) : n;
-    chunk = whole_rounds(chunk);
-    chunk = std::max<long long>(chunk, 1024);
-    chunk = std::min<long long>(chunk, n);
-    reset_pipeline();
-    ensure_staging(chunk);
-    ensure_span_staging(chunk);
+    const long long chunk = host_chunk_pairs(strips, n);
+    reset_pipeline();               // (before a scratch regrows: no chunk of a call that threw still runs; record_pipeline's own reset then finds nothing)
     for (int s = 0; s < kSlots; ++s) ensure_span_scratch(s, chunk, streams_[s].get());
-    threads = std::min(std::max(threads, 1), 64);
-    host_stats_ = HostStats{};
-    if (direct_call(n, per_pair)) {
-        // small call: the kernels read the gathered sequences out of the pinned staging and write the records there
-        auto t0 = std::chrono::steady_clock::now();
-        gather(reads, refs, n, h_reads_[0].get(), h_refs_[0].get(), threads);
-        auto t1 = std::chrono::steady_clock::now();
-        span_chunk(0, opt, n, dev_view(h_reads_[0].get()), dev_view(h_refs_[0].get()), (SpanRec *)dev_view(h_span_[0].get()), streams_[0].get());
-        hip_check(hipStreamSynchronize(streams_[0].get()), "hipStreamSynchronize");
-        auto t2 = std::chrono::steady_clock::now();
-        memcpy(spans, h_span_[0].get(), sizeof(SpanRec) * (size_t)n);
-        host_stats_.gather_ms = ms_between(t0, t1);
-        host_stats_.wait_ms = ms_between(t1, t2);
-        host_stats_.drain_ms = ms_between(t2, std::chrono::steady_clock::now());
-        host_stats_.direct = 1;
-        return;
-    }
-    auto drain = [&](int s) {
-        if (slot_pending_[s] <= 0) return;
-        memcpy(spans + slot_begin_[s], h_span_[s].get(), sizeof(SpanRec) * (size_t)slot_pending_[s]);
-        slot_pending_[s] = 0;
-    };
-    int slot = 0;
-    for (long long begin = 0; begin < n; begin += chunk, slot = (slot + 1) % kSlots) {
-        const long long cnt = std::min<long long>(chunk, n - begin);
-        auto t0 = std::chrono::steady_clock::now();
-        hip_check(hipEventSynchronize(slot_done_[slot].get()), "hipEventSynchronize");
-        auto t1 = std::chrono::steady_clock::now();
-        drain(slot);                            // the result of the chunk that used this slot
-        auto t2 = std::chrono::steady_clock::now();
-        host_stats_.wait_ms += ms_between(t0, t1);
-        host_stats_.drain_ms += ms_between(t1, t2);
-        hipStream_t st = streams_[strips ? 0 : slot].get();
-        uint8_t *h_reads = h_reads_[slot].get(), *h_refs = h_refs_[slot].get(), *d_reads = d_reads_[slot].get(), *d_refs = d_refs_[slot].get();
-        if (pack_) {
-            const size_t PR = packed_length(R_), PF = packed_length(F_);
-            packer_.gather_packed(reads + begin, refs + begin, cnt, h_reads, h_refs, threads);
-            host_stats_.gather_ms += ms_between(t2, std::chrono::steady_clock::now());
-            hip_check(hipMemcpyAsync(d_pack_reads_[slot].get(), h_reads, (size_t)cnt * PR, hipMemcpyHostToDevice, st), "H2D reads (classes)");
-            hip_check(hipMemcpyAsync(d_pack_refs_[slot].get(), h_refs, (size_t)cnt * PF, hipMemcpyHostToDevice, st), "H2D refs (classes)");
-            launch_unpack(d_pack_reads_[slot].get(), d_reads, cnt, R_, st);
-            launch_unpack(d_pack_refs_[slot].get(), d_refs, cnt, F_, st);
-            host_stats_.packed = 1;
-        } else {
-            gather(reads + begin, refs + begin, cnt, h_reads, h_refs, threads);
-            host_stats_.gather_ms += ms_between(t2, std::chrono::steady_clock::now());
-            hip_check(hipMemcpyAsync(d_reads, h_reads, (size_t)cnt * R_, hipMemcpyHostToDevice, st), "H2D reads");
-            hip_check(hipMemcpyAsync(d_refs, h_refs, (size_t)cnt * F_, hipMemcpyHostToDevice, st), "H2D refs");
-        }
-        span_chunk(slot, opt, cnt, d_reads, d_refs, d_span_[slot].get(), st);
-        hip_check(hipMemcpyAsync(h_span_[slot].get(), d_span_[slot].get(), sizeof(SpanRec) * (size_t)cnt, hipMemcpyDeviceToHost, st), "D2H spanned records");
-        hip_check(hipEventRecord(slot_done_[slot].get(), st), "hipEventRecord");
-        slot_begin_[slot] = begin;
-        slot_pending_[slot] = cnt;
-    }
-    for (int k = 0; k < kSlots; ++k) {          // oldest chunk first
-        const int s = (slot + k) % kSlots;
-        auto t0 = std::chrono::steady_clock::now();
-        hip_check(hipEventSynchronize(slot_done_[s].get()), "hipEventSynchronize");
-        auto t1 = std::chrono::steady_clock::now();
-        drain(s);
-        host_stats_.wait_ms += ms_between(t0, t1);
-        host_stats_.drain_ms += ms_between(t1, std::chrono::steady_clock::now());
-    }
+    record_pipeline(n, reads, refs, spans, RecordKind{sizeof(SpanRec), "spanned records", "D2H spanned records"}, chunk, strips, threads,
+                    [&](int slot, long long cnt, const uint8_t *d_reads, const uint8_t *d_refs, uint8_t *d_records, hipStream_t stream) {
+                        span_chunk(slot, opt, cnt, d_reads, d_refs, (SpanRec *)d_records, stream);
+                    });
 }
 
 }  // namespace valign
