@@ -457,6 +457,53 @@ int valign_hip_score_span_device(valign_hip_engine *e, int opt, long long n, con
 int valign_hip_score_span_host(valign_hip_engine *e, int opt, int n, const char *const *reads,
                                const char *const *refs, valign_hip_span *spans, int threads);
 
+/* ---- suboptimal Smith-Waterman scores: runner-up score and column without a traceback ----
+ * A mapper computes mapping quality from the SECOND-best local alignment score: SSW's score2 / ref_end2, BWA's sub -- the best
+ * score that ends at least `mask` reference columns away from where the best alignment ends.  Suboptimal scores give the placed
+ * record plus that pair of numbers from the ONE placed sweep: no second sweep, no DP matrix, no host round trip.
+ * DEFINITION, for Smith-Waterman (opt & 0xF == 0), per pair, with the caller's mask >= 0 per call:
+ *   score, read_end, ref_end
+ *                 exactly what valign_hip_score_placed_device returns for the pair.
+ *   trimmed lengths
+ *                 Rp is 1 + the position of the last ACGT byte (either case) of the read row, 0 if there is none; Fp the same
+ *                 for the reference row: the lengths without trailing non-ACGT bytes that ragged batching uses.
+ *   colmax[j] ... for 0 <= j < Fp, the maximum of H[i][j] over 0 <= i < Rp, H the Smith-Waterman matrix of the pair (interior
+ *                 non-ACGT bytes score 0 as everywhere).
+ *   candidates .. the columns j with |j - (ref_end - 1)| > mask.
+ *   score2 ...... the largest colmax[j] over the candidates.
+ *   ref_end2 .... ref_end2 - 1 is the SMALLEST candidate column that holds score2.  Both are 0 where there is no candidate or the
+ *                 largest is 0.
+ *   empty ....... a pair whose score is 0 returns five zeros.
+ * Rows and columns beyond the trimmed lengths are not candidates: a non-ACGT byte scores 0 against anything, so a value runs
+ * down the diagonal through padding unchanged, and a padded read would report its own best score again as the runner-up.
+ * THE CALLER PICKS THE MASK: columns before the window hold the best alignment's own partial scores (the prefixes of the best
+ * alignment end there), so a mask that is too small reports those.  SSW uses half the read length.
+ * REFUSED with a non-zero return and a message in valign_hip_last_error: mask < 0; everything unbanded placed scores refuse,
+ * with the same texts (opt & 0xF == 1, traceback_policy = 1, score_width = 32, a shape x scoring whose cells could leave int16)
+ * -- placed_wide = 1 does not open the int32 sweep here; every band_width > 0, WHATEVER band_placed says; and the shapes placed
+ * scores send to the row strips (reads of more than 1024 rows, or no register geometry).  The sweep holds 1 KiB of LDS per
+ * wave more than the placed one (the column ring): a block whose rings no longer fit runs with half as many waves, and only
+ * where ONE wave's reference tables come within 1 KiB of the 160 KiB -- a forced geometry on a very long reference, such as
+ * 16 x 10 at 16,200 columns; unforced calls take the row strips long before -- the call is refused too ("... leave no room for
+ * its column ring in the LDS").  opt & 0xF > 1 does nothing, as everywhere.
+ * "ran_subopt" of valign_hip_describe is the track of the last call's sweep, key or rows ("none" before any, or when it was
+ * refused); "subopt_scratch_bytes" the scratch device-resident calls hold; "subopt_ring_cols" the columns a lane group of that
+ * sweep gathers in LDS before the wave writes them out.  tests/subopt_ref.py restates the definition in numpy.              */
+typedef struct {                     /* 20 bytes */
+    int32_t score, read_end, ref_end, score2, ref_end2;
+} valign_hip_subopt;
+
+/* Device-resident: d_subopt = n records.  Asynchronous on hip_stream, no host synchronisation once the scratch exists.  The call
+ * is cut into chunks of whole rounds of the sweep's waves (of whole waves where a round is larger) so that the column maxima (4 bytes per column and pair of pairs) stay
+ * inside an engine-owned scratch of at most 256 MiB; that scratch is reused chunk after chunk in stream order: calls of one
+ * engine that use it belong on one stream.                                                                                   */
+int valign_hip_score_subopt_device(valign_hip_engine *e, int opt, long long n, const void *d_reads,
+                                   const void *d_refs, int mask, void *d_subopt, void *hip_stream);
+
+/* Host pointers in, records out: the chunk pipeline of valign_hip_score_placed_host, 20 bytes per pair on the way back.      */
+int valign_hip_score_subopt_host(valign_hip_engine *e, int opt, int n, const char *const *reads,
+                                 const char *const *refs, int mask, valign_hip_subopt *subopt, int threads);
+
 /* Page-lock a host range and map it for the device (hipHostRegister behind a C symbol, so that an FFI caller needs no
  * HIP binding).  valign_hip_align_host into result buffers that lie inside a registered range -- or inside memory the
  * caller page-locked itself -- skips the library's pinned staging and its host-side copy: the device's copy engine
@@ -489,7 +536,7 @@ int valign_hip_set_half_float_cells(valign_hip_engine *e, int mode);
  * valign_hip_align_cigar_host call copied back, "cigar_rows_scratch_bytes" the rows scratch of the compact format.
  * "ran_placed" is what the last placed-score call ran: key / rows / strip / chain / wide ("none" before any, or when it was
  * refused); "band_placed" is the key of valign_hip_set_band_placed, "placed_wide" that of valign_hip_set_placed_wide.  "ran_span", "span_ref_length" and "span_scratch_bytes"
- * belong to the spanned scores, above.                                                                                         */
+ * belong to the spanned scores, "ran_subopt", "subopt_scratch_bytes" and "subopt_ring_cols" to the suboptimal scores, above. */
 int valign_hip_describe(valign_hip_engine *e, int opt, long long n, char *buf, int cap);
 
 const char *valign_hip_last_error(void);

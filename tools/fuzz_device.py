@@ -4,7 +4,9 @@ destroyed by the hundred, score_device / align_device on torch tensors and rando
 arrays (with and without a registered destination), length-sorted batching, bands, pointer-scratch caps -- every result
 against oracle/cpu_ref; placed Smith-Waterman scores (score_placed_device / _host) against tests/placed_ref.py and, under a band with
 band_placed = 1, against tests/placed_band_ref.py; spanned scores (score_span_device / _host) against tests/span_ref.py wherever the
-unbanded placed scores run, and refused under every band.  What tools/fuzz_parity.py does for the plugin ABI, for the entry points the tests of the device path
+unbanded placed scores run, and refused under every band; suboptimal scores (score_subopt_device / _host, a random mask) against
+tests/subopt_ref.py wherever placed scores ran on the register sweep -- and `--kind subopt` draws nothing but cases for them: shapes up
+to 160 x 300 with a second, mutated copy of the read planted in the reference.  What tools/fuzz_parity.py does for the plugin ABI, for the entry points the tests of the device path
 use; a process that runs it for minutes also exercises the library's set-up and tear-down far more often than the suite.
 
     python -X faulthandler tools/fuzz_device.py --seconds 300 --seed 1
@@ -27,17 +29,21 @@ import band_nw_ref                                                 # noqa: E402
 import placed_band_ref                                             # noqa: E402
 import placed_ref                                                  # noqa: E402
 import span_ref                                                    # noqa: E402
+import subopt_ref                                                  # noqa: E402
 
 
 NW_BAND_CASES = [0]             # cases that also ran the NW variant under the band
 PLACED_CASES = [0]              # cases that also ran placed Smith-Waterman scores
 SPAN_CASES = [0]                # ... and spanned scores
+SUBOPT_CASES = [0]              # ... and suboptimal scores
 BAND_PLACED_CASES = [0]         # banded cases that also ran placed scores on the chain (band_placed = 1)
 
 
-def draw(rng):
-    kind = rng.choice(["short", "short", "mid", "long", "longref", "tiny"])
-    if kind == "tiny":
+def draw(rng, kind=None):
+    kind = kind or rng.choice(["short", "short", "mid", "long", "longref", "tiny"])
+    if kind == "subopt":
+        R, F = int(rng.integers(8, 161)), int(rng.integers(8, 301))
+    elif kind == "tiny":
         R, F = int(rng.integers(1, 24)), int(rng.integers(1, 40))
     elif kind == "short":
         R, F = int(rng.integers(8, 400)), int(rng.integers(8, 900))
@@ -59,6 +65,10 @@ def draw(rng):
         if rng.random() < 0.6:
             of, ef = orr, er
         aff = dict(open_read=orr, ext_read=er, open_ref=of, ext_ref=ef)
+    if kind == "subopt":            # nothing but the register sweep: no band, default tie-breaks
+        return dict(R=R, F=F, n=n, affine=affine, match=match, mismatch=mismatch, gr=gr, gf=gf, aff=aff, seed=int(rng.integers(1, 1 << 30)), ragged=0,
+                    band=0, stream=bool(rng.random() < 0.5), policy=0, cap_mb=0, host=bool(rng.random() < 0.3), threads=int(rng.integers(1, 9)), ckpt=False,
+                    subopt_only=True)
     return dict(R=R, F=F, n=n, affine=affine, match=match, mismatch=mismatch, gr=gr, gf=gf, aff=aff,
                 seed=int(rng.integers(1, 1 << 30)), ragged=int(rng.integers(0, 3)) if rng.random() < 0.3 else 0,
                 band=int(rng.integers(8, 300)) * 2 if (rng.random() < 0.12 and R >= 64) else 0,
@@ -71,6 +81,15 @@ def run(c):
     R, F, n = c["R"], c["F"], c["n"]
     reads, refs = synth.make_pairs(n, R, F, seed=c["seed"], sub_rate=0.1, indel_rate=0.02 if n * R < 300_000 else 0.0, n_run_frac=0.1,
                                    short_frac=0.3, lowercase_frac=0.05, junk_frac=0.05)
+    if c.get("subopt_only") and F > 16:
+        # a second copy of the read's head, three bases changed, somewhere in the reference: a runner-up worth finding
+        rng = np.random.default_rng(c["seed"])
+        L = min(R, F // 2)
+        for p in range(0, n, 2):
+            copy = reads[p, :L].copy()
+            copy[rng.integers(0, L, 3)] = ord("A")
+            at = int(rng.integers(0, F - L + 1))
+            refs[p, at:at + L] = copy
     osc = cpu_ref.Scoring.make(c["match"], c["mismatch"], c["gr"], c["gf"], *(c["aff"].values() if c["affine"] else ()))
     eng = hipkernel.Engine(R, F, hipkernel.Scoring.make(c["match"], c["mismatch"], c["gr"], c["gf"], **c["aff"]))
     try:
@@ -142,7 +161,7 @@ def run(c):
                     if not (np.array_equal(rows.cpu().numpy(), e_rows) and np.array_equal(idx.cpu().numpy(), e_idx)):
                         return "banded NW align_device differs"
             return None
-        for opt in (0, 1):
+        for opt in ((0,) if c.get("subopt_only") else (0, 1)):
             exp = cpu_ref.score(opt, reads, refs, osc, threads=8, affine=c["affine"], wide=True)
             got = eng.score_device(opt, d_reads, d_refs, stream=stream)
             if stream is not None:
@@ -175,6 +194,23 @@ def run(c):
                         h = eng.score_placed_host(0, reads, refs, threads=c["threads"])
                         if not np.array_equal(np.stack([h["score"], h["read_end"], h["ref_end"]], axis=1).astype(np.int64), pexp):
                             return "score_placed_host differs"
+                    # suboptimal scores wherever placed scores ran on the register sweep: the numpy restatement, a mask
+                    # decided by the seed (no further draw)
+                    if eng.describe(0, n)["ran_placed"] in ("key", "rows"):
+                        SUBOPT_CASES[0] += 1
+                        mask = (0, 1, R // 2, R, F, c["seed"] % (F + 2))[c["seed"] % 6]
+                        uexp = subopt_ref.subopt(reads, refs, osc, mask, affine=c["affine"])
+                        got = eng.score_subopt_device(0, d_reads, d_refs, mask, stream=stream)
+                        if stream is not None:
+                            stream.synchronize()
+                        if not np.array_equal(got.cpu().numpy().astype(np.int64), uexp):
+                            return "score_subopt_device differs (%s, mask %d)" % (eng.describe(0, n)["ran_subopt"], mask)
+                        if c["host"]:
+                            h = eng.score_subopt_host(0, reads, refs, mask, threads=c["threads"])
+                            if not np.array_equal(np.stack([h[k] for k in hipkernel.subopt_dtype().names], axis=1).astype(np.int64), uexp):
+                                return "score_subopt_host differs (mask %d)" % mask
+                    if c.get("subopt_only"):
+                        continue
                     # spanned scores wherever placed scores ran: the numpy restatement, unclipped (tests/span_ref.py)
                     SPAN_CASES[0] += 1
                     sexp = span_ref.spans(reads, refs, osc, affine=c["affine"])
@@ -187,7 +223,7 @@ def run(c):
                         h = eng.score_span_host(0, reads, refs, threads=c["threads"])
                         if not np.array_equal(np.stack([h[k] for k in hipkernel.span_dtype().names], axis=1).astype(np.int64), sexp):
                             return "score_span_host differs"
-        if R * F * n <= 30_000_000:
+        if R * F * n <= 30_000_000 and not c.get("subopt_only"):
             akw = dict(affine=True) if c["affine"] else dict(policy="sse" if c["policy"] else "default")
             for opt in (0, 1):
                 e16 = cpu_ref.align(opt, reads, refs, osc, threads=8, **akw)
@@ -216,12 +252,13 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--first", type=int, default=0)
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--kind", choices=["subopt"], default=None, help="draw cases of this kind only (default: the mix)")
     a = ap.parse_args()
     rng = np.random.default_rng(a.seed)
     t0 = time.time()
     i = done = 0
     while time.time() - t0 < a.seconds:
-        c = draw(rng)
+        c = draw(rng, a.kind)
         if i >= a.first:
             if a.verbose:
                 print("case %d: %r" % (i, c), flush=True)
@@ -237,7 +274,8 @@ def main():
                 print("%d cases, %.0f s" % (done, time.time() - t0), flush=True)
         i += 1
     print("ok: %d cases in %.0f s (seed %d), %d of them with the banded NW variant, %d with placed scores, %d with spanned scores, "
-          "%d with banded placed scores" % (done, time.time() - t0, a.seed, NW_BAND_CASES[0], PLACED_CASES[0], SPAN_CASES[0], BAND_PLACED_CASES[0]))
+          "%d with suboptimal scores, %d with banded placed scores" % (done, time.time() - t0, a.seed, NW_BAND_CASES[0], PLACED_CASES[0], SPAN_CASES[0],
+                                                                        SUBOPT_CASES[0], BAND_PLACED_CASES[0]))
     return 0
 
 

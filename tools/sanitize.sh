@@ -52,6 +52,10 @@ echo "== span_ref_length and span_choice of cell_rules.h under AddressSanitizer 
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/span_rules_check.cpp" -o "$OUT/span_rules_asan"
 "$OUT/span_rules_asan"
 
+echo "== subopt_choice of cell_rules.h under AddressSanitizer + UBSan"
+g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/subopt_rules_check.cpp" -o "$OUT/subopt_rules_asan"
+"$OUT/subopt_rules_asan"
+
 echo "== base_classes.h (the byte classifier of the kernels' set-up) under AddressSanitizer + UBSan"
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/base_classes_check.cpp" -o "$OUT/base_classes_asan"
 "$OUT/base_classes_asan"

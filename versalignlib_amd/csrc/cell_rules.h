@@ -314,6 +314,42 @@ inline PlacedChoice span_choice(const RuleInputs &in, int alg, const PlacedFacts
     return c;
 }
 
+// ---- suboptimal scores (valign_hip_score_subopt_*): the placed record plus the best column maximum outside a window of
+// `mask` reference columns around the end cell, from the placed register sweep alone ----
+// A suboptimal call is an unbanded placed call on the register sweep: refused exactly where placed_choice refuses that, with
+// its texts -- placed_wide does not open the int32 sweep here -- and, with texts of its own, for a negative mask, under a band
+// whatever band_placed says, and where placed scores would leave the register sweep for the row strips (the column maxima
+// ride the lane-to-lane hand-over of ONE sweep over all rows).  Otherwise Key or Rows, as placed_choice picks for `G x K`.
+inline PlacedChoice subopt_choice(const RuleInputs &in, int alg, const PlacedFacts &f, int G, int K, int mask = 0) {
+    PlacedFacts plain = f;
+    plain.band_width = 0;
+    plain.placed_wide = false;
+    PlacedChoice c = placed_choice(in, alg, plain, G, K);
+    if (c.route == PlacedRoute::Refused) return c;
+    const char *reason = "";
+    if (mask < 0)
+        reason = "suboptimal scores need mask >= 0";
+    else if (f.band_width > 0)
+        reason = "suboptimal scores are not built for band_width > 0";
+    else if (c.route != PlacedRoute::Key && c.route != PlacedRoute::Rows)
+        reason = "suboptimal scores run on the register sweep only: reads of more than 1024 rows and shapes without a register geometry are refused";
+    if (reason[0]) {
+        c = PlacedChoice{};
+        c.reason = reason;
+    }
+    return c;
+}
+
+// The sweep's suboptimal form adds a ring of `ring_bytes` to every wave's LDS, which the placed plan did not count: the waves
+// of a block, `placed_waves` (the placed plan's) halved until the block's tables and rings fit `block_limit`; 0 where not even
+// one wave's do, which is refused with kSuboptNoRing.
+inline int subopt_block_waves(int wave_lds, int ring_bytes, int placed_waves, int block_limit) {
+    for (int waves = placed_waves; waves >= 1; waves >>= 1)
+        if ((long long)(wave_lds + ring_bytes) * waves <= block_limit) return waves;
+    return 0;
+}
+constexpr const char *kSuboptNoRing = "suboptimal scores: one wave's reference tables leave no room for its column ring in the LDS (a shorter reference, or a geometry of more lanes per group, has it)";
+
 // ---- band_nw = 1: the NW variant under the block band (include/valign_hip.h) ----
 // Consecutive blocks' windows connect -- every in-band cell has a present candidate -- once 2 * (band_width / 2) + 1 columns
 // cover the most a window start advances per row, ceil(F / R).  Narrower bands are refused.

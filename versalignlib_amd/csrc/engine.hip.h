@@ -16,6 +16,8 @@
 //                         PlacedSweep descriptions of it); its host call is record_pipeline with a one-line launch
 //   engine_span.hip ..... spanned Smith-Waterman scores: a placed score plus the begin cell, from a second placed sweep over the
 //                         reversed prefixes (span_kernels.hip.h); its host call is record_pipeline too
+//   engine_subopt.hip ... suboptimal Smith-Waterman scores: the placed sweep's suboptimal form, which also leaves the column
+//                         maxima in a scratch, and subopt_records_kernel (subopt_kernels.hip.h); record_pipeline again
 //   engine_cigar.hip .... the compact result format: records + CIGAR ops encoded on the device behind the walks (cigar_kernels.hip.h)
 //   hip_plugin.hip ...... the plugin ABI and the flat C API over it
 // The closest reference precedent for the staging loops is the OpenCL backend's gather / copy / launch / collect loop
@@ -54,6 +56,7 @@
 #include "pack_kernels.hip.h"
 #include "ragged_kernels.hip.h"
 #include "span_kernels.hip.h"
+#include "subopt_kernels.hip.h"
 #include "strip_kernels.hip.h"
 #include "strip_plan.h"
 
@@ -75,6 +78,7 @@ struct Geometry {
                                    //                     symmetric affine / affine / symmetric linear on half floats]
     const void *fill[2][kFillKernels];      // alignment fill kernels [alg][FillKernel]; nullptr: not compiled for this geometry
     const void *(*placed)(int track, int gaps);      // placed-score kernels (placed_kernels.hip.h); returns nullptr where none is compiled
+    const void *(*subopt)(int track, int gaps);      // suboptimal-score kernels: the full geometries', nullptr elsewhere
 };
 
 template <int G, int K>
@@ -102,14 +106,14 @@ constexpr void set_fast_kernels(Geometry &g) {
 
 template <int G, int K>
 constexpr Geometry fast_geometry() {
-    Geometry g{G, K, false, &wave_lds<G, K>, {}, {}, &placed_kernel<G, K, false>};
+    Geometry g{G, K, false, &wave_lds<G, K>, {}, {}, &placed_kernel<G, K, false>, &subopt_kernel<G, K, false>};
     set_fast_kernels<G, K>(g);
     return g;
 }
 
 template <int G, int K>
 constexpr Geometry full_geometry() {
-    Geometry g{G, K, true, &wave_lds<G, K>, {}, {}, &placed_kernel<G, K, true>};
+    Geometry g{G, K, true, &wave_lds<G, K>, {}, {}, &placed_kernel<G, K, true>, &subopt_kernel<G, K, true>};
     set_fast_kernels<G, K>(g);
     g.fill[0][kFillLinear] = (const void *)&align_fill_kernel<G, K, kAlgSW, false>;
     g.fill[0][kFillLinearSym] = (const void *)&align_fill_kernel<G, K, kAlgSW, true>;
@@ -166,7 +170,7 @@ public:
         static const char *const known[] = {"no_sym", "no_tag", "no_f16", "no_fused", "no_prof_key", "no_overlap", "no_band_chain",
                                             "force_long", "wide_align", "strip_k", "no_single_strip", "no_direct_out", "ragged_min", "chunk_bytes",
                                             "align_chunk_bytes", "direct_bytes", "scratch_cap_mb", "whole_rows", "short_strips", "cigar_rows_mb", "cigar_lanes",
-                                            "span_scratch_bytes"};
+                                            "span_scratch_bytes", "subopt_scratch_bytes"};
         std::string s(env);
         for (size_t at = 0; at <= s.size();) {
             const size_t end = std::min(s.find(',', at), s.size());
@@ -488,6 +492,15 @@ public:
     void score_span_host(int opt, int n, const char *const *reads, const char *const *refs, SpanRec *spans, int threads);
     const char *ran_span() const { return ran_span_.c_str(); }
 
+    // ---- suboptimal Smith-Waterman scores (valign_hip.h: valign_hip_subopt; engine_subopt.hip) ----
+    // The placed record plus score2 / ref_end2: the placed register sweep in its suboptimal form, which also leaves every
+    // column's maximum in an engine-owned scratch, then subopt_records_kernel.  subopt_choice (cell_rules.h) decides what is
+    // refused.  Device-resident: asynchronous on `stream`, in chunks of whole rounds that keep the maxima inside
+    // subopt_scratch_bytes_; calls of one engine belong on one stream.  Host pointers: record_pipeline, 20 bytes per pair.
+    void score_subopt_device(int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int mask, SuboptRec *d_subopt, hipStream_t stream);
+    void score_subopt_host(int opt, int n, const char *const *reads, const char *const *refs, int mask, SuboptRec *subopt, int threads);
+    const char *ran_subopt() const { return ran_subopt_; }
+
     // host-side phases of the last score_host / align_host call
     std::string host_phases() const;
 
@@ -683,6 +696,21 @@ private:
     // one chunk, all of it on `stream`: forward sweep, reversal, reverse sweep, records
     void span_chunk(int c, int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, SpanRec *d_spans, hipStream_t stream);
 
+    // ---- suboptimal scores (engine_subopt.hip) ----
+    // One context per pipeline slot and one for device-resident calls: the column maxima and the placed records of one chunk
+    struct SuboptCtx {
+        DeviceBuffer<unsigned> colmax;
+        DeviceBuffer<PlacedRec> placed;
+        size_t bytes() const { return colmax.bytes() + placed.bytes(); }
+    };
+    // refusals (thrown), then the plan: the base plan where its geometry carries the kernel, else the next full geometry
+    LaunchPlan subopt_plan_for(int alg, int mask, PlacedChoice &choice, int &gaps);
+    long long subopt_chunk_pairs(const LaunchPlan &plan, long long n) const;
+    void ensure_subopt_scratch(int c, const LaunchPlan &plan, long long pairs, hipStream_t stream);
+    // one chunk, all of it on `stream`: the sweep, then the records
+    void subopt_chunk(int c, const LaunchPlan &plan, int track, int gaps, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int mask,
+                      SuboptRec *d_subopt, hipStream_t stream);
+
     // ---- length-sorted batching (score_host, Smith-Waterman) ----
 
     static double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
@@ -818,6 +846,9 @@ private:
     const char *ran_placed_ = "none";                    // what the last placed-score call ran: key / rows / strip / chain / wide (describe)
     std::string ran_span_ = "none";                      // what the last spanned call ran: forward route / reverse route (describe)
     size_t span_scratch_bytes_ = (size_t)dbg_.value("span_scratch_bytes", 256ll << 20);      // device-resident spanned calls: scratch of one chunk
+    const char *ran_subopt_ = "none";                    // what the last suboptimal call ran: key / rows (describe)
+    int subopt_ring_cols_ = 0;                           // ... and the columns of a lane group's ring in its sweep
+    size_t subopt_scratch_bytes_ = (size_t)dbg_.value("subopt_scratch_bytes", 256ll << 20);      // column maxima of one chunk
     const char *ran_result_format_ = "rows";             // of the last alignment call: rows / cigar (describe)
     long long cigar_d2h_bytes_ = 0;                      // what the last align_cigar_host call copied back
     const CigarSink *cigar_ = nullptr;
@@ -871,6 +902,7 @@ private:
     // spanned scores: the reversal scratch, the engine of the reverse sweep
     SpanCtx span_[kSlots + 1];                                   // one per pipeline slot, the last for device-resident calls
     std::unique_ptr<Engine> span_child_;
+    SuboptCtx subopt_[kSlots + 1];                               // one per pipeline slot, the last for device-resident calls
     DeviceBuffer<unsigned> d_brow_;                              // long-read path: strip boundary rows
     DeviceBuffer<BandBlock> d_band_blocks_;                      // the block chain's tables (band_plan_)
     DeviceBuffer<int> d_band_fill_;

@@ -660,6 +660,28 @@ VALIGN_EXPORT int valign_hip_score_span_host(valign_hip_engine *e, int opt, int 
     return flat_guard([&] { e->impl->score_span_host(opt, n, reads, refs, (valign::SpanRec *)spans, threads); });
 }
 
+static_assert(sizeof(valign_hip_subopt) == sizeof(valign::SuboptRec) && sizeof(valign_hip_subopt) == 20, "valign_hip_subopt is the kernels' record");
+
+VALIGN_EXPORT int valign_hip_score_subopt_device(valign_hip_engine *e, int opt, long long n, const void *d_reads, const void *d_refs,
+                                                 int mask, void *d_subopt, void *hip_stream) {
+    if (!e) {
+        g_last_error = "null engine";
+        return 1;
+    }
+    return flat_guard([&] {
+        e->impl->score_subopt_device(opt, n, (const uint8_t *)d_reads, (const uint8_t *)d_refs, mask, (valign::SuboptRec *)d_subopt, (hipStream_t)hip_stream);
+    });
+}
+
+VALIGN_EXPORT int valign_hip_score_subopt_host(valign_hip_engine *e, int opt, int n, const char *const *reads, const char *const *refs,
+                                               int mask, valign_hip_subopt *subopt, int threads) {
+    if (!e) {
+        g_last_error = "null engine";
+        return 1;
+    }
+    return flat_guard([&] { e->impl->score_subopt_host(opt, n, reads, refs, mask, (valign::SuboptRec *)subopt, threads); });
+}
+
 VALIGN_EXPORT int valign_hip_describe(valign_hip_engine *e, int opt, long long n, char *buf, int cap) {
     if (!e || !buf || cap <= 0) return 1;
     const std::string s = e->impl->describe(opt, n);

@@ -78,3 +78,7 @@
 
 // The placed-score kernels of a geometry: defined where its table is (FULL: the geometry is a full one)
 #define VALIGN_PLACED_KERNELS(PREFIX, G, K, FULL) PREFIX const void *placed_kernel<G, K, FULL>(int, int);
+
+// The suboptimal-score kernels (placed_kernels.hip.h: subopt_kernel<G, K, FULL>, the SUB form of score_placed_kernel): 44 instances,
+// all on the six full geometries
+#define VALIGN_SUBOPT_KERNELS(PREFIX, G, K, FULL) PREFIX const void *subopt_kernel<G, K, FULL>(int, int);

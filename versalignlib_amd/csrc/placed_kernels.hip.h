@@ -13,6 +13,8 @@
 // Both track the finished cell h off the dependency chain: the bookkeeping of row q - 1 sits between the links of row q.
 // write_end_cells (trace_kernels.hip.h) combines the lanes into the wave's LDS table; the group leader turns its two end
 // cells into records with plain vector stores.
+// The SUB form of the same kernel (suboptimal scores, valign_hip_score_subopt_*) also sends every column's maximum out of the
+// wave; see SuboptArgs below and subopt_kernels.hip.h.
 #pragma once
 
 #include "cell_rules.h"
@@ -38,6 +40,18 @@ struct PlacedArgs {
 
 constexpr int kPlacedKey = 0, kPlacedRows = 1;
 
+// What the suboptimal-score form of the sweep (valign_hip_score_subopt_*; engine_subopt.hip) adds to a placed launch: where the
+// column maxima go.  Lane G - 1 of a group puts every finished column into the group's ring in LDS; each time the ring is full
+// (and after the last column) the whole wave flushes the rings of its groups, 16 bytes per lane.
+struct SuboptArgs : PlacedArgs {
+    unsigned *colmax;         // one row of col_stride dwords per pair of pairs: colmax[j] of pair A (low half) and pair B (high half)
+    int col_stride;           // dwords, a multiple of 4: flushes are whole, aligned 16-byte stores
+    int ring_ofs;             // bytes from the wave's LDS to its rings (16-byte aligned): kSuboptRingBytes behind the placed tables
+};
+constexpr int kSuboptRingBytes = 1024;                                  // per wave: 64 lanes x 16 bytes, one flush
+constexpr int subopt_ring_cols(int G) { return kSuboptRingBytes / 4 / (kWave / G); }      // columns of a group's ring: 4 G, a power of two
+typedef __attribute__((address_space(3))) unsigned lds_u32;
+
 // The record of an end cell: half-open 0-based ends, zeros for the empty alignment
 __device__ __forceinline__ PlacedRec placed_record(const EndCell e) {
     PlacedRec r;
@@ -48,9 +62,11 @@ __device__ __forceinline__ PlacedRec placed_record(const EndCell e) {
     return r;
 }
 
-template <int G, int K, int GAPS, int TRACK>
+// SUB: the suboptimal-score form (its launches take SuboptArgs).  Every addition sits behind `if constexpr (SUB)`: the sweep
+// loops of the placed instances (SUB false) keep their instructions (DESIGN.md has the comparison against the assembly before).
+template <int G, int K, int GAPS, int TRACK, bool SUB = false>
 __global__ void __launch_bounds__(256)
-score_placed_kernel(const PlacedArgs args) {
+score_placed_kernel(const std::conditional_t<SUB, SuboptArgs, PlacedArgs> args) {
     static_assert(GAPS == kGapLinear || GAPS == kGapSym || GAPS == kGapAffine || GAPS == kGapAffineSym, "placed scores run on int16 cells");
     static_assert(TRACK == kPlacedRows || K <= kPlacedKeyMaxK, "the lane key exists for up to 16 rows per lane");
     using geo = Geo<G, K>;
@@ -104,6 +120,60 @@ score_placed_kernel(const PlacedArgs args) {
     s16x2 up0 = pk(0), h_last = pk(0), f_last = pk(0);
     int j = -l;
 
+    // Suboptimal scores: the column's maximum over the rows below each pair's trimmed read length travels from lane to lane
+    // beside h_last -- lane G - 1 holds column t - (G - 1) complete at step t.  Rows at or beyond the trimmed length do not
+    // count: the key track multiplies them by 0 instead of 2^BITS (their keys then carry the value 0; the placed record keeps
+    // its cell, which no such row ever holds -- they only repeat values down the diagonals), the rows track ANDs a mask.
+    // (The geometry's pad rows lie on top and hold zeros.)
+    constexpr int kRing = subopt_ring_cols(G);
+    s16x2 row_mul[SUB && KEY ? K : 1], row_keep[SUB && !KEY ? K : 1];
+    s16x2 cm_last = pk(0);
+    unsigned ring_lds = 0;
+    if constexpr (SUB) {
+        int trimmed[2];
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            int p = 2 * grp + half;
+            p = p > w.last ? w.last : p;
+            const uint8_t *rd = args.reads + (w.pair0 + p) * args.R;
+            int len = 0;
+            for (int pos = l; pos < args.R; pos += G) {
+                const int c = base_class(rd[pos]);
+                if (c >= 1 && c <= 4) len = pos + 1;
+            }
+#pragma unroll
+            for (int dd = G / 2; dd >= 1; dd >>= 1) {
+                const int other = __shfl_xor(len, dd, kWave);
+                len = other > len ? other : len;
+            }
+            trimmed[half] = len;
+        }
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+            const int pos = l * K + q - pad_rows;
+            const bool in_a = pos < trimmed[0], in_b = pos < trimmed[1];
+            if constexpr (KEY) {
+                row_mul[q] = s16x2{(short)(in_a ? 1 << kKeyBits : 0), (short)(in_b ? 1 << kKeyBits : 0)};
+                asm volatile("" : "+v"(row_mul[q]));
+            } else {
+                row_keep[q] = s16x2{(short)(in_a ? -1 : 0), (short)(in_b ? -1 : 0)};
+            }
+        }
+        ring_lds = lds_offset(w.prof) + args.ring_ofs;
+    }
+    // the wave's rings -> the rows of its pairs of pairs, columns [base, base + kRing): lane i moves dwords 4 i .. 4 i + 3
+    auto flush = [&](int base) __attribute__((always_inline)) {
+        if constexpr (SUB) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            const int g = (4 * lane) / kRing, c = base + (4 * lane) % kRing;
+            const u32x4 v = *(lds_cu32x4 *)(ring_lds + 16 * lane);
+            const long long pp = w.pair0 / 2 + g;
+            if (2 * pp < args.n && c < args.col_stride) *reinterpret_cast<u32x4 *>(args.colmax + (size_t)pp * args.col_stride + c) = v;
+            __builtin_amdgcn_wave_barrier();
+        }
+    };
+
     // LDS fetches run one step ahead of the arithmetic, as in score_kernel
     unsigned pa[K / 2], pb[K / 2];
     s16x2 S0[K], S1[K];
@@ -123,6 +193,8 @@ score_placed_kernel(const PlacedArgs args) {
         up0 = as_pk(group_prev_or_zero<G>(as_u32(h_last), lmask));
         s16x2 fup0 = pk(0);
         if (AFFINE) fup0 = as_pk(group_prev_or_zero<G>(as_u32(f_last), lmask));
+        s16x2 cm_in = pk(0);
+        if constexpr (SUB) cm_in = as_pk(group_prev_or_zero<G>(as_u32(cm_last), lmask));      // this column, as far as the lanes before have it
         merge_profile<K>(pa, pb, S);                                     // step t's scores
         lds_load_lane<K>(lane_base + ca_next * geo::kPairStride, pa);     // step t+1's profile rows
         lds_load_lane<K>(lane_base + cb_next * geo::kPairStride, pb);
@@ -131,11 +203,14 @@ score_placed_kernel(const PlacedArgs args) {
         if (!MASKED || (unsigned)j < (unsigned)F) {
             const s16x2 tt = pk((short)t);
             s16x2 step_key = pk(0);
+            s16x2 col_own = pk(0);                                       // SUB, rows track: the maximum of the lane's counted rows
             // end-cell bookkeeping of one finished cell (SW cells are >= 0: rb - h cannot wrap)
             auto track = [&](int q, s16x2 hq) __attribute__((always_inline)) {
                 if (KEY) {
-                    step_key = pk_max(step_key, pk_mad_u(hq, key_mul, row_key[q]));
+                    if constexpr (SUB) step_key = pk_max(step_key, pk_mad_u(hq, row_mul[q], row_key[q]));
+                    else step_key = pk_max(step_key, pk_mad_u(hq, key_mul, row_key[q]));
                 } else {
+                    if constexpr (SUB) col_own = pk_max(col_own, as_pk(as_u32(hq) & as_u32(row_keep[q])));
                     const s16x2 changed = (rb[q] - hq) >> fifteen;       // 0xFFFF where h beats the row's best: the first column is kept
                     fc[q] = as_pk((as_u32(changed) & as_u32(tt)) | (~as_u32(changed) & as_u32(fc[q])));
                     rb[q] = pk_max(rb[q], hq);
@@ -207,6 +282,18 @@ score_placed_kernel(const PlacedArgs args) {
                 fc[0] = as_pk((as_u32(changed) & as_u32(tt)) | (~as_u32(changed) & as_u32(fc[0])));
                 rb[0] = pk_max(rb[0], step_key);
             }
+            if constexpr (SUB) {
+                // keys travel as they are (the larger key holds the larger value); lane G - 1 drops the row bits
+                cm_last = pk_max(cm_in, KEY ? step_key : col_own);
+                if (l == G - 1) {
+                    const s16x2 done = KEY ? (s16x2)((u16x2)cm_last >> (unsigned short)kKeyBits) : cm_last;
+                    *(lds_u32 *)(ring_lds + (grp * kRing + (j & (kRing - 1))) * 4) = as_u32(done);
+                }
+            }
+        }
+        if constexpr (SUB) {
+            const int col = t - (G - 1);                                  // wave-uniform: the column the last lanes just finished
+            if (col >= 0 && (((col + 1) & (kRing - 1)) == 0 || col == F - 1)) flush(col & ~(kRing - 1));
         }
         ++j;
         code_addr += 2;
@@ -276,6 +363,31 @@ const void *placed_kernel(int track, int gaps) {
         placed[kPlacedRows][kGapAffineSym] = (const void *)&score_placed_kernel<G, K, kGapAffineSym, kPlacedRows>;
     }
     return (track == kPlacedKey || track == kPlacedRows) && gaps >= 0 && gaps < 4 ? placed[track][gaps] : nullptr;
+}
+#endif
+
+// The suboptimal-score instances, on the six full geometries only: the key track where K <= 16, the rows track on all six, the
+// four gap forms each (5 x 4 + 6 x 4 = 44 instances).  A call whose plan is another geometry is re-planned onto the next full one.
+template <int G, int K, bool FULL>
+const void *subopt_kernel(int track, int gaps);
+
+#ifdef VALIGN_KERNEL_PART_TU
+template <int G, int K, bool FULL>
+const void *subopt_kernel(int track, int gaps) {
+    const void *sub[2][4] = {};
+    if constexpr (FULL) {
+        if constexpr (K <= kPlacedKeyMaxK) {
+            sub[kPlacedKey][kGapLinear] = (const void *)&score_placed_kernel<G, K, kGapLinear, kPlacedKey, true>;
+            sub[kPlacedKey][kGapSym] = (const void *)&score_placed_kernel<G, K, kGapSym, kPlacedKey, true>;
+            sub[kPlacedKey][kGapAffine] = (const void *)&score_placed_kernel<G, K, kGapAffine, kPlacedKey, true>;
+            sub[kPlacedKey][kGapAffineSym] = (const void *)&score_placed_kernel<G, K, kGapAffineSym, kPlacedKey, true>;
+        }
+        sub[kPlacedRows][kGapLinear] = (const void *)&score_placed_kernel<G, K, kGapLinear, kPlacedRows, true>;
+        sub[kPlacedRows][kGapSym] = (const void *)&score_placed_kernel<G, K, kGapSym, kPlacedRows, true>;
+        sub[kPlacedRows][kGapAffine] = (const void *)&score_placed_kernel<G, K, kGapAffine, kPlacedRows, true>;
+        sub[kPlacedRows][kGapAffineSym] = (const void *)&score_placed_kernel<G, K, kGapAffineSym, kPlacedRows, true>;
+    }
+    return (track == kPlacedKey || track == kPlacedRows) && gaps >= 0 && gaps < 4 ? sub[track][gaps] : nullptr;
 }
 #endif
 
