@@ -530,6 +530,8 @@ int valign_hip_set_half_float_cells(valign_hip_engine *e, int mode);
  * "ran_score_geometry" / "ran_align_geometry" name the compiled geometry, "GxK" (group lanes x rows per lane), whose kernel
  * the last register-sweep score launch / the last register-path fill launch ran -- the engine's own, its latency plan's or the
  * full geometry a fallback kernel moved the call to -- and are "none" before any and for every other route;
+ * "ran_score_sym_affine" is present only where the last score call launched the int16 symmetric affine Smith-Waterman kernel,
+ * and names the form of its sweep that ran: "max3" (biased cells, three-operand maxima) or "sources" (gap sources);
  * "align_ptr_bytes_per_pair" / "align_ckpt_bytes_per_pair" are the pointer-stream and checkpoint bytes a pair holds in the plan
  * of the last alignment call, "align_scratch_bytes" the pointer scratch the engine holds after it.
  * "ran_result_format" is "rows" or "cigar" for the last alignment call, "cigar_d2h_bytes" what the last

@@ -20,6 +20,7 @@ struct RuleInputs {
     int R = 0, F = 0;
     bool sse_policy = false;
     bool no_sym = false, no_tag = false, no_f16 = false, no_prof_key = false;
+    bool no_max3 = false;           // debug switch: int16 symmetric affine SW scores on the gap-source form always
 };
 
 // int16 DP cells: the reference wraps silently.  Scores and alignments switch to int32 cells on the strip path where they could.
@@ -155,6 +156,31 @@ inline int score_gap_form(const RuleInputs &in, int alg, int R, int F, int rows)
     return gaps;
 }
 inline bool gap_form_f16(int gaps) { return gaps == kGapSymF16 || gaps == kGapAffineSymF16 || gaps == kGapAffineF16; }
+
+// ---- the two forms of score_kernel<G, K, kAlgSW, kGapAffineSym> (dp_kernels.hip.h) ----
+// The biased form keeps every int16 cell as value + B and takes its maxima three at a time with the packed half-float
+// maximum, which is an integer maximum while every operand's bit pattern lies in [0x0400, 0x7BFF], the positive normal halves.
+// With the magnitudes o = -open, x = -extend and m = the most a substitution score takes off a cell, the smallest operand of
+// the recurrence is B - o - x or B - m (the window proof is at the kernel's step), so B = 1024 + o + x + m keeps all of them at
+// or above 0x0400 ...
+constexpr int kMax3WindowLow = 0x0400, kMax3WindowHigh = 0x7BFF;
+inline int sym_affine_bias(const Scoring &sc) {
+    const int o = -sc.open_ref, x = -sc.ext_ref, m = std::max({0, -sc.mismatch, -sc.match});
+    return kMax3WindowLow + o + x + m;
+}
+// ... and the form is legal where B plus the largest cell (counted as in int16_range_ok, a positive mismatch score included)
+// stays at or below 0x7BFF.  R, F: of the launch (the padded ones of a length-sorted launch: conservative for every group).
+// Asked only where score_gap_form has answered kGapAffineSym for Smith-Waterman; beyond the window the gap-source form runs.
+inline bool sym_affine_max3_ok(const RuleInputs &in, int R, int F) {
+    const Scoring &sc = in.sc;
+    if (in.no_max3 || !sc.affine || sc.open_read != sc.open_ref || sc.ext_read != sc.ext_ref) return false;
+    if (sc.open_ref > 0 || sc.ext_ref > 0) return false;
+    const long long B = sym_affine_bias(sc);
+    const long long hi = (long long)std::min(R, F) * std::max({sc.match, sc.mismatch, 0}) + 1;
+    return B - kMax3WindowLow <= 1024 && B + hi <= kMax3WindowHigh;
+}
+// describe()'s name of the form the last such launch ran (ran_score_sym_affine)
+inline const char *ran_sym_affine_name(bool max3) { return max3 ? "max3" : "sources"; }
 
 // Which fill kernel an alignment call of this mode takes on a G x K geometry, and what its pointer stream looks like.
 struct FillChoice {

@@ -30,6 +30,8 @@
 //   * Recurrence variants (GAPS), packed instructions per register (= per two cells) incl. the
 //     profile merge: two linear gap scores 6 + maximum tracking, one shared gap score 5 +
 //     tracking, affine 10 + tracking, affine with the same open/extend for both directions 9 + tracking (Smith-Waterman:
+//     inside the window of its biased form 8 + 1/2 -- every int16 cell kept as value + B, maxima three at a time through
+//     v_pk_maximum3_f16, which is an integer maximum on bit patterns in [0x0400, 0x7BFF]; beyond it
 //     9 on gap SOURCES, tracked once per two steps -- 9 + (K + 1) / 2K; see score_kernel's step).  Where every
 //     cell provably stays a small integer the same recurrences run on packed HALF FLOATS, which
 //     gfx950 gives a three-operand maximum (v_pk_maximum3_f16) and a free [0, 1] clamp on the
@@ -80,7 +82,15 @@ struct ScoreArgs {
     int refc_stride;          // bytes of one group's interleaved class-code array
     int wave_lds;             // bytes of LDS per wave
     short match, mismatch;
-    short gap_read, gap_ref;                       // linear model, all <= 0
+    union {
+        struct {
+            short gap_read, gap_ref;               // linear model, all <= 0
+        };
+        // The affine kernels never read the linear model.  A launch of score_kernel<G, K, kAlgSW, kGapAffineSym> carries in
+        // its place what selects the form of that sweep: > 0 the biased three-operand-maximum form, and its bias B (cell_rules.h:
+        // sym_affine_max3_ok / sym_affine_bias); 0 the gap-source form.  No offset and no size changes for any kernel.
+        int sym_max3_bias;
+    };
     short open_read, ext_read, open_ref, ext_ref;  // affine extension, all <= 0
     // Length-sorted batches (ragged_kernels.hip.h; Engine::ragged_finish): one launch sweeps several packed groups
     // of pairs that share the read stride R but have their own reference stride.  Blocks
@@ -118,6 +128,25 @@ template <int G>
 __device__ __forceinline__ unsigned group_prev_or_zero(unsigned v, unsigned lmask) {
     if (G == 16) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111 /* row_shr:1 */, 0xF, 0xF, true);
     return from_prev_lane(v) & lmask;
+}
+
+// ... and a border value instead of 0 in the group's first lane; `lead_border` holds it in that lane and 0 in every other.
+// Groups of 16: OR-ed onto the zero that row_shr:1 with bound_ctrl delivers there, which folds into ONE v_or_b32 with a DPP
+// operand (a DPP move that keeps `old` would need a copy of the border in front of it)
+// (every lane takes part in the shift: the move is never written under a lane condition)
+template <int G>
+__device__ __forceinline__ s16x2 group_prev_or(s16x2 v, s16x2 lead_border, unsigned lmask) {
+    return as_pk(group_prev_or_zero<G>(as_u32(v), lmask) | as_u32(lead_border));
+}
+// max(a, b) and max(a, b, c) of int16 values whose bit patterns all lie in [0x0400, 0x7BFF], the positive normal half floats:
+// there the half-float order is the integer order and a maximum returns one of its operands bit for bit, so gfx950's
+// v_pk_maximum3_f16 is an integer maximum of three
+__device__ __forceinline__ s16x2 pk_max_h(s16x2 a, s16x2 b) {
+    return __builtin_bit_cast(s16x2, __builtin_elementwise_maximum(__builtin_bit_cast(f16x2, a), __builtin_bit_cast(f16x2, b)));
+}
+__device__ __forceinline__ s16x2 pk_max3_h(s16x2 a, s16x2 b, s16x2 c) {
+    return __builtin_bit_cast(s16x2, __builtin_elementwise_maximum(__builtin_elementwise_maximum(__builtin_bit_cast(f16x2, a), __builtin_bit_cast(f16x2, b)),
+                                                                  __builtin_bit_cast(f16x2, c)));
 }
 
 // LDS bank conflicts of one profile fetch, modelled per MI355X_MICROARCH.md section LDS: every lane of
@@ -714,6 +743,10 @@ score_kernel(const ScoreArgs args) {
         cb_next = *(lds_cu8 *)(code_addr + 3);
     }
 
+    // The kernel with two steady loops (SOURCES) walks the code array with a pointer, so that each loop's addressing is worked
+    // out from LDS address uses (one add per trip, the four prefetch offsets in the instructions) whichever loop it is
+    lds_cu8 *code_ptr = (lds_cu8 *)code_addr;
+
     // One step of the skewed sweep.  MASKED steps (NW variant only) EXEC-mask lanes whose column is outside
     // [0, F) (pipeline fill and drain); in the steady phase every lane is inside.
     // TRACK selects how a step feeds the running SW maximum: kTrackAll = every diag+S of the step;
@@ -751,8 +784,13 @@ score_kernel(const ScoreArgs args) {
             merge_profile<K>(pa, pb, S);                                     // step t's scores
             lds_load_lane<K>(lane_base + ca_next * geo::kPairStride, pa);     // step t+1's profile rows
             lds_load_lane<K>(lane_base + cb_next * geo::kPairStride, pb);
-            ca_next = *(lds_cu8 *)(code_addr + 4);                            // step t+2's slab numbers
-            cb_next = *(lds_cu8 *)(code_addr + 5);
+            if constexpr (SOURCES) {
+                ca_next = code_ptr[4];
+                cb_next = code_ptr[5];
+            } else {
+                ca_next = *(lds_cu8 *)(code_addr + 4);                        // step t+2's slab numbers
+                cb_next = *(lds_cu8 *)(code_addr + 5);
+            }
         }
         if (!MASKED || (unsigned)j < (unsigned)F) {
             if (!PIPE) {
@@ -955,7 +993,8 @@ score_kernel(const ScoreArgs args) {
             row_tilt = cell_add(row_tilt, col_step);
         }
         ++j;
-        code_addr += 2;
+        if constexpr (SOURCES) code_ptr += 2;
+        else code_addr += 2;
     };
 
     using all_t = std::integral_constant<int, kTrackAll>;
@@ -974,11 +1013,86 @@ score_kernel(const ScoreArgs args) {
         static_assert(G - 1 + 1 + 2 <= kCodePad, "the unmasked sweep and its prefetch stay inside the code pad");
         const int steps = F + G - 1 - lead;
         int t = 0;
-        for (; t + 1 < steps; t += 2) {        // two steps per trip: loop-carried registers swap roles
-            step(std::false_type{}, first_t{}, S0, S1);    // instead of being copied (+4 % SW, +4 % affine
-            step(std::false_type{}, second_t{}, S1, S0);   // together with the pipelined fetch)
+        bool biased = false;
+        if constexpr (SOURCES) {
+            biased = args.sym_max3_bias > 0;       // wave-uniform: the same sweep in its biased form
+            if (biased) {
+                const s16x2 bias_c = pk((short)args.sym_max3_bias);
+                const s16x2 lead_bias = as_pk(as_u32(bias_c) & ~lmask);          // the bias in the group's first lane, zero below it
+                // One step of the biased form.  The hand-over, the pipelined fetches and the code pointer are the step's above.
+                auto biased_step = [&](s16x2 (&S)[K]) __attribute__((always_inline)) {
+                    const s16x2 diag0 = up0;
+                    up0 = group_prev_or<G>(h_last, lead_bias, lmask);      // the group's first lane reads the bias, the zero of this form
+                    merge_profile<K>(pa, pb, S);
+                    lds_load_lane<K>(lane_base + ca_next * geo::kPairStride, pa);
+                    lds_load_lane<K>(lane_base + cb_next * geo::kPairStride, pb);
+                    ca_next = code_ptr[4];
+                    cb_next = code_ptr[5];
+                    // Every cell is kept as value + B (bias_c) and the Gotoh cell of the half-float kernel above runs on it: adds
+                    // and subtracts are plain packed int16, maxima go three at a time through v_pk_maximum3_f16 --
+                    //   d = diag + S;  e = max3(E - ext, HO, B);  f = max(f - ext, ho);  h = max3(d, e, f);  ho = h - open
+                    // -- perm, add, 3 sub, 1 max, 2 max3: 8 packed instructions per register, plus K / 2 for the tracking (every
+                    // step: gap scores, not sources, so there is no pair trick).  B in E's max3 is the zero floor of the whole cell.
+                    // THE WINDOW.  A half-float maximum is an integer maximum as long as every operand's bit pattern lies in
+                    // [0x0400, 0x7BFF].  With o = -open, x = -ext, m = max(0, -mismatch, -match):  e >= B,  h >= B,  ho >= B - o,
+                    // f >= ho >= B - o (by induction from the border f = B),  e - ext >= B - x,  f - ext >= B - o - x,  d >= B - m,
+                    // so B = 1024 + o + x + m (sym_affine_bias) keeps every operand at or above 0x0400 and no subtract wraps or needs
+                    // a clamp; nothing exceeds B + the largest cell, and the engine launches this form only where that is at most
+                    // 0x7BFF (sym_affine_max3_ok).  Nothing is ever converted to or from a half float.  A lane outside the columns
+                    // or on padding rows fetches scores of 0 and stays at exactly B: max3(B, max3(B - x, B - o, B), max(B - x, B - o)).
+                    // pass1(q) -- diag + S and E of row q, which only need the previous column -- sits between the links of the
+                    // dependent chain down the column (f, h, ho), one row ahead, as in the half-float kernel.
+                    s16x2 d_cur, e_cur, d_prev = bias_c;
+                    auto pass1 = [&](int q, s16x2 &d, s16x2 &e) __attribute__((always_inline)) {
+                        d = (q == 0 ? diag0 : Hl[q - 1]) + S[q];
+                        e = pk_max3_h(El[q] - e_read, HOl[q], bias_c);
+                        El[q] = e;
+                    };
+                    s16x2 ho = up0 - o_ref;
+                    pass1(0, d_cur, e_cur);
+                    // F of the lane above, B in the group's first lane (fetched behind the first row's pass 1: see the gap-source form)
+                    s16x2 f = group_prev_or<G>(f_last, lead_bias, lmask), h = bias_c;
+#pragma unroll
+                    for (int q = 0; q < K; ++q) {
+                        f = pk_max_h(f - e_ref, ho);
+                        s16x2 d_next = bias_c, e_next = bias_c;
+                        if (q + 1 < K) pass1(q + 1, d_next, e_next);        // before Hl[q] is overwritten
+                        h = pk_max3_h(d_cur, e_cur, f);
+                        Hl[q] = h;
+                        ho = h - o_ref;
+                        HOl[q] = ho;
+                        if (q & 1) best = pk_max3_h(best, d_prev, d_cur);
+                        else if (q == K - 1) best = pk_max_h(best, d_cur);
+                        d_prev = d_cur;
+                        d_cur = d_next;
+                        e_cur = e_next;
+                    }
+                    h_last = h;
+                    f_last = f;
+                    code_ptr += 2;
+                };
+                // every border is B, H - open of the border B - open
+#pragma unroll
+                for (int q = 0; q < K; ++q) {
+                    Hl[q] = El[q] = bias_c;
+                    HOl[q] = bias_c - o_ref;
+                }
+                up0 = h_last = f_last = best = bias_c;
+                for (; t + 1 < steps; t += 2) {        // (gap scores, not sources: both steps of a trip track)
+                    biased_step(S0);
+                    biased_step(S1);
+                }
+                if (t < steps) biased_step(S0);
+                best = best - bias_c;                  // the score is best - B
+            }
         }
-        if (t < steps) step(std::false_type{}, all_t{}, S0, S1);
+        if (!biased) {
+            for (; t + 1 < steps; t += 2) {        // two steps per trip: loop-carried registers swap roles
+                step(std::false_type{}, first_t{}, S0, S1);    // instead of being copied (+4 % SW, +4 % affine
+                step(std::false_type{}, second_t{}, S1, S0);   // together with the pipelined fetch)
+            }
+            if (t < steps) step(std::false_type{}, all_t{}, S0, S1);
+        }
     } else {
         // The NW variant's result needs every lane frozen at the last column: its fill and drain steps stay masked
         const int steps = F + G - 1;

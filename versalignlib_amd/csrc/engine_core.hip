@@ -128,7 +128,10 @@ std::string Engine::describe(int opt, long long n) const {
              ran_span_.c_str(), span_ref_length(rule_inputs()), (long long)span_[kSlots].bytes(),
              ran_subopt_, (long long)subopt_[kSlots].bytes(), subopt_ring_cols_,
              ran_geometry(ran_score_geo_).c_str(), ran_geometry(ran_align_geo_).c_str());
-    return buf;
+    std::string out(buf);
+    if (ran_score_sym_affine_)          // only where the last score call ran the int16 symmetric affine SW kernel
+        out.insert(out.size() - 1, std::string(", \"ran_score_sym_affine\": \"") + ran_score_sym_affine_ + "\"");
+    return out;
 }
 
 void Engine::band_block_shape(int &block_rows, int &col_align) const {

@@ -16,6 +16,7 @@ void Engine::score_device(int opt, long long n, const uint8_t *d_reads, const ui
         host_stats_ = HostStats{};
         ran_score_cells_ = 0;
         ran_score_geo_ = nullptr;
+        ran_score_sym_affine_ = nullptr;
     }
     if (score_width_ == 16 && !score_int16_ok(alg))
         throw std::runtime_error("shape x scoring can leave the int16 range of the DP cells (read_length " +
@@ -82,6 +83,14 @@ void Engine::launch_score(const LaunchPlan &plan, int alg, int R, int F, long lo
     const void *fn = plan.geo->kernel[alg][gaps];
     ran_score_cells_ |= gap_form_f16(gaps) ? kRanF16 : kRanInt16;
     ran_score_geo_ = plan.geo;
+    // int16 symmetric affine Smith-Waterman: the biased three-operand-maximum form inside its window, else gap sources.  Asked
+    // about the engine's shape, which holds every launch of a length-sorted call: one form per call.
+    // (the member shares its place with the linear model's gap scores, which no affine kernel reads: written for this kernel only)
+    if (alg == kAlgSW && gaps == kGapAffineSym) {
+        const bool max3 = sym_affine_max3_ok(rule_inputs(), R_, F_);
+        a.sym_max3_bias = max3 ? sym_affine_bias(sc_) : 0;
+        ran_score_sym_affine_ = ran_sym_affine_name(max3);
+    }
     const int block_lds = plan.lds.total * plan.waves_per_block;
     if (block_lds > kDefaultBlockLds)
         hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, block_lds),
@@ -211,6 +220,7 @@ void Engine::score_host(int opt, int n, const char *const *reads, const char *co
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ran_score_cells_ = 0;
     ran_score_geo_ = nullptr;
+    ran_score_sym_affine_ = nullptr;
     const size_t per_pair = (size_t)R_ + F_;
     // Long reads on row strips: their launches follow one another on one stream (the strips' boundary rows are one scratch) and
     // a 48 MB chunk of 10 kbp pairs is 1 200 waves for 3 500 resident ones -- each launch runs at a third of the device.
