@@ -98,7 +98,11 @@ int vh_time_calls(vh_plugin *p, int opt, int n, const uint8_t *reads, const uint
  * delete[]s by the calling thread.  A measuring aid for bench.py's `abi` object.                            */
 int vh_alloc_probe(int n, int row_bytes, int threads, double *seconds_out);
 
-/* delete_alignment_kernel + dlclose + free.                                          */
+/* delete_alignment_kernel + free; the library stays loaded.  A library has ONE pair of
+ * globals (_parameters / _logger) however many kernels are spawned from it, and they
+ * point into the vh_plugin that called vh_spawn / vh_reapply_params last: a global that
+ * holds a member of the closing plugin is re-pointed at the youngest surviving plugin
+ * of the same library, or at null when none survives -- never left dangling.         */
 void vh_close(vh_plugin *p);
 
 /* Lines the plugin sent to the injected logger since the last call (newline

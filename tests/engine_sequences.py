@@ -1,0 +1,556 @@
+"""Sequences of key changes and calls for ONE long-lived hipkernel.Engine, and the runner that holds such an engine against the
+references and against new engines (tests/test_engine_sequences.py, tests/test_gpu_engine_sequences.py,
+tools/fuzz_device.py --kind sequence).
+
+Every other GPU test creates an engine, sets its keys once, makes one kind of call and closes it.  A host keeps one engine for
+hours and flips band_width, score_width and traceback_policy between calls, and the engine carries plans, tables, contexts,
+pipeline state and grow-only scratch from call to call (class Engine, versalignlib_amd/csrc/engine.hip.h).  Here:
+
+  sequence(world, seed) ... a pure function -> a list of steps, drawn from synth._stream.  A step is a key change (one setter,
+                            one new value) or a call (entry point, algorithm, a slice of the world's pairs, threads / mask /
+                            extended where the entry point reads them).
+  State ................... the current value of every key; configure(engine, state) applies one to a new engine.
+  Runner .................. one engine runs the whole sequence on one non-default stream; every call is held, bit for bit,
+                            against the reference of the operation the state selects, and against a NEW engine configured to
+                            the same state that makes the same call on the same data.
+
+The generator needs no GPU; the runner imports torch when it is created."""
+import functools
+
+import numpy as np
+
+from versalignlib_amd import synth
+
+SW, NW = 0, 1
+
+# ---- the model of the state -------------------------------------------------------------------------------------------------
+KEYS = ("band_width", "band_alignments", "band_nw", "band_placed", "placed_wide", "trace_checkpoints", "score_width",
+        "traceback_policy", "ragged_batching", "host_packing", "half_float_cells", "pointer_scratch_cap_mb")
+DEFAULTS = {"band_width": 0, "band_alignments": 0, "band_nw": 0, "band_placed": 0, "placed_wide": 0, "trace_checkpoints": 0,
+            "score_width": 0, "traceback_policy": 0, "ragged_batching": 0, "host_packing": 1, "half_float_cells": 1,
+            "pointer_scratch_cap_mb": 0}
+# pointer_scratch_cap_mb can only be SET: 0 means "leave the cap as it is" to the library, so the state never returns to 0
+SET_ONLY_POSITIVE = ("pointer_scratch_cap_mb",)
+
+FAMILIES = ("score", "rows", "cigar", "placed", "span", "subopt")
+ENTRIES_OF = {"score": ("score_device", "score_host"), "rows": ("align_device", "align_host"),
+              "cigar": ("align_cigar_device", "align_cigar_host"), "placed": ("score_placed_device", "score_placed_host"),
+              "span": ("score_span_device", "score_span_host"), "subopt": ("score_subopt_device", "score_subopt_host")}
+ENTRY_POINTS = tuple(e for f in FAMILIES for e in ENTRIES_OF[f])
+FAMILY_OF = {e: f for f in FAMILIES for e in ENTRIES_OF[f]}
+
+LADDER = (1, 7, 40, 130)            # batch sizes: scratch buffers are reused, regrown and reused smaller
+POOL = 160                          # pairs of a world; a call takes a slice of them
+CALLS = 45                          # calls drawn per sequence (the repairs at the end may add a few)
+SUBOPT_CALLS = 6                    # ... of which suboptimal ones: two (world, scoring) combinations refuse every one by definition
+
+# The smallest shapes at which each route still exists.  short: the register sweep, the fused / direct small host calls, the
+# ragged classes, the block chain under a band.  long: plan_ is the long plan by construction, alignments take the row strips
+# on four 512-row strips, placed scores the strip route.  tiny: fewer rows than any geometry has.
+WORLDS = {
+    "short": {"R": 150, "F": 200, "bands": (16, 40), "scorings": ("linear", "sym_affine", "affine4", "wide"), "seeds": (1, 2, 3)},
+    "long": {"R": 1600, "F": 96, "bands": (24, 64), "scorings": ("linear", "sym_affine", "affine4"), "seeds": (1, 2, 3)},
+    "tiny": {"R": 12, "F": 20, "bands": (4, 12), "scorings": ("linear", "sym_affine", "affine4"), "seeds": (1, 2, 3)},
+}
+# match, mismatch, gap_read, gap_ref [, open_read, ext_read, open_ref, ext_ref]; wide: cells leave int16 at 150 x 200
+SCORINGS = {"linear": (2, -1, -3, -3), "sym_affine": (2, -1, -3, -3, -5, -1, -5, -1), "affine4": (2, -1, -3, -3, -6, -1, -4, -2),
+            "wide": (600, -1, -3, -3)}
+# Entry points that no state lets succeed (include/valign_hip.h, "REFUSED" of the suboptimal scores): reads of more than
+# 1 024 rows take the row strips, and a shape x scoring whose cells can leave int16 is refused whatever placed_wide says
+NEVER_SUCCEEDS = {("long", s): ENTRIES_OF["subopt"] for s in WORLDS["long"]["scorings"]}
+NEVER_SUCCEEDS[("short", "wide")] = ENTRIES_OF["subopt"]
+
+
+def key_values(world, key):
+    """Every value the key takes in this world's sequences (the default among them, but for the set-only keys)."""
+    if key == "band_width":
+        return (0,) + tuple(WORLDS[world]["bands"])
+    if key == "score_width":
+        return (0, 16, 32)
+    if key == "ragged_batching":
+        return (0, 1, 2)
+    if key == "pointer_scratch_cap_mb":
+        return (2, 64)
+    return (0, 1)
+
+
+def initial_state():
+    return dict(DEFAULTS)
+
+
+def apply_step(state, step):
+    """The state after a key-change step (a new dict); a call leaves it alone."""
+    if step["kind"] != "set":
+        return state
+    if step["key"] in SET_ONLY_POSITIVE and step["value"] <= 0:
+        raise ValueError("%s can only be set to a positive value" % step["key"])
+    out = dict(state)
+    out[step["key"]] = step["value"]
+    return out
+
+
+def configure(engine, state):
+    """Apply a whole state to a new engine, key by key in the order of KEYS."""
+    for key in KEYS:
+        if key in SET_ONLY_POSITIVE and state[key] == 0:
+            continue                        # never set: the engine's own default
+        getattr(engine, "set_" + key)(state[key])
+
+
+def pairs(world):
+    """The world's pairs: mutated copies with indels, N runs, truncated (NUL-padded) pairs, lower case and junk bytes."""
+    return _pairs(world)
+
+
+@functools.lru_cache(maxsize=None)
+def _pairs(world):
+    w = WORLDS[world]
+    reads, refs = synth.make_pairs(POOL, w["R"], w["F"], seed=1000 + 7 * w["R"] + w["F"], sub_rate=0.1, indel_rate=0.03, n_run_frac=0.1,
+                                   short_frac=0.25, lowercase_frac=0.05, junk_frac=0.05)
+    reads.setflags(write=False)
+    refs.setflags(write=False)
+    return reads, refs
+
+
+# ---- the generator ----------------------------------------------------------------------------------------------------------
+class _Draw:
+    def __init__(self, world, seed):
+        self.r = synth._stream(7000 + int(seed), 1 + sorted(WORLDS).index(world), (8192,))
+        self.k = 0
+
+    def pick(self, lo, hi):
+        v = int(lo + int(self.r[self.k] % np.uint64(hi - lo + 1)))
+        self.k += 1
+        return v
+
+    def choice(self, items):
+        return items[self.pick(0, len(items) - 1)]
+
+
+def _blockers(world, state, family, alg):
+    """What, by the header's refusal rules, stands between this state and a call of the family -- a list of alternative
+    single-key remedies for the first reason found, [] when nothing does or nothing helps.  Only steers the generator (so that
+    sequences are not mostly refusals); the tests never read it.  The short world is judged as if its scoring were the wide one."""
+    band, wide_scoring = state["band_width"], world == "short"
+    if family in ("placed", "span", "subopt") and alg == NW:
+        return []
+    if family == "score":
+        if band > 0 and alg == NW and not state["band_nw"]:
+            return [("band_nw", 1), ("band_width", 0)]
+        if band == 0 and wide_scoring and state["score_width"] == 16:
+            return [("score_width", 0), ("score_width", 32)]
+        return []
+    if family in ("rows", "cigar"):
+        if band > 0 and state["band_alignments"]:
+            if alg == NW and not state["band_nw"]:
+                return [("band_nw", 1), ("band_alignments", 0)]
+            if state["traceback_policy"]:
+                return [("traceback_policy", 0), ("band_alignments", 0)]
+        return []
+    if band > 0:
+        if family != "placed":
+            return [("band_width", 0)]
+        if not state["band_placed"]:
+            return [("band_placed", 1), ("band_width", 0)]
+        return [("traceback_policy", 0)] if state["traceback_policy"] else []
+    if state["traceback_policy"]:
+        return [("traceback_policy", 0)]
+    if family == "subopt":
+        return [("score_width", 0)] if state["score_width"] == 32 else []
+    if state["score_width"] == 32 and not state["placed_wide"]:
+        return [("placed_wide", 1), ("score_width", 0)]
+    if wide_scoring and state["score_width"] == 16:
+        return [("score_width", 0)]
+    if wide_scoring and not state["placed_wide"]:
+        return [("placed_wide", 1)]
+    return []
+
+
+def sequence(world, seed):
+    """-> the steps of (world, seed): dicts {"kind": "set", "key", "value"} and {"kind": "call", "entry", "alg", "begin", "n",
+    "threads", "mask", "extended"}.  A pure function of its arguments."""
+    w = WORLDS[world]
+    d = _Draw(world, seed)
+    state = initial_state()
+    history = {k: [state[k]] for k in KEYS}
+    steps, seen, count, likely = [], set(), {e: 0 for e in ENTRY_POINTS}, {e: 0 for e in ENTRY_POINTS}
+    last_family = None
+
+    def change(key, value):
+        nonlocal state
+        if value == state[key]:
+            return
+        step = {"kind": "set", "key": key, "value": value}
+        state = apply_step(state, step)
+        history[key].append(value)
+        steps.append(step)
+
+    def call(family, alg=None, entry=None, remedy=False):
+        nonlocal last_family
+        a, b = ENTRIES_OF[family]
+        if entry is None:
+            entry = a if count[a] < count[b] else b if count[b] < count[a] else d.choice((a, b))
+        if alg is None:
+            alg = d.choice((SW, NW)) if family in ("score", "rows", "cigar") else (NW if d.pick(0, 11) == 0 else SW)
+        if _blockers(world, state, family, alg) and (remedy or d.pick(0, 3)):
+            for _ in range(4):                  # three times in four: remedy reason after reason, then call
+                fixes = _blockers(world, state, family, alg)
+                if not fixes:
+                    break
+                change(*d.choice(fixes))
+        # (for the repairs below; an affine scoring also refuses the register routes' alignments under traceback_policy = 1)
+        if not _blockers(world, state, family, alg) and (family == "score" or alg == SW) and \
+                (family not in ("rows", "cigar") or not state["traceback_policy"]):
+            likely[entry] += 1
+        n = d.choice(LADDER)
+        steps.append({"kind": "call", "entry": entry, "alg": alg, "begin": d.pick(0, POOL - n), "n": n, "threads": d.pick(1, 3),
+                      "mask": d.choice((0, 3, w["R"] // 2, w["F"])), "extended": d.pick(0, 1)})
+        count[entry] += 1
+        if last_family is not None:
+            seen.add((last_family, family))
+        last_family = family
+
+    def family_calls(family):
+        return sum(count[e] for e in ENTRIES_OF[family])
+
+    for _ in range(CALLS):
+        for _ in range(d.pick(0, 2)):
+            key = d.choice(KEYS)
+            change(key, d.choice([v for v in key_values(world, key) if v != state[key]]))
+        open_families = [f for f in FAMILIES if f != "subopt" or family_calls(f) < SUBOPT_CALLS]
+        fresh = [f for f in open_families if f != last_family and (last_family, f) not in seen]
+        call(d.choice(fresh or open_families))
+    # repairs: what the draw above did not bring about by itself
+    for key in KEYS:
+        values, h = key_values(world, key), history[key]
+        while len(set(h)) < 2 or not any(h[i] in h[:i - 1] for i in range(2, len(h))):
+            change(key, d.choice([v for v in values if v != state[key] and (len(h) < 2 or v in h[:-1])] or
+                                 [v for v in values if v != state[key]]))
+            call("score")
+    for entry in ENTRY_POINTS:
+        while count[entry] < 3:
+            call(FAMILY_OF[entry], entry=entry)
+        while likely[entry] < 3:                # by the steering model: calls that should run, so that no entry point hides behind refusals
+            if FAMILY_OF[entry] in ("rows", "cigar"):
+                change("traceback_policy", 0)
+            call(FAMILY_OF[entry], alg=SW, entry=entry, remedy=True)
+    # ... and, always, a band that is set, used, cleared and followed by a call of every family that reads the plan
+    change("band_width", w["bands"][0])
+    call("score", alg=SW)
+    change("band_width", 0)
+    for family in ("score", "rows", "placed"):
+        call(family, alg=SW)
+    return steps
+
+
+# ---- the runner -------------------------------------------------------------------------------------------------------------
+ECHOED = ("band_width", "ragged_batching", "band_alignments", "band_nw", "band_placed", "placed_wide", "trace_checkpoints")
+PLAN_KEYS = ("long_mode", "group_lanes", "rows_per_lane", "score_cells", "band_block_rows", "band_col_align", "span_ref_length")
+RAN_KEYS = {"score": ("ran_score_cells", "ran_score_geometry", "ran_score_sym_affine"),
+            "rows": ("ran_align_fill", "ran_align_geometry", "ran_result_format"),
+            "cigar": ("ran_align_fill", "ran_align_geometry", "ran_result_format"),
+            "placed": ("ran_placed",), "span": ("ran_span", "ran_placed"), "subopt": ("ran_subopt",)}
+SENTINEL = -7
+
+
+class SequenceMismatch(AssertionError):
+    pass
+
+
+def compared(entry, desc, refused=False):
+    """The describe() keys a live engine and a new one must agree on right after a call of `entry` (a key the library leaves
+    out -- ran_score_sym_affine -- reads None).  Scratch sizes and the last-launch figures of other kinds of call are not here:
+    direct_call, packed_classes and ragged_launches are figures of the last host-pointer / score call that LAUNCHED, so after a
+    refused call they are an earlier call's and are left out."""
+    family = FAMILY_OF[entry]
+    out = {k: desc.get(k) for k in PLAN_KEYS + ECHOED + RAN_KEYS[family]}
+    if entry.endswith("_host") and not refused:
+        out["direct_call"] = desc["direct_call"]
+        out["packed_classes"] = desc["packed_classes"]
+    if family == "score" and not refused:
+        out["ragged_launches_zero"] = desc["ragged_launches"] == 0
+    return out
+
+
+def _freeze(step):
+    return tuple(sorted(step.items()))
+
+
+class Runner:
+    """One (world, scoring): the pairs on the device, the references (computed once per operation and parameter set, for the
+    whole pool, and sliced), and run(seed_or_steps)."""
+
+    def __init__(self, world, scoring):
+        import torch
+        from oracle import cpu_ref
+        from versalignlib_amd import hipkernel
+        self.torch, self.cpu_ref, self.hk = torch, cpu_ref, hipkernel
+        self.world, self.scoring = world, scoring
+        w = WORLDS[world]
+        self.R, self.F = w["R"], w["F"]
+        self.args = SCORINGS[scoring]
+        self.affine = len(self.args) > 4
+        self.osc = cpu_ref.Scoring.make(*self.args)
+        self.hsc = hipkernel.Scoring.make(*self.args)
+        self.reads, self.refs = pairs(world)
+        self.d_reads = torch.from_numpy(np.array(self.reads)).cuda()
+        self.d_refs = torch.from_numpy(np.array(self.refs)).cuda()
+        self.stride = self.R + self.F           # ops per pair of the device-resident CIGAR calls: no alignment has more
+        self._refs = {}
+
+    # -- references: the whole pool, once --
+    def _ref(self, key, make):
+        if key not in self._refs:
+            out = make()
+            for a in (out if isinstance(out, tuple) else (out,)):
+                if isinstance(a, np.ndarray):
+                    a.setflags(write=False)
+            self._refs[key] = out
+        return self._refs[key]
+
+    def ref_scores(self, alg, band, block):
+        import band_nw_ref
+        if band == 0:
+            return self._ref(("score", alg), lambda: self.cpu_ref.score(alg, self.reads, self.refs, self.osc, threads=8, affine=self.affine, wide=True))
+        if alg == SW:
+            return self._ref(("score", alg, band, block), lambda: self.cpu_ref.score_banded_sw(
+                self.reads, self.refs, band, self.osc, threads=8, block_rows=block[0], col_align=block[1], affine=self.affine))
+        return self._ref(("score", alg, band, block), lambda: np.minimum(band_nw_ref.score_banded_nw(
+            self.reads, self.refs, band, self.osc, block_rows=block[0], col_align=block[1], affine=self.affine), 32767).astype(np.int16))
+
+    def ref_rows(self, alg, band, block, policy, wide):
+        import band_align_ref
+        import band_nw_ref
+        if band == 0:
+            return self._ref(("rows", alg, policy, wide), lambda: self.cpu_ref.align(
+                alg, self.reads, self.refs, self.osc, threads=8, affine=self.affine, policy="sse" if policy else "default", wide=wide))
+        fn = band_align_ref.align_banded_sw if alg == SW else band_nw_ref.align_banded_nw
+        return self._ref(("rows", alg, band, block), lambda: fn(self.reads, self.refs, band, self.osc, block_rows=block[0], col_align=block[1],
+                                                                affine=self.affine))
+
+    def ref_cigar(self, rows_key, rows, idx, extended):
+        import cigar_ref
+        return self._ref(("cigar", rows_key, extended), lambda: cigar_ref.expected(np.array(rows), np.array(idx), self.osc, self.reads, self.refs,
+                                                                                   extended=bool(extended), affine=self.affine))
+
+    def ref_placed(self, band):
+        import placed_band_ref
+        import placed_ref
+        if band == 0:
+            return self._ref(("placed",), lambda: placed_ref.placed(self.reads, self.refs, self.hsc, affine=self.affine))
+        return self._ref(("placed", band), lambda: placed_band_ref.placed_banded(self.reads, self.refs, band, self.hsc, affine=self.affine))
+
+    def ref_span(self):
+        import span_ref
+        return self._ref(("span",), lambda: span_ref.spans(self.reads, self.refs, self.hsc, affine=self.affine))
+
+    def ref_subopt(self, mask):
+        import subopt_ref
+        prepared = self._ref(("subopt",), lambda: subopt_ref.prepare(self.reads, self.refs, self.hsc, affine=self.affine))
+        return self._ref(("subopt", mask), lambda: subopt_ref.apply_mask(prepared, mask))
+
+    # -- one call on one engine --
+    def outputs(self, step, stream=None):
+        """Preallocated, sentinel-filled outputs of a device-resident call (None for a host call); the fill is queued on
+        `stream`, in front of the call that follows there."""
+        t, n, entry = self.torch, step["n"], step["entry"]
+
+        def full(shape, dtype):
+            with t.cuda.stream(stream):
+                return t.full(shape, SENTINEL, dtype=dtype, device="cuda")
+        if entry == "score_device":
+            return (full((n,), t.int16),)
+        if entry == "align_device":
+            return (full((n, 2, self.R + self.F), t.uint8), full((n, 4), t.int16))
+        if entry == "align_cigar_device":
+            return (full((n, 6), t.int32), full((n, self.stride), t.int32))
+        if entry == "score_placed_device":
+            return (full((n, 3), t.int32),)
+        if entry in ("score_span_device", "score_subopt_device"):
+            return (full((n, 5), t.int32),)
+        return None
+
+    def issue(self, eng, step, out, stream):
+        """Make the call.  -> ("ok", result) -- a device call's result is `out`, still in flight on `stream` -- or
+        ("refused", message).  Nothing here waits for the stream."""
+        b, e, alg, entry = step["begin"], step["begin"] + step["n"], step["alg"], step["entry"]
+        dr, df, hr, hf = self.d_reads[b:e], self.d_refs[b:e], self.reads[b:e], self.refs[b:e]
+        try:
+            if entry == "score_device":
+                eng.score_device(alg, dr, df, scores=out[0], stream=stream)
+            elif entry == "align_device":
+                eng.align_device(alg, dr, df, rows=out[0], idx=out[1], stream=stream)
+            elif entry == "align_cigar_device":
+                eng.align_cigar_device(alg, dr, df, extended=bool(step["extended"]), ops_stride=self.stride, stream=stream, out=out)
+            elif entry == "score_placed_device":
+                eng.score_placed_device(alg, dr, df, out=out[0], stream=stream)
+            elif entry == "score_span_device":
+                eng.score_span_device(alg, dr, df, out=out[0], stream=stream)
+            elif entry == "score_subopt_device":
+                eng.score_subopt_device(alg, dr, df, step["mask"], out=out[0], stream=stream)
+            elif entry == "score_host":
+                out = (eng.score_host(alg, hr, hf, threads=step["threads"]),)
+            elif entry == "align_host":
+                out = eng.align_host(alg, hr, hf, threads=step["threads"])
+            elif entry == "align_cigar_host":
+                out = eng.align_cigar_host(alg, hr, hf, extended=bool(step["extended"]), threads=step["threads"])
+            elif entry == "score_placed_host":
+                out = (eng.score_placed_host(alg, hr, hf, threads=step["threads"]),)
+            elif entry == "score_span_host":
+                out = (eng.score_span_host(alg, hr, hf, threads=step["threads"]),)
+            elif entry == "score_subopt_host":
+                out = (eng.score_subopt_host(alg, hr, hf, step["mask"], threads=step["threads"]),)
+            else:
+                raise ValueError(entry)
+        except self.hk.HipKernelError as err:
+            return "refused", str(err)
+        return "ok", out
+
+    @staticmethod
+    def landed(out):
+        """The result as numpy arrays, once the stream is through."""
+        return tuple(a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a) for a in out)
+
+    def fresh(self, state, step, cache):
+        """What a NEW engine configured to `state` returns for the call: (outcome, arrays or message, compared describe keys)."""
+        key = (tuple(state[k] for k in KEYS), _freeze(step))
+        if key not in cache:
+            eng = self.hk.Engine(self.R, self.F, self.hsc)
+            try:
+                configure(eng, state)
+                out = self.outputs(step)
+                outcome, res = self.issue(eng, step, out, None)
+                self.torch.cuda.synchronize()
+                desc = compared(step["entry"], eng.describe(step["alg"], step["n"]), outcome == "refused")
+                cache[key] = (outcome, self.landed(res) if outcome == "ok" else res, desc)
+            finally:
+                eng.close()
+        return cache[key]
+
+    # -- the reference of a successful call --
+    def expected(self, state, step, desc):
+        """The arrays the call must have returned, in the entry point's own layout, from the reference of the operation the
+        state selects (include/valign_hip.h says which); desc: the live engine's describe() right after the call."""
+        b, e, alg, family = step["begin"], step["begin"] + step["n"], step["alg"], FAMILY_OF[step["entry"]]
+        band = state["band_width"]
+        block = (desc["band_block_rows"], desc["band_col_align"])
+        if family == "score":
+            return (self.ref_scores(alg, band, block)[b:e],)
+        if family in ("rows", "cigar"):
+            banded = band > 0 and state["band_alignments"]
+            fill = desc["ran_align_fill"]
+            # the cell width of the expected alignments is the one that ran, never "either": strip_wide* is the oracle's wide=True
+            wide = fill.startswith("strip_wide")
+            key = ("rows", alg, band, block) if banded else ("rows", alg, state["traceback_policy"], wide)
+            rows, idx = self.ref_rows(alg, band if banded else 0, block, state["traceback_policy"], wide)
+            if family == "rows":
+                return rows[b:e], idx[b:e]
+            exp = self.ref_cigar(key, rows, idx, step["extended"])
+            return {k: v[b:e] for k, v in exp.items()}
+        if family == "placed":
+            return (self.ref_placed(band)[b:e],)
+        if family == "span":
+            return (self.ref_span()[b:e],)
+        return (self.ref_subopt(step["mask"])[b:e],)
+
+    def verify(self, step, got, exp, where):
+        import cigar_ref
+        entry, family = step["entry"], FAMILY_OF[step["entry"]]
+        b, e = step["begin"], step["begin"] + step["n"]
+        if family == "cigar":
+            if entry.endswith("_device"):
+                recs = got[0].view(self.hk.aln_dtype()).reshape(-1)
+                ops = got[1].view(np.uint32)
+                assert (recs["n_ops"] <= self.stride).all(), (where, "n_ops beyond the stride")
+                cigar_ref.check(recs, lambda p: ops[p, :recs["n_ops"][p]], exp, self.reads[b:e], self.refs[b:e], where)
+                tail = np.arange(self.stride)[None, :] >= recs["n_ops"][:, None].astype(np.int64)
+                assert (got[1][tail] == SENTINEL).all(), (where, "words past a pair's ops were written")
+            else:
+                recs, ops, offsets = got
+                assert offsets[0] == 0 and np.array_equal(np.diff(offsets), recs["n_ops"].astype(np.int64)) and len(ops) == offsets[-1], (where, "offsets")
+                cigar_ref.check(recs, lambda p: ops[offsets[p]:offsets[p + 1]], exp, self.reads[b:e], self.refs[b:e], where)
+            return
+        if entry.endswith("_host") and family in ("placed", "span", "subopt"):
+            got = (np.stack([got[0][k] for k in got[0].dtype.names], axis=1),)
+        for g, x in zip(got, exp):
+            g, x = np.asarray(g), np.asarray(x)
+            same = g.astype(np.int64) == x.astype(np.int64)
+            if not same.all():
+                bad = np.nonzero(~same.reshape(len(g), -1).all(axis=1))[0]
+                raise SequenceMismatch((where, "differs from the reference at pairs", bad[:6].tolist(), "got", g[bad[:2]].tolist()[:2],
+                                        "expected", x[bad[:2]].tolist()[:2]))
+
+    # -- the whole sequence on one engine --
+    def run(self, seed=None, steps=None, log=None):
+        """Run sequence(world, seed) -- or `steps` -- on ONE engine.  Raises SequenceMismatch (an AssertionError) that names world,
+        scoring, seed and step index.  -> {"calls", "refused", "succeeded": {entry: count}}."""
+        torch = self.torch
+        steps = sequence(self.world, seed) if steps is None else steps
+        tag = (self.world, self.scoring, "seed", seed)
+        # 1. the new engines first: each is created, configured, called once, waited for and closed (closing frees device
+        #    memory, which waits for the device -- nothing of that may happen between the live engine's steps)
+        cache, news, state = {}, {}, initial_state()
+        for i, step in enumerate(steps):
+            state = apply_step(state, step)
+            if step["kind"] == "call":
+                news[i] = (dict(state), self.fresh(state, step, cache))
+        # 2. the live engine: one non-default stream, device steps back to back, a wait only before a host-pointer step and
+        #    at the end; describe() is host-side state, read right after the call without one
+        stream = torch.cuda.Stream()
+        live = self.hk.Engine(self.R, self.F, self.hsc)
+        pending, stats = [], {"calls": 0, "refused": 0, "succeeded": {e: 0 for e in ENTRY_POINTS}}
+
+        def settle():
+            stream.synchronize()
+            for i, step, outcome, res, desc in pending:
+                self._settle(tag, i, step, outcome, res, desc, news[i])
+            del pending[:]
+
+        try:
+            for i, step in enumerate(steps):
+                if step["kind"] == "set":
+                    getattr(live, "set_" + step["key"])(step["value"])
+                    continue
+                if step["entry"].endswith("_host"):
+                    settle()
+                out = self.outputs(step, stream)
+                outcome, res = self.issue(live, step, out, stream)
+                desc = live.describe(step["alg"], step["n"])
+                if log:
+                    log("%4d %s %s -> %s %s" % (i, step["entry"], {k: v for k, v in step.items() if k not in ("kind", "entry")}, outcome,
+                                                 res if outcome == "refused" else ""))
+                stats["calls"] += 1
+                if outcome == "ok":
+                    stats["succeeded"][step["entry"]] += 1
+                else:
+                    stats["refused"] += 1
+                pending.append((i, step, outcome, res if outcome == "ok" else (res, out), desc))
+            settle()
+        finally:
+            stream.synchronize()
+            live.close()
+        return stats
+
+    def _settle(self, tag, i, step, outcome, res, desc, fresh):
+        where = tag + ("step", i, step["entry"], "alg", step["alg"], "pairs", (step["begin"], step["n"]))
+        state, (f_outcome, f_res, f_desc) = fresh
+        if outcome != f_outcome:
+            raise SequenceMismatch((where, "live engine:", outcome, res[0] if outcome == "refused" else "", "new engine:", f_outcome,
+                                    f_res if f_outcome == "refused" else "", "state", state))
+        l_desc = compared(step["entry"], desc, outcome == "refused")
+        if l_desc != f_desc:
+            diff = {k: (l_desc[k], f_desc[k]) for k in l_desc if l_desc[k] != f_desc[k]}
+            raise SequenceMismatch((where, "describe() of the live engine and of a new one differ (live, new)", diff, "state", state))
+        if outcome == "refused":
+            message, out = res
+            if message != f_res:
+                raise SequenceMismatch((where, "refused with another text", message, f_res))
+            for a in (out or ()):
+                if not bool((a == SENTINEL).all()):
+                    raise SequenceMismatch((where, "a refused call wrote its output"))
+            return
+        got = self.landed(res)
+        self.verify(step, got, self.expected(state, step, desc), where)       # the authority: the reference, bit for bit
+        for g, f in zip(got, f_res):                                          # ... and the new engine (unwritten words hold the sentinel in both)
+            if not np.array_equal(g, f):
+                raise SequenceMismatch((where, "live engine and new engine return different results", "state", state))

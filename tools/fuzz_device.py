@@ -246,15 +246,43 @@ def run(c):
             eng.close()
 
 
+def soak_sequences(rng, a):
+    """--kind sequence: the generator and the runner of tests/engine_sequences.py (what tests/test_gpu_engine_sequences.py runs
+    on its committed seeds) on random seeds: ONE engine per sequence through key changes and calls, every call against its
+    reference and against a new engine.  No code path of its own: a mismatch is the runner's, with world, seed and step index."""
+    os.environ["VALIGN_HIP_DEBUG"] = "ragged_min=8"        # (before any engine exists: the length classes at these batch sizes)
+    import engine_sequences as es
+    runners, t0, done = {}, time.time(), 0
+    while time.time() - t0 < a.seconds:
+        world = str(rng.choice(sorted(es.WORLDS)))
+        scoring = str(rng.choice(es.WORLDS[world]["scorings"]))
+        seed = int(rng.integers(10, 1 << 30))
+        if (world, scoring) not in runners:
+            runners[(world, scoring)] = es.Runner(world, scoring)
+        try:
+            stats = runners[(world, scoring)].run(seed, log=print if a.verbose else None)
+        except AssertionError as e:               # (es.SequenceMismatch is one; so are the references' own checks)
+            print("MISMATCH world %s scoring %s seed %d: %s" % (world, scoring, seed, e), flush=True)
+            return 1
+        done += 1
+        print("%s %s seed %d: %d calls, %d refused; %d sequences, %.0f s" % (world, scoring, seed, stats["calls"], stats["refused"], done,
+                                                                              time.time() - t0), flush=True)
+    print("ok: %d sequences in %.0f s (seed %d)" % (done, time.time() - t0, a.seed))
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=120.0)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--first", type=int, default=0)
     ap.add_argument("--verbose", action="store_true")
-    ap.add_argument("--kind", choices=["subopt"], default=None, help="draw cases of this kind only (default: the mix)")
+    ap.add_argument("--kind", choices=["subopt", "sequence"], default=None,
+                    help="draw cases of this kind only (default: the mix); sequence: one engine through tests/engine_sequences.py's sequences")
     a = ap.parse_args()
     rng = np.random.default_rng(a.seed)
+    if a.kind == "sequence":
+        return soak_sequences(rng, a)
     t0 = time.time()
     i = done = 0
     while time.time() - t0 < a.seconds:

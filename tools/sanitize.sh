@@ -60,6 +60,11 @@ echo "== base_classes.h (the byte classifier of the kernels' set-up) under Addre
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/base_classes_check.cpp" -o "$OUT/base_classes_asan"
 "$OUT/base_classes_asan"
 
+echo "== several kernels of one plugin library through valign_host.cpp under AddressSanitizer + UBSan"
+g++ -std=c++14 $SAN -Wall -Werror -fPIC -shared -I"$R/include" "$R/tests/host_plugins_stub.cpp" -o "$OUT/libStubKernel.so"
+g++ -std=c++14 $SAN -Wall -Werror -pthread -I"$R/include" "$R/tests/host_plugins_check.cpp" "$CS/valign_host.cpp" -o "$OUT/host_plugins_asan" -ldl
+ASAN_OPTIONS="detect_leaks=1" "$OUT/host_plugins_asan" "$OUT/libStubKernel.so"
+
 echo "== libvalignhost.so, valign-bench, libcpuref.so with $SAN"
 g++ -std=c++14 $SAN -fPIC -shared -Wall -pthread -I"$R/include" "$CS/valign_host.cpp" -o "$OUT/libvalignhost.so" -ldl
 g++ -std=c++14 $SAN -Wall -I"$R/include" "$CS/valign_bench.cpp" -o "$OUT/valign-bench" -L"$OUT" -lvalignhost -Wl,-rpath,'$ORIGIN' -ldl -pthread

@@ -225,11 +225,12 @@ public:
     ~Engine();
 
     // Banded Smith-Waterman scores (strip band of long_kernels.hip.h); 0 = every cell.  Takes the
-    // long-read path whatever the shape.
+    // long-read path whatever the shape -- while the band is set: 0 puts the plan chosen at construction back, so an
+    // engine whose band was set and cleared plans every call as a new one does.
     void set_band_width(int diagonals) {
         if (diagonals < 0) throw std::runtime_error("band_width must be >= 0");
         band_width_ = diagonals;
-        if (diagonals > 0 && !plan_.long_mode) plan_ = long_plan();
+        plan_ = (diagonals > 0 && !base_plan_.long_mode) ? long_plan() : base_plan_;
         band_plan_ = band_chain_plan(R_, F_, band_width_, sc_.affine);      // (once per band_width: shape and scoring are the engine's)
     }
     int band_width() const { return band_width_; }
@@ -825,6 +826,7 @@ private:
     bool chain_regions_busy_[2] = {false, false};                 // WalkChain: the region's last walk may still be running
     std::string arch_;
     LaunchPlan plan_, latency_plan_;
+    LaunchPlan base_plan_;              // plan_ as the constructor chose it: what set_band_width(0) restores
     LaunchPlan align_resident_;         // what choose_plan picked before the score path's preferences for the long-read kernels
     LaunchPlan fallback_plan_;          // alignments that need a kernel only the full geometries carry (align_plan_for)
     long long slot_begin_[kSlots] = {}, slot_pending_[kSlots] = {};

@@ -367,6 +367,7 @@ void Engine::align_host(int opt, int n, const char *const *reads, const char *co
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ran_align_fill_ = "none";
     ran_align_geo_ = nullptr;
+    ran_result_format_ = "rows";            // (before the refusals: a refused call must not report the format of an earlier one)
     const int AL = R_ + F_;
     const size_t per_pair = (size_t)3 * AL + 8;
     // (row strips run chunk after chunk on one pointer scratch: chunks that fill the device -- 2 000 pairs-of-pairs and more --

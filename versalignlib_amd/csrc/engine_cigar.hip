@@ -104,6 +104,7 @@ bool Engine::align_cigar_host(int opt, int n, const char *const *reads, const ch
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ran_align_fill_ = "none";
     ran_align_geo_ = nullptr;
+    ran_result_format_ = "cigar";           // (before the refusals: a refused call must not report the format of an earlier one)
     const int AL = R_ + F_;
     const size_t per_pair = (size_t)3 * AL + 8;                 // (the chunks of align_host: same launches, same rounds)
     const RouteFacts facts = route_facts(true);

@@ -43,6 +43,7 @@ Engine::Engine(int device, int R, int F, const Scoring &sc, int force_g, int for
         const bool pads_alike = R_ <= 1024 && ((R_ + strip_rows - 1) / strip_rows) * strip_rows * 100 <= plan_.geo->G * plan_.geo->K * 115;
         if (waves_per_cu <= 1 || (waves_per_cu <= 2 && (!sc_.affine || pads_alike)) || (waves_per_cu <= 4 && pads_alike)) plan_ = long_plan();
     }
+    base_plan_ = plan_;
     latency_plan_ = (force_g || force_k || plan_.long_mode) ? plan_ : choose_plan(R_, F_, 0, 0, true);
     build_length_classes();
     for (int s = 0; s < kSlots; ++s) streams_[s] = make_stream();

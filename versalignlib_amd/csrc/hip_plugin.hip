@@ -153,9 +153,12 @@ struct ShardSplit {
 // The kernel object handed to the host.  Reads the same six required keys as every
 // reference backend at construction (DefaultKernel.h:70-81) and num_threads per call
 // (DefaultKernel.cpp:45); the latter sizes the host gather pool here.
+// A host may spawn several kernels of one library, each after set_parameters / set_logger of its own: the kernel keeps, for
+// its whole life, the two objects it was spawned with (params_ / logger_) and never re-reads the globals -- another kernel's
+// spawn (or its owner's end) must not change this one's num_threads or where its lines go.
 class HIPKernel : public AlignmentKernel {
 public:
-    HIPKernel() {
+    HIPKernel() : params_(_parameters), logger_(_logger) {
         if (!_parameters) throw "Cannot instantiate Kernel. Lacking parameters";
         static const char *const required[] = {"score_match", "score_mismatch", "score_gap_read",
                                                "score_gap_ref", "read_length", "ref_length"};
@@ -266,7 +269,7 @@ public:
     void score_alignments(int const &opt, int const &aln_number, char const *const *const reads,
                           char const *const *const refs, short *const scores) override {
         if ((opt & 0xF) > 1) return;       // unsupported mode: silent no-op, like the reference
-        const int threads = Parameters.has_key("num_threads") ? Parameters.param_int("num_threads") : 1;
+        const int threads = params_->has_key("num_threads") ? params_->param_int("num_threads") : 1;
         log_line(0, "Running HIPKernel score with " + std::to_string(threads) + " host threads on " +
                         engine_->describe(opt, aln_number));
         try {
@@ -296,7 +299,7 @@ public:
     void compute_alignments(int const &opt, int const &aln_number, char const *const *const reads,
                             char const *const *const refs, Alignment *const alignments) override {
         if ((opt & 0xF) > 1) return;
-        const int threads = Parameters.has_key("num_threads") ? Parameters.param_int("num_threads") : 1;
+        const int threads = params_->has_key("num_threads") ? params_->param_int("num_threads") : 1;
         log_line(0, "Running HIPKernel align with " + std::to_string(threads) + " host threads on " +
                         engine_->describe(opt, aln_number));
         try {
@@ -310,6 +313,11 @@ public:
     }
 
 private:
+    // the lines of this kernel (the constructor runs before any other spawn can move the globals: the same logger)
+    void log_line(int level, const std::string &msg) const {
+        if (logger_) logger_->log(level, kModule, msg.c_str());
+    }
+
     // Errors leave the virtuals the way the reference's kernels raise theirs: logged at level 3, then thrown
     // as `const char *` (DefaultKernel.h:79-81) -- reference-style hosts catch nothing else, a std::exception
     // crossing the plugin boundary would end in std::terminate.
@@ -349,6 +357,8 @@ private:
             if (err) std::rethrow_exception(err);
     }
 
+    AlignmentParameters *const params_;                      // what set_parameters / set_logger held when the kernel was spawned
+    AlignmentLogger *const logger_;
     std::unique_ptr<valign::Engine> engine_;
     std::vector<std::unique_ptr<valign::Engine>> more_;      // hip_devices > 1: one engine per further device
     std::unique_ptr<ShardGather> gather_;                    // hip_devices_allgather = 1

@@ -106,6 +106,60 @@ bool lengths(vh_plugin *p, int *R, int *F) {
     return *R >= 0 && *F >= 0;
 }
 
+// What the globals of each loaded library (its _parameters / _logger, set through set_parameters / set_logger) point at.
+// A library has ONE pair of globals however many kernels a host spawns from it, and they point into a vh_plugin: vh_close
+// must not leave them pointing into the plugin it deletes.  Per dlopen handle (one per library): the plugins that have been
+// given to the library, oldest first, and whose members each global holds now.  vh_close re-points a global that held the
+// closing plugin's member at the youngest surviving plugin of the library, or at null when none survives.
+struct LibraryGlobals {
+    std::vector<vh_plugin *> given;
+    vh_plugin *params_of = nullptr, *logger_of = nullptr;
+};
+std::mutex g_libraries_mu;
+std::map<void *, LibraryGlobals> g_libraries;
+
+void give_params(vh_plugin *p) {
+    std::lock_guard<std::mutex> lock(g_libraries_mu);
+    LibraryGlobals &g = g_libraries[p->dl];
+    bool known = false;
+    for (vh_plugin *q : g.given) known = known || q == p;
+    if (!known) g.given.push_back(p);
+    p->set_params(&p->params);
+    g.params_of = p;
+}
+
+void give_logger(vh_plugin *p) {
+    std::lock_guard<std::mutex> lock(g_libraries_mu);
+    LibraryGlobals &g = g_libraries[p->dl];
+    bool known = false;
+    for (vh_plugin *q : g.given) known = known || q == p;
+    if (!known) g.given.push_back(p);
+    p->set_log(&p->logger);
+    g.logger_of = p;
+}
+
+void take_back(vh_plugin *p) {
+    std::lock_guard<std::mutex> lock(g_libraries_mu);
+    auto it = g_libraries.find(p->dl);
+    if (it == g_libraries.end()) return;
+    LibraryGlobals &g = it->second;
+    for (size_t i = 0; i < g.given.size(); ++i)
+        if (g.given[i] == p) {
+            g.given.erase(g.given.begin() + (long)i);
+            break;
+        }
+    vh_plugin *heir = g.given.empty() ? nullptr : g.given.back();
+    if (g.params_of == p) {
+        p->set_params(heir ? &heir->params : nullptr);
+        g.params_of = heir;
+    }
+    if (g.logger_of == p) {
+        p->set_log(heir ? &heir->logger : nullptr);
+        g.logger_of = heir;
+    }
+    if (g.given.empty()) g_libraries.erase(it);
+}
+
 template <typename Fn>
 int guarded(const char *what, Fn &&fn) {
     try {
@@ -167,15 +221,15 @@ int vh_unset_param(vh_plugin *p, const char *key) {
 
 int vh_reapply_params(vh_plugin *p) {
     if (!p) return fail("null plugin");
-    p->set_params(&p->params);
+    give_params(p);
     return 0;
 }
 
 int vh_spawn(vh_plugin *p) {
     if (!p) return fail("null plugin");
     if (p->kernel) return fail("kernel already spawned");
-    p->set_params(&p->params);
-    p->set_log(&p->logger);
+    give_params(p);
+    give_logger(p);
     int rc = guarded("spawn_alignment_kernel", [&] { p->kernel = p->spawn(); });
     if (rc == 0 && !p->kernel) return fail("spawn_alignment_kernel returned null");
     return rc;
@@ -341,7 +395,8 @@ void vh_close(vh_plugin *p) {
     }
     // The library stays loaded, as under the reference's host (src/util/versalignUtil.cpp:45-76 never closes a kernel
     // library): a plugin that owns device state, worker threads and registered code objects is not something to map and
-    // unmap once per kernel object.
+    // unmap once per kernel object.  Its globals therefore outlive this plugin: they move on to a surviving one, or to null.
+    take_back(p);
     delete p;
 }
 
