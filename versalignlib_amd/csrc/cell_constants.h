@@ -16,6 +16,9 @@ constexpr int kAlgNW = 1;
 // GAPS of score_kernel selects the recurrence (dp_kernels.hip.h describes each form)
 constexpr int kGapLinear = 0, kGapSym = 1, kGapAffine = 2, kGapAffineSym = 3;       // int16 cells
 constexpr int kGapAffineSymF16 = 4, kGapAffineF16 = 5, kGapSymF16 = 6;              // the same recurrences on half floats
+// The tilted biased form of kGapAffineSym (Smith-Waterman) unrolls its steady loop K steps deep: built for K <= 12 (at 16, 24
+// or 32 rows per lane one trip is tens of KB of code); the rule sym_affine_tilt_ok (cell_rules.h) reads the same constant
+constexpr int kTiltMaxK = 12;
 
 // band_nw: what an ABSENT cell holds on the packed int16 strips (= kNegInf, the "minus infinity" of the affine NW borders;
 // band_nw_int16_ok, cell_rules.h, says where it is safe) and on int32 cells (chain, strips: -2^29)

@@ -21,6 +21,7 @@ struct RuleInputs {
     bool sse_policy = false;
     bool no_sym = false, no_tag = false, no_f16 = false, no_prof_key = false;
     bool no_max3 = false;           // debug switch: int16 symmetric affine SW scores on the gap-source form always
+    bool no_tilt = false;           // debug switch: ... and its biased form in the plain frame always
 };
 
 // int16 DP cells: the reference wraps silently.  Scores and alignments switch to int32 cells on the strip path where they could.
@@ -181,6 +182,31 @@ inline bool sym_affine_max3_ok(const RuleInputs &in, int R, int F) {
 }
 // describe()'s name of the form the last such launch ran (ran_score_sym_affine)
 inline const char *ran_sym_affine_name(bool max3) { return max3 ? "max3" : "sources"; }
+
+// The biased form in a TILTED frame: cell (p, j) kept as value + B + x * u, u = p + j + c0, where an extension costs nothing
+// (two subtracts per register less; the proof is at the kernel's step).  The zero floor of a cell is then B + x * u, the smallest
+// operand of a maximum lies max(o - x, m) below a floor, and c0 puts the smallest u any register carries at 0, so
+// B = 1024 + max(o - x, m) ...
+inline int sym_affine_tilt_bias(const Scoring &sc) {
+    const int o = -sc.open_ref, x = -sc.ext_ref, m = std::max({0, -sc.mismatch, -sc.match});
+    return kMax3WindowLow + std::max(o - x, m);
+}
+// ... the largest u belongs to the last row of the last lane at the last step of the sweep, unmasked steps included: a sweep of
+// `rows` padded rows in lanes of K rows starts `lead` lanes down and ends at u = rows + F - lead
+inline long long sym_affine_tilt_top_index(int R, int F, int rows, int K) {
+    const int lead = rows > R ? (rows - R) / K : 0;
+    return (long long)rows + F - lead;
+}
+// ... and the form is legal inside the plain biased form's window, for K <= kTiltMaxK (cell_constants.h), where B plus the largest tilt plus the largest cell stays at
+// or below 0x7BFF.  R, F as in sym_affine_max3_ok; rows, K: of the geometry the launch runs on.
+inline bool sym_affine_tilt_ok(const RuleInputs &in, int R, int F, int rows, int K) {
+    if (in.no_tilt || K > kTiltMaxK || !sym_affine_max3_ok(in, R, F)) return false;
+    const Scoring &sc = in.sc;
+    const long long B = sym_affine_tilt_bias(sc);
+    const long long hi = (long long)std::min(R, F) * std::max({sc.match, sc.mismatch, 0}) + 1;
+    return B + (long long)-sc.ext_ref * sym_affine_tilt_top_index(R, F, rows, K) + hi <= kMax3WindowHigh;
+}
+inline const char *ran_sym_affine_frame_name(bool tilted) { return tilted ? "tilted" : "plain"; }
 
 // Which fill kernel an alignment call of this mode takes on a G x K geometry, and what its pointer stream looks like.
 struct FillChoice {

@@ -31,8 +31,10 @@
 //     profile merge: two linear gap scores 6 + maximum tracking, one shared gap score 5 +
 //     tracking, affine 10 + tracking, affine with the same open/extend for both directions 9 + tracking (Smith-Waterman:
 //     inside the window of its biased form 8 + 1/2 -- every int16 cell kept as value + B, maxima three at a time through
-//     v_pk_maximum3_f16, which is an integer maximum on bit patterns in [0x0400, 0x7BFF]; beyond it
-//     9 on gap SOURCES, tracked once per two steps -- 9 + (K + 1) / 2K; see score_kernel's step).  Where every
+//     v_pk_maximum3_f16, which is an integer maximum on bit patterns in [0x0400, 0x7BFF]; with at most 12 rows per lane
+//     and a little further inside that window 6 + (K / 2 + 4) / K: the same biased cells in a TILTED frame, value + B +
+//     x (p + j + c0), where an extension costs nothing and the zero floor is a register that moves with the frame; beyond
+//     the window 9 on gap SOURCES, tracked once per two steps -- 9 + (K + 1) / 2K; see score_kernel's sweep).  Where every
 //     cell provably stays a small integer the same recurrences run on packed HALF FLOATS, which
 //     gfx950 gives a three-operand maximum (v_pk_maximum3_f16) and a free [0, 1] clamp on the
 //     add: shared-gap linear SW 4 (keeps (h, max(h + g, 0)) scaled by 2^-10), symmetric affine 8,
@@ -54,6 +56,7 @@
 #include <stdint.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "base_classes.h"
 #include "cell_constants.h"
@@ -89,6 +92,7 @@ struct ScoreArgs {
         // The affine kernels never read the linear model.  A launch of score_kernel<G, K, kAlgSW, kGapAffineSym> carries in
         // its place what selects the form of that sweep: > 0 the biased three-operand-maximum form, and its bias B (cell_rules.h:
         // sym_affine_max3_ok / sym_affine_bias); 0 the gap-source form.  No offset and no size changes for any kernel.
+        // Bit 16 set: the biased form in its tilted frame, the low 16 bits its bias (sym_affine_tilt_ok / sym_affine_tilt_bias).
         int sym_max3_bias;
     };
     short open_read, ext_read, open_ref, ext_ref;  // affine extension, all <= 0
@@ -147,6 +151,12 @@ __device__ __forceinline__ s16x2 pk_max_h(s16x2 a, s16x2 b) {
 __device__ __forceinline__ s16x2 pk_max3_h(s16x2 a, s16x2 b, s16x2 c) {
     return __builtin_bit_cast(s16x2, __builtin_elementwise_maximum(__builtin_elementwise_maximum(__builtin_bit_cast(f16x2, a), __builtin_bit_cast(f16x2, b)),
                                                                   __builtin_bit_cast(f16x2, c)));
+}
+
+// fn(integral_constant<int, 0>), fn(integral_constant<int, 1>), ...: a loop whose counter is a compile-time constant in every pass
+template <int... Is, class Fn>
+__device__ __forceinline__ void unrolled_steps(std::integer_sequence<int, Is...>, Fn &&fn) {
+    (fn(std::integral_constant<int, Is>{}), ...);
 }
 
 // LDS bank conflicts of one profile fetch, modelled per MI355X_MICROARCH.md section LDS: every lane of
@@ -639,7 +649,12 @@ score_kernel(const ScoreArgs args) {
     constexpr bool HALF = F16 || LINF16;          // cells are half floats (bit patterns in the s16x2 containers)
     const int tilt_row = TILT ? -(int)(AFFINE ? args.ext_ref : args.gap_ref) : 0;
     const int tilt_col = TILT ? -(int)(AFFINE ? args.ext_read : args.gap_read) : 0;
-    const int fold = tilt_row + tilt_col;
+    int fold = tilt_row + tilt_col;
+    // (int16 symmetric affine Smith-Waterman in its tilted biased form -- see the sweep below -- pays both extensions on the
+    // diagonal as the NW frame does: 2x on every score of the profile, the zero slab included)
+    if constexpr (SOURCES && K <= kTiltMaxK) {
+        if (args.sym_max3_bias > 0 && (args.sym_max3_bias >> 16) != 0) fold = -2 * (int)args.ext_ref;
+    }
     // Half-float cells are exact up to 2048 in magnitude and the frame only ever adds: a constant taken off every cell
     // (borders start at -centre, results get it back) puts the sweep's value range [~0, top + tilt] around zero.  The
     // host checks the range with the same formula (Engine::half_float_exact).
@@ -1016,7 +1031,123 @@ score_kernel(const ScoreArgs args) {
         bool biased = false;
         if constexpr (SOURCES) {
             biased = args.sym_max3_bias > 0;       // wave-uniform: the same sweep in its biased form
-            if (biased) {
+            // ... in the tilted frame (the bias: the low 16 bits); built for K <= 12: the engine asks for it nowhere else
+            const bool tilted = K <= kTiltMaxK && biased && (args.sym_max3_bias >> 16) != 0;
+            if constexpr (K <= kTiltMaxK) if (tilted) {
+                // THE TILTED BIASED FORM.  Cell (p, j) -- p the padded row, j the column -- is kept as value + B + x u with
+                // u = p + j + c0 and x = -extend.  In that frame an extension costs nothing: E(p, j-1) - x IS the register of
+                // (p, j-1) read in the frame of (p, j), F likewise down the column, the diagonal pays 2x through the profile
+                // (S' = S + 2x, zero slab included), and ONE H - (o - x) serves E of the next column and F of the next row:
+                //   d = diag + S';  e = max3(E, HO, floor);  f = max(f, ho);  h = max3(d, e, f);  ho = h - (o - x)
+                // -- perm, add, 1 sub, 1 max, 2 max3: 6 packed instructions per register.  floor = B + x u is the zero of the
+                // cell's own frame; as the third operand of E's max3 it floors the whole cell.
+                // Lane l at step t holds row q of its K rows at u = l (K - 1) + q + t + 2 (c0 = 2 - lead), so within a lane
+                // the floor depends on c = q + t alone: K floor registers, slot c % K, each read by one row per step and
+                // moved K x on once row 0 has used it.  With the steady loop unrolled K steps deep every slot index is a
+                // constant: the registers change names, nothing is copied.
+                // THE WINDOW.  Every register starts, by formula, as the cell of an all-zero matrix, the smallest u (row -1
+                // of the first lane before step 0) being 0.  e >= floor, h >= floor, ho >= floor - (o - x), f >= ho of the
+                // row above, and d >= floor(p-1, j-1) + 2x - m = floor(p, j) - m: with B = 1024 + max(o - x, m)
+                // (cell_rules.h: sym_affine_tilt_bias) no operand falls below 0x0400 -- but F above the group's first lane,
+                // which is the zero of the lane shift: +0.0, it loses to every pattern of the window.  Every operand is a
+                // value that exists in the matrix plus B + x u of the cell that reads it, u <= rows + F - lead, and the engine
+                // launches this form only where that stays at or below 0x7BFF (sym_affine_tilt_ok).
+                // A lane outside the columns or on padding rows fetches S' = 2x and stays exactly at its floors:
+                // d = floor(p-1, j-1) + 2x = floor(p, j), e = max3(floor - x, floor - o, floor), f <= floor.
+                // THE RUNNING MAXIMUM.  The diag + S' of one step carry K different tilts, those with the same c = q + t one:
+                // an accumulator per live c in the floors' slots, fed with this step's d and the previous step's two at a
+                // time on every second step (row 0's alone on the others), and taken out of the frame -- acc - floor, a plain
+                // int16 maximum into `best`, which is the score itself -- when row 0 completes its anti-diagonal: once per step.
+                // steps % K remainder steps run first; they feed every d singly and rotate the slots by copying.
+                // tests/test_sym_affine_tilted_sweep.py restates all of this on the CPU.
+                const int B = args.sym_max3_bias & 0xFFFF, xi = -(int)args.ext_ref;
+                const s16x2 ox_c = pk((short)(-(int)args.open_ref - xi)), kx_c = pk((short)(K * xi));
+                const int u0 = l * (K - 1);                                    // u of row -1 before step 0
+                s16x2 lead_border = as_pk(as_u32(pk((short)(B + xi))) & ~lmask);     // row -1 as the group's first lane reads it at step 0
+                const s16x2 lead_step = as_pk(as_u32(pk((short)xi)) & ~lmask);        // ... one x on per step; zero below that lane
+                s16x2 fl[K], acc[K], dprev[K];
+#pragma unroll
+                for (int q = 0; q < K; ++q) {
+                    Hl[q] = El[q] = pk((short)(B + xi * (u0 + q + 1)));
+                    HOl[q] = Hl[q] - ox_c;
+                    fl[q] = acc[q] = pk((short)(B + xi * (u0 + q + 2)));      // an accumulator at its floor holds 0
+                    dprev[q] = fl[q];
+                }
+                up0 = pk((short)(B + xi * u0));
+                h_last = Hl[K - 1];
+                f_last = h_last - ox_c;
+                best = pk(0);
+                constexpr int kFeedAll = 0, kFeedRow0 = 1, kFeedPairs = 2;
+                // One step; row q reads slot (q + SLOT0) % K.  The hand-over, the pipelined fetches and the code pointer are
+                // the plain biased step's.
+                auto tilted_step = [&](auto slot_tag, auto feed_tag) __attribute__((always_inline)) {
+                    constexpr int SLOT0 = decltype(slot_tag)::value, FEED = decltype(feed_tag)::value;
+                    s16x2 S[K], d[K];
+                    const s16x2 diag0 = up0;
+                    up0 = group_prev_or<G>(h_last, lead_border, lmask);
+                    lead_border = lead_border + lead_step;
+                    merge_profile<K>(pa, pb, S);
+                    lds_load_lane<K>(lane_base + ca_next * geo::kPairStride, pa);
+                    lds_load_lane<K>(lane_base + cb_next * geo::kPairStride, pb);
+                    ca_next = code_ptr[4];
+                    cb_next = code_ptr[5];
+                    s16x2 e_cur;
+                    auto pass1 = [&](int q, s16x2 &e) __attribute__((always_inline)) {
+                        d[q] = (q == 0 ? diag0 : Hl[q - 1]) + S[q];
+                        e = pk_max3_h(El[q], HOl[q], fl[(q + SLOT0) % K]);
+                        El[q] = e;
+                    };
+                    s16x2 ho = up0 - ox_c;
+                    pass1(0, e_cur);
+                    // F of the lane above, the shift's zero in the group's first lane (fetched behind the first row's pass 1)
+                    s16x2 f = as_pk(group_prev_or_zero<G>(as_u32(f_last), lmask)), h = pk(0);
+#pragma unroll
+                    for (int q = 0; q < K; ++q) {
+                        f = pk_max_h(f, ho);
+                        s16x2 e_next = pk(0);
+                        if (q + 1 < K) pass1(q + 1, e_next);            // before Hl[q] is overwritten
+                        h = pk_max3_h(d[q], e_cur, f);
+                        Hl[q] = h;
+                        ho = h - ox_c;
+                        HOl[q] = ho;
+                        s16x2 &a = acc[(q + SLOT0) % K];
+                        if (FEED == kFeedAll) a = pk_max_h(a, d[q]);
+                        else if (FEED == kFeedRow0) { if (q == 0) a = pk_max_h(a, d[q]); }
+                        else if (q == K - 1) a = d[q];                                 // a new anti-diagonal: its first cell
+                        else if (q == K - 2) a = pk_max_h(d[q], dprev[q + 1]);          // ... its first two
+                        else a = pk_max3_h(a, d[q], dprev[q + 1]);
+                        e_cur = e_next;
+                    }
+                    if (FEED == kFeedRow0) {
+#pragma unroll
+                        for (int q = 1; q < K; ++q) dprev[q] = d[q];
+                    }
+                    h_last = h;
+                    f_last = f;
+                    // row 0's anti-diagonal is complete: out of the frame; the slot's floor moves on to c + K
+                    best = pk_max(best, acc[SLOT0 % K] - fl[SLOT0 % K]);
+                    fl[SLOT0 % K] = fl[SLOT0 % K] + kx_c;
+                    code_ptr += 2;
+                };
+                for (int r = steps % K; r > 0; --r) {
+                    tilted_step(std::integral_constant<int, 0>{}, std::integral_constant<int, kFeedAll>{});
+                    const s16x2 moved = fl[0];
+#pragma unroll
+                    for (int q = 0; q + 1 < K; ++q) {
+                        fl[q] = fl[q + 1];
+                        acc[q] = acc[q + 1];
+                    }
+                    fl[K - 1] = acc[K - 1] = moved;
+                }
+                for (int trips = steps / K; trips > 0; --trips)
+                    unrolled_steps(std::make_integer_sequence<int, K>{}, [&](auto slot_tag) __attribute__((always_inline)) {
+                        constexpr int s = decltype(slot_tag)::value;
+                        tilted_step(slot_tag, std::integral_constant<int, (s & 1) ? kFeedPairs : kFeedRow0>{});
+                    });
+#pragma unroll
+                for (int q = 0; q < K; ++q) best = pk_max(best, acc[q] - fl[q]);        // the anti-diagonals still open
+            }
+            if (biased && !tilted) {
                 const s16x2 bias_c = pk((short)args.sym_max3_bias);
                 const s16x2 lead_bias = as_pk(as_u32(bias_c) & ~lmask);          // the bias in the group's first lane, zero below it
                 // One step of the biased form.  The hand-over, the pipelined fetches and the code pointer are the step's above.

@@ -131,7 +131,8 @@ std::string Engine::describe(int opt, long long n) const {
              ran_geometry(ran_score_geo_).c_str(), ran_geometry(ran_align_geo_).c_str());
     std::string out(buf);
     if (ran_score_sym_affine_)          // only where the last score call ran the int16 symmetric affine SW kernel
-        out.insert(out.size() - 1, std::string(", \"ran_score_sym_affine\": \"") + ran_score_sym_affine_ + "\"");
+        out.insert(out.size() - 1, std::string(", \"ran_score_sym_affine\": \"") + ran_score_sym_affine_ + "\", \"ran_score_sym_affine_frame\": \"" +
+                                       ran_score_sym_affine_frame_ + "\"");
     return out;
 }
 

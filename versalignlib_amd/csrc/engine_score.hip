@@ -89,7 +89,12 @@ void Engine::launch_score(const LaunchPlan &plan, int alg, int R, int F, long lo
     if (alg == kAlgSW && gaps == kGapAffineSym) {
         const bool max3 = sym_affine_max3_ok(rule_inputs(), R_, F_);
         a.sym_max3_bias = max3 ? sym_affine_bias(sc_) : 0;
+        // ... and inside the biased form's window the tilted frame where its own, narrower window holds on this geometry (bit 16
+        // of the same member says so to the kernel, which then folds 2x into its query profile)
+        const bool tilted = sym_affine_tilt_ok(rule_inputs(), R_, F_, plan.geo->G * plan.geo->K, plan.geo->K);
+        if (tilted) a.sym_max3_bias = sym_affine_tilt_bias(sc_) | 1 << 16;
         ran_score_sym_affine_ = ran_sym_affine_name(max3);
+        ran_score_sym_affine_frame_ = ran_sym_affine_frame_name(tilted);
     }
     const int block_lds = plan.lds.total * plan.waves_per_block;
     if (block_lds > kDefaultBlockLds)
