@@ -457,6 +457,63 @@ int valign_hip_score_span_device(valign_hip_engine *e, int opt, long long n, con
 int valign_hip_score_span_host(valign_hip_engine *e, int opt, int n, const char *const *reads,
                                const char *const *refs, valign_hip_span *spans, int threads);
 
+/* ---- spanned CIGARs: the alignment of the span, from the span's window instead of the full matrix ----
+ * The fourth call of a mapper, after placed, spanned and suboptimal scores: the alignment itself.  valign_hip_align_cigar_device
+ * fills and walks the whole read_length x ref_length matrix; after a spanned call the best local alignment is known to lie in
+ * read[0, read_end) x ref[ref_end - span_ref_length, ref_end), so this call fills and walks THAT window -- pointer stream and fill
+ * grow with span_ref_length (249 / 449 columns at 150 rows with linear 2 / -1 / -3 and affine -5 / -1 gaps), whatever ref_length is.
+ * Results are valign_hip_aln records and `length << 4 | code` ops, as in the compact result format above.
+ * DEFINITION, for Smith-Waterman (opt & 0xF == 0), per pair:
+ *   coordinates . read_begin, read_end, ref_begin, ref_end are exactly the record valign_hip_score_span_device returns for the pair.
+ *   ops ......... Take the alignment valign_hip_align_cigar_device would return for the pair (reversed read[0, read_end),
+ *                 reversed ref[0, ref_end)) under the Default tie-breaks.  The ops are that alignment's columns read from last to
+ *                 first, then classified and run-length encoded by vh_cigar's column rule (above).  Read backwards, that
+ *                 alignment is one of read[read_begin, read_end) against ref[ref_begin, ref_end): its end cell is the spanned
+ *                 record's begin cell (both are the first cell in row-major order of the reversed matrix that holds `score`),
+ *                 and its walk ends in the reversed origin, because the forward end cell is the only cell of the prefix
+ *                 rectangle that holds `score`.  The reversed reference is clipped to span_ref_length columns: no cell beyond
+ *                 the clip can hold `score`, and the pointers inside the clip do not depend on later columns.
+ *   score ....... the returned alignment re-scored, as in valign_hip_aln.
+ *   empty ....... a pair whose maximum is 0 returns an all-zero record and no ops.
+ * GUARANTEED: `score` equals the placed score of the pair (valign_hip_score_placed_device), and the ops consume exactly
+ * read_end - read_begin read bases and ref_end - ref_begin reference bases.  (For sequences that hold no '-' byte: the column
+ * rule reads a literal '-' as a gap, as vh_cigar does, and the begin coordinates -- the ends minus the non-gap bases of the
+ * rows, as in valign_hip_aln -- and the re-score then follow the ops.)
+ * NOT GUARANTEED: equality of the ops (or of read_begin / ref_begin) with those of valign_hip_align_cigar_device on the forward
+ * pair.  Both are optimal alignments that end in the same cell, walked under tie-breaks in opposite directions; where two
+ * optimal alignments share the end cell they may differ.  The two are not interchangeable.
+ * REFUSED with a non-zero return and a message in valign_hip_last_error: everything valign_hip_score_span_device refuses, with
+ * the same texts (opt & 0xF == 1; traceback_policy = 1; every band_width > 0, whatever band_placed says; score_width = 32 or a
+ * shape x scoring whose cells could leave int16, unless placed_wide = 1) -- and whatever the alignment route of the window's
+ * shape refuses, prefixed with "spanned CIGARs: ".  extended must be 0 or 1; anything else is refused.
+ * NOT REFUSED: under placed_wide = 1 the forward sweep runs on int32 cells and the window's alignment picks its own cells, as
+ * valign_hip_align_device always does.  pointer_scratch_cap_mb and trace_checkpoints apply to the window's alignment.
+ * opt & 0xF > 1 does nothing, as everywhere.
+ * "ran_span_cigar" of valign_hip_describe names the forward route and the window's "ran_align_fill", joined ("key/tag_prof_key",
+ * "strip/strip_ckpt", ...; "none" before any call, or when it was refused); "ran_result_format" is then "cigar" and
+ * "span_cigar_scratch_bytes" the scratch the calls hold.                                                                       */
+
+/* Device-resident: asynchronous on hip_stream.  d_recs = n records, d_ops = n * ops_stride uint32: a pair stores its first
+ * min(n_ops, ops_stride) ops in reading order at d_ops + pair * ops_stride, words past them are not written, and n_ops always
+ * says how many there are.  The call is cut into chunks (whole rounds of the forward sweep's waves) so that the reversed
+ * prefixes, the forward records and the window's rows -- 3 * (read_length + span_ref_length) + 20 bytes per pair -- stay inside
+ * an engine-owned scratch of at most 768 MiB, reused chunk after chunk in stream order: calls of one engine that use it belong
+ * on one stream.                                                                                                             */
+int valign_hip_align_span_device(valign_hip_engine *e, int opt, long long n, const void *d_reads,
+                                 const void *d_refs, int extended, void *d_recs, void *d_ops,
+                                 int ops_stride, void *hip_stream);
+
+/* Host pointers in, packed results out, with the contract of valign_hip_align_cigar_host: recs[n], offsets[n + 1] (offsets[0] =
+ * 0), pair p's ops are ops[offsets[p] .. offsets[p + 1]); if the call needs more than ops_cap ops it returns non-zero,
+ * *ops_needed holds the total and recs / offsets are complete; n = 0 sets offsets[0] = 0; opt & 0xF > 1 writes nothing.  Per
+ * chunk: gather, H2D, the launches above with a records-only sink, a scan of n_ops, the ops packed at their offsets beside the
+ * records and ONE copy back -- 24 bytes per pair, 4 per op and 8 per chunk ("cigar_d2h_bytes"); the rows never cross PCIe.
+ * Chunks follow one another on one stream and do not overlap.                                                               */
+int valign_hip_align_span_host(valign_hip_engine *e, int opt, int n, const char *const *reads,
+                               const char *const *refs, int extended, valign_hip_aln *recs,
+                               uint32_t *ops, long long ops_cap, long long *offsets,
+                               long long *ops_needed, int threads);
+
 /* ---- suboptimal Smith-Waterman scores: runner-up score and column without a traceback ----
  * A mapper computes mapping quality from the SECOND-best local alignment score: SSW's score2 / ref_end2, BWA's sub -- the best
  * score that ends at least `mask` reference columns away from where the best alignment ends.  Suboptimal scores give the placed

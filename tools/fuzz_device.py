@@ -6,7 +6,9 @@ against oracle/cpu_ref; placed Smith-Waterman scores (score_placed_device / _hos
 band_placed = 1, against tests/placed_band_ref.py; spanned scores (score_span_device / _host) against tests/span_ref.py wherever the
 unbanded placed scores run, and refused under every band; suboptimal scores (score_subopt_device / _host, a random mask) against
 tests/subopt_ref.py wherever placed scores ran on the register sweep -- and `--kind subopt` draws nothing but cases for them: shapes up
-to 160 x 300 with a second, mutated copy of the read planted in the reference.  What tools/fuzz_parity.py does for the plugin ABI, for the entry points the tests of the device path
+to 160 x 300 with a second, mutated copy of the read planted in the reference; `--kind span_cigar` draws nothing but cases for the
+spanned CIGARs (align_span_device / _host against tests/span_cigar_ref.py: random shapes up to 320 x 900 and one in eight on the row
+strips, scorings, extended, ops_stride, trace_checkpoints, pointer_scratch_cap_mb, placed_wide).  What tools/fuzz_parity.py does for the plugin ABI, for the entry points the tests of the device path
 use; a process that runs it for minutes also exercises the library's set-up and tear-down far more often than the suite.
 
     python -X faulthandler tools/fuzz_device.py --seconds 300 --seed 1
@@ -28,6 +30,7 @@ from versalignlib_amd import hipkernel, synth                      # noqa: E402
 import band_nw_ref                                                 # noqa: E402
 import placed_band_ref                                             # noqa: E402
 import placed_ref                                                  # noqa: E402
+import span_cigar_ref                                              # noqa: E402
 import span_ref                                                    # noqa: E402
 import subopt_ref                                                  # noqa: E402
 
@@ -246,6 +249,68 @@ def run(c):
             eng.close()
 
 
+def draw_span_cigar(rng):
+    """--kind span_cigar: a shape the plain-Python walk of the reference can follow, a scoring, and the keys a spanned CIGAR call reads"""
+    c = draw(rng, "subopt")
+    if rng.random() < 0.5:
+        c["R"], c["F"] = int(rng.integers(1, 321)), int(rng.integers(1, 901))
+    if rng.random() < 0.125:
+        c["R"], c["F"] = int(rng.integers(1025, 1400)), int(rng.integers(40, 1500))          # the row strips
+    c["n"] = int(max(1, min(rng.integers(1, 200), 3_000_000 // max(c["R"] * c["F"], 1))))
+    c.update(subopt_only=False, span_cigar=True, extended=bool(rng.random() < 0.5), stride=int(rng.choice([1, 2, 5, 64, 700])),
+             ckpt=bool(rng.random() < 0.3), cap_mb=int(rng.integers(1, 8)) if rng.random() < 0.2 else 0, wide=bool(rng.random() < 0.2))
+    return c
+
+
+def run_span_cigar(c):
+    R, F, n = c["R"], c["F"], c["n"]
+    reads, refs = synth.make_pairs(n, R, F, seed=c["seed"], sub_rate=0.1, indel_rate=0.02, n_run_frac=0.1, short_frac=0.3, lowercase_frac=0.05, junk_frac=0.05)
+    # a junk byte that happens to be '-' is a gap to the column rule (vh_cigar's, the encoders'): the ops would then consume one
+    # base fewer than the span holds -- of the input's making, in the reference as in the library; not what this kind is after
+    reads[reads == ord("-")] = ord("#")
+    refs[refs == ord("-")] = ord("#")
+    sc = hipkernel.Scoring.make(c["match"], c["mismatch"], c["gr"], c["gf"], **c["aff"])
+    eng = hipkernel.Engine(R, F, sc)
+    try:
+        if c["ckpt"]:
+            eng.set_trace_checkpoints(1)
+        if c["cap_mb"]:
+            eng.set_pointer_scratch_cap_mb(c["cap_mb"])
+        if c["wide"]:
+            eng.set_score_width(32)
+            eng.set_placed_wide(1)
+        stream = torch.cuda.Stream() if c["stream"] else None
+        d_reads, d_refs = torch.from_numpy(reads).cuda(), torch.from_numpy(refs).cuda()
+        torch.cuda.synchronize()
+        exp = span_cigar_ref.expected(reads, refs, sc, affine=c["affine"], extended=c["extended"])
+        recs = torch.full((n, 6), -7, dtype=torch.int32, device="cuda")
+        ops = torch.full((n, c["stride"]), -7, dtype=torch.int32, device="cuda")
+        eng.align_span_device(0, d_reads, d_refs, extended=c["extended"], ops_stride=c["stride"], stream=stream, out=(recs, ops))
+        (stream or torch.cuda.current_stream()).synchronize()
+        what = eng.describe(0, n)["ran_span_cigar"]
+        if not np.array_equal(recs.cpu().numpy().astype(np.int64), exp["recs"]):
+            return "align_span_device records differ (%s)" % what
+        got = ops.cpu().numpy()
+        for p in range(n):
+            k = min(len(exp["ops"][p]), c["stride"])
+            if got[p, :k].view(np.uint32).tolist() != exp["ops"][p][:k] or not (got[p, k:] == -7).all():
+                return "align_span_device ops of pair %d differ (%s)" % (p, what)
+        spans = eng.score_span_device(0, d_reads, d_refs, stream=stream)
+        (stream or torch.cuda.current_stream()).synchronize()
+        if not np.array_equal(spans.cpu().numpy().astype(np.int64), exp["spans"]):
+            return "score_span_device after align_span_device differs"
+        if c["host"]:
+            h_recs, h_ops, offsets = eng.align_span_host(0, reads, refs, extended=c["extended"], threads=c["threads"])
+            flat = np.stack([h_recs[k] for k in hipkernel.aln_dtype().names], axis=1).astype(np.int64)
+            if not np.array_equal(flat, exp["recs"]) or h_ops.tolist() != [o for pair in exp["ops"] for o in pair]:
+                return "align_span_host differs (%s)" % what
+            if not np.array_equal(np.diff(offsets), exp["recs"][:, 5]):
+                return "align_span_host offsets differ"
+        return None
+    finally:
+        eng.close()
+
+
 def soak_sequences(rng, a):
     """--kind sequence: the generator and the runner of tests/engine_sequences.py (what tests/test_gpu_engine_sequences.py runs
     on its committed seeds) on random seeds: ONE engine per sequence through key changes and calls, every call against its
@@ -277,7 +342,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--first", type=int, default=0)
     ap.add_argument("--verbose", action="store_true")
-    ap.add_argument("--kind", choices=["subopt", "sequence"], default=None,
+    ap.add_argument("--kind", choices=["subopt", "sequence", "span_cigar"], default=None,
                     help="draw cases of this kind only (default: the mix); sequence: one engine through tests/engine_sequences.py's sequences")
     a = ap.parse_args()
     rng = np.random.default_rng(a.seed)
@@ -286,12 +351,12 @@ def main():
     t0 = time.time()
     i = done = 0
     while time.time() - t0 < a.seconds:
-        c = draw(rng, a.kind)
+        c = draw_span_cigar(rng) if a.kind == "span_cigar" else draw(rng, a.kind)
         if i >= a.first:
             if a.verbose:
                 print("case %d: %r" % (i, c), flush=True)
             try:
-                err = run(c)
+                err = run_span_cigar(c) if a.kind == "span_cigar" else run(c)
             except hipkernel.HipKernelError as e:
                 err = "library error: %s" % e
             done += 1

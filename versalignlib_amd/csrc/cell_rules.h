@@ -496,4 +496,33 @@ inline const char *ran_fill_name(AlignRoute r, int fill_kernel = -1) {
     return fill_kernel >= 0 && fill_kernel < kFillKernels ? names[fill_kernel] : "none";
 }
 
+// ---- spanned CIGARs (valign_hip_align_span_*): the alignment of the span, filled and walked on the span's window ----
+// A spanned CIGAR call is a spanned call whose reverse sweep is an ALIGNMENT of the child shape (R, span_ref_length): refused
+// exactly where span_choice refuses, with its texts, and where align_route refuses the child's call, that text prefixed with
+// "spanned CIGARs: ".  Asked before anything is staged or launched.  `child` / `child_facts`: the rule inputs and route facts of
+// the child engine (Engine::span_cigar_prepare); `G x K` as in span_choice.
+struct SpanCigarChoice {
+    PlacedChoice forward;                       // the forward sweep's choice (route Refused: see reason)
+    AlignRoute child = AlignRoute::Register;    // the route of the child's alignment call, where nothing is refused
+    std::string reason;                         // why the call is refused; empty where it is not
+    bool refused() const { return !reason.empty(); }
+};
+constexpr const char *kSpanCigarPrefix = "spanned CIGARs: ";
+inline SpanCigarChoice span_cigar_choice(const RuleInputs &in, int alg, const PlacedFacts &f, const RuleInputs &child, const RouteFacts &child_facts,
+                                         int G = 0, int K = 0) {
+    SpanCigarChoice c;
+    c.forward = span_choice(in, alg, f, G, K);
+    if (c.forward.route == PlacedRoute::Refused) {
+        c.reason = c.forward.reason;
+        return c;
+    }
+    try {
+        c.child = align_route(child, alg, child_facts);
+    } catch (const std::runtime_error &e) {
+        c.forward = PlacedChoice{};
+        c.reason = std::string(kSpanCigarPrefix) + e.what();
+    }
+    return c;
+}
+
 }  // namespace valign

@@ -19,6 +19,9 @@
 //   engine_subopt.hip ... suboptimal Smith-Waterman scores: the placed sweep's suboptimal form, which also leaves the column
 //                         maxima in a scratch, and subopt_records_kernel (subopt_kernels.hip.h); record_pipeline again
 //   engine_cigar.hip .... the compact result format: records + CIGAR ops encoded on the device behind the walks (cigar_kernels.hip.h)
+//   engine_span_cigar.hip spanned CIGARs: the alignment of the span from the span's window -- the forward placed sweep, the
+//                         reversal, the child engine's ALIGNMENT of the reversed prefixes and the backward encoder
+//                         (span_cigar_kernels.hip.h) behind its walk
 //   hip_plugin.hip ...... the plugin ABI and the flat C API over it
 // The closest reference precedent for the staging loops is the OpenCL backend's gather / copy / launch / collect loop
 // (src/Kernels/OpenCL/OpenCLKernel.cpp:57-108); unlike it, chunks here are large, asynchronous and overlapped.
@@ -56,6 +59,7 @@
 #include "pack_kernels.hip.h"
 #include "ragged_kernels.hip.h"
 #include "span_kernels.hip.h"
+#include "span_cigar_kernels.hip.h"
 #include "subopt_kernels.hip.h"
 #include "strip_kernels.hip.h"
 #include "strip_plan.h"
@@ -170,7 +174,7 @@ public:
         static const char *const known[] = {"no_sym", "no_tag", "no_f16", "no_max3", "no_tilt", "no_fused", "no_prof_key", "no_overlap", "no_band_chain",
                                             "force_long", "wide_align", "strip_k", "no_single_strip", "no_direct_out", "ragged_min", "chunk_bytes",
                                             "align_chunk_bytes", "direct_bytes", "scratch_cap_mb", "whole_rows", "short_strips", "cigar_rows_mb", "cigar_lanes",
-                                            "span_scratch_bytes", "subopt_scratch_bytes"};
+                                            "span_scratch_bytes", "subopt_scratch_bytes", "span_cigar_mb"};
         std::string s(env);
         for (size_t at = 0; at <= s.size();) {
             const size_t end = std::min(s.find(',', at), s.size());
@@ -493,6 +497,21 @@ public:
     void score_span_host(int opt, int n, const char *const *reads, const char *const *refs, SpanRec *spans, int threads);
     const char *ran_span() const { return ran_span_.c_str(); }
 
+    // ---- spanned CIGARs (valign_hip.h: valign_hip_align_span_*; engine_span_cigar.hip) ----
+    // The alignment of the span, filled and walked on the span's window instead of the whole matrix: score_placed_device as it
+    // stands, the reversal, align_device of the child engine (shape (R, span_ref_length), every route it has) over the reversed
+    // prefixes into an engine-owned rows scratch, and span_cigar_encode_kernel behind its walk, which reads the rows backwards
+    // and places the record with the forward one.  span_cigar_choice (cell_rules.h) decides what is refused, before anything is
+    // staged or launched.  Device-resident: asynchronous on `stream`, in chunks of whole rounds that keep the reversed
+    // prefixes, the forward records and the child's rows inside span_cigar_bytes_; calls of one engine belong on one stream.
+    // Host pointers: chunk after chunk on one stream -- gather, H2D, the chunk with a records-only sink, the scan, the emit
+    // pass, ONE copy of records and ops back; chunks do not overlap.  false: the call needs more than ops_cap ops.
+    void align_span_device(int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int extended, CigarRec *d_recs, unsigned *d_ops,
+                           int ops_stride, hipStream_t stream);
+    bool align_span_host(int opt, int n, const char *const *reads, const char *const *refs, int extended, CigarRec *recs, unsigned *ops,
+                         long long ops_cap, long long *offsets, long long *ops_needed, int threads);
+    const char *ran_span_cigar() const { return ran_span_cigar_.c_str(); }
+
     // ---- suboptimal Smith-Waterman scores (valign_hip.h: valign_hip_subopt; engine_subopt.hip) ----
     // The placed record plus score2 / ref_end2: the placed register sweep in its suboptimal form, which also leaves every
     // column's maximum in an engine-owned scratch, then subopt_records_kernel.  subopt_choice (cell_rules.h) decides what is
@@ -646,11 +665,15 @@ private:
         CigarRec *recs;
         unsigned *ops;              // null: records only (host path: the ops follow the chunk's scan)
         int ops_stride, extended;
+        const PlacedRec *fwd = nullptr;     // not null (the child engine of a spanned CIGAR call): the rows are those of the reversed
+        int fwd_ref_length = 0;             // prefixes -- the backward encoder places them with these forward records of an R x fwd_ref_length pair
     };
     // encode `cnt` pairs from pair `begin` of the call on `stream`: rows / idx / ends are those of pair `begin`
     void launch_cigar(hipStream_t stream, const uint8_t *rows, const short *idx, const EndCell *ends, long long begin, long long cnt);
     void launch_cigar_args(hipStream_t stream, CigarArgs &a);
     void ensure_cigar_scratch(int slots, long long pairs, hipStream_t stream);
+    // offsets[0 .. n] = exclusive scan of recs[p].n_ops on `stream` (cigar_scan_kernel)
+    void launch_cigar_scan(const CigarRec *recs, long long *offsets, long long n, hipStream_t stream);
 
     // gather / scatter between the caller's scattered blocks and the staging: host_pipeline.h (host-only, sanitizer-tested)
     template <typename Sink>
@@ -696,6 +719,34 @@ private:
     void ensure_span_scratch(int c, long long pairs, hipStream_t stream);
     // one chunk, all of it on `stream`: forward sweep, reversal, reverse sweep, records
     void span_chunk(int c, int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, SpanRec *d_spans, hipStream_t stream);
+    // span_reverse_kernel on `stream`: the prefixes that end in fwd's end cells, reversed, Fr columns of the reference's
+    void launch_span_reverse(long long n, const uint8_t *d_reads, const uint8_t *d_refs, const PlacedRec *fwd, uint8_t *rev_reads, uint8_t *rev_refs,
+                             int Fr, hipStream_t stream);
+
+    // ---- spanned CIGARs (engine_span_cigar.hip) ----
+    // One context for host-pointer calls and one for device-resident calls: the reversed prefixes, the forward records and the
+    // child's rows / idx of one chunk; host path: the count pass's records, the scanned offsets, records + ops as they cross PCIe
+    struct SpanCigarCtx {
+        long long cap = 0;                     // pairs the buffers hold
+        DeviceBuffer<uint8_t> rev_reads, rev_refs, rows;
+        DeviceBuffer<PlacedRec> fwd;
+        DeviceBuffer<short> idx;
+        DeviceBuffer<CigarRec> recs;
+        DeviceBuffer<long long> offsets;
+        DeviceBuffer<uint8_t> out;
+        PinnedBuffer<uint8_t> h_out;
+        PinnedBuffer<long long> h_total;
+        size_t bytes() const { return rev_reads.bytes() + rev_refs.bytes() + rows.bytes() + fwd.bytes() + idx.bytes(); }
+    };
+    // refusals (thrown), then the child engine, configured as the parent is for this call
+    Engine &span_cigar_prepare(int alg);
+    long long span_cigar_chunk_pairs(long long n) const;
+    void ensure_span_cigar_scratch(int c, long long pairs, bool host, hipStream_t stream);
+    // one chunk, all of it on `stream`: forward sweep, reversal, the child's alignment with `sink` behind its walk
+    void span_cigar_chunk(int c, int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, const CigarSink &sink, hipStream_t stream);
+    // (of the child) encode `cnt` pairs from pair `begin` of the call behind their walk, or, with filled args, any pass
+    void launch_span_cigar(hipStream_t stream, const uint8_t *rows, const short *idx, long long begin, long long cnt);
+    void launch_span_cigar_args(hipStream_t stream, SpanCigarArgs &a);
 
     // ---- suboptimal scores (engine_subopt.hip) ----
     // One context per pipeline slot and one for device-resident calls: the column maxima and the placed records of one chunk
@@ -854,6 +905,8 @@ private:
     const char *ran_placed_ = "none";                    // what the last placed-score call ran: key / rows / strip / chain / wide (describe)
     std::string ran_span_ = "none";                      // what the last spanned call ran: forward route / reverse route (describe)
     size_t span_scratch_bytes_ = (size_t)dbg_.value("span_scratch_bytes", 256ll << 20);      // device-resident spanned calls: scratch of one chunk
+    std::string ran_span_cigar_ = "none";                // what the last spanned CIGAR call ran: forward route / the child's ran_align_fill (describe)
+    size_t span_cigar_bytes_ = (size_t)std::max(0ll, dbg_.value("span_cigar_mb", 768)) << 20;      // scratch of one chunk: the spanned scores' 256 MiB + 512 MiB of rows
     const char *ran_subopt_ = "none";                    // what the last suboptimal call ran: key / rows (describe)
     int subopt_ring_cols_ = 0;                           // ... and the columns of a lane group's ring in its sweep
     size_t subopt_scratch_bytes_ = (size_t)dbg_.value("subopt_scratch_bytes", 256ll << 20);      // column maxima of one chunk
@@ -910,6 +963,7 @@ private:
     // spanned scores: the reversal scratch, the engine of the reverse sweep
     SpanCtx span_[kSlots + 1];                                   // one per pipeline slot, the last for device-resident calls
     std::unique_ptr<Engine> span_child_;
+    SpanCigarCtx span_cigar_[2];                                 // spanned CIGARs: [0] host-pointer calls, [1] device-resident calls
     SuboptCtx subopt_[kSlots + 1];                               // one per pipeline slot, the last for device-resident calls
     DeviceBuffer<unsigned> d_brow_;                              // long-read path: strip boundary rows
     DeviceBuffer<BandBlock> d_band_blocks_;                      // the block chain's tables (band_plan_)

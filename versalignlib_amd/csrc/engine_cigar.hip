@@ -41,6 +41,10 @@ void Engine::launch_cigar_args(hipStream_t stream, CigarArgs &a) {
 
 void Engine::launch_cigar(hipStream_t stream, const uint8_t *rows, const short *idx, const EndCell *ends, long long begin, long long cnt) {
     if (!cigar_ || cnt <= 0) return;
+    if (cigar_->fwd) {                      // the child engine of a spanned CIGAR call: the backward encoder (engine_span_cigar.hip)
+        launch_span_cigar(stream, rows, idx, begin, cnt);
+        return;
+    }
     CigarArgs a{};
     a.rows = rows;
     a.idx = idx;
@@ -51,6 +55,11 @@ void Engine::launch_cigar(hipStream_t stream, const uint8_t *rows, const short *
     a.n = cnt;
     a.extended = cigar_->extended;
     launch_cigar_args(stream, a);
+}
+
+void Engine::launch_cigar_scan(const CigarRec *recs, long long *offsets, long long n, hipStream_t stream) {
+    hipLaunchKernelGGL(cigar_scan_kernel, dim3(1), dim3(1024), 0, stream, recs, offsets, n);
+    hip_check(hipGetLastError(), "hipLaunchKernel(cigar_scan_kernel)");
 }
 
 void Engine::ensure_cigar_scratch(int slots, long long pairs, hipStream_t stream) {
@@ -221,8 +230,7 @@ bool Engine::align_cigar_host(int opt, int n, const char *const *reads, const ch
             }
         }
         hipStream_t tail = chained ? trace_stream_.get() : kernels;
-        hipLaunchKernelGGL(cigar_scan_kernel, dim3(1), dim3(1024), 0, tail, (const CigarRec *)d_cig_recs_[s].get(), d_cig_offsets_[s].get(), cnt);
-        hip_check(hipGetLastError(), "hipLaunchKernel(cigar_scan_kernel)");
+        launch_cigar_scan(d_cig_recs_[s].get(), d_cig_offsets_[s].get(), cnt, tail);
         hip_check(hipMemcpyAsync(h_cig_total_.get() + s, d_cig_offsets_[s].get() + cnt, sizeof(long long), hipMemcpyDeviceToHost, tail), "D2H op total");
         hip_check(hipEventRecord(kernels_done_[s].get(), tail), "hipEventRecord");
         pend[s].begin = begin;

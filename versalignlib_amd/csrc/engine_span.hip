@@ -52,27 +52,32 @@ void Engine::ensure_span_scratch(int c, long long pairs, hipStream_t stream) {
     x.cap = pairs;
 }
 
-void Engine::span_chunk(int c, int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, SpanRec *d_spans, hipStream_t stream) {
-    SpanCtx &x = span_[c];
-    Engine &child = *span_child_;
-    if (n > x.cap) throw std::runtime_error("spanned scores: chunk larger than its scratch");
-    score_placed_device(opt, n, d_reads, d_refs, x.fwd.get(), stream);
+void Engine::launch_span_reverse(long long n, const uint8_t *d_reads, const uint8_t *d_refs, const PlacedRec *fwd, uint8_t *rev_reads, uint8_t *rev_refs,
+                                 int Fr, hipStream_t stream) {
     SpanReverseArgs a{};
     a.reads = d_reads;
     a.refs = d_refs;
-    a.fwd = x.fwd.get();
-    a.rev_reads = x.rev_reads.get();
-    a.rev_refs = x.rev_refs.get();
+    a.fwd = fwd;
+    a.rev_reads = rev_reads;
+    a.rev_refs = rev_refs;
     a.n = n;
     a.R = R_;
     a.F = F_;
-    a.Fr = child.ref_length();
+    a.Fr = Fr;
     // about 4 KB of destination bytes per block, whole pairs
     a.pairs_per_block = (int)std::min<long long>(64, std::max<long long>(1, 4096 / std::max(1, R_ + a.Fr)));
     const long long blocks = (n + a.pairs_per_block - 1) / a.pairs_per_block;
     if (blocks > 0x7FFFFFFFll) throw std::runtime_error("batch too large for one launch");
     hipLaunchKernelGGL(span_reverse_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
     hip_check(hipGetLastError(), "hipLaunchKernel(span_reverse_kernel)");
+}
+
+void Engine::span_chunk(int c, int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, SpanRec *d_spans, hipStream_t stream) {
+    SpanCtx &x = span_[c];
+    Engine &child = *span_child_;
+    if (n > x.cap) throw std::runtime_error("spanned scores: chunk larger than its scratch");
+    score_placed_device(opt, n, d_reads, d_refs, x.fwd.get(), stream);
+    launch_span_reverse(n, d_reads, d_refs, x.fwd.get(), x.rev_reads.get(), x.rev_refs.get(), child.ref_length(), stream);
     child.score_placed_device(opt, n, x.rev_reads.get(), x.rev_refs.get(), x.rev.get(), stream);
     hip_check(hipSetDevice(device_), "hipSetDevice");
     hipLaunchKernelGGL(span_records_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const PlacedRec *)x.fwd.get(),

@@ -670,6 +670,36 @@ VALIGN_EXPORT int valign_hip_score_span_host(valign_hip_engine *e, int opt, int 
     return flat_guard([&] { e->impl->score_span_host(opt, n, reads, refs, (valign::SpanRec *)spans, threads); });
 }
 
+VALIGN_EXPORT int valign_hip_align_span_device(valign_hip_engine *e, int opt, long long n, const void *d_reads, const void *d_refs,
+                                               int extended, void *d_recs, void *d_ops, int ops_stride, void *hip_stream) {
+    if (!e) {
+        g_last_error = "null engine";
+        return 1;
+    }
+    return flat_guard([&] {
+        e->impl->align_span_device(opt, n, (const uint8_t *)d_reads, (const uint8_t *)d_refs, extended, (valign::CigarRec *)d_recs,
+                                   (unsigned *)d_ops, ops_stride, (hipStream_t)hip_stream);
+    });
+}
+
+VALIGN_EXPORT int valign_hip_align_span_host(valign_hip_engine *e, int opt, int n, const char *const *reads, const char *const *refs,
+                                             int extended, valign_hip_aln *recs, uint32_t *ops, long long ops_cap, long long *offsets,
+                                             long long *ops_needed, int threads) {
+    if (!e) {
+        g_last_error = "null engine";
+        return 1;
+    }
+    bool fits = true;
+    const int rc = flat_guard([&] {
+        fits = e->impl->align_span_host(opt, n, reads, refs, extended, (valign::CigarRec *)recs, ops, ops_cap, offsets, ops_needed, threads);
+    });
+    if (rc == 0 && !fits) {
+        g_last_error = "ops_cap is too small: the call needs " + std::to_string(*ops_needed) + " ops";
+        return 2;
+    }
+    return rc;
+}
+
 static_assert(sizeof(valign_hip_subopt) == sizeof(valign::SuboptRec) && sizeof(valign_hip_subopt) == 20, "valign_hip_subopt is the kernels' record");
 
 VALIGN_EXPORT int valign_hip_score_subopt_device(valign_hip_engine *e, int opt, long long n, const void *d_reads, const void *d_refs,

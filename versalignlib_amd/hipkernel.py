@@ -104,6 +104,8 @@ def lib():
                                                     ctypes.c_int, vp]
         L.valign_hip_align_cigar_host.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp,
                                                   ctypes.c_longlong, vp, vp, ctypes.c_int]
+        L.valign_hip_align_span_device.argtypes = L.valign_hip_align_cigar_device.argtypes
+        L.valign_hip_align_span_host.argtypes = L.valign_hip_align_cigar_host.argtypes
         L.valign_hip_score_placed_device.argtypes = [vp, ctypes.c_int, ctypes.c_longlong, vp, vp, vp, vp]
         L.valign_hip_score_placed_host.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int]
         L.valign_hip_score_span_device.argtypes = [vp, ctypes.c_int, ctypes.c_longlong, vp, vp, vp, vp]
@@ -120,7 +122,7 @@ def lib():
 EXPORTED_SYMBOLS = (
     "spawn_alignment_kernel", "set_parameters", "set_logger", "delete_alignment_kernel",
     "valign_hip_device_count", "valign_hip_shard_range", "valign_hip_engine_create", "valign_hip_engine_destroy",
-    "valign_hip_set_traceback_policy", "valign_hip_set_pointer_scratch_cap_mb", "valign_hip_set_host_packing", "valign_hip_set_half_float_cells", "valign_hip_host_register", "valign_hip_host_unregister", "valign_hip_set_band_width", "valign_hip_set_band_alignments", "valign_hip_set_band_nw", "valign_hip_set_band_placed", "valign_hip_set_placed_wide", "valign_hip_set_trace_checkpoints", "valign_hip_set_score_width", "valign_hip_set_ragged_batching", "valign_hip_score_device", "valign_hip_align_device", "valign_hip_score_host", "valign_hip_align_host", "valign_hip_align_cigar_device", "valign_hip_align_cigar_host", "valign_hip_score_placed_device", "valign_hip_score_placed_host", "valign_hip_score_span_device", "valign_hip_score_span_host", "valign_hip_score_subopt_device", "valign_hip_score_subopt_host", "valign_hip_describe",
+    "valign_hip_set_traceback_policy", "valign_hip_set_pointer_scratch_cap_mb", "valign_hip_set_host_packing", "valign_hip_set_half_float_cells", "valign_hip_host_register", "valign_hip_host_unregister", "valign_hip_set_band_width", "valign_hip_set_band_alignments", "valign_hip_set_band_nw", "valign_hip_set_band_placed", "valign_hip_set_placed_wide", "valign_hip_set_trace_checkpoints", "valign_hip_set_score_width", "valign_hip_set_ragged_batching", "valign_hip_score_device", "valign_hip_align_device", "valign_hip_score_host", "valign_hip_align_host", "valign_hip_align_cigar_device", "valign_hip_align_cigar_host", "valign_hip_score_placed_device", "valign_hip_score_placed_host", "valign_hip_score_span_device", "valign_hip_score_span_host", "valign_hip_align_span_device", "valign_hip_align_span_host", "valign_hip_score_subopt_device", "valign_hip_score_subopt_host", "valign_hip_describe",
     "valign_hip_last_error",
 )
 
@@ -446,6 +448,57 @@ class Engine:
         if rc != 0:
             raise HipKernelError(_err())
         return spans
+
+    def align_span_device(self, opt, reads, refs, extended=False, ops_stride=64, stream=None, out=None):
+        """Spanned CIGARs: the alignment of every pair's span, filled and walked on the span's window instead of the whole
+        matrix (include/valign_hip.h has the definition).  -> recs int32 CUDA [n, 6] and ops int32 CUDA [n, ops_stride], as
+        align_cigar_device returns them; the coordinates are score_span_device's, the score score_placed_device's.
+        Asynchronous on the current stream (or `stream`).  `out` = (recs, ops) of an earlier call is written in place.
+        Refused (HipKernelError) where spanned scores are."""
+        import torch
+        n = reads.shape[0]
+        assert reads.is_cuda and refs.is_cuda and reads.is_contiguous() and refs.is_contiguous()
+        assert reads.dtype == torch.uint8 and refs.dtype == torch.uint8
+        assert tuple(reads.shape) == (n, self.read_length) and tuple(refs.shape) == (n, self.ref_length)
+        if out is not None:
+            recs, ops = out
+            assert recs.is_cuda and recs.is_contiguous() and recs.dtype == torch.int32 and tuple(recs.shape) == (n, 6)
+            assert ops.is_cuda and ops.is_contiguous() and ops.dtype == torch.int32 and tuple(ops.shape) == (n, max(int(ops_stride), 1))
+        else:
+            recs = torch.empty((n, 6), dtype=torch.int32, device=reads.device)
+            ops = torch.empty((n, max(int(ops_stride), 1)), dtype=torch.int32, device=reads.device)
+        st = stream if stream is not None else torch.cuda.current_stream(reads.device)
+        rc = lib().valign_hip_align_span_device(self._h, int(opt), n, reads.data_ptr(), refs.data_ptr(), int(extended),
+                                                recs.data_ptr(), ops.data_ptr(), int(ops_stride), st.cuda_stream)
+        if rc != 0:
+            raise HipKernelError(_err())
+        return recs, ops
+
+    def align_span_host(self, opt, reads, refs, extended=False, threads=1, ops_cap=None):
+        """Host-pointer path of the spanned CIGARs: -> recs (structured, aln_dtype()) [n], ops uint32 [offsets[n]], offsets
+        int64 [n + 1], as align_cigar_host returns them.  `ops` is sized from a guess (`ops_cap`, default 16 per pair) and the
+        call repeated once with the exact size where that was too small."""
+        import numpy as np
+        n = reads.shape[0]
+        assert reads.dtype == np.uint8 and refs.dtype == np.uint8 and reads.flags.c_contiguous and refs.flags.c_contiguous
+        assert tuple(reads.shape) == (n, self.read_length) and tuple(refs.shape) == (n, self.ref_length)
+        rp = (reads.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(self.read_length)).astype(np.uint64)
+        fp = (refs.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(self.ref_length)).astype(np.uint64)
+        recs = np.zeros(n, dtype=aln_dtype())
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        cap = 16 * n if ops_cap is None else int(ops_cap)
+        for _ in range(2):
+            ops = np.zeros(max(cap, 1), dtype=np.uint32)
+            needed = ctypes.c_longlong(0)
+            rc = lib().valign_hip_align_span_host(self._h, int(opt), n, rp.ctypes.data, fp.ctypes.data, int(extended),
+                                                  recs.ctypes.data, ops.ctypes.data, cap, offsets.ctypes.data,
+                                                  ctypes.byref(needed), int(threads))
+            if rc == 0:
+                return recs, ops[:int(offsets[n])], offsets
+            if needed.value <= cap:
+                break
+            cap = needed.value
+        raise HipKernelError(_err())
 
     def score_subopt_device(self, opt, reads, refs, mask, out=None, stream=None):
         """Suboptimal Smith-Waterman scores: -> int32 CUDA [n, 5] (score, read_end, ref_end, score2, ref_end2 --
