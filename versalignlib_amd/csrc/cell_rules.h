@@ -199,6 +199,10 @@ inline long long sym_affine_tilt_top_index(int R, int F, int rows, int K) {
 }
 // ... and the form is legal inside the plain biased form's window, for K <= kTiltMaxK (cell_constants.h), where B plus the largest tilt plus the largest cell stays at
 // or below 0x7BFF.  R, F as in sym_affine_max3_ok; rows, K: of the geometry the launch runs on.
+// The running maxima of the sweep stay in the frame: an accumulator is carried from anti-diagonal to anti-diagonal of its lane and
+// holds, whenever a maximum reads it, the largest cell that lane has seen so far plus B + x * u of a cell of the sweep (u <= the top
+// index) -- a cell of the matrix plus a tilt of the sweep, which is what `hi` and the top index bound already: the rule stands as it is
+// (tests/test_sym_affine_inframe_sweep.py asserts it of every operand at the rule's edge).
 inline bool sym_affine_tilt_ok(const RuleInputs &in, int R, int F, int rows, int K) {
     if (in.no_tilt || K > kTiltMaxK || !sym_affine_max3_ok(in, R, F)) return false;
     const Scoring &sc = in.sc;

@@ -291,7 +291,7 @@ __device__ __forceinline__ bool wave_setup(const uint8_t *reads, const uint8_t *
                                            int prof_area, int refc_stride, int wave_lds, short match,
                                            short mismatch, WaveTables &w, bool bad_is_non_acgt = false,
                                            unsigned block = blockIdx.x, short zero_score = 0,
-                                           int strip_row0 = kOneSweep, short row_key_step = 0) {
+                                           int strip_row0 = kOneSweep, short row_key_step = 0, short row0_score = 0) {
     using geo = Geo<G, K>;
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x / kWave;
@@ -418,7 +418,7 @@ __device__ __forceinline__ bool wave_setup(const uint8_t *reads, const uint8_t *
     // per item.  The classes leave the staging area before the barrier, the profile overwrites it after.
     unsigned rd4[K / 2];
     constexpr int kItemPairs = 256 / geo::kRows, kItemRows = 256 % geo::kRows;
-    const int item_p0 = (4 * lane) / geo::kRows, item_rr0 = (4 * lane) % geo::kRows;
+    const int item_p0 = (4 * lane) / geo::kRows, item_rr0 = (4 * lane) % geo::kRows, item_q0 = (4 * lane) % K;
     if (live && rd_staged) {
         const unsigned char *raw = prof + rd_off + (int)((unsigned long long)(reads + pair0 * R) & 15ull);
         int p = item_p0, rr = item_rr0;
@@ -467,6 +467,20 @@ __device__ __forceinline__ bool wave_setup(const uint8_t *reads, const uint8_t *
                 key01 = u16x2{(unsigned short)(row_key_step * (15 - q0)), (unsigned short)(row_key_step * (15 - q1))};
                 key23 = u16x2{(unsigned short)(row_key_step * (15 - q2)), (unsigned short)(row_key_step * (15 - q3))};
             }
+            // row0_score: every score of row 0 of a lane also carries it (score_kernel's tilted sweep: see its hand-over)
+            if (row0_score != 0) {
+                // rr % K without a division per item: kRows is a multiple of K, so it is (4 lane + 256 it) % K
+                int q0 = item_q0 + (256 * it) % K;
+                q0 -= q0 >= K ? K : 0;
+                // row rr + i of the item is a lane's row 0 where q0 + i is a multiple of K (q0 + i <= K + 2)
+                auto row0 = [&](int i) __attribute__((always_inline)) {
+                    const int q = q0 + i;
+                    return (i == 0 ? q == 0 : q == K) || (K < 4 && q == 2 * K);
+                };
+                const unsigned short a = (unsigned short)row0_score, none = 0;
+                key01 = key01 + u16x2{row0(0) ? a : none, row0(1) ? a : none};
+                key23 = key23 + u16x2{row0(2) ? a : none, row0(3) ? a : none};
+            }
             unsigned char *dst = prof + p * geo::kPairStride + 2 * rr;          // row_offset(rr / K, rr % K) == 2 rr
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
@@ -498,7 +512,8 @@ __device__ __forceinline__ bool wave_setup(const uint8_t *reads, const uint8_t *
             const int off = p * geo::kPairStride + geo::row_offset(rr / K, rr % K);
             // row_key_step: every score of row q of a lane also carries (15 - q) * step -- the Smith-Waterman end-cell key
             // of align_fill_tag_kernel<..., PROFKEY>, which then rides on every diagonal candidate for free
-            const short row_key = (short)(row_key_step * (15 - rr % K));
+            // row0_score: ... and every score of row 0 of a lane that (score_kernel's tilted sweep)
+            const short row_key = (short)(row_key_step * (15 - rr % K) + (rr % K == 0 ? row0_score : 0));
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const short sc = (short)((valid ? (a == c + 1 ? match : mismatch) : zero_score) + row_key);
@@ -508,8 +523,8 @@ __device__ __forceinline__ bool wave_setup(const uint8_t *reads, const uint8_t *
     }
     if (live) {
         for (int idx = lane; idx < geo::kPairStride / 4; idx += kWave) {          // dword idx: rows 2 idx, 2 idx + 1
-            const unsigned lo = (unsigned short)(zero_score + row_key_step * (15 - (2 * idx) % K));
-            const unsigned hi = (unsigned short)(zero_score + row_key_step * (15 - (2 * idx + 1) % K));
+            const unsigned lo = (unsigned short)(zero_score + row_key_step * (15 - (2 * idx) % K) + ((2 * idx) % K == 0 ? row0_score : 0));
+            const unsigned hi = (unsigned short)(zero_score + row_key_step * (15 - (2 * idx + 1) % K) + ((2 * idx + 1) % K == 0 ? row0_score : 0));
             reinterpret_cast<unsigned *>(prof + geo::kZeroSlab * geo::kPairStride)[idx] = lo | (hi << 16);
         }
     }
@@ -652,8 +667,13 @@ score_kernel(const ScoreArgs args) {
     int fold = tilt_row + tilt_col;
     // (int16 symmetric affine Smith-Waterman in its tilted biased form -- see the sweep below -- pays both extensions on the
     // diagonal as the NW frame does: 2x on every score of the profile, the zero slab included)
+    // (... and its lanes hand H - (o - x) of their last row down, so every score of a lane's row 0 carries the o - x back)
+    short s_row0 = 0;
     if constexpr (SOURCES && K <= kTiltMaxK) {
-        if (args.sym_max3_bias > 0 && (args.sym_max3_bias >> 16) != 0) fold = -2 * (int)args.ext_ref;
+        if (args.sym_max3_bias > 0 && (args.sym_max3_bias >> 16) != 0) {
+            fold = -2 * (int)args.ext_ref;
+            s_row0 = (short)((int)args.ext_ref - (int)args.open_ref);
+        }
     }
     // Half-float cells are exact up to 2048 in magnitude and the frame only ever adds: a constant taken off every cell
     // (borders start at -centre, results get it back) puts the sweep's value range [~0, top + tilt] around zero.  The
@@ -677,7 +697,7 @@ score_kernel(const ScoreArgs args) {
     const short s_mismatch = HALF ? __builtin_bit_cast(short, (_Float16)(((int)args.mismatch + fold) * unit)) : (short)(args.mismatch + fold);
     const short s_zero = HALF ? __builtin_bit_cast(short, (_Float16)fold) : (short)fold;
     if (!wave_setup<G, K, false>(reads, refs, n_pairs, args.R, F_batch, args.prof_area, args.refc_stride,
-                                 args.wave_lds, s_match, s_mismatch, w, false, block, s_zero))
+                                 args.wave_lds, s_match, s_mismatch, w, false, block, s_zero, kOneSweep, 0, s_row0))
         return;
     const long long pair0 = w.pair0;
     // Smith-Waterman: columns after the last ACGT base of every reference in the wave (the NUL
@@ -1055,36 +1075,49 @@ score_kernel(const ScoreArgs args) {
                 // A lane outside the columns or on padding rows fetches S' = 2x and stays exactly at its floors:
                 // d = floor(p-1, j-1) + 2x = floor(p, j), e = max3(floor - x, floor - o, floor), f <= floor.
                 // THE RUNNING MAXIMUM.  The diag + S' of one step carry K different tilts, those with the same c = q + t one:
-                // an accumulator per live c in the floors' slots, fed with this step's d and the previous step's two at a
-                // time on every second step (row 0's alone on the others), and taken out of the frame -- acc - floor, a plain
-                // int16 maximum into `best`, which is the score itself -- when row 0 completes its anti-diagonal: once per step.
-                // steps % K remainder steps run first; they feed every d singly and rotate the slots by copying.
-                // tests/test_sym_affine_tilted_sweep.py restates all of this on the CPU.
+                // an accumulator per live c in the floors' slots (how it is fed and carried: at the step below).
+                // tests/test_sym_affine_tilted_sweep.py restates the frame on the CPU, tests/test_sym_affine_inframe_sweep.py
+                // the sweep as it runs here.
                 const int B = args.sym_max3_bias & 0xFFFF, xi = -(int)args.ext_ref;
-                const s16x2 ox_c = pk((short)(-(int)args.open_ref - xi)), kx_c = pk((short)(K * xi));
+                const int oxi = -(int)args.open_ref - xi;
+                const s16x2 ox_c = pk((short)oxi), kx_c = pk((short)(K * xi));
                 const int u0 = l * (K - 1);                                    // u of row -1 before step 0
-                s16x2 lead_border = as_pk(as_u32(pk((short)(B + xi))) & ~lmask);     // row -1 as the group's first lane reads it at step 0
-                const s16x2 lead_step = as_pk(as_u32(pk((short)xi)) & ~lmask);        // ... one x on per step; zero below that lane
+                // THE HAND-OVER carries H - (o - x) of the lane's last row, which that lane has anyway (its ho): it is F's source
+                // of row 0 as it comes, and row 0's diagonal one step later with the o - x back from the profile -- wave_setup
+                // adds it to every score of a lane's row 0, zero slab included, for this loop only.  The moving border of the
+                // group's first lane (row -1 as it reads it at step 0, one x on per step, zero below that lane) enters alike.
+                s16x2 lead_border = as_pk(as_u32(pk((short)(B + xi - oxi))) & ~lmask);
+                const s16x2 lead_step = as_pk(as_u32(pk((short)xi)) & ~lmask);
+                // THE REMAINDER.  steps % K steps run first, as the LAST steps of a trip: the slots start out named as that
+                // step finds them (row q of the first step reads slot (q + s0) % K) and nothing is copied to rotate them.
+                // (Each step of that tail is conditional; where a skipped and a run step join the compiler places some register
+                // copies.  Entering the trip through a switch, or leaving a trailing one through side exits, cost 146 and 495
+                // VGPRs at 16 x 10 against 118: profiles/r20_sym_affine_inframe.txt.)
+                const int s0 = K - steps % K;                                  // 1 .. K; K: no remainder
                 s16x2 fl[K], acc[K], dprev[K];
 #pragma unroll
                 for (int q = 0; q < K; ++q) {
                     Hl[q] = El[q] = pk((short)(B + xi * (u0 + q + 1)));
                     HOl[q] = Hl[q] - ox_c;
-                    fl[q] = acc[q] = pk((short)(B + xi * (u0 + q + 2)));      // an accumulator at its floor holds 0
-                    dprev[q] = fl[q];
+                    int c = q - s0;                                           // the anti-diagonal slot q stands for at step 0
+                    c += c < 0 ? K : 0;
+                    fl[q] = acc[q] = pk((short)(B + xi * (u0 + c + 2)));      // an accumulator at its floor holds 0
+                    dprev[q] = Hl[q];                                         // (odd q) "row q at step -1": the floor of c = q - 1
                 }
-                up0 = pk((short)(B + xi * u0));
-                h_last = Hl[K - 1];
-                f_last = h_last - ox_c;
-                best = pk(0);
-                constexpr int kFeedAll = 0, kFeedRow0 = 1, kFeedPairs = 2;
-                // One step; row q reads slot (q + SLOT0) % K.  The hand-over, the pipelined fetches and the code pointer are
-                // the plain biased step's.
-                auto tilted_step = [&](auto slot_tag, auto feed_tag) __attribute__((always_inline)) {
-                    constexpr int SLOT0 = decltype(slot_tag)::value, FEED = decltype(feed_tag)::value;
+                up0 = pk((short)(B + xi * u0 - oxi));
+                f_last = HOl[K - 1];
+                // One step; row q reads slot (q + SLOT0) % K.  The pipelined fetches and the code pointer are the plain biased
+                // step's.
+                // THE RUNNING MAXIMUM STAYS IN THE FRAME.  Rows go in pairs: the d of an even row q and the previous step's d of
+                // row q + 1 lie on the same anti-diagonal c = q + t and enter its accumulator in one max3, K / 2 per step.  When
+                // row 0 completes its anti-diagonal the slot moves on to c + K, floor and accumulator alike (+ K x: the same value
+                // read in the new frame), and the accumulator keeps collecting: it holds the largest cell so far plus B + x u of a
+                // cell of the sweep, which sym_affine_tilt_ok bounds.  The K accumulators leave the frame once, after the last step.
+                auto tilted_step = [&](auto slot_tag) __attribute__((always_inline)) {
+                    constexpr int SLOT0 = decltype(slot_tag)::value;
                     s16x2 S[K], d[K];
                     const s16x2 diag0 = up0;
-                    up0 = group_prev_or<G>(h_last, lead_border, lmask);
+                    up0 = group_prev_or<G>(HOl[K - 1], lead_border, lmask);
                     lead_border = lead_border + lead_step;
                     merge_profile<K>(pa, pb, S);
                     lds_load_lane<K>(lane_base + ca_next * geo::kPairStride, pa);
@@ -1097,7 +1130,7 @@ score_kernel(const ScoreArgs args) {
                         e = pk_max3_h(El[q], HOl[q], fl[(q + SLOT0) % K]);
                         El[q] = e;
                     };
-                    s16x2 ho = up0 - ox_c;
+                    s16x2 ho = up0;
                     pass1(0, e_cur);
                     // F of the lane above, the shift's zero in the group's first lane (fetched behind the first row's pass 1)
                     s16x2 f = as_pk(group_prev_or_zero<G>(as_u32(f_last), lmask)), h = pk(0);
@@ -1110,42 +1143,33 @@ score_kernel(const ScoreArgs args) {
                         Hl[q] = h;
                         ho = h - ox_c;
                         HOl[q] = ho;
-                        s16x2 &a = acc[(q + SLOT0) % K];
-                        if (FEED == kFeedAll) a = pk_max_h(a, d[q]);
-                        else if (FEED == kFeedRow0) { if (q == 0) a = pk_max_h(a, d[q]); }
-                        else if (q == K - 1) a = d[q];                                 // a new anti-diagonal: its first cell
-                        else if (q == K - 2) a = pk_max_h(d[q], dprev[q + 1]);          // ... its first two
-                        else a = pk_max3_h(a, d[q], dprev[q + 1]);
+                        if (!(q & 1)) {
+                            s16x2 &a = acc[(q + SLOT0) % K];
+                            a = pk_max3_h(a, d[q], dprev[q + 1]);
+                        }
                         e_cur = e_next;
                     }
-                    if (FEED == kFeedRow0) {
 #pragma unroll
-                        for (int q = 1; q < K; ++q) dprev[q] = d[q];
-                    }
-                    h_last = h;
+                    for (int q = 1; q < K; q += 2) dprev[q] = d[q];
                     f_last = f;
-                    // row 0's anti-diagonal is complete: out of the frame; the slot's floor moves on to c + K
-                    best = pk_max(best, acc[SLOT0 % K] - fl[SLOT0 % K]);
+                    // row 0's anti-diagonal is complete: the slot moves on to c + K
+                    acc[SLOT0 % K] = acc[SLOT0 % K] + kx_c;
                     fl[SLOT0 % K] = fl[SLOT0 % K] + kx_c;
                     code_ptr += 2;
                 };
-                for (int r = steps % K; r > 0; --r) {
-                    tilted_step(std::integral_constant<int, 0>{}, std::integral_constant<int, kFeedAll>{});
-                    const s16x2 moved = fl[0];
-#pragma unroll
-                    for (int q = 0; q + 1 < K; ++q) {
-                        fl[q] = fl[q + 1];
-                        acc[q] = acc[q + 1];
+                unrolled_steps(std::make_integer_sequence<int, K>{}, [&](auto slot_tag) __attribute__((always_inline)) {
+                    if constexpr (decltype(slot_tag)::value > 0) {
+                        if (decltype(slot_tag)::value >= s0) tilted_step(slot_tag);
                     }
-                    fl[K - 1] = acc[K - 1] = moved;
-                }
+                });
                 for (int trips = steps / K; trips > 0; --trips)
-                    unrolled_steps(std::make_integer_sequence<int, K>{}, [&](auto slot_tag) __attribute__((always_inline)) {
-                        constexpr int s = decltype(slot_tag)::value;
-                        tilted_step(slot_tag, std::integral_constant<int, (s & 1) ? kFeedPairs : kFeedRow0>{});
-                    });
+                    unrolled_steps(std::make_integer_sequence<int, K>{}, [&](auto slot_tag) __attribute__((always_inline)) { tilted_step(slot_tag); });
+                // the odd rows of the last step, then out of the frame: after a whole trip slot q stands for c = q + steps
+                best = pk(0);
 #pragma unroll
-                for (int q = 0; q < K; ++q) best = pk_max(best, acc[q] - fl[q]);        // the anti-diagonals still open
+                for (int q = 0; q < K; q += 2) acc[q] = pk_max_h(acc[q], dprev[q + 1]);
+#pragma unroll
+                for (int q = 0; q < K; ++q) best = pk_max(best, acc[q] - fl[q]);
             }
             if (biased && !tilted) {
                 const s16x2 bias_c = pk((short)args.sym_max3_bias);
