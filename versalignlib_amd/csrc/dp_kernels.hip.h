@@ -1113,6 +1113,10 @@ score_kernel(const ScoreArgs args) {
                 // row 0 completes its anti-diagonal the slot moves on to c + K, floor and accumulator alike (+ K x: the same value
                 // read in the new frame), and the accumulator keeps collecting: it holds the largest cell so far plus B + x u of a
                 // cell of the sweep, which sym_affine_tilt_ok bounds.  The K accumulators leave the frame once, after the last step.
+                // THE CODE FETCHES are volatile: one LDS byte load each, waited for by the compiler as any other load.  In the
+                // K-step trip their offsets are adjacent constants, and plain loads get merged into wide, unaligned ones whose
+                // bytes come apart again on the VALU (18 instructions per trip at 16 x 10), which has no slot to spare; the LDS
+                // port has.  profiles/r21_sym_affine_bookkeeping.txt.
                 auto tilted_step = [&](auto slot_tag) __attribute__((always_inline)) {
                     constexpr int SLOT0 = decltype(slot_tag)::value;
                     s16x2 S[K], d[K];
@@ -1122,8 +1126,8 @@ score_kernel(const ScoreArgs args) {
                     merge_profile<K>(pa, pb, S);
                     lds_load_lane<K>(lane_base + ca_next * geo::kPairStride, pa);
                     lds_load_lane<K>(lane_base + cb_next * geo::kPairStride, pb);
-                    ca_next = code_ptr[4];
-                    cb_next = code_ptr[5];
+                    ca_next = ((volatile lds_cu8 *)code_ptr)[4];
+                    cb_next = ((volatile lds_cu8 *)code_ptr)[5];
                     s16x2 e_cur;
                     auto pass1 = [&](int q, s16x2 &e) __attribute__((always_inline)) {
                         d[q] = (q == 0 ? diag0 : Hl[q - 1]) + S[q];
