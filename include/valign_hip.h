@@ -561,6 +561,57 @@ int valign_hip_score_subopt_device(valign_hip_engine *e, int opt, long long n, c
 int valign_hip_score_subopt_host(valign_hip_engine *e, int opt, int n, const char *const *reads,
                                  const char *const *refs, int mask, valign_hip_subopt *subopt, int threads);
 
+/* ---- extension scores: anchored score, end cell and read-end score per pair, without a traceback ----
+ * Every call above is Smith-Waterman: a free start anywhere in the matrix.  A seed-and-extend mapper (BWA-MEM's ksw_extend,
+ * minimap2's extension stage) has an ANCHOR -- a seed that fixes where read and reference correspond -- and asks, from there:
+ * what is the best score of an alignment that starts exactly at the anchor and ends anywhere, and where does it end; and what is
+ * the best score if the read is consumed to its last base (end-to-end or clip?).  Extension scores answer both from one sweep.
+ * DEFINITION, for opt & 0xF == 0, per pair; the engine's scoring applies, with the usual class rule: `match` or `mismatch`
+ * between two ACGT bases of either case, 0 for any other pair of bytes, interior ones included.
+ *   anchor ...... the alignment starts before read[0] and ref[0]: THE CALLER PASSES THE SEQUENCE AFTER ITS SEED.  For a leftward
+ *                 extension the caller reverses both sequences.
+ *   trimmed lengths
+ *                 Rp is 1 + the position of the last ACGT byte (either case) of the read row, 0 if there is none; Fp the same
+ *                 for the reference row: the rule of the suboptimal scores and of ragged batching.
+ *   matrix ...... X(-1,-1) = 0.  The border column X(i,-1) is a gap of i + 1 read bases against nothing: (i + 1) * gap_ref with
+ *                 linear gaps, open_ref + i * ext_ref with affine gaps.  The border row X(-1,j) is the same in the other
+ *                 direction: (j + 1) * gap_read, or open_read + j * ext_read.  Inside, the library's linear or Gotoh recurrence
+ *                 with NO FLOOR AT ZERO: X(i,j) is the best score of any DIAG / UP / LEFT path from the origin to the cell,
+ *                 maximal gap runs priced open + (k - 1) * ext per direction.
+ *   score ....... max(0, max X(i,j)) over 0 <= i < Rp, 0 <= j < Fp.
+ *   read_end, ref_end
+ *                 (read_end - 1, ref_end - 1) is the row-major first cell that holds score (DefaultKernel.cpp:252-256); half-open,
+ *                 0-based ends.
+ *   empty ....... if score is 0, then score = read_end = ref_end = 0.
+ *   gscore ...... the maximum of X(Rp - 1, j) over the candidates -1 <= j < Fp; the border column counts as j = -1.  int32, may
+ *                 be negative.
+ *   gref_end .... gref_end - 1 is the smallest candidate column that holds gscore (0: the border column).
+ *   Rp = 0 ...... the record is five zeros.
+ * Columns at or beyond Fp are not candidates for gscore: padding scores 0 against anything, and a read longer than the trimmed
+ * reference would otherwise ride its tail down the padding for free.
+ * NOT BUILT: Z-drop or X-drop termination -- every cell is swept; an end bonus -- the caller compares gscore + bonus with score
+ * itself.  ragged_batching and half_float_cells are not read.
+ * REFUSED with a non-zero return, a message in valign_hip_last_error and "ran_extend": "none": opt & 0xF == 1;
+ * traceback_policy = 1; band_width > 0, WHATEVER band_placed says; score_width = 32, WHATEVER placed_wide says; a shape x
+ * scoring whose cells could leave int16 -- signed cells: min(R, F) * max(match, mismatch, 0) above 32000, or the all-gaps path
+ * to the far corner (R reference-direction steps and F read-direction steps at their worst price) plus the largest single addend
+ * below -32000; and the shapes placed scores send to the row strips (reads of more than 1024 rows, or no register geometry).
+ * opt & 0xF > 1 does nothing, as everywhere.
+ * "ran_extend" of valign_hip_describe is "rows" after a call that ran ("none" before any, or when it was refused).  The device
+ * call holds no scratch.  tests/extend_ref.py restates the definition in numpy.                                            */
+typedef struct {                     /* 20 bytes */
+    int32_t score, read_end, ref_end, gscore, gref_end;
+} valign_hip_extend;
+
+/* Device-resident: d_extend = n records.  Asynchronous on hip_stream, no host synchronisation: one launch, nothing but the
+ * records is written.                                                                                                        */
+int valign_hip_score_extend_device(valign_hip_engine *e, int opt, long long n, const void *d_reads,
+                                   const void *d_refs, void *d_extend, void *hip_stream);
+
+/* Host pointers in, records out: the chunk pipeline of valign_hip_score_placed_host, 20 bytes per pair on the way back.      */
+int valign_hip_score_extend_host(valign_hip_engine *e, int opt, int n, const char *const *reads,
+                                 const char *const *refs, valign_hip_extend *extend, int threads);
+
 /* Page-lock a host range and map it for the device (hipHostRegister behind a C symbol, so that an FFI caller needs no
  * HIP binding).  valign_hip_align_host into result buffers that lie inside a registered range -- or inside memory the
  * caller page-locked itself -- skips the library's pinned staging and its host-side copy: the device's copy engine

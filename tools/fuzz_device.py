@@ -8,7 +8,9 @@ unbanded placed scores run, and refused under every band; suboptimal scores (sco
 tests/subopt_ref.py wherever placed scores ran on the register sweep -- and `--kind subopt` draws nothing but cases for them: shapes up
 to 160 x 300 with a second, mutated copy of the read planted in the reference; `--kind span_cigar` draws nothing but cases for the
 spanned CIGARs (align_span_device / _host against tests/span_cigar_ref.py: random shapes up to 320 x 900 and one in eight on the row
-strips, scorings, extended, ops_stride, trace_checkpoints, pointer_scratch_cap_mb, placed_wide).  What tools/fuzz_parity.py does for the plugin ABI, for the entry points the tests of the device path
+strips, scorings, extended, ops_stride, trace_checkpoints, pointer_scratch_cap_mb, placed_wide); `--kind extend` draws nothing but
+cases for the extension scores (score_extend_device / _host against tests/extend_ref.py: random shapes up to 200 x 300, the four gap
+forms at several scales, the engine's own or a forced geometry, planted extensions, ragged tails and interior junk).  What tools/fuzz_parity.py does for the plugin ABI, for the entry points the tests of the device path
 use; a process that runs it for minutes also exercises the library's set-up and tear-down far more often than the suite.
 
     python -X faulthandler tools/fuzz_device.py --seconds 300 --seed 1
@@ -28,6 +30,7 @@ import torch                                                       # noqa: E402
 from oracle import cpu_ref                                          # noqa: E402
 from versalignlib_amd import hipkernel, synth                      # noqa: E402
 import band_nw_ref                                                 # noqa: E402
+import extend_ref                                                  # noqa: E402
 import placed_band_ref                                             # noqa: E402
 import placed_ref                                                  # noqa: E402
 import span_cigar_ref                                              # noqa: E402
@@ -311,6 +314,58 @@ def run_span_cigar(c):
         eng.close()
 
 
+EXTEND_GEOMETRIES = [(0, 0), (8, 8), (16, 10), (32, 10), (64, 8), (64, 16), (64, 32), (8, 4), (16, 12), (64, 24)]
+EXTEND_FORMS = [(-3, -3), (-2, -4), (-3, -3, -5, -1, -5, -1), (-3, -3, -6, -2, -4, -1)]
+
+
+def draw_extend(rng):
+    """--kind extend: a shape, a scoring inside the signed int16 bound (extend_choice, cell_rules.h: 500 gap steps at 60 stay above
+    -32000), a geometry that holds the read, and whether the host entry runs too"""
+    R, F = int(rng.integers(1, 201)), int(rng.integers(1, 301))
+    match = int(rng.choice([1, 2, 3, 14, 60]))
+    scale = {1: 1, 2: 1, 3: 1, 14: 4, 60: 10}[match]
+    form = EXTEND_FORMS[int(rng.integers(0, 4))]
+    fits = [gk for gk in EXTEND_GEOMETRIES if gk == (0, 0) or gk[0] * gk[1] >= R]
+    return dict(R=R, F=F, n=int(rng.integers(1, 200)), scoring=(match, -int(rng.integers(1, match + 2))) + tuple(g * scale for g in form),
+                affine=len(form) > 2, geometry=fits[int(rng.integers(0, len(fits)))], host=bool(rng.random() < 0.3), threads=int(rng.integers(1, 9)),
+                seed=int(rng.integers(0, 1 << 30)))
+
+
+def run_extend(c):
+    """one extension-score case: the device entry (and, for some, the host entry) against tests/extend_ref.py, all five fields"""
+    rng = np.random.default_rng(c["seed"])
+    R, F, n = c["R"], c["F"], c["n"]
+    bases = np.frombuffer(b"ACGT", np.uint8)
+    reads, refs = bases[rng.integers(0, 4, (n, R))], bases[rng.integers(0, 4, (n, F))]
+    for p in range(n):
+        if p % 3 < 2:                       # an extension from the anchor, a third of them behind extra reference bases
+            L, shift = int(rng.integers(1, min(R, F) + 1)), (int(rng.integers(0, 3)) if p % 3 == 1 else 0)
+            span = min(L, F - shift)
+            if span > 0:
+                refs[p, shift:shift + span] = reads[p, :span]
+        if rng.random() < 0.3:
+            reads[p, int(rng.integers(0, R + 1)):] = rng.choice([0, ord("N")])
+        if rng.random() < 0.3:
+            refs[p, int(rng.integers(0, F + 1)):] = rng.choice([0, ord("N")])
+        if rng.random() < 0.2:
+            refs[p, int(rng.integers(0, F))] = rng.choice([0, ord("N"), 0x80, 0xFF])
+    sc = hipkernel.Scoring.make(*c["scoring"])
+    exp = extend_ref.extend(reads, refs, sc, affine=c["affine"], chunk=64)
+    eng = hipkernel.Engine(R, F, sc, group_lanes=c["geometry"][0], rows_per_lane=c["geometry"][1])
+    try:
+        got = eng.score_extend_device(0, torch.from_numpy(reads).cuda(), torch.from_numpy(refs).cuda())
+        torch.cuda.synchronize()
+        if not np.array_equal(got.cpu().numpy().astype(np.int64), exp):
+            return "score_extend_device differs (%s)" % eng.describe(0, n)["ran_extend"]
+        if c["host"]:
+            h = eng.score_extend_host(0, reads, refs, threads=c["threads"])
+            if not np.array_equal(np.stack([h[k] for k in hipkernel.extend_dtype().names], axis=1).astype(np.int64), exp):
+                return "score_extend_host differs"
+        return None
+    finally:
+        eng.close()
+
+
 def soak_sequences(rng, a):
     """--kind sequence: the generator and the runner of tests/engine_sequences.py (what tests/test_gpu_engine_sequences.py runs
     on its committed seeds) on random seeds: ONE engine per sequence through key changes and calls, every call against its
@@ -342,7 +397,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--first", type=int, default=0)
     ap.add_argument("--verbose", action="store_true")
-    ap.add_argument("--kind", choices=["subopt", "sequence", "span_cigar"], default=None,
+    ap.add_argument("--kind", choices=["subopt", "sequence", "span_cigar", "extend"], default=None,
                     help="draw cases of this kind only (default: the mix); sequence: one engine through tests/engine_sequences.py's sequences")
     a = ap.parse_args()
     rng = np.random.default_rng(a.seed)
@@ -351,12 +406,12 @@ def main():
     t0 = time.time()
     i = done = 0
     while time.time() - t0 < a.seconds:
-        c = draw_span_cigar(rng) if a.kind == "span_cigar" else draw(rng, a.kind)
+        c = draw_span_cigar(rng) if a.kind == "span_cigar" else (draw_extend(rng) if a.kind == "extend" else draw(rng, a.kind))
         if i >= a.first:
             if a.verbose:
                 print("case %d: %r" % (i, c), flush=True)
             try:
-                err = run_span_cigar(c) if a.kind == "span_cigar" else run(c)
+                err = run_span_cigar(c) if a.kind == "span_cigar" else (run_extend(c) if a.kind == "extend" else run(c))
             except hipkernel.HipKernelError as e:
                 err = "library error: %s" % e
             done += 1

@@ -406,6 +406,54 @@ inline int subopt_block_waves(int wave_lds, int ring_bytes, int placed_waves, in
 }
 constexpr const char *kSuboptNoRing = "suboptimal scores: one wave's reference tables leave no room for its column ring in the LDS (a shorter reference, or a geometry of more lanes per group, has it)";
 
+// ---- extension scores (valign_hip_score_extend_*): the anchored score, its end cell and the read-end score, from one register
+// sweep with gap-priced borders and no floor at zero (extend_kernels.hip.h) ----
+// The cells are signed int16 and nothing clamps them from below, so the range is derived from the matrix itself:
+//   * no cell is above min(R, F) * max(match, mismatch, 0): a path takes at most min(R, F) diagonal steps, nothing else adds;
+//   * no cell of H is below the all-gaps path to the far corner -- R steps in the reference direction and F in the read
+//     direction, each at its worst price (the path "down the border column, then along the row" reaches every cell and costs
+//     at most that, since every gap score is <= 0);
+//   * a candidate of a maximum (E, F, a diagonal) lies at most the largest single addend below an H.
+// Both ends must stay within the +-32000 of int16_range_ok.
+inline long long extend_cell_top(const RuleInputs &in) {
+    return (long long)std::min(in.R, in.F) * std::max({in.sc.match, in.sc.mismatch, 0});
+}
+inline long long extend_cell_bottom(const RuleInputs &in) {
+    const Scoring &sc = in.sc;
+    const long long per_row = sc.affine ? std::min({sc.open_ref, sc.ext_ref, 0}) : std::min(sc.gap_ref, 0);
+    const long long per_col = sc.affine ? std::min({sc.open_read, sc.ext_read, 0}) : std::min(sc.gap_read, 0);
+    const long long addend = sc.affine ? std::min({sc.match, sc.mismatch, sc.open_read, sc.ext_read, sc.open_ref, sc.ext_ref, 0})
+                                       : std::min({sc.match, sc.mismatch, sc.gap_read, sc.gap_ref, 0});
+    return per_row * in.R + per_col * in.F + addend;
+}
+inline bool extend_int16_ok(const RuleInputs &in) { return extend_cell_top(in) <= 32000 && extend_cell_bottom(in) >= -32000; }
+
+// An extension call runs on the register sweep's rows track or not at all: refused for the NW variant's mode bit, for
+// traceback_policy = 1, under a band whatever band_placed says, for score_width = 32 whatever placed_wide says, where the cells
+// could leave int16 (above), and for the shapes placed scores would send to the row strips.  Otherwise Rows.
+// `G x K`: the register geometry the call would run on -- every full geometry carries the four gap forms, so the choice
+// does not depend on it today.
+inline PlacedChoice extend_choice(const RuleInputs &in, int alg, const PlacedFacts &f, int G, int K) {
+    PlacedChoice c;
+    (void)G;
+    (void)K;
+    if (alg != kAlgSW)
+        c.reason = "extension scores are defined for opt & 0xF == 0 only (the NW variant's free reference start is another matrix)";
+    else if (in.sse_policy)
+        c.reason = "extension scores are not built for traceback_policy = 1 (SSE/AVX tie-breaks)";
+    else if (f.band_width > 0)
+        c.reason = "extension scores are not built for band_width > 0";
+    else if (f.score_width == 32)
+        c.reason = "extension scores are not built for score_width = 32 (int32 cells)";
+    else if (!extend_int16_ok(in))
+        c.reason = "extension scores run on signed int16 cells: shape x scoring can leave their range";
+    else if (f.long_plan || (!f.forced && in.R > kPlacedStripRows))
+        c.reason = "extension scores run on the register sweep only: reads of more than 1024 rows and shapes without a register geometry are refused";
+    else
+        c.route = PlacedRoute::Rows;
+    return c;
+}
+
 // ---- band_nw = 1: the NW variant under the block band (include/valign_hip.h) ----
 // Consecutive blocks' windows connect -- every in-band cell has a present candidate -- once 2 * (band_width / 2) + 1 columns
 // cover the most a window start advances per row, ceil(F / R).  Narrower bands are refused.

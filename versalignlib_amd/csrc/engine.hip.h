@@ -18,6 +18,8 @@
 //                         reversed prefixes (span_kernels.hip.h); its host call is record_pipeline too
 //   engine_subopt.hip ... suboptimal Smith-Waterman scores: the placed sweep's suboptimal form, which also leaves the column
 //                         maxima in a scratch, and subopt_records_kernel (subopt_kernels.hip.h); record_pipeline again
+//   engine_extend.hip ... extension scores: the anchored score, its end cell and the read-end score from one sweep with gap-priced
+//                         borders and no floor (extend_kernels.hip.h); record_pipeline again
 //   engine_cigar.hip .... the compact result format: records + CIGAR ops encoded on the device behind the walks (cigar_kernels.hip.h)
 //   engine_span_cigar.hip spanned CIGARs: the alignment of the span from the span's window -- the forward placed sweep, the
 //                         reversal, the child engine's ALIGNMENT of the reversed prefixes and the backward encoder
@@ -83,6 +85,7 @@ struct Geometry {
     const void *fill[2][kFillKernels];      // alignment fill kernels [alg][FillKernel]; nullptr: not compiled for this geometry
     const void *(*placed)(int track, int gaps);      // placed-score kernels (placed_kernels.hip.h); returns nullptr where none is compiled
     const void *(*subopt)(int track, int gaps);      // suboptimal-score kernels: the full geometries', nullptr elsewhere
+    const void *(*extend)(int gaps);                 // extension-score kernels (extend_kernels.hip.h): the full geometries', nullptr elsewhere
 };
 
 template <int G, int K>
@@ -110,14 +113,14 @@ constexpr void set_fast_kernels(Geometry &g) {
 
 template <int G, int K>
 constexpr Geometry fast_geometry() {
-    Geometry g{G, K, false, &wave_lds<G, K>, {}, {}, &placed_kernel<G, K, false>, &subopt_kernel<G, K, false>};
+    Geometry g{G, K, false, &wave_lds<G, K>, {}, {}, &placed_kernel<G, K, false>, &subopt_kernel<G, K, false>, &extend_kernel<G, K, false>};
     set_fast_kernels<G, K>(g);
     return g;
 }
 
 template <int G, int K>
 constexpr Geometry full_geometry() {
-    Geometry g{G, K, true, &wave_lds<G, K>, {}, {}, &placed_kernel<G, K, true>, &subopt_kernel<G, K, true>};
+    Geometry g{G, K, true, &wave_lds<G, K>, {}, {}, &placed_kernel<G, K, true>, &subopt_kernel<G, K, true>, &extend_kernel<G, K, true>};
     set_fast_kernels<G, K>(g);
     g.fill[0][kFillLinear] = (const void *)&align_fill_kernel<G, K, kAlgSW, false>;
     g.fill[0][kFillLinearSym] = (const void *)&align_fill_kernel<G, K, kAlgSW, true>;
@@ -521,6 +524,15 @@ public:
     void score_subopt_host(int opt, int n, const char *const *reads, const char *const *refs, int mask, SuboptRec *subopt, int threads);
     const char *ran_subopt() const { return ran_subopt_; }
 
+    // ---- extension scores (valign_hip.h: valign_hip_extend; engine_extend.hip) ----
+    // The best score of an alignment anchored before read[0] / ref[0], the cell it ends in, and the best score that consumes the
+    // read to its last base: one register sweep with gap-priced borders and no floor (extend_kernels.hip.h), no scratch.
+    // extend_choice (cell_rules.h) decides what is refused.  Device-resident: asynchronous on `stream`, writes d_extend only.
+    // Host pointers: record_pipeline, 20 bytes per pair.
+    void score_extend_device(int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, ExtendRec *d_extend, hipStream_t stream);
+    void score_extend_host(int opt, int n, const char *const *reads, const char *const *refs, ExtendRec *extend, int threads);
+    const char *ran_extend() const { return ran_extend_; }
+
     // host-side phases of the last score_host / align_host call
     std::string host_phases() const;
 
@@ -763,6 +775,10 @@ private:
     void subopt_chunk(int c, const LaunchPlan &plan, int track, int gaps, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int mask,
                       SuboptRec *d_subopt, hipStream_t stream);
 
+    // ---- extension scores (engine_extend.hip) ----
+    // refusals (thrown), then the plan: the base plan where its geometry carries the kernel, else the next full geometry
+    const LaunchPlan &extend_plan_for(int alg, int &gaps);
+
     // ---- length-sorted batching (score_host, Smith-Waterman) ----
 
     static double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
@@ -910,6 +926,7 @@ private:
     const char *ran_subopt_ = "none";                    // what the last suboptimal call ran: key / rows (describe)
     int subopt_ring_cols_ = 0;                           // ... and the columns of a lane group's ring in its sweep
     size_t subopt_scratch_bytes_ = (size_t)dbg_.value("subopt_scratch_bytes", 256ll << 20);      // column maxima of one chunk
+    const char *ran_extend_ = "none";                    // what the last extension call ran: rows (describe)
     const char *ran_result_format_ = "rows";             // of the last alignment call: rows / cigar (describe)
     long long cigar_d2h_bytes_ = 0;                      // what the last align_cigar_host call copied back
     const CigarSink *cigar_ = nullptr;

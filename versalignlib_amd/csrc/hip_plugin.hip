@@ -722,6 +722,28 @@ VALIGN_EXPORT int valign_hip_score_subopt_host(valign_hip_engine *e, int opt, in
     return flat_guard([&] { e->impl->score_subopt_host(opt, n, reads, refs, mask, (valign::SuboptRec *)subopt, threads); });
 }
 
+static_assert(sizeof(valign_hip_extend) == sizeof(valign::ExtendRec) && sizeof(valign_hip_extend) == 20, "valign_hip_extend is the kernels' record");
+
+VALIGN_EXPORT int valign_hip_score_extend_device(valign_hip_engine *e, int opt, long long n, const void *d_reads, const void *d_refs,
+                                                 void *d_extend, void *hip_stream) {
+    if (!e) {
+        g_last_error = "null engine";
+        return 1;
+    }
+    return flat_guard([&] {
+        e->impl->score_extend_device(opt, n, (const uint8_t *)d_reads, (const uint8_t *)d_refs, (valign::ExtendRec *)d_extend, (hipStream_t)hip_stream);
+    });
+}
+
+VALIGN_EXPORT int valign_hip_score_extend_host(valign_hip_engine *e, int opt, int n, const char *const *reads, const char *const *refs,
+                                               valign_hip_extend *extend, int threads) {
+    if (!e) {
+        g_last_error = "null engine";
+        return 1;
+    }
+    return flat_guard([&] { e->impl->score_extend_host(opt, n, reads, refs, (valign::ExtendRec *)extend, threads); });
+}
+
 VALIGN_EXPORT int valign_hip_describe(valign_hip_engine *e, int opt, long long n, char *buf, int cap) {
     if (!e || !buf || cap <= 0) return 1;
     const std::string s = e->impl->describe(opt, n);

@@ -22,6 +22,7 @@
 #include "dp_kernels.hip.h"
 #include "trace_kernels.hip.h"
 #include "placed_kernels.hip.h"
+#include "extend_kernels.hip.h"
 
 // X(G, K): geometries with every kernel;  Y(G, K): geometries with the fast set only.  Parts are balanced by rows per
 // lane (compile time grows with K).
@@ -82,3 +83,7 @@
 // The suboptimal-score kernels (placed_kernels.hip.h: subopt_kernel<G, K, FULL>, the SUB form of score_placed_kernel): 44 instances,
 // all on the six full geometries
 #define VALIGN_SUBOPT_KERNELS(PREFIX, G, K, FULL) PREFIX const void *subopt_kernel<G, K, FULL>(int, int);
+
+// The extension-score kernels (extend_kernels.hip.h: extend_kernel<G, K, FULL>, score_extend_kernel): the four gap forms on the six
+// full geometries, 24 instances
+#define VALIGN_EXTEND_KERNELS(PREFIX, G, K, FULL) PREFIX const void *extend_kernel<G, K, FULL>(int);

@@ -112,6 +112,8 @@ def lib():
         L.valign_hip_score_span_host.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int]
         L.valign_hip_score_subopt_device.argtypes = [vp, ctypes.c_int, ctypes.c_longlong, vp, vp, ctypes.c_int, vp, vp]
         L.valign_hip_score_subopt_host.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int]
+        L.valign_hip_score_extend_device.argtypes = [vp, ctypes.c_int, ctypes.c_longlong, vp, vp, vp, vp]
+        L.valign_hip_score_extend_host.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int]
         L.valign_hip_describe.argtypes = [vp, ctypes.c_int, ctypes.c_longlong, ctypes.c_char_p,
                                           ctypes.c_int]
         L.valign_hip_last_error.restype = ctypes.c_char_p
@@ -122,7 +124,7 @@ def lib():
 EXPORTED_SYMBOLS = (
     "spawn_alignment_kernel", "set_parameters", "set_logger", "delete_alignment_kernel",
     "valign_hip_device_count", "valign_hip_shard_range", "valign_hip_engine_create", "valign_hip_engine_destroy",
-    "valign_hip_set_traceback_policy", "valign_hip_set_pointer_scratch_cap_mb", "valign_hip_set_host_packing", "valign_hip_set_half_float_cells", "valign_hip_host_register", "valign_hip_host_unregister", "valign_hip_set_band_width", "valign_hip_set_band_alignments", "valign_hip_set_band_nw", "valign_hip_set_band_placed", "valign_hip_set_placed_wide", "valign_hip_set_trace_checkpoints", "valign_hip_set_score_width", "valign_hip_set_ragged_batching", "valign_hip_score_device", "valign_hip_align_device", "valign_hip_score_host", "valign_hip_align_host", "valign_hip_align_cigar_device", "valign_hip_align_cigar_host", "valign_hip_score_placed_device", "valign_hip_score_placed_host", "valign_hip_score_span_device", "valign_hip_score_span_host", "valign_hip_align_span_device", "valign_hip_align_span_host", "valign_hip_score_subopt_device", "valign_hip_score_subopt_host", "valign_hip_describe",
+    "valign_hip_set_traceback_policy", "valign_hip_set_pointer_scratch_cap_mb", "valign_hip_set_host_packing", "valign_hip_set_half_float_cells", "valign_hip_host_register", "valign_hip_host_unregister", "valign_hip_set_band_width", "valign_hip_set_band_alignments", "valign_hip_set_band_nw", "valign_hip_set_band_placed", "valign_hip_set_placed_wide", "valign_hip_set_trace_checkpoints", "valign_hip_set_score_width", "valign_hip_set_ragged_batching", "valign_hip_score_device", "valign_hip_align_device", "valign_hip_score_host", "valign_hip_align_host", "valign_hip_align_cigar_device", "valign_hip_align_cigar_host", "valign_hip_score_placed_device", "valign_hip_score_placed_host", "valign_hip_score_span_device", "valign_hip_score_span_host", "valign_hip_align_span_device", "valign_hip_align_span_host", "valign_hip_score_subopt_device", "valign_hip_score_subopt_host", "valign_hip_score_extend_device", "valign_hip_score_extend_host", "valign_hip_describe",
     "valign_hip_last_error",
 )
 
@@ -144,6 +146,13 @@ def subopt_dtype():
     """numpy structured dtype of valign_hip_subopt (20 bytes): the placed record, the runner-up score and where it ends."""
     import numpy as np
     return np.dtype([("score", "<i4"), ("read_end", "<i4"), ("ref_end", "<i4"), ("score2", "<i4"), ("ref_end2", "<i4")])
+
+
+def extend_dtype():
+    """numpy structured dtype of valign_hip_extend (20 bytes): the anchored score and its half-open end cell, the read-end score
+    and the half-open reference end that holds it."""
+    import numpy as np
+    return np.dtype([("score", "<i4"), ("read_end", "<i4"), ("ref_end", "<i4"), ("gscore", "<i4"), ("gref_end", "<i4")])
 
 
 def span_dtype():
@@ -535,6 +544,41 @@ class Engine:
         if rc != 0:
             raise HipKernelError(_err())
         return subopt
+
+    def score_extend_device(self, opt, reads, refs, out=None, stream=None):
+        """Extension scores: -> int32 CUDA [n, 5] (score, read_end, ref_end, gscore, gref_end --
+        `out.cpu().numpy().view(extend_dtype())[:, 0]` names them): the best score of an alignment that starts before read[0]
+        and ref[0] with the cell it ends in, and the best score that consumes the read to its last ACGT base with the smallest
+        reference end that holds it (include/valign_hip.h has the definition).  Asynchronous on the current stream (or
+        `stream`); `out` of an earlier call is written in place.  Refused (HipKernelError) for opt & 0xF == 1,
+        traceback_policy = 1, any band, score_width = 32, cells that could leave int16 and on the row strips."""
+        import torch
+        assert reads.is_cuda and refs.is_cuda and reads.dtype == torch.uint8 and refs.dtype == torch.uint8
+        assert reads.is_contiguous() and refs.is_contiguous()
+        n = reads.shape[0]
+        assert tuple(reads.shape) == (n, self.read_length) and tuple(refs.shape) == (n, self.ref_length)
+        if out is None:
+            out = torch.empty((n, 5), dtype=torch.int32, device=reads.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == torch.int32 and tuple(out.shape) == (n, 5)
+        st = stream if stream is not None else torch.cuda.current_stream(reads.device)
+        rc = lib().valign_hip_score_extend_device(self._h, int(opt), n, reads.data_ptr(), refs.data_ptr(), out.data_ptr(), st.cuda_stream)
+        if rc != 0:
+            raise HipKernelError(_err())
+        return out
+
+    def score_extend_host(self, opt, reads, refs, threads=1):
+        """Host-pointer path of the extension scores: numpy uint8 [n, R] / [n, F] -> structured array [n] (extend_dtype())."""
+        import numpy as np
+        n = reads.shape[0]
+        assert reads.dtype == np.uint8 and refs.dtype == np.uint8 and reads.flags.c_contiguous and refs.flags.c_contiguous
+        assert tuple(reads.shape) == (n, self.read_length) and tuple(refs.shape) == (n, self.ref_length)
+        rp = (reads.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(self.read_length)).astype(np.uint64)
+        fp = (refs.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(self.ref_length)).astype(np.uint64)
+        extend = np.zeros(n, dtype=extend_dtype())
+        rc = lib().valign_hip_score_extend_host(self._h, int(opt), n, rp.ctypes.data, fp.ctypes.data, extend.ctypes.data, int(threads))
+        if rc != 0:
+            raise HipKernelError(_err())
+        return extend
 
     def describe(self, opt=0, n=0):
         buf = ctypes.create_string_buffer(4096)
