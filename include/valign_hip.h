@@ -638,6 +638,11 @@ int valign_hip_set_half_float_cells(valign_hip_engine *e, int mode);
  * "ran_score_geometry" / "ran_align_geometry" name the compiled geometry, "GxK" (group lanes x rows per lane), whose kernel
  * the last register-sweep score launch / the last register-path fill launch ran -- the engine's own, its latency plan's or the
  * full geometry a fallback kernel moved the call to -- and are "none" before any and for every other route;
+ * "ran_placed_geometry" / "ran_subopt_geometry" / "ran_extend_geometry" name, in the same way, the geometry whose kernel the last
+ * placed-score / suboptimal-score / extension-score register sweep ran -- the engine's own or, where that one carries no kernel
+ * for the track and gap form, the full geometry the call was moved to (the key / rows rule is asked again for its rows per lane)
+ * -- and are "none" before any such call, after a refused one, and for the strip, chain and wide routes; the forward sweep of a
+ * spanned call sets "ran_placed_geometry" like any placed call (the reverse sweep's child engine is not reported);
  * "ran_score_sym_affine" is present only where the last score call launched the int16 symmetric affine Smith-Waterman kernel,
  * and names the form of its sweep that ran: "max3" (biased cells, three-operand maxima) or "sources" (gap sources);
  * "ran_score_sym_affine_frame", present beside it, names the frame of that sweep: "tilted" (the biased form with free gap

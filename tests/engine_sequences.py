@@ -249,7 +249,8 @@ PLAN_KEYS = ("long_mode", "group_lanes", "rows_per_lane", "score_cells", "band_b
 RAN_KEYS = {"score": ("ran_score_cells", "ran_score_geometry", "ran_score_sym_affine"),
             "rows": ("ran_align_fill", "ran_align_geometry", "ran_result_format"),
             "cigar": ("ran_align_fill", "ran_align_geometry", "ran_result_format"),
-            "placed": ("ran_placed",), "span": ("ran_span", "ran_placed"), "subopt": ("ran_subopt",)}
+            "placed": ("ran_placed", "ran_placed_geometry"), "span": ("ran_span", "ran_placed", "ran_placed_geometry"),
+            "subopt": ("ran_subopt", "ran_subopt_geometry")}
 SENTINEL = -7
 
 

@@ -1,6 +1,7 @@
-"""The table behind tests/test_gpu_instance_matrix.py: every (G, K) register geometry libHIPKernel.so is compiled for, the
-kernel instances each one carries (kernel_instances.hip.h), and the shapes, batch and scorings that reach them through
-the public API.  No GPU here: tests/test_instance_matrix_table.py checks this table against the header."""
+"""The table behind tests/test_gpu_instance_matrix.py and tests/test_gpu_placed_matrix.py: every (G, K) register geometry
+libHIPKernel.so is compiled for, the kernel instances each one carries (kernel_instances.hip.h; placed_kernels.hip.h and
+extend_kernels.hip.h for the placed family), and the shapes, batch and scorings that reach them through the public API.  No GPU
+here: tests/test_instance_matrix_table.py checks this table against the headers."""
 
 # (group lanes, rows per lane) -> full: the geometry carries the fallback fill kernels too
 GEOMETRIES = {
@@ -31,6 +32,48 @@ NEEDS_NO_TAG = {(64, 32)}
 
 def carried_fills(G, K):
     return FAST_FILLS | (FALLBACK_FILLS if GEOMETRIES[(G, K)] else frozenset())
+
+
+# ---- the placed family: score_placed_kernel<G, K, GAPS, TRACK[, SUB]> and score_extend_kernel<G, K, GAPS>, looked up by
+# placed_kernel / subopt_kernel (placed_kernels.hip.h) and extend_kernel (extend_kernels.hip.h); walked on the GPU by
+# tests/test_gpu_placed_matrix.py.  An instance is (track, form): track as describe()'s ran_placed names it ----
+PLACED_FORMS = ("Linear", "Sym", "Affine", "AffineSym")
+PLACED_SYM_FORMS = ("Sym", "AffineSym")
+PLACED_KEY_MAX_K = 16           # kPlacedKeyMaxK (cell_rules.h): the lane key exists for up to 16 rows per lane
+
+
+def placed_key_bits(K):
+    """placed_key_bits (cell_rules.h): the bits of the row below the value in the lane key"""
+    return 2 if K <= 4 else (3 if K <= 8 else 4)
+
+
+def carried_placed(G, K):
+    """The key track with the symmetric forms wherever the key exists, with all four on the full geometries; the rows track with
+    all four on the full geometries and on 64 x 24."""
+    full = GEOMETRIES[(G, K)]
+    out = set()
+    if K <= PLACED_KEY_MAX_K:
+        out |= {("key", f) for f in (PLACED_FORMS if full else PLACED_SYM_FORMS)}
+    if full or (G, K) == (64, 24):
+        out |= {("rows", f) for f in PLACED_FORMS}
+    return frozenset(out)
+
+
+def carried_subopt(G, K):
+    """The suboptimal form of the placed sweep: the full geometries only, the key track where the key exists."""
+    if not GEOMETRIES[(G, K)]:
+        return frozenset()
+    return frozenset((t, f) for t in (("key", "rows") if K <= PLACED_KEY_MAX_K else ("rows",)) for f in PLACED_FORMS)
+
+
+def carried_extend(G, K):
+    """Extension scores: the rows track's sweep, on the full geometries only."""
+    return frozenset(("rows", f) for f in PLACED_FORMS) if GEOMETRIES[(G, K)] else frozenset()
+
+
+# Placed instances the matrix cannot select at its shapes, as {(G, K): {(track, form): reason}}: none -- min(R, F) <= 135 there,
+# so match 2 is inside the key's range at every K <= 16, and a match beyond it stays inside int16.
+PLACED_UNSELECTABLE = {}
 
 
 def shapes(G, K):

@@ -88,6 +88,7 @@ def test_every_instance(G, K, shape):
         eng.close()
         _check(got, exp, (G, K, R, F, form))
         assert d["ran_extend"] == "rows", (G, K, R, F, form, d["ran_extend"])
+        assert d["ran_extend_geometry"] == "%dx%d" % (G, K), (G, K, R, F, form, d["ran_extend_geometry"])
     assert (exp[:, 0] > 0).any() and (exp[:, 3] < 0).any()
 
 

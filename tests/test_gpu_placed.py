@@ -71,22 +71,32 @@ def test_register_geometries(R, F):
             _check(got, exp, (R, F, form, G, K))
             k_ran = K or d["rows_per_lane"]
             assert d["ran_placed"] == _predict(R, F, 2, k_ran, bool(G)), (R, F, form, G, K, d["ran_placed"])
+            if G:               # a full geometry carries every placed kernel: the call ran on the forced one
+                assert d["ran_placed_geometry"] == "%dx%d" % (G, K), (R, F, form, G, K, d["ran_placed_geometry"])
 
 
-def test_rows_form_on_64x24_and_small_8x4():
+def test_rows_form_on_64x24_and_forced_8x4_symmetric_there_asymmetric_replanned():
+    """64 x 24 carries the rows track with all four forms.  8 x 4 carries the key track with the symmetric forms only: forced there,
+    the calls with gap_read != gap_ref and with four affine scores are moved to a full geometry, and say so."""
     for form in FORMS:
         reads, refs, exp = _case(1000, 200, form, 5)
         eng = hipkernel.Engine(1000, 200, _scoring(form), group_lanes=64, rows_per_lane=24)
         got = _run(eng, reads, refs)
-        assert eng.describe(0, 64)["ran_placed"] == "rows"
+        d = eng.describe(0, 64)
+        assert d["ran_placed"] == "rows" and d["ran_placed_geometry"] == "64x24", (form, d["ran_placed"], d["ran_placed_geometry"])
         eng.close()
         _check(got, exp, ("64x24", form))
         reads, refs, exp = _case(12, 20, form, 6)
         eng = hipkernel.Engine(12, 20, _scoring(form), group_lanes=8, rows_per_lane=4)
         got = _run(eng, reads, refs)
-        assert eng.describe(0, 64)["ran_placed"] == "key"
+        d = eng.describe(0, 64)
+        assert d["ran_placed"] == "key"
+        if form in ("sym", "affsym"):
+            assert d["ran_placed_geometry"] == "8x4", (form, d["ran_placed_geometry"])
+        else:
+            assert d["ran_placed_geometry"] != "8x4" and tuple(int(v) for v in d["ran_placed_geometry"].split("x")) in FULL, (form, d["ran_placed_geometry"])
         eng.close()
-        _check(got, exp, ("8x4", form))
+        _check(got, exp, ("forced 8x4, ran on " + d["ran_placed_geometry"], form))
 
 
 # ---- 2. ties, built deliberately (forced 16 x 10 at 150 x 200: lane = (row + 10) // 10) ----

@@ -71,6 +71,7 @@ def test_shapes_forms_geometries(R, F):
             assert d["ran_placed"] == fwd and rev in ("key", "rows"), d["ran_span"]
             if G:               # (forced: both sweeps run on G x K; unforced, each engine picks the geometry of its own shape)
                 assert d["ran_span"] == "%s/%s" % (_route(R, F, 2, K, True), _route(R, Fr, 2, K, True)), (R, F, form, d["ran_span"])
+                assert d["ran_placed_geometry"] == "%dx%d" % (G, K), (R, F, form, d["ran_placed_geometry"])       # (the forward sweep's; a full geometry carries every form)
     assert sc_.span_ref_length(20, 120, sc_.scoring("sym")) == 33 and sc_.span_ref_length(150, 500, sc_.scoring("sym")) == 249
 
 
@@ -84,6 +85,7 @@ def test_rows_route_on_64x24():
         eng.close()
         _check(got, exp, ("64x24", form))
         assert d["ran_span"] == "rows/rows" and d["span_ref_length"] == 200
+        assert d["ran_placed_geometry"] == "64x24", d["ran_placed_geometry"]
 
 
 @pytest.mark.parametrize("form", ["sym", "aff"])

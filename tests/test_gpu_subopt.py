@@ -82,6 +82,7 @@ def test_every_instance(G, K, shape):
             d = eng.describe(0, n)
             eng.close()
             assert d["ran_subopt"] == track and d["subopt_ring_cols"] == 4 * G, (G, K, R, F, track, form, d["ran_subopt"])
+            assert d["ran_subopt_geometry"] == "%dx%d" % (G, K), (G, K, R, F, track, form, d["ran_subopt_geometry"])
             ran.add((track, form))
     assert len(ran) == (8 if K <= 16 else 4)
 

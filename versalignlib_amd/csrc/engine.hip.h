@@ -914,6 +914,9 @@ private:
     // ... and the (G, K) geometry whose table the kernel pointer was taken from: of the last register-sweep score launch and
     // of the last AlignRoute::Register fill launch (null -- "none" -- before any, and for every other route)
     const Geometry *ran_score_geo_ = nullptr, *ran_align_geo_ = nullptr;
+    // ... and likewise of the last placed, suboptimal and extension register sweep (describe: ran_placed_geometry,
+    // ran_subopt_geometry, ran_extend_geometry): the forced or planned geometry, or the full one *_plan_for moved the call to
+    const Geometry *ran_placed_geo_ = nullptr, *ran_subopt_geo_ = nullptr, *ran_extend_geo_ = nullptr;
     // ... and the form of the last score_kernel<G, K, kAlgSW, kGapAffineSym> launch of the last score call: "max3" / "sources"
     // (describe: ran_score_sym_affine; null -- the key is absent -- where the call launched no such kernel)
     const char *ran_score_sym_affine_ = nullptr;

@@ -102,7 +102,7 @@ std::string Engine::describe(int opt, long long n) const {
     const long long ppb = (long long)plan_.pairs_per_wave * plan_.waves_per_block;
     int band_rows = 0, band_align = 0;
     band_block_shape(band_rows, band_align);
-    char buf[3584];
+    char buf[4096];
     snprintf(buf, sizeof buf,
              "{\"arch\": \"%s\", \"device\": %d, \"alg\": %d, \"affine\": %d, \"group_lanes\": %d, "
              "\"rows_per_lane\": %d, \"padded_rows\": %d, \"pairs_per_wave\": %d, \"waves_per_block\": %d, "
@@ -115,7 +115,8 @@ std::string Engine::describe(int opt, long long n) const {
              "\"ran_span\": \"%s\", \"span_ref_length\": %lld, \"span_scratch_bytes\": %lld, "
              "\"ran_span_cigar\": \"%s\", \"span_cigar_scratch_bytes\": %lld, "
              "\"ran_subopt\": \"%s\", \"subopt_scratch_bytes\": %lld, \"subopt_ring_cols\": %d, \"ran_extend\": \"%s\", "
-             "\"ran_score_geometry\": \"%s\", \"ran_align_geometry\": \"%s\"}",
+             "\"ran_score_geometry\": \"%s\", \"ran_align_geometry\": \"%s\", "
+             "\"ran_placed_geometry\": \"%s\", \"ran_subopt_geometry\": \"%s\", \"ran_extend_geometry\": \"%s\"}",
              arch_.c_str(), device_, opt & 0xF, sc_.affine ? 1 : 0, plan_.geo->G, plan_.geo->K,
              plan_.geo->G * plan_.geo->K, plan_.pairs_per_wave, plan_.waves_per_block, plan_.lds.total,
              plan_.lds.total * plan_.waves_per_block, F_ + plan_.geo->G - 1, n > 0 ? (n + ppb - 1) / ppb : 0,
@@ -130,7 +131,8 @@ std::string Engine::describe(int opt, long long n) const {
              ran_span_.c_str(), span_ref_length(rule_inputs()), (long long)span_[kSlots].bytes(),
              ran_span_cigar_.c_str(), (long long)(span_cigar_[0].bytes() + span_cigar_[1].bytes()),
              ran_subopt_, (long long)subopt_[kSlots].bytes(), subopt_ring_cols_, ran_extend_,
-             ran_geometry(ran_score_geo_).c_str(), ran_geometry(ran_align_geo_).c_str());
+             ran_geometry(ran_score_geo_).c_str(), ran_geometry(ran_align_geo_).c_str(),
+             ran_geometry(ran_placed_geo_).c_str(), ran_geometry(ran_subopt_geo_).c_str(), ran_geometry(ran_extend_geo_).c_str());
     std::string out(buf);
     if (ran_score_sym_affine_)          // only where the last score call ran the int16 symmetric affine SW kernel
         out.insert(out.size() - 1, std::string(", \"ran_score_sym_affine\": \"") + ran_score_sym_affine_ + "\", \"ran_score_sym_affine_frame\": \"" +

@@ -27,6 +27,7 @@ void Engine::score_extend_device(int opt, long long n, const uint8_t *d_reads, c
     const int alg = opt & 0xF;
     if (alg > 1 || n <= 0) return;          // reference: unsupported mode is a silent no-op
     ran_extend_ = "none";
+    ran_extend_geo_ = nullptr;
     int gaps = 0;
     const LaunchPlan &plan = extend_plan_for(alg, gaps);
     hip_check(hipSetDevice(device_), "hipSetDevice");
@@ -40,6 +41,7 @@ void Engine::score_extend_device(int opt, long long n, const uint8_t *d_reads, c
     put_lds(a, plan.lds);
     put_scoring(a);
     const void *fn = plan.geo->extend(gaps);
+    ran_extend_geo_ = plan.geo;
     const long long ppb = (long long)plan.pairs_per_wave * plan.waves_per_block;
     const long long blocks = (n + ppb - 1) / ppb;
     if (blocks > 0x7FFFFFFFll) throw std::runtime_error("batch too large for one launch");
@@ -57,6 +59,7 @@ void Engine::score_extend_host(int opt, int n, const char *const *reads, const c
     if (alg > 1 || n <= 0) return;
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ran_extend_ = "none";
+    ran_extend_geo_ = nullptr;
     int gaps = 0;
     (void)extend_plan_for(alg, gaps);          // (refusals leave here, before anything is staged)
     record_pipeline(n, reads, refs, extend, RecordKind{sizeof(ExtendRec), "extension records", "D2H extension records"}, host_chunk_pairs(false, n), false, threads,

@@ -39,6 +39,7 @@ void Engine::score_placed_device(int opt, long long n, const uint8_t *d_reads, c
     const int alg = opt & 0xF;
     if (alg > 1 || n <= 0) return;          // reference: unsupported mode is a silent no-op
     ran_placed_ = ran_placed_name(PlacedRoute::Refused);
+    ran_placed_geo_ = nullptr;
     PlacedChoice choice;
     int gaps = 0;
     const LaunchPlan &plan = placed_plan_for(alg, choice, gaps);
@@ -60,6 +61,7 @@ void Engine::score_placed_device(int opt, long long n, const uint8_t *d_reads, c
         put_lds(a, plan.lds);
         put_scoring(a);
         const void *fn = plan.geo->placed(choice.route == PlacedRoute::Key ? kPlacedKey : kPlacedRows, gaps);
+        ran_placed_geo_ = plan.geo;
         const long long ppb = (long long)plan.pairs_per_wave * plan.waves_per_block;
         const long long blocks = (n + ppb - 1) / ppb;
         if (blocks > 0x7FFFFFFFll) throw std::runtime_error("batch too large for one launch");
@@ -125,6 +127,7 @@ void Engine::score_placed_host(int opt, int n, const char *const *reads, const c
     if (alg > 1 || n <= 0) return;
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ran_placed_ = ran_placed_name(PlacedRoute::Refused);
+    ran_placed_geo_ = nullptr;
     PlacedChoice choice;
     int gaps = 0;
     (void)placed_plan_for(alg, choice, gaps);          // (refusals leave here, before anything is staged)

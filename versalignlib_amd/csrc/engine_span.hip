@@ -91,6 +91,7 @@ void Engine::score_span_device(int opt, long long n, const uint8_t *d_reads, con
     if (alg > 1 || n <= 0) return;          // reference: unsupported mode is a silent no-op
     ran_span_ = "none";
     ran_placed_ = ran_placed_name(PlacedRoute::Refused);
+    ran_placed_geo_ = nullptr;
     bool strips = false;
     (void)span_prepare(alg, strips);
     hip_check(hipSetDevice(device_), "hipSetDevice");
@@ -108,6 +109,7 @@ void Engine::score_span_host(int opt, int n, const char *const *reads, const cha
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ran_span_ = "none";
     ran_placed_ = ran_placed_name(PlacedRoute::Refused);
+    ran_placed_geo_ = nullptr;
     bool strips = false;                                        // their launches share the boundary rows: one stream, large chunks
     (void)span_prepare(alg, strips);                            // (refusals leave here, before anything is staged)
     hip_check(hipSetDevice(device_), "hipSetDevice");

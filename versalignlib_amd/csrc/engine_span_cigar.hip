@@ -135,6 +135,7 @@ void Engine::align_span_device(int opt, long long n, const uint8_t *d_reads, con
     const int alg = opt & 0xF;
     if (alg > 1 || n <= 0) return;          // reference: unsupported mode is a silent no-op
     ran_placed_ = ran_placed_name(PlacedRoute::Refused);
+    ran_placed_geo_ = nullptr;
     ran_result_format_ = "cigar";
     (void)span_cigar_prepare(alg);          // (refusals leave here, before anything is launched)
     hip_check(hipSetDevice(device_), "hipSetDevice");
@@ -167,6 +168,7 @@ bool Engine::align_span_host(int opt, int n, const char *const *reads, const cha
     if (!reads || !refs) throw std::runtime_error("null sequence array");
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ran_placed_ = ran_placed_name(PlacedRoute::Refused);
+    ran_placed_geo_ = nullptr;
     ran_result_format_ = "cigar";
     Engine &child = span_cigar_prepare(alg);        // (refusals leave here, before anything is staged)
     hip_check(hipSetDevice(device_), "hipSetDevice");

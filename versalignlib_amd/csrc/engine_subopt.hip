@@ -82,6 +82,7 @@ void Engine::subopt_chunk(int c, const LaunchPlan &plan, int track, int gaps, lo
     a.colmax = x.colmax.get();
     a.col_stride = stride;
     const void *fn = plan.geo->subopt(track, gaps);
+    ran_subopt_geo_ = plan.geo;
     const long long ppb = (long long)plan.pairs_per_wave * plan.waves_per_block;
     const long long blocks = (n + ppb - 1) / ppb;
     if (blocks > 0x7FFFFFFFll) throw std::runtime_error("batch too large for one launch");
@@ -108,6 +109,7 @@ void Engine::score_subopt_device(int opt, long long n, const uint8_t *d_reads, c
     const int alg = opt & 0xF;
     if (alg > 1 || n <= 0) return;          // reference: unsupported mode is a silent no-op
     ran_subopt_ = "none";
+    ran_subopt_geo_ = nullptr;
     PlacedChoice choice;
     int gaps = 0;
     const LaunchPlan &plan = subopt_plan_for(alg, mask, choice, gaps);
@@ -128,6 +130,7 @@ void Engine::score_subopt_host(int opt, int n, const char *const *reads, const c
     if (alg > 1 || n <= 0) return;
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ran_subopt_ = "none";
+    ran_subopt_geo_ = nullptr;
     PlacedChoice choice;
     int gaps = 0;
     const LaunchPlan &plan = subopt_plan_for(alg, mask, choice, gaps);          // (refusals leave here, before anything is staged)
