@@ -646,7 +646,9 @@ int valign_hip_set_half_float_cells(valign_hip_engine *e, int mode);
  * "ran_score_sym_affine" is present only where the last score call launched the int16 symmetric affine Smith-Waterman kernel,
  * and names the form of its sweep that ran: "max3" (biased cells, three-operand maxima) or "sources" (gap sources);
  * "ran_score_sym_affine_frame", present beside it, names the frame of that sweep: "tilted" (the biased form with free gap
- * extensions) or "plain" (also for the gap-source form);
+ * extensions) or "plain" (also for the gap-source form); "ran_score_sym_affine_scores", present with them, names where the
+ * sweep took its substitution scores from: "row_tables" (the tilted frame with one byte per score, kept in registers) or
+ * "lds_profile" (everything else);
  * "align_ptr_bytes_per_pair" / "align_ckpt_bytes_per_pair" are the pointer-stream and checkpoint bytes a pair holds in the plan
  * of the last alignment call, "align_scratch_bytes" the pointer scratch the engine holds after it.
  * "ran_result_format" is "rows" or "cigar" for the last alignment call, "cigar_d2h_bytes" what the last

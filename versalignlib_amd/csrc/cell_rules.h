@@ -22,6 +22,7 @@ struct RuleInputs {
     bool no_sym = false, no_tag = false, no_f16 = false, no_prof_key = false;
     bool no_max3 = false;           // debug switch: int16 symmetric affine SW scores on the gap-source form always
     bool no_tilt = false;           // debug switch: ... and its biased form in the plain frame always
+    bool no_row_tables = false;     // debug switch: ... and its tilted frame on the LDS profile always
 };
 
 // int16 DP cells: the reference wraps silently.  Scores and alignments switch to int32 cells on the strip path where they could.
@@ -211,6 +212,26 @@ inline bool sym_affine_tilt_ok(const RuleInputs &in, int R, int F, int rows, int
     return B + (long long)-sc.ext_ref * sym_affine_tilt_top_index(R, F, rows, K) + hi <= kMax3WindowHigh;
 }
 inline const char *ran_sym_affine_frame_name(bool tilted) { return tilted ? "tilted" : "plain"; }
+
+// The tilted sweep's substitution scores from ROW TABLES in registers instead of the LDS profile (dp_kernels.hip.h:
+// wave_setup_tables and the step's kRowTables form): four bytes per row and pair, so every score the tilted frame adds on
+// the diagonal -- match' = match + 2x, mismatch' = mismatch + 2x, zero' = 2x, and on a lane's row 0 each of them plus o - x --
+// must be a byte: the smallest of them >= 0, the largest + (o - x) <= 255, o - x >= 0 (the tables add it byte-wise).
+// The window needs nothing more: a column outside the reference scores 0 instead of zero', which puts its diagonal candidate
+// 2x (row 0: o + x) below a floor whose u is at least 3 (2), no lower than B + x (B - (o - x)) >= 0x0400 for every scoring
+// sym_affine_tilt_ok lets through (x >= 0, B >= 1024 + o - x).  lds_profile / lds_tables: bytes of LDS per wave of the launch's
+// plan and of the row-table set-up (row_table_lds): the tables are taken where they need no more, so that no block asks for
+// more LDS than its plan was sized for (long references: the selector stream has four bytes per column, the codes two).
+inline int sym_affine_row_table_low(const Scoring &sc) { return std::min({sc.match, sc.mismatch, 0}) - 2 * sc.ext_ref; }
+inline int sym_affine_row_table_high(const Scoring &sc) {
+    return std::max({sc.match, sc.mismatch, 0}) - 2 * sc.ext_ref + (sc.ext_ref - sc.open_ref);
+}
+inline bool sym_affine_row_tables_ok(const RuleInputs &in, int R, int F, int rows, int K, int lds_profile, int lds_tables) {
+    if (in.no_row_tables || !sym_affine_tilt_ok(in, R, F, rows, K)) return false;
+    if (in.sc.ext_ref - in.sc.open_ref < 0 || F > 60000) return false;        // (the set-up keeps column numbers in 16 bits)
+    return sym_affine_row_table_low(in.sc) >= 0 && sym_affine_row_table_high(in.sc) <= 255 && lds_tables <= lds_profile;
+}
+inline const char *ran_sym_affine_scores_name(bool row_tables) { return row_tables ? "row_tables" : "lds_profile"; }
 
 // Which fill kernel an alignment call of this mode takes on a G x K geometry, and what its pointer stream looks like.
 struct FillChoice {

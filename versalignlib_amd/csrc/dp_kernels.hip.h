@@ -27,6 +27,9 @@
 //     model (profile_conflicts) finds conflict-free.  Inputs are raw ASCII as delivered
 //     by the ABI (1 byte per base): refs via 16-byte coalesced loads, reads as coalesced
 //     byte loads.
+//     (The tilted int16 symmetric affine Smith-Waterman sweep keeps them in REGISTERS instead where every score is a
+//     byte: four bytes per row and pair, looked up by the one v_perm_b32 the merge takes anyway, from a stream of
+//     selector dwords -- wave_setup_tables; no profile, no slab numbers.)
 //   * Recurrence variants (GAPS), packed instructions per register (= per two cells) incl. the
 //     profile merge: two linear gap scores 6 + maximum tracking, one shared gap score 5 +
 //     tracking, affine 10 + tracking, affine with the same open/extend for both directions 9 + tracking (Smith-Waterman:
@@ -543,6 +546,162 @@ __device__ __forceinline__ bool wave_setup(const uint8_t *reads, const uint8_t *
     return live;
 }
 
+// ---- row tables: the set-up of score_kernel<G, K, kAlgSW, kGapAffineSym>'s tilted sweep where every score fits a byte ----
+// (cell_rules.h: sym_affine_row_tables_ok).  No profile is built.  Each lane keeps, for its K rows, one dword per row and
+// pair -- Ta[q], Tb[q]: byte c the score of the row's read base against reference class c + 1 (match or mismatch; all four
+// zero_score where the row is a padding row or the base no ACGT; row 0 of every lane plus row0_score) -- and the references
+// become a stream of SELECTOR dwords, one per column and lane group: bytes {ca, 0x0c, 4 + cb, 0x0c}, ca / cb the class - 1
+// of pair A's / pair B's base, so that v_perm_b32(Tb[q], Ta[q], selector) IS the packed score of row q (selector byte 0x0c
+// yields 0x00: the high bytes).  A base that is no ACGT, and every column of the pads, selects 0x0c in its half too: the
+// score 0 where the profile has zero_score.  score_kernel says why that is exact outside a reference's ACGT columns;
+// `repair` comes back true (wave-uniform) where some pair of the wave has such a base BEFORE its last ACGT base.
+// LDS of a wave (row_table_lds): the wave's raw references, then the stream, row_table_pad(G) pad columns at either end of
+// every group's; the raw reads are staged where the stream is built once they have been read.
+constexpr int row_table_pad(int G) { return G + 4; }       // columns -(G - 1) .. F + G are read (the sweep, two steps of prefetch)
+constexpr unsigned kSelZero4 = 0x0c0c0c0cu;
+
+template <int G, int K>
+__device__ __forceinline__ bool wave_setup_tables(const uint8_t *reads, const uint8_t *refs, long long n, int R, int F,
+                                                  int refs_area, int sel_stride, int wave_lds, short match, short mismatch,
+                                                  short zero_score, short row0_score, unsigned block, WaveTables &w,
+                                                  unsigned (&Ta)[K], unsigned (&Tb)[K], bool &repair) {
+    using geo = Geo<G, K>;
+    constexpr int kPad = row_table_pad(G);
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x / kWave;
+    const int row0 = R - geo::kRows;                     // read position of padded row 0 (one sweep covers the read)
+
+    unsigned char *raw = valign_smem + (size_t)wave * wave_lds;
+    unsigned char *sel = raw + refs_area;
+
+    const int waves = blockDim.x / kWave;
+    const long long pair0 = ((long long)block * waves + wave) * geo::kPairs;
+    const bool live = pair0 < n;
+    long long pair_end = pair0 + geo::kPairs;
+    if (pair_end > n) pair_end = n;
+    const int last = (int)(pair_end - pair0) - 1;
+
+    if (live) {
+        stage_span(raw, refs, pair0 * F, pair_end * F, lane);
+        stage_span(sel, reads, pair0 * R, pair_end * R, lane);
+    }
+    __syncthreads();
+
+    // ---- the lane's 2K rows: four read bases at a time to their classes, the classes to the four score bytes of each row ----
+    if (live) {
+        // byte a of {hi, lo}: the score of a read base of class a against reference class c + 1
+        auto table = [&](int c, unsigned &lo, unsigned &hi) __attribute__((always_inline)) {
+            unsigned b[8];
+#pragma unroll
+            for (int a = 0; a < 8; ++a) b[a] = (unsigned)(a >= 1 && a <= 4 ? (a == c + 1 ? match : mismatch) : zero_score) & 0xFFu;
+            lo = b[0] | b[1] << 8 | b[2] << 16 | b[3] << 24;
+            hi = b[4] | b[5] << 8 | b[6] << 16 | b[7] << 24;
+        };
+        unsigned t_lo[4], t_hi[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) table(c, t_lo[c], t_hi[c]);
+        const unsigned char *raw_rd = sel + (int)((unsigned long long)(reads + pair0 * R) & 15ull);
+        const int grp = lane / G, l = lane % G;
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            int p = 2 * grp + half;
+            p = p > last ? last : p;
+#pragma unroll
+            for (int q0 = 0; q0 < K; q0 += 4) {
+                const int pos = row0 + l * K + q0;
+                const int at = pos < -3 ? -3 : pos;
+                unsigned w4 = lds_dword_at(raw_rd + p * R + at);
+                if (pos < 0) w4 = pos < -3 ? 0u : w4 & (0xFFFFFFFFu << (8 * -pos));      // rows before the read: class 0
+                const unsigned cls = base_class4(w4);
+                unsigned col[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) col[c] = select_bytes8(t_hi[c], t_lo[c], cls);   // byte i: row q0 + i against class c + 1
+                const unsigned lo01 = __builtin_amdgcn_perm(col[1], col[0], 0x05010400u), hi01 = __builtin_amdgcn_perm(col[1], col[0], 0x07030602u);
+                const unsigned lo23 = __builtin_amdgcn_perm(col[3], col[2], 0x05010400u), hi23 = __builtin_amdgcn_perm(col[3], col[2], 0x07030602u);
+                unsigned (&T)[K] = half ? Tb : Ta;
+                T[q0] = __builtin_amdgcn_perm(lo23, lo01, 0x05040100u);
+                T[q0 + 1] = __builtin_amdgcn_perm(lo23, lo01, 0x07060302u);
+                if (q0 + 2 < K) {
+                    T[q0 + 2] = __builtin_amdgcn_perm(hi23, hi01, 0x05040100u);
+                    T[q0 + 3] = __builtin_amdgcn_perm(hi23, hi01, 0x07060302u);
+                }
+            }
+        }
+        const unsigned r4 = ((unsigned)row0_score & 0xFFu) * 0x01010101u;      // (no byte carries: the rule bounds every sum by 255)
+        Ta[0] += r4;
+        Tb[0] += r4;
+    }
+    __syncthreads();                                                           // the raw reads make way for the stream
+
+    // ---- the selector stream ----
+    int cols_used = 0;
+    bool before_last = false;
+    unsigned *stream = reinterpret_cast<unsigned *>(sel);
+    const int stride_dw = sel_stride / 4;
+    if (live) {
+        for (int idx = lane; idx < geo::kGroups * 2 * kPad; idx += kWave) {
+            const int g = idx / (2 * kPad), x = idx - g * (2 * kPad);
+            stream[g * stride_dw + (x < kPad ? x : F + x)] = kSelZero4;          // [0, pad) and [F + pad, F + 2 pad)
+        }
+        const int ref_skew = (int)((unsigned long long)(refs + pair0 * F) & 15ull);
+        typedef unsigned short u16;
+#pragma unroll
+        for (int g = 0; g < geo::kGroups; ++g) {
+            int pa = 2 * g, pb = 2 * g + 1;
+            pa = pa > last ? last : pa;
+            pb = pb > last ? last : pb;
+            const unsigned char *raw_a = raw + ref_skew + pa * F, *raw_b = raw + ref_skew + pb * F;
+            unsigned *out_g = stream + g * stride_dw + kPad;
+            // per pair: {1 + its last ACGT column, 0xFFFF - its first column that is none} -- one packed maximum each
+            u16x2 ends_a = u16x2{0, 0}, ends_b = u16x2{0, 0};
+            auto note = [](u16x2 &ends, unsigned acgt, int j) __attribute__((always_inline)) {     // acgt: a byte is non-zero where the column has an ACGT base
+                const unsigned none = ~nonzero_bytes(acgt) & 0x80808080u;
+                const u16 end = acgt ? (u16)(j + 4 - (__builtin_clz(acgt) >> 3)) : (u16)0;
+                const u16 first_none = none ? (u16)(0xFFFF - (j + (__builtin_ctz(none) >> 3))) : (u16)0;
+                ends = __builtin_elementwise_max(ends, u16x2{end, first_none});
+            };
+            const int F4 = F & ~3;
+            for (int j = 4 * lane; j < F4; j += 4 * kWave) {                    // four columns per lane and trip
+                const unsigned ca = base_class4(lds_dword_at(raw_a + j)), cb = base_class4(lds_dword_at(raw_b + j));
+                // selector by class: 1..4 the table byte (pair B: of the second table), 0 and 5..7 the constant zero
+                const unsigned sa = select_bytes8(0x0c0c0c03u, 0x0201000cu, ca), sb = select_bytes8(0x0c0c0c07u, 0x0605040cu, cb);
+                uint4 s;
+                s.x = __builtin_amdgcn_perm(sb, sa, 0x0c040c00u) | 0x0c000c00u;
+                s.y = __builtin_amdgcn_perm(sb, sa, 0x0c050c01u) | 0x0c000c00u;
+                s.z = __builtin_amdgcn_perm(sb, sa, 0x0c060c02u) | 0x0c000c00u;
+                s.w = __builtin_amdgcn_perm(sb, sa, 0x0c070c03u) | 0x0c000c00u;
+                *reinterpret_cast<uint4 *>(out_g + j) = s;
+                note(ends_a, sa ^ kSelZero4, j);
+                note(ends_b, sb ^ kSelZero4, j);
+            }
+            for (int j = F4 + lane; j < F; j += kWave) {                        // the rim
+                const int ca = base_class(raw_a[j]), cb = base_class(raw_b[j]);
+                const bool va = ca >= 1 && ca <= 4, vb = cb >= 1 && cb <= 4;
+                out_g[j] = (va ? (unsigned)(ca - 1) : 0x0cu) | (vb ? (unsigned)(cb + 3) : 0x0cu) << 16 | 0x0c000c00u;
+                ends_a = __builtin_elementwise_max(ends_a, u16x2{va ? (u16)(j + 1) : (u16)0, va ? (u16)0 : (u16)(0xFFFF - j)});
+                ends_b = __builtin_elementwise_max(ends_b, u16x2{vb ? (u16)(j + 1) : (u16)0, vb ? (u16)0 : (u16)(0xFFFF - j)});
+            }
+#pragma unroll
+            for (int d = kWave / 2; d >= 1; d >>= 1) {
+                ends_a = __builtin_elementwise_max(ends_a, __builtin_bit_cast(u16x2, __shfl_xor(__builtin_bit_cast(int, ends_a), d, kWave)));
+                ends_b = __builtin_elementwise_max(ends_b, __builtin_bit_cast(u16x2, __shfl_xor(__builtin_bit_cast(int, ends_b), d, kWave)));
+            }
+            before_last |= 0xFFFF - (int)ends_a.y < (int)ends_a.x || 0xFFFF - (int)ends_b.y < (int)ends_b.x;
+            cols_used = (int)ends_a.x > cols_used ? (int)ends_a.x : cols_used;
+            cols_used = (int)ends_b.x > cols_used ? (int)ends_b.x : cols_used;
+        }
+    }
+    __syncthreads();
+    repair = __builtin_amdgcn_readfirstlane((int)before_last) != 0;
+    w.cols_used = __builtin_amdgcn_readfirstlane(cols_used);
+    w.prof = raw;
+    w.refc = reinterpret_cast<unsigned char *>(stream + kPad);          // entry of column 0 of the first group
+    w.first_bad = nullptr;
+    w.pair0 = pair0;
+    w.last = last;
+    return live;
+}
+
 // K/2 dwords starting at LDS byte offset `addr`, with the widest loads the lane stride allows
 template <int K>
 __device__ __forceinline__ void lds_load_lane(unsigned addr, unsigned (&v)[K / 2]) {
@@ -696,8 +855,22 @@ score_kernel(const ScoreArgs args) {
     const short s_match = HALF ? __builtin_bit_cast(short, (_Float16)(((int)args.match + fold) * unit)) : (short)(args.match + fold);
     const short s_mismatch = HALF ? __builtin_bit_cast(short, (_Float16)(((int)args.mismatch + fold) * unit)) : (short)(args.mismatch + fold);
     const short s_zero = HALF ? __builtin_bit_cast(short, (_Float16)fold) : (short)fold;
-    if (!wave_setup<G, K, false>(reads, refs, n_pairs, args.R, F_batch, args.prof_area, args.refc_stride,
-                                 args.wave_lds, s_match, s_mismatch, w, false, block, s_zero, kOneSweep, 0, s_row0))
+    // (... and where every such score fits a byte -- bit 17, sym_affine_row_tables_ok -- the scores of a lane's rows stay in
+    // registers and no profile is built: wave_setup_tables)
+    bool tables = false, repair = false;
+    unsigned Ta[K], Tb[K];
+    if constexpr (SOURCES && K <= kTiltMaxK) {
+        tables = args.sym_max3_bias > 0 && (args.sym_max3_bias >> 16 & 3) == 3;
+        bool live = false;
+        if (tables)
+            live = wave_setup_tables<G, K>(reads, refs, n_pairs, args.R, F_batch, args.prof_area, args.refc_stride, args.wave_lds,
+                                           s_match, s_mismatch, s_zero, s_row0, block, w, Ta, Tb, repair);
+        if (!tables)
+            live = wave_setup<G, K, false>(reads, refs, n_pairs, args.R, F_batch, args.prof_area, args.refc_stride,
+                                           args.wave_lds, s_match, s_mismatch, w, false, block, s_zero, kOneSweep, 0, s_row0);
+        if (!live) return;
+    } else if (!wave_setup<G, K, false>(reads, refs, n_pairs, args.R, F_batch, args.prof_area, args.refc_stride,
+                                        args.wave_lds, s_match, s_mismatch, w, false, block, s_zero, kOneSweep, 0, s_row0))
         return;
     const long long pair0 = w.pair0;
     // Smith-Waterman: columns after the last ACGT base of every reference in the wave (the NUL
@@ -770,7 +943,7 @@ score_kernel(const ScoreArgs args) {
     unsigned pa[K / 2], pb[K / 2];
     s16x2 S0[K], S1[K];          // the scores of a step (two buffers: the steady loop takes two steps per trip)
     unsigned ca_next = 0, cb_next = 0;
-    if (PIPE) {
+    if (PIPE && !tables) {          // (the row-table sweep has no profile and fetches its own stream)
         const unsigned ca = *(lds_cu8 *)(code_addr), cb = *(lds_cu8 *)(code_addr + 1);
         lds_load_lane<K>(lane_base + ca * geo::kPairStride, pa);
         lds_load_lane<K>(lane_base + cb * geo::kPairStride, pb);
@@ -1117,17 +1290,66 @@ score_kernel(const ScoreArgs args) {
                 // K-step trip their offsets are adjacent constants, and plain loads get merged into wide, unaligned ones whose
                 // bytes come apart again on the VALU (18 instructions per trip at 16 x 10), which has no slot to spare; the LDS
                 // port has.  profiles/r21_sym_affine_bookkeeping.txt.
-                auto tilted_step = [&](auto slot_tag) __attribute__((always_inline)) {
+                // THE ROW TABLES (FORM kRowTables; kLdsProfile is the step as described so far).  Where every S' fits a byte the lane
+                // holds them -- Ta[q], Tb[q]: four bytes, row q against the four reference classes, pair A and pair B, built by
+                // wave_setup_tables, row 0 with its o - x -- and a step fetches ONE selector dword {ca, 0x0c, 4 + cb, 0x0c}:
+                // S'[q] = v_perm_b32(Tb[q], Ta[q], selector), the perm the profile's merge takes anyway.  No slab numbers, no address
+                // arithmetic, no profile loads; the stream is fetched two steps ahead (volatile, as the code bytes are).
+                // A base that is no ACGT, and every column of the pads, selects the constant 0x00 in its half: S' = 0 where the profile
+                // has 2x (row 0: 2x + o - x).  OUTSIDE A REFERENCE'S ACGT COLUMNS THAT IS EXACT:
+                //   * left of column 0 every register holds its floor (by induction from the start values).  d = floor(p-1, j-1) + 0 =
+                //     floor(p, j) - 2x in rows 1 .. K-1 and, row 0, (floor(p-1, j-1) - (o - x)) + 0 = floor(p, j) - o - x: at or below
+                //     the floor, so e = max3(floor - x, floor - o, floor) = floor wins h's max3, the accumulator's too, and the cell
+                //     stays exactly at its floor as with S' = 2x.
+                //   * right of a pair's last ACGT column (the wave sweeps on to its longest reference's) the profile form repeats
+                //     cells that exist: S' = 2x makes d the cell (p-1, j-1) itself.  Every operation of the cell is monotone in its
+                //     operands and S' only got smaller (d: that cell less 2x, row 0: less o + x), so by induction no register there
+                //     exceeds what the profile form holds, the accumulators are offered nothing they have not seen, and the columns
+                //     up to the last ACGT base -- which never read a column to their right -- are computed as before.
+                //   * THE WINDOW.  Every cell that is computed has u >= 2 (u = l (K - 1) + q + t + 2), rows 1 .. K-1 u >= 3: the
+                //     smallest such d is B + 3x - 2x = B + x, row 0's B + 2x - o - x = B - (o - x), both at or above 0x0400 by the
+                //     bias of the frame (B >= 1024 + o - x, x >= 0: sym_affine_tilt_bias, sym_affine_max3_ok); upwards nothing
+                //     grew.  The rule has no scoring to refuse on the window's account.
+                // A base that is no ACGT BEFORE its reference's last ACGT base must score exactly 2x, which a table cannot give:
+                // wave_setup_tables finds such a wave (`repair`, wave-uniform) and it runs FORM kRowTablesRepair, the same step with
+                // every half that selected 0x00 set to 2x (row 0: 2x + o - x) -- one v_or_b32 per register and four per step
+                // more: the profile's scores at every column, pads included, so exact by the profile form's argument.
+                // tests/test_sym_affine_row_tables_sweep.py restates this step on the CPU.
+                constexpr int kLdsProfile = 0, kRowTables = 1, kRowTablesRepair = 2;
+                lds_cu32 *sel_ptr = (lds_cu32 *)(lds_offset(w.refc) + grp * args.refc_stride - 4 * (l - lead));   // + 4 per step
+                unsigned sel_cur = 0, sel_next = 0;
+                if (tables) {
+                    sel_cur = sel_ptr[0];
+                    sel_next = sel_ptr[1];
+                }
+                const unsigned zero_q = as_u32(pk(s_zero)), zero_0 = as_u32(pk((short)(s_zero + s_row0)));
+                auto tilted_step = [&](auto slot_tag, auto form_tag) __attribute__((always_inline)) {
                     constexpr int SLOT0 = decltype(slot_tag)::value;
+                    constexpr int FORM = decltype(form_tag)::value;
                     s16x2 S[K], d[K];
                     const s16x2 diag0 = up0;
                     up0 = group_prev_or<G>(HOl[K - 1], lead_border, lmask);
                     lead_border = lead_border + lead_step;
-                    merge_profile<K>(pa, pb, S);
-                    lds_load_lane<K>(lane_base + ca_next * geo::kPairStride, pa);
-                    lds_load_lane<K>(lane_base + cb_next * geo::kPairStride, pb);
-                    ca_next = ((volatile lds_cu8 *)code_ptr)[4];
-                    cb_next = ((volatile lds_cu8 *)code_ptr)[5];
+                    if constexpr (FORM == kLdsProfile) {
+                        merge_profile<K>(pa, pb, S);
+                        lds_load_lane<K>(lane_base + ca_next * geo::kPairStride, pa);
+                        lds_load_lane<K>(lane_base + cb_next * geo::kPairStride, pb);
+                        ca_next = ((volatile lds_cu8 *)code_ptr)[4];
+                        cb_next = ((volatile lds_cu8 *)code_ptr)[5];
+                    } else {
+#pragma unroll
+                        for (int q = 0; q < K; ++q) S[q] = as_pk(__builtin_amdgcn_perm(Tb[q], Ta[q], sel_cur));
+                        if constexpr (FORM == kRowTablesRepair) {
+                            // bit 3 of a selector byte is set where it is 0x0c: 0xFFFF in the halves that selected the constant
+                            const unsigned none = ((sel_cur >> 3) & 0x00010001u) * 0xFFFFu;
+                            const unsigned fix_0 = zero_0 & none, fix_q = zero_q & none;
+#pragma unroll
+                            for (int q = 0; q < K; ++q) S[q] = as_pk(as_u32(S[q]) | (q == 0 ? fix_0 : fix_q));
+                        }
+                        sel_cur = sel_next;
+                        sel_next = ((volatile lds_cu32 *)sel_ptr)[2];
+                        sel_ptr += 1;
+                    }
                     s16x2 e_cur;
                     auto pass1 = [&](int q, s16x2 &e) __attribute__((always_inline)) {
                         d[q] = (q == 0 ? diag0 : Hl[q - 1]) + S[q];
@@ -1159,15 +1381,26 @@ score_kernel(const ScoreArgs args) {
                     // row 0's anti-diagonal is complete: the slot moves on to c + K
                     acc[SLOT0 % K] = acc[SLOT0 % K] + kx_c;
                     fl[SLOT0 % K] = fl[SLOT0 % K] + kx_c;
-                    code_ptr += 2;
+                    if constexpr (FORM == kLdsProfile) code_ptr += 2;
                 };
-                unrolled_steps(std::make_integer_sequence<int, K>{}, [&](auto slot_tag) __attribute__((always_inline)) {
-                    if constexpr (decltype(slot_tag)::value > 0) {
-                        if (decltype(slot_tag)::value >= s0) tilted_step(slot_tag);
-                    }
-                });
-                for (int trips = steps / K; trips > 0; --trips)
-                    unrolled_steps(std::make_integer_sequence<int, K>{}, [&](auto slot_tag) __attribute__((always_inline)) { tilted_step(slot_tag); });
+                auto tilted_sweep = [&](auto form_tag) __attribute__((always_inline)) {
+                    unrolled_steps(std::make_integer_sequence<int, K>{}, [&](auto slot_tag) __attribute__((always_inline)) {
+                        if constexpr (decltype(slot_tag)::value > 0) {
+                            if (decltype(slot_tag)::value >= s0) tilted_step(slot_tag, form_tag);
+                        }
+                    });
+                    for (int trips = steps / K; trips > 0; --trips)
+                        unrolled_steps(std::make_integer_sequence<int, K>{}, [&](auto slot_tag) __attribute__((always_inline)) { tilted_step(slot_tag, form_tag); });
+                };
+                // One copy of the tail and the trip per form, each under a comparison of its own: written as if / else the copies'
+                // common parts get hoisted and the kernel allocates half as many registers again
+                // (profiles/r21_sym_affine_bookkeeping.txt, section 1).
+                int form = __builtin_amdgcn_readfirstlane(tables ? (repair ? kRowTablesRepair : kRowTables) : kLdsProfile);
+                if (form == kLdsProfile) tilted_sweep(std::integral_constant<int, kLdsProfile>{});
+                asm volatile("" : "+s"(form));          // (each comparison on a value the compiler knows nothing about)
+                if (form == kRowTables) tilted_sweep(std::integral_constant<int, kRowTables>{});
+                asm volatile("" : "+s"(form));
+                if (form == kRowTablesRepair) tilted_sweep(std::integral_constant<int, kRowTablesRepair>{});
                 // the odd rows of the last step, then out of the frame: after a whole trip slot q stands for c = q + steps
                 best = pk(0);
 #pragma unroll
@@ -1324,6 +1557,21 @@ inline WaveLds wave_lds(int R, int F) {
     w.prof_area = ((w.prof_area + 15) / 16) * 16;
     w.refc_stride = ((2 * (F + 2 * kCodePad) + 15) / 16) * 16;
     w.total = w.prof_area + geo::kGroups * w.refc_stride + ((geo::kPairs * 8 + 15) / 16) * 16;
+    return w;
+}
+
+// ... and with the row tables (wave_setup_tables): prof_area holds the wave's raw references, refc_stride is one group's selector
+// stream, and the raw reads are staged where the streams are built afterwards.  A group's lanes read G consecutive dwords of
+// its stream: a stride of G (mod 64) dwords puts the groups of a wave on disjoint banks.
+inline WaveLds row_table_lds(int G, int R, int F) {
+    const int groups = kWave / G, pairs = 2 * groups;
+    WaveLds w;
+    w.prof_area = ((pairs * F + 32 + 15) / 16) * 16;
+    int stride_dw = F + 2 * row_table_pad(G);
+    stride_dw += ((G - stride_dw) % 64 + 64) % 64;
+    w.refc_stride = 4 * stride_dw;
+    const int streams = groups * w.refc_stride, raw_reads = ((pairs * R + 32 + 15) / 16) * 16;
+    w.total = w.prof_area + (streams > raw_reads ? streams : raw_reads);
     return w;
 }
 

@@ -174,7 +174,7 @@ public:
     DebugSwitches() {
         const char *env = getenv("VALIGN_HIP_DEBUG");
         if (!env) return;
-        static const char *const known[] = {"no_sym", "no_tag", "no_f16", "no_max3", "no_tilt", "no_fused", "no_prof_key", "no_overlap", "no_band_chain",
+        static const char *const known[] = {"no_sym", "no_tag", "no_f16", "no_max3", "no_tilt", "no_row_tables", "no_fused", "no_prof_key", "no_overlap", "no_band_chain",
                                             "force_long", "wide_align", "strip_k", "no_single_strip", "no_direct_out", "ragged_min", "chunk_bytes",
                                             "align_chunk_bytes", "direct_bytes", "scratch_cap_mb", "whole_rows", "short_strips", "cigar_rows_mb", "cigar_lanes",
                                             "span_scratch_bytes", "subopt_scratch_bytes", "span_cigar_mb"};
@@ -374,7 +374,11 @@ public:
     std::string ran_kernels() const;
 
     // What the pure rules of cell_rules.h read of this engine
-    RuleInputs rule_inputs() const { return RuleInputs{sc_, R_, F_, sse_policy_, no_sym_, no_tag_, no_f16_, no_prof_key_, no_max3_, no_tilt_}; }
+    RuleInputs rule_inputs() const {
+        RuleInputs in = RuleInputs{sc_, R_, F_, sse_policy_, no_sym_, no_tag_, no_f16_, no_prof_key_, no_max3_, no_tilt_};
+        in.no_row_tables = no_row_tables_;
+        return in;
+    }
     // score_alignments at the engine's full shape stays inside int16 cells (int16_range_ok with this engine's plans: the
     // NW variant's tilt over the tallest register sweep a call may take)
     bool score_int16_ok(int alg) const;
@@ -881,6 +885,7 @@ private:
     bool no_f16_ = dbg_.on("no_f16");   // int16 cells for symmetric affine SW too
     bool no_max3_ = dbg_.on("no_max3");   // int16 symmetric affine SW scores on the gap-source form always
     bool no_tilt_ = dbg_.on("no_tilt");   // ... and their biased form in the plain frame always
+    bool no_row_tables_ = dbg_.on("no_row_tables");   // ... and their tilted frame on the LDS profile always
     bool no_fused_ = dbg_.on("no_fused");   // small alignment calls as fill + traceback kernels
     bool no_prof_key_ = dbg_.on("no_prof_key");   // compute the SW lane key instead of carrying it in the profile
     bool copy_engines_primed_ = false;
@@ -921,6 +926,7 @@ private:
     // (describe: ran_score_sym_affine; null -- the key is absent -- where the call launched no such kernel)
     const char *ran_score_sym_affine_ = nullptr;
     const char *ran_score_sym_affine_frame_ = "plain";   // ... and its frame: "tilted" / "plain" (describe: ran_score_sym_affine_frame, beside that key)
+    const char *ran_score_sym_affine_scores_ = "lds_profile";   // ... and where its substitution scores came from: "row_tables" / "lds_profile" (ran_score_sym_affine_scores)
     const char *ran_placed_ = "none";                    // what the last placed-score call ran: key / rows / strip / chain / wide (describe)
     std::string ran_span_ = "none";                      // what the last spanned call ran: forward route / reverse route (describe)
     size_t span_scratch_bytes_ = (size_t)dbg_.value("span_scratch_bytes", 256ll << 20);      // device-resident spanned calls: scratch of one chunk

@@ -136,7 +136,7 @@ std::string Engine::describe(int opt, long long n) const {
     std::string out(buf);
     if (ran_score_sym_affine_)          // only where the last score call ran the int16 symmetric affine SW kernel
         out.insert(out.size() - 1, std::string(", \"ran_score_sym_affine\": \"") + ran_score_sym_affine_ + "\", \"ran_score_sym_affine_frame\": \"" +
-                                       ran_score_sym_affine_frame_ + "\"");
+                                       ran_score_sym_affine_frame_ + "\", \"ran_score_sym_affine_scores\": \"" + ran_score_sym_affine_scores_ + "\"");
     return out;
 }
 

@@ -93,10 +93,21 @@ void Engine::launch_score(const LaunchPlan &plan, int alg, int R, int F, long lo
         // of the same member says so to the kernel, which then folds 2x into its query profile)
         const bool tilted = sym_affine_tilt_ok(rule_inputs(), R_, F_, plan.geo->G * plan.geo->K, plan.geo->K);
         if (tilted) a.sym_max3_bias = sym_affine_tilt_bias(sc_) | 1 << 16;
+        // ... and in the tilted frame the substitution scores from row tables in registers where every one of them is a byte (bit
+        // 17): that set-up builds no profile and lays the wave's LDS out its own way, never larger than the plan's
+        const WaveLds tables_lds = row_table_lds(plan.geo->G, R, F);
+        const bool row_tables = tilted && sym_affine_row_tables_ok(rule_inputs(), R_, F_, plan.geo->G * plan.geo->K, plan.geo->K, plan.lds.total, tables_lds.total);
+        if (row_tables) {
+            a.sym_max3_bias |= 1 << 17;
+            a.prof_area = tables_lds.prof_area;
+            a.refc_stride = tables_lds.refc_stride;
+            a.wave_lds = tables_lds.total;
+        }
         ran_score_sym_affine_ = ran_sym_affine_name(max3);
         ran_score_sym_affine_frame_ = ran_sym_affine_frame_name(tilted);
+        ran_score_sym_affine_scores_ = ran_sym_affine_scores_name(row_tables);
     }
-    const int block_lds = plan.lds.total * plan.waves_per_block;
+    const int block_lds = a.wave_lds * plan.waves_per_block;
     if (block_lds > kDefaultBlockLds)
         hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, block_lds),
                   "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
