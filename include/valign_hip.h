@@ -596,9 +596,11 @@ int valign_hip_score_subopt_host(valign_hip_engine *e, int opt, int n, const cha
  * scoring whose cells could leave int16 -- signed cells: min(R, F) * max(match, mismatch, 0) above 32000, or the all-gaps path
  * to the far corner (R reference-direction steps and F read-direction steps at their worst price) plus the largest single addend
  * below -32000; and the shapes placed scores send to the row strips (reads of more than 1024 rows, or no register geometry).
- * opt & 0xF > 1 does nothing, as everywhere.
- * "ran_extend" of valign_hip_describe is "rows" after a call that ran ("none" before any, or when it was refused).  The device
- * call holds no scratch.  tests/extend_ref.py restates the definition in numpy.                                            */
+ * The last three -- score_width = 32, the int16 range under score_width = 0, the row strips' shapes -- run on int32 cells under
+ * valign_hip_set_extend_wide(e, 1), below.  opt & 0xF > 1 does nothing, as everywhere.
+ * "ran_extend" of valign_hip_describe is "rows" after a call that ran on the register sweep, "wide" (extend_wide, below) after
+ * one that ran on the int32 sweep ("none" before any, or when it was refused).  The register sweep's device call holds no
+ * scratch.  tests/extend_ref.py restates the definition in numpy.                                                          */
 typedef struct {                     /* 20 bytes */
     int32_t score, read_end, ref_end, gscore, gref_end;
 } valign_hip_extend;
@@ -611,6 +613,31 @@ int valign_hip_score_extend_device(valign_hip_engine *e, int opt, long long n, c
 /* Host pointers in, records out: the chunk pipeline of valign_hip_score_placed_host, 20 bytes per pair on the way back.      */
 int valign_hip_score_extend_host(valign_hip_engine *e, int opt, int n, const char *const *reads,
                                  const char *const *refs, valign_hip_extend *extend, int threads);
+
+/* Extension scores on int32 cells and row strips (key extend_wide; flat API only).  0 (default): every extension call runs or is
+ * refused exactly as stated above.  1: a call that would be refused for one of THREE reasons runs instead, with the same
+ * definition and the same record, on the int32 extension sweep (score_extend_wide_kernel: signed int32 cells, 512-row strips, a
+ * launch per strip, boundary rows handed from strip to strip; "ran_extend": "wide", "ran_extend_geometry": "none"):
+ *   - score_width = 32;
+ *   - a shape x scoring whose cells could leave int16, under score_width = 0 (16 means "int16 or refuse" and stays refused);
+ *   - reads of more than 1024 rows, and shapes without a register geometry -- whatever score_width says: the long reads a
+ *     seed-and-extend mapper extends on.
+ * Every other call decides as with 0: a call the register sweep serves keeps it ("rows"), and opt & 0xF == 1,
+ * traceback_policy = 1 and every band_width > 0 stay refused with their texts.  placed_wide is not read by extension calls, nor
+ * extend_wide by placed, spanned or suboptimal ones.  Values and coordinates are int32 from the cell to the record: nothing
+ * saturates (33 x 1000 is 33000).
+ * REFUSED under extend_wide = 1, with a message that begins "extend_wide:": a shape x scoring whose cells could leave +-2^28 --
+ * min(R, F) * max(match, mismatch, 0) above 2^28, or the all-gaps path to the far corner plus the largest single addend below
+ * -2^28 (the bounds of the int16 rule, at this width).  The gap states of the two borders are a finite value of -2^29 that
+ * drifts down by an extension per step: the bound keeps it below every cell and inside int32.  Other values than 0 / 1 are
+ * refused.
+ * The device call is cut into chunks whose boundary rows fit the engine's strip scratch (the placed int32 sweep's, shared with
+ * it: calls of one engine that use it belong on one stream); per pair it also holds a 20-byte partial record and the two trimmed
+ * lengths.  The host call is the chunk pipeline with the strip path's chunk sizes, on one stream.
+ * KNOWN: a short read fills a fraction of its one 512-row strip, as on the placed int32 sweep -- the register sweep is the route
+ * for short reads wherever the rule lets it run.  Z-drop, a band around the anchor's diagonal and an end bonus remain unbuilt.
+ * "extend_wide" of valign_hip_describe is the key.                                                                           */
+int valign_hip_set_extend_wide(valign_hip_engine *e, int on);
 
 /* Page-lock a host range and map it for the device (hipHostRegister behind a C symbol, so that an FFI caller needs no
  * HIP binding).  valign_hip_align_host into result buffers that lie inside a registered range -- or inside memory the
@@ -654,7 +681,7 @@ int valign_hip_set_half_float_cells(valign_hip_engine *e, int mode);
  * "ran_result_format" is "rows" or "cigar" for the last alignment call, "cigar_d2h_bytes" what the last
  * valign_hip_align_cigar_host call copied back, "cigar_rows_scratch_bytes" the rows scratch of the compact format.
  * "ran_placed" is what the last placed-score call ran: key / rows / strip / chain / wide ("none" before any, or when it was
- * refused); "band_placed" is the key of valign_hip_set_band_placed, "placed_wide" that of valign_hip_set_placed_wide.  "ran_span", "span_ref_length" and "span_scratch_bytes"
+ * refused); "band_placed" is the key of valign_hip_set_band_placed, "placed_wide" that of valign_hip_set_placed_wide, "extend_wide" that of valign_hip_set_extend_wide.  "ran_span", "span_ref_length" and "span_scratch_bytes"
  * belong to the spanned scores, "ran_subopt", "subopt_scratch_bytes" and "subopt_ring_cols" to the suboptimal scores, above. */
 int valign_hip_describe(valign_hip_engine *e, int opt, long long n, char *buf, int cap);
 

@@ -9,7 +9,7 @@ tests/subopt_ref.py wherever placed scores ran on the register sweep -- and `--k
 to 160 x 300 with a second, mutated copy of the read planted in the reference; `--kind span_cigar` draws nothing but cases for the
 spanned CIGARs (align_span_device / _host against tests/span_cigar_ref.py: random shapes up to 320 x 900 and one in eight on the row
 strips, scorings, extended, ops_stride, trace_checkpoints, pointer_scratch_cap_mb, placed_wide); `--kind extend` draws nothing but
-cases for the extension scores (score_extend_device / _host against tests/extend_ref.py: random shapes up to 200 x 300, the four gap
+cases for the extension scores (a third of them extend_wide = 1 cases -- long reads, scorings out of int16, score_width = 32; score_extend_device / _host against tests/extend_ref.py: random shapes up to 200 x 300, the four gap
 forms at several scales, the engine's own or a forced geometry, planted extensions, ragged tails and interior junk).  What tools/fuzz_parity.py does for the plugin ABI, for the entry points the tests of the device path
 use; a process that runs it for minutes also exercises the library's set-up and tear-down far more often than the suite.
 
@@ -318,9 +318,30 @@ EXTEND_GEOMETRIES = [(0, 0), (8, 8), (16, 10), (32, 10), (64, 8), (64, 16), (64,
 EXTEND_FORMS = [(-3, -3), (-2, -4), (-3, -3, -5, -1, -5, -1), (-3, -3, -6, -2, -4, -1)]
 
 
+def draw_extend_wide(rng):
+    """an extend_wide = 1 case (a third of --kind extend): a long read that takes two to four 512-row strips, a scoring out of the
+    signed int16 bound (match 970, or gaps of -320 and beyond), or score_width = 32 on an in-range call -- each on the int32 extension sweep"""
+    why = ("long", "scoring", "width")[int(rng.integers(0, 3))]
+    form = EXTEND_FORMS[int(rng.integers(0, 4))]
+    match, scale, width = 2, 1, 0
+    if why == "long":
+        R, F, n = int(rng.integers(1025, 1600)), int(rng.integers(1, 301)), int(rng.integers(1, 10))
+    else:
+        R, F, n = int(rng.integers(1, 201)), int(rng.integers(1, 301)), int(rng.integers(1, 100))
+    if why == "scoring":
+        R, F = max(R, 34), max(F, 70)               # 34 x 970 and 104 gap steps at -320 or worse leave +-32000
+        match, scale = ((970, 1), (2, 160))[int(rng.integers(0, 2))]
+    if why == "width":
+        width = 32
+    return dict(R=R, F=F, n=n, scoring=(match, -int(rng.integers(1, 4))) + tuple(g * scale for g in form), affine=len(form) > 2, geometry=(0, 0),
+                host=bool(rng.random() < 0.3), threads=int(rng.integers(1, 9)), seed=int(rng.integers(0, 1 << 30)), wide=why, width=width)
+
+
 def draw_extend(rng):
     """--kind extend: a shape, a scoring inside the signed int16 bound (extend_choice, cell_rules.h: 500 gap steps at 60 stay above
-    -32000), a geometry that holds the read, and whether the host entry runs too"""
+    -32000), a geometry that holds the read, and whether the host entry runs too; a third of the cases are draw_extend_wide's"""
+    if rng.random() < 1 / 3:
+        return draw_extend_wide(rng)
     R, F = int(rng.integers(1, 201)), int(rng.integers(1, 301))
     match = int(rng.choice([1, 2, 3, 14, 60]))
     scale = {1: 1, 2: 1, 3: 1, 14: 4, 60: 10}[match]
@@ -350,13 +371,19 @@ def run_extend(c):
         if rng.random() < 0.2:
             refs[p, int(rng.integers(0, F))] = rng.choice([0, ord("N"), 0x80, 0xFF])
     sc = hipkernel.Scoring.make(*c["scoring"])
-    exp = extend_ref.extend(reads, refs, sc, affine=c["affine"], chunk=64)
+    exp = extend_ref.extend(reads, refs, sc, affine=c["affine"], chunk=64 if R <= 200 else 4)
     eng = hipkernel.Engine(R, F, sc, group_lanes=c["geometry"][0], rows_per_lane=c["geometry"][1])
     try:
+        if c.get("wide"):
+            eng.set_extend_wide(1)
+            eng.set_score_width(c["width"])
         got = eng.score_extend_device(0, torch.from_numpy(reads).cuda(), torch.from_numpy(refs).cuda())
         torch.cuda.synchronize()
+        ran = eng.describe(0, n)["ran_extend"]
+        if ran != ("wide" if c.get("wide") else "rows"):
+            return "score_extend_device ran %s" % ran
         if not np.array_equal(got.cpu().numpy().astype(np.int64), exp):
-            return "score_extend_device differs (%s)" % eng.describe(0, n)["ran_extend"]
+            return "score_extend_device differs (%s)" % ran
         if c["host"]:
             h = eng.score_extend_host(0, reads, refs, threads=c["threads"])
             if not np.array_equal(np.stack([h[k] for k in hipkernel.extend_dtype().names], axis=1).astype(np.int64), exp):

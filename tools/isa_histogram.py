@@ -4,7 +4,8 @@
     python tools/isa_histogram.py --part 5 --kernel 'align_fill_affine_tag_kernelILi16ELi10ELi1ELb1'
 
 compiles versalignlib_amd/csrc/kernel_part.hip (-DVALIGN_PART=n), engine_long.hip (--part main: band / long-read kernels),
-engine_align.hip (--part align: strip / fused / traceback kernels) or engine_placed.hip (--part placed: the int32 placed sweep) for gfx950 with
+engine_align.hip (--part align: strip / fused / traceback kernels), engine_placed.hip (--part placed: the int32 placed sweep) or
+engine_extend.hip (--part extend: the int32 extension sweep) for gfx950 with
 --cuda-device-only -S, finds the largest innermost loop of the first kernel whose mangled name contains --kernel, and
 counts its instructions by issue class; --all-loops prints every innermost loop of that kernel in program order (the fixed
 part of a sweep -- set-up, fill, drain -- sits in the small ones).  Classes follow the measured rates of
@@ -51,10 +52,10 @@ def main():
     asm = a.asm
     if not asm:
         asm = os.path.join(tempfile.gettempdir(), "valign_part_%s.s" % a.part)
-        src = {"main": "engine_long.hip", "align": "engine_align.hip", "placed": "engine_placed.hip"}.get(a.part, "kernel_part.hip")
+        src = {"main": "engine_long.hip", "align": "engine_align.hip", "placed": "engine_placed.hip", "extend": "engine_extend.hip"}.get(a.part, "kernel_part.hip")
         cmd = ["hipcc", "--offload-arch=gfx950", "-std=c++17", "-O3", "--cuda-device-only", "-S", "-I" + os.path.join(ROOT, "include"),
                "-I" + CSRC, os.path.join(CSRC, src), "-o", asm]
-        if a.part not in ("main", "align", "placed"):
+        if a.part not in ("main", "align", "placed", "extend"):
             cmd.insert(5, "-DVALIGN_PART=%s" % a.part)
         subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
     lines = open(asm).read().split("\n")

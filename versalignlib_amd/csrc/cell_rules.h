@@ -286,6 +286,7 @@ struct PlacedFacts {
     bool band_placed = false;       // band_placed = 1: under a band the call runs on the block chain, on the chain's band
     bool chain_usable = false;      // band_chain_plan(...).usable for this band_width (long_plan.h)
     bool placed_wide = false;       // placed_wide = 1: unbanded calls on int32 cells run on the pointer-free int32 sweep
+    bool extend_wide = false;       // extend_wide = 1: extension calls the int16 register sweep refuses run on the int32 strip sweep
 };
 
 struct PlacedChoice {
@@ -449,29 +450,68 @@ inline long long extend_cell_bottom(const RuleInputs &in) {
 }
 inline bool extend_int16_ok(const RuleInputs &in) { return extend_cell_top(in) <= 32000 && extend_cell_bottom(in) >= -32000; }
 
-// An extension call runs on the register sweep's rows track or not at all: refused for the NW variant's mode bit, for
-// traceback_policy = 1, under a band whatever band_placed says, for score_width = 32 whatever placed_wide says, where the cells
-// could leave int16 (above), and for the shapes placed scores would send to the row strips.  Otherwise Rows.
-// `G x K`: the register geometry the call would run on -- every full geometry carries the four gap forms, so the choice
+// extend_wide = 1: the same matrix on signed int32 cells (extend_wide_kernels.hip.h).  Nothing clamps them either, and the gap
+// states of the two borders -- E of the border column, F of the border row -- are the finite sentinel kExtendWideLoses, which a
+// step adds an extension score (<= 0) to like to any other cell: it drifts down, one extension per step.  With
+// B = kExtendWideCellBound the call is legal where every cell and every candidate of a maximum lies in [-B, B]
+// (extend_cell_top / extend_cell_bottom, above) and
+//   * the sentinel plus any single addend -- the largest one a positive substitution score -- stays below -B, so below every real
+//     cell and candidate: a value that derives from the sentinel loses every maximum a real value takes part in;
+//   * the sentinel less (R + F) extensions at the worst price, and one more addend, stays inside int32: a sweep has fewer than
+//     R + F steps, so no drift wraps round to a large value.
+// Both hold for every scoring of int16 scores on shapes of R + F <= 32767 (2^28 > 2^15 and 2^29 + 2^15 x 2^15 + 2^15 < 2^31);
+// they are tested all the same: the rule reads what it is given, not what the engine validates.
+constexpr long long kExtendWideCellBound = 1ll << 28;
+constexpr int kExtendWideLoses = -(1 << 29);
+inline bool extend_int32_ok(const RuleInputs &in) {
+    const Scoring &sc = in.sc;
+    const long long top_addend = std::max({sc.match, sc.mismatch, 0});
+    const long long worst_ext = sc.affine ? std::min({sc.ext_read, sc.ext_ref, 0}) : std::min({sc.gap_read, sc.gap_ref, 0});
+    const long long low_addend = sc.affine ? std::min({sc.match, sc.mismatch, sc.open_read, sc.ext_read, sc.open_ref, sc.ext_ref, 0})
+                                           : std::min({sc.match, sc.mismatch, sc.gap_read, sc.gap_ref, 0});
+    if (extend_cell_top(in) > kExtendWideCellBound || extend_cell_bottom(in) < -kExtendWideCellBound) return false;
+    if (kExtendWideLoses + top_addend >= -kExtendWideCellBound) return false;
+    return kExtendWideLoses + worst_ext * ((long long)in.R + in.F) + low_addend >= -(1ll << 31);
+}
+
+// An extension call runs on the register sweep's rows track or, under extend_wide = 1, on the int32 strip sweep: refused for the NW
+// variant's mode bit, for traceback_policy = 1 and under a band whatever band_placed says -- whatever extend_wide says too.
+// extend_wide = 0: refused as well for score_width = 32 whatever placed_wide says, where the cells could leave int16 (above), and
+// for the shapes placed scores would send to the row strips; otherwise Rows.  extend_wide = 1: Wide exactly where one of those
+// three refusals would stand (the int16 range one under score_width = 0 only: 16 means "int16 or refuse" and stays refused, as for
+// placed scores) -- refused there, with a text of its own, only where extend_int32_ok fails; every other call decides as without
+// the key.  `G x K`: the register geometry the call would run on -- every full geometry carries the four gap forms, so the choice
 // does not depend on it today.
 inline PlacedChoice extend_choice(const RuleInputs &in, int alg, const PlacedFacts &f, int G, int K) {
     PlacedChoice c;
     (void)G;
     (void)K;
+    bool opens_wide = false;            // the refusal is one of the three extend_wide = 1 answers
     if (alg != kAlgSW)
         c.reason = "extension scores are defined for opt & 0xF == 0 only (the NW variant's free reference start is another matrix)";
     else if (in.sse_policy)
         c.reason = "extension scores are not built for traceback_policy = 1 (SSE/AVX tie-breaks)";
     else if (f.band_width > 0)
         c.reason = "extension scores are not built for band_width > 0";
-    else if (f.score_width == 32)
+    else if (f.score_width == 32) {
         c.reason = "extension scores are not built for score_width = 32 (int32 cells)";
-    else if (!extend_int16_ok(in))
+        opens_wide = true;
+    } else if (!extend_int16_ok(in)) {
         c.reason = "extension scores run on signed int16 cells: shape x scoring can leave their range";
-    else if (f.long_plan || (!f.forced && in.R > kPlacedStripRows))
+        opens_wide = f.score_width == 0;
+    } else if (f.long_plan || (!f.forced && in.R > kPlacedStripRows)) {
         c.reason = "extension scores run on the register sweep only: reads of more than 1024 rows and shapes without a register geometry are refused";
-    else
+        opens_wide = true;
+    } else
         c.route = PlacedRoute::Rows;
+    if (opens_wide && f.extend_wide) {
+        if (extend_int32_ok(in)) {
+            c.reason = "";
+            c.route = PlacedRoute::Wide;
+        } else {
+            c.reason = "extend_wide: shape x scoring can leave the range the int32 cells keep below their borders' sentinel";
+        }
+    }
     return c;
 }
 

@@ -19,7 +19,8 @@
 //   engine_subopt.hip ... suboptimal Smith-Waterman scores: the placed sweep's suboptimal form, which also leaves the column
 //                         maxima in a scratch, and subopt_records_kernel (subopt_kernels.hip.h); record_pipeline again
 //   engine_extend.hip ... extension scores: the anchored score, its end cell and the read-end score from one sweep with gap-priced
-//                         borders and no floor (extend_kernels.hip.h); record_pipeline again
+//                         borders and no floor (extend_kernels.hip.h) or, under extend_wide = 1, from score_placed_strips with the
+//                         int32 extension sweep (extend_wide_kernels.hip.h); record_pipeline again
 //   engine_cigar.hip .... the compact result format: records + CIGAR ops encoded on the device behind the walks (cigar_kernels.hip.h)
 //   engine_span_cigar.hip spanned CIGARs: the alignment of the span from the span's window -- the forward placed sweep, the
 //                         reversal, the child engine's ALIGNMENT of the reversed prefixes and the backward encoder
@@ -272,6 +273,14 @@ public:
         placed_wide_ = on == 1;
     }
     int placed_wide() const { return placed_wide_ ? 1 : 0; }
+    // Extension scores on int32 cells and row strips (opt-in; include/valign_hip.h has the definition): 1 = extension calls that
+    // score_width = 32, the int16 range rule or the read length would refuse run on the int32 extension sweep
+    // (extend_wide_kernels.hip.h); 0 = they are refused (default).  Calls the register sweep serves keep it.
+    void set_extend_wide(int on) {
+        if (on != 0 && on != 1) throw std::runtime_error("extend_wide must be 0 or 1");
+        extend_wide_ = on == 1;
+    }
+    int extend_wide() const { return extend_wide_ ? 1 : 0; }
     // Checkpointed traceback of long-read alignments (opt-in; ckpt_plan.h): 1 = calls that take the plain row strips (unbanded,
     // int16 cells, traceback_policy 0; both algorithms, linear and affine gaps) keep one boundary row per strip and ONE strip's
     // pointer region instead of every pointer, and re-fill strip after strip along the walk -- identical results, a scratch that
@@ -599,20 +608,32 @@ private:
         a.band = plan.band;
         return a;
     }
-    // The pointer-free strip sweep of PlacedRoute::Strip and PlacedRoute::Wide: what differs between the two is this description.
+    // The pointer-free strip sweep of PlacedRoute::Strip and PlacedRoute::Wide, of placed and of extension scores: what differs
+    // between them is this description.
     struct PlacedSweep {
+        // a step of a chunk outside its strips: `a` = the chunk's StripArgs of strip 0 (sequences, count, scratch pointers),
+        // `begin` = the chunk's first pair of the call
+        using ChunkStep = std::function<void(const StripArgs &a, long long begin, hipStream_t stream)>;
         const void *fn;             // the strip kernel
         WaveLds lds;
         StripPlan plan;
         bool first_bad;             // the kernel takes a first-invalid table (int16 strips: zeros, read by the NW variant only)
-        bool wide_records;          // placed_wide_records_kernel closes a chunk, else placed_records_kernel
         const char *rows_label, *what;      // names of the boundary-row allocation and of the launch, in errors
+        ChunkStep close;            // after the strips: the merged per-pair scratch -> the call's records (placed scores: one of the two record kernels)
+        size_t pair_bytes = sizeof(EndCell);        // the merged per-pair scratch behind StripArgs.ends: an EndCell, or ...
+        // ... extension scores: a partial record and the trimmed lengths, which `bind` points StripArgs.ptr / .first_bad at (`pairs`:
+        // those the scratch is sized for) and `open` fills before the chunk's first strip
+        std::function<void(StripArgs &a, long long pairs)> bind;
+        ChunkStep open;
     };
-    PlacedSweep placed_strip_sweep() const;         // int16 cells: the forward pass of the checkpointed traceback (engine_align.hip)
-    PlacedSweep placed_wide_sweep() const;          // placed_wide = 1: the int32 sweep, 8 rows per lane (engine_placed.hip)
-    // Chunk after chunk of what the scratch cap holds: strip after strip through two boundary row sets that ping-pong, the end
-    // cell merged on the way, then one record per end cell.  The scratch is the engine's, shared by both descriptions.
-    void score_placed_strips(const PlacedSweep &sweep, long long n, const uint8_t *d_reads, const uint8_t *d_refs, PlacedRec *d_placed, hipStream_t stream);
+    PlacedSweep placed_strip_sweep(PlacedRec *d_placed) const;        // int16 cells: the forward pass of the checkpointed traceback (engine_align.hip)
+    PlacedSweep placed_wide_sweep(PlacedRec *d_placed) const;         // placed_wide = 1: the int32 sweep, 8 rows per lane (engine_placed.hip)
+    // what closes a chunk of placed scores: placed_records_kernel, or placed_wide_records_kernel (wide), into d_placed (engine_placed.hip)
+    PlacedSweep::ChunkStep placed_records_step(PlacedRec *d_placed, bool wide) const;
+    PlacedSweep extend_wide_sweep(ExtendRec *d_extend) const;         // extend_wide = 1: the int32 extension sweep, 8 rows per lane (engine_extend.hip)
+    // Chunk after chunk of what the scratch cap holds: strip after strip through two boundary row sets that ping-pong, the per-pair
+    // scratch merged on the way, then the description's records.  The scratch is the engine's, shared by every description.
+    void score_placed_strips(const PlacedSweep &sweep, long long n, const uint8_t *d_reads, const uint8_t *d_refs, hipStream_t stream);
     // a block of more than the default LDS: the kernel's attribute first
     static void raise_block_lds(const void *fn, int bytes) {
         if (bytes > kDefaultBlockLds)
@@ -781,7 +802,8 @@ private:
 
     // ---- extension scores (engine_extend.hip) ----
     // refusals (thrown), then the plan: the base plan where its geometry carries the kernel, else the next full geometry
-    const LaunchPlan &extend_plan_for(int alg, int &gaps);
+    // (route Wide: the base plan, which nothing launches on)
+    const LaunchPlan &extend_plan_for(int alg, int &gaps, PlacedRoute &route);
 
     // ---- length-sorted batching (score_host, Smith-Waterman) ----
 
@@ -865,6 +887,7 @@ private:
     bool band_nw_ = false;
     bool band_placed_ = false;
     bool placed_wide_ = false;
+    bool extend_wide_ = false;
     bool trace_checkpoints_ = false;
     int score_width_ = 0;
     int ragged_ = 0, force_g_ = 0, force_k_ = 0;
@@ -935,7 +958,7 @@ private:
     const char *ran_subopt_ = "none";                    // what the last suboptimal call ran: key / rows (describe)
     int subopt_ring_cols_ = 0;                           // ... and the columns of a lane group's ring in its sweep
     size_t subopt_scratch_bytes_ = (size_t)dbg_.value("subopt_scratch_bytes", 256ll << 20);      // column maxima of one chunk
-    const char *ran_extend_ = "none";                    // what the last extension call ran: rows (describe)
+    const char *ran_extend_ = "none";                    // what the last extension call ran: rows, wide (describe)
     const char *ran_result_format_ = "rows";             // of the last alignment call: rows / cigar (describe)
     long long cigar_d2h_bytes_ = 0;                      // what the last align_cigar_host call copied back
     const CigarSink *cigar_ = nullptr;

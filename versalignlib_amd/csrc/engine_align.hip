@@ -350,13 +350,13 @@ void Engine::align_strips_device(const StripMode &mode, long long n, const uint8
 
 // Placed scores of reads that take the row strips (Engine::score_placed_strips, engine_placed.hip): the forward pass of the
 // checkpointed traceback at the K the strip rule picks, with a first-invalid table (zeros: read by the NW variant only).
-Engine::PlacedSweep Engine::placed_strip_sweep() const {
+Engine::PlacedSweep Engine::placed_strip_sweep(PlacedRec *d_placed) const {
     const StripMode mode{kAlgSW, sc_.affine, false, false, false, true};
     const int K = strip_rows_per_lane(R_, mode, strip_k_);
     if (!K) throw std::runtime_error("no strip kernel for placed scores");
     const StripGeometry &geo = *std::find_if(std::begin(kStripGeometries), std::end(kStripGeometries), [&](const StripGeometry &g) { return g.K == K; });
-    return PlacedSweep{geo.kernel(mode, 0), geo.lds, strip_plan(R_, F_, K, mode, kNoBand), true, false, "placed-score boundary rows",
-                       "hipLaunchKernel(align_strip_kernel, placed scores)"};
+    return PlacedSweep{geo.kernel(mode, 0), geo.lds, strip_plan(R_, F_, K, mode, kNoBand), true, "placed-score boundary rows",
+                       "hipLaunchKernel(align_strip_kernel, placed scores)", placed_records_step(d_placed, false)};
 }
 
 template <typename Sink>

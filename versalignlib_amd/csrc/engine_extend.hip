@@ -1,21 +1,28 @@
 // engine_extend.hip -- Engine: extension scores (include/valign_hip.h: valign_hip_score_extend_*): per pair the best score of an
 // alignment that starts at the anchor, before read[0] and ref[0], the cell it ends in, and the best score that consumes the read
-// to its last base.  extend_choice (cell_rules.h) decides what is refused; this unit launches score_extend_kernel
-// (extend_kernels.hip.h: the rows track's sweep with gap-priced borders and no floor), which writes the records itself -- no
-// scratch, one launch per call.  The host-pointer path is record_pipeline (engine_score.hip) with 20-byte records on the way back.
+// to its last base.  extend_choice (cell_rules.h) decides what is refused and which route runs; this unit launches
+// score_extend_kernel (extend_kernels.hip.h: the rows track's sweep with gap-priced borders and no floor), which writes the records
+// itself -- no scratch, one launch per call -- or, where the rule answers Wide (extend_wide = 1), hands score_placed_strips
+// (engine_placed.hip) the description of the int32 extension sweep (extend_wide_kernels.hip.h): a length pre-pass per chunk, one
+// launch per strip, a record kernel.  The host-pointer path is record_pipeline (engine_score.hip), 20-byte records on the way back.
+// extend_wide_lengths_kernel and extend_wide_records_kernel (not templates) are defined in this translation unit.
+#define VALIGN_TU_EXTEND 1
 #include "engine.hip.h"
+#include "extend_wide_kernels.hip.h"
 
 namespace valign {
 
 // The plan of an extension call: the one alignments start from where its geometry carries the kernel, otherwise the cheapest
 // full geometry that fits the read.  Throws what the rule refuses.
-const LaunchPlan &Engine::extend_plan_for(int alg, int &gaps) {
+const LaunchPlan &Engine::extend_plan_for(int alg, int &gaps, PlacedRoute &route) {
     const LaunchPlan &base = align_base_plan();
     const PlacedFacts facts = placed_facts();
     RuleInputs in = rule_inputs();
     in.no_f16 = true;                   // int16 cells: the gap form is one of the four integer ones
     const PlacedChoice choice = extend_choice(in, alg, facts, base.geo ? base.geo->G : 0, base.geo ? base.geo->K : 0);
     if (choice.route == PlacedRoute::Refused) throw std::runtime_error(choice.reason);
+    route = choice.route;
+    if (route == PlacedRoute::Wide) return base;        // (nothing launches on the plan)
     gaps = score_gap_form(in, kAlgSW, R_, F_, base.geo->G * base.geo->K);
     if (base.geo->extend(gaps)) return base;
     if (!fallback_plan_.geo) fallback_plan_ = choose_plan(R_, F_, 0, 0, false, true);
@@ -29,8 +36,14 @@ void Engine::score_extend_device(int opt, long long n, const uint8_t *d_reads, c
     ran_extend_ = "none";
     ran_extend_geo_ = nullptr;
     int gaps = 0;
-    const LaunchPlan &plan = extend_plan_for(alg, gaps);
+    PlacedRoute route = PlacedRoute::Refused;
+    const LaunchPlan &plan = extend_plan_for(alg, gaps, route);
     hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (route == PlacedRoute::Wide) {
+        score_placed_strips(extend_wide_sweep(d_extend), n, d_reads, d_refs, stream);
+        ran_extend_ = ran_placed_name(route);
+        return;
+    }
     ExtendArgs a{};
     a.reads = d_reads;
     a.refs = d_refs;
@@ -53,6 +66,33 @@ void Engine::score_extend_device(int opt, long long n, const uint8_t *d_reads, c
     ran_extend_ = ran_placed_name(PlacedRoute::Rows);
 }
 
+// extend_wide = 1: the int32 extension sweep.  8 rows per lane; the wide plan's row sets (an int32 row per pair, and an F row
+// beside it, affine) -- its padding rows are counted above the read, the kernel puts them below: the strips, the row sets and their
+// sizes are the same either way.  The per-pair scratch is the partial record and, behind the records of every pair the scratch
+// holds, the two trimmed lengths.
+Engine::PlacedSweep Engine::extend_wide_sweep(ExtendRec *d_extend) const {
+    constexpr int K = kExtendWideK;
+    const void *fn = sc_.affine ? (const void *)&score_extend_wide_kernel<K, true> : (const void *)&score_extend_wide_kernel<K, false>;
+    PlacedSweep sweep{fn, WaveLds{StripLds<K>::kRing, 0, StripLds<K>::kTotal}, strip_plan(R_, F_, K, StripMode{kAlgSW, sc_.affine, false, true, false, false}, kNoBand),
+                      false, "extension-score boundary rows (int32)", "hipLaunchKernel(score_extend_wide_kernel)"};
+    sweep.pair_bytes = sizeof(ExtendRec) + 2 * sizeof(int);
+    sweep.bind = [](StripArgs &a, long long pairs) {
+        a.ptr = reinterpret_cast<unsigned *>(a.ends);
+        a.first_bad = reinterpret_cast<const int *>(a.ptr + (size_t)kExtendWideRecDwords * pairs);
+        a.ends = nullptr;
+    };
+    const int R = R_, F = F_;
+    sweep.open = [R, F](const StripArgs &a, long long, hipStream_t stream) {
+        hipLaunchKernelGGL(extend_wide_lengths_kernel, dim3((unsigned)a.n), dim3(kWave), 0, stream, a.reads, a.refs, a.n, R, F, const_cast<int *>(a.first_bad));
+        hip_check(hipGetLastError(), "hipLaunchKernel(extend_wide_lengths_kernel)");
+    };
+    sweep.close = [d_extend](const StripArgs &a, long long begin, hipStream_t stream) {
+        hipLaunchKernelGGL(extend_wide_records_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, stream, (const int *)a.ptr, a.first_bad, d_extend + begin, a.n);
+        hip_check(hipGetLastError(), "hipLaunchKernel(extend_wide_records_kernel)");
+    };
+    return sweep;
+}
+
 // Host pointers in, host records out: record_pipeline, 20 bytes per pair on the way back.
 void Engine::score_extend_host(int opt, int n, const char *const *reads, const char *const *refs, ExtendRec *extend, int threads) {
     const int alg = opt & 0xF;
@@ -61,8 +101,10 @@ void Engine::score_extend_host(int opt, int n, const char *const *reads, const c
     ran_extend_ = "none";
     ran_extend_geo_ = nullptr;
     int gaps = 0;
-    (void)extend_plan_for(alg, gaps);          // (refusals leave here, before anything is staged)
-    record_pipeline(n, reads, refs, extend, RecordKind{sizeof(ExtendRec), "extension records", "D2H extension records"}, host_chunk_pairs(false, n), false, threads,
+    PlacedRoute route = PlacedRoute::Refused;
+    (void)extend_plan_for(alg, gaps, route);          // (refusals leave here, before anything is staged)
+    const bool strips = route == PlacedRoute::Wide;      // the strips' launches share the boundary rows: one stream, large chunks
+    record_pipeline(n, reads, refs, extend, RecordKind{sizeof(ExtendRec), "extension records", "D2H extension records"}, host_chunk_pairs(strips, n), strips, threads,
                     [&](int, long long cnt, const uint8_t *d_reads, const uint8_t *d_refs, uint8_t *d_records, hipStream_t stream) {
                         score_extend_device(opt, cnt, d_reads, d_refs, (ExtendRec *)d_records, stream);
                     });

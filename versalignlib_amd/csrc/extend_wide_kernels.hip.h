@@ -1,0 +1,322 @@
+// extend_wide_kernels.hip.h -- extension scores on int32 cells and row strips (key extend_wide; include/valign_hip.h): the anchored
+// score, its end cell and the read-end score (extend_kernels.hip.h has the matrix, tests/extend_ref.py restates it) for the calls
+// the packed int16 register sweep refuses -- score_width = 32, cells that can leave int16, reads of more than 1 024 rows.
+//
+// score_extend_wide_kernel is score_placed_wide_kernel (placed_wide_kernels.hip.h) on the extension's matrix.  Kept: one wave per
+// pair-of-pairs and one launch per strip of 64 K rows, both int32 chains of a lane in ONE pass, the profile of the strip's rows and
+// the ring of slab numbers in LDS (strip_ring_setup, fetch_profile), the wave_shr hand-over of h_last / f_last, the boundary row
+// sets that ping-pong from strip to strip (StripArgs.top / .bottom, the layout of score_placed_wide_kernel), a first arg-max per
+// row and the reduction value -> smallest row -> that row's first column.  What differs is the matrix:
+//   * no floor: plain signed adds of the gap scores (all <= 0) and signed maxima; extend_int32_ok (cell_rules.h) vouches for the
+//     range and for the sentinel kExtendWideLoses that stands for the gap states of the two borders.
+//   * the read sits TOP-aligned: strip s holds the read positions [s * 64 K, (s + 1) * 64 K), the padding rows lie below the
+//     read in the last strip.  A padding row above row 0 could not reproduce a gap-priced border row; below the read nothing
+//     reads one, and strip_ring_setup scores rows at or beyond R as 0.  (A padding row's border value is that of row R - 1.)
+//   * the border column X(i, -1) = open_ref + i ext_ref (linear: (i + 1) gap_ref) in closed form, in every strip: each row's Hl
+//     (the LEFT and DIAG input of column 0), up0 of the lane's first row (X(-1, -1) = 0 above row 0 of strip 0), h_last (what the
+//     lane behind receives while this lane has not started), and the row's running best rb with fc = the step at which the lane
+//     would sweep column -1 -- so that the border column is candidate 0 of the read-end score.  E starts at the sentinel.
+//   * the border row X(-1, j) = open_read + j ext_read in strip 0: lane 0's `above` of step t, wave-uniform -- one running add on
+//     the scalar unit -- with the sentinel as its F; later strips read the boundary rows as the placed sweep does.
+//   * trimmed lengths Rp, Fp (1 + the position of the last ACGT byte) per pair, wave-uniform, from extend_wide_lengths_kernel,
+//     which runs once per chunk: a row tracks column j only while j < Fp of ITS pair.  Columns at or beyond the larger Fp of the
+//     wave are candidates of nothing and feed no candidate: the sweep ends there; a strip wholly below both reads' Rp returns.
+//   * records across strips: a partial record per pair (five dwords, StripArgs.ptr) -- score / read_end / ref_end merged strip
+//     after strip, a later strip winning only with a strictly larger value (the row-major first maximum, as EndCell is merged by
+//     score_placed_wide_kernel), gscore / gref_end written by the strip and lane that hold row Rp - 1 from that row's rb / fc.
+//     extend_wide_records_kernel copies them out and applies the definition's last empty case, Rp = 0: five zeros (score <= 0:
+//     three zeros is what the merge leaves).  Values and coordinates are int32 from the cell to the record: nothing saturates.
+// A short read fills a fraction of its one 512-row strip (as on the placed int32 sweep): the int16 register sweep is the route for
+// those wherever the rule lets it run.  Z-drop, a band around the anchor's diagonal and an end bonus are not built.
+#pragma once
+
+#include "extend_kernels.hip.h"
+#include "strip_kernels.hip.h"
+
+namespace valign {
+
+constexpr int kExtendWideK = 8;                 // rows per lane: the K of the placed int32 sweep
+constexpr int kExtendWideRecDwords = 5;         // a partial record: ExtendRec's five ints
+static_assert(sizeof(ExtendRec) == 4 * kExtendWideRecDwords, "the partial record is an ExtendRec");
+
+// StripArgs of this sweep: ptr = the partial records (n x 5 dwords), first_bad = the trimmed lengths (n x 2: Rp, Fp); ends unused.
+template <int K, bool AFFINE>
+__global__ void __launch_bounds__(64)
+score_extend_wide_kernel(const StripArgs args) {
+    constexpr int G = 64;
+    constexpr int kSets = AFFINE ? 2 : 1;                 // boundary row sets per pair
+    constexpr int kLoses = kExtendWideLoses;
+    using geo = Geo<G, K>;
+    const int lane = threadIdx.x;
+    const int l = lane;
+    const int R = args.R;
+    const int row0 = args.strip * geo::kRows;             // top-aligned: the read position of the strip's first row
+
+    // ---- trimmed lengths of the wave's two pairs (wave-uniform) ----
+    const long long first_pair = (long long)blockIdx.x * geo::kPairs;
+    if (first_pair >= args.n) return;
+    int Rp[2], Fp[2];
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const long long pair = first_pair + half < args.n ? first_pair + half : first_pair;
+        Rp[half] = __builtin_amdgcn_readfirstlane(args.first_bad[2 * pair]);
+        Fp[half] = __builtin_amdgcn_readfirstlane(args.first_bad[2 * pair + 1]);
+    }
+    // rows at or beyond Rp are no candidates and nothing above them reads them: strip 0 always runs (it starts the records)
+    if (args.strip > 0 && (Rp[0] > Rp[1] ? Rp[0] : Rp[1]) <= row0) return;
+    // columns at or beyond the larger Fp: tracked by neither pair, read by no column before them
+    const int F = Fp[0] > Fp[1] ? Fp[0] : Fp[1];
+
+    WaveTables w;
+    if (!strip_ring_setup<K>(args.reads, args.n, R, F, args.match, args.mismatch, row0, w)) return;
+    const unsigned lane_base = lds_offset(w.prof) + l * geo::kLaneBytes;
+    const unsigned ring_base = lds_offset(w.refc);
+    const uint8_t *ref_a = args.refs + w.pair0 * args.F, *ref_b = args.refs + (w.pair0 + (w.last >= 1 ? 1 : 0)) * args.F;
+    // the scores themselves, all <= 0: added
+    const int g_read = args.gap_read, g_ref = args.gap_ref;
+    const int o_read = args.open_read, e_read = args.ext_read;
+    const int o_ref = args.open_ref, e_ref = args.ext_ref;
+    auto max2 = [](int a, int b) __attribute__((always_inline)) { return a > b ? a : b; };
+    // X(i, -1): a gap of i + 1 read bases against nothing; X(-1, -1) = 0; padding rows as row R - 1
+    auto border_col = [&](int row) __attribute__((always_inline)) -> int {
+        const int i = row < R ? row : R - 1;
+        if (i < 0) return 0;
+        return AFFINE ? o_ref + i * e_ref : (i + 1) * g_ref;
+    };
+    const long long pp = w.pair0 / 2;
+    const size_t set_dwords = (size_t)(args.top_f - args.top);
+    const bool has_top = args.strip > 0, has_bottom = args.strip + 1 < args.strips;
+    const int steps = F + G - 1;
+    const int row_dwords = args.row_dwords;
+    const unsigned *top[2], *top_f[2];
+    unsigned *bottom[2], *bottom_f[2];
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        top[half] = args.top + (size_t)(kSets * half) * set_dwords + pp * row_dwords;
+        bottom[half] = args.bottom + (size_t)(kSets * half) * set_dwords + pp * row_dwords;
+        top_f[half] = top[half] + set_dwords;             // (affine only)
+        bottom_f[half] = bottom[half] + set_dwords;
+    }
+
+    int Hl[2][K], El[2][AFFINE ? K : 1];
+    int rb[2][K], fc[2][K];                               // per row: the best value and the step of its first occurrence
+    int h_last[2], f_last[2], up0[2];
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+            Hl[half][q] = border_col(row0 + l * K + q);
+            if (AFFINE) El[half][q] = kLoses;
+            rb[half][q] = Hl[half][q];                    // the row's best so far: column -1 ...
+            fc[half][q] = l - 1;                          // ... which this lane would sweep at step l - 1
+        }
+        up0[half] = border_col(row0 + l * K - 1);
+        h_last[half] = border_col(row0 + l * K + K - 1);
+        f_last[half] = kLoses;
+    }
+    unsigned top_cur[2] = {0u, 0u}, top_next[2], topf_cur[2] = {0u, 0u}, topf_next[2] = {0u, 0u};
+    unsigned bot_acc[2] = {0u, 0u}, botf_acc[2] = {0u, 0u};
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        top_next[half] = has_top ? top[half][lane] : 0u;
+        if (AFFINE) topf_next[half] = has_top ? top_f[half][lane] : 0u;
+    }
+    // the border row of strip 0: X(-1, t) and what a step adds to it (wave-uniform)
+    int lead = AFFINE ? o_read : g_read;
+    const int lead_step = AFFINE ? e_read : g_read;
+    int j = -l;
+    unsigned code_addr = ring_base | ((unsigned)(-2 * l) & (2u * kStripRingCols - 1u));
+    StripRefBytes ref_raw = strip_ring_request(ref_a, ref_b, lane, F);     // columns [0, 64)
+
+    for (int t = 0; t < steps; ++t) {
+        if ((t & 63) == 0) {
+            const bool more = has_top && t + 64 + lane < row_dwords;
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                top_cur[half] = top_next[half];
+                top_next[half] = more ? top[half][t + 64 + lane] : 0u;
+                if (AFFINE) {
+                    topf_cur[half] = topf_next[half];
+                    topf_next[half] = more ? top_f[half][t + 64 + lane] : 0u;
+                }
+            }
+            strip_ring_commit<K>(w.refc, t + lane, F, ref_raw);
+            ref_raw = strip_ring_request(ref_a, ref_b, t + 64 + lane, F);
+        }
+        int diag0[2], fup0[2] = {0, 0};
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            diag0[half] = up0[half];
+            // every lane takes part in the DPP move, before the select on the lane's column
+            const int above = has_top ? __builtin_amdgcn_readlane((int)top_cur[half], t & 63) : lead;
+            int from_lane = __builtin_amdgcn_update_dpp(0, h_last[half], 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
+            asm volatile("" : "+v"(from_lane));
+            up0[half] = l == 0 ? above : from_lane;
+            if (AFFINE) {
+                const int above_f = has_top ? __builtin_amdgcn_readlane((int)topf_cur[half], t & 63) : kLoses;
+                int f_lane = __builtin_amdgcn_update_dpp(0, f_last[half], 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
+                asm volatile("" : "+v"(f_lane));
+                fup0[half] = l == 0 ? above_f : f_lane;
+            }
+        }
+        lead += lead_step;
+        if ((unsigned)j < (unsigned)F) {
+            const unsigned ca = *(lds_cu8 *)(code_addr), cb = *(lds_cu8 *)(code_addr + 1);
+            s16x2 S[K];
+            fetch_profile<G, K>(lane_base + ca * geo::kPairStride, lane_base + cb * geo::kPairStride, S);
+            const bool in_cols[2] = {j < Fp[0], j < Fp[1]};       // the column is one of the pair's own
+            int h[2] = {up0[0], up0[1]}, f[2] = {fup0[0], fup0[1]};
+            int d_cur[2] = {diag0[0] + (int)S[0].x, diag0[1] + (int)S[0].y};
+#pragma unroll
+            for (int q = 0; q < K; ++q) {
+#pragma unroll
+                for (int half = 0; half < 2; ++half) {             // two independent chains: pair A, pair B
+                    int d_next = 0;
+                    if (q + 1 < K) d_next = Hl[half][q] + (int)(half ? S[q + 1].y : S[q + 1].x);      // before Hl[q] is overwritten
+                    int m;
+                    if constexpr (AFFINE) {
+                        const int e = max2(El[half][q] + e_read, Hl[half][q] + o_read);
+                        El[half][q] = e;
+                        f[half] = max2(f[half] + e_ref, h[half] + o_ref);
+                        m = max2(max2(d_cur[half], e), f[half]);
+                    } else {
+                        m = max2(d_cur[half], max2(Hl[half][q] + g_read, h[half] + g_ref));
+                    }
+                    h[half] = m;
+                    Hl[half][q] = m;
+                    d_cur[half] = d_next;
+                    if (m > rb[half][q] && in_cols[half]) {        // strictly greater: the first arg-max of the row wins
+                        rb[half][q] = m;
+                        fc[half][q] = t;
+                    }
+                }
+            }
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                h_last[half] = h[half];
+                f_last[half] = f[half];
+            }
+        }
+        if (has_bottom) {
+            const int col = t - (G - 1);
+            if (col >= 0) {
+                const bool mine = lane == (col & 63), flush = (col & 63) == 63 || t == steps - 1;
+#pragma unroll
+                for (int half = 0; half < 2; ++half) {
+                    const int v = __builtin_amdgcn_readlane(h_last[half], G - 1);
+                    bot_acc[half] = mine ? (unsigned)v : bot_acc[half];
+                    if (flush) bottom[half][(col & ~63) + lane] = bot_acc[half];
+                    if (AFFINE) {
+                        const int vf = __builtin_amdgcn_readlane(f_last[half], G - 1);
+                        botf_acc[half] = mine ? (unsigned)vf : botf_acc[half];
+                        if (flush) bottom_f[half][(col & ~63) + lane] = botf_acc[half];
+                    }
+                }
+            }
+        }
+        ++j;
+        code_addr = ((code_addr + 2u) & (2u * kStripRingCols - 1u)) | ring_base;
+    }
+
+    // ---- the partial records.  Anchored score: the largest value > 0, then the smallest row, then the row's first column; over
+    // the strips, a later one only wins with a larger value.  Read-end score: row Rp - 1's own entry, the border column included ----
+    int *partial = reinterpret_cast<int *>(args.ptr);
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const long long pair = w.pair0 + half;
+        int bv = 0, bq = 0, bcol = 0;
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+            if (rb[half][q] > bv) {
+                bv = rb[half][q];
+                bq = q;
+                bcol = fc[half][q];
+            }
+        }
+        int vmax = bv;
+#pragma unroll
+        for (int dd = G / 2; dd >= 1; dd >>= 1) {
+            const int other = __shfl_xor(vmax, dd, kWave);
+            vmax = other > vmax ? other : vmax;
+        }
+        int p = bv == vmax ? l * K + bq : 0x7FFFFFFF;
+#pragma unroll
+        for (int dd = G / 2; dd >= 1; dd >>= 1) {
+            const int other = __shfl_xor(p, dd, kWave);
+            p = other < p ? other : p;
+        }
+        const int win_lane = p / K;
+        const int col_t = __shfl(bcol, win_lane, kWave);
+        if (pair >= args.n) continue;
+        int *rec = partial + kExtendWideRecDwords * pair;
+        if (l == 0) {
+            const bool hit = vmax > 0;
+            if (args.strip == 0 || vmax > rec[0]) {       // (rec[0] >= 0 once strip 0 has run)
+                rec[0] = hit ? vmax : 0;
+                rec[1] = hit ? row0 + p + 1 : 0;          // half-open ends
+                rec[2] = hit ? col_t - win_lane + 1 : 0;
+            }
+        }
+        const int last_row = Rp[half] - 1 - row0;         // row Rp - 1, counted from the strip's first
+        if (last_row >= 0 && last_row < geo::kRows && last_row / K == l) {
+            int gs = 0, gt = 0;
+#pragma unroll
+            for (int q = 0; q < K; ++q) {
+                if (q == last_row % K) {
+                    gs = rb[half][q];
+                    gt = fc[half][q];
+                }
+            }
+            rec[3] = gs;
+            rec[4] = gt - l + 1;                          // step -> column, half-open: the border column is 0
+        }
+    }
+}
+
+#ifdef VALIGN_TU_EXTEND      // not templates: defined once, in engine_extend.hip
+// Trimmed lengths of a chunk's pairs, one wave per pair: lens[2 * pair] = Rp, lens[2 * pair + 1] = Fp -- 1 + the position of the
+// last ACGT byte (either case), 0 where there is none.
+__global__ void __launch_bounds__(64)
+extend_wide_lengths_kernel(const uint8_t *reads, const uint8_t *refs, long long n, int R, int F, int *lens) {
+    const long long pair = blockIdx.x;
+    if (pair >= n) return;
+    const int lane = threadIdx.x;
+    int rlen = 0, flen = 0;
+    for (int i = lane; i < R; i += kWave) {
+        const int c = base_class(reads[pair * R + i]);
+        if (c >= 1 && c <= 4) rlen = i + 1;
+    }
+    for (int jj = lane; jj < F; jj += kWave) {
+        const int c = base_class(refs[pair * F + jj]);
+        if (c >= 1 && c <= 4) flen = jj + 1;
+    }
+#pragma unroll
+    for (int d = kWave / 2; d >= 1; d >>= 1) {
+        const int other_r = __shfl_xor(rlen, d, kWave), other_f = __shfl_xor(flen, d, kWave);
+        rlen = other_r > rlen ? other_r : rlen;
+        flen = other_f > flen ? other_f : flen;
+    }
+    if (lane == 0) {
+        lens[2 * pair] = rlen;
+        lens[2 * pair + 1] = flen;
+    }
+}
+
+// The merged partial records -> the call's records; a read without an ACGT byte is five zeros (no strip wrote its read-end score)
+__global__ void __launch_bounds__(256)
+extend_wide_records_kernel(const int *partial, const int *lens, ExtendRec *extend, long long n) {
+    const long long pair = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (pair >= n) return;
+    const int *rec = partial + kExtendWideRecDwords * pair;
+    const bool empty = lens[2 * pair] == 0;
+    ExtendRec r;
+    r.score = empty ? 0 : rec[0];
+    r.read_end = empty ? 0 : rec[1];
+    r.ref_end = empty ? 0 : rec[2];
+    r.gscore = empty ? 0 : rec[3];
+    r.gref_end = empty ? 0 : rec[4];
+    extend[pair] = r;
+}
+#endif
+
+}  // namespace valign

@@ -88,6 +88,7 @@ def lib():
         L.valign_hip_set_band_nw.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_band_placed.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_placed_wide.argtypes = [vp, ctypes.c_int]
+        L.valign_hip_set_extend_wide.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_trace_checkpoints.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_pointer_scratch_cap_mb.argtypes = [vp, ctypes.c_longlong]
         L.valign_hip_set_host_packing.argtypes = [vp, ctypes.c_int]
@@ -124,7 +125,7 @@ def lib():
 EXPORTED_SYMBOLS = (
     "spawn_alignment_kernel", "set_parameters", "set_logger", "delete_alignment_kernel",
     "valign_hip_device_count", "valign_hip_shard_range", "valign_hip_engine_create", "valign_hip_engine_destroy",
-    "valign_hip_set_traceback_policy", "valign_hip_set_pointer_scratch_cap_mb", "valign_hip_set_host_packing", "valign_hip_set_half_float_cells", "valign_hip_host_register", "valign_hip_host_unregister", "valign_hip_set_band_width", "valign_hip_set_band_alignments", "valign_hip_set_band_nw", "valign_hip_set_band_placed", "valign_hip_set_placed_wide", "valign_hip_set_trace_checkpoints", "valign_hip_set_score_width", "valign_hip_set_ragged_batching", "valign_hip_score_device", "valign_hip_align_device", "valign_hip_score_host", "valign_hip_align_host", "valign_hip_align_cigar_device", "valign_hip_align_cigar_host", "valign_hip_score_placed_device", "valign_hip_score_placed_host", "valign_hip_score_span_device", "valign_hip_score_span_host", "valign_hip_align_span_device", "valign_hip_align_span_host", "valign_hip_score_subopt_device", "valign_hip_score_subopt_host", "valign_hip_score_extend_device", "valign_hip_score_extend_host", "valign_hip_describe",
+    "valign_hip_set_traceback_policy", "valign_hip_set_pointer_scratch_cap_mb", "valign_hip_set_host_packing", "valign_hip_set_half_float_cells", "valign_hip_host_register", "valign_hip_host_unregister", "valign_hip_set_band_width", "valign_hip_set_band_alignments", "valign_hip_set_band_nw", "valign_hip_set_band_placed", "valign_hip_set_placed_wide", "valign_hip_set_extend_wide", "valign_hip_set_trace_checkpoints", "valign_hip_set_score_width", "valign_hip_set_ragged_batching", "valign_hip_score_device", "valign_hip_align_device", "valign_hip_score_host", "valign_hip_align_host", "valign_hip_align_cigar_device", "valign_hip_align_cigar_host", "valign_hip_score_placed_device", "valign_hip_score_placed_host", "valign_hip_score_span_device", "valign_hip_score_span_host", "valign_hip_align_span_device", "valign_hip_align_span_host", "valign_hip_score_subopt_device", "valign_hip_score_subopt_host", "valign_hip_score_extend_device", "valign_hip_score_extend_host", "valign_hip_describe",
     "valign_hip_last_error",
 )
 
@@ -254,6 +255,14 @@ class Engine:
         include/valign_hip.h has the definition); 0 (default): such calls are refused.  Calls inside the int16 range run as
         ever; not read under a band."""
         if lib().valign_hip_set_placed_wide(self._h, int(on)) != 0:
+            raise HipKernelError(_err())
+
+    def set_extend_wide(self, on):
+        """1: Smith-Waterman-mode score_extend_* calls the int16 register sweep refuses -- score_width = 32, cells that can leave
+        int16 under score_width = 0, reads of more than 1024 rows or without a register geometry -- run on the int32 extension sweep
+        over 512-row strips (describe: ran_extend "wide"; nothing saturates; include/valign_hip.h has the definition); 0 (default):
+        such calls are refused.  Calls the register sweep serves run on it as ever; bands stay refused."""
+        if lib().valign_hip_set_extend_wide(self._h, int(on)) != 0:
             raise HipKernelError(_err())
 
     def set_trace_checkpoints(self, on):
