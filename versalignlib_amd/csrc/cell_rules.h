@@ -23,6 +23,7 @@ struct RuleInputs {
     bool no_max3 = false;           // debug switch: int16 symmetric affine SW scores on the gap-source form always
     bool no_tilt = false;           // debug switch: ... and its biased form in the plain frame always
     bool no_row_tables = false;     // debug switch: ... and its tilted frame on the LDS profile always
+    bool no_side_tile = false;      // debug switch: ... and never on the 8 x 19 side geometry (the plan of the geometry table always)
 };
 
 // int16 DP cells: the reference wraps silently.  Scores and alignments switch to int32 cells on the strip path where they could.
@@ -198,14 +199,15 @@ inline long long sym_affine_tilt_top_index(int R, int F, int rows, int K) {
     const int lead = rows > R ? (rows - R) / K : 0;
     return (long long)rows + F - lead;
 }
-// ... and the form is legal inside the plain biased form's window, for K <= kTiltMaxK (cell_constants.h), where B plus the largest tilt plus the largest cell stays at
+// ... and the form is legal inside the plain biased form's window, for K <= kTiltMaxK and on the 8 x 19 side tile (cell_constants.h:
+// tilt_frame_built; the rule sees rows and K, the group is rows / K), where B plus the largest tilt plus the largest cell stays at
 // or below 0x7BFF.  R, F as in sym_affine_max3_ok; rows, K: of the geometry the launch runs on.
 // The running maxima of the sweep stay in the frame: an accumulator is carried from anti-diagonal to anti-diagonal of its lane and
 // holds, whenever a maximum reads it, the largest cell that lane has seen so far plus B + x * u of a cell of the sweep (u <= the top
 // index) -- a cell of the matrix plus a tilt of the sweep, which is what `hi` and the top index bound already: the rule stands as it is
 // (tests/test_sym_affine_inframe_sweep.py asserts it of every operand at the rule's edge).
 inline bool sym_affine_tilt_ok(const RuleInputs &in, int R, int F, int rows, int K) {
-    if (in.no_tilt || K > kTiltMaxK || !sym_affine_max3_ok(in, R, F)) return false;
+    if (in.no_tilt || K <= 0 || !tilt_frame_built(rows / K, K) || !sym_affine_max3_ok(in, R, F)) return false;
     const Scoring &sc = in.sc;
     const long long B = sym_affine_tilt_bias(sc);
     const long long hi = (long long)std::min(R, F) * std::max({sc.match, sc.mismatch, 0}) + 1;
@@ -232,6 +234,43 @@ inline bool sym_affine_row_tables_ok(const RuleInputs &in, int R, int F, int row
     return sym_affine_row_table_low(in.sc) >= 0 && sym_affine_row_table_high(in.sc) <= 255 && lds_tables <= lds_profile;
 }
 inline const char *ran_sym_affine_scores_name(bool row_tables) { return row_tables ? "row_tables" : "lds_profile"; }
+
+// ---- the 8 x 19 SIDE TILE of that sweep (cell_constants.h: kSideTileG x kSideTileK; engine.hip.h: kSideGeometry) ----
+// 152 rows in a wave64: a read of 129 .. 152 bases pads 1.3 % where 16 x 10 pads 6.25 %, the skew of the sweep is 7 steps instead
+// of 15 and the fixed part of a step is paid once per 19 rows.  Its one kernel carries the row-table forms only, 16 pairs per wave,
+// and issues well only with two waves per SIMD: the plan is a 4-wave block, and it is taken only where TWO such blocks fit a CU's
+// LDS: side_tile_wave_lds(R, F) bytes per wave (cell_constants.h; dp_kernels.hip.h lays them out).  A block's LDS is
+// granted in granules (three blocks of 54,016 B did not fit the 163,840 B of a CU), so the budget counts each block rounded up to
+// 2 KB and leaves 8 KB of the CU alone: nothing is planned to the last byte.
+constexpr int kSideTileRows = kSideTileG * kSideTileK, kSideTileMinRead = 129;
+constexpr int kSideTileBlockWaves = 4, kSideTileLdsGranule = 2048, kSideTileLdsBudget = 152 * 1024;
+inline bool side_tile_lds_ok(int lds_wave) {
+    const long long block = ((long long)lds_wave * kSideTileBlockWaves + kSideTileLdsGranule - 1) / kSideTileLdsGranule * kSideTileLdsGranule;
+    return lds_wave > 0 && 2 * block <= kSideTileLdsBudget;
+}
+// Why a Smith-Waterman (`alg`) score launch of gap form `gaps` (score_gap_form) over R x F does NOT run on the side tile; "" where
+// it does.  R, F: of the launch (a length-sorted launch: its read class and widest reference), which size its LDS; the windows are asked about the
+// engine's shape in.R x in.F, as for every launch of a call.  latency: the call is small enough for the latency plan, whose
+// sweeps are as short as can be -- the side tile is a throughput plan.  forced: group_lanes = 8, rows_per_lane = 19; a forced tile
+// runs whatever the call's size and however short the read (R <= 152 is what fits; R = 1 leaves one live row in the last lane),
+// the other conditions hold for it as they stand and the engine raises the text.
+inline const char *sym_affine_side_tile_refusal(const RuleInputs &in, int alg, int gaps, int R, int F, bool latency, bool forced) {
+    const int lds_wave = side_tile_wave_lds(R, F);
+    if (in.no_side_tile) return "the side tile is switched off (VALIGN_HIP_DEBUG=no_side_tile)";
+    if (alg != kAlgSW) return "the 8 x 19 tile exists for Smith-Waterman scores only";
+    if (gaps != kGapAffineSym)
+        return "the 8 x 19 tile exists for int16 cells with symmetric affine gaps only (half_float_cells = 0, open_read = open_ref, ext_read = ext_ref)";
+    if (R > kSideTileRows) return "the 8 x 19 tile holds reads of at most 152 bases";
+    if (in.no_tilt) return "the 8 x 19 tile runs the tilted frame only (VALIGN_HIP_DEBUG=no_tilt)";
+    if (in.no_row_tables) return "the 8 x 19 tile runs the row tables only (VALIGN_HIP_DEBUG=no_row_tables)";
+    if (!sym_affine_row_tables_ok(in, in.R, in.F, kSideTileRows, kSideTileK, lds_wave, lds_wave))
+        return "the 8 x 19 tile runs the tilted frame with row tables only: shape x scoring leave its window, or a substitution score of the frame is no byte (sym_affine_row_tables_ok)";
+    if (!side_tile_lds_ok(lds_wave)) return "the 8 x 19 tile needs two 4-wave blocks per CU: the reference is too long for its LDS budget";
+    if (forced) return "";
+    if (R < kSideTileMinRead) return "reads of at most 128 bases fit a smaller tile";
+    if (latency) return "small calls take the latency plan";
+    return "";
+}
 
 // Which fill kernel an alignment call of this mode takes on a G x K geometry, and what its pointer stream looks like.
 struct FillChoice {

@@ -29,7 +29,8 @@
 //     byte loads.
 //     (The tilted int16 symmetric affine Smith-Waterman sweep keeps them in REGISTERS instead where every score is a
 //     byte: four bytes per row and pair, looked up by the one v_perm_b32 the merge takes anyway, from a stream of
-//     selector dwords -- wave_setup_tables; no profile, no slab numbers.)
+//     selector dwords -- wave_setup_tables; no profile, no slab numbers.  One tile exists for that form alone: 8 lanes x 19 rows,
+//     152 rows for reads of 129 .. 152 bases, 16 pairs per wave, its stream 16 bits per column -- cell_constants.h: tilt_tables_only.)
 //   * Recurrence variants (GAPS), packed instructions per register (= per two cells) incl. the
 //     profile merge: two linear gap scores 6 + maximum tracking, one shared gap score 5 +
 //     tracking, affine 10 + tracking, affine with the same open/extend for both directions 9 + tracking (Smith-Waterman:
@@ -111,6 +112,10 @@ struct ScoreArgs {
         long long pair_ofs;         // into scores
         long long read_ofs, ref_ofs;   // bytes into reads / refs
     } groups[kMaxScoreGroups];
+    // Behind everything else, so that no other member moves: two device words the 8 x 19 instance (the only one that reads this
+    // member) reports its form in -- a wave that ran the plain row-table step sets word 0, one that ran the repairing copy word 1
+    // (describe: ran_score_sym_affine_form).  Null: nothing is reported.
+    unsigned *form_seen;
 };
 
 // ---- packed int16 helpers (each is one VOP3P instruction on gfx950) ----
@@ -201,7 +206,9 @@ constexpr int profile_conflicts(int G, int lane_dw, int width, int stride_dw) {
 template <int G, int K>
 struct Geo {
     static_assert(G == 4 || G == 8 || G == 16 || G == 32 || G == 64, "group size");
-    static_assert(K % 2 == 0, "rows per lane must be even");
+    // (8 x 19, the row-table tile of the tilted symmetric affine sweep, builds no profile: kNoProfile leaves the slab constants out)
+    static constexpr bool kNoProfile = tilt_tables_only(G, K);
+    static_assert(K % 2 == 0 || kNoProfile, "rows per lane must be even");
     static constexpr int kGroups = kWave / G;        // lane groups per wave
     static constexpr int kPairs = 2 * kGroups;       // pairs per wave
     static constexpr int kRows = G * K;              // padded rows
@@ -222,7 +229,7 @@ struct Geo {
         }
         return best;
     }
-    static constexpr int kPairStride = slab_dwords() * 4;   // bytes of one (class, pair) slab
+    static constexpr int kPairStride = kNoProfile ? 0 : slab_dwords() * 4;   // bytes of one (class, pair) slab
     // profile slabs: slab (class * kPairs + pair) for classes 0..3, plus ONE all-zero slab
     // shared by every pair for "this reference base scores nothing"
     static constexpr int kZeroSlab = 4 * kPairs;
@@ -557,8 +564,14 @@ __device__ __forceinline__ bool wave_setup(const uint8_t *reads, const uint8_t *
 // `repair` comes back true (wave-uniform) where some pair of the wave has such a base BEFORE its last ACGT base.
 // LDS of a wave (row_table_lds): the wave's raw references, then the stream, row_table_pad(G) pad columns at either end of
 // every group's; the raw reads are staged where the stream is built once they have been read.
+// THE COMPACT STREAM (8 x 19 only: tilt_tables_only).  That tile holds 16 pairs per wave and runs two 4-wave blocks per CU or not
+// at all, so its stream is 16 bits per column and group -- {ca, 4 + cb}, the two bytes of the selector that carry anything -- and
+// the sweep widens each entry with one v_perm_b32 against kSelZero4 (row_table_lds16 has the sizes).  Everything else here -- the
+// tables, the pads, `repair` -- is the same; the rows of a lane are still looked up four at a time, and the group of four that
+// holds row 16 .. 18 reads one base past the lane's rows and drops it.
 constexpr int row_table_pad(int G) { return G + 4; }       // columns -(G - 1) .. F + G are read (the sweep, two steps of prefetch)
 constexpr unsigned kSelZero4 = 0x0c0c0c0cu;
+constexpr unsigned kSelWiden = 0x04010400u;                // v_perm_b32(kSelZero4, {ca, 4 + cb, -, -}, .) = {ca, 0x0c, 4 + cb, 0x0c}
 
 template <int G, int K>
 __device__ __forceinline__ bool wave_setup_tables(const uint8_t *reads, const uint8_t *refs, long long n, int R, int F,
@@ -620,10 +633,16 @@ __device__ __forceinline__ bool wave_setup_tables(const uint8_t *reads, const ui
                 const unsigned lo23 = __builtin_amdgcn_perm(col[3], col[2], 0x05010400u), hi23 = __builtin_amdgcn_perm(col[3], col[2], 0x07030602u);
                 unsigned (&T)[K] = half ? Tb : Ta;
                 T[q0] = __builtin_amdgcn_perm(lo23, lo01, 0x05040100u);
-                T[q0 + 1] = __builtin_amdgcn_perm(lo23, lo01, 0x07060302u);
-                if (q0 + 2 < K) {
-                    T[q0 + 2] = __builtin_amdgcn_perm(hi23, hi01, 0x05040100u);
-                    T[q0 + 3] = __builtin_amdgcn_perm(hi23, hi01, 0x07060302u);
+                if constexpr (K % 2 == 0) {
+                    T[q0 + 1] = __builtin_amdgcn_perm(lo23, lo01, 0x07060302u);
+                    if (q0 + 2 < K) {
+                        T[q0 + 2] = __builtin_amdgcn_perm(hi23, hi01, 0x05040100u);
+                        T[q0 + 3] = __builtin_amdgcn_perm(hi23, hi01, 0x07060302u);
+                    }
+                } else {                                    // (odd K: the last group of four has one or three rows)
+                    if (q0 + 1 < K) T[q0 + 1] = __builtin_amdgcn_perm(lo23, lo01, 0x07060302u);
+                    if (q0 + 2 < K) T[q0 + 2] = __builtin_amdgcn_perm(hi23, hi01, 0x05040100u);
+                    if (q0 + 3 < K) T[q0 + 3] = __builtin_amdgcn_perm(hi23, hi01, 0x07060302u);
                 }
             }
         }
@@ -638,10 +657,14 @@ __device__ __forceinline__ bool wave_setup_tables(const uint8_t *reads, const ui
     bool before_last = false;
     unsigned *stream = reinterpret_cast<unsigned *>(sel);
     const int stride_dw = sel_stride / 4;
+    constexpr bool SEL16 = tilt_tables_only(G, K);                   // the compact stream: 16 bits per column and group
+    unsigned short *stream16 = reinterpret_cast<unsigned short *>(sel);
+    const int stride_h = sel_stride / 2;
     if (live) {
         for (int idx = lane; idx < geo::kGroups * 2 * kPad; idx += kWave) {
             const int g = idx / (2 * kPad), x = idx - g * (2 * kPad);
-            stream[g * stride_dw + (x < kPad ? x : F + x)] = kSelZero4;          // [0, pad) and [F + pad, F + 2 pad)
+            if constexpr (SEL16) stream16[g * stride_h + (x < kPad ? x : F + x)] = (unsigned short)0x0c0c;
+            else stream[g * stride_dw + (x < kPad ? x : F + x)] = kSelZero4;     // [0, pad) and [F + pad, F + 2 pad)
         }
         const int ref_skew = (int)((unsigned long long)(refs + pair0 * F) & 15ull);
         typedef unsigned short u16;
@@ -652,6 +675,7 @@ __device__ __forceinline__ bool wave_setup_tables(const uint8_t *reads, const ui
             pb = pb > last ? last : pb;
             const unsigned char *raw_a = raw + ref_skew + pa * F, *raw_b = raw + ref_skew + pb * F;
             unsigned *out_g = stream + g * stride_dw + kPad;
+            unsigned short *out16_g = stream16 + g * stride_h + kPad;           // (8-byte aligned: the stride and the pad are)
             // per pair: {1 + its last ACGT column, 0xFFFF - its first column that is none} -- one packed maximum each
             u16x2 ends_a = u16x2{0, 0}, ends_b = u16x2{0, 0};
             auto note = [](u16x2 &ends, unsigned acgt, int j) __attribute__((always_inline)) {     // acgt: a byte is non-zero where the column has an ACGT base
@@ -665,19 +689,27 @@ __device__ __forceinline__ bool wave_setup_tables(const uint8_t *reads, const ui
                 const unsigned ca = base_class4(lds_dword_at(raw_a + j)), cb = base_class4(lds_dword_at(raw_b + j));
                 // selector by class: 1..4 the table byte (pair B: of the second table), 0 and 5..7 the constant zero
                 const unsigned sa = select_bytes8(0x0c0c0c03u, 0x0201000cu, ca), sb = select_bytes8(0x0c0c0c07u, 0x0605040cu, cb);
-                uint4 s;
-                s.x = __builtin_amdgcn_perm(sb, sa, 0x0c040c00u) | 0x0c000c00u;
-                s.y = __builtin_amdgcn_perm(sb, sa, 0x0c050c01u) | 0x0c000c00u;
-                s.z = __builtin_amdgcn_perm(sb, sa, 0x0c060c02u) | 0x0c000c00u;
-                s.w = __builtin_amdgcn_perm(sb, sa, 0x0c070c03u) | 0x0c000c00u;
-                *reinterpret_cast<uint4 *>(out_g + j) = s;
+                if constexpr (SEL16) {
+                    uint2 s;                                                    // (sa | sb << 8) of columns j, j + 1 | j + 2, j + 3
+                    s.x = __builtin_amdgcn_perm(sb, sa, 0x05010400u);
+                    s.y = __builtin_amdgcn_perm(sb, sa, 0x07030602u);
+                    *reinterpret_cast<uint2 *>(out16_g + j) = s;
+                } else {
+                    uint4 s;
+                    s.x = __builtin_amdgcn_perm(sb, sa, 0x0c040c00u) | 0x0c000c00u;
+                    s.y = __builtin_amdgcn_perm(sb, sa, 0x0c050c01u) | 0x0c000c00u;
+                    s.z = __builtin_amdgcn_perm(sb, sa, 0x0c060c02u) | 0x0c000c00u;
+                    s.w = __builtin_amdgcn_perm(sb, sa, 0x0c070c03u) | 0x0c000c00u;
+                    *reinterpret_cast<uint4 *>(out_g + j) = s;
+                }
                 note(ends_a, sa ^ kSelZero4, j);
                 note(ends_b, sb ^ kSelZero4, j);
             }
             for (int j = F4 + lane; j < F; j += kWave) {                        // the rim
                 const int ca = base_class(raw_a[j]), cb = base_class(raw_b[j]);
                 const bool va = ca >= 1 && ca <= 4, vb = cb >= 1 && cb <= 4;
-                out_g[j] = (va ? (unsigned)(ca - 1) : 0x0cu) | (vb ? (unsigned)(cb + 3) : 0x0cu) << 16 | 0x0c000c00u;
+                if constexpr (SEL16) out16_g[j] = (unsigned short)((va ? (unsigned)(ca - 1) : 0x0cu) | (vb ? (unsigned)(cb + 3) : 0x0cu) << 8);
+                else out_g[j] = (va ? (unsigned)(ca - 1) : 0x0cu) | (vb ? (unsigned)(cb + 3) : 0x0cu) << 16 | 0x0c000c00u;
                 ends_a = __builtin_elementwise_max(ends_a, u16x2{va ? (u16)(j + 1) : (u16)0, va ? (u16)0 : (u16)(0xFFFF - j)});
                 ends_b = __builtin_elementwise_max(ends_b, u16x2{vb ? (u16)(j + 1) : (u16)0, vb ? (u16)0 : (u16)(0xFFFF - j)});
             }
@@ -695,7 +727,7 @@ __device__ __forceinline__ bool wave_setup_tables(const uint8_t *reads, const ui
     repair = __builtin_amdgcn_readfirstlane((int)before_last) != 0;
     w.cols_used = __builtin_amdgcn_readfirstlane(cols_used);
     w.prof = raw;
-    w.refc = reinterpret_cast<unsigned char *>(stream + kPad);          // entry of column 0 of the first group
+    w.refc = SEL16 ? reinterpret_cast<unsigned char *>(stream16 + kPad) : reinterpret_cast<unsigned char *>(stream + kPad);          // entry of column 0 of the first group
     w.first_bad = nullptr;
     w.pair0 = pair0;
     w.last = last;
@@ -828,7 +860,10 @@ score_kernel(const ScoreArgs args) {
     // diagonal as the NW frame does: 2x on every score of the profile, the zero slab included)
     // (... and its lanes hand H - (o - x) of their last row down, so every score of a lane's row 0 carries the o - x back)
     short s_row0 = 0;
-    if constexpr (SOURCES && K <= kTiltMaxK) {
+    // TILT_BUILT: the instance carries the tilted biased form; TABLES_ONLY (8 x 19): that form with the row tables and nothing else --
+    // no LDS profile, no plain biased form, no gap-source form: a launch without the row-table bits does nothing
+    constexpr bool TILT_BUILT = SOURCES && tilt_frame_built(G, K), TABLES_ONLY = SOURCES && tilt_tables_only(G, K);
+    if constexpr (TILT_BUILT) {
         if (args.sym_max3_bias > 0 && (args.sym_max3_bias >> 16) != 0) {
             fold = -2 * (int)args.ext_ref;
             s_row0 = (short)((int)args.ext_ref - (int)args.open_ref);
@@ -859,7 +894,15 @@ score_kernel(const ScoreArgs args) {
     // registers and no profile is built: wave_setup_tables)
     bool tables = false, repair = false;
     unsigned Ta[K], Tb[K];
-    if constexpr (SOURCES && K <= kTiltMaxK) {
+    if constexpr (TABLES_ONLY) {
+        tables = args.sym_max3_bias > 0 && (args.sym_max3_bias >> 16 & 3) == 3;
+        if (!tables) return;                   // (wave-uniform, before any barrier)
+        if (!wave_setup_tables<G, K>(reads, refs, n_pairs, args.R, F_batch, args.prof_area, args.refc_stride, args.wave_lds,
+                                     s_match, s_mismatch, s_zero, s_row0, block, w, Ta, Tb, repair))
+            return;
+        // which form this wave runs, once per wave: a plain store of 1 (every wave that writes a word writes the same value)
+        if (args.form_seen != nullptr && lane == 0) args.form_seen[repair ? 1 : 0] = 1u;
+    } else if constexpr (TILT_BUILT) {
         tables = args.sym_max3_bias > 0 && (args.sym_max3_bias >> 16 & 3) == 3;
         bool live = false;
         if (tables)
@@ -943,7 +986,7 @@ score_kernel(const ScoreArgs args) {
     unsigned pa[K / 2], pb[K / 2];
     s16x2 S0[K], S1[K];          // the scores of a step (two buffers: the steady loop takes two steps per trip)
     unsigned ca_next = 0, cb_next = 0;
-    if (PIPE && !tables) {          // (the row-table sweep has no profile and fetches its own stream)
+    if constexpr (!TABLES_ONLY) if (PIPE && !tables) {          // (the row-table sweep has no profile and fetches its own stream)
         const unsigned ca = *(lds_cu8 *)(code_addr), cb = *(lds_cu8 *)(code_addr + 1);
         lds_load_lane<K>(lane_base + ca * geo::kPairStride, pa);
         lds_load_lane<K>(lane_base + cb * geo::kPairStride, pb);
@@ -1224,9 +1267,9 @@ score_kernel(const ScoreArgs args) {
         bool biased = false;
         if constexpr (SOURCES) {
             biased = args.sym_max3_bias > 0;       // wave-uniform: the same sweep in its biased form
-            // ... in the tilted frame (the bias: the low 16 bits); built for K <= 12: the engine asks for it nowhere else
-            const bool tilted = K <= kTiltMaxK && biased && (args.sym_max3_bias >> 16) != 0;
-            if constexpr (K <= kTiltMaxK) if (tilted) {
+            // ... in the tilted frame (the bias: the low 16 bits); built for K <= 12 and for 8 x 19: the engine asks for it nowhere else
+            const bool tilted = TILT_BUILT && biased && (args.sym_max3_bias >> 16) != 0;
+            if constexpr (TILT_BUILT) if (tilted) {
                 // THE TILTED BIASED FORM.  Cell (p, j) -- p the padded row, j the column -- is kept as value + B + x u with
                 // u = p + j + c0 and x = -extend.  In that frame an extension costs nothing: E(p, j-1) - x IS the register of
                 // (p, j-1) read in the frame of (p, j), F likewise down the column, the diagonal pays 2x through the profile
@@ -1315,10 +1358,25 @@ score_kernel(const ScoreArgs args) {
                 // every half that selected 0x00 set to 2x (row 0: 2x + o - x) -- one v_or_b32 per register and four per step
                 // more: the profile's scores at every column, pads included, so exact by the profile form's argument.
                 // tests/test_sym_affine_row_tables_sweep.py restates this step on the CPU.
+                // 8 x 19 (TABLES_ONLY).  K is odd: rows 0 .. 17 enter the accumulators in pairs as above, and row 18, which has no
+                // partner, enters the slot of its own anti-diagonal c = 18 + t alone, at once, with ONE two-operand packed maximum.
+                // That keeps the running maximum exact by the same anti-diagonal argument with one operand fewer: every d of
+                // anti-diagonal c still reaches slot c before row 0 completes c and the slot moves on (row 18 at step c - 18, the
+                // pairs as before, row 1 with row 0 at step c), each d enters exactly one slot, and a two-operand half-float
+                // maximum of two patterns of the window is the integer maximum as the three-operand one is.  After the last step
+                // only odd rows wait in dprev, as for an even K.  Its stream is the compact one (wave_setup_tables): one volatile
+                // 16-bit LDS load two steps ahead, widened to the selector dword by one v_perm_b32 when its step comes.
+                // tests/test_sym_affine_odd_tile_sweep.py restates this step on the CPU.
                 constexpr int kLdsProfile = 0, kRowTables = 1, kRowTablesRepair = 2;
+                constexpr bool SEL16 = TABLES_ONLY;
+                typedef __attribute__((address_space(3))) const unsigned short lds_cu16;
                 lds_cu32 *sel_ptr = (lds_cu32 *)(lds_offset(w.refc) + grp * args.refc_stride - 4 * (l - lead));   // + 4 per step
+                lds_cu16 *sel16_ptr = (lds_cu16 *)(lds_offset(w.refc) + grp * args.refc_stride - 2 * (l - lead));  // (compact: + 2 per step)
                 unsigned sel_cur = 0, sel_next = 0;
-                if (tables) {
+                if constexpr (SEL16) {
+                    sel_cur = __builtin_amdgcn_perm(kSelZero4, (unsigned)sel16_ptr[0], kSelWiden);
+                    sel_next = sel16_ptr[1];                              // (kept narrow until its step)
+                } else if (tables) {
                     sel_cur = sel_ptr[0];
                     sel_next = sel_ptr[1];
                 }
@@ -1346,9 +1404,15 @@ score_kernel(const ScoreArgs args) {
 #pragma unroll
                             for (int q = 0; q < K; ++q) S[q] = as_pk(as_u32(S[q]) | (q == 0 ? fix_0 : fix_q));
                         }
-                        sel_cur = sel_next;
-                        sel_next = ((volatile lds_cu32 *)sel_ptr)[2];
-                        sel_ptr += 1;
+                        if constexpr (SEL16) {
+                            sel_cur = __builtin_amdgcn_perm(kSelZero4, sel_next, kSelWiden);
+                            sel_next = ((volatile lds_cu16 *)sel16_ptr)[2];
+                            sel16_ptr += 1;
+                        } else {
+                            sel_cur = sel_next;
+                            sel_next = ((volatile lds_cu32 *)sel_ptr)[2];
+                            sel_ptr += 1;
+                        }
                     }
                     s16x2 e_cur;
                     auto pass1 = [&](int q, s16x2 &e) __attribute__((always_inline)) {
@@ -1371,7 +1435,8 @@ score_kernel(const ScoreArgs args) {
                         HOl[q] = ho;
                         if (!(q & 1)) {
                             s16x2 &a = acc[(q + SLOT0) % K];
-                            a = pk_max3_h(a, d[q], dprev[q + 1]);
+                            if (q + 1 < K) a = pk_max3_h(a, d[q], dprev[q + 1]);
+                            else a = pk_max_h(a, d[q]);                  // (odd K: the unpaired last row)
                         }
                         e_cur = e_next;
                     }
@@ -1396,7 +1461,7 @@ score_kernel(const ScoreArgs args) {
                 // common parts get hoisted and the kernel allocates half as many registers again
                 // (profiles/r21_sym_affine_bookkeeping.txt, section 1).
                 int form = __builtin_amdgcn_readfirstlane(tables ? (repair ? kRowTablesRepair : kRowTables) : kLdsProfile);
-                if (form == kLdsProfile) tilted_sweep(std::integral_constant<int, kLdsProfile>{});
+                if constexpr (!TABLES_ONLY) if (form == kLdsProfile) tilted_sweep(std::integral_constant<int, kLdsProfile>{});
                 asm volatile("" : "+s"(form));          // (each comparison on a value the compiler knows nothing about)
                 if (form == kRowTables) tilted_sweep(std::integral_constant<int, kRowTables>{});
                 asm volatile("" : "+s"(form));
@@ -1404,11 +1469,11 @@ score_kernel(const ScoreArgs args) {
                 // the odd rows of the last step, then out of the frame: after a whole trip slot q stands for c = q + steps
                 best = pk(0);
 #pragma unroll
-                for (int q = 0; q < K; q += 2) acc[q] = pk_max_h(acc[q], dprev[q + 1]);
+                for (int q = 0; q + 1 < K; q += 2) acc[q] = pk_max_h(acc[q], dprev[q + 1]);
 #pragma unroll
                 for (int q = 0; q < K; ++q) best = pk_max(best, acc[q] - fl[q]);
             }
-            if (biased && !tilted) {
+            if constexpr (!TABLES_ONLY) if (biased && !tilted) {
                 const s16x2 bias_c = pk((short)args.sym_max3_bias);
                 const s16x2 lead_bias = as_pk(as_u32(bias_c) & ~lmask);          // the bias in the group's first lane, zero below it
                 // One step of the biased form.  The hand-over, the pipelined fetches and the code pointer are the step's above.
@@ -1478,7 +1543,7 @@ score_kernel(const ScoreArgs args) {
                 best = best - bias_c;                  // the score is best - B
             }
         }
-        if (!biased) {
+        if constexpr (!TABLES_ONLY) if (!biased) {
             for (; t + 1 < steps; t += 2) {        // two steps per trip: loop-carried registers swap roles
                 step(std::false_type{}, first_t{}, S0, S1);    // instead of being copied (+4 % SW, +4 % affine
                 step(std::false_type{}, second_t{}, S1, S0);   // together with the pipelined fetch)
@@ -1572,6 +1637,21 @@ inline WaveLds row_table_lds(int G, int R, int F) {
     w.refc_stride = 4 * stride_dw;
     const int streams = groups * w.refc_stride, raw_reads = ((pairs * R + 32 + 15) / 16) * 16;
     w.total = w.prof_area + (streams > raw_reads ? streams : raw_reads);
+    return w;
+}
+
+// ... and with the compact stream of the 8 x 19 tile: 16 bits per column and group.  The 8 lanes of a group read 8 consecutive
+// entries, 16 bytes that touch up to five dwords wherever they start; ds_read_u16 is served 32 lanes -- four groups -- at a time on
+// banks (a / 4) mod 32, so a group stride of 8 (mod 64) dwords, the dword stream's `G mod 64`, keeps the four windows of a
+// half-wave on disjoint banks (two lanes in one dword read the same address: a broadcast).  150 x 500: 8,032 B of raw references +
+// 8 x 1,056 B of streams = 16,480 B per wave, 65,920 B per 4-wave block (the dword stream: 26,720 and 106,880).
+// (the arithmetic is cell_constants.h's, where the rule that budgets it reads it too)
+static_assert(kSideTilePad == row_table_pad(kSideTileG) && kSideTilePairs == 2 * (kWave / kSideTileG), "cell_constants.h restates the side tile's layout");
+inline WaveLds row_table_lds16(int R, int F) {
+    WaveLds w;
+    w.prof_area = side_tile_refs_area(F);
+    w.refc_stride = side_tile_stream_stride(F);
+    w.total = side_tile_wave_lds(R, F);
     return w;
 }
 

@@ -75,6 +75,7 @@ namespace valign {
 VALIGN_ALL_PARTS(VALIGN_DECLARE_FULL, VALIGN_DECLARE_FAST)
 #undef VALIGN_DECLARE_FULL
 #undef VALIGN_DECLARE_FAST
+VALIGN_SIDE_KERNELS(extern template)
 
 // One compiled (G, K) geometry with its kernel variants.
 struct Geometry {
@@ -156,7 +157,13 @@ constexpr int kNumGeometries = sizeof(kGeometries) / sizeof(kGeometries[0]);
 static_assert(kNumGeometries == 0 VALIGN_ALL_PARTS(VALIGN_COUNT, VALIGN_COUNT), "kernel_instances.hip.h lists other geometries than this table");
 #undef VALIGN_COUNT
 
+// The side geometry (kernel_instances.hip.h): 8 x 19 with ONE kernel, [SW][symmetric affine], and the compact row-table stream's
+// LDS.  It is in no table: only Engine::score_plan_for hands it out, where sym_affine_side_tile_refusal (cell_rules.h) is empty.
+// ONE object, defined in engine_core.hip.
+extern const Geometry kSideGeometry;
+
 constexpr int kMaxBlockLds = 160 * 1024;       // gfx950: 160 KiB per CU, one block may take it all
+static_assert(kSideTileLdsBudget < kMaxBlockLds, "the side tile's LDS budget leaves a margin inside a CU's LDS");
 constexpr int kSlots = 4;                      // staging slots of the host-pointer pipeline
 constexpr int kDefaultBlockLds = 64 * 1024;    // above this the kernel attribute must be raised
 
@@ -175,7 +182,7 @@ public:
     DebugSwitches() {
         const char *env = getenv("VALIGN_HIP_DEBUG");
         if (!env) return;
-        static const char *const known[] = {"no_sym", "no_tag", "no_f16", "no_max3", "no_tilt", "no_row_tables", "no_fused", "no_prof_key", "no_overlap", "no_band_chain",
+        static const char *const known[] = {"no_sym", "no_tag", "no_f16", "no_max3", "no_tilt", "no_row_tables", "no_side_tile", "no_fused", "no_prof_key", "no_overlap", "no_band_chain",
                                             "force_long", "wide_align", "strip_k", "no_single_strip", "no_direct_out", "ragged_min", "chunk_bytes",
                                             "align_chunk_bytes", "direct_bytes", "scratch_cap_mb", "whole_rows", "short_strips", "cigar_rows_mb", "cigar_lanes",
                                             "span_scratch_bytes", "subopt_scratch_bytes", "span_cigar_mb"};
@@ -386,6 +393,7 @@ public:
     RuleInputs rule_inputs() const {
         RuleInputs in = RuleInputs{sc_, R_, F_, sse_policy_, no_sym_, no_tag_, no_f16_, no_prof_key_, no_max3_, no_tilt_};
         in.no_row_tables = no_row_tables_;
+        in.no_side_tile = no_side_tile_;
         return in;
     }
     // score_alignments at the engine's full shape stays inside int16 cells (int16_range_ok with this engine's plans: the
@@ -648,11 +656,29 @@ private:
 
     static LaunchPlan long_plan();
 
+    // The plan of one register-sweep SCORE launch of `alg` over R x F: `base` (the engine's, the latency plan or a length class's),
+    // or the 8 x 19 side tile where its rule has nothing to refuse (cell_rules.h: sym_affine_side_tile_refusal).  Every other
+    // call of the engine -- alignments, placed, spanned, suboptimal and extension scores, the NW variant -- plans from the
+    // geometry table as ever: the side geometry has one kernel.  A FORCED side tile (group_lanes = 8, rows_per_lane = 19)
+    // raises the rule's text where it refuses.
+    // refuse = false (describe): what the launch WOULD take, nothing is raised.
+    LaunchPlan score_plan_for(const LaunchPlan &base, int alg, int R, int F, bool latency, bool refuse = true) const;
+    static LaunchPlan side_plan(int R, int F);
+    const char *side_tile_refusal(int alg, int R, int F, bool latency) const;
+    // a device-resident score call of n pairs is small enough for the latency plan (score_device and describe share it)
+    bool few_pairs(long long n) const { return n > 0 && n <= (long long)latency_plan_.pairs_per_wave * 1024 && band_width_ == 0; }
+    // The forms the 8 x 19 launches of the last score call ran, read back from the device (waits for it): "row_tables",
+    // "row_tables_repair", "both", or "none" where no wave of such a launch has run
+    const char *ran_side_tile_form() const;
+    void reset_side_tile_form(hipStream_t stream);      // stream null: synchronously (the host pipeline, whose chunks run on several streams)
+
 
     // A chunk of the host-pointer pipeline is one kernel launch: sized in whole "rounds" of the waves the device runs side by
     // side (16,384 pairs at 16 x 10: 8 pairs per wave, 8 waves per CU, 256 CUs), it leaves no partly filled last round --
     // a 48 MB chunk of 150 x 500 was 4.57 rounds and paid for 5.
-    long long whole_rounds(long long pairs) const;
+    // sw_scores: the chunk is one of a Smith-Waterman SCORE call, whose launches take the 8 x 19 side tile where its rule holds:
+    // whole rounds of that plan too (32,768 pairs at 150 x 500, a multiple of 16 x 10's 16,384).  Every other call rounds as ever.
+    long long whole_rounds(long long pairs, bool sw_scores = false) const;
 
     // Small calls skip the chunk pipeline (VALIGN_HIP_DIRECT_BYTES: sequence bytes up to which they do; 0 = never)
     bool direct_call(long long n, size_t per_pair) const;
@@ -723,7 +749,7 @@ private:
     // ---- the pieces of the host-pointer chunk pipeline (engine_score.hip), shared by score_host and record_pipeline ----
     // Pairs of one chunk: score_chunk_bytes_ of sequences -- at least 192 MB where the chunks' launches share a scratch and
     // follow one another on one stream (not under the chunk_bytes debug switch) --, in whole rounds, at least 1024, at most n
-    long long host_chunk_pairs(bool shared_scratch, long long n) const;
+    long long host_chunk_pairs(bool shared_scratch, long long n, bool sw_scores = false) const;
     // gather (4-bit classes where host_packing is on), H2D and unpacking on `stream`: the chunk lies in d_reads_ / d_refs_[slot]
     void stage_chunk(int slot, hipStream_t stream, const char *const *reads, const char *const *refs, long long cnt, int threads);
     // the slot's event, then drain(slot): the result of the chunk that used the slot last
@@ -909,6 +935,8 @@ private:
     bool no_max3_ = dbg_.on("no_max3");   // int16 symmetric affine SW scores on the gap-source form always
     bool no_tilt_ = dbg_.on("no_tilt");   // ... and their biased form in the plain frame always
     bool no_row_tables_ = dbg_.on("no_row_tables");   // ... and their tilted frame on the LDS profile always
+    bool no_side_tile_ = dbg_.on("no_side_tile");     // ... and never on the 8 x 19 side geometry
+    bool side_forced_ = false;                        // group_lanes = 8, rows_per_lane = 19: score calls run the side tile or raise
     bool no_fused_ = dbg_.on("no_fused");   // small alignment calls as fill + traceback kernels
     bool no_prof_key_ = dbg_.on("no_prof_key");   // compute the SW lane key instead of carrying it in the profile
     bool copy_engines_primed_ = false;
@@ -1018,6 +1046,7 @@ private:
     DeviceBuffer<BandBlock> d_band_blocks_;                      // the block chain's tables (band_plan_)
     DeviceBuffer<int> d_band_fill_;
     RaggedCtx rag_[kSlots + 1];                                  // one per pipeline slot, the last for device-resident batches
+    DeviceBuffer<unsigned> d_form_seen_;                         // the 8 x 19 kernel's two form words (ScoreArgs::form_seen)
     DeviceBuffer<uint8_t> d_read_class_;                         // length -> class tables of the length-sorted batches
     DeviceBuffer<uint16_t> d_ref_class_;
 };

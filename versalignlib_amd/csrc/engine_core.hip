@@ -1,7 +1,19 @@
 // engine_core.hip -- Engine: construction, launch-plan selection, staging, describe().
+#include <numeric>
+
 #include "engine.hip.h"
 
 namespace valign {
+
+// The side geometry: 8 x 19, ONE kernel, the compact row-table stream's LDS; no fill, placed, suboptimal or extension kernel
+static WaveLds side_tile_lds(int R, int F) { return row_table_lds16(R, F); }
+static Geometry side_geometry() {
+    Geometry g{kSideTileG, kSideTileK, false, &side_tile_lds, {}, {}, [](int, int) -> const void * { return nullptr; },
+               [](int, int) -> const void * { return nullptr; }, [](int) -> const void * { return nullptr; }};
+    g.kernel[kAlgSW][kGapAffineSym] = (const void *)&score_kernel<kSideTileG, kSideTileK, kAlgSW, kGapAffineSym>;
+    return g;
+}
+const Geometry kSideGeometry = side_geometry();
 
 Engine::Engine(int device, int R, int F, const Scoring &sc, int force_g, int force_k)
     : device_(device), R_(R), F_(F), sc_(sc) {
@@ -23,6 +35,14 @@ Engine::Engine(int device, int R, int F, const Scoring &sc, int force_g, int for
         throw std::runtime_error("device is " + arch_ + "; this library carries gfx950 code only");
     force_g_ = force_g;
     force_k_ = force_k;
+    // The side tile is in no table: forcing it forces the SCORE launches (score_plan_for), and everything else the engine does
+    // plans as an unforced engine of this shape would -- the tile has no other kernel.
+    side_forced_ = tilt_tables_only(force_g, force_k);
+    if (side_forced_) {
+        if (R_ > kSideTileRows)
+            throw std::runtime_error("the forced kernel geometry does not fit read_length=" + std::to_string(R) + ", ref_length=" + std::to_string(F));
+        force_g = force_k = 0;
+    }
     plan_ = choose_plan(R_, F_, force_g, force_k);
     align_resident_ = plan_;
     // Reads of more than 1 536 rows would take the 64 x 32 geometry -- 45 to 53 KB of LDS, three waves per CU --: the long-read
@@ -99,7 +119,13 @@ std::string Engine::host_phases() const {
 }
 
 std::string Engine::describe(int opt, long long n) const {
-    const long long ppb = (long long)plan_.pairs_per_wave * plan_.waves_per_block;
+    // the launch plan of a SCORE call of (opt, n): the engine's -- or the 8 x 19 side tile where score_device would take it
+    // (score_plan_for and few_pairs: the decision score_device makes)
+    LaunchPlan shown = plan_;
+    const int alg_shown = opt & 0xF;
+    if (alg_shown <= kAlgNW && !plan_.long_mode && band_width_ == 0 && !score_wide_cells(alg_shown))
+        shown = score_plan_for(plan_, alg_shown, R_, F_, few_pairs(n), false);
+    const long long ppb = (long long)shown.pairs_per_wave * shown.waves_per_block;
     int band_rows = 0, band_align = 0;
     band_block_shape(band_rows, band_align);
     char buf[4096];
@@ -117,9 +143,9 @@ std::string Engine::describe(int opt, long long n) const {
              "\"ran_subopt\": \"%s\", \"subopt_scratch_bytes\": %lld, \"subopt_ring_cols\": %d, \"ran_extend\": \"%s\", \"extend_wide\": %d, "
              "\"ran_score_geometry\": \"%s\", \"ran_align_geometry\": \"%s\", "
              "\"ran_placed_geometry\": \"%s\", \"ran_subopt_geometry\": \"%s\", \"ran_extend_geometry\": \"%s\"}",
-             arch_.c_str(), device_, opt & 0xF, sc_.affine ? 1 : 0, plan_.geo->G, plan_.geo->K,
-             plan_.geo->G * plan_.geo->K, plan_.pairs_per_wave, plan_.waves_per_block, plan_.lds.total,
-             plan_.lds.total * plan_.waves_per_block, F_ + plan_.geo->G - 1, n > 0 ? (n + ppb - 1) / ppb : 0,
+             arch_.c_str(), device_, opt & 0xF, sc_.affine ? 1 : 0, shown.geo->G, shown.geo->K,
+             shown.geo->G * shown.geo->K, shown.pairs_per_wave, shown.waves_per_block, shown.lds.total,
+             shown.lds.total * shown.waves_per_block, F_ + shown.geo->G - 1, n > 0 ? (n + ppb - 1) / ppb : 0,
              plan_.long_mode ? 1 : 0, band_width_, ragged_, host_stats_.launches,
              host_stats_.cells_padded > 0 ? host_stats_.cells_swept / host_stats_.cells_padded : 1.0,
              score_cell_format(opt & 0xF, n), host_stats_.direct, host_stats_.packed, host_stats_.direct_out,
@@ -137,6 +163,9 @@ std::string Engine::describe(int opt, long long n) const {
     if (ran_score_sym_affine_)          // only where the last score call ran the int16 symmetric affine SW kernel
         out.insert(out.size() - 1, std::string(", \"ran_score_sym_affine\": \"") + ran_score_sym_affine_ + "\", \"ran_score_sym_affine_frame\": \"" +
                                        ran_score_sym_affine_frame_ + "\", \"ran_score_sym_affine_scores\": \"" + ran_score_sym_affine_scores_ + "\"");
+    // ... and, where its last such launch ran on the 8 x 19 side tile, which form of the row-table step its waves took
+    if (ran_score_sym_affine_ && ran_score_geo_ == &kSideGeometry)
+        out.insert(out.size() - 1, std::string(", \"ran_score_sym_affine_form\": \"") + ran_side_tile_form() + "\"");
     return out;
 }
 
@@ -199,7 +228,9 @@ LaunchPlan Engine::choose_plan(int R, int F, int force_g, int force_k, bool late
         // lane-steps per pair, weighted by instructions per step: per-row work + fixed part, measured
         // on the score kernels (5.6 / 9.3 packed instructions per register, linear / affine), and a
         // penalty for long register tiles, which lose occupancy (16x12: +14 %, 16x16: +35 %,
-        // 8x20: +60 % per step over the linear estimate; tools/shape_sweep.sh)
+        // 8x20: +60 % per step over the linear estimate; tools/shape_sweep.sh).  (The penalty dates from kernels bound by
+        // the LDS profile and by occupancy.  The row-table path of the int16 symmetric affine SW sweep is bound by neither:
+        // its 8 x 19 side tile is no entry of this table and is not costed here -- score_plan_for takes it by rule.)
         double per_step = g.K * (sc_.affine ? 9.3 : 5.6) + 7.0;
         if (g.K > 10) per_step *= 1.0 + 0.06 * (g.K - 10);
         double cost = (double)(F + g.G - 1) * per_step * g.G / 2.0;
@@ -219,6 +250,45 @@ LaunchPlan Engine::choose_plan(int R, int F, int force_g, int force_k, bool late
     return best;
 }
 
+LaunchPlan Engine::side_plan(int R, int F) {
+    LaunchPlan p;
+    p.geo = &kSideGeometry;
+    p.lds = kSideGeometry.lds(R, F);
+    p.waves_per_block = kSideTileBlockWaves;
+    p.pairs_per_wave = 2 * (kWave / kSideTileG);
+    return p;
+}
+
+const char *Engine::side_tile_refusal(int alg, int R, int F, bool latency) const {
+    const RuleInputs in = rule_inputs();
+    const int gaps = alg <= kAlgNW ? score_gap_form(in, alg, R, F, kSideTileRows) : -1;
+    return sym_affine_side_tile_refusal(in, alg, gaps, R, F, latency, side_forced_);
+}
+
+const char *Engine::ran_side_tile_form() const {
+    if (!d_form_seen_.get()) return "none";
+    unsigned seen[2] = {0, 0};
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    hip_check(hipMemcpy(seen, d_form_seen_.get(), sizeof seen, hipMemcpyDeviceToHost), "hipMemcpy(form words)");
+    return seen[0] && seen[1] ? "both" : (seen[1] ? "row_tables_repair" : (seen[0] ? "row_tables" : "none"));
+}
+
+void Engine::reset_side_tile_form(hipStream_t stream) {
+    if (!d_form_seen_.get()) return;             // (allocated by the first 8 x 19 launch, zeroed there)
+    if (stream) hip_check(hipMemsetAsync(d_form_seen_.get(), 0, 2 * sizeof(unsigned), stream), "hipMemsetAsync(form words)");
+    else hip_check(hipMemset(d_form_seen_.get(), 0, 2 * sizeof(unsigned)), "hipMemset(form words)");
+}
+
+LaunchPlan Engine::score_plan_for(const LaunchPlan &base, int alg, int R, int F, bool latency, bool refuse) const {
+    const bool chosen = (force_g_ || force_k_) && !side_forced_;         // another forced geometry is a forced geometry
+    if (chosen) return base;
+    const char *refusal = side_tile_refusal(alg, R, F, latency);
+    if (!refusal[0]) return side_plan(R, F);
+    if (side_forced_ && refuse) throw std::runtime_error(std::string("group_lanes = 8, rows_per_lane = 19: ") + refusal);
+    return base;
+}
+
 LaunchPlan Engine::long_plan() {        // row strips + column phases: any length the ABI allows
     LaunchPlan p;
     p.long_mode = true;
@@ -230,10 +300,18 @@ LaunchPlan Engine::long_plan() {        // row strips + column phases: any lengt
     return p;
 }
 
-long long Engine::whole_rounds(long long pairs) const {
+long long Engine::whole_rounds(long long pairs, bool sw_scores) const {
     if (plan_.long_mode || !plan_.geo || cu_count_ <= 0) return pairs;
     const long long waves_per_cu = std::min<long long>(32, (kMaxBlockLds / std::max(1, plan_.lds.total * plan_.waves_per_block)) * plan_.waves_per_block);
-    const long long round_pairs = std::max<long long>(1, waves_per_cu) * cu_count_ * plan_.pairs_per_wave;
+    long long round_pairs = std::max<long long>(1, waves_per_cu) * cu_count_ * plan_.pairs_per_wave;
+    // ... and where this engine's Smith-Waterman score calls take the 8 x 19 side tile, of that plan's rounds too (two 4-wave
+    // blocks per CU, 16 pairs per wave: 32,768 pairs on 256 CUs, a multiple of the 16,384 of 16 x 10)
+    if (sw_scores && !((force_g_ || force_k_) && !side_forced_) && !side_tile_refusal(kAlgSW, R_, F_, false)[0]) {
+        const LaunchPlan side = side_plan(R_, F_);
+        const long long side_waves = std::min<long long>(32, (kMaxBlockLds / std::max(1, side.lds.total * side.waves_per_block)) * side.waves_per_block);
+        const long long side_round = std::max<long long>(1, side_waves) * cu_count_ * side.pairs_per_wave;
+        round_pairs = round_pairs / std::gcd(round_pairs, side_round) * side_round;
+    }
     return pairs >= round_pairs ? pairs / round_pairs * round_pairs : pairs;
 }
 

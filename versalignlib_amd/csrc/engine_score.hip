@@ -17,11 +17,14 @@ void Engine::score_device(int opt, long long n, const uint8_t *d_reads, const ui
         ran_score_cells_ = 0;
         ran_score_geo_ = nullptr;
         ran_score_sym_affine_ = nullptr;
+        reset_side_tile_form(stream);
     }
     if (score_width_ == 16 && !score_int16_ok(alg))
         throw std::runtime_error("shape x scoring can leave the int16 range of the DP cells (read_length " +
                                  std::to_string(R_) + ", ref_length " + std::to_string(F_) + ")");
     const bool wide = score_wide_cells(alg);
+    if (side_forced_ && (plan_.long_mode || wide || band_width_ > 0))
+        throw std::runtime_error("group_lanes = 8, rows_per_lane = 19: the call takes the long-read kernels (a band, int32 cells, or a reference too long for the register sweep)");
     if (plan_.long_mode || wide) {      // int32 cells exist on the strip path only
         score_long_device(alg, n, d_reads, d_refs, d_scores, stream);
         return;
@@ -44,8 +47,8 @@ void Engine::score_device(int opt, long long n, const uint8_t *d_reads, const ui
         if (swept) return;
     }
     // a batch that leaves most SIMDs with at most one wave is over when its slowest wave is: shortest sweep
-    const bool few = n <= (long long)latency_plan_.pairs_per_wave * 1024 && band_width_ == 0;
-    launch_score(few ? latency_plan_ : plan_, alg, R_, F_, n, d_reads, d_refs, d_scores, stream);
+    const bool few = few_pairs(n);
+    launch_score(score_plan_for(few ? latency_plan_ : plan_, alg, R_, F_, few), alg, R_, F_, n, d_reads, d_refs, d_scores, stream);
 }
 
 void Engine::launch_score(const LaunchPlan &plan, int alg, int R, int F, long long n, const uint8_t *d_reads,
@@ -59,6 +62,7 @@ void Engine::launch_score(const LaunchPlan &plan, int alg, int R, int F, long lo
     a.R = R;
     a.F = F;
     a.n_groups = n_groups;
+    a.form_seen = nullptr;
     const long long pairs_per_block = (long long)plan.pairs_per_wave * plan.waves_per_block;
     long long blocks = (n + pairs_per_block - 1) / pairs_per_block;
     if (n_groups > 0) {
@@ -81,6 +85,7 @@ void Engine::launch_score(const LaunchPlan &plan, int alg, int R, int F, long lo
     put_scoring(a);
     const int gaps = score_gap_form(rule_inputs(), alg, R, F, plan.geo->G * plan.geo->K);
     const void *fn = plan.geo->kernel[alg][gaps];
+    if (!fn) throw std::runtime_error("no score kernel of this gap form on " + ran_geometry(plan.geo));      // (the side geometry has one)
     ran_score_cells_ |= gap_form_f16(gaps) ? kRanF16 : kRanInt16;
     ran_score_geo_ = plan.geo;
     // int16 symmetric affine Smith-Waterman: the biased three-operand-maximum form inside its window, else gap sources.  Asked
@@ -95,8 +100,18 @@ void Engine::launch_score(const LaunchPlan &plan, int alg, int R, int F, long lo
         if (tilted) a.sym_max3_bias = sym_affine_tilt_bias(sc_) | 1 << 16;
         // ... and in the tilted frame the substitution scores from row tables in registers where every one of them is a byte (bit
         // 17): that set-up builds no profile and lays the wave's LDS out its own way, never larger than the plan's
-        const WaveLds tables_lds = row_table_lds(plan.geo->G, R, F);
+        // (the 8 x 19 side tile runs nothing else: its plan's LDS IS the tables', with the compact stream)
+        const WaveLds tables_lds = tilt_tables_only(plan.geo->G, plan.geo->K) ? plan.lds : row_table_lds(plan.geo->G, R, F);
         const bool row_tables = tilted && sym_affine_row_tables_ok(rule_inputs(), R_, F_, plan.geo->G * plan.geo->K, plan.geo->K, plan.lds.total, tables_lds.total);
+        // (that tile's kernel runs nothing else and would write no score: score_plan_for hands it out only where this holds)
+        if (tilt_tables_only(plan.geo->G, plan.geo->K)) {
+            if (!row_tables) throw std::runtime_error("the 8 x 19 side tile was planned for a launch whose row tables are refused");
+            if (!d_form_seen_.get()) {
+                d_form_seen_.reserve(2 * sizeof(unsigned), "side tile form words");
+                hip_check(hipMemset(d_form_seen_.get(), 0, 2 * sizeof(unsigned)), "hipMemset(form words)");      // (once per engine, before any launch reads the pointer)
+            }
+            a.form_seen = d_form_seen_.get();
+        }
         if (row_tables) {
             a.sym_max3_bias |= 1 << 17;
             a.prof_area = tables_lds.prof_area;
@@ -132,11 +147,11 @@ void Engine::launch_unpack(const uint8_t *d_packed, uint8_t *d_out, long long n,
               "hipLaunchKernel(unpack_kernel)");
 }
 
-long long Engine::host_chunk_pairs(bool shared_scratch, long long n) const {
+long long Engine::host_chunk_pairs(bool shared_scratch, long long n, bool sw_scores) const {
     const size_t per_pair = (size_t)R_ + F_;
     const size_t chunk_bytes = shared_scratch && !dbg_.on("chunk_bytes") ? std::max<size_t>(score_chunk_bytes_, 192u << 20) : score_chunk_bytes_;
     long long chunk = per_pair ? (long long)(chunk_bytes / per_pair) : n;
-    chunk = whole_rounds(chunk);
+    chunk = whole_rounds(chunk, sw_scores);
     chunk = std::max<long long>(chunk, 1024);
     return std::min<long long>(chunk, n);
 }
@@ -247,8 +262,10 @@ void Engine::score_host(int opt, int n, const char *const *reads, const char *co
     // single-strip instances (short reads against a long reference).
     const bool shared_scratch = (plan_.long_mode || score_wide_cells(alg)) && long_mode(alg, false).brow;
     const bool strips_in_turn = plan_.long_mode && shared_scratch;
-    const long long chunk = host_chunk_pairs(strips_in_turn, n);
+    const bool sw_scores = alg == kAlgSW;
+    const long long chunk = host_chunk_pairs(strips_in_turn, n, sw_scores);
     reset_pipeline();
+    reset_side_tile_form(nullptr);
     ensure_staging(chunk);
     if (threads < 1) threads = 1;
     threads = std::min(threads, 64);
@@ -308,7 +325,7 @@ void Engine::score_host(int opt, int n, const char *const *reads, const char *co
     // then half a chunk); chunks of many calls deep in the pipeline stay large (fewer launches, full waves).
     long long chunk_no = 0, cnt = 0;
     for (long long begin = 0; begin < n; begin += cnt, slot = (slot + 1) % kSlots, ++chunk_no) {
-        const long long ramp = (n > 2 * chunk) ? (chunk_no == 0 ? whole_rounds(chunk / 4) : (chunk_no == 1 ? whole_rounds(chunk / 2) : chunk)) : chunk;
+        const long long ramp = (n > 2 * chunk) ? (chunk_no == 0 ? whole_rounds(chunk / 4, sw_scores) : (chunk_no == 1 ? whole_rounds(chunk / 2, sw_scores) : chunk)) : chunk;
         cnt = std::min<long long>(std::max<long long>(ramp, 1024), n - begin);
         wait_slot(slot, drain);                 // the result of the chunk that used this slot
         // kernels that share a scratch (strip boundary rows) stay on one stream
@@ -486,8 +503,8 @@ bool Engine::ragged_finish(int c, int alg, long long n, int16_t *d_scores, hipSt
         size_t end = first;
         int widest = 0;
         while (end < groups.size() && groups[end].R == groups[first].R) widest = std::max(widest, groups[end++].F);
-        launch_score(class_plan(groups[first].R, widest), alg, groups[first].R, widest, 0, x.reads.get(), x.refs.get(), x.scores.get(), stream,
-                     groups.data() + first, (int)(end - first));
+        launch_score(score_plan_for(class_plan(groups[first].R, widest), alg, groups[first].R, widest, false), alg, groups[first].R, widest, 0,
+                     x.reads.get(), x.refs.get(), x.scores.get(), stream, groups.data() + first, (int)(end - first));
         host_stats_.launches += 1;
         first = end;
     }

@@ -17,6 +17,12 @@
 // the lane key on the 15 geometries of up to 16 rows per lane, the asymmetric ones on the five full geometries among them, and
 // the four per-row forms on the six full geometries and 64 x 24.  VALIGN_PLACED_KERNELS instantiates a geometry's table.
 // Two instances are compiled but unselectable: SW tag_prof_key on 64 x 24 and 64 x 32 (prof_key_ok, cell_rules.h, needs K <= 16).
+// ONE SIDE GEOMETRY stands outside the table: 8 x 19, 152 rows, with ONE kernel -- score_kernel<8, 19, kAlgSW, kGapAffineSym>, the
+// tilted sweep's row-table forms (cell_constants.h: tilt_tables_only).  It is not an 18th geometry: no fill, placed, suboptimal or
+// extension kernel exists for it, nothing is re-planned onto it, and the counts above (17 geometries, 68 / 44 / 24) stand.  The
+// engine takes it for int16 symmetric affine Smith-Waterman scores of reads of 129 .. 152 bases where cell_rules.h:
+// sym_affine_side_tile_refusal has nothing to refuse.  VALIGN_SIDE_KERNELS names it; it is compiled in part VALIGN_SIDE_PART, the
+// lightest one (part 1 finishes first and is the smallest object).
 #pragma once
 
 #include "dp_kernels.hip.h"
@@ -33,6 +39,8 @@
 #define VALIGN_PART4(X, Y) X(32, 10) Y(16, 12) Y(64, 12)
 #define VALIGN_PART5(X, Y) X(64, 8) X(8, 8) Y(32, 8) Y(32, 12)
 #define VALIGN_KERNEL_PARTS 6
+#define VALIGN_SIDE_PART 1
+#define VALIGN_SIDE_KERNELS(PREFIX) PREFIX __global__ void score_kernel<kSideTileG, kSideTileK, kAlgSW, kGapAffineSym>(const ScoreArgs);
 
 #define VALIGN_ALL_PARTS(X, Y) VALIGN_PART0(X, Y) VALIGN_PART1(X, Y) VALIGN_PART2(X, Y) VALIGN_PART3(X, Y) VALIGN_PART4(X, Y) VALIGN_PART5(X, Y)
 

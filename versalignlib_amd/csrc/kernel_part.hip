@@ -31,5 +31,8 @@ VALIGN_PART5(VALIGN_DEFINE_FULL, VALIGN_DEFINE_FAST)
 #else
 #error "VALIGN_PART out of range"
 #endif
+#if VALIGN_PART == VALIGN_SIDE_PART
+VALIGN_SIDE_KERNELS(template)
+#endif
 
 }  // namespace valign
