@@ -5,7 +5,9 @@
 //      (128 / 129, 152 / 153), the three debug words, the bytes of the row tables (255 / 256, 0 / -1), the tilted window,
 //      the LDS budget (two 4-wave blocks per CU with a margin), the latency plan;
 //   3. a forced tile: no lower bound on the read and no latency plan, everything else as it stands;
-//   4. the older rules answer as before whatever the new switch says.
+//   4. the older rules answer as before whatever the new switch says;
+//   5. the numbers the GPU edge tests run at, as literals: the last reference the LDS budget takes (558, 19,456 B per wave), the
+//      stream stride's five values and where each begins, the last match score inside the tilted window per shape and scoring.
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -139,6 +141,55 @@ int main() {
         in.no_side_tile = true;
         CHECK(tilt && tables && sym_affine_tilt_ok(in, 150, 500, 160, 10) && sym_affine_row_tables_ok(in, 150, 500, 160, 10, 1000, 1000));
         CHECK(score_gap_form(in, kAlgSW, 150, 500, 160) == form);
+    }
+
+    // 5. the literals tests/test_gpu_sym_affine_side_tile_edges.py runs the kernel at: they are THIS arithmetic's, so a header that
+    //    moves an edge fails here and not by silently moving what the GPU tests cover
+    {
+        // the LDS budget's edge: F = 558 fills two 4-wave blocks to the byte, whatever the read (the streams are the larger area)
+        for (int R : {129, 150, 152}) {
+            int last = 0;
+            for (int F = 1; F < 2000; ++F)
+                if (side_tile_lds_ok(side_tile_wave_lds(R, F))) last = F;
+            CHECK(last == 558);
+            CHECK(side_tile_wave_lds(R, 558) == 19456 && side_tile_wave_lds(R, 559) == 19472);
+            CHECK(2 * kSideTileBlockWaves * side_tile_wave_lds(R, 558) == kSideTileLdsBudget);
+            CHECK(why(inputs(bench, R, 558), kAlgSW, kGapAffineSym, false, true).empty());
+            CHECK(has(why(inputs(bench, R, 559), kAlgSW, kGapAffineSym, false, true), "too long for its LDS budget"));
+        }
+        // the stream stride's steps: five values up to the budget's edge, and the reference length at which each begins
+        const int strides[5][2] = {{1, 288}, {121, 544}, {249, 800}, {377, 1056}, {505, 1312}};
+        int step = 0, prev = 0;
+        for (int F = 1; F <= 559; ++F) {
+            const int s = side_tile_stream_stride(F);
+            if (s != prev) {
+                CHECK(step < 5 && strides[step][0] == F && strides[step][1] == s);
+                ++step;
+                prev = s;
+            }
+            CHECK(s % 256 == 32 && s >= 2 * (F + 2 * kSideTilePad));         // 8 (mod 64) dwords, and room for every column and both pads
+        }
+        CHECK(step == 5);
+        // the tilted window's edge on 152 rows of 19: the last match score the forced tile runs, the first it refuses -- by the
+        // window, not by the bytes, which pass at both
+        const struct {
+            int R, F, mismatch, open, ext, edge;
+        } edges[] = {{152, 152, -1, -5, -1, 200}, {152, 558, -1, -5, -1, 197},  {150, 500, -1, -5, -1, 200},
+                     {152, 558, -20, -24, -20, 108}, {133, 558, -20, -24, -20, 124}};
+        for (const auto &e : edges) {
+            const Scoring at = aff(e.edge, e.mismatch, e.open, e.ext), past = aff(e.edge + 1, e.mismatch, e.open, e.ext);
+            CHECK(why(inputs(at, e.R, e.F), kAlgSW, kGapAffineSym, false, true).empty());
+            CHECK(has(why(inputs(past, e.R, e.F), kAlgSW, kGapAffineSym, false, true), "sym_affine_row_tables_ok"));
+            CHECK(sym_affine_tilt_ok(inputs(at, e.R, e.F), e.R, e.F, kSideTileRows, kSideTileK) &&
+                  !sym_affine_tilt_ok(inputs(past, e.R, e.F), e.R, e.F, kSideTileRows, kSideTileK));
+            CHECK(sym_affine_max3_ok(inputs(past, e.R, e.F), e.R, e.F));                 // (the plain biased form's window is not what refuses)
+            for (const Scoring &sc : {at, past}) CHECK(sym_affine_row_table_low(sc) >= 0 && sym_affine_row_table_high(sc) <= 255 && sc.ext_ref - sc.open_ref >= 0);
+            const long long lead = (kSideTileRows - e.R) / kSideTileK, top = kSideTileRows + e.F - lead;
+            CHECK(sym_affine_tilt_top_index(e.R, e.F, kSideTileRows, kSideTileK) == top);
+            const long long B = sym_affine_tilt_bias(at), room = kMax3WindowHigh - 1 - B - (long long)-e.ext * top;
+            CHECK(B == sym_affine_tilt_bias(past) && room / std::min(e.R, e.F) == e.edge);
+        }
+        CHECK(sym_affine_tilt_top_index(133, 558, kSideTileRows, kSideTileK) == 709 && sym_affine_tilt_top_index(152, 558, kSideTileRows, kSideTileK) == 710);
     }
 
     if (failures) {

@@ -94,10 +94,11 @@ def _ran_tile(d, what):
 
 
 def _forced(R, F, scoring, batch, counts, form=None):
-    """form: what ran_score_sym_affine_form must say after every call (None: one of the three it can)"""
+    """form: what ran_score_sym_affine_form must say after every call (None: one of the three it can); -> what it said, per call"""
     reads, refs, _ = batch
     exp = _expected(batch, scoring)
     eng = _engine(R, F, scoring)
+    seen = []
     for n in counts:
         got = eng.score_device(host.SW, _device(reads[:n].copy()), _device(refs[:n].copy())).cpu().numpy()
         what = (R, F, scoring, n)
@@ -106,7 +107,9 @@ def _forced(R, F, scoring, batch, counts, form=None):
         d = eng.describe(host.SW, n)
         _ran_tile(d, what)
         assert d["ran_score_sym_affine_form"] == form if form else d["ran_score_sym_affine_form"] in FORMS, what + (d["ran_score_sym_affine_form"],)
+        seen.append(d["ran_score_sym_affine_form"])
     eng.close()
+    return seen
 
 
 # ---- a. rows x columns x pairs ----

@@ -11,7 +11,9 @@ tables, plain and repairing form -- with what an odd K changes:
   * the selector stream is the compact one: 16 bits per column, {ca, 4 + cb}, widened to {ca, 0x0c, 4 + cb, 0x0c} by one byte
     permute against 0x0c0c0c0c -- restated with the permute's own selector constant, both pairs of a register.
 
-Scores are compared exactly with oracle.cpu_ref.score; the even-K models of the older file run through this restatement too."""
+Scores are compared exactly with oracle.cpu_ref.score; the even-K models of the older file run through this restatement too.
+At the last match score the rule admits on 8 x 19 (side_tile_edge_match) the operands of every maximum are collected and bounded:
+the constructions of tests/test_gpu_sym_affine_side_tile_edges.py (edge_quarters), whose operands the GPU cannot show."""
 import numpy as np
 import pytest
 
@@ -222,6 +224,78 @@ def test_the_8x19_tile(shape):
     _check(read, ref, SCORING, 8, 19, cols=F + 2)
     read = np.frombuffer(b"NnXN" * R, dtype=np.uint8)[:R]
     assert _check(read, ref, SCORING, 8, 19)[0] == 0
+
+
+def side_tile_edge_match(R, F, mismatch, gap_open, gap_ext, top_index=None):
+    """The last match score cell_rules.h: sym_affine_tilt_ok lets the 8 x 19 tile run on R x F, restated:
+    B + x * (rows + F - lead) + min(R, F) * match + 1 <= 0x7BFF.  top_index: another top index than the rule's."""
+    B, x = tilt_bias(1, mismatch, gap_open, gap_ext), -gap_ext
+    top = frame.tilt_top_index(R, F, 8, 19) if top_index is None else top_index
+    match = (frame.WINDOW[1] - 1 - B - x * top) // min(R, F)
+    assert match > 0 and tilt_bias(match, mismatch, gap_open, gap_ext) == B
+    # ... inside the plain biased form's window (sym_affine_max3_ok) and the bytes of the row tables, one match score further too
+    plain = 1024 - gap_open - gap_ext + max(0, -mismatch)
+    assert plain - 1024 <= 1024 and plain + min(R, F) * (match + 1) + 1 <= frame.WINDOW[1]
+    assert rule_ok(match + 1, mismatch, gap_open, gap_ext)
+    return match
+
+
+def edge_quarters(R, F, seed):
+    """The four constructions that put the largest score a shape holds against the top of the tilted window: the read is the
+    reference's LAST R bases (the full score lands in the last row at the last column, where the tilt is largest), its FIRST R
+    bases (the maximum is found early and rides the accumulators to the top index), and each again with one N inside the
+    matched piece of the reference (one base short, the repairing form).  -> [(name, read, ref, clean)]"""
+    assert F >= R
+    rng = np.random.default_rng(seed)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    out = []
+    for name, at in (("last", F - R), ("first", 0)):
+        ref = acgt[rng.integers(0, 4, size=F)].copy()
+        read = ref[at:at + R].copy()
+        out.append((name, read, ref, True))
+        dirty = ref.copy()
+        dirty[at + int(rng.integers(1, R - 1))] = ord("N")
+        assert needs_repair(dirty)
+        out.append((name + "-N", read, dirty, False))
+    return out
+
+
+EDGE_SCORINGS = ((-1, -5, -1), (-20, -24, -20))          # (mismatch, open, extend): score-dominated, tilt-dominated (x = 20: 380 per trip)
+EDGE_MATCHES = {(152, 152, -1): 200, (152, 152, -20): 161, (133, 160, -1): 228, (133, 160, -20): 184}
+
+
+@pytest.mark.parametrize("gaps", EDGE_SCORINGS, ids=lambda s: "%d_%d_%d" % s)
+@pytest.mark.parametrize("shape", ((152, 152), (133, 160)), ids=lambda s: "%dx%d" % s)
+def test_the_8x19_tile_at_the_windows_upper_edge(monkeypatch, shape, gaps):
+    """The last match score the rule admits on the 8 x 19 tile: the sweep is the oracle and EVERY operand of every maximum, the
+    accumulators included (acc[slot] += K x once per trip, up to the top index), lies in [0x0400, 0x7BFF] -- seen here, operand
+    by operand, where a GPU test could only infer it from a wrong score.  The largest operand is the rule's own bound less its
+    one spare unit where the full score lands in the last cell, and within two trips of it where it is carried there."""
+    R, F = shape
+    mismatch, gap_open, gap_ext = gaps
+    match = side_tile_edge_match(R, F, mismatch, gap_open, gap_ext)
+    assert match == EDGE_MATCHES[(R, F, mismatch)]
+    scoring = (match, mismatch, gap_open, gap_ext)
+    B, x, top = tilt_bias(*scoring), -gap_ext, frame.tilt_top_index(R, F, 8, 19)
+    assert B + x * top + R * match + 1 <= frame.WINDOW[1] < B + x * top + R * (match + 1) + 1
+    seen = []
+    real = frame._hmax
+
+    def spy(*patterns):
+        seen.extend(patterns)
+        return real(*patterns)
+
+    monkeypatch.setattr(frame, "_hmax", spy)
+    for name, read, ref, clean in edge_quarters(R, F, seed=R + F):
+        del seen[:]
+        exp = _oracle(read, ref, *scoring)
+        got = sweep_score(read, ref, *scoring, 8, 19, TABLES if clean else REPAIR)
+        assert got == exp and (exp == R * match if clean else (R - 1) * match <= exp < R * match), (name, got, exp)
+        assert frame.WINDOW[0] <= min(seen) and max(seen) <= B + x * top + R * match, (name, hex(min(seen)), hex(max(seen)))
+        if clean and name == "last":
+            assert max(seen) == B + x * top + R * match, (name, max(seen))
+        elif clean:
+            assert max(seen) >= B + x * (top - 2 * 19) + R * match, (name, max(seen))
 
 
 def test_one_matching_base_at_every_cell():
