@@ -589,8 +589,9 @@ int valign_hip_score_subopt_host(valign_hip_engine *e, int opt, int n, const cha
  *   Rp = 0 ...... the record is five zeros.
  * Columns at or beyond Fp are not candidates for gscore: padding scores 0 against anything, and a read longer than the trimmed
  * reference would otherwise ride its tail down the padding for free.
- * NOT BUILT: Z-drop or X-drop termination -- every cell is swept; an end bonus -- the caller compares gscore + bonus with score
- * itself.  ragged_batching and half_float_cells are not read.
+ * NOT BUILT: Z-drop or X-drop termination -- every cell is swept.  An end bonus is not part of the scores -- the caller compares
+ * gscore + bonus with score itself; extension alignments (valign_hip_align_extend_*, below) take it as the rule that picks the end
+ * cell they walk from.  ragged_batching and half_float_cells are not read.
  * REFUSED with a non-zero return, a message in valign_hip_last_error and "ran_extend": "none": opt & 0xF == 1;
  * traceback_policy = 1; band_width > 0, WHATEVER band_placed says; score_width = 32, WHATEVER placed_wide says; a shape x
  * scoring whose cells could leave int16 -- signed cells: min(R, F) * max(match, mismatch, 0) above 32000, or the all-gaps path
@@ -635,9 +636,61 @@ int valign_hip_score_extend_host(valign_hip_engine *e, int opt, int n, const cha
  * it: calls of one engine that use it belong on one stream); per pair it also holds a 20-byte partial record and the two trimmed
  * lengths.  The host call is the chunk pipeline with the strip path's chunk sizes, on one stream.
  * KNOWN: a short read fills a fraction of its one 512-row strip, as on the placed int32 sweep -- the register sweep is the route
- * for short reads wherever the rule lets it run.  Z-drop, a band around the anchor's diagonal and an end bonus remain unbuilt.
+ * for short reads wherever the rule lets it run.  Z-drop and a band around the anchor's diagonal remain unbuilt; extension
+ * alignments (below) refuse the calls this key moves to the int32 sweep.
  * "extend_wide" of valign_hip_describe is the key.                                                                           */
 int valign_hip_set_extend_wide(valign_hip_engine *e, int on);
+
+/* ---- extension alignments: the CIGAR of an extension, from the anchor to the chosen end cell ----
+ * Extension scores say how far to extend and whether to go end-to-end or clip; this call returns the alignment of that extension.
+ * No other alignment call can: Smith-Waterman has a free start and a floor at zero, the NW variant a free row 0, spanned CIGARs
+ * place a local alignment.  Here both borders are gap-priced, the path is forced through the anchor, and the walk runs from a
+ * given end cell back to (-1, -1).
+ * DEFINITION, for opt & 0xF == 0, per pair, with X, Rp, Fp, score, read_end, ref_end, gscore and gref_end exactly as the
+ * extension scores define them (above):
+ *   end cell .... end_bonus < 0: the best cell (read_end - 1, ref_end - 1).  end_bonus >= 0: the read end (Rp - 1, gref_end - 1)
+ *                 if Rp > 0 and (int64) gscore + end_bonus >= score, otherwise the best cell; the column may be the border
+ *                 column -1.  |gscore| <= 32000 on this route, so end_bonus = INT32_MAX means "always the read end".  Ties go to
+ *                 the read end.
+ *   empty ....... the best cell was chosen and score == 0, or Rp == 0: an all-zero record and no ops.
+ *   walk ........ from the end cell back to (-1, -1), decided on cell values.  Linear gaps, at an interior cell: DIAG if
+ *                 X(i,j) == X(i-1,j-1) + S(i,j), else UP if X(i,j) == X(i-1,j) + gap_ref, else LEFT (the Default priority).
+ *                 Affine gaps: the library's three-state rule -- at H: DIAG if h == diag, else the vertical state if h == f, else
+ *                 the horizontal state; inside a gap state: emit one column, then stay in the state iff its value differs from
+ *                 its "open" candidate (f != f_open, e != e_open), otherwise return to H.  On a border cell the walk is at H and
+ *                 follows the border: UP on column -1, LEFT on row -1 (the gap states do not exist on the borders: a gap run that
+ *                 turns the corner opens again).  It stops at (-1, -1).
+ *   ops ......... the columns in reading order, classified and run-length encoded by the column rule of valign_hip_align_cigar_*
+ *                 (extended: 0 = M, 1 = '=' / X), length << 4 | code.  A first op of I or D is legal: a gap directly after the seed.
+ *   record ...... read_begin = ref_begin = 0; read_end, ref_end: the end cell + 1 (ref_end = 0 for the border column); score: the
+ *                 ops re-scored under the engine's scoring, as in valign_hip_aln.
+ * GUARANTEED: score == X(end cell) -- the extension record's score, or its gscore, whichever end was chosen -- and the ops
+ * consume exactly read_end read bases and ref_end reference bases; for sequences without a literal '-' byte (the caveat of spanned
+ * CIGARs).
+ * Records, ops, ops_stride, n_ops on overflow, offsets, ops_cap, ops_needed, n = 0 and opt & 0xF > 1 follow the contracts of
+ * valign_hip_align_cigar_device / _host exactly.  If d_extend / extend is not null it receives the pair's valign_hip_extend
+ * record, bit for bit what valign_hip_score_extend_device returns.
+ * REFUSED with a non-zero return, a message in valign_hip_last_error and "ran_extend_align": "none": everything
+ * valign_hip_score_extend_device refuses with extend_wide = 0, with the same texts; under extend_wide = 1, any call whose
+ * extension route is "wide", with a text that begins "extension alignments:" (the int32 / row-strip form keeps no back
+ * pointers); extended not 0 or 1; ops_stride < 1; null result buffers.
+ * NOT BUILT: Z-drop / X-drop, a band around the anchor's diagonal, the int32 route.  ragged_batching and half_float_cells are not
+ * read.
+ * The device call is asynchronous on hip_stream.  It is cut into chunks that keep the pointer stream (2 bits per cell, twice that
+ * with affine gaps) under pointer_scratch_cap_mb and the walk's rows under the compact format's rows scratch; the chunks reuse both
+ * in stream order, and both are shared with the other alignment calls: calls of one engine belong on one stream.
+ * "ran_extend_align" of valign_hip_describe is "rows" after a call that ran ("none" before any, or when it was refused),
+ * "ran_extend_align_geometry" the geometry whose fill ran, "extend_align_scratch_bytes" the pointer scratch, end cells and staged
+ * extension records the engine holds.  tests/extend_align_ref.py restates the definition in numpy.                            */
+int valign_hip_align_extend_device(valign_hip_engine *e, int opt, long long n, const void *d_reads, const void *d_refs,
+                                   int end_bonus, int extended, void *d_recs, void *d_ops, int ops_stride,
+                                   void *d_extend /* may be null */, void *hip_stream);
+
+/* Host pointers in, packed results out: chunk after chunk -- gather, H2D, fill, walk, the count pass, the scan, the emit pass and
+ * ONE copy of records, extension records (where asked for) and ops back.                                                      */
+int valign_hip_align_extend_host(valign_hip_engine *e, int opt, int n, const char *const *reads, const char *const *refs,
+                                 int end_bonus, int extended, valign_hip_aln *recs, uint32_t *ops, long long ops_cap,
+                                 long long *offsets, long long *ops_needed, valign_hip_extend *extend /* may be null */, int threads);
 
 /* Page-lock a host range and map it for the device (hipHostRegister behind a C symbol, so that an FFI caller needs no
  * HIP binding).  valign_hip_align_host into result buffers that lie inside a registered range -- or inside memory the
@@ -682,7 +735,8 @@ int valign_hip_set_half_float_cells(valign_hip_engine *e, int mode);
  * valign_hip_align_cigar_host call copied back, "cigar_rows_scratch_bytes" the rows scratch of the compact format.
  * "ran_placed" is what the last placed-score call ran: key / rows / strip / chain / wide ("none" before any, or when it was
  * refused); "band_placed" is the key of valign_hip_set_band_placed, "placed_wide" that of valign_hip_set_placed_wide, "extend_wide" that of valign_hip_set_extend_wide.  "ran_span", "span_ref_length" and "span_scratch_bytes"
- * belong to the spanned scores, "ran_subopt", "subopt_scratch_bytes" and "subopt_ring_cols" to the suboptimal scores, above. */
+ * belong to the spanned scores, "ran_subopt", "subopt_scratch_bytes" and "subopt_ring_cols" to the suboptimal scores,
+ * "ran_extend_align", "ran_extend_align_geometry" and "extend_align_scratch_bytes" to the extension alignments, above.          */
 int valign_hip_describe(valign_hip_engine *e, int opt, long long n, char *buf, int cap);
 
 const char *valign_hip_last_error(void);

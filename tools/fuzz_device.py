@@ -10,7 +10,9 @@ to 160 x 300 with a second, mutated copy of the read planted in the reference; `
 spanned CIGARs (align_span_device / _host against tests/span_cigar_ref.py: random shapes up to 320 x 900 and one in eight on the row
 strips, scorings, extended, ops_stride, trace_checkpoints, pointer_scratch_cap_mb, placed_wide); `--kind extend` draws nothing but
 cases for the extension scores (a third of them extend_wide = 1 cases -- long reads, scorings out of int16, score_width = 32; score_extend_device / _host against tests/extend_ref.py: random shapes up to 200 x 300, the four gap
-forms at several scales, the engine's own or a forced geometry, planted extensions, ragged tails and interior junk).  What tools/fuzz_parity.py does for the plugin ABI, for the entry points the tests of the device path
+forms at several scales, the engine's own or a forced geometry, planted extensions, ragged tails and interior junk); `--kind extend_align`
+draws nothing but cases for the extension alignments (align_extend_device / _host against tests/extend_align_ref.py: the register-sweep
+cases of `--kind extend` with an end bonus, extended, ops_stride, with or without the extension records, pointer_scratch_cap_mb).  What tools/fuzz_parity.py does for the plugin ABI, for the entry points the tests of the device path
 use; a process that runs it for minutes also exercises the library's set-up and tear-down far more often than the suite.
 
     python -X faulthandler tools/fuzz_device.py --seconds 300 --seed 1
@@ -30,6 +32,7 @@ import torch                                                       # noqa: E402
 from oracle import cpu_ref                                          # noqa: E402
 from versalignlib_amd import hipkernel, synth                      # noqa: E402
 import band_nw_ref                                                 # noqa: E402
+import extend_align_ref                                            # noqa: E402
 import extend_ref                                                  # noqa: E402
 import placed_band_ref                                             # noqa: E402
 import placed_ref                                                  # noqa: E402
@@ -393,6 +396,76 @@ def run_extend(c):
         eng.close()
 
 
+def draw_extend_align(rng):
+    """--kind extend_align: draw_extend's register-sweep cases (shape, scoring inside the signed int16 bound, the engine's own or a
+    forced full geometry) with an end bonus -- none, zero, small, of the scale of the scores, or "always the read end" --, extended,
+    an ops_stride that some alignments overflow, and a pointer-scratch cap for some"""
+    c = None
+    while c is None or c.get("wide"):
+        c = draw_extend(rng)
+    top = c["scoring"][0] * min(c["R"], c["F"])
+    c.update(n=min(c["n"], 60), bonus=int(rng.choice([-1, -1, 0, int(rng.integers(1, 12)), int(rng.integers(0, top + 2)), 2 ** 31 - 1, 2 ** 31 - 1])),
+             extended=bool(rng.random() < 0.5), stride=int(rng.choice([1, 2, 5, 64, 700])), cap_mb=int(rng.integers(1, 4)) if rng.random() < 0.2 else 0,
+             with_extend=bool(rng.random() < 0.7))
+    return c
+
+
+def run_extend_align(c):
+    """one extension-alignment case: the device entry (and, for some, the host entry) against tests/extend_align_ref.py -- records,
+    the stored ops with the sentinel behind them untouched, and the extension records"""
+    rng = np.random.default_rng(c["seed"])
+    R, F, n = c["R"], c["F"], c["n"]
+    bases = np.frombuffer(b"ACGT", np.uint8)
+    reads, refs = bases[rng.integers(0, 4, (n, R))], bases[rng.integers(0, 4, (n, F))]
+    for p in range(n):
+        if p % 3 < 2:                       # an extension from the anchor, a third of them behind extra reference bases
+            L, shift = int(rng.integers(1, min(R, F) + 1)), (int(rng.integers(0, 3)) if p % 3 == 1 else 0)
+            span = min(L, F - shift)
+            if span > 0:
+                refs[p, shift:shift + span] = reads[p, :span]
+        if rng.random() < 0.3:
+            reads[p, int(rng.integers(0, R + 1)):] = rng.choice([0, ord("N")])
+        if rng.random() < 0.3:
+            refs[p, int(rng.integers(0, F + 1)):] = rng.choice([0, ord("N")])
+        if rng.random() < 0.2:
+            refs[p, int(rng.integers(0, F))] = rng.choice([0, ord("N"), 0x80, 0xFF])
+    sc = hipkernel.Scoring.make(*c["scoring"])
+    exp_recs, exp_ops, exp_ext, _ = extend_align_ref.align(reads, refs, sc, c["affine"], end_bonus=c["bonus"], extended=c["extended"])
+    eng = hipkernel.Engine(R, F, sc, group_lanes=c["geometry"][0], rows_per_lane=c["geometry"][1])
+    try:
+        if c["cap_mb"]:
+            eng.set_pointer_scratch_cap_mb(c["cap_mb"])
+        stride = c["stride"]
+        recs = torch.full((n, 6), -7, dtype=torch.int32, device="cuda")
+        ops = torch.full((n, stride), -7, dtype=torch.int32, device="cuda")
+        ext = torch.full((n, 5), -7, dtype=torch.int32, device="cuda") if c["with_extend"] else None
+        eng.align_extend_device(0, torch.from_numpy(reads).cuda(), torch.from_numpy(refs).cuda(), end_bonus=c["bonus"], extended=c["extended"],
+                                ops_stride=stride, out=(recs, ops, ext))
+        torch.cuda.synchronize()
+        if eng.describe(0, n)["ran_extend_align"] != "rows":
+            return "align_extend_device ran %s" % eng.describe(0, n)["ran_extend_align"]
+        if not np.array_equal(recs.cpu().numpy().astype(np.int64), exp_recs):
+            return "align_extend_device: records differ"
+        got = ops.cpu().numpy()
+        for p, want in enumerate(exp_ops):
+            k = min(len(want), stride)
+            if got[p, :k].view(np.uint32).tolist() != want[:k] or not (got[p, k:] == -7).all():
+                return "align_extend_device: ops of pair %d differ" % p
+        if ext is not None and not np.array_equal(ext.cpu().numpy().astype(np.int64), exp_ext):
+            return "align_extend_device: extension records differ"
+        if c["host"]:
+            h_recs, h_ops, offsets, h_ext = eng.align_extend_host(0, reads, refs, end_bonus=c["bonus"], extended=c["extended"],
+                                                                  with_extend=c["with_extend"], threads=c["threads"])
+            flat = np.stack([h_recs[k] for k in hipkernel.aln_dtype().names], axis=1).astype(np.int64)
+            if not np.array_equal(flat, exp_recs) or h_ops.tolist() != [o for pair in exp_ops for o in pair]:
+                return "align_extend_host differs"
+            if h_ext is not None and not np.array_equal(np.stack([h_ext[k] for k in hipkernel.extend_dtype().names], axis=1).astype(np.int64), exp_ext):
+                return "align_extend_host: extension records differ"
+        return None
+    finally:
+        eng.close()
+
+
 def soak_sequences(rng, a):
     """--kind sequence: the generator and the runner of tests/engine_sequences.py (what tests/test_gpu_engine_sequences.py runs
     on its committed seeds) on random seeds: ONE engine per sequence through key changes and calls, every call against its
@@ -424,7 +497,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--first", type=int, default=0)
     ap.add_argument("--verbose", action="store_true")
-    ap.add_argument("--kind", choices=["subopt", "sequence", "span_cigar", "extend"], default=None,
+    ap.add_argument("--kind", choices=["subopt", "sequence", "span_cigar", "extend", "extend_align"], default=None,
                     help="draw cases of this kind only (default: the mix); sequence: one engine through tests/engine_sequences.py's sequences")
     a = ap.parse_args()
     rng = np.random.default_rng(a.seed)
@@ -433,12 +506,13 @@ def main():
     t0 = time.time()
     i = done = 0
     while time.time() - t0 < a.seconds:
-        c = draw_span_cigar(rng) if a.kind == "span_cigar" else (draw_extend(rng) if a.kind == "extend" else draw(rng, a.kind))
+        own = {"span_cigar": (draw_span_cigar, run_span_cigar), "extend": (draw_extend, run_extend), "extend_align": (draw_extend_align, run_extend_align)}.get(a.kind)
+        c = own[0](rng) if own else draw(rng, a.kind)
         if i >= a.first:
             if a.verbose:
                 print("case %d: %r" % (i, c), flush=True)
             try:
-                err = run_span_cigar(c) if a.kind == "span_cigar" else (run_extend(c) if a.kind == "extend" else run(c))
+                err = own[1](c) if own else run(c)
             except hipkernel.HipKernelError as e:
                 err = "library error: %s" % e
             done += 1

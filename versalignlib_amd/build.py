@@ -26,12 +26,12 @@ if SANITIZED_DIR:
     HOST_LIB = os.path.join(SANITIZED_DIR, "libvalignhost.so")
     BENCH_CLI = os.path.join(SANITIZED_DIR, "valign-bench")
 
-HIP_SOURCES = ["hip_plugin.hip", "engine_core.hip", "engine_score.hip", "engine_long.hip", "engine_align.hip", "engine_cigar.hip", "engine_placed.hip", "engine_span.hip", "engine_span_cigar.hip", "engine_subopt.hip", "engine_extend.hip"]
+HIP_SOURCES = ["hip_plugin.hip", "engine_core.hip", "engine_score.hip", "engine_long.hip", "engine_align.hip", "engine_cigar.hip", "engine_placed.hip", "engine_span.hip", "engine_span_cigar.hip", "engine_subopt.hip", "engine_extend.hip", "engine_extend_align.hip"]
 HIP_KERNEL_PART = "kernel_part.hip"          # compiled once per part (kernel_instances.hip.h), in parallel
 HIP_KERNEL_PARTS = 6
 # every header (a unit is rebuilt when its own source or any header changes; the kernel parts only look at KERNEL_PART_DEPS)
 HIP_HEADERS = ["kernel_instances.hip.h", "placed_kernels.hip.h", "dp_kernels.hip.h", "trace_kernels.hip.h", "long_kernels.hip.h", "strip_kernels.hip.h",
-               "engine.hip.h", "base_classes.h", "cell_constants.h", "cell_rules.h", "align_parts.h", "ckpt_plan.h", "strip_plan.h", "long_plan.h", "hip_handles.h", "host_runtime.hip.h", "host_pipeline.h", "band_kernels.hip.h", "band_window.h", "pack_kernels.hip.h", "ragged_kernels.hip.h", "cigar_kernels.hip.h", "span_kernels.hip.h", "span_cigar_kernels.hip.h", "placed_wide_kernels.hip.h", "subopt_kernels.hip.h", "extend_kernels.hip.h", "extend_wide_kernels.hip.h"]
+               "engine.hip.h", "base_classes.h", "cell_constants.h", "cell_rules.h", "align_parts.h", "ckpt_plan.h", "strip_plan.h", "long_plan.h", "hip_handles.h", "host_runtime.hip.h", "host_pipeline.h", "band_kernels.hip.h", "band_window.h", "pack_kernels.hip.h", "ragged_kernels.hip.h", "cigar_kernels.hip.h", "span_kernels.hip.h", "span_cigar_kernels.hip.h", "placed_wide_kernels.hip.h", "subopt_kernels.hip.h", "extend_kernels.hip.h", "extend_wide_kernels.hip.h", "extend_align_kernels.hip.h"]
 OBJ = os.path.join(PKG, "build")             # intermediate objects (git-ignored)
 HOST_SOURCES = ["valign_host.cpp"]
 
@@ -75,7 +75,7 @@ def build_host(force=False):
     return HOST_LIB
 
 
-KERNEL_PART_DEPS = ["kernel_part.hip", "kernel_instances.hip.h", "placed_kernels.hip.h", "extend_kernels.hip.h", "dp_kernels.hip.h", "base_classes.h", "cell_constants.h", "trace_kernels.hip.h", "band_window.h", "ckpt_plan.h", "strip_plan.h", "cell_rules.h"]
+KERNEL_PART_DEPS = ["kernel_part.hip", "kernel_instances.hip.h", "placed_kernels.hip.h", "extend_kernels.hip.h", "extend_align_kernels.hip.h", "dp_kernels.hip.h", "base_classes.h", "cell_constants.h", "trace_kernels.hip.h", "band_window.h", "ckpt_plan.h", "strip_plan.h", "cell_rules.h"]
 
 
 def build_hip(force=False, extra_flags=(), jobs=None):

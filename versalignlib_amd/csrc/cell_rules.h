@@ -554,6 +554,46 @@ inline PlacedChoice extend_choice(const RuleInputs &in, int alg, const PlacedFac
     return c;
 }
 
+// ---- extension alignments (valign_hip_align_extend_*): the alignment from the anchor to the end cell the end-bonus rule picks, on
+// the int16 register sweep with a back pointer per cell (extend_align_kernels.hip.h) ----
+// An extension-alignment call is an extension call on the register sweep: refused exactly where extend_choice refuses with
+// extend_wide = 0, with its texts; under extend_wide = 1, where extend_choice answers Wide (or refuses the int32 cells), refused
+// with a text of its own -- the int32 / row-strip form has no back pointers.  Otherwise Rows, and the bytes of pointer stream a
+// wave of the `G x K` geometry writes over `F` reference columns: ceil((F + G - 1) / 8) blocks of 8 steps, 64 lanes, K dwords per
+// lane and block (linear gaps) or 2 K (affine: H codes and gap codes).  G = 0 (no register geometry): 0 bytes.
+struct ExtendAlignChoice {
+    PlacedRoute route = PlacedRoute::Refused;       // Rows or Refused
+    const char *reason = "";                        // Refused: why
+    int blocks8 = 0;                                // 8-step blocks per lane
+    long long wave_ptr_bytes = 0;                   // pointer-scratch bytes of one wave
+};
+constexpr const char *kExtendAlignNoWide = "extension alignments: not built for the int32 / row-strip route of extend_wide = 1 (the extension scores of this call run there)";
+inline long long extend_align_wave_ptr_bytes(int G, int K, int F, bool affine) {
+    if (G <= 0 || K <= 0) return 0;
+    return (long long)((F + G - 1 + 7) / 8) * 64 * K * 4 * (affine ? 2 : 1);
+}
+inline ExtendAlignChoice extend_align_choice(const RuleInputs &in, int alg, const PlacedFacts &f, int G, int K) {
+    ExtendAlignChoice c;
+    const PlacedChoice scores = extend_choice(in, alg, f, G, K);
+    if (f.extend_wide && scores.route != PlacedRoute::Rows) {
+        PlacedFacts narrow = f;
+        narrow.extend_wide = false;
+        const PlacedChoice plain = extend_choice(in, alg, narrow, G, K);
+        // the key changed the answer: the call's extension route is the wide one (or its int32 refusal)
+        const bool wide = scores.route == PlacedRoute::Wide || std::string(scores.reason) != plain.reason;
+        c.reason = wide ? kExtendAlignNoWide : plain.reason;
+        return c;
+    }
+    if (scores.route != PlacedRoute::Rows) {
+        c.reason = scores.reason;
+        return c;
+    }
+    c.route = PlacedRoute::Rows;
+    c.blocks8 = G > 0 ? (in.F + G - 1 + 7) / 8 : 0;
+    c.wave_ptr_bytes = extend_align_wave_ptr_bytes(G, K, in.F, in.sc.affine);
+    return c;
+}
+
 // ---- band_nw = 1: the NW variant under the block band (include/valign_hip.h) ----
 // Consecutive blocks' windows connect -- every in-band cell has a present candidate -- once 2 * (band_width / 2) + 1 columns
 // cover the most a window start advances per row, ceil(F / R).  Narrower bands are refused.

@@ -25,6 +25,8 @@
 //   engine_span_cigar.hip spanned CIGARs: the alignment of the span from the span's window -- the forward placed sweep, the
 //                         reversal, the child engine's ALIGNMENT of the reversed prefixes and the backward encoder
 //                         (span_cigar_kernels.hip.h) behind its walk
+//   engine_extend_align.hip  extension alignments: the extension sweep with back pointers, the walk from the chosen end cell to
+//                         the anchor, the compact result format's encoder (extend_align_kernels.hip.h)
 //   hip_plugin.hip ...... the plugin ABI and the flat C API over it
 // The closest reference precedent for the staging loops is the OpenCL backend's gather / copy / launch / collect loop
 // (src/Kernels/OpenCL/OpenCLKernel.cpp:57-108); unlike it, chunks here are large, asynchronous and overlapped.
@@ -88,6 +90,7 @@ struct Geometry {
     const void *(*placed)(int track, int gaps);      // placed-score kernels (placed_kernels.hip.h); returns nullptr where none is compiled
     const void *(*subopt)(int track, int gaps);      // suboptimal-score kernels: the full geometries', nullptr elsewhere
     const void *(*extend)(int gaps);                 // extension-score kernels (extend_kernels.hip.h): the full geometries', nullptr elsewhere
+    const void *(*extend_align)(int affine);         // extension-alignment fills (extend_align_kernels.hip.h): the full geometries', nullptr elsewhere
 };
 
 template <int G, int K>
@@ -115,14 +118,14 @@ constexpr void set_fast_kernels(Geometry &g) {
 
 template <int G, int K>
 constexpr Geometry fast_geometry() {
-    Geometry g{G, K, false, &wave_lds<G, K>, {}, {}, &placed_kernel<G, K, false>, &subopt_kernel<G, K, false>, &extend_kernel<G, K, false>};
+    Geometry g{G, K, false, &wave_lds<G, K>, {}, {}, &placed_kernel<G, K, false>, &subopt_kernel<G, K, false>, &extend_kernel<G, K, false>, &extend_align_kernel<G, K, false>};
     set_fast_kernels<G, K>(g);
     return g;
 }
 
 template <int G, int K>
 constexpr Geometry full_geometry() {
-    Geometry g{G, K, true, &wave_lds<G, K>, {}, {}, &placed_kernel<G, K, true>, &subopt_kernel<G, K, true>, &extend_kernel<G, K, true>};
+    Geometry g{G, K, true, &wave_lds<G, K>, {}, {}, &placed_kernel<G, K, true>, &subopt_kernel<G, K, true>, &extend_kernel<G, K, true>, &extend_align_kernel<G, K, true>};
     set_fast_kernels<G, K>(g);
     g.fill[0][kFillLinear] = (const void *)&align_fill_kernel<G, K, kAlgSW, false>;
     g.fill[0][kFillLinearSym] = (const void *)&align_fill_kernel<G, K, kAlgSW, true>;
@@ -554,6 +557,21 @@ public:
     void score_extend_host(int opt, int n, const char *const *reads, const char *const *refs, ExtendRec *extend, int threads);
     const char *ran_extend() const { return ran_extend_; }
 
+    // ---- extension alignments (valign_hip.h: valign_hip_align_extend_*; engine_extend_align.hip) ----
+    // The alignment of an extension, from the anchor to the end cell the end-bonus rule picks: align_extend_fill_kernel
+    // (extend_align_kernels.hip.h: the extension sweep with a back pointer per cell, which also writes the extension record where
+    // d_extend is not null, and the cell the walk starts from), extend_walk_kernel into the CIGAR rows scratch, then the encoder of
+    // the compact result format.  extend_align_choice (cell_rules.h) decides what is refused.  Device-resident: asynchronous on
+    // `stream`, in chunks that keep the pointer stream under the pointer scratch's cap and the rows under cigar_rows_mb, reused
+    // in stream order; calls of one engine belong on one stream.  Host pointers: chunk after chunk on one stream -- gather, H2D,
+    // the chunk with a records-only sink, the scan, the emit pass, ONE copy of records, extension records and ops back.
+    // false: the call needs more than ops_cap ops.
+    void align_extend_device(int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int end_bonus, int extended, CigarRec *d_recs,
+                             unsigned *d_ops, int ops_stride, ExtendRec *d_extend, hipStream_t stream);
+    bool align_extend_host(int opt, int n, const char *const *reads, const char *const *refs, int end_bonus, int extended, CigarRec *recs, unsigned *ops,
+                           long long ops_cap, long long *offsets, long long *ops_needed, ExtendRec *extend, int threads);
+    const char *ran_extend_align() const { return ran_extend_align_; }
+
     // host-side phases of the last score_host / align_host call
     std::string host_phases() const;
 
@@ -831,6 +849,19 @@ private:
     // (route Wide: the base plan, which nothing launches on)
     const LaunchPlan &extend_plan_for(int alg, int &gaps, PlacedRoute &route);
 
+    // ---- extension alignments (engine_extend_align.hip) ----
+    // refusals (thrown), then the plan: the base plan where its geometry carries the fill, else the next full geometry
+    const LaunchPlan &extend_align_plan_for(int alg, ExtendAlignChoice &choice);
+    // pairs of one chunk of a call of n pairs: the pointer stream under the pointer scratch's cap, the rows under `rows_cap` bytes
+    long long extend_align_chunk_pairs(const LaunchPlan &plan, const ExtendAlignChoice &choice, long long n, size_t rows_cap) const;
+    // the rows scratch of `slots` slots for `pairs` pairs at the walk's row pitch (R + F + 1)
+    void ensure_extend_align_rows(int slots, long long pairs, hipStream_t stream);
+    // one chunk, all of it on `stream`: fill, walk, encoder (records at recs, ops at ops where not null)
+    void extend_align_chunk(const LaunchPlan &plan, const ExtendAlignChoice &choice, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int end_bonus,
+                            int extended, CigarRec *recs, unsigned *ops, int ops_stride, ExtendRec *d_extend, int slot, hipStream_t stream);
+    // the encoder over the walk's rows (any pass: the caller fills what launch_cigar_args leaves open)
+    void launch_extend_align_cigar(hipStream_t stream, CigarArgs &a);
+
     // ---- length-sorted batching (score_host, Smith-Waterman) ----
 
     static double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
@@ -987,6 +1018,8 @@ private:
     int subopt_ring_cols_ = 0;                           // ... and the columns of a lane group's ring in its sweep
     size_t subopt_scratch_bytes_ = (size_t)dbg_.value("subopt_scratch_bytes", 256ll << 20);      // column maxima of one chunk
     const char *ran_extend_ = "none";                    // what the last extension call ran: rows, wide (describe)
+    const char *ran_extend_align_ = "none";              // what the last extension-alignment call ran: rows (describe)
+    const Geometry *ran_extend_align_geo_ = nullptr;     // ... and the geometry its fill was taken from (ran_extend_align_geometry)
     const char *ran_result_format_ = "rows";             // of the last alignment call: rows / cigar (describe)
     long long cigar_d2h_bytes_ = 0;                      // what the last align_cigar_host call copied back
     const CigarSink *cigar_ = nullptr;
@@ -1028,6 +1061,7 @@ private:
     DeviceBuffer<uint8_t> d_cig_out_[2];
     PinnedBuffer<uint8_t> h_cig_out_[2];
     PinnedBuffer<long long> h_cig_total_;
+    DeviceBuffer<ExtendRec> d_extend_align_recs_;                // extension alignments, host path: the chunk's extension records before they join the packed copy
     DeviceBuffer<int> d_min_start_;                              // per slot: first column of the chunk's rows that holds a string
     PinnedBuffer<int> h_min_start_;                              // ... on its way to the host
     // record_pipeline: record staging (placed or spanned records: one host call runs on an engine at a time)

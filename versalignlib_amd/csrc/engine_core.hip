@@ -9,7 +9,7 @@ namespace valign {
 static WaveLds side_tile_lds(int R, int F) { return row_table_lds16(R, F); }
 static Geometry side_geometry() {
     Geometry g{kSideTileG, kSideTileK, false, &side_tile_lds, {}, {}, [](int, int) -> const void * { return nullptr; },
-               [](int, int) -> const void * { return nullptr; }, [](int) -> const void * { return nullptr; }};
+               [](int, int) -> const void * { return nullptr; }, [](int) -> const void * { return nullptr; }, [](int) -> const void * { return nullptr; }};
     g.kernel[kAlgSW][kGapAffineSym] = (const void *)&score_kernel<kSideTileG, kSideTileK, kAlgSW, kGapAffineSym>;
     return g;
 }
@@ -160,7 +160,11 @@ std::string Engine::describe(int opt, long long n) const {
              ran_geometry(ran_score_geo_).c_str(), ran_geometry(ran_align_geo_).c_str(),
              ran_geometry(ran_placed_geo_).c_str(), ran_geometry(ran_subopt_geo_).c_str(), ran_geometry(ran_extend_geo_).c_str());
     std::string out(buf);
-    if (ran_score_sym_affine_)          // only where the last score call ran the int16 symmetric affine SW kernel
+    // extension alignments (engine_extend_align.hip): what the last call ran, on which geometry, and the pointer scratch it shares
+    out.insert(out.size() - 1, std::string(", \"ran_extend_align\": \"") + ran_extend_align_ + "\", \"ran_extend_align_geometry\": \"" +
+                                   ran_geometry(ran_extend_align_geo_) + "\", \"extend_align_scratch_bytes\": " +
+                                   std::to_string((long long)(d_ptr_.bytes() + d_ends_.bytes() + d_extend_align_recs_.bytes())));
+    if (ran_score_sym_affine_)         // only where the last score call ran the int16 symmetric affine SW kernel
         out.insert(out.size() - 1, std::string(", \"ran_score_sym_affine\": \"") + ran_score_sym_affine_ + "\", \"ran_score_sym_affine_frame\": \"" +
                                        ran_score_sym_affine_frame_ + "\", \"ran_score_sym_affine_scores\": \"" + ran_score_sym_affine_scores_ + "\"");
     // ... and, where its last such launch ran on the 8 x 19 side tile, which form of the row-table step its waves took

@@ -1,0 +1,261 @@
+// engine_extend_align.hip -- Engine: extension alignments (include/valign_hip.h: valign_hip_align_extend_*): per pair the alignment
+// from the anchor before read[0] and ref[0] to the end cell the end-bonus rule picks, as a valign_hip_aln record and CIGAR ops, and
+// the pair's extension record where asked for.  extend_align_choice (cell_rules.h) decides what is refused; a chunk runs
+// align_extend_fill_kernel (extend_align_kernels.hip.h) into the pointer scratch alignments use, extend_walk_kernel into the CIGAR
+// rows scratch at a row pitch of R + F + 1, and cigar_encode_kernel behind it.  extend_walk_kernel (not a template) is defined in
+// this translation unit.
+#define VALIGN_TU_EXTEND_ALIGN 1
+#include "engine.hip.h"
+
+namespace valign {
+
+const LaunchPlan &Engine::extend_align_plan_for(int alg, ExtendAlignChoice &choice) {
+    const LaunchPlan &base = align_base_plan();
+    const PlacedFacts facts = placed_facts();
+    RuleInputs in = rule_inputs();
+    in.no_f16 = true;                   // int16 cells
+    choice = extend_align_choice(in, alg, facts, base.geo ? base.geo->G : 0, base.geo ? base.geo->K : 0);
+    if (choice.route == PlacedRoute::Refused) throw std::runtime_error(choice.reason);
+    if (base.geo->extend_align(sc_.affine ? 1 : 0)) return base;
+    if (!fallback_plan_.geo) fallback_plan_ = choose_plan(R_, F_, 0, 0, false, true);
+    if (fallback_plan_.long_mode || !fallback_plan_.geo->extend_align(sc_.affine ? 1 : 0)) throw std::runtime_error("no extension-alignment kernel for this mode");
+    choice = extend_align_choice(in, alg, facts, fallback_plan_.geo->G, fallback_plan_.geo->K);
+    return fallback_plan_;
+}
+
+long long Engine::extend_align_chunk_pairs(const LaunchPlan &plan, const ExtendAlignChoice &choice, long long n, size_t rows_cap) const {
+    const long long ppw = plan.pairs_per_wave, ppb = ppw * plan.waves_per_block;
+    size_t free_b = 0, total_b = 0;
+    hip_check(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
+    // the pointer scratch's bound is the one alignments size theirs by (align_parts.h), under pointer_scratch_cap_mb
+    size_t ptr_cap = std::min<size_t>(64ull << 30, std::max<size_t>((free_b + d_ptr_.bytes()) / 2, 256ull << 20));
+    if (scratch_cap_mb_ > 0) ptr_cap = std::min<size_t>(ptr_cap, (size_t)scratch_cap_mb_ << 20);
+    const long long by_ptr = (long long)(ptr_cap / (size_t)choice.wave_ptr_bytes) * ppw;
+    const long long by_rows = (long long)(rows_cap / (2 * ((size_t)R_ + F_ + 1)));
+    long long chunk = std::min(by_ptr, by_rows);
+    chunk = std::max(ppb, chunk / ppb * ppb);           // whole blocks, at least one
+    return std::min(chunk, n);
+}
+
+void Engine::ensure_extend_align_rows(int slots, long long pairs, hipStream_t stream) {
+    // ensure_cigar_scratch sizes rows of R + F bytes: as many such pairs as hold `pairs` pairs at the walk's pitch
+    const size_t AL = (size_t)R_ + F_;
+    const long long as_pairs = AL ? (long long)(((size_t)pairs * 2 * (AL + 1) + 2 * AL - 1) / (2 * AL)) : pairs;
+    ensure_cigar_scratch(slots, std::max(as_pairs, pairs), stream);
+}
+
+void Engine::launch_extend_align_cigar(hipStream_t stream, CigarArgs &a) {
+    a.AL = R_ + F_ + 1;                 // the walk's row pitch
+    a.affine = sc_.affine ? 1 : 0;
+    a.match = sc_.match;
+    a.mismatch = sc_.mismatch;
+    a.gap_read = sc_.gap_read;
+    a.gap_ref = sc_.gap_ref;
+    a.open_read = sc_.open_read;
+    a.ext_read = sc_.ext_read;
+    a.open_ref = sc_.open_ref;
+    a.ext_ref = sc_.ext_ref;
+    // the lane group of launch_cigar_args
+    int lanes = std::min(R_, F_) <= 256 ? 16 : 64;
+    const long long forced = dbg_.value("cigar_lanes", 0);
+    if (forced == 16 || forced == 64) lanes = (int)forced;
+    const long long per_block = 256 / lanes;
+    const long long blocks = (a.n + per_block - 1) / per_block;
+    if (blocks > 0x7FFFFFFFll) throw std::runtime_error("batch too large for one launch");
+    const dim3 grid((unsigned)blocks), block(256);
+    if (lanes == 16) hipLaunchKernelGGL(cigar_encode_kernel<16>, grid, block, 0, stream, a);
+    else hipLaunchKernelGGL(cigar_encode_kernel<64>, grid, block, 0, stream, a);
+    hip_check(hipGetLastError(), "hipLaunchKernel(cigar_encode_kernel)");
+}
+
+void Engine::extend_align_chunk(const LaunchPlan &plan, const ExtendAlignChoice &choice, long long n, const uint8_t *d_reads, const uint8_t *d_refs,
+                                int end_bonus, int extended, CigarRec *recs, unsigned *ops, int ops_stride, ExtendRec *d_extend, int slot,
+                                hipStream_t stream) {
+    const int G = plan.geo->G, K = plan.geo->K;
+    const long long ppw = plan.pairs_per_wave, ppb = ppw * plan.waves_per_block;
+    const long long blocks = (n + ppb - 1) / ppb;
+    if (blocks > 0x7FFFFFFFll) throw std::runtime_error("batch too large for one launch");
+    if ((size_t)((n + ppw - 1) / ppw) * (size_t)choice.wave_ptr_bytes > d_ptr_.bytes() || sizeof(EndCell) * (size_t)n > d_ends_.bytes() ||
+        (size_t)n * 2 * ((size_t)R_ + F_ + 1) > d_cig_rows_[slot].bytes())
+        throw std::runtime_error("extension alignments: chunk larger than its scratch");
+    ExtendAlignArgs f{};
+    f.reads = d_reads;
+    f.refs = d_refs;
+    f.ptr = d_ptr_.get();
+    f.ends = d_ends_.get();
+    f.extend = d_extend;
+    f.n = n;
+    f.R = R_;
+    f.F = F_;
+    f.blocks8 = choice.blocks8;
+    f.end_bonus = end_bonus;
+    put_lds(f, plan.lds);
+    put_scoring(f);
+    const void *fn = plan.geo->extend_align(sc_.affine ? 1 : 0);
+    ran_extend_align_geo_ = plan.geo;
+    const int block_lds = plan.lds.total * plan.waves_per_block;
+    raise_block_lds(fn, block_lds);
+    void *fargs[] = {&f};
+    hip_check(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(plan.waves_per_block * kWave), fargs, (size_t)block_lds, stream),
+              "hipLaunchKernel(align_extend_fill_kernel)");
+    ExtendWalkArgs t{};
+    t.reads = d_reads;
+    t.refs = d_refs;
+    t.ptr = d_ptr_.get();
+    t.ends = d_ends_.get();
+    t.rows = d_cig_rows_[slot].get();
+    t.idx = d_cig_idx_[slot].get();
+    t.n = n;
+    t.R = R_;
+    t.F = F_;
+    t.G = G;
+    t.K = K;
+    t.blocks8 = choice.blocks8;
+    t.affine = sc_.affine ? 1 : 0;
+    t.pitch = R_ + F_ + 1;
+    hipLaunchKernelGGL(extend_walk_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, t);
+    hip_check(hipGetLastError(), "hipLaunchKernel(extend_walk_kernel)");
+    CigarArgs a{};
+    a.rows = t.rows;
+    a.idx = t.idx;
+    a.ends = d_ends_.get();
+    a.recs = recs;
+    a.ops = ops;
+    a.ops_stride = ops_stride;
+    a.n = n;
+    a.extended = extended;
+    launch_extend_align_cigar(stream, a);
+    ran_extend_align_ = ran_placed_name(PlacedRoute::Rows);
+}
+
+void Engine::align_extend_device(int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int end_bonus, int extended, CigarRec *d_recs,
+                                 unsigned *d_ops, int ops_stride, ExtendRec *d_extend, hipStream_t stream) {
+    ran_extend_align_ = "none";
+    ran_extend_align_geo_ = nullptr;
+    if (extended != 0 && extended != 1) throw std::runtime_error("extended must be 0 (M) or 1 (= / X)");
+    if (ops_stride < 1) throw std::runtime_error("ops_stride must be >= 1");
+    if (!d_recs || !d_ops) throw std::runtime_error("null result buffer");
+    const int alg = opt & 0xF;
+    if (alg > 1 || n <= 0) return;          // reference: unsupported mode is a silent no-op
+    ExtendAlignChoice choice;
+    const LaunchPlan &plan = extend_align_plan_for(alg, choice);        // (refusals leave here, before anything is launched)
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    ran_result_format_ = "cigar";
+    const size_t rows_cap = (size_t)std::max<long long>(1, dbg_.value("cigar_rows_mb", 512)) << 20;
+    const long long chunk = extend_align_chunk_pairs(plan, choice, n, rows_cap);
+    ensure_extend_align_rows(1, chunk, stream);
+    ensure_trace_scratch(chunk, (size_t)(choice.wave_ptr_bytes / (plan.pairs_per_wave / 2)), plan.pairs_per_wave, stream);
+    for (long long begin = 0; begin < n; begin += chunk)          // (stream order: the next chunk reuses the scratch behind this one's encoder)
+        extend_align_chunk(plan, choice, std::min(chunk, n - begin), d_reads + (size_t)begin * R_, d_refs + (size_t)begin * F_, end_bonus, extended,
+                           d_recs + begin, d_ops + (size_t)begin * ops_stride, ops_stride, d_extend ? d_extend + begin : nullptr, 0, stream);
+}
+
+// Host pointers in, packed results out.  Chunk after chunk on streams_[0], each waited for: gather, H2D, the chunk above with a
+// records-only sink (count pass), the scan of n_ops, the op total to the host, the emit pass at the scanned offsets beside the
+// records (and, where asked for, the extension records between them), ONE copy back.
+bool Engine::align_extend_host(int opt, int n, const char *const *reads, const char *const *refs, int end_bonus, int extended, CigarRec *recs,
+                               unsigned *ops, long long ops_cap, long long *offsets, long long *ops_needed, ExtendRec *extend, int threads) {
+    ran_extend_align_ = "none";
+    ran_extend_align_geo_ = nullptr;
+    if (extended != 0 && extended != 1) throw std::runtime_error("extended must be 0 (M) or 1 (= / X)");
+    if (!recs || !offsets || !ops_needed || (!ops && ops_cap > 0)) throw std::runtime_error("null result buffer");
+    if (n < 0 || ops_cap < 0) throw std::runtime_error("negative size");
+    const int alg = opt & 0xF;
+    if (alg > 1) return true;                       // (the same silent no-op as every entry point)
+    offsets[0] = 0;
+    *ops_needed = 0;
+    cigar_d2h_bytes_ = 0;
+    if (n == 0) return true;
+    if (!reads || !refs) throw std::runtime_error("null sequence array");
+    ExtendAlignChoice choice;
+    const LaunchPlan &plan = extend_align_plan_for(alg, choice);        // (refusals leave here, before anything is staged)
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    ran_result_format_ = "cigar";
+    const size_t per_pair = (size_t)3 * (R_ + F_) + 8;         // (the chunks of align_cigar_host)
+    long long chunk = std::max<long long>(whole_rounds((long long)(align_chunk_bytes_ / per_pair)), 1024);
+    chunk = std::min<long long>(chunk, extend_align_chunk_pairs(plan, choice, n, (size_t)std::max<long long>(1, dbg_.value("cigar_rows_mb", 512)) << 20));
+    reset_pipeline();
+    ensure_staging(chunk);
+    threads = std::min(std::max(threads, 1), 64);
+    hipStream_t st = streams_[0].get();
+    ensure_extend_align_rows(1, chunk, st);
+    ensure_trace_scratch(chunk, (size_t)(choice.wave_ptr_bytes / (plan.pairs_per_wave / 2)), plan.pairs_per_wave, st);
+    if (extend) d_extend_align_recs_.reserve(sizeof(ExtendRec) * (size_t)chunk, "extension records");
+    host_stats_ = HostStats{};
+    struct Quiesce {            // an error part-way leaves nothing in flight
+        hipStream_t st;
+        bool armed = true;
+        ~Quiesce() {
+            if (armed) (void)hipStreamSynchronize(st);
+        }
+    } quiesce{st};
+    long long total_ops = 0;
+    for (long long begin = 0; begin < n; begin += chunk) {
+        const long long cnt = std::min<long long>(chunk, n - begin);
+        uint8_t *h_reads = h_reads_[0].get(), *h_refs = h_refs_[0].get(), *d_reads = d_reads_[0].get(), *d_refs = d_refs_[0].get();
+        auto t0 = std::chrono::steady_clock::now();
+        gather(reads + begin, refs + begin, cnt, h_reads, h_refs, threads);
+        host_stats_.gather_ms += ms_between(t0, std::chrono::steady_clock::now());
+        hip_check(hipMemcpyAsync(d_reads, h_reads, (size_t)cnt * R_, hipMemcpyHostToDevice, st), "H2D reads");
+        hip_check(hipMemcpyAsync(d_refs, h_refs, (size_t)cnt * F_, hipMemcpyHostToDevice, st), "H2D refs");
+        // records only: the ops wait for the chunk's scan
+        extend_align_chunk(plan, choice, cnt, d_reads, d_refs, end_bonus, extended, d_cig_recs_[0].get(), nullptr, 1,
+                           extend ? d_extend_align_recs_.get() : nullptr, 0, st);
+        launch_cigar_scan(d_cig_recs_[0].get(), d_cig_offsets_[0].get(), cnt, st);
+        hip_check(hipMemcpyAsync(h_cig_total_.get(), d_cig_offsets_[0].get() + cnt, sizeof(long long), hipMemcpyDeviceToHost, st), "D2H op total");
+        t0 = std::chrono::steady_clock::now();
+        hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+        host_stats_.wait_ms += ms_between(t0, std::chrono::steady_clock::now());
+        const long long total = h_cig_total_.get()[0];
+        total_ops += total;
+        const bool with_ops = total_ops <= ops_cap;
+        const size_t rec_bytes = sizeof(CigarRec) * (size_t)cnt, ext_bytes = extend ? sizeof(ExtendRec) * (size_t)cnt : 0;
+        const size_t bytes = rec_bytes + ext_bytes + (with_ops ? sizeof(unsigned) * (size_t)total : 0);
+        if (bytes > h_cig_out_[0].bytes()) {                     // (the last copy out of it was waited for)
+            h_cig_out_[0].reserve(bytes + bytes / 4, "packed alignment results");
+            d_cig_out_[0].reserve(bytes + bytes / 4, "packed alignment results");
+        }
+        uint8_t *out = d_cig_out_[0].get();
+        if (with_ops) {                             // emit pass: the ops at their offsets, the records in front
+            CigarArgs a{};
+            a.rows = d_cig_rows_[0].get();
+            a.idx = d_cig_idx_[0].get();
+            a.ops = reinterpret_cast<unsigned *>(out + rec_bytes + ext_bytes);
+            a.offsets = d_cig_offsets_[0].get();
+            a.recs_in = d_cig_recs_[0].get();
+            a.recs_out = reinterpret_cast<CigarRec *>(out);
+            a.n = cnt;
+            a.extended = extended;
+            launch_extend_align_cigar(st, a);
+        } else {
+            hip_check(hipMemcpyAsync(out, d_cig_recs_[0].get(), rec_bytes, hipMemcpyDeviceToDevice, st), "D2D records");
+        }
+        if (extend) hip_check(hipMemcpyAsync(out + rec_bytes, d_extend_align_recs_.get(), ext_bytes, hipMemcpyDeviceToDevice, st), "D2D extension records");
+        hip_check(hipMemcpyAsync(h_cig_out_[0].get(), out, bytes, hipMemcpyDeviceToHost, st), "D2H records + ops");
+        cigar_d2h_bytes_ += (long long)(bytes + sizeof(long long));
+        t0 = std::chrono::steady_clock::now();
+        hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+        auto t1 = std::chrono::steady_clock::now();
+        const uint8_t *h = h_cig_out_[0].get();
+        const CigarRec *h_recs = reinterpret_cast<const CigarRec *>(h);
+        for_ranges(threads, cnt, 4096, [&](int, long long lo, long long hi) { memcpy(recs + begin + lo, h_recs + lo, sizeof(CigarRec) * (size_t)(hi - lo)); });
+        if (extend) memcpy(extend + begin, h + rec_bytes, ext_bytes);
+        long long at = offsets[begin];
+        for (long long i = 0; i < cnt; ++i) {                    // offsets follow from n_ops: rebased on the host
+            at += h_recs[i].n_ops;
+            offsets[begin + i + 1] = at;
+        }
+        if (with_ops && total > 0) {
+            unsigned *to = ops + offsets[begin];
+            const unsigned *from = reinterpret_cast<const unsigned *>(h + rec_bytes + ext_bytes);
+            for_ranges(threads, total, 1 << 16, [&](int, long long lo, long long hi) { memcpy(to + lo, from + lo, sizeof(unsigned) * (size_t)(hi - lo)); });
+        }
+        host_stats_.wait_ms += ms_between(t0, t1);
+        host_stats_.drain_ms += ms_between(t1, std::chrono::steady_clock::now());
+    }
+    quiesce.armed = false;
+    *ops_needed = total_ops;
+    return total_ops <= ops_cap;
+}
+
+}  // namespace valign

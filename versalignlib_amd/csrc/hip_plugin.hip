@@ -752,6 +752,38 @@ VALIGN_EXPORT int valign_hip_score_extend_host(valign_hip_engine *e, int opt, in
     return flat_guard([&] { e->impl->score_extend_host(opt, n, reads, refs, (valign::ExtendRec *)extend, threads); });
 }
 
+VALIGN_EXPORT int valign_hip_align_extend_device(valign_hip_engine *e, int opt, long long n, const void *d_reads, const void *d_refs,
+                                                 int end_bonus, int extended, void *d_recs, void *d_ops, int ops_stride, void *d_extend,
+                                                 void *hip_stream) {
+    if (!e) {
+        g_last_error = "null engine";
+        return 1;
+    }
+    return flat_guard([&] {
+        e->impl->align_extend_device(opt, n, (const uint8_t *)d_reads, (const uint8_t *)d_refs, end_bonus, extended, (valign::CigarRec *)d_recs,
+                                     (unsigned *)d_ops, ops_stride, (valign::ExtendRec *)d_extend, (hipStream_t)hip_stream);
+    });
+}
+
+VALIGN_EXPORT int valign_hip_align_extend_host(valign_hip_engine *e, int opt, int n, const char *const *reads, const char *const *refs,
+                                               int end_bonus, int extended, valign_hip_aln *recs, uint32_t *ops, long long ops_cap,
+                                               long long *offsets, long long *ops_needed, valign_hip_extend *extend, int threads) {
+    if (!e) {
+        g_last_error = "null engine";
+        return 1;
+    }
+    bool fits = true;
+    const int rc = flat_guard([&] {
+        fits = e->impl->align_extend_host(opt, n, reads, refs, end_bonus, extended, (valign::CigarRec *)recs, ops, ops_cap, offsets, ops_needed,
+                                          (valign::ExtendRec *)extend, threads);
+    });
+    if (rc == 0 && !fits) {
+        g_last_error = "ops_cap is too small: the call needs " + std::to_string(*ops_needed) + " ops";
+        return 2;
+    }
+    return rc;
+}
+
 VALIGN_EXPORT int valign_hip_describe(valign_hip_engine *e, int opt, long long n, char *buf, int cap) {
     if (!e || !buf || cap <= 0) return 1;
     const std::string s = e->impl->describe(opt, n);

@@ -29,6 +29,7 @@
 #include "trace_kernels.hip.h"
 #include "placed_kernels.hip.h"
 #include "extend_kernels.hip.h"
+#include "extend_align_kernels.hip.h"
 
 // X(G, K): geometries with every kernel;  Y(G, K): geometries with the fast set only.  Parts are balanced by rows per
 // lane (compile time grows with K).
@@ -95,3 +96,7 @@
 // The extension-score kernels (extend_kernels.hip.h: extend_kernel<G, K, FULL>, score_extend_kernel): the four gap forms on the six
 // full geometries, 24 instances
 #define VALIGN_EXTEND_KERNELS(PREFIX, G, K, FULL) PREFIX const void *extend_kernel<G, K, FULL>(int);
+
+// The extension-alignment fills (extend_align_kernels.hip.h: extend_align_kernel<G, K, FULL>, align_extend_fill_kernel): linear and
+// affine gaps on the six full geometries, 12 instances
+#define VALIGN_EXTEND_ALIGN_KERNELS(PREFIX, G, K, FULL) PREFIX const void *extend_align_kernel<G, K, FULL>(int);

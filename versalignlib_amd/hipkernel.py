@@ -115,6 +115,10 @@ def lib():
         L.valign_hip_score_subopt_host.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int]
         L.valign_hip_score_extend_device.argtypes = [vp, ctypes.c_int, ctypes.c_longlong, vp, vp, vp, vp]
         L.valign_hip_score_extend_host.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int]
+        L.valign_hip_align_extend_device.argtypes = [vp, ctypes.c_int, ctypes.c_longlong, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp,
+                                                     ctypes.c_int, vp, vp]
+        L.valign_hip_align_extend_host.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp,
+                                                   ctypes.c_longlong, vp, vp, vp, ctypes.c_int]
         L.valign_hip_describe.argtypes = [vp, ctypes.c_int, ctypes.c_longlong, ctypes.c_char_p,
                                           ctypes.c_int]
         L.valign_hip_last_error.restype = ctypes.c_char_p
@@ -125,7 +129,7 @@ def lib():
 EXPORTED_SYMBOLS = (
     "spawn_alignment_kernel", "set_parameters", "set_logger", "delete_alignment_kernel",
     "valign_hip_device_count", "valign_hip_shard_range", "valign_hip_engine_create", "valign_hip_engine_destroy",
-    "valign_hip_set_traceback_policy", "valign_hip_set_pointer_scratch_cap_mb", "valign_hip_set_host_packing", "valign_hip_set_half_float_cells", "valign_hip_host_register", "valign_hip_host_unregister", "valign_hip_set_band_width", "valign_hip_set_band_alignments", "valign_hip_set_band_nw", "valign_hip_set_band_placed", "valign_hip_set_placed_wide", "valign_hip_set_extend_wide", "valign_hip_set_trace_checkpoints", "valign_hip_set_score_width", "valign_hip_set_ragged_batching", "valign_hip_score_device", "valign_hip_align_device", "valign_hip_score_host", "valign_hip_align_host", "valign_hip_align_cigar_device", "valign_hip_align_cigar_host", "valign_hip_score_placed_device", "valign_hip_score_placed_host", "valign_hip_score_span_device", "valign_hip_score_span_host", "valign_hip_align_span_device", "valign_hip_align_span_host", "valign_hip_score_subopt_device", "valign_hip_score_subopt_host", "valign_hip_score_extend_device", "valign_hip_score_extend_host", "valign_hip_describe",
+    "valign_hip_set_traceback_policy", "valign_hip_set_pointer_scratch_cap_mb", "valign_hip_set_host_packing", "valign_hip_set_half_float_cells", "valign_hip_host_register", "valign_hip_host_unregister", "valign_hip_set_band_width", "valign_hip_set_band_alignments", "valign_hip_set_band_nw", "valign_hip_set_band_placed", "valign_hip_set_placed_wide", "valign_hip_set_extend_wide", "valign_hip_set_trace_checkpoints", "valign_hip_set_score_width", "valign_hip_set_ragged_batching", "valign_hip_score_device", "valign_hip_align_device", "valign_hip_score_host", "valign_hip_align_host", "valign_hip_align_cigar_device", "valign_hip_align_cigar_host", "valign_hip_score_placed_device", "valign_hip_score_placed_host", "valign_hip_score_span_device", "valign_hip_score_span_host", "valign_hip_align_span_device", "valign_hip_align_span_host", "valign_hip_score_subopt_device", "valign_hip_score_subopt_host", "valign_hip_score_extend_device", "valign_hip_score_extend_host", "valign_hip_align_extend_device", "valign_hip_align_extend_host", "valign_hip_describe",
     "valign_hip_last_error",
 )
 
@@ -589,8 +593,66 @@ class Engine:
             raise HipKernelError(_err())
         return extend
 
+    def align_extend_device(self, opt, reads, refs, end_bonus=-1, extended=False, ops_stride=64, with_extend=True, stream=None, out=None):
+        """Extension alignments: -> recs int32 CUDA [n, 6], ops int32 CUDA [n, ops_stride] (the layout of align_cigar_device)
+        and, with_extend, the extension records int32 CUDA [n, 5] (else None): per pair the alignment from the anchor before
+        read[0] and ref[0] to the best cell (end_bonus < 0) or, where gscore + end_bonus >= score, to the read end
+        (include/valign_hip.h has the definition).  Asynchronous on the current stream (or `stream`); `out` = (recs, ops,
+        extend) of an earlier call is written in place.  Refused (HipKernelError) where score_extend_device is, and on the
+        int32 route of extend_wide."""
+        import torch
+        n = reads.shape[0]
+        assert reads.is_cuda and refs.is_cuda and reads.dtype == torch.uint8 and refs.dtype == torch.uint8
+        assert reads.is_contiguous() and refs.is_contiguous()
+        assert tuple(reads.shape) == (n, self.read_length) and tuple(refs.shape) == (n, self.ref_length)
+        if out is not None:
+            recs, ops, extend = out
+        else:
+            recs = torch.empty((n, 6), dtype=torch.int32, device=reads.device)
+            ops = torch.empty((n, int(ops_stride)), dtype=torch.int32, device=reads.device)
+            extend = torch.empty((n, 5), dtype=torch.int32, device=reads.device) if with_extend else None
+        assert recs.is_cuda and recs.is_contiguous() and recs.dtype == torch.int32 and tuple(recs.shape) == (n, 6)
+        assert ops.is_cuda and ops.is_contiguous() and ops.dtype == torch.int32 and tuple(ops.shape) == (n, int(ops_stride))
+        assert extend is None or (extend.is_cuda and extend.is_contiguous() and extend.dtype == torch.int32 and tuple(extend.shape) == (n, 5))
+        st = stream if stream is not None else torch.cuda.current_stream(reads.device)
+        rc = lib().valign_hip_align_extend_device(self._h, int(opt), n, reads.data_ptr(), refs.data_ptr(), int(end_bonus),
+                                                  1 if extended else 0, recs.data_ptr(), ops.data_ptr(), int(ops_stride),
+                                                  extend.data_ptr() if extend is not None else None, st.cuda_stream)
+        if rc != 0:
+            raise HipKernelError(_err())
+        return recs, ops, extend
+
+    def align_extend_host(self, opt, reads, refs, end_bonus=-1, extended=False, with_extend=True, threads=1, ops_cap=None):
+        """Host-pointer path of the extension alignments: -> recs (structured, aln_dtype()) [n], ops uint32 [offsets[n]],
+        offsets int64 [n + 1] as align_cigar_host returns them, and the extension records (structured, extend_dtype()) [n]
+        with_extend (else None).  `ops` is sized from a guess (`ops_cap`, default 16 per pair) and the call repeated once
+        with the exact size where that was too small."""
+        import numpy as np
+        n = reads.shape[0]
+        assert reads.dtype == np.uint8 and refs.dtype == np.uint8 and reads.flags.c_contiguous and refs.flags.c_contiguous
+        assert tuple(reads.shape) == (n, self.read_length) and tuple(refs.shape) == (n, self.ref_length)
+        rp = (reads.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(self.read_length)).astype(np.uint64)
+        fp = (refs.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(self.ref_length)).astype(np.uint64)
+        recs = np.zeros(n, dtype=aln_dtype())
+        extend = np.zeros(n, dtype=extend_dtype()) if with_extend else None
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        cap = 16 * n if ops_cap is None else int(ops_cap)
+        for _ in range(2):
+            ops = np.zeros(max(cap, 1), dtype=np.uint32)
+            needed = ctypes.c_longlong(0)
+            rc = lib().valign_hip_align_extend_host(self._h, int(opt), n, rp.ctypes.data, fp.ctypes.data, int(end_bonus),
+                                                    1 if extended else 0, recs.ctypes.data, ops.ctypes.data, cap,
+                                                    offsets.ctypes.data, ctypes.byref(needed),
+                                                    extend.ctypes.data if extend is not None else None, int(threads))
+            if rc == 0:
+                return recs, ops[:int(offsets[n])], offsets, extend
+            if needed.value <= cap:
+                break
+            cap = needed.value
+        raise HipKernelError(_err())
+
     def describe(self, opt=0, n=0):
-        buf = ctypes.create_string_buffer(4096)
+        buf = ctypes.create_string_buffer(8192)
         lib().valign_hip_describe(self._h, int(opt), int(n), buf, len(buf))
         return json.loads(buf.value.decode())
 
