@@ -8,11 +8,22 @@ pipeline state and grow-only scratch from call to call (class Engine, versalignl
 
   sequence(world, seed) ... a pure function -> a list of steps, drawn from synth._stream.  A step is a key change (one setter,
                             one new value) or a call (entry point, algorithm, a slice of the world's pairs, threads / mask /
-                            extended where the entry point reads them).
+                            extended / end_bonus / with_extend where the entry point reads them).
   State ................... the current value of every key; configure(engine, state) applies one to a new engine.
   Runner .................. one engine runs the whole sequence on one non-default stream; every call is held, bit for bit,
                             against the reference of the operation the state selects, and against a NEW engine configured to
                             the same state that makes the same call on the same data.
+
+Nine families of entry points share the engine: scores, alignment rows, CIGARs, placed, spanned and suboptimal scores, spanned
+CIGARs, extension scores and extension alignments.  The last three came with the most shared scratch: spanned scores and
+spanned CIGARs re-key ONE child engine, each with its own set of keys; extension alignments walk in the rows scratch of the
+CIGAR calls at another row pitch; extension scores under extend_wide sweep on the boundary rows of the placed int32 sweep.
+
+describe() is host-side state -- with one exception: after a score call whose last launch ran on the 8 x 19 side tile it reports
+"ran_score_sym_affine_form" from two words the kernels wrote, and waits for the DEVICE to read them (Engine::ran_side_tile_form).
+The short world's 150-row reads under sym_affine are that tile's window: a length-sorted score call with half_float_cells = 0
+takes it there, and from then until the next score call that runs elsewhere every describe() drains the stream.  Runner.run
+therefore reads describe() late, behind the wait it makes anyway, wherever the very next step settles.
 
 The generator needs no GPU; the runner imports torch when it is created."""
 import functools
@@ -24,25 +35,30 @@ from versalignlib_amd import synth
 SW, NW = 0, 1
 
 # ---- the model of the state -------------------------------------------------------------------------------------------------
-KEYS = ("band_width", "band_alignments", "band_nw", "band_placed", "placed_wide", "trace_checkpoints", "score_width",
+KEYS = ("band_width", "band_alignments", "band_nw", "band_placed", "placed_wide", "extend_wide", "trace_checkpoints", "score_width",
         "traceback_policy", "ragged_batching", "host_packing", "half_float_cells", "pointer_scratch_cap_mb")
-DEFAULTS = {"band_width": 0, "band_alignments": 0, "band_nw": 0, "band_placed": 0, "placed_wide": 0, "trace_checkpoints": 0,
-            "score_width": 0, "traceback_policy": 0, "ragged_batching": 0, "host_packing": 1, "half_float_cells": 1,
+DEFAULTS = {"band_width": 0, "band_alignments": 0, "band_nw": 0, "band_placed": 0, "placed_wide": 0, "extend_wide": 0,
+            "trace_checkpoints": 0, "score_width": 0, "traceback_policy": 0, "ragged_batching": 0, "host_packing": 1, "half_float_cells": 1,
             "pointer_scratch_cap_mb": 0}
 # pointer_scratch_cap_mb can only be SET: 0 means "leave the cap as it is" to the library, so the state never returns to 0
 SET_ONLY_POSITIVE = ("pointer_scratch_cap_mb",)
 
-FAMILIES = ("score", "rows", "cigar", "placed", "span", "subopt")
+FAMILIES = ("score", "rows", "cigar", "placed", "span", "subopt", "span_cigar", "extend", "extend_align")
 ENTRIES_OF = {"score": ("score_device", "score_host"), "rows": ("align_device", "align_host"),
               "cigar": ("align_cigar_device", "align_cigar_host"), "placed": ("score_placed_device", "score_placed_host"),
-              "span": ("score_span_device", "score_span_host"), "subopt": ("score_subopt_device", "score_subopt_host")}
+              "span": ("score_span_device", "score_span_host"), "subopt": ("score_subopt_device", "score_subopt_host"),
+              "span_cigar": ("align_span_device", "align_span_host"), "extend": ("score_extend_device", "score_extend_host"),
+              "extend_align": ("align_extend_device", "align_extend_host")}
 ENTRY_POINTS = tuple(e for f in FAMILIES for e in ENTRIES_OF[f])
 FAMILY_OF = {e: f for f in FAMILIES for e in ENTRIES_OF[f]}
 
 LADDER = (1, 7, 40, 130)            # batch sizes: scratch buffers are reused, regrown and reused smaller
 POOL = 160                          # pairs of a world; a call takes a slice of them
-CALLS = 45                          # calls drawn per sequence (the repairs at the end may add a few)
-SUBOPT_CALLS = 6                    # ... of which suboptimal ones: two (world, scoring) combinations refuse every one by definition
+CALLS = 62                          # calls drawn per sequence (the repairs at the end add some twenty): at 60 the tiny world's seeds
+                                    # still missed one of the 72 ordered pairs of families as neighbours
+SUBOPT_CALLS = 6                    # ... of which suboptimal ones, and of every family capped_families() names: each of their calls is refused
+                                    # by definition under some scoring of the world, and would eat the budget of refusals
+END_BONUSES = (-1, 0, 5, 2 ** 31 - 1)       # extension alignments: the best cell, the rule in between (twice), always the read end
 
 # The smallest shapes at which each route still exists.  short: the register sweep, the fused / direct small host calls, the
 # ragged classes, the block chain under a band.  long: plan_ is the long plan by construction, alignments take the row strips
@@ -59,6 +75,27 @@ SCORINGS = {"linear": (2, -1, -3, -3), "sym_affine": (2, -1, -3, -3, -5, -1, -5,
 # 1 024 rows take the row strips, and a shape x scoring whose cells can leave int16 is refused whatever placed_wide says
 NEVER_SUCCEEDS = {("long", s): ENTRIES_OF["subopt"] for s in WORLDS["long"]["scorings"]}
 NEVER_SUCCEEDS[("short", "wide")] = ENTRIES_OF["subopt"]
+# "REFUSED" of the extension alignments: "everything valign_hip_score_extend_device refuses with extend_wide = 0 ... under
+# extend_wide = 1, any call whose extension route is "wide"" -- and of the extension scores: "the shapes placed scores send to the
+# row strips (reads of more than 1024 rows, or no register geometry)": every scoring of the long world, whatever extend_wide says
+for _key in [("long", s) for s in WORLDS["long"]["scorings"]]:
+    NEVER_SUCCEEDS[_key] += ENTRIES_OF["extend_align"]
+# ... and of the extension scores: "a shape x scoring whose cells could leave int16 -- signed cells: min(R, F) * max(match,
+# mismatch, 0) above 32000": 150 x 600; extend_wide = 1 moves the scores to the int32 sweep, which the alignments refuse
+NEVER_SUCCEEDS[("short", "wide")] += ENTRIES_OF["extend_align"]
+# (Nothing else: extension scores run under extend_wide = 1 wherever the register sweep refuses them here -- 96 x 2 and 150 x
+# 600 are far below 2^28 --, and spanned CIGARs are refused where spanned scores are, "and whatever the alignment route of the
+# window's shape refuses": an unbanded Smith-Waterman alignment under traceback_policy = 0 picks its own cells and refuses nothing.)
+
+
+def capped_families(world):
+    """The families whose calls a sequence of this world holds to SUBOPT_CALLS in its drawn part: the suboptimal scores, as ever,
+    and every family that some scoring of the world refuses whatever the keys say."""
+    out = {"subopt"}
+    for scoring in WORLDS[world]["scorings"]:
+        never = set(NEVER_SUCCEEDS.get((world, scoring), ()))
+        out |= {f for f in FAMILIES if set(ENTRIES_OF[f]) <= never}
+    return out
 
 
 def key_values(world, key):
@@ -130,9 +167,24 @@ class _Draw:
 def _blockers(world, state, family, alg):
     """What, by the header's refusal rules, stands between this state and a call of the family -- a list of alternative
     single-key remedies for the first reason found, [] when nothing does or nothing helps.  Only steers the generator (so that
-    sequences are not mostly refusals); the tests never read it.  The short world is judged as if its scoring were the wide one."""
+    sequences are not mostly refusals); the tests never read it.  The short world is judged as if its scoring were the wide one.
+    Spanned CIGARs are steered as spanned scores are: the window's alignment refuses nothing of its own here."""
     band, wide_scoring = state["band_width"], world == "short"
-    if family in ("placed", "span", "subopt") and alg == NW:
+    if family in ("placed", "span", "subopt", "span_cigar", "extend", "extend_align") and alg == NW:
+        return []
+    if family in ("extend", "extend_align"):           # no band whatever band_placed says; placed_wide is not read
+        if state["traceback_policy"]:
+            return [("traceback_policy", 0)]
+        if band > 0:
+            return [("band_width", 0)]
+        if family == "extend_align":                    # refused wherever the extension route would be wide: nothing helps there
+            return [("score_width", 0)] if state["score_width"] == 32 else []
+        if state["score_width"] == 32 and not state["extend_wide"]:
+            return [("extend_wide", 1), ("score_width", 0)]
+        if wide_scoring and state["score_width"] == 16:
+            return [("score_width", 0)]
+        if (wide_scoring or world == "long") and not state["extend_wide"]:
+            return [("extend_wide", 1)]
         return []
     if family == "score":
         if band > 0 and alg == NW and not state["band_nw"]:
@@ -168,12 +220,14 @@ def _blockers(world, state, family, alg):
 
 def sequence(world, seed):
     """-> the steps of (world, seed): dicts {"kind": "set", "key", "value"} and {"kind": "call", "entry", "alg", "begin", "n",
-    "threads", "mask", "extended"}.  A pure function of its arguments."""
+    "threads", "mask", "extended", "end_bonus", "with_extend"}.  A pure function of its arguments."""
     w = WORLDS[world]
     d = _Draw(world, seed)
     state = initial_state()
     history = {k: [state[k]] for k in KEYS}
     steps, seen, count, likely = [], set(), {e: 0 for e in ENTRY_POINTS}, {e: 0 for e in ENTRY_POINTS}
+    made = []                           # (family, the state it was made in, the step) of every call so far
+    capped = capped_families(world)
     last_family = None
 
     def change(key, value):
@@ -185,15 +239,15 @@ def sequence(world, seed):
         history[key].append(value)
         steps.append(step)
 
-    def call(family, alg=None, entry=None, remedy=False):
+    def call(family, alg=None, entry=None, remedy=False, **fixed):
         nonlocal last_family
         a, b = ENTRIES_OF[family]
         if entry is None:
             entry = a if count[a] < count[b] else b if count[b] < count[a] else d.choice((a, b))
         if alg is None:
             alg = d.choice((SW, NW)) if family in ("score", "rows", "cigar") else (NW if d.pick(0, 11) == 0 else SW)
-        if _blockers(world, state, family, alg) and (remedy or d.pick(0, 3)):
-            for _ in range(4):                  # three times in four: remedy reason after reason, then call
+        if _blockers(world, state, family, alg) and (remedy or d.pick(0, 7)):
+            for _ in range(4):                  # seven times in eight: remedy reason after reason, then call
                 fixes = _blockers(world, state, family, alg)
                 if not fixes:
                     break
@@ -203,8 +257,12 @@ def sequence(world, seed):
                 (family not in ("rows", "cigar") or not state["traceback_policy"]):
             likely[entry] += 1
         n = d.choice(LADDER)
-        steps.append({"kind": "call", "entry": entry, "alg": alg, "begin": d.pick(0, POOL - n), "n": n, "threads": d.pick(1, 3),
-                      "mask": d.choice((0, 3, w["R"] // 2, w["F"])), "extended": d.pick(0, 1)})
+        step = {"kind": "call", "entry": entry, "alg": alg, "begin": d.pick(0, POOL - n), "n": n, "threads": d.pick(1, 3),
+                "mask": d.choice((0, 3, w["R"] // 2, w["F"])), "extended": d.pick(0, 1), "end_bonus": d.choice(END_BONUSES),
+                "with_extend": d.pick(0, 1)}
+        step.update(fixed)
+        steps.append(step)
+        made.append((family, state, step))
         count[entry] += 1
         if last_family is not None:
             seen.add((last_family, family))
@@ -217,7 +275,7 @@ def sequence(world, seed):
         for _ in range(d.pick(0, 2)):
             key = d.choice(KEYS)
             change(key, d.choice([v for v in key_values(world, key) if v != state[key]]))
-        open_families = [f for f in FAMILIES if f != "subopt" or family_calls(f) < SUBOPT_CALLS]
+        open_families = [f for f in FAMILIES if f not in capped or family_calls(f) < SUBOPT_CALLS]
         fresh = [f for f in open_families if f != last_family and (last_family, f) not in seen]
         call(d.choice(fresh or open_families))
     # repairs: what the draw above did not bring about by itself
@@ -234,23 +292,61 @@ def sequence(world, seed):
             if FAMILY_OF[entry] in ("rows", "cigar"):
                 change("traceback_policy", 0)
             call(FAMILY_OF[entry], alg=SW, entry=entry, remedy=True)
+    # ... every value of the fields that only the new CIGAR families read
+    for family, field, values in (("extend_align", "end_bonus", END_BONUSES), ("extend_align", "with_extend", (0, 1)),
+                                  ("span_cigar", "extended", (0, 1))):
+        for value in values:
+            if not any(f == family and step[field] == value for f, _, step in made):
+                call(family, alg=SW, remedy=True, **{field: value})
+    # ... the orders in which two families use ONE piece of the engine: the spanned calls' child engine, the CIGAR calls' rows
+    # scratch at its two pitches, the strip scratch of the two int32 sweeps
+    for order in (("span", "span_cigar", "span"), ("cigar", "extend_align", "cigar")):
+        families = [f for f, _, _ in made]
+        if not any(tuple(families[i:i + 3]) == order for i in range(len(families) - 2)):
+            for family in order:
+                call(family, alg=SW, remedy=True)
+    if not wide_sweeps_are_neighbours(made):
+        change("placed_wide", 1)
+        change("extend_wide", 1)
+        call("placed", alg=SW, remedy=True)
+        call("extend", alg=SW, remedy=True)
     # ... and, always, a band that is set, used, cleared and followed by a call of every family that reads the plan
     change("band_width", w["bands"][0])
     call("score", alg=SW)
     change("band_width", 0)
-    for family in ("score", "rows", "placed"):
+    for family in ("score", "rows", "placed", "extend", "span_cigar"):
         call(family, alg=SW)
     return steps
 
 
+def wide_sweeps_are_neighbours(made):
+    """made: (family, state, step) per call, in order.  True where a placed call under placed_wide = 1 and an extension-score call
+    under extend_wide = 1 follow one another, in either order: the two int32 sweeps on the one strip scratch."""
+    def wide(family, state):
+        return (family == "placed" and state["placed_wide"] == 1) or (family == "extend" and state["extend_wide"] == 1)
+    return any(wide(fa, sa) and wide(fb, sb) and fa != fb for (fa, sa, _), (fb, sb, _) in zip(made, made[1:]))
+
+
+def calls_with_state(steps):
+    """-> (family, the state the call is made in, the step) of every call of `steps`, in order"""
+    out, state = [], initial_state()
+    for step in steps:
+        state = apply_step(state, step)
+        if step["kind"] == "call":
+            out.append((FAMILY_OF[step["entry"]], state, step))
+    return out
+
+
 # ---- the runner -------------------------------------------------------------------------------------------------------------
-ECHOED = ("band_width", "ragged_batching", "band_alignments", "band_nw", "band_placed", "placed_wide", "trace_checkpoints")
+ECHOED = ("band_width", "ragged_batching", "band_alignments", "band_nw", "band_placed", "placed_wide", "extend_wide", "trace_checkpoints")
 PLAN_KEYS = ("long_mode", "group_lanes", "rows_per_lane", "score_cells", "band_block_rows", "band_col_align", "span_ref_length")
 RAN_KEYS = {"score": ("ran_score_cells", "ran_score_geometry", "ran_score_sym_affine"),
             "rows": ("ran_align_fill", "ran_align_geometry", "ran_result_format"),
             "cigar": ("ran_align_fill", "ran_align_geometry", "ran_result_format"),
             "placed": ("ran_placed", "ran_placed_geometry"), "span": ("ran_span", "ran_placed", "ran_placed_geometry"),
-            "subopt": ("ran_subopt", "ran_subopt_geometry")}
+            "subopt": ("ran_subopt", "ran_subopt_geometry"),
+            "span_cigar": ("ran_span_cigar", "ran_placed", "ran_placed_geometry", "ran_result_format"),
+            "extend": ("ran_extend", "ran_extend_geometry"), "extend_align": ("ran_extend_align", "ran_extend_align_geometry")}
 SENTINEL = -7
 
 
@@ -345,6 +441,22 @@ class Runner:
         import span_ref
         return self._ref(("span",), lambda: span_ref.spans(self.reads, self.refs, self.hsc, affine=self.affine))
 
+    def ref_span_cigar(self, extended):
+        import span_cigar_ref
+        return self._ref(("span_cigar", extended), lambda: span_cigar_ref.expected(self.reads, self.refs, self.hsc, affine=self.affine,
+                                                                                   extended=bool(extended)))
+
+    def ref_extend(self):
+        """one reference for both routes: the record is the same on the register sweep and on the int32 sweep"""
+        import extend_ref
+        return self._ref(("extend",), lambda: extend_ref.extend(self.reads, self.refs, self.hsc, self.affine))
+
+    def ref_extend_align(self, extended):
+        """-> {end_bonus: (recs, ops, extension records, end cells)}: every bonus from ONE fill of the matrices"""
+        import extend_align_ref
+        return self._ref(("extend_align", extended), lambda: dict(zip(END_BONUSES, extend_align_ref.align(
+            self.reads, self.refs, self.hsc, self.affine, end_bonus=END_BONUSES, extended=bool(extended)))))
+
     def ref_subopt(self, mask):
         import subopt_ref
         prepared = self._ref(("subopt",), lambda: subopt_ref.prepare(self.reads, self.refs, self.hsc, affine=self.affine))
@@ -367,8 +479,12 @@ class Runner:
             return (full((n, 6), t.int32), full((n, self.stride), t.int32))
         if entry == "score_placed_device":
             return (full((n, 3), t.int32),)
-        if entry in ("score_span_device", "score_subopt_device"):
+        if entry in ("score_span_device", "score_subopt_device", "score_extend_device"):
             return (full((n, 5), t.int32),)
+        if entry == "align_span_device":
+            return (full((n, 6), t.int32), full((n, self.stride), t.int32))
+        if entry == "align_extend_device":         # ... and the extension records only where the call asks for them
+            return (full((n, 6), t.int32), full((n, self.stride), t.int32)) + ((full((n, 5), t.int32),) if step["with_extend"] else ())
         return None
 
     def issue(self, eng, step, out, stream):
@@ -389,6 +505,24 @@ class Runner:
                 eng.score_span_device(alg, dr, df, out=out[0], stream=stream)
             elif entry == "score_subopt_device":
                 eng.score_subopt_device(alg, dr, df, step["mask"], out=out[0], stream=stream)
+            elif entry == "align_span_device":
+                eng.align_span_device(alg, dr, df, extended=bool(step["extended"]), ops_stride=self.stride, stream=stream, out=out)
+            elif entry == "score_extend_device":
+                eng.score_extend_device(alg, dr, df, out=out[0], stream=stream)
+            elif entry == "align_extend_device":
+                back = eng.align_extend_device(alg, dr, df, end_bonus=step["end_bonus"], extended=bool(step["extended"]), ops_stride=self.stride,
+                                               with_extend=bool(step["with_extend"]), stream=stream, out=out if step["with_extend"] else out + (None,))
+                assert step["with_extend"] or back[2] is None, "extension records nobody asked for"
+            elif entry == "align_span_host":
+                out = eng.align_span_host(alg, hr, hf, extended=bool(step["extended"]), threads=step["threads"])
+            elif entry == "score_extend_host":
+                out = (eng.score_extend_host(alg, hr, hf, threads=step["threads"]),)
+            elif entry == "align_extend_host":
+                out = eng.align_extend_host(alg, hr, hf, end_bonus=step["end_bonus"], extended=bool(step["extended"]),
+                                            with_extend=bool(step["with_extend"]), threads=step["threads"])
+                if not step["with_extend"]:
+                    assert out[3] is None, "extension records nobody asked for"
+                    out = out[:3]
             elif entry == "score_host":
                 out = (eng.score_host(alg, hr, hf, threads=step["threads"]),)
             elif entry == "align_host":
@@ -452,6 +586,14 @@ class Runner:
             return (self.ref_placed(band)[b:e],)
         if family == "span":
             return (self.ref_span()[b:e],)
+        if family == "span_cigar":
+            exp = self.ref_span_cigar(step["extended"])
+            return exp["recs"][b:e], exp["ops"][b:e], None
+        if family == "extend":
+            return (self.ref_extend()[b:e],)
+        if family == "extend_align":
+            recs, ops, _, _ = self.ref_extend_align(step["extended"])[step["end_bonus"]]
+            return recs[b:e], ops[b:e], self.ref_extend()[b:e] if step["with_extend"] else None      # (the score call's record, bit for bit)
         return (self.ref_subopt(step["mask"])[b:e],)
 
     def verify(self, step, got, exp, where):
@@ -471,7 +613,10 @@ class Runner:
                 assert offsets[0] == 0 and np.array_equal(np.diff(offsets), recs["n_ops"].astype(np.int64)) and len(ops) == offsets[-1], (where, "offsets")
                 cigar_ref.check(recs, lambda p: ops[offsets[p]:offsets[p + 1]], exp, self.reads[b:e], self.refs[b:e], where)
             return
-        if entry.endswith("_host") and family in ("placed", "span", "subopt"):
+        if family in ("span_cigar", "extend_align"):
+            self._verify_compact(entry, got, exp, where)
+            return
+        if entry.endswith("_host") and family in ("placed", "span", "subopt", "extend"):
             got = (np.stack([got[0][k] for k in got[0].dtype.names], axis=1),)
         for g, x in zip(got, exp):
             g, x = np.asarray(g), np.asarray(x)
@@ -480,6 +625,50 @@ class Runner:
                 bad = np.nonzero(~same.reshape(len(g), -1).all(axis=1))[0]
                 raise SequenceMismatch((where, "differs from the reference at pairs", bad[:6].tolist(), "got", g[bad[:2]].tolist()[:2],
                                         "expected", x[bad[:2]].tolist()[:2]))
+
+    def _verify_compact(self, entry, got, exp, where):
+        """Spanned CIGARs and extension alignments, exactly (test_gpu_span_cigar._check, test_gpu_extend_align._check): every
+        record field, every op of every pair, the sentinel behind a pair's ops (device) or the offsets (host), and the extension
+        records where the call asked for them -- no buffer of them where it did not."""
+        exp_recs, exp_ops, exp_ext = exp
+        n = len(exp_recs)
+        if entry.endswith("_device"):
+            recs, ext = got[0].astype(np.int64), got[2] if len(got) > 2 else None
+            ops = got[1].view(np.uint32)
+            if not (recs[:, 5] <= self.stride).all():
+                raise SequenceMismatch((where, "n_ops beyond the stride", int(recs[:, 5].max()), self.stride))
+
+            def ops_of(p):
+                return ops[p, :recs[p, 5]]
+            tail = np.arange(self.stride)[None, :] >= recs[:, 5][:, None]
+            if not (got[1][tail] == SENTINEL).all():
+                raise SequenceMismatch((where, "words past a pair's ops were written, at pairs",
+                                        np.nonzero(((got[1] != SENTINEL) & tail).any(axis=1))[0][:6].tolist()))
+        else:
+            recs = np.stack([got[0][k] for k in self.hk.aln_dtype().names], axis=1).astype(np.int64)
+            ops, offsets, ext = got[1], got[2], got[3] if len(got) > 3 else None
+            if ext is not None:
+                ext = np.stack([ext[k] for k in self.hk.extend_dtype().names], axis=1)
+            if not (len(offsets) == n + 1 and offsets[0] == 0 and np.array_equal(np.diff(offsets), recs[:, 5]) and len(ops) == offsets[-1]):
+                raise SequenceMismatch((where, "offsets", offsets[:8].tolist(), recs[:8, 5].tolist(), len(ops)))
+
+            def ops_of(p):
+                return ops[offsets[p]:offsets[p + 1]]
+        bad = np.nonzero((recs != exp_recs).any(axis=1))[0]
+        if bad.size:
+            raise SequenceMismatch((where, "records differ from the reference at pairs", bad[:6].tolist(), "got", recs[bad[:2]].tolist(),
+                                    "expected", exp_recs[bad[:2]].tolist()))
+        for p in range(n):
+            want = [int(o) for o in exp_ops[p]]
+            if [int(o) for o in ops_of(p)] != want:
+                raise SequenceMismatch((where, "ops differ from the reference at pair", p, [int(o) for o in ops_of(p)][:12], want[:12]))
+        if (ext is None) != (exp_ext is None):
+            raise SequenceMismatch((where, "extension records", "missing" if ext is None else "returned though with_extend = 0"))
+        if ext is not None:
+            bad = np.nonzero((ext.astype(np.int64) != exp_ext).any(axis=1))[0]
+            if bad.size:
+                raise SequenceMismatch((where, "extension records differ from the reference at pairs", bad[:6].tolist(), "got", ext[bad[:2]].tolist(),
+                                        "expected", exp_ext[bad[:2]].tolist()))
 
     # -- the whole sequence on one engine --
     def run(self, seed=None, steps=None, log=None):
@@ -496,14 +685,23 @@ class Runner:
             if step["kind"] == "call":
                 news[i] = (dict(state), self.fresh(state, step, cache))
         # 2. the live engine: one non-default stream, device steps back to back, a wait only before a host-pointer step and
-        #    at the end; describe() is host-side state, read right after the call without one
+        #    at the end.  describe() is host-side state and is read right after the call -- but where the very next step settles
+        #    (a host-pointer call, or the end): nothing can change the state in between, so it is read in settle(), behind the
+        #    wait.  After a score call on the 8 x 19 side tile describe() itself waits for the device (the module's docstring):
+        #    read late, it costs a device step its place in the queue only where a key change or another device step follows.
         stream = torch.cuda.Stream()
         live = self.hk.Engine(self.R, self.F, self.hsc)
         pending, stats = [], {"calls": 0, "refused": 0, "succeeded": {e: 0 for e in ENTRY_POINTS}}
 
+        def settles_next(i):
+            return i + 1 == len(steps) or (steps[i + 1]["kind"] == "call" and steps[i + 1]["entry"].endswith("_host"))
+
         def settle():
             stream.synchronize()
             for i, step, outcome, res, desc in pending:
+                if desc is None:            # (the last one pending: no step since)
+                    assert i == pending[-1][0]
+                    desc = live.describe(step["alg"], step["n"])
                 self._settle(tag, i, step, outcome, res, desc, news[i])
             del pending[:]
 
@@ -516,7 +714,7 @@ class Runner:
                     settle()
                 out = self.outputs(step, stream)
                 outcome, res = self.issue(live, step, out, stream)
-                desc = live.describe(step["alg"], step["n"])
+                desc = None if step["entry"].endswith("_device") and settles_next(i) else live.describe(step["alg"], step["n"])
                 if log:
                     log("%4d %s %s -> %s %s" % (i, step["entry"], {k: v for k, v in step.items() if k not in ("kind", "entry")}, outcome,
                                                  res if outcome == "refused" else ""))

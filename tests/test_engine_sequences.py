@@ -20,6 +20,7 @@ def test_the_sequence_is_a_pure_function(world, seed):
             assert step["kind"] == "call" and step["entry"] in es.ENTRY_POINTS and step["alg"] in (es.SW, es.NW)
             assert step["n"] in es.LADDER and 0 <= step["begin"] and step["begin"] + step["n"] <= es.POOL
             assert 1 <= step["threads"] <= 3 and step["mask"] >= 0 and step["extended"] in (0, 1)
+            assert step["end_bonus"] in es.END_BONUSES and step["with_extend"] in (0, 1)
 
 
 @pytest.mark.parametrize("world,seed", CASES)
@@ -55,6 +56,53 @@ def test_every_sequence_moves_every_key_and_makes_every_call(world, seed):
             used = True
     assert used
     assert {s["n"] for s in calls} == set(es.LADDER)
+    # the fields only the new CIGAR families read take every value there
+    extend_align = [c for c in calls if es.FAMILY_OF[c["entry"]] == "extend_align"]
+    assert {c["end_bonus"] for c in extend_align} == set(es.END_BONUSES) == {-1, 0, 5, 2 ** 31 - 1}
+    assert {c["with_extend"] for c in extend_align} == {0, 1}
+    assert {c["extended"] for c in calls if es.FAMILY_OF[c["entry"]] == "span_cigar"} == {0, 1}
+
+
+def test_the_model_holds_the_whole_library():
+    """the key, the eighteen entry points and the nine families"""
+    from versalignlib_amd import hipkernel
+    assert len(es.KEYS) == 13 and set(es.KEYS) == set(es.DEFAULTS) and es.DEFAULTS["extend_wide"] == 0 and set(es.ECHOED) <= set(es.KEYS)
+    assert "extend_wide" in es.ECHOED and es.key_values("short", "extend_wide") == (0, 1)
+    assert len(es.FAMILIES) == 9 and len(es.ENTRY_POINTS) == 18 and len(set(es.ENTRY_POINTS)) == 18
+    assert es.ENTRIES_OF["span_cigar"] == ("align_span_device", "align_span_host")
+    assert es.ENTRIES_OF["extend"] == ("score_extend_device", "score_extend_host")
+    assert es.ENTRIES_OF["extend_align"] == ("align_extend_device", "align_extend_host")
+    for key in es.KEYS:
+        assert callable(getattr(hipkernel.Engine, "set_" + key)), key
+    for entry in es.ENTRY_POINTS:
+        assert callable(getattr(hipkernel.Engine, entry)), entry
+    assert set(es.RAN_KEYS) == set(es.FAMILIES)
+    for (world, scoring), entries in es.NEVER_SUCCEEDS.items():
+        assert scoring in es.WORLDS[world]["scorings"] and set(entries) <= set(es.ENTRY_POINTS)
+        assert set(entries) == set(es.ENTRIES_OF["subopt"] + es.ENTRIES_OF["extend_align"])
+    assert set(es.NEVER_SUCCEEDS) == {("long", s) for s in es.WORLDS["long"]["scorings"]} | {("short", "wide")}
+    assert es.capped_families("tiny") == {"subopt"} and es.capped_families("long") == es.capped_families("short") == {"subopt", "extend_align"}
+    assert es.CALLS >= 60
+
+
+@pytest.mark.parametrize("world", sorted(es.WORLDS))
+def test_the_orders_that_share_state_occur(world):
+    """Per world, over its seeds: the orders in which two families use one piece of the engine -- the spanned calls' child
+    engine, the CIGAR rows scratch at its two pitches, the strip scratch of the two int32 sweeps -- with batch sizes from the
+    ladder on both sides."""
+    triples, wide = set(), False
+    for seed in es.WORLDS[world]["seeds"]:
+        made = es.calls_with_state(es.sequence(world, seed))
+        assert all(step["n"] in es.LADDER for _, _, step in made)
+        families = [f for f, _, _ in made]
+        triples |= set(zip(families, families[1:], families[2:]))
+        for (fa, sa, _), (fb, sb, _) in zip(made, made[1:]):
+            if {fa, fb} == {"placed", "extend"}:
+                placed, extend = (sa, sb) if fa == "placed" else (sb, sa)
+                wide = wide or (placed["placed_wide"] == 1 and extend["extend_wide"] == 1)
+    assert ("span", "span_cigar", "span") in triples
+    assert ("cigar", "extend_align", "cigar") in triples
+    assert wide, "no placed call under placed_wide = 1 next to an extension-score call under extend_wide = 1"
 
 
 @pytest.mark.parametrize("world", sorted(es.WORLDS))

@@ -468,8 +468,10 @@ def run_extend_align(c):
 
 def soak_sequences(rng, a):
     """--kind sequence: the generator and the runner of tests/engine_sequences.py (what tests/test_gpu_engine_sequences.py runs
-    on its committed seeds) on random seeds: ONE engine per sequence through key changes and calls, every call against its
-    reference and against a new engine.  No code path of its own: a mismatch is the runner's, with world, seed and step index."""
+    on its committed seeds) on random seeds: ONE engine per sequence through key changes (extend_wide among them) and calls of all
+    nine families -- spanned CIGARs, extension scores and extension alignments included, with their end_bonus, with_extend and
+    extended --, every call against its reference and against a new engine.  No code path of its own: a mismatch is the runner's,
+    with world, seed and step index."""
     os.environ["VALIGN_HIP_DEBUG"] = "ragged_min=8"        # (before any engine exists: the length classes at these batch sizes)
     import engine_sequences as es
     runners, t0, done = {}, time.time(), 0
