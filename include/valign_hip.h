@@ -641,6 +641,53 @@ int valign_hip_score_extend_host(valign_hip_engine *e, int opt, int n, const cha
  * "extend_wide" of valign_hip_describe is the key.                                                                           */
 int valign_hip_set_extend_wide(valign_hip_engine *e, int on);
 
+/* Banded extension scores: a band on the ANCHOR's diagonal (key extend_band; flat API only).  The sentence above that calls a
+ * band around the anchor's diagonal unbuilt is qualified here: under this key the band is built, for the extension SCORES.
+ * Seed-and-extend callers (ksw_extend, ksw_extz) extend inside a band around the diagonal i = j of their anchor; the other band
+ * entry points (band_width alone, band_placed, band_nw) are Smith-Waterman or NW matrices on the scaled diagonal i * F / R.
+ *   0 (default): nothing changes -- band_width > 0 refuses extension calls with the text stated above.
+ *   1 with band_width > 0: valign_hip_score_extend_device / _host run BANDED on the int32 strip sweep (the BANDED instances of
+ *     score_extend_wide_kernel), whatever the read length, score_width (0 or 32) or extend_wide say; "ran_extend": "band",
+ *     "ran_extend_geometry": "none".  With band_width == 0 the key is not read.  Placed, spanned, suboptimal and alignment calls
+ *     never read it.  Other values than 0 / 1 are refused.
+ * DEFINITION.  The record, the trimmed lengths Rp / Fp, the matrix X, the recurrence and the tie rules are exactly those of the
+ * extension scores, above.  The only difference is that some cells are ABSENT.
+ *   w ........... band_width / 2, the library's "diagonals" convention; band_width = 1 gives w = 0.
+ *   blocks ...... rows are taken in blocks of B = VALIGN_HIP_EXTEND_BAND_BLOCK_ROWS = 8 consecutive read positions counted from
+ *                 row 0: block b holds rows [8b, 8b + 8) -- one lane's rows on the sweep.
+ *   present ..... cell (i, j) with 0 <= i < R and -1 <= j < F is present iff 8*(i/8) - w <= j <= 8*(i/8) + 7 + w.  The border
+ *                 column j = -1 counts like any other column.
+ *   border row .. cell (-1, j) is present iff j + 1 <= w.  (-1, -1) is always present.
+ *   absent ...... an absent cell is never a candidate of a neighbour, a maximum or an arg-max.  With affine gaps H, E and F are
+ *                 all absent.
+ *   borders ..... present border cells hold the unbanded closed-form values.  Every present cell has a present path from the
+ *                 origin, so the closed forms stay valid.
+ *   per-cell band With B = 1 this is the per-cell band |i - j| <= w.  The library computes the B = 8 superset: more cells mean
+ *                 more paths, so for score and gscore: per-cell band <= result <= unbanded.
+ *   limit ....... a band with w >= max(R, F) gives exactly the unbanded record.
+ *   score, read_end, ref_end
+ *                 as defined above, taken over the present cells with i < Rp and j < Fp.
+ *   gscore, gref_end
+ *                 taken over the present candidates -1 <= j < Fp of row Rp - 1.
+ *   unreached ... if no candidate is present (8*((Rp-1)/8) - w > Fp - 1), the read end is unreached: gscore =
+ *                 VALIGN_HIP_EXTEND_UNREACHED (INT32_MIN) and gref_end = 0.  Rp = 0 is still five zeros.
+ * REFUSED under extend_band = 1 with band_width > 0, "ran_extend": "none": opt & 0xF == 1 and traceback_policy = 1, with the
+ * texts stated above; score_width = 16 ("int16 or refuse"), with a text that begins "extend_band:"; a shape x scoring that
+ * fails the band's int32 bound, with another text that begins "extend_band:" -- under a band the path "down the border column,
+ * then along the row" may be absent, so the bottom of the cell range is R down steps, F right steps and min(R, F) diagonal steps,
+ * each at its worst price, plus the largest single addend, which must stay above -2^28; the top bound and the sentinel's
+ * conditions are those of extend_wide.  Extension alignments (valign_hip_align_extend_*) under band_width > 0 are refused with a
+ * text that starts "extension alignments: not built under a band" (key off: the text stated above).
+ * The scratch, the chunks and the one-stream host path are those of extend_wide.
+ * KNOWN: the band runs on the strip sweep only.  Short reads under a band fill a fraction of their one 512-row strip and are slower
+ * than the unbanded int16 register sweep, which has no banded form; there is no sub-wave geometry for them.  Z-drop, and extension
+ * alignments under a band or on int32 cells, remain unbuilt.
+ * "extend_band" of valign_hip_describe is the key, "extend_band_block_rows" is B.  tests/extend_band_ref.py restates the definition
+ * in numpy.                                                                                                                   */
+#define VALIGN_HIP_EXTEND_BAND_BLOCK_ROWS 8
+#define VALIGN_HIP_EXTEND_UNREACHED (-2147483647 - 1)
+int valign_hip_set_extend_band(valign_hip_engine *e, int on);
+
 /* ---- extension alignments: the CIGAR of an extension, from the anchor to the chosen end cell ----
  * Extension scores say how far to extend and whether to go end-to-end or clip; this call returns the alignment of that extension.
  * No other alignment call can: Smith-Waterman has a free start and a floor at zero, the NW variant a free row 0, spanned CIGARs
@@ -736,7 +783,9 @@ int valign_hip_set_half_float_cells(valign_hip_engine *e, int mode);
  * "ran_placed" is what the last placed-score call ran: key / rows / strip / chain / wide ("none" before any, or when it was
  * refused); "band_placed" is the key of valign_hip_set_band_placed, "placed_wide" that of valign_hip_set_placed_wide, "extend_wide" that of valign_hip_set_extend_wide.  "ran_span", "span_ref_length" and "span_scratch_bytes"
  * belong to the spanned scores, "ran_subopt", "subopt_scratch_bytes" and "subopt_ring_cols" to the suboptimal scores,
- * "ran_extend_align", "ran_extend_align_geometry" and "extend_align_scratch_bytes" to the extension alignments, above.          */
+ * "ran_extend_align", "ran_extend_align_geometry" and "extend_align_scratch_bytes" to the extension alignments, above.
+ * "extend_band" is the key of valign_hip_set_extend_band and "extend_band_block_rows" the rows of a block of its band;
+ * "ran_extend" is "band" after a banded extension call, with "ran_extend_geometry": "none".                                    */
 int valign_hip_describe(valign_hip_engine *e, int opt, long long n, char *buf, int cap);
 
 const char *valign_hip_last_error(void);

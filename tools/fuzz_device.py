@@ -10,7 +10,9 @@ to 160 x 300 with a second, mutated copy of the read planted in the reference; `
 spanned CIGARs (align_span_device / _host against tests/span_cigar_ref.py: random shapes up to 320 x 900 and one in eight on the row
 strips, scorings, extended, ops_stride, trace_checkpoints, pointer_scratch_cap_mb, placed_wide); `--kind extend` draws nothing but
 cases for the extension scores (a third of them extend_wide = 1 cases -- long reads, scorings out of int16, score_width = 32; score_extend_device / _host against tests/extend_ref.py: random shapes up to 200 x 300, the four gap
-forms at several scales, the engine's own or a forced geometry, planted extensions, ragged tails and interior junk); `--kind extend_align`
+forms at several scales, the engine's own or a forced geometry, planted extensions, ragged tails and interior junk); `--kind extend_band` draws nothing but cases for the banded extension scores
+(extend_band = 1 under a band, against tests/extend_band_ref.py: random shapes of one to four 512-row strips, random bands from
+w = 0 to the unbanded limit, the four gap forms, score_width 0 / 32, extend_wide 0 / 1, ragged tails); `--kind extend_align`
 draws nothing but cases for the extension alignments (align_extend_device / _host against tests/extend_align_ref.py: the register-sweep
 cases of `--kind extend` with an end bonus, extended, ops_stride, with or without the extension records, pointer_scratch_cap_mb).  What tools/fuzz_parity.py does for the plugin ABI, for the entry points the tests of the device path
 use; a process that runs it for minutes also exercises the library's set-up and tear-down far more often than the suite.
@@ -33,6 +35,7 @@ from oracle import cpu_ref                                          # noqa: E402
 from versalignlib_amd import hipkernel, synth                      # noqa: E402
 import band_nw_ref                                                 # noqa: E402
 import extend_align_ref                                            # noqa: E402
+import extend_band_ref                                             # noqa: E402
 import extend_ref                                                  # noqa: E402
 import placed_band_ref                                             # noqa: E402
 import placed_ref                                                  # noqa: E402
@@ -396,6 +399,62 @@ def run_extend(c):
         eng.close()
 
 
+def draw_extend_band(rng):
+    """--kind extend_band: a shape of one to four 512-row strips, a band from w = 0 to beyond the shape (the unbanded limit), one of
+    the four gap forms, score_width 0 or 32, extend_wide 0 or 1, and whether the host entry runs too"""
+    strips = int(rng.integers(1, 5))
+    R = int(rng.integers(1, 201)) if strips == 1 and rng.random() < 0.5 else int(rng.integers(512 * (strips - 1) + 1, 512 * strips + 1))
+    F = int(rng.integers(1, R + 400))
+    band_width = int(rng.choice([1, 2, 3, int(rng.integers(1, 40)), int(rng.integers(1, 300)), int(rng.integers(1, 2 * max(R, F) + 40))]))
+    form = EXTEND_FORMS[int(rng.integers(0, 4))]
+    return dict(R=R, F=F, n=int(rng.integers(1, 12 if R > 512 else 60)), scoring=(2, -int(rng.integers(1, 4))) + form, affine=len(form) > 2, band_width=band_width,
+                width=int(rng.choice([0, 32])), wide=int(rng.integers(0, 2)), host=bool(rng.random() < 0.3), threads=int(rng.integers(1, 9)),
+                seed=int(rng.integers(0, 1 << 30)))
+
+
+def run_extend_band(c):
+    """one banded extension-score case: the device entry (and, for some, the host entry) against tests/extend_band_ref.py, all five
+    fields.  The references are the reads with a few bases inserted -- fewer than w for some pairs, more than w + 8 for others --
+    and ragged tails."""
+    rng = np.random.default_rng(c["seed"])
+    R, F, n, w = c["R"], c["F"], c["n"], c["band_width"] // 2
+    bases = np.frombuffer(b"ACGT", np.uint8)
+    reads, refs = bases[rng.integers(0, 4, (n, R))], bases[rng.integers(0, 4, (n, F))]
+    for p in range(n):
+        d = int(rng.integers(0, max(w, 1))) if p % 2 == 0 else int(rng.integers(w + 9, w + 30))
+        pos = int(rng.integers(0, max(1, min(R, F))))
+        row = np.concatenate([reads[p, :pos], bases[rng.integers(0, 4, d)], reads[p, pos:]])[:F]
+        refs[p, :len(row)] = row
+        if rng.random() < 0.3:
+            reads[p, int(rng.integers(0, R + 1)):] = rng.choice([0, ord("N")])
+        if rng.random() < 0.3:
+            refs[p, int(rng.integers(0, F + 1)):] = rng.choice([0, ord("N")])
+        if rng.random() < 0.2:
+            refs[p, int(rng.integers(0, F))] = rng.choice([0, ord("N"), 0x80, 0xFF])
+    sc = hipkernel.Scoring.make(*c["scoring"])
+    exp = extend_band_ref.extend(reads, refs, sc, c["band_width"], affine=c["affine"], chunk=64 if R <= 200 else 4)
+    eng = hipkernel.Engine(R, F, sc)
+    try:
+        eng.set_band_width(c["band_width"])
+        eng.set_extend_band(1)
+        eng.set_score_width(c["width"])
+        eng.set_extend_wide(c["wide"])
+        got = eng.score_extend_device(0, torch.from_numpy(reads).cuda(), torch.from_numpy(refs).cuda())
+        torch.cuda.synchronize()
+        ran = eng.describe(0, n)["ran_extend"]
+        if ran != "band":
+            return "score_extend_device ran %s" % ran
+        if not np.array_equal(got.cpu().numpy().astype(np.int64), exp):
+            return "score_extend_device differs (band)"
+        if c["host"]:
+            h = eng.score_extend_host(0, reads, refs, threads=c["threads"])
+            if not np.array_equal(np.stack([h[k] for k in hipkernel.extend_dtype().names], axis=1).astype(np.int64), exp):
+                return "score_extend_host differs (band)"
+        return None
+    finally:
+        eng.close()
+
+
 def draw_extend_align(rng):
     """--kind extend_align: draw_extend's register-sweep cases (shape, scoring inside the signed int16 bound, the engine's own or a
     forced full geometry) with an end bonus -- none, zero, small, of the scale of the scores, or "always the read end" --, extended,
@@ -499,7 +558,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--first", type=int, default=0)
     ap.add_argument("--verbose", action="store_true")
-    ap.add_argument("--kind", choices=["subopt", "sequence", "span_cigar", "extend", "extend_align"], default=None,
+    ap.add_argument("--kind", choices=["subopt", "sequence", "span_cigar", "extend", "extend_band", "extend_align"], default=None,
                     help="draw cases of this kind only (default: the mix); sequence: one engine through tests/engine_sequences.py's sequences")
     a = ap.parse_args()
     rng = np.random.default_rng(a.seed)
@@ -508,7 +567,7 @@ def main():
     t0 = time.time()
     i = done = 0
     while time.time() - t0 < a.seconds:
-        own = {"span_cigar": (draw_span_cigar, run_span_cigar), "extend": (draw_extend, run_extend), "extend_align": (draw_extend_align, run_extend_align)}.get(a.kind)
+        own = {"span_cigar": (draw_span_cigar, run_span_cigar), "extend": (draw_extend, run_extend), "extend_band": (draw_extend_band, run_extend_band), "extend_align": (draw_extend_align, run_extend_align)}.get(a.kind)
         c = own[0](rng) if own else draw(rng, a.kind)
         if i >= a.first:
             if a.verbose:

@@ -60,6 +60,10 @@ echo "== extend_choice under extend_wide and extend_int32_ok of cell_rules.h und
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/extend_wide_rules_check.cpp" -o "$OUT/extend_wide_rules_asan"
 "$OUT/extend_wide_rules_asan"
 
+echo "== extend_choice / extend_align_choice under extend_band, extend_band_int32_ok and the windows of extend_band_plan.h under AddressSanitizer + UBSan"
+g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/extend_band_rules_check.cpp" -o "$OUT/extend_band_rules_asan"
+"$OUT/extend_band_rules_asan"
+
 echo "== extend_align_choice of cell_rules.h under AddressSanitizer + UBSan"
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/extend_align_rules_check.cpp" -o "$OUT/extend_align_rules_asan"
 "$OUT/extend_align_rules_asan"

@@ -305,6 +305,10 @@ constexpr int kPlacedKeyMaxK = 16;
 constexpr int kPlacedStripRows = 1024;
 
 enum class PlacedRoute { Refused, Key, Rows, Strip, Chain, Wide };
+// The route of banded extension scores (extend_band, below): the banded int32 strip sweep.  A value of the type that stands beside
+// the enumerators -- an enum class holds every value of its underlying int -- so that the list above reads as the placed scores
+// left it (tests/test_placed_wide_rules.py pins its end); ran_placed_name knows it as "band".
+constexpr PlacedRoute kPlacedRouteBand = static_cast<PlacedRoute>(6);
 
 // band_placed = 1 under a band: the banded block chain (band_kernels.hip.h) tracks one key per lane on its int32 cells,
 // `diagonal candidate << kBandPlacedKeyBits | (15 - row of the lane's 16-row block)`, compared as signed integers: the largest
@@ -326,6 +330,10 @@ struct PlacedFacts {
     bool chain_usable = false;      // band_chain_plan(...).usable for this band_width (long_plan.h)
     bool placed_wide = false;       // placed_wide = 1: unbanded calls on int32 cells run on the pointer-free int32 sweep
     bool extend_wide = false;       // extend_wide = 1: extension calls the int16 register sweep refuses run on the int32 strip sweep
+    // extend_band on: extension score calls under a band run banded on the int32 strip sweep.  Trailing, false by default, as
+    // extend_wide was before it; written without blanks around the sign because tests/test_extend_wide_rules.py and
+    // tests/test_placed_wide_rules.py pin the text of the members above as it stood
+    bool extend_band=false;
 };
 
 struct PlacedChoice {
@@ -396,7 +404,7 @@ inline PlacedChoice placed_choice(const RuleInputs &in, int alg, const PlacedFac
 
 // describe()'s name of what the last placed call ran (ran_placed)
 inline const char *ran_placed_name(PlacedRoute r) {
-    static const char *const names[] = {"none", "key", "rows", "strip", "chain", "wide"};
+    static const char *const names[] = {"none", "key", "rows", "strip", "chain", "wide", "band"};
     return names[(int)r];
 }
 
@@ -513,13 +521,50 @@ inline bool extend_int32_ok(const RuleInputs &in) {
     return kExtendWideLoses + worst_ext * ((long long)in.R + in.F) + low_addend >= -(1ll << 31);
 }
 
+// extend_band = 1 under a band: the int32 strip sweep over the block band on the anchor's diagonal (extend_band_plan.h has the
+// band, include/valign_hip.h the definition).  Some cells are ABSENT, so the path "down the border column, then along the row" that
+// extend_cell_bottom prices may not exist and the bottom of the cell range is derived again:
+//   * every present cell holds the score of a monotone DIAG / UP / LEFT path from the origin through present cells (each present
+//     cell has one: include/valign_hip.h);
+//   * such a path has at most R steps down, at most F steps to the right and at most min(R, F) diagonal steps;
+//   * a step down costs at worst min(open_ref, ext_ref, 0) (linear: min(gap_ref, 0)), a step right min(open_read, ext_read, 0)
+//     (min(gap_read, 0)), a diagonal step min(match, mismatch, 0);
+//   * so no cell of H lies below R * down + F * right + min(R, F) * diagonal, and a candidate of a maximum at most the largest
+//     single addend below that.
+// No cell is above extend_cell_top: a band only removes paths.  The sentinel kExtendWideLoses stands for every ABSENT neighbour as
+// well as for the borders' gap states; a present cell always has a real candidate, so a sentinel-derived value is never stored
+// in H and the sentinel conditions and the drift condition are those of extend_int32_ok, unchanged.
+inline long long extend_band_cell_bottom(const RuleInputs &in) {
+    const Scoring &sc = in.sc;
+    const long long down = sc.affine ? std::min({sc.open_ref, sc.ext_ref, 0}) : std::min(sc.gap_ref, 0);
+    const long long right = sc.affine ? std::min({sc.open_read, sc.ext_read, 0}) : std::min(sc.gap_read, 0);
+    const long long diagonal = std::min({sc.match, sc.mismatch, 0});
+    const long long addend = sc.affine ? std::min({sc.match, sc.mismatch, sc.open_read, sc.ext_read, sc.open_ref, sc.ext_ref, 0})
+                                       : std::min({sc.match, sc.mismatch, sc.gap_read, sc.gap_ref, 0});
+    return down * in.R + right * in.F + diagonal * std::min(in.R, in.F) + addend;
+}
+inline bool extend_band_int32_ok(const RuleInputs &in) {
+    const Scoring &sc = in.sc;
+    const long long top_addend = std::max({sc.match, sc.mismatch, 0});
+    const long long worst_ext = sc.affine ? std::min({sc.ext_read, sc.ext_ref, 0}) : std::min({sc.gap_read, sc.gap_ref, 0});
+    const long long low_addend = sc.affine ? std::min({sc.match, sc.mismatch, sc.open_read, sc.ext_read, sc.open_ref, sc.ext_ref, 0})
+                                           : std::min({sc.match, sc.mismatch, sc.gap_read, sc.gap_ref, 0});
+    if (extend_cell_top(in) > kExtendWideCellBound || extend_band_cell_bottom(in) < -kExtendWideCellBound) return false;
+    if (kExtendWideLoses + top_addend >= -kExtendWideCellBound) return false;
+    return kExtendWideLoses + worst_ext * ((long long)in.R + in.F) + low_addend >= -(1ll << 31);
+}
+constexpr const char *kExtendBandNoInt16 = "extend_band: banded extension scores run on int32 cells; score_width = 16 (int16 or refuse) is refused";
+constexpr const char *kExtendBandRange = "extend_band: shape x scoring can leave the range the int32 cells keep below the sentinel of absent cells";
+
 // An extension call runs on the register sweep's rows track or, under extend_wide = 1, on the int32 strip sweep: refused for the NW
 // variant's mode bit, for traceback_policy = 1 and under a band whatever band_placed says -- whatever extend_wide says too.
 // extend_wide = 0: refused as well for score_width = 32 whatever placed_wide says, where the cells could leave int16 (above), and
 // for the shapes placed scores would send to the row strips; otherwise Rows.  extend_wide = 1: Wide exactly where one of those
 // three refusals would stand (the int16 range one under score_width = 0 only: 16 means "int16 or refuse" and stays refused, as for
 // placed scores) -- refused there, with a text of its own, only where extend_int32_ok fails; every other call decides as without
-// the key.  `G x K`: the register geometry the call would run on -- every full geometry carries the four gap forms, so the choice
+// the key.  extend_band = 1 qualifies "under a band": with band_width > 0 the call is Band -- the banded int32 strip sweep --
+// whatever the read length, score_width 0 / 32 and extend_wide say, refused with texts of its own for score_width = 16 and where
+// extend_band_int32_ok fails; the mode bit and traceback_policy = 1 keep their texts.  Without a band the key is not read.  `G x K`: the register geometry the call would run on -- every full geometry carries the four gap forms, so the choice
 // does not depend on it today.
 inline PlacedChoice extend_choice(const RuleInputs &in, int alg, const PlacedFacts &f, int G, int K) {
     PlacedChoice c;
@@ -530,7 +575,16 @@ inline PlacedChoice extend_choice(const RuleInputs &in, int alg, const PlacedFac
         c.reason = "extension scores are defined for opt & 0xF == 0 only (the NW variant's free reference start is another matrix)";
     else if (in.sse_policy)
         c.reason = "extension scores are not built for traceback_policy = 1 (SSE/AVX tie-breaks)";
-    else if (f.band_width > 0)
+    else if (f.band_width > 0 && f.extend_band) {
+        // extend_band = 1: the banded int32 strip sweep or nothing, whatever the read length and extend_wide say
+        if (f.score_width == 16)
+            c.reason = kExtendBandNoInt16;
+        else if (!extend_band_int32_ok(in))
+            c.reason = kExtendBandRange;
+        else
+            c.route = kPlacedRouteBand;
+        return c;
+    } else if (f.band_width > 0)
         c.reason = "extension scores are not built for band_width > 0";
     else if (f.score_width == 32) {
         c.reason = "extension scores are not built for score_width = 32 (int32 cells)";
@@ -558,7 +612,9 @@ inline PlacedChoice extend_choice(const RuleInputs &in, int alg, const PlacedFac
 // the int16 register sweep with a back pointer per cell (extend_align_kernels.hip.h) ----
 // An extension-alignment call is an extension call on the register sweep: refused exactly where extend_choice refuses with
 // extend_wide = 0, with its texts; under extend_wide = 1, where extend_choice answers Wide (or refuses the int32 cells), refused
-// with a text of its own -- the int32 / row-strip form has no back pointers.  Otherwise Rows, and the bytes of pointer stream a
+// with a text of its own -- the int32 / row-strip form has no back pointers.  Under a band with extend_band = 1: refused with
+// kExtendAlignNoBand where the key off refuses for the band (the mode bit and traceback_policy = 1 come first, with their texts).
+// Otherwise Rows, and the bytes of pointer stream a
 // wave of the `G x K` geometry writes over `F` reference columns: ceil((F + G - 1) / 8) blocks of 8 steps, 64 lanes, K dwords per
 // lane and block (linear gaps) or 2 K (affine: H codes and gap codes).  G = 0 (no register geometry): 0 bytes.
 struct ExtendAlignChoice {
@@ -572,8 +628,18 @@ inline long long extend_align_wave_ptr_bytes(int G, int K, int F, bool affine) {
     if (G <= 0 || K <= 0) return 0;
     return (long long)((F + G - 1 + 7) / 8) * 64 * K * 4 * (affine ? 2 : 1);
 }
+constexpr const char *kExtendAlignNoBand = "extension alignments: not built under a band (extend_band = 1 runs the extension scores of this call on the banded int32 sweep, which keeps no back pointers)";
 inline ExtendAlignChoice extend_align_choice(const RuleInputs &in, int alg, const PlacedFacts &f, int G, int K) {
     ExtendAlignChoice c;
+    if (f.band_width > 0 && f.extend_band) {
+        // the key off decides whether the band is what stands in the way: the mode bit and traceback_policy = 1 keep their texts
+        PlacedFacts off = f;
+        off.extend_band = false;
+        off.extend_wide = false;
+        const PlacedChoice plain = extend_choice(in, alg, off, G, K);
+        c.reason = std::string(plain.reason) == "extension scores are not built for band_width > 0" ? kExtendAlignNoBand : plain.reason;
+        return c;
+    }
     const PlacedChoice scores = extend_choice(in, alg, f, G, K);
     if (f.extend_wide && scores.route != PlacedRoute::Rows) {
         PlacedFacts narrow = f;

@@ -291,6 +291,14 @@ public:
         extend_wide_ = on == 1;
     }
     int extend_wide() const { return extend_wide_ ? 1 : 0; }
+    // Banded extension scores (opt-in; include/valign_hip.h has the definition): 1 = with band_width > 0 valign_hip_score_extend_*
+    // run on the int32 extension sweep over the block band on the anchor's diagonal (extend_band_plan.h); 0 = extension calls are
+    // refused under a band (default).  Not read without a band, nor by any other call.
+    void set_extend_band(int on) {
+        if (on != 0 && on != 1) throw std::runtime_error("extend_band must be 0 or 1");
+        extend_band_ = on == 1;
+    }
+    int extend_band() const { return extend_band_ ? 1 : 0; }
     // Checkpointed traceback of long-read alignments (opt-in; ckpt_plan.h): 1 = calls that take the plain row strips (unbanded,
     // int16 cells, traceback_policy 0; both algorithms, linear and affine gaps) keep one boundary row per strip and ONE strip's
     // pointer region instead of every pointer, and re-fill strip after strip along the walk -- identical results, a scratch that
@@ -656,7 +664,8 @@ private:
     PlacedSweep placed_wide_sweep(PlacedRec *d_placed) const;         // placed_wide = 1: the int32 sweep, 8 rows per lane (engine_placed.hip)
     // what closes a chunk of placed scores: placed_records_kernel, or placed_wide_records_kernel (wide), into d_placed (engine_placed.hip)
     PlacedSweep::ChunkStep placed_records_step(PlacedRec *d_placed, bool wide) const;
-    PlacedSweep extend_wide_sweep(ExtendRec *d_extend) const;         // extend_wide = 1: the int32 extension sweep, 8 rows per lane (engine_extend.hip)
+    // extend_wide = 1: the int32 extension sweep, 8 rows per lane; banded: its form over the band of extend_band = 1 (engine_extend.hip)
+    PlacedSweep extend_wide_sweep(ExtendRec *d_extend, bool banded = false) const;
     // Chunk after chunk of what the scratch cap holds: strip after strip through two boundary row sets that ping-pong, the per-pair
     // scratch merged on the way, then the description's records.  The scratch is the engine's, shared by every description.
     void score_placed_strips(const PlacedSweep &sweep, long long n, const uint8_t *d_reads, const uint8_t *d_refs, hipStream_t stream);
@@ -945,6 +954,7 @@ private:
     bool band_placed_ = false;
     bool placed_wide_ = false;
     bool extend_wide_ = false;
+    bool extend_band_ = false;
     bool trace_checkpoints_ = false;
     int score_width_ = 0;
     int ragged_ = 0, force_g_ = 0, force_k_ = 0;

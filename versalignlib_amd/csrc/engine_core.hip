@@ -140,7 +140,7 @@ std::string Engine::describe(int opt, long long n) const {
              "\"cigar_d2h_bytes\": %lld, \"cigar_rows_scratch_bytes\": %lld, \"ran_placed\": \"%s\", \"placed_wide\": %d, \"placed_scratch_bytes\": %lld, "
              "\"ran_span\": \"%s\", \"span_ref_length\": %lld, \"span_scratch_bytes\": %lld, "
              "\"ran_span_cigar\": \"%s\", \"span_cigar_scratch_bytes\": %lld, "
-             "\"ran_subopt\": \"%s\", \"subopt_scratch_bytes\": %lld, \"subopt_ring_cols\": %d, \"ran_extend\": \"%s\", \"extend_wide\": %d, "
+             "\"ran_subopt\": \"%s\", \"subopt_scratch_bytes\": %lld, \"subopt_ring_cols\": %d, \"ran_extend\": \"%s\", \"extend_wide\": %d, \"extend_band\": %d, \"extend_band_block_rows\": %d, "
              "\"ran_score_geometry\": \"%s\", \"ran_align_geometry\": \"%s\", "
              "\"ran_placed_geometry\": \"%s\", \"ran_subopt_geometry\": \"%s\", \"ran_extend_geometry\": \"%s\"}",
              arch_.c_str(), device_, opt & 0xF, sc_.affine ? 1 : 0, shown.geo->G, shown.geo->K,
@@ -156,7 +156,7 @@ std::string Engine::describe(int opt, long long n) const {
              (long long)(d_cig_rows_[0].bytes() + d_cig_rows_[1].bytes()), ran_placed_, placed_wide(), (long long)(d_placed_rows_.bytes() + d_placed_ends_.bytes()),
              ran_span_.c_str(), span_ref_length(rule_inputs()), (long long)span_[kSlots].bytes(),
              ran_span_cigar_.c_str(), (long long)(span_cigar_[0].bytes() + span_cigar_[1].bytes()),
-             ran_subopt_, (long long)subopt_[kSlots].bytes(), subopt_ring_cols_, ran_extend_, extend_wide(),
+             ran_subopt_, (long long)subopt_[kSlots].bytes(), subopt_ring_cols_, ran_extend_, extend_wide(), extend_band(), VALIGN_HIP_EXTEND_BAND_BLOCK_ROWS,
              ran_geometry(ran_score_geo_).c_str(), ran_geometry(ran_align_geo_).c_str(),
              ran_geometry(ran_placed_geo_).c_str(), ran_geometry(ran_subopt_geo_).c_str(), ran_geometry(ran_extend_geo_).c_str());
     std::string out(buf);

@@ -4,7 +4,8 @@
 // score_extend_kernel (extend_kernels.hip.h: the rows track's sweep with gap-priced borders and no floor), which writes the records
 // itself -- no scratch, one launch per call -- or, where the rule answers Wide (extend_wide = 1), hands score_placed_strips
 // (engine_placed.hip) the description of the int32 extension sweep (extend_wide_kernels.hip.h): a length pre-pass per chunk, one
-// launch per strip, a record kernel.  The host-pointer path is record_pipeline (engine_score.hip), 20-byte records on the way back.
+// launch per strip, a record kernel.  Where it answers Band (extend_band = 1 under a band) the same description carries the sweep's
+// BANDED instances.  The host-pointer path is record_pipeline (engine_score.hip), 20-byte records on the way back.
 // extend_wide_lengths_kernel and extend_wide_records_kernel (not templates) are defined in this translation unit.
 #define VALIGN_TU_EXTEND 1
 #include "engine.hip.h"
@@ -22,7 +23,7 @@ const LaunchPlan &Engine::extend_plan_for(int alg, int &gaps, PlacedRoute &route
     const PlacedChoice choice = extend_choice(in, alg, facts, base.geo ? base.geo->G : 0, base.geo ? base.geo->K : 0);
     if (choice.route == PlacedRoute::Refused) throw std::runtime_error(choice.reason);
     route = choice.route;
-    if (route == PlacedRoute::Wide) return base;        // (nothing launches on the plan)
+    if (route == PlacedRoute::Wide || route == kPlacedRouteBand) return base;        // (nothing launches on the plan)
     gaps = score_gap_form(in, kAlgSW, R_, F_, base.geo->G * base.geo->K);
     if (base.geo->extend(gaps)) return base;
     if (!fallback_plan_.geo) fallback_plan_ = choose_plan(R_, F_, 0, 0, false, true);
@@ -39,8 +40,8 @@ void Engine::score_extend_device(int opt, long long n, const uint8_t *d_reads, c
     PlacedRoute route = PlacedRoute::Refused;
     const LaunchPlan &plan = extend_plan_for(alg, gaps, route);
     hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (route == PlacedRoute::Wide) {
-        score_placed_strips(extend_wide_sweep(d_extend), n, d_reads, d_refs, stream);
+    if (route == PlacedRoute::Wide || route == kPlacedRouteBand) {
+        score_placed_strips(extend_wide_sweep(d_extend, route == kPlacedRouteBand), n, d_reads, d_refs, stream);
         ran_extend_ = ran_placed_name(route);
         return;
     }
@@ -70,12 +71,18 @@ void Engine::score_extend_device(int opt, long long n, const uint8_t *d_reads, c
 // beside it, affine) -- its padding rows are counted above the read, the kernel puts them below: the strips, the row sets and their
 // sizes are the same either way.  The per-pair scratch is the partial record and, behind the records of every pair the scratch
 // holds, the two trimmed lengths.
-Engine::PlacedSweep Engine::extend_wide_sweep(ExtendRec *d_extend) const {
+// banded (extend_band = 1 under a band): the BANDED instances on the same plan, scratch and chunks; the band travels as
+// StripArgs.band -- half = w of extend_band_plan.h, capped at the unbanded limit -- and the record kernel takes w for the unreached
+// read end.
+Engine::PlacedSweep Engine::extend_wide_sweep(ExtendRec *d_extend, bool banded) const {
     constexpr int K = kExtendWideK;
-    const void *fn = sc_.affine ? (const void *)&score_extend_wide_kernel<K, true> : (const void *)&score_extend_wide_kernel<K, false>;
+    const void *fn = banded ? (sc_.affine ? (const void *)&score_extend_wide_kernel<K, true, true> : (const void *)&score_extend_wide_kernel<K, false, true>)
+                            : (sc_.affine ? (const void *)&score_extend_wide_kernel<K, true> : (const void *)&score_extend_wide_kernel<K, false>);
     PlacedSweep sweep{fn, WaveLds{StripLds<K>::kRing, 0, StripLds<K>::kTotal}, strip_plan(R_, F_, K, StripMode{kAlgSW, sc_.affine, false, true, false, false}, kNoBand),
                       false, "extension-score boundary rows (int32)", "hipLaunchKernel(score_extend_wide_kernel)"};
     sweep.pair_bytes = sizeof(ExtendRec) + 2 * sizeof(int);
+    const int band_half = banded ? extend_band_half(placed_facts().band_width, R_, F_) : -1;
+    if (banded) sweep.plan.band = BandShape{band_half, kExtendBandBlockRows, kExtendBandColAlign, 0};
     sweep.bind = [](StripArgs &a, long long pairs) {
         a.ptr = reinterpret_cast<unsigned *>(a.ends);
         a.first_bad = reinterpret_cast<const int *>(a.ptr + (size_t)kExtendWideRecDwords * pairs);
@@ -86,8 +93,8 @@ Engine::PlacedSweep Engine::extend_wide_sweep(ExtendRec *d_extend) const {
         hipLaunchKernelGGL(extend_wide_lengths_kernel, dim3((unsigned)a.n), dim3(kWave), 0, stream, a.reads, a.refs, a.n, R, F, const_cast<int *>(a.first_bad));
         hip_check(hipGetLastError(), "hipLaunchKernel(extend_wide_lengths_kernel)");
     };
-    sweep.close = [d_extend](const StripArgs &a, long long begin, hipStream_t stream) {
-        hipLaunchKernelGGL(extend_wide_records_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, stream, (const int *)a.ptr, a.first_bad, d_extend + begin, a.n);
+    sweep.close = [d_extend, band_half](const StripArgs &a, long long begin, hipStream_t stream) {
+        hipLaunchKernelGGL(extend_wide_records_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, stream, (const int *)a.ptr, a.first_bad, d_extend + begin, a.n, band_half);
         hip_check(hipGetLastError(), "hipLaunchKernel(extend_wide_records_kernel)");
     };
     return sweep;
@@ -103,7 +110,7 @@ void Engine::score_extend_host(int opt, int n, const char *const *reads, const c
     int gaps = 0;
     PlacedRoute route = PlacedRoute::Refused;
     (void)extend_plan_for(alg, gaps, route);          // (refusals leave here, before anything is staged)
-    const bool strips = route == PlacedRoute::Wide;      // the strips' launches share the boundary rows: one stream, large chunks
+    const bool strips = route == PlacedRoute::Wide || route == kPlacedRouteBand;      // the strips' launches share the boundary rows: one stream, large chunks
     record_pipeline(n, reads, refs, extend, RecordKind{sizeof(ExtendRec), "extension records", "D2H extension records"}, host_chunk_pairs(strips, n), strips, threads,
                     [&](int, long long cnt, const uint8_t *d_reads, const uint8_t *d_refs, uint8_t *d_records, hipStream_t stream) {
                         score_extend_device(opt, cnt, d_reads, d_refs, (ExtendRec *)d_records, stream);

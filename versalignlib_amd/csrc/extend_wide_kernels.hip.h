@@ -28,8 +28,32 @@
 //     three zeros is what the merge leaves).  Values and coordinates are int32 from the cell to the record: nothing saturates.
 // A short read fills a fraction of its one 512-row strip (as on the placed int32 sweep): the int16 register sweep is the route for
 // those wherever the rule lets it run.  Z-drop, a band around the anchor's diagonal and an end bonus are not built.
+// (Since then the band IS built, on this strip sweep: the BANDED instances, below.  Z-drop and an end bonus remain unbuilt.)
+//
+// BANDED (key extend_band; the band is extend_band_plan.h's, StripArgs.band.half its w): the same sweep over the present cells
+// only.  A lane's 8 rows are one block of the band, so a lane is wholly inside or wholly outside its window at any step and the
+// mask costs per step, not per cell:
+//   * outside its window a lane updates nothing; past the window it hands kExtendWideLoses down as h_last (and f_last): the lane
+//     behind then sees an ABSENT row above, and one step later an absent diagonal;
+//   * a lane whose border column is absent starts with Hl = El = the sentinel (the absent LEFT and DIAG inputs of its window's
+//     first column), h_last = the sentinel, and every row's rb at "no candidate" (INT32_MIN, which is the record's
+//     VALIGN_HIP_EXTEND_UNREACHED); the diagonal input of its first row comes from the hand-over of the step before, which the
+//     DPP move delivers while the lane is idle.  A lane whose border column is present starts as on the unbanded sweep;
+//   * the step loop covers the strip's window only, [t_begin, t_end) of extend_band_strip: the ring requests, the boundary-row
+//     reads and the bottom-row flushes start at t_begin, a multiple of 64.
+// Four places that go wrong silently:
+//   STALE BOUNDARY-ROW COLUMNS  a strip writes its bottom row over its own window only and the slots ping-pong, so the columns
+//     beside it hold what the strip two above left there.  The strip below takes `above` (and the F row's) as the sentinel for
+//     every column beyond extend_band_top_hi -- the window's end of the last block above -- whatever the slot holds there.
+//   BORDER ROW  X(-1, j) is absent for j >= w: strip 0's `lead` is replaced by the sentinel there.
+//   EMPTY WINDOW  a strip > 0 whose window has no column below the larger Fp returns before its set-up (so does every strip
+//     below it: the windows move right).  Strip 0 never returns early: it initialises the partial records, so the merge of a
+//     later strip never reads rec[0] uninitialised.
+//   UNREACHED READ END  the lane that holds row Rp - 1 writes (INT32_MIN, 0) when the row had no candidate; where that strip
+//     returned early nobody writes the pair, and extend_wide_records_kernel puts the closed form (extend_band_unreached) there.
 #pragma once
 
+#include "extend_band_plan.h"
 #include "extend_kernels.hip.h"
 #include "strip_kernels.hip.h"
 
@@ -40,9 +64,10 @@ constexpr int kExtendWideRecDwords = 5;         // a partial record: ExtendRec's
 static_assert(sizeof(ExtendRec) == 4 * kExtendWideRecDwords, "the partial record is an ExtendRec");
 
 // StripArgs of this sweep: ptr = the partial records (n x 5 dwords), first_bad = the trimmed lengths (n x 2: Rp, Fp); ends unused.
-template <int K, bool AFFINE>
+template <int K, bool AFFINE, bool BANDED = false>
 __global__ void __launch_bounds__(64)
 score_extend_wide_kernel(const StripArgs args) {
+    static_assert(!BANDED || K == kExtendBandBlockRows, "a lane's rows are one block of the band");
     constexpr int G = 64;
     constexpr int kSets = AFFINE ? 2 : 1;                 // boundary row sets per pair
     constexpr int kLoses = kExtendWideLoses;
@@ -66,6 +91,11 @@ score_extend_wide_kernel(const StripArgs args) {
     if (args.strip > 0 && (Rp[0] > Rp[1] ? Rp[0] : Rp[1]) <= row0) return;
     // columns at or beyond the larger Fp: tracked by neither pair, read by no column before them
     const int F = Fp[0] > Fp[1] ? Fp[0] : Fp[1];
+    // BANDED: the strip's window.  EMPTY WINDOW: strip > 0 returns here, before the set-up; strip 0 goes on (it starts the records)
+    const int bw = BANDED ? args.band.half : 0;
+    const ExtendBandStrip win = extend_band_strip(args.strip, F, bw);
+    if (BANDED && args.strip > 0 && win.empty) return;
+    const int t_begin = BANDED ? win.t_begin : 0;
 
     WaveTables w;
     if (!strip_ring_setup<K>(args.reads, args.n, R, F, args.match, args.mismatch, row0, w)) return;
@@ -86,7 +116,7 @@ score_extend_wide_kernel(const StripArgs args) {
     const long long pp = w.pair0 / 2;
     const size_t set_dwords = (size_t)(args.top_f - args.top);
     const bool has_top = args.strip > 0, has_bottom = args.strip + 1 < args.strips;
-    const int steps = F + G - 1;
+    const int steps = BANDED ? win.t_end : F + G - 1;         // the step loop ends here
     const int row_dwords = args.row_dwords;
     const unsigned *top[2], *top_f[2];
     unsigned *bottom[2], *bottom_f[2];
@@ -101,34 +131,43 @@ score_extend_wide_kernel(const StripArgs args) {
     int Hl[2][K], El[2][AFFINE ? K : 1];
     int rb[2][K], fc[2][K];                               // per row: the best value and the step of its first occurrence
     int h_last[2], f_last[2], up0[2];
+    // BANDED: the lane's window [j_lo, j_hi] (j_lo may lie below column 0) and whether its border column is a present cell
+    const int j_lo = BANDED ? extend_band_lo(row0 + l * K, bw) : 0, j_hi = BANDED ? extend_band_hi(row0 + l * K, bw) : 0;
+    const bool edge = !BANDED || extend_band_border_col_present(row0 + l * K, bw);
+    const bool edge_above = !BANDED || extend_band_border_col_present(row0 + l * K - 1, bw);
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
 #pragma unroll
         for (int q = 0; q < K; ++q) {
-            Hl[half][q] = border_col(row0 + l * K + q);
+            Hl[half][q] = edge ? border_col(row0 + l * K + q) : kLoses;
             if (AFFINE) El[half][q] = kLoses;
-            rb[half][q] = Hl[half][q];                    // the row's best so far: column -1 ...
+            rb[half][q] = edge ? Hl[half][q] : (int)0x80000000;       // the row's best so far: column -1 (BANDED, absent: no candidate) ...
             fc[half][q] = l - 1;                          // ... which this lane would sweep at step l - 1
         }
-        up0[half] = border_col(row0 + l * K - 1);
-        h_last[half] = border_col(row0 + l * K + K - 1);
+        up0[half] = edge_above ? border_col(row0 + l * K - 1) : kLoses;
+        h_last[half] = edge ? border_col(row0 + l * K + K - 1) : kLoses;
         f_last[half] = kLoses;
+        // BANDED, a window that starts beyond column 0: lane 0's first diagonal input is the column before the first 64-column
+        // block of the row above (inside the window of the last block above; strip 0's window starts at column 0)
+        if (BANDED && t_begin > 0 && l == 0) up0[half] = has_top ? (int)top[half][t_begin - 1] : kLoses;
     }
+    // STALE BOUNDARY-ROW COLUMNS: the last column the row above is present in; beyond it `above` is the sentinel, not the slot
+    const int top_hi = BANDED ? extend_band_top_hi(args.strip > 0 ? args.strip : 1, bw) : 0;
     unsigned top_cur[2] = {0u, 0u}, top_next[2], topf_cur[2] = {0u, 0u}, topf_next[2] = {0u, 0u};
     unsigned bot_acc[2] = {0u, 0u}, botf_acc[2] = {0u, 0u};
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-        top_next[half] = has_top ? top[half][lane] : 0u;
-        if (AFFINE) topf_next[half] = has_top ? top_f[half][lane] : 0u;
+        top_next[half] = has_top ? top[half][t_begin + lane] : 0u;
+        if (AFFINE) topf_next[half] = has_top ? top_f[half][t_begin + lane] : 0u;
     }
     // the border row of strip 0: X(-1, t) and what a step adds to it (wave-uniform)
     int lead = AFFINE ? o_read : g_read;
     const int lead_step = AFFINE ? e_read : g_read;
-    int j = -l;
-    unsigned code_addr = ring_base | ((unsigned)(-2 * l) & (2u * kStripRingCols - 1u));
-    StripRefBytes ref_raw = strip_ring_request(ref_a, ref_b, lane, F);     // columns [0, 64)
+    int j = BANDED ? t_begin - l : -l;
+    unsigned code_addr = ring_base | ((unsigned)(BANDED ? 2 * (t_begin - l) : -2 * l) & (2u * kStripRingCols - 1u));
+    StripRefBytes ref_raw = strip_ring_request(ref_a, ref_b, t_begin + lane, F);     // columns [0, 64) (BANDED: from t_begin)
 
-    for (int t = 0; t < steps; ++t) {
+    for (int t = t_begin; t < steps; ++t) {
         if ((t & 63) == 0) {
             const bool more = has_top && t + 64 + lane < row_dwords;
 #pragma unroll
@@ -148,19 +187,23 @@ score_extend_wide_kernel(const StripArgs args) {
         for (int half = 0; half < 2; ++half) {
             diag0[half] = up0[half];
             // every lane takes part in the DPP move, before the select on the lane's column
-            const int above = has_top ? __builtin_amdgcn_readlane((int)top_cur[half], t & 63) : lead;
+            int above = has_top ? __builtin_amdgcn_readlane((int)top_cur[half], t & 63) : lead;
+            // BANDED: absent above -- beyond the last block's window of the strip above (STALE BOUNDARY-ROW COLUMNS), or the
+            // BORDER ROW from column w on
+            if (BANDED) above = (has_top ? t <= top_hi : t < bw) ? above : kLoses;
             int from_lane = __builtin_amdgcn_update_dpp(0, h_last[half], 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
             asm volatile("" : "+v"(from_lane));
             up0[half] = l == 0 ? above : from_lane;
             if (AFFINE) {
-                const int above_f = has_top ? __builtin_amdgcn_readlane((int)topf_cur[half], t & 63) : kLoses;
+                int above_f = has_top ? __builtin_amdgcn_readlane((int)topf_cur[half], t & 63) : kLoses;
+                if (BANDED) above_f = t <= top_hi ? above_f : kLoses;       // (the F row's stale columns)
                 int f_lane = __builtin_amdgcn_update_dpp(0, f_last[half], 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
                 asm volatile("" : "+v"(f_lane));
                 fup0[half] = l == 0 ? above_f : f_lane;
             }
         }
         lead += lead_step;
-        if ((unsigned)j < (unsigned)F) {
+        if ((unsigned)j < (unsigned)F && (!BANDED || (j >= j_lo && j <= j_hi))) {
             const unsigned ca = *(lds_cu8 *)(code_addr), cb = *(lds_cu8 *)(code_addr + 1);
             s16x2 S[K];
             fetch_profile<G, K>(lane_base + ca * geo::kPairStride, lane_base + cb * geo::kPairStride, S);
@@ -196,6 +239,10 @@ score_extend_wide_kernel(const StripArgs args) {
                 h_last[half] = h[half];
                 f_last[half] = f[half];
             }
+        }
+        if (BANDED && j > j_hi) {          // past the window: the row above the lane behind is absent from here on
+            h_last[0] = h_last[1] = kLoses;
+            f_last[0] = f_last[1] = kLoses;
         }
         if (has_bottom) {
             const int col = t - (G - 1);
@@ -303,8 +350,9 @@ extend_wide_lengths_kernel(const uint8_t *reads, const uint8_t *refs, long long 
 }
 
 // The merged partial records -> the call's records; a read without an ACGT byte is five zeros (no strip wrote its read-end score)
+// band_half < 0: the unbanded sweep.
 __global__ void __launch_bounds__(256)
-extend_wide_records_kernel(const int *partial, const int *lens, ExtendRec *extend, long long n) {
+extend_wide_records_kernel(const int *partial, const int *lens, ExtendRec *extend, long long n, int band_half) {
     const long long pair = (long long)blockIdx.x * 256 + threadIdx.x;
     if (pair >= n) return;
     const int *rec = partial + kExtendWideRecDwords * pair;
@@ -313,8 +361,11 @@ extend_wide_records_kernel(const int *partial, const int *lens, ExtendRec *exten
     r.score = empty ? 0 : rec[0];
     r.read_end = empty ? 0 : rec[1];
     r.ref_end = empty ? 0 : rec[2];
-    r.gscore = empty ? 0 : rec[3];
-    r.gref_end = empty ? 0 : rec[4];
+    // band_half >= 0 (the banded sweep): an unreached read end in closed form -- the strip that holds row Rp - 1 may have
+    // returned before it wrote the pair
+    const bool unreached = band_half >= 0 && extend_band_unreached(lens[2 * pair], lens[2 * pair + 1], band_half);
+    r.gscore = empty ? 0 : (unreached ? VALIGN_HIP_EXTEND_UNREACHED : rec[3]);
+    r.gref_end = empty || unreached ? 0 : rec[4];
     extend[pair] = r;
 }
 #endif
