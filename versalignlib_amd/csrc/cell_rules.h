@@ -217,11 +217,17 @@ inline const char *ran_sym_affine_frame_name(bool tilted) { return tilted ? "til
 
 // The tilted sweep's substitution scores from ROW TABLES in registers instead of the LDS profile (dp_kernels.hip.h:
 // wave_setup_tables and the step's kRowTables form): four bytes per row and pair, so every score the tilted frame adds on
-// the diagonal -- match' = match + 2x, mismatch' = mismatch + 2x, zero' = 2x, and on a lane's row 0 each of them plus o - x --
+// the diagonal -- match' = match + 2x, mismatch' = mismatch + 2x, zero' = 2x, each of them plus o - x (every row takes its
+// diagonal from H - (o - x), the register E reads anyway, and gets the o - x back from its table) --
 // must be a byte: the smallest of them >= 0, the largest + (o - x) <= 255, o - x >= 0 (the tables add it byte-wise).
-// The window needs nothing more: a column outside the reference scores 0 instead of zero', which puts its diagonal candidate
-// 2x (row 0: o + x) below a floor whose u is at least 3 (2), no lower than B + x (B - (o - x)) >= 0x0400 for every scoring
-// sym_affine_tilt_ok lets through (x >= 0, B >= 1024 + o - x).  lds_profile / lds_tables: bytes of LDS per wave of the launch's
+// The window needs nothing more: a column outside the reference scores 0 instead of zero' + (o - x), which puts its diagonal
+// candidate o + x below a floor whose u is at least 2, no lower than B - (o - x) >= 0x0400 for every scoring
+// sym_affine_tilt_ok lets through (x >= 0, B >= 1024 + o - x).
+// The same bytes let the row-table step add and subtract on the 32-bit word that holds two pairs (v_add_u32 / v_sub_u32 in place
+// of v_pk_add_u16 / v_pk_sub_i16): a score in [0, 255] added to a half of the window cannot carry, since the sum is an operand of
+// the window itself (sym_affine_tilt_ok), and o - x in [0, 255] taken off an H >= B >= 0x0400 + (o - x) cannot borrow; the
+// LDS-profile form, whose scores may be negative, keeps the packed instructions (dp_kernels.hip.h: WORD ARITHMETIC).
+// lds_profile / lds_tables: bytes of LDS per wave of the launch's
 // plan and of the row-table set-up (row_table_lds): the tables are taken where they need no more, so that no block asks for
 // more LDS than its plan was sized for (long references: the selector stream has four bytes per column, the codes two).
 inline int sym_affine_row_table_low(const Scoring &sc) { return std::min({sc.match, sc.mismatch, 0}) - 2 * sc.ext_ref; }

@@ -556,7 +556,8 @@ __device__ __forceinline__ bool wave_setup(const uint8_t *reads, const uint8_t *
 // ---- row tables: the set-up of score_kernel<G, K, kAlgSW, kGapAffineSym>'s tilted sweep where every score fits a byte ----
 // (cell_rules.h: sym_affine_row_tables_ok).  No profile is built.  Each lane keeps, for its K rows, one dword per row and
 // pair -- Ta[q], Tb[q]: byte c the score of the row's read base against reference class c + 1 (match or mismatch; all four
-// zero_score where the row is a padding row or the base no ACGT; row 0 of every lane plus row0_score) -- and the references
+// zero_score where the row is a padding row or the base no ACGT; EVERY row plus row0_score, the o - x its diagonal is short
+// of: the step reads it from H - (o - x) in every row, as row 0 always did) -- and the references
 // become a stream of SELECTOR dwords, one per column and lane group: bytes {ca, 0x0c, 4 + cb, 0x0c}, ca / cb the class - 1
 // of pair A's / pair B's base, so that v_perm_b32(Tb[q], Ta[q], selector) IS the packed score of row q (selector byte 0x0c
 // yields 0x00: the high bytes).  A base that is no ACGT, and every column of the pads, selects 0x0c in its half too: the
@@ -647,8 +648,11 @@ __device__ __forceinline__ bool wave_setup_tables(const uint8_t *reads, const ui
             }
         }
         const unsigned r4 = ((unsigned)row0_score & 0xFFu) * 0x01010101u;      // (no byte carries: the rule bounds every sum by 255)
-        Ta[0] += r4;
-        Tb[0] += r4;
+#pragma unroll
+        for (int q = 0; q < K; ++q) {                                          // every row: the step takes its diagonals from H - (o - x)
+            Ta[q] += r4;
+            Tb[q] += r4;
+        }
     }
     __syncthreads();                                                           // the raw reads make way for the stream
 
@@ -1335,29 +1339,54 @@ score_kernel(const ScoreArgs args) {
                 // port has.  profiles/r21_sym_affine_bookkeeping.txt.
                 // THE ROW TABLES (FORM kRowTables; kLdsProfile is the step as described so far).  Where every S' fits a byte the lane
                 // holds them -- Ta[q], Tb[q]: four bytes, row q against the four reference classes, pair A and pair B, built by
-                // wave_setup_tables, row 0 with its o - x -- and a step fetches ONE selector dword {ca, 0x0c, 4 + cb, 0x0c}:
-                // S'[q] = v_perm_b32(Tb[q], Ta[q], selector), the perm the profile's merge takes anyway.  No slab numbers, no address
-                // arithmetic, no profile loads; the stream is fetched two steps ahead (volatile, as the code bytes are).
-                // A base that is no ACGT, and every column of the pads, selects the constant 0x00 in its half: S' = 0 where the profile
-                // has 2x (row 0: 2x + o - x).  OUTSIDE A REFERENCE'S ACGT COLUMNS THAT IS EXACT:
-                //   * left of column 0 every register holds its floor (by induction from the start values).  d = floor(p-1, j-1) + 0 =
-                //     floor(p, j) - 2x in rows 1 .. K-1 and, row 0, (floor(p-1, j-1) - (o - x)) + 0 = floor(p, j) - o - x: at or below
-                //     the floor, so e = max3(floor - x, floor - o, floor) = floor wins h's max3, the accumulator's too, and the cell
-                //     stays exactly at its floor as with S' = 2x.
+                // wave_setup_tables, EVERY row with o - x on top (S'' = S' + o - x) -- and a step fetches ONE selector dword
+                // {ca, 0x0c, 4 + cb, 0x0c}: S''[q] = v_perm_b32(Tb[q], Ta[q], selector), the perm the profile's merge takes anyway.
+                // No slab numbers, no address arithmetic, no profile loads; the stream is fetched two steps ahead (volatile, as the
+                // code bytes are).
+                // NO H REGISTERS.  Hl[q] is read only as the next step's diagonal of row q + 1, and HOl[q] = Hl[q] - (o - x) is kept
+                // anyway (E's source).  So every row does what row 0 does with the handed-over ho: d[q] = HOl[q - 1] + S''[q], the
+                // o - x back from the table.  (H + S') and (H - (o - x)) + (S' + (o - x)) are the same 16 bits; the byte rule counted
+                // + (o - x) on every score already (sym_affine_row_table_high).  pass1(q + 1) reads HOl[q] before this step's ho
+                // overwrites it, as it read Hl[q].  The row-table forms keep no Hl at all (28 VGPRs at 8 x 19); the LDS-profile form,
+                // whose profile carries o - x in row 0 only, keeps it.
+                // A base that is no ACGT, and every column of the pads, selects the constant 0x00 in its half: S'' = 0 where the
+                // profile form adds 2x.  OUTSIDE A REFERENCE'S ACGT COLUMNS THAT IS EXACT, by one argument for every row:
+                //   * left of column 0 every register holds its floor, HOl its floor less o - x (by induction from the start values).
+                //     d = (floor(p-1, j-1) - (o - x)) + 0 = floor(p, j) - o - x: at or below the floor, so e = max3(floor - x,
+                //     floor - o, floor) = floor wins h's max3, the accumulator's too, and the cell stays exactly at its floor as
+                //     with S' = 2x.
                 //   * right of a pair's last ACGT column (the wave sweeps on to its longest reference's) the profile form repeats
                 //     cells that exist: S' = 2x makes d the cell (p-1, j-1) itself.  Every operation of the cell is monotone in its
-                //     operands and S' only got smaller (d: that cell less 2x, row 0: less o + x), so by induction no register there
-                //     exceeds what the profile form holds, the accumulators are offered nothing they have not seen, and the columns
-                //     up to the last ACGT base -- which never read a column to their right -- are computed as before.
-                //   * THE WINDOW.  Every cell that is computed has u >= 2 (u = l (K - 1) + q + t + 2), rows 1 .. K-1 u >= 3: the
-                //     smallest such d is B + 3x - 2x = B + x, row 0's B + 2x - o - x = B - (o - x), both at or above 0x0400 by the
-                //     bias of the frame (B >= 1024 + o - x, x >= 0: sym_affine_tilt_bias, sym_affine_max3_ok); upwards nothing
-                //     grew.  The rule has no scoring to refuse on the window's account.
+                //     operands and d only got smaller (that cell less o + x), so by induction no register there exceeds what the
+                //     profile form holds, the accumulators are offered nothing they have not seen, and the columns up to the last
+                //     ACGT base -- which never read a column to their right -- are computed as before.
+                //   * THE WINDOW.  Every cell that is computed has u >= 2 (u = l (K - 1) + q + t + 2): the smallest such d is
+                //     B + 2x - o - x = B - (o - x) + x, at or above 0x0400 by the bias of the frame (B >= 1024 + o - x, x >= 0:
+                //     sym_affine_tilt_bias, sym_affine_max3_ok); upwards nothing grew.  The rule has no scoring to refuse on the
+                //     window's account.
                 // A base that is no ACGT BEFORE its reference's last ACGT base must score exactly 2x, which a table cannot give:
                 // wave_setup_tables finds such a wave (`repair`, wave-uniform) and it runs FORM kRowTablesRepair, the same step with
-                // every half that selected 0x00 set to 2x (row 0: 2x + o - x) -- one v_or_b32 per register and four per step
-                // more: the profile's scores at every column, pads included, so exact by the profile form's argument.
-                // tests/test_sym_affine_row_tables_sweep.py restates this step on the CPU.
+                // every half that selected 0x00 set to 2x + o - x (zero_0: a non-negative byte by the same rule, OR-ed onto a half
+                // that is 0) -- one v_or_b32 per register and four per step more: the profile's scores at every column, pads
+                // included, so exact by the profile form's argument.
+                // WORD ARITHMETIC (both row-table forms; the LDS-profile form keeps its packed instructions: its S' may be negative
+                // and its o - x is not bounded below by a rule).  The adds and the subtract of the step are 32-bit ones on the packed
+                // word -- v_add_u32 / v_sub_u32 issue in the full-rate class, v_pk_add_u16 / v_pk_sub_i16 in the half-rate one
+                // (profiles/r02_valu_rate_bitops.txt) -- which is the packed result bit for bit because no half carries or borrows
+                // into its neighbour.  Per operand, smallest and largest half:
+                //   d = diag + S''     diag in [0x0400, 0x7BFF]: an HO of the window (above) or the border; S'' in [0, 255]
+                //                      (sym_affine_row_tables_ok: every table byte and zero_0); the sum is an operand of h's max3,
+                //                      at most 0x7BFF (sym_affine_tilt_ok).  No carry.
+                //   ho = h - (o - x)   h in [floor, 0x7BFF], floor >= B >= 0x0400 + (o - x), o - x in [0, 255]
+                //                      (sym_affine_row_tables_ok, sym_affine_tilt_bias): ho >= 0x0400.  No borrow.
+                //   acc, fl + K x      acc, fl in [0x0400, 0x7BFF]; K x <= x * top index <= 0x77FF (sym_affine_tilt_ok: rows >= K):
+                //                      the sum stays below 0x10000.  (It is within 0x7BFF wherever a maximum reads it afterwards;
+                //                      the last move of a slot may lie past the top index, read by the closing subtract alone.)
+                //   lead_border + lead_step   the group's first lane: B + x - (o - x) + x t in [0x0400, 0x7BFF], x >= 0; every
+                //                      other lane: both halves 0 + 0, the masked halves stay 0.
+                // tests/test_sym_affine_word_arith.py asserts these bounds operand by operand and the equality of every register,
+                // word against halves.
+                // tests/test_sym_affine_row_tables_sweep.py restates the step on the CPU with the H registers it had.
                 // 8 x 19 (TABLES_ONLY).  K is odd: rows 0 .. 17 enter the accumulators in pairs as above, and row 18, which has no
                 // partner, enters the slot of its own anti-diagonal c = 18 + t alone, at once, with ONE two-operand packed maximum.
                 // That keeps the running maximum exact by the same anti-diagonal argument with one operand fewer: every d of
@@ -1380,14 +1409,23 @@ score_kernel(const ScoreArgs args) {
                     sel_cur = sel_ptr[0];
                     sel_next = sel_ptr[1];
                 }
-                const unsigned zero_q = as_u32(pk(s_zero)), zero_0 = as_u32(pk((short)(s_zero + s_row0)));
+                const unsigned zero_0 = as_u32(pk((short)(s_zero + s_row0)));
                 auto tilted_step = [&](auto slot_tag, auto form_tag) __attribute__((always_inline)) {
                     constexpr int SLOT0 = decltype(slot_tag)::value;
                     constexpr int FORM = decltype(form_tag)::value;
+                    // the step's adds and its subtract: on the 32-bit word in the row-table forms (WORD ARITHMETIC, above)
+                    auto add2 = [](s16x2 a, s16x2 b) __attribute__((always_inline)) {
+                        if constexpr (FORM != kLdsProfile) return as_pk(as_u32(a) + as_u32(b));
+                        else return a + b;
+                    };
+                    auto sub2 = [](s16x2 a, s16x2 b) __attribute__((always_inline)) {
+                        if constexpr (FORM != kLdsProfile) return as_pk(as_u32(a) - as_u32(b));
+                        else return a - b;
+                    };
                     s16x2 S[K], d[K];
                     const s16x2 diag0 = up0;
                     up0 = group_prev_or<G>(HOl[K - 1], lead_border, lmask);
-                    lead_border = lead_border + lead_step;
+                    lead_border = add2(lead_border, lead_step);
                     if constexpr (FORM == kLdsProfile) {
                         merge_profile<K>(pa, pb, S);
                         lds_load_lane<K>(lane_base + ca_next * geo::kPairStride, pa);
@@ -1400,9 +1438,9 @@ score_kernel(const ScoreArgs args) {
                         if constexpr (FORM == kRowTablesRepair) {
                             // bit 3 of a selector byte is set where it is 0x0c: 0xFFFF in the halves that selected the constant
                             const unsigned none = ((sel_cur >> 3) & 0x00010001u) * 0xFFFFu;
-                            const unsigned fix_0 = zero_0 & none, fix_q = zero_q & none;
+                            const unsigned fix_0 = zero_0 & none;           // (a non-negative byte per half, as every table byte is)
 #pragma unroll
-                            for (int q = 0; q < K; ++q) S[q] = as_pk(as_u32(S[q]) | (q == 0 ? fix_0 : fix_q));
+                            for (int q = 0; q < K; ++q) S[q] = as_pk(as_u32(S[q]) | fix_0);
                         }
                         if constexpr (SEL16) {
                             sel_cur = __builtin_amdgcn_perm(kSelZero4, sel_next, kSelWiden);
@@ -1416,7 +1454,8 @@ score_kernel(const ScoreArgs args) {
                     }
                     s16x2 e_cur;
                     auto pass1 = [&](int q, s16x2 &e) __attribute__((always_inline)) {
-                        d[q] = (q == 0 ? diag0 : Hl[q - 1]) + S[q];
+                        if constexpr (FORM == kLdsProfile) d[q] = add2(q == 0 ? diag0 : Hl[q - 1], S[q]);
+                        else d[q] = add2(q == 0 ? diag0 : HOl[q - 1], S[q]);     // (NO H REGISTERS: o - x rides on every row's table)
                         e = pk_max3_h(El[q], HOl[q], fl[(q + SLOT0) % K]);
                         El[q] = e;
                     };
@@ -1428,10 +1467,10 @@ score_kernel(const ScoreArgs args) {
                     for (int q = 0; q < K; ++q) {
                         f = pk_max_h(f, ho);
                         s16x2 e_next = pk(0);
-                        if (q + 1 < K) pass1(q + 1, e_next);            // before Hl[q] is overwritten
+                        if (q + 1 < K) pass1(q + 1, e_next);            // before Hl[q] / HOl[q] is overwritten
                         h = pk_max3_h(d[q], e_cur, f);
-                        Hl[q] = h;
-                        ho = h - ox_c;
+                        if constexpr (FORM == kLdsProfile) Hl[q] = h;
+                        ho = sub2(h, ox_c);
                         HOl[q] = ho;
                         if (!(q & 1)) {
                             s16x2 &a = acc[(q + SLOT0) % K];
@@ -1444,8 +1483,8 @@ score_kernel(const ScoreArgs args) {
                     for (int q = 1; q < K; q += 2) dprev[q] = d[q];
                     f_last = f;
                     // row 0's anti-diagonal is complete: the slot moves on to c + K
-                    acc[SLOT0 % K] = acc[SLOT0 % K] + kx_c;
-                    fl[SLOT0 % K] = fl[SLOT0 % K] + kx_c;
+                    acc[SLOT0 % K] = add2(acc[SLOT0 % K], kx_c);
+                    fl[SLOT0 % K] = add2(fl[SLOT0 % K], kx_c);
                     if constexpr (FORM == kLdsProfile) code_ptr += 2;
                 };
                 auto tilted_sweep = [&](auto form_tag) __attribute__((always_inline)) {
