@@ -739,6 +739,49 @@ int valign_hip_align_extend_host(valign_hip_engine *e, int opt, int n, const cha
                                  int end_bonus, int extended, valign_hip_aln *recs, uint32_t *ops, long long ops_cap,
                                  long long *offsets, long long *ops_needed, valign_hip_extend *extend /* may be null */, int threads);
 
+/* Banded extension alignments: CIGARs inside the anchor's band (key extend_band_align; flat API only).  The sentences above that
+ * call extension alignments under a band, or on int32 cells, unbuilt or refused are qualified here: under this key they are built,
+ * on the banded int32 strip sweep, as the extend_band section qualified the sentence before it.
+ *   0 (default): every call runs or is refused exactly as stated above, with the texts stated above.
+ *   1 with band_width > 0 and extend_band = 1: valign_hip_align_extend_device / _host run BANDED (align_extend_band_fill_kernel:
+ *     the BANDED extension sweep that also streams a back pointer per present cell; a launch per 512-row strip), whatever the read
+ *     length, score_width (0 or 32) or extend_wide say; "ran_extend_align": "band", "ran_extend_align_geometry": "none".  With
+ *     band_width == 0 or extend_band == 0 the key is not read: the register route and the refusals above stand.  No other call
+ *     reads the key.  Other values than 0 / 1 are refused with "extend_band_align must be 0 or 1".
+ * DEFINITION.
+ *   matrix ...... X, E, G, the trimmed lengths Rp / Fp, w = band_width / 2, the blocks of B = 8 rows, present and absent cells and
+ *                 the present border cells with their closed forms are exactly those of banded extension scores, above.
+ *   extension record
+ *                 the banded one, bit for bit what valign_hip_score_extend_device returns under the same keys -- gscore =
+ *                 VALIGN_HIP_EXTEND_UNREACHED, gref_end = 0 for an unreached read end included.
+ *   end cell .... the rule of extension alignments, computed in 64 bits.  An unreached read end is never chosen, whatever end_bonus
+ *                 is: INT32_MIN + INT32_MAX = -1 < 0 <= score, so the rule already says so.  end_bonus = INT32_MAX still means
+ *                 "the read end wherever it is reached": |gscore| < 2^28 on this route.
+ *   empty ....... the best cell was chosen and score == 0, or Rp == 0.
+ *   walk ........ the rules of extension alignments, on cell values; an absent candidate equals nothing.  (i, -1) present implies
+ *                 (i-1, -1) present, (-1, j) present implies (-1, j-1) present, and every present interior cell has a present
+ *                 candidate: the walk never leaves the band.
+ * GUARANTEED: score == X_band(end cell), and the ops consume exactly read_end read bases and ref_end reference bases; the
+ * literal-'-' caveat applies as elsewhere.
+ *   limit ....... w >= max(R, F) gives the unbanded extension alignment: on a call the register sweep serves, its result; on a call
+ *                 it refuses (int32 cells, long reads), the definition as tests/extend_align_ref.py restates it.
+ * Records, ops, ops_stride, overflow, offsets, ops_cap / ops_needed, n = 0, opt & 0xF > 1 and d_extend follow
+ * valign_hip_align_extend_* exactly.
+ * REFUSED under the key, with "ran_extend_align": "none": opt & 0xF == 1 and traceback_policy = 1, with their texts;
+ * score_width = 16, with the text that begins "extend_band:"; a shape x scoring that fails the band's int32 bound, with its
+ * "extend_band:" text; extended not 0 or 1; ops_stride < 1; null result buffers.
+ * NOT BUILT, still: Z-drop / X-drop; a register (int16, sub-wave) form of the band -- short reads under a band fill a fraction of
+ * one 512-row strip, as for the scores; checkpointed pointers for this route.
+ * The pointer stream holds 2 bits per swept step and row (twice that with affine gaps) of every strip's window, in the layout of
+ * versalignlib_amd/csrc/extend_band_align_plan.h; chunks keep it under pointer_scratch_cap_mb, the boundary rows in the strip
+ * scratch banded extension scores use and the walk's rows in the compact format's rows scratch.  Calls of one engine belong on one
+ * stream.
+ * valign_hip_describe: "extend_band_align" is the key; after such a call "ran_extend_align" is "band" and
+ * "ran_extend_align_geometry" "none", "align_ptr_bytes_per_pair" the band's pointer bytes per pair, "extend_align_scratch_bytes" the
+ * pointer scratch, end cells and staged extension records the engine holds, "ran_extend_align_chunks" the chunks the call was cut
+ * into.  tests/extend_band_align_ref.py restates the definition in numpy.                                                      */
+int valign_hip_set_extend_band_align(valign_hip_engine *e, int on);
+
 /* Page-lock a host range and map it for the device (hipHostRegister behind a C symbol, so that an FFI caller needs no
  * HIP binding).  valign_hip_align_host into result buffers that lie inside a registered range -- or inside memory the
  * caller page-locked itself -- skips the library's pinned staging and its host-side copy: the device's copy engine

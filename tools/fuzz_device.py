@@ -12,7 +12,10 @@ strips, scorings, extended, ops_stride, trace_checkpoints, pointer_scratch_cap_m
 cases for the extension scores (a third of them extend_wide = 1 cases -- long reads, scorings out of int16, score_width = 32; score_extend_device / _host against tests/extend_ref.py: random shapes up to 200 x 300, the four gap
 forms at several scales, the engine's own or a forced geometry, planted extensions, ragged tails and interior junk); `--kind extend_band` draws nothing but cases for the banded extension scores
 (extend_band = 1 under a band, against tests/extend_band_ref.py: random shapes of one to four 512-row strips, random bands from
-w = 0 to the unbanded limit, the four gap forms, score_width 0 / 32, extend_wide 0 / 1, ragged tails); `--kind extend_align`
+w = 0 to the unbanded limit, the four gap forms, score_width 0 / 32, extend_wide 0 / 1, ragged tails); `--kind extend_band_align`
+draws the same shapes and bands for banded extension alignments (extend_band_align = 1: align_extend_device / _host against
+tests/extend_band_align_ref.py, from the best cell, from the read end and at bonus 20, extended, ops_stride, pointer_scratch_cap_mb);
+`--kind extend_align`
 draws nothing but cases for the extension alignments (align_extend_device / _host against tests/extend_align_ref.py: the register-sweep
 cases of `--kind extend` with an end bonus, extended, ops_stride, with or without the extension records, pointer_scratch_cap_mb).  What tools/fuzz_parity.py does for the plugin ABI, for the entry points the tests of the device path
 use; a process that runs it for minutes also exercises the library's set-up and tear-down far more often than the suite.
@@ -36,6 +39,7 @@ from versalignlib_amd import hipkernel, synth                      # noqa: E402
 import band_nw_ref                                                 # noqa: E402
 import extend_align_ref                                            # noqa: E402
 import extend_band_ref                                             # noqa: E402
+import extend_band_align_ref                                       # noqa: E402
 import extend_ref                                                  # noqa: E402
 import placed_band_ref                                             # noqa: E402
 import placed_ref                                                  # noqa: E402
@@ -525,6 +529,79 @@ def run_extend_align(c):
         eng.close()
 
 
+def draw_extend_band_align(rng):
+    """--kind extend_band_align: draw_extend_band's cases (one to four 512-row strips, random bands up to the unbanded limit, four
+    gap forms, ragged tails) with one of three end bonuses -- the best cell, "the read end wherever it is reached", 20 --, extended,
+    an ops_stride that some alignments overflow, and a pointer-scratch cap for some"""
+    c = draw_extend_band(rng)
+    c.update(n=min(c["n"], 8 if c["R"] > 512 else 24), bonus=int(rng.choice([-1, 2 ** 31 - 1, 20])), extended=bool(rng.random() < 0.5),
+             stride=int(rng.choice([1, 5, 64, 3000])), cap_mb=1 if rng.random() < 0.3 else 0, with_extend=bool(rng.random() < 0.7))
+    return c
+
+
+def run_extend_band_align(c):
+    """one banded extension-alignment case: the device entry (and, for some, the host entry) against
+    tests/extend_band_align_ref.py -- records, the stored ops with the sentinel behind them untouched, and the extension records.
+    The references are the reads with a few bases inserted -- fewer than w for some pairs, more than w + 8 for others -- and ragged
+    tails; no literal '-' byte (the caveat of every CIGAR call)."""
+    rng = np.random.default_rng(c["seed"])
+    R, F, n, w = c["R"], c["F"], c["n"], c["band_width"] // 2
+    bases = np.frombuffer(b"ACGT", np.uint8)
+    reads, refs = bases[rng.integers(0, 4, (n, R))], bases[rng.integers(0, 4, (n, F))]
+    for p in range(n):
+        d = int(rng.integers(0, max(w, 1))) if p % 2 == 0 else int(rng.integers(w + 9, w + 30))
+        pos = int(rng.integers(0, max(1, min(R, F))))
+        row = np.concatenate([reads[p, :pos], bases[rng.integers(0, 4, d)], reads[p, pos:]])[:F]
+        refs[p, :len(row)] = row
+        if rng.random() < 0.3:
+            reads[p, int(rng.integers(0, R + 1)):] = rng.choice([0, ord("N")])
+        if rng.random() < 0.3:
+            refs[p, int(rng.integers(0, F + 1)):] = rng.choice([0, ord("N")])
+        if rng.random() < 0.2:
+            refs[p, int(rng.integers(0, F))] = rng.choice([0, ord("N"), 0x80, 0xFF])
+    sc = hipkernel.Scoring.make(*c["scoring"])
+    exp_recs, exp_ops, exp_ext, _, _ = extend_band_align_ref.align(reads, refs, sc, c["band_width"], c["affine"], end_bonus=c["bonus"], extended=c["extended"],
+                                                                   chunk=16 if R <= 200 else 2)
+    eng = hipkernel.Engine(R, F, sc)
+    try:
+        eng.set_band_width(c["band_width"])
+        eng.set_extend_band(1)
+        eng.set_extend_band_align(1)
+        eng.set_score_width(c["width"])
+        eng.set_extend_wide(c["wide"])
+        if c["cap_mb"]:
+            eng.set_pointer_scratch_cap_mb(c["cap_mb"])
+        stride = c["stride"]
+        recs = torch.full((n, 6), -7, dtype=torch.int32, device="cuda")
+        ops = torch.full((n, stride), -7, dtype=torch.int32, device="cuda")
+        ext = torch.full((n, 5), -7, dtype=torch.int32, device="cuda") if c["with_extend"] else None
+        eng.align_extend_device(0, torch.from_numpy(reads).cuda(), torch.from_numpy(refs).cuda(), end_bonus=c["bonus"], extended=c["extended"],
+                                ops_stride=stride, out=(recs, ops, ext))
+        torch.cuda.synchronize()
+        if eng.describe(0, n)["ran_extend_align"] != "band":
+            return "align_extend_device ran %s" % eng.describe(0, n)["ran_extend_align"]
+        if not np.array_equal(recs.cpu().numpy().astype(np.int64), exp_recs):
+            return "align_extend_device (band): records differ"
+        got = ops.cpu().numpy()
+        for p, want in enumerate(exp_ops):
+            k = min(len(want), stride)
+            if got[p, :k].view(np.uint32).tolist() != want[:k] or not (got[p, k:] == -7).all():
+                return "align_extend_device (band): ops of pair %d differ" % p
+        if ext is not None and not np.array_equal(ext.cpu().numpy().astype(np.int64), exp_ext):
+            return "align_extend_device (band): extension records differ"
+        if c["host"]:
+            h_recs, h_ops, offsets, h_ext = eng.align_extend_host(0, reads, refs, end_bonus=c["bonus"], extended=c["extended"],
+                                                                  with_extend=c["with_extend"], threads=c["threads"])
+            flat = np.stack([h_recs[k] for k in hipkernel.aln_dtype().names], axis=1).astype(np.int64)
+            if not np.array_equal(flat, exp_recs) or h_ops.tolist() != [o for pair in exp_ops for o in pair]:
+                return "align_extend_host differs (band)"
+            if h_ext is not None and not np.array_equal(np.stack([h_ext[k] for k in hipkernel.extend_dtype().names], axis=1).astype(np.int64), exp_ext):
+                return "align_extend_host (band): extension records differ"
+        return None
+    finally:
+        eng.close()
+
+
 def soak_sequences(rng, a):
     """--kind sequence: the generator and the runner of tests/engine_sequences.py (what tests/test_gpu_engine_sequences.py runs
     on its committed seeds) on random seeds: ONE engine per sequence through key changes (extend_wide among them) and calls of all
@@ -558,7 +635,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--first", type=int, default=0)
     ap.add_argument("--verbose", action="store_true")
-    ap.add_argument("--kind", choices=["subopt", "sequence", "span_cigar", "extend", "extend_band", "extend_align"], default=None,
+    ap.add_argument("--kind", choices=["subopt", "sequence", "span_cigar", "extend", "extend_band", "extend_align", "extend_band_align"], default=None,
                     help="draw cases of this kind only (default: the mix); sequence: one engine through tests/engine_sequences.py's sequences")
     a = ap.parse_args()
     rng = np.random.default_rng(a.seed)
@@ -567,7 +644,8 @@ def main():
     t0 = time.time()
     i = done = 0
     while time.time() - t0 < a.seconds:
-        own = {"span_cigar": (draw_span_cigar, run_span_cigar), "extend": (draw_extend, run_extend), "extend_band": (draw_extend_band, run_extend_band), "extend_align": (draw_extend_align, run_extend_align)}.get(a.kind)
+        own = {"span_cigar": (draw_span_cigar, run_span_cigar), "extend": (draw_extend, run_extend), "extend_band": (draw_extend_band, run_extend_band), "extend_align": (draw_extend_align, run_extend_align),
+               "extend_band_align": (draw_extend_band_align, run_extend_band_align)}.get(a.kind)
         c = own[0](rng) if own else draw(rng, a.kind)
         if i >= a.first:
             if a.verbose:

@@ -5,7 +5,8 @@
 
 compiles versalignlib_amd/csrc/kernel_part.hip (-DVALIGN_PART=n), engine_long.hip (--part main: band / long-read kernels),
 engine_align.hip (--part align: strip / fused / traceback kernels), engine_placed.hip (--part placed: the int32 placed sweep) or
-engine_extend.hip (--part extend: the int32 extension sweep) for gfx950 with
+engine_extend.hip (--part extend: the int32 extension sweep), engine_extend_align.hip (--part extend_align: the banded extension
+sweep with back pointers) for gfx950 with
 --cuda-device-only -S, finds the largest innermost loop of the first kernel whose mangled name contains --kernel, and
 counts its instructions by issue class; --all-loops prints every innermost loop of that kernel in program order (the fixed
 part of a sweep -- set-up, fill, drain -- sits in the small ones).  Classes follow the measured rates of
@@ -52,10 +53,11 @@ def main():
     asm = a.asm
     if not asm:
         asm = os.path.join(tempfile.gettempdir(), "valign_part_%s.s" % a.part)
-        src = {"main": "engine_long.hip", "align": "engine_align.hip", "placed": "engine_placed.hip", "extend": "engine_extend.hip"}.get(a.part, "kernel_part.hip")
+        src = {"main": "engine_long.hip", "align": "engine_align.hip", "placed": "engine_placed.hip", "extend": "engine_extend.hip",
+               "extend_align": "engine_extend_align.hip"}.get(a.part, "kernel_part.hip")
         cmd = ["hipcc", "--offload-arch=gfx950", "-std=c++17", "-O3", "--cuda-device-only", "-S", "-I" + os.path.join(ROOT, "include"),
                "-I" + CSRC, os.path.join(CSRC, src), "-o", asm]
-        if a.part not in ("main", "align", "placed", "extend"):
+        if a.part not in ("main", "align", "placed", "extend", "extend_align"):
             cmd.insert(5, "-DVALIGN_PART=%s" % a.part)
         subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
     lines = open(asm).read().split("\n")

@@ -68,6 +68,12 @@ echo "== extend_align_choice of cell_rules.h under AddressSanitizer + UBSan"
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/extend_align_rules_check.cpp" -o "$OUT/extend_align_rules_asan"
 "$OUT/extend_align_rules_asan"
 
+echo "== the pointer layout of extend_band_align_plan.h and extend_align_choice under extend_band_align under AddressSanitizer + UBSan"
+g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/extend_band_align_plan_check.cpp" -o "$OUT/extend_band_align_plan_asan"
+"$OUT/extend_band_align_plan_asan"
+g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/extend_band_align_rules_check.cpp" -o "$OUT/extend_band_align_rules_asan"
+"$OUT/extend_band_align_rules_asan"
+
 echo "== base_classes.h (the byte classifier of the kernels' set-up) under AddressSanitizer + UBSan"
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/base_classes_check.cpp" -o "$OUT/base_classes_asan"
 "$OUT/base_classes_asan"

@@ -11,6 +11,7 @@
 #include <string>
 
 #include "cell_constants.h"
+#include "extend_band_align_plan.h"
 
 namespace valign {
 
@@ -340,6 +341,10 @@ struct PlacedFacts {
     // extend_wide was before it; written without blanks around the sign because tests/test_extend_wide_rules.py and
     // tests/test_placed_wide_rules.py pin the text of the members above as it stood
     bool extend_band=false;
+    // extend_band_align on: extension ALIGNMENT calls under a band with extend_band on run banded, with back pointers, on the same
+    // sweep.  Appended, false by default; the declaration stands behind its name for the same reason as above: tests/
+    // test_extend_band_rules.py pins extend_band as the last line that begins with a member's type
+    /* extend_band_align: */ bool extend_band_align=false;
 };
 
 struct PlacedChoice {
@@ -628,7 +633,27 @@ struct ExtendAlignChoice {
     const char *reason = "";                        // Refused: why
     int blocks8 = 0;                                // 8-step blocks per lane
     long long wave_ptr_bytes = 0;                   // pointer-scratch bytes of one wave
+    int band_half = 0;                              // Band: w of the band (extend_band_plan.h), capped at the unbanded limit
 };
+// extend_band_align = 1 under a band with extend_band = 1 (include/valign_hip.h): the call is Band -- the banded int32 strip sweep
+// with back pointers (extend_band_align_kernels.hip.h) -- wherever banded extension scores run, whatever the read length,
+// score_width 0 / 32 and extend_wide say, and refused where they are refused, with their texts: the mode bit, traceback_policy = 1,
+// score_width = 16 and the band's int32 range.  blocks8 and wave_ptr_bytes are then those of a pair-of-pairs -- the sweep's wave --
+// over all strips, in the layout of extend_band_align_plan.h.  With the key off, without a band or without extend_band nothing
+// below changes.
+inline ExtendAlignChoice extend_band_align_choice(const RuleInputs &in, int alg, const PlacedFacts &f, int G, int K) {
+    ExtendAlignChoice c;
+    const PlacedChoice scores = extend_choice(in, alg, f, G, K);
+    if (scores.route != kPlacedRouteBand) {
+        c.reason = scores.reason;
+        return c;
+    }
+    c.route = kPlacedRouteBand;
+    c.band_half = extend_band_half(f.band_width, in.R, in.F);
+    c.blocks8 = (int)extend_band_align_blocks_before(extend_band_align_strips(in.R), in.F, c.band_half);
+    c.wave_ptr_bytes = extend_band_align_pp_dwords(in.R, in.F, c.band_half, in.sc.affine) * 4;
+    return c;
+}
 constexpr const char *kExtendAlignNoWide = "extension alignments: not built for the int32 / row-strip route of extend_wide = 1 (the extension scores of this call run there)";
 inline long long extend_align_wave_ptr_bytes(int G, int K, int F, bool affine) {
     if (G <= 0 || K <= 0) return 0;
@@ -637,6 +662,7 @@ inline long long extend_align_wave_ptr_bytes(int G, int K, int F, bool affine) {
 constexpr const char *kExtendAlignNoBand = "extension alignments: not built under a band (extend_band = 1 runs the extension scores of this call on the banded int32 sweep, which keeps no back pointers)";
 inline ExtendAlignChoice extend_align_choice(const RuleInputs &in, int alg, const PlacedFacts &f, int G, int K) {
     ExtendAlignChoice c;
+    if (f.band_width > 0 && f.extend_band && f.extend_band_align) return extend_band_align_choice(in, alg, f, G, K);
     if (f.band_width > 0 && f.extend_band) {
         // the key off decides whether the band is what stands in the way: the mode bit and traceback_policy = 1 keep their texts
         PlacedFacts off = f;

@@ -299,6 +299,14 @@ public:
         extend_band_ = on == 1;
     }
     int extend_band() const { return extend_band_ ? 1 : 0; }
+    // Banded extension alignments (opt-in; include/valign_hip.h has the definition): 1 = with band_width > 0 and extend_band = 1
+    // valign_hip_align_extend_* run banded on the int32 strip sweep with back pointers (extend_band_align_kernels.hip.h); 0 = they
+    // are refused under a band (default).  Not read without a band or without extend_band, nor by any other call.
+    void set_extend_band_align(int on) {
+        if (on != 0 && on != 1) throw std::runtime_error("extend_band_align must be 0 or 1");
+        extend_band_align_ = on == 1;
+    }
+    int extend_band_align() const { return extend_band_align_ ? 1 : 0; }
     // Checkpointed traceback of long-read alignments (opt-in; ckpt_plan.h): 1 = calls that take the plain row strips (unbanded,
     // int16 cells, traceback_policy 0; both algorithms, linear and affine gaps) keep one boundary row per strip and ONE strip's
     // pointer region instead of every pointer, and re-fill strip after strip along the walk -- identical results, a scratch that
@@ -666,6 +674,9 @@ private:
     PlacedSweep::ChunkStep placed_records_step(PlacedRec *d_placed, bool wide) const;
     // extend_wide = 1: the int32 extension sweep, 8 rows per lane; banded: its form over the band of extend_band = 1 (engine_extend.hip)
     PlacedSweep extend_wide_sweep(ExtendRec *d_extend, bool banded = false) const;
+    // its banded form without a record sink: the plan, the LDS, the scratch binding and the lengths pre-pass that banded extension
+    // alignments share with the scores (engine_extend_align.hip launches its own fill and closes the chunk itself)
+    PlacedSweep extend_band_sweep() const;
     // Chunk after chunk of what the scratch cap holds: strip after strip through two boundary row sets that ping-pong, the per-pair
     // scratch merged on the way, then the description's records.  The scratch is the engine's, shared by every description.
     void score_placed_strips(const PlacedSweep &sweep, long long n, const uint8_t *d_reads, const uint8_t *d_refs, hipStream_t stream);
@@ -870,6 +881,13 @@ private:
                             int extended, CigarRec *recs, unsigned *ops, int ops_stride, ExtendRec *d_extend, int slot, hipStream_t stream);
     // the encoder over the walk's rows (any pass: the caller fills what launch_cigar_args leaves open)
     void launch_extend_align_cigar(hipStream_t stream, CigarArgs &a);
+    // the scratch of a chunk of `pairs` pairs: the walk's rows, the pointer scratch and end cells and, on the Band route, the
+    // boundary rows, partial records and trimmed lengths in the strip scratch extension scores use
+    void ensure_extend_align_scratch(const LaunchPlan &plan, const ExtendAlignChoice &choice, long long pairs, hipStream_t stream);
+    // the Band route's chunk (extend_band_align = 1): the lengths pre-pass, one fill launch per strip, the ends kernel, the walk
+    // and the encoder
+    void extend_band_align_chunk(const ExtendAlignChoice &choice, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int end_bonus, int extended,
+                                 CigarRec *recs, unsigned *ops, int ops_stride, ExtendRec *d_extend, int slot, hipStream_t stream);
 
     // ---- length-sorted batching (score_host, Smith-Waterman) ----
 
@@ -955,6 +973,7 @@ private:
     bool placed_wide_ = false;
     bool extend_wide_ = false;
     bool extend_band_ = false;
+    bool extend_band_align_ = false;
     bool trace_checkpoints_ = false;
     int score_width_ = 0;
     int ragged_ = 0, force_g_ = 0, force_k_ = 0;
@@ -1030,6 +1049,7 @@ private:
     const char *ran_extend_ = "none";                    // what the last extension call ran: rows, wide (describe)
     const char *ran_extend_align_ = "none";              // what the last extension-alignment call ran: rows (describe)
     const Geometry *ran_extend_align_geo_ = nullptr;     // ... and the geometry its fill was taken from (ran_extend_align_geometry)
+    long long ran_extend_align_chunks_ = 0;              // ... and the chunks it was cut into (ran_extend_align_chunks)
     const char *ran_result_format_ = "rows";             // of the last alignment call: rows / cigar (describe)
     long long cigar_d2h_bytes_ = 0;                      // what the last align_cigar_host call copied back
     const CigarSink *cigar_ = nullptr;

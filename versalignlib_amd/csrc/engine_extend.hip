@@ -100,6 +100,8 @@ Engine::PlacedSweep Engine::extend_wide_sweep(ExtendRec *d_extend, bool banded) 
     return sweep;
 }
 
+Engine::PlacedSweep Engine::extend_band_sweep() const { return extend_wide_sweep(nullptr, true); }
+
 // Host pointers in, host records out: record_pipeline, 20 bytes per pair on the way back.
 void Engine::score_extend_host(int opt, int n, const char *const *reads, const char *const *refs, ExtendRec *extend, int threads) {
     const int alg = opt & 0xF;

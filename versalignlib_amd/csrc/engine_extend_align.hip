@@ -4,8 +4,14 @@
 // align_extend_fill_kernel (extend_align_kernels.hip.h) into the pointer scratch alignments use, extend_walk_kernel into the CIGAR
 // rows scratch at a row pitch of R + F + 1, and cigar_encode_kernel behind it.  extend_walk_kernel (not a template) is defined in
 // this translation unit.
+// Where the rule answers Band (extend_band_align = 1 under a band with extend_band = 1) a chunk is extend_band_align_chunk: the
+// lengths pre-pass and the boundary rows of banded extension scores (extend_band_sweep, engine_extend.hip), one launch of
+// align_extend_band_fill_kernel per strip into the same pointer scratch, extend_band_ends_kernel, extend_band_walk_kernel and the
+// encoder (extend_band_align_kernels.hip.h; its two fill instances and the two other kernels are defined here).  Chunk sizes, the
+// scratch and both entry points are shared: only the chunk body differs.
 #define VALIGN_TU_EXTEND_ALIGN 1
 #include "engine.hip.h"
+#include "extend_band_align_kernels.hip.h"
 
 namespace valign {
 
@@ -16,6 +22,7 @@ const LaunchPlan &Engine::extend_align_plan_for(int alg, ExtendAlignChoice &choi
     in.no_f16 = true;                   // int16 cells
     choice = extend_align_choice(in, alg, facts, base.geo ? base.geo->G : 0, base.geo ? base.geo->K : 0);
     if (choice.route == PlacedRoute::Refused) throw std::runtime_error(choice.reason);
+    if (choice.route == kPlacedRouteBand) return base;                  // (nothing launches on the plan)
     if (base.geo->extend_align(sc_.affine ? 1 : 0)) return base;
     if (!fallback_plan_.geo) fallback_plan_ = choose_plan(R_, F_, 0, 0, false, true);
     if (fallback_plan_.long_mode || !fallback_plan_.geo->extend_align(sc_.affine ? 1 : 0)) throw std::runtime_error("no extension-alignment kernel for this mode");
@@ -33,6 +40,15 @@ long long Engine::extend_align_chunk_pairs(const LaunchPlan &plan, const ExtendA
     const long long by_ptr = (long long)(ptr_cap / (size_t)choice.wave_ptr_bytes) * ppw;
     const long long by_rows = (long long)(rows_cap / (2 * ((size_t)R_ + F_ + 1)));
     long long chunk = std::min(by_ptr, by_rows);
+    if (choice.route == kPlacedRouteBand) {
+        // a wave is a pair-of-pairs; the boundary rows of the chunk's strips lie in the strip scratch, under its cap
+        const StripPlan strips = extend_band_sweep().plan;
+        const size_t rows_per_pp = (size_t)2 * strips.row_sets * strips.row_dwords * 4;
+        const long long by_ptr_pp = (long long)(ptr_cap / (size_t)choice.wave_ptr_bytes) * 2;
+        chunk = std::min({by_ptr_pp, by_rows, strip_chunk_pairs(strip_scratch_cap(free_b + d_placed_rows_.bytes(), scratch_cap_mb_), rows_per_pp, n)});
+        chunk = std::max<long long>(2, chunk / 2 * 2);              // whole waves, at least one
+        return std::min(chunk, n);
+    }
     chunk = std::max(ppb, chunk / ppb * ppb);           // whole blocks, at least one
     return std::min(chunk, n);
 }
@@ -42,6 +58,85 @@ void Engine::ensure_extend_align_rows(int slots, long long pairs, hipStream_t st
     const size_t AL = (size_t)R_ + F_;
     const long long as_pairs = AL ? (long long)(((size_t)pairs * 2 * (AL + 1) + 2 * AL - 1) / (2 * AL)) : pairs;
     ensure_cigar_scratch(slots, std::max(as_pairs, pairs), stream);
+}
+
+void Engine::ensure_extend_align_scratch(const LaunchPlan &plan, const ExtendAlignChoice &choice, long long pairs, hipStream_t stream) {
+    ensure_extend_align_rows(1, pairs, stream);
+    if (choice.route != kPlacedRouteBand) {
+        ensure_trace_scratch(pairs, (size_t)(choice.wave_ptr_bytes / (plan.pairs_per_wave / 2)), plan.pairs_per_wave, stream);
+        return;
+    }
+    ensure_trace_scratch(pairs, (size_t)choice.wave_ptr_bytes, 2, stream);
+    const PlacedSweep sweep = extend_band_sweep();
+    const size_t rows = (size_t)((pairs + 1) / 2) * 2 * sweep.plan.row_sets * sweep.plan.row_dwords * 4, per_pair = sweep.pair_bytes * (size_t)(pairs + 1);
+    if (rows > d_placed_rows_.bytes() || per_pair > d_placed_ends_.bytes()) {
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");          // nothing may still read the old scratch
+        d_placed_rows_.reserve(rows, sweep.rows_label);
+        d_placed_ends_.reserve(per_pair, "extension partial records and trimmed lengths");
+    }
+}
+
+// The Band route.  The strip loop is score_placed_strips' (engine_placed.hip) with the fill in the kernel's place and the pointer
+// regions in StripArgs.ends; what follows the last strip is this route's own.
+void Engine::extend_band_align_chunk(const ExtendAlignChoice &choice, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int end_bonus, int extended,
+                                     CigarRec *recs, unsigned *ops, int ops_stride, ExtendRec *d_extend, int slot, hipStream_t stream) {
+    constexpr int K = kExtendWideK;
+    const PlacedSweep sweep = extend_band_sweep();
+    const StripPlan &plan = sweep.plan;
+    const long long waves = (n + 1) / 2;
+    if (waves > 0x7FFFFFFFll) throw std::runtime_error("batch too large for one launch");
+    const size_t bytes_per_pp = (size_t)2 * plan.row_sets * plan.row_dwords * 4;
+    if ((size_t)waves * (size_t)choice.wave_ptr_bytes > d_ptr_.bytes() || sizeof(EndCell) * (size_t)n > d_ends_.bytes() ||
+        (size_t)n * 2 * ((size_t)R_ + F_ + 1) > d_cig_rows_[slot].bytes() || (size_t)waves * bytes_per_pp > d_placed_rows_.bytes() ||
+        sweep.pair_bytes * (size_t)n > d_placed_ends_.bytes())
+        throw std::runtime_error("extension alignments: chunk larger than its scratch");
+    const void *fn = sc_.affine ? (const void *)align_extend_band_fill_kernel<K, true> : (const void *)align_extend_band_fill_kernel<K, false>;
+    raise_block_lds(fn, sweep.lds.total);
+    const size_t f_rows = plan.f_rows_at(waves), slot_dwords = plan.row_sets * f_rows;
+    StripArgs first{};
+    for (int s = 0; s < plan.strips; ++s) {
+        StripArgs a = strip_args(d_reads, d_refs, n, plan, sweep.lds, s, d_placed_rows_.get(), (size_t)((s + 1) & 1) * slot_dwords, (size_t)(s & 1) * slot_dwords,
+                                 f_rows, d_placed_ends_.get(), nullptr);
+        sweep.bind(a, n);                                           // ptr: the partial records, first_bad: the trimmed lengths behind them
+        if (s == 0) {
+            sweep.open(a, 0, stream);                               // the lengths pre-pass
+            first = a;
+        }
+        a.ends = reinterpret_cast<EndCell *>(d_ptr_.get());         // the chunk's pointer regions
+        void *kargs[] = {&a};
+        hip_check(hipLaunchKernel(fn, dim3((unsigned)waves), dim3(kWave), kargs, (size_t)sweep.lds.total, stream), "hipLaunchKernel(align_extend_band_fill_kernel)");
+    }
+    hipLaunchKernelGGL(extend_band_ends_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const int *)first.ptr, first.first_bad, d_extend, d_ends_.get(), n,
+                       choice.band_half, end_bonus);
+    hip_check(hipGetLastError(), "hipLaunchKernel(extend_band_ends_kernel)");
+    ExtendWalkArgs t{};
+    t.reads = d_reads;
+    t.refs = d_refs;
+    t.ptr = d_ptr_.get();
+    t.ends = d_ends_.get();
+    t.rows = d_cig_rows_[slot].get();
+    t.idx = d_cig_idx_[slot].get();
+    t.n = n;
+    t.R = R_;
+    t.F = F_;
+    t.blocks8 = choice.blocks8;
+    t.affine = sc_.affine ? 1 : 0;
+    t.pitch = R_ + F_ + 1;
+    t.band_half = choice.band_half;
+    hipLaunchKernelGGL(extend_band_walk_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, t);
+    hip_check(hipGetLastError(), "hipLaunchKernel(extend_band_walk_kernel)");
+    CigarArgs a{};
+    a.rows = t.rows;
+    a.idx = t.idx;
+    a.ends = d_ends_.get();
+    a.recs = recs;
+    a.ops = ops;
+    a.ops_stride = ops_stride;
+    a.n = n;
+    a.extended = extended;
+    launch_extend_align_cigar(stream, a);
+    ran_extend_align_ = ran_placed_name(kPlacedRouteBand);
+    align_ptr_bytes_per_pair_ = choice.wave_ptr_bytes / 2;
 }
 
 void Engine::launch_extend_align_cigar(hipStream_t stream, CigarArgs &a) {
@@ -71,6 +166,9 @@ void Engine::launch_extend_align_cigar(hipStream_t stream, CigarArgs &a) {
 void Engine::extend_align_chunk(const LaunchPlan &plan, const ExtendAlignChoice &choice, long long n, const uint8_t *d_reads, const uint8_t *d_refs,
                                 int end_bonus, int extended, CigarRec *recs, unsigned *ops, int ops_stride, ExtendRec *d_extend, int slot,
                                 hipStream_t stream) {
+    ++ran_extend_align_chunks_;
+    if (choice.route == kPlacedRouteBand)
+        return extend_band_align_chunk(choice, n, d_reads, d_refs, end_bonus, extended, recs, ops, ops_stride, d_extend, slot, stream);
     const int G = plan.geo->G, K = plan.geo->K;
     const long long ppw = plan.pairs_per_wave, ppb = ppw * plan.waves_per_block;
     const long long blocks = (n + ppb - 1) / ppb;
@@ -132,6 +230,7 @@ void Engine::align_extend_device(int opt, long long n, const uint8_t *d_reads, c
                                  unsigned *d_ops, int ops_stride, ExtendRec *d_extend, hipStream_t stream) {
     ran_extend_align_ = "none";
     ran_extend_align_geo_ = nullptr;
+    ran_extend_align_chunks_ = 0;
     if (extended != 0 && extended != 1) throw std::runtime_error("extended must be 0 (M) or 1 (= / X)");
     if (ops_stride < 1) throw std::runtime_error("ops_stride must be >= 1");
     if (!d_recs || !d_ops) throw std::runtime_error("null result buffer");
@@ -143,8 +242,7 @@ void Engine::align_extend_device(int opt, long long n, const uint8_t *d_reads, c
     ran_result_format_ = "cigar";
     const size_t rows_cap = (size_t)std::max<long long>(1, dbg_.value("cigar_rows_mb", 512)) << 20;
     const long long chunk = extend_align_chunk_pairs(plan, choice, n, rows_cap);
-    ensure_extend_align_rows(1, chunk, stream);
-    ensure_trace_scratch(chunk, (size_t)(choice.wave_ptr_bytes / (plan.pairs_per_wave / 2)), plan.pairs_per_wave, stream);
+    ensure_extend_align_scratch(plan, choice, chunk, stream);
     for (long long begin = 0; begin < n; begin += chunk)          // (stream order: the next chunk reuses the scratch behind this one's encoder)
         extend_align_chunk(plan, choice, std::min(chunk, n - begin), d_reads + (size_t)begin * R_, d_refs + (size_t)begin * F_, end_bonus, extended,
                            d_recs + begin, d_ops + (size_t)begin * ops_stride, ops_stride, d_extend ? d_extend + begin : nullptr, 0, stream);
@@ -157,6 +255,7 @@ bool Engine::align_extend_host(int opt, int n, const char *const *reads, const c
                                unsigned *ops, long long ops_cap, long long *offsets, long long *ops_needed, ExtendRec *extend, int threads) {
     ran_extend_align_ = "none";
     ran_extend_align_geo_ = nullptr;
+    ran_extend_align_chunks_ = 0;
     if (extended != 0 && extended != 1) throw std::runtime_error("extended must be 0 (M) or 1 (= / X)");
     if (!recs || !offsets || !ops_needed || (!ops && ops_cap > 0)) throw std::runtime_error("null result buffer");
     if (n < 0 || ops_cap < 0) throw std::runtime_error("negative size");
@@ -174,12 +273,12 @@ bool Engine::align_extend_host(int opt, int n, const char *const *reads, const c
     const size_t per_pair = (size_t)3 * (R_ + F_) + 8;         // (the chunks of align_cigar_host)
     long long chunk = std::max<long long>(whole_rounds((long long)(align_chunk_bytes_ / per_pair)), 1024);
     chunk = std::min<long long>(chunk, extend_align_chunk_pairs(plan, choice, n, (size_t)std::max<long long>(1, dbg_.value("cigar_rows_mb", 512)) << 20));
+    if (choice.route == kPlacedRouteBand && chunk < n) chunk = std::max<long long>(2, chunk / 2 * 2);       // whole waves
     reset_pipeline();
     ensure_staging(chunk);
     threads = std::min(std::max(threads, 1), 64);
     hipStream_t st = streams_[0].get();
-    ensure_extend_align_rows(1, chunk, st);
-    ensure_trace_scratch(chunk, (size_t)(choice.wave_ptr_bytes / (plan.pairs_per_wave / 2)), plan.pairs_per_wave, st);
+    ensure_extend_align_scratch(plan, choice, chunk, st);
     if (extend) d_extend_align_recs_.reserve(sizeof(ExtendRec) * (size_t)chunk, "extension records");
     host_stats_ = HostStats{};
     struct Quiesce {            // an error part-way leaves nothing in flight

@@ -14,7 +14,7 @@ namespace valign {
 
 PlacedFacts Engine::placed_facts() const {
     return PlacedFacts{band_width_, score_width_, force_g_ != 0 || force_k_ != 0, align_base_plan().long_mode, band_placed_, band_plan_.usable && !no_band_chain_, placed_wide_,
-                       extend_wide_, extend_band_};
+                       extend_wide_, extend_band_, extend_band_align_};
 }
 
 // The plan a placed call runs on: the one alignments start from where its geometry carries the kernel the rule asks for;

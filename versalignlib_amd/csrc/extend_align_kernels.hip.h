@@ -298,22 +298,27 @@ struct ExtendWalkArgs {
     int G, K, blocks8;
     int affine;               // 1: pointer blocks hold K H-code words followed by K gap-code words
     int pitch;                // bytes of one row: R + F + 1
+    int band_half;            // extend_band_walk_kernel (extend_band_align_kernels.hip.h): w of the band
 };
 
-#ifdef VALIGN_TU_EXTEND_ALIGN      // not a template: defined once, in engine_extend_align.hip
-// One lane per pair.  A chain of dependent loads, as trace_walk is: pointer words are fetched 16 bytes at a time, bases 4 at a
-// time, and the two output rows are written as dwords.
-__global__ void __launch_bounds__(256)
-extend_walk_kernel(const ExtendWalkArgs a) {
-    const long long pair = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (pair >= a.n) return;
-    const int R = a.R, F = a.F, K = a.K, G = a.G;
-    const int wpb = a.affine ? 2 * K : K;
+// The register form's addressing for extend_walk_pair: [block of 8 steps][lane of the wave][wpb words] from the group's first lane
+struct ExtendWalkLayout {
+    int K, wpb, kGapWord;     // kGapWord: the gap codes' word lies this far behind the H codes' (affine)
+    __device__ long long word(int i, int j, int &t) const {
+        const int l = i / K, q = i - l * K;
+        t = j + l;
+        return ((long long)(t >> 3) * kWave + l) * wpb + q;
+    }
+};
+
+// The walk of one pair, one lane.  A chain of dependent loads, as trace_walk is: pointer words are fetched 16 bytes at a time,
+// bases 4 at a time, and the two output rows are written as dwords.  ptr_pair: the first word `layout` counts from, ptr_words:
+// the words that may be read from there; layout.word(i, j, t): the word that holds the H code of the interior cell (i, j), and
+// the step t whose bits are its.
+template <class Layout>
+__device__ __forceinline__ void extend_walk_pair(const ExtendWalkArgs &a, long long pair, const unsigned *ptr_pair, long long ptr_words, Layout &layout) {
+    const int R = a.R, F = a.F;
     const int half_shift = (int)(pair & 1) * 16;
-    // pointer stream: [wave][block][lane of the wave][wpb]; this pair's group starts at lane (pair-of-pairs % groups) * G
-    const int ppw = 2 * (kWave / G);
-    const unsigned *ptr_pair = a.ptr + ((pair / ppw) * a.blocks8 * kWave + ((pair % ppw) >> 1) * G) * (long long)wpb;
-    const long long ptr_words = ((long long)(a.blocks8 - 1) * kWave + G) * wpb;      // words from there to the end of the group's last block
     const uint8_t *read = a.reads + pair * R, *ref = a.refs + pair * F;
     uint8_t *row_read = a.rows + pair * 2 * a.pitch, *row_ref = row_read + a.pitch;
 
@@ -370,8 +375,8 @@ extend_walk_kernel(const ExtendWalkArgs a) {
             move = 2;                                   // the border row: LEFT to the anchor, at H
             state = 0;
         } else {
-            const int l = i / K, q = i - l * K, t = j + l;
-            const long long wi = ((long long)(t >> 3) * kWave + l) * wpb + q;
+            int t;
+            const long long wi = layout.word(i, j, t);
             if (!a.affine) {
                 move = code_at(wi, t);
             } else if (state == 0) {
@@ -381,7 +386,7 @@ extend_walk_kernel(const ExtendWalkArgs a) {
                     continue;
                 }
             } else {
-                const int bits = code_at(wi + K, t);    // bit 0: vertical state extended, bit 1: horizontal state extended
+                const int bits = code_at(wi + layout.kGapWord, t);    // bit 0: vertical state extended, bit 1: horizontal state extended
                 move = state;
                 if (!(bits & state)) state = 0;         // opened here: back to H behind this column
             }
@@ -419,6 +424,22 @@ extend_walk_kernel(const ExtendWalkArgs a) {
     out[1] = (short)(a.pitch - 1);
     out[2] = (short)(k + 1);
     out[3] = (short)(a.pitch - 1);
+}
+
+#ifdef VALIGN_TU_EXTEND_ALIGN      // not a template: defined once, in engine_extend_align.hip
+// One lane per pair.
+__global__ void __launch_bounds__(256)
+extend_walk_kernel(const ExtendWalkArgs a) {
+    const long long pair = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pair >= a.n) return;
+    const int K = a.K, G = a.G;
+    const int wpb = a.affine ? 2 * K : K;
+    // pointer stream: [wave][block][lane of the wave][wpb]; this pair's group starts at lane (pair-of-pairs % groups) * G
+    const int ppw = 2 * (kWave / G);
+    const unsigned *ptr_pair = a.ptr + ((pair / ppw) * a.blocks8 * kWave + ((pair % ppw) >> 1) * G) * (long long)wpb;
+    const long long ptr_words = ((long long)(a.blocks8 - 1) * kWave + G) * wpb;      // words from there to the end of the group's last block
+    ExtendWalkLayout layout{K, wpb, K};
+    extend_walk_pair(a, pair, ptr_pair, ptr_words, layout);
 }
 #endif
 

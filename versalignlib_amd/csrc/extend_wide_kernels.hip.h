@@ -53,6 +53,7 @@
 //     returned early nobody writes the pair, and extend_wide_records_kernel puts the closed form (extend_band_unreached) there.
 #pragma once
 
+#include "extend_band_align_plan.h"
 #include "extend_band_plan.h"
 #include "extend_kernels.hip.h"
 #include "strip_kernels.hip.h"
@@ -64,10 +65,15 @@ constexpr int kExtendWideRecDwords = 5;         // a partial record: ExtendRec's
 static_assert(sizeof(ExtendRec) == 4 * kExtendWideRecDwords, "the partial record is an ExtendRec");
 
 // StripArgs of this sweep: ptr = the partial records (n x 5 dwords), first_bad = the trimmed lengths (n x 2: Rp, Fp); ends unused.
-template <int K, bool AFFINE, bool BANDED = false>
+// PTRS (BANDED only; extend_band_align_kernels.hip.h names the instances and has the codes): the sweep also derives every cell's
+// back pointer and streams the codes to StripArgs.ends, taken as the dwords of the chunk's pointer regions in the layout of
+// extend_band_align_plan.h.  Everything PTRS adds stands under `if constexpr (PTRS)`: the score instances compile to the
+// instructions they had without it.
+template <int K, bool AFFINE, bool BANDED = false, bool PTRS = false>
 __global__ void __launch_bounds__(64)
 score_extend_wide_kernel(const StripArgs args) {
     static_assert(!BANDED || K == kExtendBandBlockRows, "a lane's rows are one block of the band");
+    static_assert(!PTRS || BANDED, "the pointer stream is the banded sweep's");
     constexpr int G = 64;
     constexpr int kSets = AFFINE ? 2 : 1;                 // boundary row sets per pair
     constexpr int kLoses = kExtendWideLoses;
@@ -166,6 +172,19 @@ score_extend_wide_kernel(const StripArgs args) {
     int j = BANDED ? t_begin - l : -l;
     unsigned code_addr = ring_base | ((unsigned)(BANDED ? 2 * (t_begin - l) : -2 * l) & (2u * kStripRingCols - 1u));
     StripRefBytes ref_raw = strip_ring_request(ref_a, ref_b, t_begin + lane, F);     // columns [0, 64) (BANDED: from t_begin)
+    // PTRS: a dword per row, pair A's codes in the low half, pair B's in the high half, 2 bits per step, the newest lowest; and
+    // the lane's first dword of the strip's first block (the regions are sized for the engine's F: args.F)
+    unsigned acc_h[PTRS ? K : 1], acc_g[PTRS && AFFINE ? K : 1];
+    unsigned *stream = nullptr;
+    if constexpr (PTRS) {
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+            acc_h[q] = 0u;
+            if (AFFINE) acc_g[q] = 0u;
+        }
+        stream = reinterpret_cast<unsigned *>(args.ends) + pp * extend_band_align_pp_dwords(R, args.F, bw, AFFINE) +
+                 extend_band_align_strip_base(args.strip, args.F, bw, AFFINE) + extend_band_align_word(0, l, 0, AFFINE);
+    }
 
     for (int t = t_begin; t < steps; ++t) {
         if ((t & 63) == 0) {
@@ -203,6 +222,13 @@ score_extend_wide_kernel(const StripArgs args) {
             }
         }
         lead += lead_step;
+        if constexpr (PTRS) {       // every step in every lane, so that bit positions depend on the step alone; each half drops its oldest code
+#pragma unroll
+            for (int q = 0; q < K; ++q) {
+                acc_h[q] = (acc_h[q] << 2) & 0xFFFCFFFCu;
+                if (AFFINE) acc_g[q] = (acc_g[q] << 2) & 0xFFFCFFFCu;
+            }
+        }
         if ((unsigned)j < (unsigned)F && (!BANDED || (j >= j_lo && j <= j_hi))) {
             const unsigned ca = *(lds_cu8 *)(code_addr), cb = *(lds_cu8 *)(code_addr + 1);
             s16x2 S[K];
@@ -217,7 +243,27 @@ score_extend_wide_kernel(const StripArgs args) {
                     int d_next = 0;
                     if (q + 1 < K) d_next = Hl[half][q] + (int)(half ? S[q + 1].y : S[q + 1].x);      // before Hl[q] is overwritten
                     int m;
-                    if constexpr (AFFINE) {
+                    if constexpr (PTRS) {
+                        // the equality tests of align_extend_fill_kernel on int32 cells; a sentinel-derived candidate equals no cell
+                        const int d = d_cur[half];
+                        unsigned code;
+                        if constexpr (AFFINE) {
+                            const int e_open = Hl[half][q] + o_read, f_open = h[half] + o_ref;
+                            const int e = max2(El[half][q] + e_read, e_open);
+                            El[half][q] = e;
+                            f[half] = max2(f[half] + e_ref, f_open);
+                            m = max2(max2(d, e), f[half]);
+                            // bit 0: the vertical state was extended, bit 1: the horizontal one -- an open wins a tie
+                            const unsigned gap = (f[half] != f_open ? 1u : 0u) | (e != e_open ? 2u : 0u);
+                            acc_g[q] |= gap << (16 * half);
+                            code = m == d ? 0u : (m == f[half] ? 1u : 2u);      // DIAG before the vertical before the horizontal state
+                        } else {
+                            const int up = h[half] + g_ref;
+                            m = max2(d, max2(Hl[half][q] + g_read, up));
+                            code = m == d ? 0u : (m == up ? 1u : 2u);           // DIAG before UP before LEFT
+                        }
+                        acc_h[q] |= code << (16 * half);
+                    } else if constexpr (AFFINE) {
                         const int e = max2(El[half][q] + e_read, Hl[half][q] + o_read);
                         El[half][q] = e;
                         f[half] = max2(f[half] + e_ref, h[half] + o_ref);
@@ -243,6 +289,24 @@ score_extend_wide_kernel(const StripArgs args) {
         if (BANDED && j > j_hi) {          // past the window: the row above the lane behind is absent from here on
             h_last[0] = h_last[1] = kLoses;
             f_last[0] = f_last[1] = kLoses;
+        }
+        if constexpr (PTRS) {
+            // a block every 8 steps from t_begin (a multiple of 64); the strip's last block is stored even when it holds fewer
+            // steps, its codes moved up to the positions of a whole block
+            const int in_block = t & (kExtendBandAlignBlockSteps - 1);
+            if (in_block == kExtendBandAlignBlockSteps - 1 || t == steps - 1) {
+                const int up = 2 * (kExtendBandAlignBlockSteps - 1 - in_block);
+                const unsigned keep = ~(((1u << up) - 1u) << 16);                // what pair A's half would push into pair B's
+                uint4 *block = reinterpret_cast<uint4 *>(stream + extend_band_align_word((t - t_begin) / kExtendBandAlignBlockSteps, 0, 0, AFFINE));
+#pragma unroll
+                for (int q = 0; q < K; q += 4)
+                    block[q / 4] = uint4{(acc_h[q] << up) & keep, (acc_h[q + 1] << up) & keep, (acc_h[q + 2] << up) & keep, (acc_h[q + 3] << up) & keep};
+                if constexpr (AFFINE) {
+#pragma unroll
+                    for (int q = 0; q < K; q += 4)
+                        block[(K + q) / 4] = uint4{(acc_g[q] << up) & keep, (acc_g[q + 1] << up) & keep, (acc_g[q + 2] << up) & keep, (acc_g[q + 3] << up) & keep};
+                }
+            }
         }
         if (has_bottom) {
             const int col = t - (G - 1);

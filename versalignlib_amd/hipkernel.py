@@ -90,6 +90,7 @@ def lib():
         L.valign_hip_set_placed_wide.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_extend_wide.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_extend_band.argtypes = [vp, ctypes.c_int]
+        L.valign_hip_set_extend_band_align.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_trace_checkpoints.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_pointer_scratch_cap_mb.argtypes = [vp, ctypes.c_longlong]
         L.valign_hip_set_host_packing.argtypes = [vp, ctypes.c_int]
@@ -133,7 +134,7 @@ EXTEND_UNREACHED = -(1 << 31)           # VALIGN_HIP_EXTEND_UNREACHED: gscore of
 EXPORTED_SYMBOLS = (
     "spawn_alignment_kernel", "set_parameters", "set_logger", "delete_alignment_kernel",
     "valign_hip_device_count", "valign_hip_shard_range", "valign_hip_engine_create", "valign_hip_engine_destroy",
-    "valign_hip_set_traceback_policy", "valign_hip_set_pointer_scratch_cap_mb", "valign_hip_set_host_packing", "valign_hip_set_half_float_cells", "valign_hip_host_register", "valign_hip_host_unregister", "valign_hip_set_band_width", "valign_hip_set_band_alignments", "valign_hip_set_band_nw", "valign_hip_set_band_placed", "valign_hip_set_placed_wide", "valign_hip_set_extend_wide", "valign_hip_set_extend_band", "valign_hip_set_trace_checkpoints", "valign_hip_set_score_width", "valign_hip_set_ragged_batching", "valign_hip_score_device", "valign_hip_align_device", "valign_hip_score_host", "valign_hip_align_host", "valign_hip_align_cigar_device", "valign_hip_align_cigar_host", "valign_hip_score_placed_device", "valign_hip_score_placed_host", "valign_hip_score_span_device", "valign_hip_score_span_host", "valign_hip_align_span_device", "valign_hip_align_span_host", "valign_hip_score_subopt_device", "valign_hip_score_subopt_host", "valign_hip_score_extend_device", "valign_hip_score_extend_host", "valign_hip_align_extend_device", "valign_hip_align_extend_host", "valign_hip_describe",
+    "valign_hip_set_traceback_policy", "valign_hip_set_pointer_scratch_cap_mb", "valign_hip_set_host_packing", "valign_hip_set_half_float_cells", "valign_hip_host_register", "valign_hip_host_unregister", "valign_hip_set_band_width", "valign_hip_set_band_alignments", "valign_hip_set_band_nw", "valign_hip_set_band_placed", "valign_hip_set_placed_wide", "valign_hip_set_extend_wide", "valign_hip_set_extend_band", "valign_hip_set_extend_band_align", "valign_hip_set_trace_checkpoints", "valign_hip_set_score_width", "valign_hip_set_ragged_batching", "valign_hip_score_device", "valign_hip_align_device", "valign_hip_score_host", "valign_hip_align_host", "valign_hip_align_cigar_device", "valign_hip_align_cigar_host", "valign_hip_score_placed_device", "valign_hip_score_placed_host", "valign_hip_score_span_device", "valign_hip_score_span_host", "valign_hip_align_span_device", "valign_hip_align_span_host", "valign_hip_score_subopt_device", "valign_hip_score_subopt_host", "valign_hip_score_extend_device", "valign_hip_score_extend_host", "valign_hip_align_extend_device", "valign_hip_align_extend_host", "valign_hip_describe",
     "valign_hip_last_error",
 )
 
@@ -279,6 +280,14 @@ class Engine:
         unreached read end has gscore EXTEND_UNREACHED; include/valign_hip.h has the definition); 0 (default): extension calls are
         refused under a band.  Not read without a band, nor by placed, spanned, suboptimal or alignment calls."""
         if lib().valign_hip_set_extend_band(self._h, int(on)) != 0:
+            raise HipKernelError(_err())
+
+    def set_extend_band_align(self, on):
+        """1: with band_width > 0 and extend_band = 1, align_extend_* calls run banded on the int32 extension sweep with back
+        pointers, whatever the read length (describe: ran_extend_align "band"; an unreached read end is never chosen;
+        include/valign_hip.h has the definition); 0 (default): extension alignments are refused under a band.  Not read without a
+        band or without extend_band, nor by any other call."""
+        if lib().valign_hip_set_extend_band_align(self._h, int(on)) != 0:
             raise HipKernelError(_err())
 
     def set_trace_checkpoints(self, on):
