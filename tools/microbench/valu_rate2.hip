@@ -5,8 +5,11 @@
 // the instruction timed; 16 independent chains per wave.  Rates are reported against the wall
 // clock (nominal 2.4 GHz) AND in s_memtime ticks (= shader cycles per the guide).
 // Build: hipcc --offload-arch=gfx950 -O3 tools/microbench/valu_rate2.hip -o /tmp/valu_rate2
+// Run:   valu_rate2 (first batch) | valu_rate2 second | valu_rate2 handover [CASE] (the lane hand-over's instructions and sequences;
+//        with CASE one case alone, so that a job can give every case a time limit of its own)
 #include <hip/hip_runtime.h>
 #include <stdio.h>
+#include <string>
 #include <vector>
 
 #define ITER 4096
@@ -21,8 +24,18 @@ enum Op {
     DOT2_I32_I16, SAD_U16, LSHL_ADD, BFE, MAX_U16,
     // second batch: the bit operations and 16-bit forms the tagged alignment kernels are made of, and a 1:1 mix
     AND_OR_B32, BFI_B32, LSHL_OR_B32, OR3_B32, XOR_B32, OR_B32, LSHLREV_B32, PK_ADD_I16, PK_ADD_I16_CLAMP,
-    PK_SUB_U16_CLAMP, PK_LSHLREV_B16, SUB_U32, MAX_I16, ADD_U16, BITOP3_B32, MIX_PKMAX_AND, MIX_PKMAX_AND_2TO1, ADD_U32_SDWA, ASHRREV_I32, BFE_I32
+    PK_SUB_U16_CLAMP, PK_LSHLREV_B16, SUB_U32, MAX_I16, ADD_U16, BITOP3_B32, MIX_PKMAX_AND, MIX_PKMAX_AND_2TO1, ADD_U32_SDWA, ASHRREV_I32, BFE_I32,
+    // third batch: what the lane hand-over of the tilted sweep's step is made of (dp_kernels.hip.h: group_prev_or / row_prev_or), alone
+    // and as the two hand-overs of a step between 130 packed maxima -- the 8 x 19 tile's ratio
+    CNDMASK_E64_SGPR, OR_B32_DPP_SHR2, MOV_DPP_SHR2, MOV_DPP_WAVE_SHR1, HANDOVER_OLD_130, HANDOVER_NEW_130, NO_HANDOVER_130
 };
+
+// wave instructions per pass of the timed loop's body: UNROLL of the op itself, or one block of a sequence case
+constexpr int kSeqOthers = 130;
+constexpr bool is_sequence(int op) { return op == HANDOVER_OLD_130 || op == HANDOVER_NEW_130 || op == NO_HANDOVER_130; }
+constexpr int instr_per_pass(int op) {
+    return op == HANDOVER_OLD_130 ? kSeqOthers + 7 : op == HANDOVER_NEW_130 ? kSeqOthers + 2 : op == NO_HANDOVER_130 ? kSeqOthers : UNROLL;
+}
 
 template <int OP>
 __global__ void __launch_bounds__(512) rate(unsigned *out, unsigned seed, long long *cycles) {
@@ -36,8 +49,31 @@ __global__ void __launch_bounds__(512) rate(unsigned *out, unsigned seed, long l
     unsigned g = seed | 0x00030003u, h = seed * 7u;
     u32x2 gw = u32x2{g, h};
     asm volatile("" : "+v"(g), "+v"(h), "+v"(gw));
+    unsigned long long lm = 0xFEFEFEFEFEFEFEFEull;            // "not the first lane of a group of 8" in an SGPR pair
+    asm volatile("" : "+s"(lm));
     long long t0 = clock64();
     for (int it = 0; it < ITER; ++it) {
+        if (is_sequence(OP)) {
+            // the two hand-overs of a step first, as the step has them, then the others; sources and destinations are chains whose
+            // last write lies eight instructions back (a DPP read needs two wait states after the write)
+            if (OP == HANDOVER_OLD_130) {
+                unsigned t, u;
+                asm volatile("v_mov_b32 %0, 0" : "=v"(t));
+                asm volatile("v_mov_b32_dpp %0, %1 wave_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(t) : "v"(r[8]));
+                asm volatile("v_cndmask_b32_e64 %0, %0, 0, %1" : "+v"(t) : "s"(lm));
+                asm volatile("v_or_b32 %0, %1, %2" : "=v"(r[9]) : "v"(t), "v"(g));
+                asm volatile("v_mov_b32 %0, 0" : "=v"(u));
+                asm volatile("v_mov_b32_dpp %0, %1 wave_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(u) : "v"(r[10]));
+                asm volatile("v_cndmask_b32_e64 %0, %1, 0, %2" : "=v"(r[11]) : "v"(u), "s"(lm));
+            }
+            if (OP == HANDOVER_NEW_130) {
+                asm volatile("v_or_b32_dpp %0, %1, %2 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(r[9]) : "v"(r[8]), "v"(g));
+                asm volatile("v_mov_b32_dpp %0, %1 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(r[11]) : "v"(r[10]));
+            }
+#pragma unroll
+            for (int j = 0; j < kSeqOthers; ++j) asm volatile("v_pk_maximum3_f16 %0, %0, %1, %2" : "+v"(r[j % UNROLL]) : "v"(g), "v"(h));
+            continue;
+        }
 #pragma unroll
         for (int i = 0; i < UNROLL; ++i) {
             if (OP == PK_MAX_I16) asm volatile("v_pk_max_i16 %0, %0, %1" : "+v"(r[i]) : "v"(g));
@@ -92,6 +128,10 @@ __global__ void __launch_bounds__(512) rate(unsigned *out, unsigned seed, long l
             if (OP == ADD_U32_SDWA) asm volatile("v_add_u32_sdwa %0, %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1" : "+v"(r[i]) : "v"(g));
             if (OP == ASHRREV_I32) asm volatile("v_ashrrev_i32 %0, 16, %0" : "+v"(r[i]));
             if (OP == BFE_I32) asm volatile("v_bfe_i32 %0, %0, 0, 16" : "+v"(r[i]));
+            if (OP == CNDMASK_E64_SGPR) asm volatile("v_cndmask_b32_e64 %0, %0, 0, %1" : "+v"(r[i]) : "s"(lm));
+            if (OP == OR_B32_DPP_SHR2) asm volatile("v_or_b32_dpp %0, %0, %1 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(r[i]) : "v"(g));
+            if (OP == MOV_DPP_SHR2) asm volatile("v_mov_b32_dpp %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(r[i]));
+            if (OP == MOV_DPP_WAVE_SHR1) asm volatile("v_mov_b32_dpp %0, %0 wave_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(r[i]));
             if (OP == MIX_PKMAX_AND) {          // half of the instructions packed maxima, half plain ANDs
                 if (i & 1) asm volatile("v_and_b32 %0, %0, %1" : "+v"(r[i]) : "v"(g));
                 else asm volatile("v_pk_max_i16 %0, %0, %1" : "+v"(r[i]) : "v"(g));
@@ -139,12 +179,15 @@ void run(const char *name) {
         for (int b = 0; b < blocks; ++b)
             for (int w = 0; w < wpb; ++w) avg += (double)h[b * 8 + w];
         avg /= (double)blocks * wpb;
-        const double instr_per_wave = (double)ITER * UNROLL;
+        const double instr_per_wave = (double)ITER * instr_per_pass(OP);
         const double wave_instr = instr_per_wave * blocks * wpb;
         const double per_simd_per_s = wave_instr / (ms * 1e-3) / 1024.0;
         // ticks per instruction per SIMD: a wave's own ticks / its instructions / waves sharing the SIMD
         printf("%-20s waves/SIMD %d: %7.3f ms  %.2f cyc/instr/SIMD at 2.4 GHz wall | %.2f by s_memtime\n", name,
                waves_per_simd, ms, 2.4e9 / per_simd_per_s, avg / instr_per_wave / waves_per_simd);
+        if (is_sequence(OP))           // a sequence case: the block of instr_per_pass instructions is the unit
+            printf("%-20s waves/SIMD %d: %.1f ticks per block of %d per SIMD by s_memtime\n", name, waves_per_simd,
+                   avg / ITER / waves_per_simd, instr_per_pass(OP));
     }
     hipFree(out);
     hipFree(cyc);
@@ -152,6 +195,13 @@ void run(const char *name) {
 
 int main(int argc, char **argv) {
 #define RUN(op) run<op>(#op)
+    if (argc > 1 && std::string(argv[1]) == "handover") {       // third batch; a second argument names one case (a run of its own)
+        const std::string only = argc > 2 ? argv[2] : "";
+#define RUN_IF(op) if (only.empty() || only == #op) run<op>(#op)
+        RUN_IF(PK_MAXIMUM3_F16); RUN_IF(CNDMASK_E64_SGPR); RUN_IF(OR_B32_DPP_SHR2); RUN_IF(MOV_DPP_SHR2); RUN_IF(MOV_DPP_WAVE_SHR1); RUN_IF(OR_B32);
+        RUN_IF(NO_HANDOVER_130); RUN_IF(HANDOVER_OLD_130); RUN_IF(HANDOVER_NEW_130);
+        return 0;
+    }
     if (argc > 1) {                                 // second batch only
         RUN(AND_OR_B32); RUN(BFI_B32); RUN(LSHL_OR_B32); RUN(OR3_B32); RUN(XOR_B32); RUN(OR_B32); RUN(LSHLREV_B32);
         RUN(PK_ADD_I16); RUN(PK_ADD_I16_CLAMP); RUN(PK_SUB_U16_CLAMP); RUN(PK_LSHLREV_B16); RUN(SUB_U32); RUN(MAX_I16);

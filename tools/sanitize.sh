@@ -78,6 +78,10 @@ echo "== base_classes.h (the byte classifier of the kernels' set-up) under Addre
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/base_classes_check.cpp" -o "$OUT/base_classes_asan"
 "$OUT/base_classes_asan"
 
+echo "== lane_map.h (lane <-> group and lane of the group, contiguous and interleaved) under AddressSanitizer + UBSan"
+g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/lane_map_check.cpp" -o "$OUT/lane_map_asan"
+"$OUT/lane_map_asan"
+
 echo "== several kernels of one plugin library through valign_host.cpp under AddressSanitizer + UBSan"
 g++ -std=c++14 $SAN -Wall -Werror -fPIC -shared -I"$R/include" "$R/tests/host_plugins_stub.cpp" -o "$OUT/libStubKernel.so"
 g++ -std=c++14 $SAN -Wall -Werror -pthread -I"$R/include" "$R/tests/host_plugins_check.cpp" "$CS/valign_host.cpp" -o "$OUT/host_plugins_asan" -ldl

@@ -30,7 +30,9 @@
 //     (The tilted int16 symmetric affine Smith-Waterman sweep keeps them in REGISTERS instead where every score is a
 //     byte: four bytes per row and pair, looked up by the one v_perm_b32 the merge takes anyway, from a stream of
 //     selector dwords -- wave_setup_tables; no profile, no slab numbers.  One tile exists for that form alone: 8 lanes x 19 rows,
-//     152 rows for reads of 129 .. 152 bases, 16 pairs per wave, its stream 16 bits per column -- cell_constants.h: tilt_tables_only.)
+//     152 rows for reads of 129 .. 152 bases, 16 pairs per wave, its stream 16 bits per column -- cell_constants.h: tilt_tables_only.
+//     Its lane groups INTERLEAVE, two to a 16-lane DPP row on alternating lanes, so that the row's boundary is the groups' and
+//     each lane hand-over of a step is one DPP instruction -- lane_map.h; every other kernel keeps contiguous groups.)
 //   * Recurrence variants (GAPS), packed instructions per register (= per two cells) incl. the
 //     profile merge: two linear gap scores 6 + maximum tracking, one shared gap score 5 +
 //     tracking, affine 10 + tracking, affine with the same open/extend for both directions 9 + tracking (Smith-Waterman:
@@ -64,6 +66,7 @@
 
 #include "base_classes.h"
 #include "cell_constants.h"
+#include "lane_map.h"
 
 namespace valign {
 
@@ -149,6 +152,18 @@ __device__ __forceinline__ unsigned group_prev_or_zero(unsigned v, unsigned lmas
 template <int G>
 __device__ __forceinline__ s16x2 group_prev_or(s16x2 v, s16x2 lead_border, unsigned lmask) {
     return as_pk(group_prev_or_zero<G>(as_u32(v), lmask) | as_u32(lead_border));
+}
+// The same two hand-overs under the INTERLEAVED lane map (lane_map.h: the S = 16 / G groups of a DPP row on alternating lanes).
+// The previous lane of the group is lane - S in the same row and the leaders are the row's first S lanes, which row_shr:S with
+// bound_ctrl zeroes: ONE v_mov_b32_dpp whatever the group size, no mask; the border form folds into ONE v_or_b32 with a DPP
+// operand as it does for contiguous groups of 16.
+template <int S>
+__device__ __forceinline__ unsigned row_prev_or_zero(unsigned v) {
+    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x110 + S /* row_shr:S */, 0xF, 0xF, true);
+}
+template <int S>
+__device__ __forceinline__ s16x2 row_prev_or(s16x2 v, s16x2 lead_border) {
+    return as_pk(row_prev_or_zero<S>(as_u32(v)) | as_u32(lead_border));
 }
 // max(a, b) and max(a, b, c) of int16 values whose bit patterns all lie in [0x0400, 0x7BFF], the positive normal half floats:
 // there the half-float order is the integer order and a maximum returns one of its operands bit for bit, so gfx950's
@@ -615,7 +630,8 @@ __device__ __forceinline__ bool wave_setup_tables(const uint8_t *reads, const ui
 #pragma unroll
         for (int c = 0; c < 4; ++c) table(c, t_lo[c], t_hi[c]);
         const unsigned char *raw_rd = sel + (int)((unsigned long long)(reads + pair0 * R) & 15ull);
-        const int grp = lane / G, l = lane % G;
+        using lmap = LaneMap<G, score_lane_stride(G, K)>;               // (the rows a lane loads follow its place in the group)
+        const int grp = lmap::kInterleaved ? lmap::grp(lane) : lane / G, l = lmap::kInterleaved ? lmap::l(lane) : lane % G;   // (score_kernel says why both)
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             int p = 2 * grp + half;
@@ -824,8 +840,14 @@ score_kernel(const ScoreArgs args) {
     constexpr bool AFFSYM = GAPS == kGapAffineSym;
     constexpr bool SOURCES = AFFSYM && ALG == kAlgSW;      // int16 symmetric affine SW carries gap sources (see the step)
     const int lane = threadIdx.x & (kWave - 1);
-    const int grp = lane / G;
-    const int l = lane % G;
+    // lane -> (group, lane of the group): contiguous, but for the 8 x 19 tile, whose two groups of a DPP row interleave (lane_map.h)
+    using lmap = LaneMap<G, score_lane_stride(G, K)>;
+    // (The contiguous map stays written out here: taken through the map's functions the same arithmetic reaches the compiler in
+    // another order, and every contiguous instance -- 168 score kernels -- comes out an instruction or two different from the
+    // code it has had.  The static_assert ties the two; tests/lane_map_check.cpp checks the map lane by lane.)
+    static_assert(lmap::kInterleaved || (lmap::grp(kWave - 3) == (kWave - 3) / G && lmap::l(kWave - 3) == (kWave - 3) % G), "the contiguous map is lane / G, lane % G");
+    const int grp = lmap::kInterleaved ? lmap::grp(lane) : lane / G;
+    const int l = lmap::kInterleaved ? lmap::l(lane) : lane % G;
 
     // the batch (or, in a length-sorted launch, the group this block belongs to): wave-uniform
     const uint8_t *reads = args.reads, *refs = args.refs;
@@ -1424,7 +1446,8 @@ score_kernel(const ScoreArgs args) {
                     };
                     s16x2 S[K], d[K];
                     const s16x2 diag0 = up0;
-                    up0 = group_prev_or<G>(HOl[K - 1], lead_border, lmask);
+                    if constexpr (lmap::kInterleaved) up0 = row_prev_or<lmap::kStride>(HOl[K - 1], lead_border);
+                    else up0 = group_prev_or<G>(HOl[K - 1], lead_border, lmask);
                     lead_border = add2(lead_border, lead_step);
                     if constexpr (FORM == kLdsProfile) {
                         merge_profile<K>(pa, pb, S);
@@ -1462,7 +1485,9 @@ score_kernel(const ScoreArgs args) {
                     s16x2 ho = up0;
                     pass1(0, e_cur);
                     // F of the lane above, the shift's zero in the group's first lane (fetched behind the first row's pass 1)
-                    s16x2 f = as_pk(group_prev_or_zero<G>(as_u32(f_last), lmask)), h = pk(0);
+                    s16x2 f = pk(0), h = pk(0);
+                    if constexpr (lmap::kInterleaved) f = as_pk(row_prev_or_zero<lmap::kStride>(as_u32(f_last)));
+                    else f = as_pk(group_prev_or_zero<G>(as_u32(f_last), lmask));
 #pragma unroll
                     for (int q = 0; q < K; ++q) {
                         f = pk_max_h(f, ho);
@@ -1634,8 +1659,8 @@ score_kernel(const ScoreArgs args) {
         res = pk_max(col, pk(0));
     }
 #pragma unroll
-    for (int d = G / 2; d >= 1; d >>= 1)
-        res = pk_max(res, as_pk((unsigned)__shfl_xor((int)as_u32(res), d, kWave)));
+    for (int i = 0; i < lmap::kReduceSteps; ++i)             // over the lanes of the group: G / 2 ... 1 lanes apart, times the map's stride
+        res = pk_max(res, as_pk((unsigned)__shfl_xor((int)as_u32(res), lmap::reduce_distance(i), kWave)));
     if (l == 0) {
         const long long pa = pair0 + 2 * grp;
         if (pa + 1 < n_pairs && ((unsigned long long)scores & 3ull) == 0) {
