@@ -727,8 +727,9 @@ int valign_hip_set_extend_band(valign_hip_engine *e, int on);
  * with affine gaps) under pointer_scratch_cap_mb and the walk's rows under the compact format's rows scratch; the chunks reuse both
  * in stream order, and both are shared with the other alignment calls: calls of one engine belong on one stream.
  * "ran_extend_align" of valign_hip_describe is "rows" after a call that ran ("none" before any, or when it was refused),
- * "ran_extend_align_geometry" the geometry whose fill ran, "extend_align_scratch_bytes" the pointer scratch, end cells and staged
- * extension records the engine holds.  tests/extend_align_ref.py restates the definition in numpy.                            */
+ * "ran_extend_align_geometry" the geometry whose fill ran, "align_ptr_bytes_per_pair" the pointer-stream bytes a pair holds in that
+ * fill (after a call that ran), "extend_align_scratch_bytes" the pointer scratch, end cells and staged extension records the engine
+ * holds.  tests/extend_align_ref.py restates the definition in numpy.                                                          */
 int valign_hip_align_extend_device(valign_hip_engine *e, int opt, long long n, const void *d_reads, const void *d_refs,
                                    int end_bonus, int extended, void *d_recs, void *d_ops, int ops_stride,
                                    void *d_extend /* may be null */, void *hip_stream);

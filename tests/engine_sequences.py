@@ -19,6 +19,15 @@ CIGARs, extension scores and extension alignments.  The last three came with the
 spanned CIGARs re-key ONE child engine, each with its own set of keys; extension alignments walk in the rows scratch of the
 CIGAR calls at another row pitch; extension scores under extend_wide sweep on the boundary rows of the placed int32 sweep.
 
+The two newest keys, extend_band and extend_band_align, move the two extension families to the BANDED int32 strip sweep under
+band_width > 0 (extension_route() restates the rule of include/valign_hip.h).  That route lies on more shared, grow-only state
+than any before it: its boundary rows and partial records are the strip scratch of the placed int32 sweep, of extend_wide and of
+the placed strip route -- three record layouts --, its pointer regions and end cells the pointer scratch of every alignment fill,
+its walk the CIGAR rows scratch at a pitch of R + F + 1.  The references there are tests/extend_band_ref.py and
+tests/extend_band_align_ref.py, and expected() asserts that the route describe() reports is the one the rule names before it
+picks a reference.  A fourth world, strips (520 x 600), exists for the hand-written sequences only: the smallest shape at which a
+read crosses a 512-row strip boundary and still reaches its end inside the band.
+
 describe() is host-side state -- with one exception: after a score call whose last launch ran on the 8 x 19 side tile it reports
 "ran_score_sym_affine_form" from two words the kernels wrote, and waits for the DEVICE to read them (Engine::ran_side_tile_form).
 The short world's 150-row reads under sym_affine are that tile's window: a length-sorted score call with half_float_cells = 0
@@ -35,11 +44,11 @@ from versalignlib_amd import synth
 SW, NW = 0, 1
 
 # ---- the model of the state -------------------------------------------------------------------------------------------------
-KEYS = ("band_width", "band_alignments", "band_nw", "band_placed", "placed_wide", "extend_wide", "trace_checkpoints", "score_width",
-        "traceback_policy", "ragged_batching", "host_packing", "half_float_cells", "pointer_scratch_cap_mb")
-DEFAULTS = {"band_width": 0, "band_alignments": 0, "band_nw": 0, "band_placed": 0, "placed_wide": 0, "extend_wide": 0,
-            "trace_checkpoints": 0, "score_width": 0, "traceback_policy": 0, "ragged_batching": 0, "host_packing": 1, "half_float_cells": 1,
-            "pointer_scratch_cap_mb": 0}
+KEYS = ("band_width", "band_alignments", "band_nw", "band_placed", "placed_wide", "extend_wide", "extend_band", "extend_band_align",
+        "trace_checkpoints", "score_width", "traceback_policy", "ragged_batching", "host_packing", "half_float_cells", "pointer_scratch_cap_mb")
+DEFAULTS = {"band_width": 0, "band_alignments": 0, "band_nw": 0, "band_placed": 0, "placed_wide": 0, "extend_wide": 0, "extend_band": 0,
+            "extend_band_align": 0, "trace_checkpoints": 0, "score_width": 0, "traceback_policy": 0, "ragged_batching": 0, "host_packing": 1,
+            "half_float_cells": 1, "pointer_scratch_cap_mb": 0}
 # pointer_scratch_cap_mb can only be SET: 0 means "leave the cap as it is" to the library, so the state never returns to 0
 SET_ONLY_POSITIVE = ("pointer_scratch_cap_mb",)
 
@@ -54,8 +63,8 @@ FAMILY_OF = {e: f for f in FAMILIES for e in ENTRIES_OF[f]}
 
 LADDER = (1, 7, 40, 130)            # batch sizes: scratch buffers are reused, regrown and reused smaller
 POOL = 160                          # pairs of a world; a call takes a slice of them
-CALLS = 62                          # calls drawn per sequence (the repairs at the end add some twenty): at 60 the tiny world's seeds
-                                    # still missed one of the 72 ordered pairs of families as neighbours
+CALLS = 64                          # calls drawn per sequence (the repairs at the end add some forty): with fifteen keys the tiny
+                                    # world's seeds still missed one of the 72 ordered pairs of families as neighbours at 62
 SUBOPT_CALLS = 6                    # ... of which suboptimal ones, and of every family capped_families() names: each of their calls is refused
                                     # by definition under some scoring of the world, and would eat the budget of refusals
 END_BONUSES = (-1, 0, 5, 2 ** 31 - 1)       # extension alignments: the best cell, the rule in between (twice), always the read end
@@ -63,11 +72,19 @@ END_BONUSES = (-1, 0, 5, 2 ** 31 - 1)       # extension alignments: the best cel
 # The smallest shapes at which each route still exists.  short: the register sweep, the fused / direct small host calls, the
 # ragged classes, the block chain under a band.  long: plan_ is the long plan by construction, alignments take the row strips
 # on four 512-row strips, placed scores the strip route.  tiny: fewer rows than any geometry has.
+# Under the band of the extension families (the anchor's diagonal i = j) the long world's band ends near row 130 of its 1600: 159 /
+# 158 of its 160 pairs have an UNREACHED read end at bands 24 / 64.  It covers the unreached rule, the four strips with empty
+# windows behind the first and the sizes of the strip scratch -- and nothing else of the banded walk.  strips is the smallest shape
+# at which a read crosses a 512-row strip boundary AND reaches its end inside the band (F > R: the reference outlasts the read): 142 /
+# 144 reached read ends, 74 and more best cells below row 512.  It has no seeds -- no generated sequences -- and is used by the
+# hand-written sequences only: its references take seconds on the CPU for the whole pool, and are computed lazily like all others.
 WORLDS = {
     "short": {"R": 150, "F": 200, "bands": (16, 40), "scorings": ("linear", "sym_affine", "affine4", "wide"), "seeds": (1, 2, 3)},
     "long": {"R": 1600, "F": 96, "bands": (24, 64), "scorings": ("linear", "sym_affine", "affine4"), "seeds": (1, 2, 3)},
     "tiny": {"R": 12, "F": 20, "bands": (4, 12), "scorings": ("linear", "sym_affine", "affine4"), "seeds": (1, 2, 3)},
+    "strips": {"R": 520, "F": 600, "bands": (40, 130), "scorings": ("linear", "sym_affine", "affine4"), "seeds": ()},
 }
+_STREAM_OF = {"long": 1, "short": 2, "tiny": 3, "strips": 4}       # the generator's stream per world: a new world moves no other's
 # match, mismatch, gap_read, gap_ref [, open_read, ext_read, open_ref, ext_ref]; wide: cells leave int16 at 150 x 200
 SCORINGS = {"linear": (2, -1, -3, -3), "sym_affine": (2, -1, -3, -3, -5, -1, -5, -1), "affine4": (2, -1, -3, -3, -6, -1, -4, -2),
             "wide": (600, -1, -3, -3)}
@@ -75,17 +92,30 @@ SCORINGS = {"linear": (2, -1, -3, -3), "sym_affine": (2, -1, -3, -3, -5, -1, -5,
 # 1 024 rows take the row strips, and a shape x scoring whose cells can leave int16 is refused whatever placed_wide says
 NEVER_SUCCEEDS = {("long", s): ENTRIES_OF["subopt"] for s in WORLDS["long"]["scorings"]}
 NEVER_SUCCEEDS[("short", "wide")] = ENTRIES_OF["subopt"]
-# "REFUSED" of the extension alignments: "everything valign_hip_score_extend_device refuses with extend_wide = 0 ... under
-# extend_wide = 1, any call whose extension route is "wide"" -- and of the extension scores: "the shapes placed scores send to the
-# row strips (reads of more than 1024 rows, or no register geometry)": every scoring of the long world, whatever extend_wide says
-for _key in [("long", s) for s in WORLDS["long"]["scorings"]]:
-    NEVER_SUCCEEDS[_key] += ENTRIES_OF["extend_align"]
-# ... and of the extension scores: "a shape x scoring whose cells could leave int16 -- signed cells: min(R, F) * max(match,
-# mismatch, 0) above 32000": 150 x 600; extend_wide = 1 moves the scores to the int32 sweep, which the alignments refuse
-NEVER_SUCCEEDS[("short", "wide")] += ENTRIES_OF["extend_align"]
-# (Nothing else: extension scores run under extend_wide = 1 wherever the register sweep refuses them here -- 96 x 2 and 150 x
-# 600 are far below 2^28 --, and spanned CIGARs are refused where spanned scores are, "and whatever the alignment route of the
-# window's shape refuses": an unbanded Smith-Waterman alignment under traceback_policy = 0 picks its own cells and refuses nothing.)
+# (Nothing else.  Extension scores run under extend_wide = 1 wherever the register sweep refuses them here -- 96 x 2 and 150 x
+# 600 are far below 2^28.  Extension alignments are refused on the register route for every scoring of the long world ("reads of
+# more than 1024 rows") and for 150 x 600 ("cells could leave int16"), whatever extend_wide says -- but under band_width > 0 with
+# extend_band = extend_band_align = 1 they run BANDED "whatever the read length, score_width (0 or 32) or extend_wide say", so
+# every (world, scoring) has a state in which they succeed.  Spanned CIGARs are refused where spanned scores are, "and whatever
+# the alignment route of the window's shape refuses": an unbanded Smith-Waterman alignment under traceback_policy = 0 picks its
+# own cells and refuses nothing.)
+
+
+def extension_route(state, family):
+    """The route include/valign_hip.h gives a call of an extension family ("extend": the scores, "extend_align": the alignments)
+    in this state, as far as the two band keys decide it -- a pure function of the state:
+      "band" ...... the banded int32 strip sweep: the scores iff band_width > 0 and extend_band == 1, the alignments iff, in
+                    addition, extend_band_align == 1.  (The route still refuses score_width = 16, traceback_policy = 1 and the NW
+                    mode bit, with texts of its own: a refused call has run on no route.)
+      "unbanded" .. band_width == 0: neither key is read; the register sweep, the int32 sweep of extend_wide, or their refusals.
+      "refused" ... band_width > 0 and the family's keys are not all on: every call is refused for the band."""
+    if family not in ("extend", "extend_align"):
+        raise ValueError(family)
+    if state["band_width"] == 0:
+        return "unbanded"
+    if state["extend_band"] == 1 and (family == "extend" or state["extend_band_align"] == 1):
+        return "band"
+    return "refused"
 
 
 def capped_families(world):
@@ -152,7 +182,7 @@ def _pairs(world):
 # ---- the generator ----------------------------------------------------------------------------------------------------------
 class _Draw:
     def __init__(self, world, seed):
-        self.r = synth._stream(7000 + int(seed), 1 + sorted(WORLDS).index(world), (8192,))
+        self.r = synth._stream(7000 + int(seed), _STREAM_OF[world], (8192,))
         self.k = 0
 
     def pick(self, lo, hi):
@@ -168,23 +198,35 @@ def _blockers(world, state, family, alg):
     """What, by the header's refusal rules, stands between this state and a call of the family -- a list of alternative
     single-key remedies for the first reason found, [] when nothing does or nothing helps.  Only steers the generator (so that
     sequences are not mostly refusals); the tests never read it.  The short world is judged as if its scoring were the wide one.
-    Spanned CIGARs are steered as spanned scores are: the window's alignment refuses nothing of its own here."""
+    Spanned CIGARs are steered as spanned scores are: the window's alignment refuses nothing of its own here.  The two extension
+    families are steered by extension_route(): under a band towards their keys or away from the band, and from band_width = 0
+    towards a band of the world wherever only the Band route can run the call (the long world, the wide scoring)."""
     band, wide_scoring = state["band_width"], world == "short"
     if family in ("placed", "span", "subopt", "span_cigar", "extend", "extend_align") and alg == NW:
         return []
-    if family in ("extend", "extend_align"):           # no band whatever band_placed says; placed_wide is not read
+    if family in ("extend", "extend_align"):           # band_placed and placed_wide are not read
+        bands = [("band_width", b) for b in WORLDS[world]["bands"]]
         if state["traceback_policy"]:
             return [("traceback_policy", 0)]
-        if band > 0:
-            return [("band_width", 0)]
-        if family == "extend_align":                    # refused wherever the extension route would be wide: nothing helps there
-            return [("score_width", 0)] if state["score_width"] == 32 else []
+        route = extension_route(state, family)
+        if route == "band":                             # whatever the read length, score_width 0 / 32 and extend_wide say
+            return [("score_width", 0)] if state["score_width"] == 16 else []
+        if route == "refused":                          # under a band: the family's keys, one at a time, or no band
+            if not state["extend_band"]:
+                return [("extend_band", 1), ("band_width", 0)]
+            return [("extend_band_align", 1), ("band_width", 0)]
+        if family == "extend_align":                    # no band: refused wherever the extension route would be wide -- the band route is what helps
+            if world == "long":
+                return bands
+            if state["score_width"] == 32:
+                return [("score_width", 0)] + bands
+            return []                                   # (the register route serves every scoring but the wide one)
         if state["score_width"] == 32 and not state["extend_wide"]:
             return [("extend_wide", 1), ("score_width", 0)]
         if wide_scoring and state["score_width"] == 16:
             return [("score_width", 0)]
         if (wide_scoring or world == "long") and not state["extend_wide"]:
-            return [("extend_wide", 1)]
+            return [("extend_wide", 1)] + bands[:1]
         return []
     if family == "score":
         if band > 0 and alg == NW and not state["band_nw"]:
@@ -226,6 +268,8 @@ def sequence(world, seed):
     state = initial_state()
     history = {k: [state[k]] for k in KEYS}
     steps, seen, count, likely = [], set(), {e: 0 for e in ENTRY_POINTS}, {e: 0 for e in ENTRY_POINTS}
+    likely_band = {e: 0 for f in ("extend", "extend_align") for e in ENTRIES_OF[f]}        # ... of which on the Band route
+    likely_unbanded = dict(likely_band)                                                     # ... and without a band
     made = []                           # (family, the state it was made in, the step) of every call so far
     capped = capped_families(world)
     last_family = None
@@ -239,15 +283,17 @@ def sequence(world, seed):
         history[key].append(value)
         steps.append(step)
 
-    def call(family, alg=None, entry=None, remedy=False, **fixed):
+    def call(family, alg=None, entry=None, remedy=False, as_it_is=False, **fixed):
         nonlocal last_family
         a, b = ENTRIES_OF[family]
         if entry is None:
             entry = a if count[a] < count[b] else b if count[b] < count[a] else d.choice((a, b))
         if alg is None:
             alg = d.choice((SW, NW)) if family in ("score", "rows", "cigar") else (NW if d.pick(0, 11) == 0 else SW)
-        if _blockers(world, state, family, alg) and (remedy or d.pick(0, 7)):
-            for _ in range(4):                  # seven times in eight: remedy reason after reason, then call
+        if not as_it_is and _blockers(world, state, family, alg) and (remedy or d.pick(0, 7)):
+            # seven times in eight: remedy reason after reason, then call.  Five reasons at the most: traceback_policy, the band,
+            # extend_band, extend_band_align, score_width
+            for _ in range(5):
                 fixes = _blockers(world, state, family, alg)
                 if not fixes:
                     break
@@ -256,6 +302,10 @@ def sequence(world, seed):
         if not _blockers(world, state, family, alg) and (family == "score" or alg == SW) and \
                 (family not in ("rows", "cigar") or not state["traceback_policy"]):
             likely[entry] += 1
+            if entry in likely_band and extension_route(state, family) == "band":
+                likely_band[entry] += 1
+            if entry in likely_band and extension_route(state, family) == "unbanded":
+                likely_unbanded[entry] += 1
         n = d.choice(LADDER)
         step = {"kind": "call", "entry": entry, "alg": alg, "begin": d.pick(0, POOL - n), "n": n, "threads": d.pick(1, 3),
                 "mask": d.choice((0, 3, w["R"] // 2, w["F"])), "extended": d.pick(0, 1), "end_bonus": d.choice(END_BONUSES),
@@ -310,6 +360,84 @@ def sequence(world, seed):
         change("extend_wide", 1)
         call("placed", alg=SW, remedy=True)
         call("extend", alg=SW, remedy=True)
+    # ... the state the Band route of the two extension families shares (module docstring); every call below is made as_it_is, in
+    # a state set up so that the model expects it to run
+    bands = w["bands"]
+
+    def on_band(width):
+        """the keys under which both extension families run BANDED, under the band `width`"""
+        change("traceback_policy", 0)
+        if state["score_width"] == 16:
+            change("score_width", 0)
+        change("extend_band", 1)
+        change("extend_band_align", 1)
+        change("band_width", width)
+
+    # the strip scratch under three layouts: the placed int32 sweep, banded extension scores, banded extension alignments --
+    # pairwise neighbours in both orders
+    if not STRIP_SCRATCH_ORDERS <= strip_scratch_neighbours(made):
+        band = state["band_width"] or bands[0]
+        change("placed_wide", 1)
+        change("score_width", 32)
+        for family in ("placed", "extend", "extend_align", "placed", "extend_align", "extend", "placed"):
+            on_band(0 if family == "placed" else band)
+            call(family, alg=SW, as_it_is=True)
+    # the pointer scratch and the rows scratch at two pitches: unbanded CIGARs around a banded extension alignment
+    if not pointer_scratch_order(made):
+        on_band(state["band_width"] or bands[1])
+        change("band_alignments", 0)
+        for family in ("cigar", "extend_align", "cigar"):
+            call(family, alg=SW, as_it_is=True)
+    # the pointer layout of the band at two w: one band, the other, the first again
+    if not two_bands_order(made):
+        for width in (bands[0], bands[1], bands[0]):
+            on_band(width)
+            call("extend_align", alg=SW, as_it_is=True)
+    # a banded extension call directly before and after band_width goes to 0 and comes back: the register route in between (tiny)
+    # or the routes extend_wide opens
+    if not band_cleared_order(made):
+        band = state["band_width"] or bands[1]
+        on_band(band)
+        call("extend", alg=SW, as_it_is=True)
+        change("band_width", 0)
+        if world == "tiny":
+            change("score_width", 0)
+            call("extend_align", alg=SW, as_it_is=True)
+        else:
+            change("extend_wide", 1)
+            call("extend", alg=SW, as_it_is=True)
+        on_band(band)
+        call("extend_align", alg=SW, as_it_is=True)
+    # every value of end_bonus and with_extend ON the Band route, every extension entry point there twice by the model, and both
+    # families under a band with their keys off (refused: the text and the describe() of a new engine)
+    for field, values in (("end_bonus", END_BONUSES), ("with_extend", (0, 1))):
+        for value in values:
+            if not any(f == "extend_align" and runs_banded(f, s, step) and step[field] == value for f, s, step in made):
+                on_band(state["band_width"] or bands[0])
+                call("extend_align", alg=SW, as_it_is=True, **{field: value})
+    for entry in likely_band:
+        while likely_band[entry] < 2:
+            on_band(state["band_width"] or bands[1])
+            call(FAMILY_OF[entry], alg=SW, entry=entry, as_it_is=True)
+    # ... the routes without a band keep their share: every extension entry point twice by the model where a route without a band
+    # can serve it (the scores everywhere, under extend_wide where need be; the alignments on the register route -- not in the long
+    # world, where only the Band route runs them)
+    for entry in likely_unbanded:
+        family = FAMILY_OF[entry]
+        while likely_unbanded[entry] < 2 and (family == "extend" or world != "long"):
+            change("band_width", 0)
+            change("traceback_policy", 0)
+            if family == "extend_align" or state["score_width"] == 16:
+                change("score_width", 0)
+            if family == "extend":
+                change("extend_wide", 1)
+            call(family, alg=SW, entry=entry, as_it_is=True)
+    off = {f for f, s, _ in made if f in ("extend", "extend_align") and extension_route(s, f) == "refused"}
+    for family in ("extend", "extend_align"):
+        if family not in off:
+            change("band_width", state["band_width"] or bands[0])
+            change("extend_band", 0)
+            call(family, alg=SW, as_it_is=True)
     # ... and, always, a band that is set, used, cleared and followed by a call of every family that reads the plan
     change("band_width", w["bands"][0])
     call("score", alg=SW)
@@ -327,6 +455,58 @@ def wide_sweeps_are_neighbours(made):
     return any(wide(fa, sa) and wide(fb, sb) and fa != fb for (fa, sa, _), (fb, sb, _) in zip(made, made[1:]))
 
 
+def runs_banded(family, state, step):
+    """The model's statement that this call runs on the Band route of its extension family: the route is "band" and nothing of what
+    that route refuses stands in the way."""
+    return (family in ("extend", "extend_align") and step["alg"] == SW and extension_route(state, family) == "band"
+            and state["traceback_policy"] == 0 and state["score_width"] != 16)
+
+
+def placed_on_int32(family, state, step):
+    """a placed call that takes the int32 sweep whatever the world and the scoring: no band, score_width = 32 under placed_wide = 1"""
+    return (family == "placed" and step["alg"] == SW and state["band_width"] == 0 and state["placed_wide"] == 1
+            and state["score_width"] == 32 and state["traceback_policy"] == 0)
+
+
+STRIP_SCRATCH_ORDERS = frozenset((a, b) for a in ("placed", "extend", "extend_align") for b in ("placed", "extend", "extend_align") if a != b)
+
+
+def strip_scratch_neighbours(made):
+    """made: (family, state, step) per call, in order -> the ordered pairs of ("placed", "extend", "extend_align") that follow one
+    another as a placed call on its int32 sweep, a banded extension score and a banded extension alignment: the strip scratch
+    (Engine::d_placed_rows_ / d_placed_ends_) under its three record layouts."""
+    def kind(family, state, step):
+        if placed_on_int32(family, state, step):
+            return "placed"
+        return family if runs_banded(family, state, step) else None
+    kinds = [kind(*m) for m in made]
+    return {(a, b) for a, b in zip(kinds, kinds[1:]) if a and b and a != b}
+
+
+def _triples(made):
+    return zip(made, made[1:], made[2:])
+
+
+def pointer_scratch_order(made):
+    """True where an unbanded CIGAR call, a banded extension alignment and an unbanded CIGAR call follow one another: the pointer
+    scratch of every alignment fill, and the CIGAR rows scratch at the pitches R + F and R + F + 1."""
+    def unbanded_cigar(family, state, step):
+        return family == "cigar" and (state["band_width"] == 0 or state["band_alignments"] == 0)
+    return any(unbanded_cigar(*a) and b[0] == "extend_align" and runs_banded(*b) and unbanded_cigar(*c) for a, b, c in _triples(made))
+
+
+def two_bands_order(made):
+    """True where three banded extension alignments follow one another under one band, another, and the first again."""
+    return any(all(m[0] == "extend_align" and runs_banded(*m) for m in (a, b, c)) and a[1]["band_width"] == c[1]["band_width"] != b[1]["band_width"]
+               for a, b, c in _triples(made))
+
+
+def band_cleared_order(made):
+    """True where a banded extension call, an extension call under band_width = 0 and a banded extension call follow one another."""
+    return any(runs_banded(*a) and b[0] in ("extend", "extend_align") and b[2]["alg"] == SW and b[1]["band_width"] == 0 and runs_banded(*c)
+               for a, b, c in _triples(made))
+
+
 def calls_with_state(steps):
     """-> (family, the state the call is made in, the step) of every call of `steps`, in order"""
     out, state = [], initial_state()
@@ -338,8 +518,10 @@ def calls_with_state(steps):
 
 
 # ---- the runner -------------------------------------------------------------------------------------------------------------
-ECHOED = ("band_width", "ragged_batching", "band_alignments", "band_nw", "band_placed", "placed_wide", "extend_wide", "trace_checkpoints")
-PLAN_KEYS = ("long_mode", "group_lanes", "rows_per_lane", "score_cells", "band_block_rows", "band_col_align", "span_ref_length")
+ECHOED = ("band_width", "ragged_batching", "band_alignments", "band_nw", "band_placed", "placed_wide", "extend_wide", "extend_band",
+          "extend_band_align", "trace_checkpoints")
+PLAN_KEYS = ("long_mode", "group_lanes", "rows_per_lane", "score_cells", "band_block_rows", "band_col_align", "span_ref_length",
+             "extend_band_block_rows")
 RAN_KEYS = {"score": ("ran_score_cells", "ran_score_geometry", "ran_score_sym_affine"),
             "rows": ("ran_align_fill", "ran_align_geometry", "ran_result_format"),
             "cigar": ("ran_align_fill", "ran_align_geometry", "ran_result_format"),
@@ -358,9 +540,13 @@ def compared(entry, desc, refused=False):
     """The describe() keys a live engine and a new one must agree on right after a call of `entry` (a key the library leaves
     out -- ran_score_sym_affine -- reads None).  Scratch sizes and the last-launch figures of other kinds of call are not here:
     direct_call, packed_classes and ragged_launches are figures of the last host-pointer / score call that LAUNCHED, so after a
-    refused call they are an earlier call's and are left out."""
+    refused call they are an earlier call's and are left out.  After an extension alignment that ran, align_ptr_bytes_per_pair is
+    the call's own -- on the Band route a function of state and shape alone -- and is compared.  ran_extend_align_chunks is NOT:
+    the chunk size reads hipMemGetInfo, and a live engine that holds scratch sees other free memory than a new one."""
     family = FAMILY_OF[entry]
     out = {k: desc.get(k) for k in PLAN_KEYS + ECHOED + RAN_KEYS[family]}
+    if family == "extend_align" and not refused:
+        out["align_ptr_bytes_per_pair"] = desc["align_ptr_bytes_per_pair"]
     if entry.endswith("_host") and not refused:
         out["direct_call"] = desc["direct_call"]
         out["packed_classes"] = desc["packed_classes"]
@@ -375,13 +561,13 @@ def _freeze(step):
 
 class Runner:
     """One (world, scoring): the pairs on the device, the references (computed once per operation and parameter set, for the
-    whole pool, and sliced), and run(seed_or_steps)."""
+    whole pool, and sliced), and run(seed_or_steps).  device=False: the part that only compares -- the references, expected() and
+    verify() -- without torch and without a GPU (tests/test_engine_sequences.py holds verify() to two mutants there)."""
 
-    def __init__(self, world, scoring):
-        import torch
+    def __init__(self, world, scoring, device=True):
         from oracle import cpu_ref
         from versalignlib_amd import hipkernel
-        self.torch, self.cpu_ref, self.hk = torch, cpu_ref, hipkernel
+        self.torch, self.cpu_ref, self.hk = None, cpu_ref, hipkernel
         self.world, self.scoring = world, scoring
         w = WORLDS[world]
         self.R, self.F = w["R"], w["F"]
@@ -390,8 +576,11 @@ class Runner:
         self.osc = cpu_ref.Scoring.make(*self.args)
         self.hsc = hipkernel.Scoring.make(*self.args)
         self.reads, self.refs = pairs(world)
-        self.d_reads = torch.from_numpy(np.array(self.reads)).cuda()
-        self.d_refs = torch.from_numpy(np.array(self.refs)).cuda()
+        if device:
+            import torch
+            self.torch = torch
+            self.d_reads = torch.from_numpy(np.array(self.reads)).cuda()
+            self.d_refs = torch.from_numpy(np.array(self.refs)).cuda()
         self.stride = self.R + self.F           # ops per pair of the device-resident CIGAR calls: no alignment has more
         self._refs = {}
 
@@ -456,6 +645,18 @@ class Runner:
         import extend_align_ref
         return self._ref(("extend_align", extended), lambda: dict(zip(END_BONUSES, extend_align_ref.align(
             self.reads, self.refs, self.hsc, self.affine, end_bonus=END_BONUSES, extended=bool(extended)))))
+
+    def ref_extend_band(self, band):
+        """the Band route's records: the cells outside the band on the anchor's diagonal are absent, an unreached read end is
+        VALIGN_HIP_EXTEND_UNREACHED"""
+        import extend_band_ref
+        return self._ref(("extend_band", band), lambda: extend_band_ref.extend(self.reads, self.refs, self.hsc, band, self.affine))
+
+    def ref_extend_band_align(self, band, extended):
+        """-> {end_bonus: (recs, ops, extension records, end cells, paths)}: every bonus from ONE fill per (band, extended)"""
+        import extend_band_align_ref
+        return self._ref(("extend_band_align", band, extended), lambda: dict(zip(END_BONUSES, extend_band_align_ref.align(
+            self.reads, self.refs, self.hsc, band, self.affine, end_bonus=END_BONUSES, extended=bool(extended)))))
 
     def ref_subopt(self, mask):
         import subopt_ref
@@ -589,11 +790,21 @@ class Runner:
         if family == "span_cigar":
             exp = self.ref_span_cigar(step["extended"])
             return exp["recs"][b:e], exp["ops"][b:e], None
-        if family == "extend":
-            return (self.ref_extend()[b:e],)
-        if family == "extend_align":
-            recs, ops, _, _ = self.ref_extend_align(step["extended"])[step["end_bonus"]]
-            return recs[b:e], ops[b:e], self.ref_extend()[b:e] if step["with_extend"] else None      # (the score call's record, bit for bit)
+        if family in ("extend", "extend_align"):
+            # the route that ran must be the one the rule names, before any reference is picked: a call that quietly took another
+            # route is not judged against that route's reference
+            ran = "ran_extend" if family == "extend" else "ran_extend_align"
+            route = extension_route(state, family)
+            if route == "refused" or (desc[ran] == "band") != (route == "band") or (route == "band" and desc[ran + "_geometry"] != "none"):
+                raise SequenceMismatch(("the extension route", route, "by include/valign_hip.h, but describe() says", ran, desc[ran],
+                                        ran + "_geometry", desc[ran + "_geometry"], "state", state))
+            banded = route == "band"
+            # (the extension records of an alignment call are the SCORE call's, bit for bit -- UNREACHED included under a band)
+            scores = self.ref_extend_band(band) if banded else self.ref_extend()
+            if family == "extend":
+                return (scores[b:e],)
+            res = (self.ref_extend_band_align(band, step["extended"]) if banded else self.ref_extend_align(step["extended"]))[step["end_bonus"]]
+            return res[0][b:e], res[1][b:e], scores[b:e] if step["with_extend"] else None
         return (self.ref_subopt(step["mask"])[b:e],)
 
     def verify(self, step, got, exp, where):
@@ -673,7 +884,9 @@ class Runner:
     # -- the whole sequence on one engine --
     def run(self, seed=None, steps=None, log=None):
         """Run sequence(world, seed) -- or `steps` -- on ONE engine.  Raises SequenceMismatch (an AssertionError) that names world,
-        scoring, seed and step index.  -> {"calls", "refused", "succeeded": {entry: count}}."""
+        scoring, seed and step index.  -> {"calls", "refused", "succeeded": {entry: count}, "routes": {extension entry: {what
+        ran_extend / ran_extend_align said after a call that ran: count}}, "chunks": {step index of an extension alignment that
+        ran: the live engine's ran_extend_align_chunks}}."""
         torch = self.torch
         steps = sequence(self.world, seed) if steps is None else steps
         tag = (self.world, self.scoring, "seed", seed)
@@ -691,7 +904,8 @@ class Runner:
         #    read late, it costs a device step its place in the queue only where a key change or another device step follows.
         stream = torch.cuda.Stream()
         live = self.hk.Engine(self.R, self.F, self.hsc)
-        pending, stats = [], {"calls": 0, "refused": 0, "succeeded": {e: 0 for e in ENTRY_POINTS}}
+        pending, stats = [], {"calls": 0, "refused": 0, "succeeded": {e: 0 for e in ENTRY_POINTS},
+                              "routes": {e: {} for f in ("extend", "extend_align") for e in ENTRIES_OF[f]}, "chunks": {}}
 
         def settles_next(i):
             return i + 1 == len(steps) or (steps[i + 1]["kind"] == "call" and steps[i + 1]["entry"].endswith("_host"))
@@ -703,6 +917,11 @@ class Runner:
                     assert i == pending[-1][0]
                     desc = live.describe(step["alg"], step["n"])
                 self._settle(tag, i, step, outcome, res, desc, news[i])
+                if outcome == "ok" and step["entry"] in stats["routes"]:       # the route of a call that ran and was verified
+                    ran = desc["ran_extend" if FAMILY_OF[step["entry"]] == "extend" else "ran_extend_align"]
+                    stats["routes"][step["entry"]][ran] = stats["routes"][step["entry"]].get(ran, 0) + 1
+                    if FAMILY_OF[step["entry"]] == "extend_align":         # (the live engine's own figure: compared() says why it is not compared)
+                        stats["chunks"][i] = desc["ran_extend_align_chunks"]
             del pending[:]
 
         try:
@@ -749,7 +968,11 @@ class Runner:
                     raise SequenceMismatch((where, "a refused call wrote its output"))
             return
         got = self.landed(res)
-        self.verify(step, got, self.expected(state, step, desc), where)       # the authority: the reference, bit for bit
+        try:
+            exp = self.expected(state, step, desc)
+        except SequenceMismatch as err:                                       # (the route check: it does not know where it is)
+            raise SequenceMismatch((where,) + tuple(err.args[0])) from None
+        self.verify(step, got, exp, where)                                    # the authority: the reference, bit for bit
         for g, f in zip(got, f_res):                                          # ... and the new engine (unwritten words hold the sentinel in both)
             if not np.array_equal(g, f):
                 raise SequenceMismatch((where, "live engine and new engine return different results", "state", state))

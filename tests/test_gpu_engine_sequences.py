@@ -13,24 +13,37 @@ device steps are not back to back.  Every call step is held against
     alignments (the cell width of an alignment read from ran_align_fill, never "either"), cpu_ref.score_banded_sw /
     band_align_ref / band_nw_ref under a band on the block shape describe() reports, cigar_ref, placed_ref / placed_band_ref,
     span_ref, subopt_ref, span_cigar_ref, extend_ref (one reference for the register sweep and the int32 sweep) and
-    extend_align_ref;
+    extend_align_ref -- and, where engine_sequences.extension_route() says "band", extend_band_ref and extend_band_align_ref,
+    after asserting that ran_extend / ran_extend_align say "band" exactly there: a call that quietly took another route is not
+    judged against that route's reference;
   * a NEW engine of the same shape and scoring, configured to the current state, that makes the same call on the same data:
     the same result or the same refusal with the same text, and the same describe() keys (engine_sequences.compared);
   * its own sentinel, where a device-resident call was refused.
 A sequence must not hide behind refusals: at most a third of its calls end refused and every entry point succeeds at least
-twice -- but for the suboptimal scores and the extension alignments where include/valign_hip.h refuses them whatever the keys
-say (engine_sequences.NEVER_SUCCEEDS: reads of more than 1 024 rows; a scoring whose cells leave int16).
+twice -- but for the suboptimal scores where include/valign_hip.h refuses them whatever the keys say
+(engine_sequences.NEVER_SUCCEEDS: reads of more than 1 024 rows; a scoring whose cells leave int16).  Extension alignments are
+no exception any more: in the long world and under the wide scoring the Band route runs them, and every extension entry point
+must have run on that route at least twice in every sequence (the runner's per-route counts, read from ran_extend /
+ran_extend_align).
 
 Four hand-written sequences, one per piece of state that the newer entry points share with the older ones and with each other:
 test_spanned_calls_share_one_child_engine, test_cigar_rows_scratch_at_two_pitches, test_int32_sweeps_share_the_strip_scratch,
-test_extend_wide_flips_around_a_refusal.
+test_extend_wide_flips_around_a_refusal.  Four more for the Band route of the extension families (extend_band,
+extend_band_align), with exact call, refusal, per-entry and per-route counts: test_band_route_shares_the_strip_scratch (the strip
+scratch of the placed int32 sweep, of extend_wide and of the placed strip route, at batch sizes that shrink to one pair and grow
+again, device and host entries), test_band_route_shares_the_pointer_scratch (the pointer scratch in chunks under a 2 MB cap and
+the CIGAR rows scratch at two pitches), test_two_bands_on_one_engine, test_extend_band_keys_flip_around_refusals.  Three of them
+also run in the strips world (520 x 600, engine_sequences.WORLDS): a read that crosses a 512-row strip boundary and reaches its
+end inside the band; its references take seconds each on the CPU.
 
 Regression cases, named: test_band_set_and_cleared -- Engine::set_band_width(0) did not put the plan chosen at construction
 back, so an engine whose band had been set and cleared stayed on the long-read path (describe: long_mode 1, ragged batching
 silently off, other cells judged).  test_refused_alignment_call_reports_its_own_format -- a refused align_host /
 align_cigar_host call left ran_result_format as the previous alignment call had set it ("cigar" after a refused rows call,
 "rows" after a refused CIGAR call), where a new engine reports the refused call's own format; the sequences exposed it at
-tiny, seed 2, step 30."""
+tiny, seed 2, step 30.  test_extension_alignment_reports_its_own_pointer_bytes -- an extension alignment on the register route
+left align_ptr_bytes_per_pair as the last other alignment call had set it; comparing that key after every extension alignment
+that ran exposed it."""
 import functools
 
 import pytest
@@ -54,8 +67,12 @@ def _check_not_hidden(world, scoring, stats):
     for entry in es.ENTRY_POINTS:
         if entry in es.NEVER_SUCCEEDS.get((world, scoring), ()):
             assert stats["succeeded"][entry] == 0, (entry, "is refused by definition here, and ran")
-        else:
+        else:           # (align_extend_* in the long world and under the wide scoring too: the Band route runs them)
             assert stats["succeeded"][entry] >= 2, (entry, "succeeded fewer than twice", stats)
+    # the Band route, from what ran_extend / ran_extend_align said after calls that ran and were verified: every extension entry
+    # point at least twice in every sequence (test_engine_sequences holds the generator to as many calls that should)
+    for entry, routes in stats["routes"].items():
+        assert routes.get("band", 0) >= 2, (entry, "ran on the Band route fewer than twice", stats["routes"])
 
 
 @pytest.mark.parametrize("world,scoring,seed", CASES, ids=lambda v: str(v))
@@ -197,3 +214,163 @@ def test_extend_wide_flips_around_a_refusal(world, monkeypatch):
         refused = [line.partition(" -> refused ")[2] for line in lines if " -> refused " in line]
         assert len(refused) == 4 and all(text.startswith("extension alignments:") for text in refused[:2]), refused
         assert all("score_width = 32" in text and not text.startswith("extension alignments:") for text in refused[2:]), refused
+
+
+# ---- the Band route of the two extension families (extend_band, extend_band_align) and the state it shares ----
+ALWAYS = es.END_BONUSES[-1]
+NO_BAND_TEXT = "extension scores are not built for band_width > 0"
+
+
+def _band_routes(stats):
+    return {e: routes.get("band", 0) for e, routes in stats["routes"].items() if routes.get("band", 0)}
+
+
+@pytest.mark.parametrize("world,scorings", [("short", ("wide",)), ("long", ("linear", "affine4")), ("strips", ("linear", "affine4"))])
+def test_band_route_shares_the_strip_scratch(world, scorings, monkeypatch):
+    """The Band route's boundary rows and partial records lie in the strip scratch (Engine::d_placed_rows_ / d_placed_ends_) of the
+    placed int32 sweep, of extend_wide and of the placed strip route, each with a record layout and sizes of its own.  With
+    placed_wide = extend_wide = extend_band = extend_band_align = 1 one engine rotates, at 130, 7, 1 and 130 pairs (7 and 1 are
+    odd: a wave is two pairs, the scratch is sized by pairs + 1): an unbanded placed call (150 x 600: the int32 sweep; the long
+    world under score_width = 0: the strip route), an unbanded extension-score call (extend_wide's int32 sweep in both), then
+    under a band banded extension scores and alignments through the device and the host entries, then no band again.  In the long
+    world a spanned CIGAR call follows a banded extension alignment."""
+    debug_switches(monkeypatch, ragged_min=8)
+    band = es.WORLDS[world]["bands"][0]
+    steps = [_set(key, 1) for key in ("placed_wide", "extend_wide", "extend_band", "extend_band_align")]
+    for k, (n, begin) in enumerate(((130, 3), (7, 20), (1, 64), (130, 30))):
+        call = dict(CALL, n=n, begin=begin)
+        steps += [dict(call, entry="score_placed_device"), dict(call, entry="score_extend_device"),
+                  _set("band_width", band),
+                  dict(call, entry="score_extend_device"), dict(call, entry="align_extend_device", end_bonus=es.END_BONUSES[k], with_extend=k % 2),
+                  dict(call, entry="score_extend_host"), dict(call, entry="align_extend_host", end_bonus=es.END_BONUSES[3 - k], with_extend=1 - k % 2),
+                  _set("band_width", 0)]
+        if world == "long" and k == 1:
+            steps.append(dict(call, entry="align_span_device"))
+    spans = 1 if world == "long" else 0
+    for scoring in scorings:
+        stats = _runner(world, scoring).run(steps=steps)
+        assert stats["calls"] == 24 + spans and stats["refused"] == 0, stats
+        want = {"score_placed_device": 4, "score_extend_device": 8, "score_extend_host": 4, "align_extend_device": 4, "align_extend_host": 4}
+        assert _counts(stats) == (dict(want, align_span_device=1) if spans else want), stats
+        assert _band_routes(stats) == {"score_extend_device": 4, "score_extend_host": 4, "align_extend_device": 4, "align_extend_host": 4}, stats
+        if world != "strips":           # the unbanded extension scores between them ran on extend_wide's int32 sweep, on the same scratch
+            assert stats["routes"]["score_extend_device"] == {"band": 4, "wide": 4}, stats
+
+
+@pytest.mark.parametrize("world", ("short", "tiny", "strips"))
+def test_band_route_shares_the_pointer_scratch(world, monkeypatch):
+    """The Band route's pointer regions and end cells lie in the pointer scratch of every alignment fill (d_ptr_ / d_ends_), cut
+    into chunks under pointer_scratch_cap_mb, and its walk writes the CIGAR rows scratch at a pitch of R + F + 1 where
+    align_cigar_* has R + F.  Under a cap of 2 MB a banded Smith-Waterman alignment (band_alignments = 1) sizes the scratch first;
+    then banded extension alignments at 130, 7 and 130 pairs alternate with unbanded CIGAR calls and unbanded extension alignments
+    on the register route, with trace_checkpoints = 1 from partway on (not at 520 rows: more than one strip).  At 520 x 600 a pair
+    of the band of 40 holds at least 87 KB of pointers (tests/test_gpu_extend_band_align.py::test_chunks pins 175 to 512 KB with
+    affine gaps, linear gaps take half), so the 130-pair call cannot fit 2 MB: the live engine must report more than one chunk."""
+    debug_switches(monkeypatch, ragged_min=8)
+    band = es.WORLDS[world]["bands"][0]
+    steps = [_set("pointer_scratch_cap_mb", 2), _set("band_width", band), _set("band_alignments", 1), dict(CALL, entry="align_cigar_device", n=40),
+             _set("extend_band", 1), _set("extend_band_align", 1)]
+    big = len(steps)
+    steps += [dict(CALL, entry="align_extend_device"),
+              _set("band_width", 0),
+              dict(CALL, entry="align_cigar_device"), dict(CALL, entry="align_extend_host", end_bonus=-1),
+              _set("band_width", band),
+              dict(CALL, entry="align_extend_host", n=7, with_extend=0),
+              _set("band_width", 0)]
+    if world != "strips":
+        steps.append(_set("trace_checkpoints", 1))
+    steps += [dict(CALL, entry="align_cigar_host", n=7, extended=0), dict(CALL, entry="align_extend_device", n=40, end_bonus=ALWAYS),
+              _set("band_width", band),
+              dict(CALL, entry="align_extend_device", begin=30, end_bonus=ALWAYS),
+              _set("band_width", 0),
+              dict(CALL, entry="align_cigar_host", begin=30),
+              _set("band_width", band),
+              dict(CALL, entry="align_extend_host", begin=9, extended=0)]
+    for scoring in ("linear", "affine4"):
+        stats = _runner(world, scoring).run(steps=steps)
+        assert stats["calls"] == 10 and stats["refused"] == 0, stats
+        assert _counts(stats) == {"align_cigar_device": 2, "align_cigar_host": 2, "align_extend_device": 3, "align_extend_host": 3}, stats
+        assert stats["routes"]["align_extend_device"] == {"band": 2, "rows": 1} and stats["routes"]["align_extend_host"] == {"band": 2, "rows": 1}, stats
+        if world == "strips":
+            assert stats["chunks"][big] > 1, ("the 130-pair banded call was not cut into chunks", stats["chunks"])
+
+
+@pytest.mark.parametrize("world", ("short", "strips"))
+def test_two_bands_on_one_engine(world, monkeypatch):
+    """The pointer layout of a banded extension alignment (versalignlib_amd/csrc/extend_band_align_plan.h) and the windows of the
+    banded sweep depend on w = band_width / 2: one engine runs banded extension scores and alignments under the world's first
+    band, its second and the first again, at 130, 40 and 130 pairs, with all four end bonuses.  In the short world a spanned CIGAR
+    call stands between two of the banded alignments (the band cleared around it)."""
+    debug_switches(monkeypatch, ragged_min=8)
+    bands = es.WORLDS[world]["bands"]
+    steps = [_set("extend_band", 1), _set("extend_band_align", 1)]
+    for k, (band, n) in enumerate(((bands[0], 130), (bands[1], 40), (bands[0], 130))):
+        call = dict(CALL, n=n, begin=3 + 10 * k)
+        steps += [_set("band_width", band),
+                  dict(call, entry="align_extend_device", end_bonus=es.END_BONUSES[k]), dict(call, entry="score_extend_device"),
+                  dict(call, entry="align_extend_host", end_bonus=es.END_BONUSES[3 - k], with_extend=k % 2)]
+        if world == "short" and k == 0:
+            steps += [_set("band_width", 0), dict(call, entry="align_span_device", n=40)]
+    spans = 1 if world == "short" else 0
+    for scoring in ("linear", "affine4"):
+        stats = _runner(world, scoring).run(steps=steps)
+        assert stats["calls"] == 9 + spans and stats["refused"] == 0, stats
+        want = {"score_extend_device": 3, "align_extend_device": 3, "align_extend_host": 3}
+        assert _counts(stats) == (dict(want, align_span_device=1) if spans else want), stats
+        assert _band_routes(stats) == want, stats
+
+
+@pytest.mark.parametrize("world", ("tiny", "short"))
+def test_extend_band_keys_flip_around_refusals(world, monkeypatch):
+    """The route of an extension call is picked by band_width, extend_band, extend_band_align and score_width together, and a
+    refused call must fall back to "none" with the text a new engine gives (include/valign_hip.h).  Under a band: both keys off --
+    both families refused with the scores' text; extend_band = 1 -- the scores run banded, the alignments are refused with a text
+    of their own; extend_band_align = 1 -- both run; score_width = 16 -- both refused with a text that begins "extend_band:";
+    score_width = 32 -- both run; extend_band = 0 with extend_band_align still 1 -- both refused with the scores' text again;
+    band_width = 0 (and score_width = 0, which the register route needs) -- the register route.  After every call, refused ones
+    included, ran_extend* / ran_extend_align* are a new engine's."""
+    debug_switches(monkeypatch, ragged_min=8)
+    steps = [_set("band_width", es.WORLDS[world]["bands"][1]),
+             dict(CALL, entry="score_extend_device"), dict(CALL, entry="align_extend_device"),
+             _set("extend_band", 1),
+             dict(CALL, entry="score_extend_host"), dict(CALL, entry="align_extend_host"),
+             _set("extend_band_align", 1),
+             dict(CALL, entry="score_extend_device", n=40), dict(CALL, entry="align_extend_device"),
+             _set("score_width", 16),
+             dict(CALL, entry="score_extend_device"), dict(CALL, entry="align_extend_host", n=40),
+             _set("score_width", 32),
+             dict(CALL, entry="score_extend_host", n=7), dict(CALL, entry="align_extend_device", n=7, end_bonus=ALWAYS),
+             _set("extend_band", 0),
+             dict(CALL, entry="score_extend_device", n=1), dict(CALL, entry="align_extend_device", n=1),
+             _set("band_width", 0), _set("score_width", 0),
+             dict(CALL, entry="score_extend_device"), dict(CALL, entry="align_extend_host", with_extend=0)]
+    for scoring in ("linear", "sym_affine"):
+        lines = []
+        stats = _runner(world, scoring).run(steps=steps, log=lines.append)
+        assert stats["calls"] == 14 and stats["refused"] == 7, stats
+        assert _counts(stats) == {"score_extend_device": 2, "score_extend_host": 2, "align_extend_device": 2, "align_extend_host": 1}, stats
+        assert stats["routes"] == {"score_extend_device": {"band": 1, "rows": 1}, "score_extend_host": {"band": 2}, "align_extend_device": {"band": 2},
+                                   "align_extend_host": {"rows": 1}}, stats
+        refused = [line.partition(" -> refused ")[2].strip() for line in lines if " -> refused " in line]
+        assert len(refused) == 7, refused
+        assert refused[0] == refused[1] == refused[5] == refused[6] == NO_BAND_TEXT, refused
+        assert refused[2].startswith("extension alignments: not built under a band"), refused
+        assert refused[3].startswith("extend_band:") and refused[4].startswith("extend_band:") and "score_width = 16" in refused[3], refused
+
+
+def test_extension_alignment_reports_its_own_pointer_bytes(monkeypatch):
+    """Regression, named: an extension alignment on the register route left align_ptr_bytes_per_pair as the last OTHER alignment call
+    had set it (describe: "the pointer-stream bytes a pair holds in the plan of the last alignment call"), so a live engine
+    reported a CIGAR call's -- or a banded extension alignment's -- figure where a new engine reports the call's own.  A register
+    extension alignment after an unbanded CIGAR call, after a banded extension alignment, and first of all."""
+    debug_switches(monkeypatch, ragged_min=8)
+    steps = [dict(CALL, entry="align_extend_device", n=40),
+             dict(CALL, entry="align_cigar_device"), dict(CALL, entry="align_extend_device"),
+             _set("extend_band", 1), _set("extend_band_align", 1), _set("band_width", 16),
+             dict(CALL, entry="align_extend_host"),
+             _set("band_width", 0),
+             dict(CALL, entry="align_extend_host", n=7)]
+    for scoring in ("linear", "affine4"):
+        stats = _runner("short", scoring).run(steps=steps)
+        assert stats["calls"] == 5 and stats["refused"] == 0, stats
+        assert stats["routes"]["align_extend_device"] == {"rows": 2} and stats["routes"]["align_extend_host"] == {"band": 1, "rows": 1}, stats

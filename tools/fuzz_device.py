@@ -604,15 +604,18 @@ def run_extend_band_align(c):
 
 def soak_sequences(rng, a):
     """--kind sequence: the generator and the runner of tests/engine_sequences.py (what tests/test_gpu_engine_sequences.py runs
-    on its committed seeds) on random seeds: ONE engine per sequence through key changes (extend_wide among them) and calls of all
-    nine families -- spanned CIGARs, extension scores and extension alignments included, with their end_bonus, with_extend and
-    extended --, every call against its reference and against a new engine.  No code path of its own: a mismatch is the runner's,
-    with world, seed and step index."""
+    on its committed seeds) on random seeds: ONE engine per sequence through changes of all fifteen keys (extend_wide, extend_band
+    and extend_band_align among them) and calls of all nine families -- spanned CIGARs, extension scores and extension alignments
+    included, with their end_bonus, with_extend and extended, on the register route, the int32 sweep and the BANDED strip sweep --,
+    every call against the reference of the route the state selects and against a new engine.  The worlds are the three with
+    committed seeds (12 x 20, 150 x 200, 1 600 x 96); the 520 x 600 world of the hand-written sequences has no generated ones.
+    No code path of its own: a mismatch is the runner's, with world, seed and step index."""
     os.environ["VALIGN_HIP_DEBUG"] = "ragged_min=8"        # (before any engine exists: the length classes at these batch sizes)
     import engine_sequences as es
     runners, t0, done = {}, time.time(), 0
+    worlds = sorted(world for world in es.WORLDS if es.WORLDS[world]["seeds"])
     while time.time() - t0 < a.seconds:
-        world = str(rng.choice(sorted(es.WORLDS)))
+        world = str(rng.choice(worlds))
         scoring = str(rng.choice(es.WORLDS[world]["scorings"]))
         seed = int(rng.integers(10, 1 << 30))
         if (world, scoring) not in runners:
@@ -636,7 +639,8 @@ def main():
     ap.add_argument("--first", type=int, default=0)
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--kind", choices=["subopt", "sequence", "span_cigar", "extend", "extend_band", "extend_align", "extend_band_align"], default=None,
-                    help="draw cases of this kind only (default: the mix); sequence: one engine through tests/engine_sequences.py's sequences")
+                    help="draw cases of this kind only (default: the mix); sequence: one engine through tests/engine_sequences.py's sequences "
+                         "(fifteen keys, extend_band and extend_band_align among them; nine families of calls, the banded extension routes included)")
     a = ap.parse_args()
     rng = np.random.default_rng(a.seed)
     if a.kind == "sequence":

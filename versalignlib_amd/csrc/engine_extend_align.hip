@@ -224,6 +224,7 @@ void Engine::extend_align_chunk(const LaunchPlan &plan, const ExtendAlignChoice 
     a.extended = extended;
     launch_extend_align_cigar(stream, a);
     ran_extend_align_ = ran_placed_name(PlacedRoute::Rows);
+    align_ptr_bytes_per_pair_ = choice.wave_ptr_bytes / ppw;           // (the call's own, as on the Band route: not the last other alignment's)
 }
 
 void Engine::align_extend_device(int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int end_bonus, int extended, CigarRec *d_recs,
