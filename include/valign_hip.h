@@ -824,6 +824,9 @@ int valign_hip_set_half_float_cells(valign_hip_engine *e, int mode);
  * of the last alignment call, "align_scratch_bytes" the pointer scratch the engine holds after it.
  * "ran_result_format" is "rows" or "cigar" for the last alignment call, "cigar_d2h_bytes" what the last
  * valign_hip_align_cigar_host call copied back, "cigar_rows_scratch_bytes" the rows scratch of the compact format.
+ * "ran_cigar_lanes" is the lane group per pair the CIGAR encoder of the last valign_hip_align_cigar_*, _align_span_* or
+ * _align_extend_* call ran on: 16 (min(R, F) <= 256) or 64 -- for a spanned call those of the window that was walked, R x
+ * span_ref_length --, 0 before any such call and after one that was refused or launched nothing.
  * "ran_placed" is what the last placed-score call ran: key / rows / strip / chain / wide ("none" before any, or when it was
  * refused); "band_placed" is the key of valign_hip_set_band_placed, "placed_wide" that of valign_hip_set_placed_wide, "extend_wide" that of valign_hip_set_extend_wide.  "ran_span", "span_ref_length" and "span_scratch_bytes"
  * belong to the spanned scores, "ran_subopt", "subopt_scratch_bytes" and "subopt_ring_cols" to the suboptimal scores,

@@ -524,11 +524,12 @@ PLAN_KEYS = ("long_mode", "group_lanes", "rows_per_lane", "score_cells", "band_b
              "extend_band_block_rows")
 RAN_KEYS = {"score": ("ran_score_cells", "ran_score_geometry", "ran_score_sym_affine"),
             "rows": ("ran_align_fill", "ran_align_geometry", "ran_result_format"),
-            "cigar": ("ran_align_fill", "ran_align_geometry", "ran_result_format"),
+            "cigar": ("ran_align_fill", "ran_align_geometry", "ran_result_format", "ran_cigar_lanes"),
             "placed": ("ran_placed", "ran_placed_geometry"), "span": ("ran_span", "ran_placed", "ran_placed_geometry"),
             "subopt": ("ran_subopt", "ran_subopt_geometry"),
-            "span_cigar": ("ran_span_cigar", "ran_placed", "ran_placed_geometry", "ran_result_format"),
-            "extend": ("ran_extend", "ran_extend_geometry"), "extend_align": ("ran_extend_align", "ran_extend_align_geometry")}
+            "span_cigar": ("ran_span_cigar", "ran_placed", "ran_placed_geometry", "ran_result_format", "ran_cigar_lanes"),
+            "extend": ("ran_extend", "ran_extend_geometry"),
+            "extend_align": ("ran_extend_align", "ran_extend_align_geometry", "ran_cigar_lanes")}
 SENTINEL = -7
 
 

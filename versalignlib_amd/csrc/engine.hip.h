@@ -772,6 +772,16 @@ private:
     // encode `cnt` pairs from pair `begin` of the call on `stream`: rows / idx / ends are those of pair `begin`
     void launch_cigar(hipStream_t stream, const uint8_t *rows, const short *idx, const EndCell *ends, long long begin, long long cnt);
     void launch_cigar_args(hipStream_t stream, CigarArgs &a);
+    // The encoders' lane group per pair, for all three launch sites (here, engine_span_cigar.hip, engine_extend_align.hip): 16 lanes
+    // where an alignment is a few steps of 16 columns (short reads: ~160 columns at 150 x 500), a wave beyond that (DESIGN 3:
+    // measured).  Debug switch cigar_lanes forces one.  The answer is noted for describe() ("ran_cigar_lanes").
+    int take_cigar_lanes() {
+        int lanes = std::min(R_, F_) <= 256 ? 16 : 64;
+        const long long forced = dbg_.value("cigar_lanes", 0);
+        if (forced == 16 || forced == 64) lanes = (int)forced;
+        ran_cigar_lanes_ = lanes;
+        return lanes;
+    }
     void ensure_cigar_scratch(int slots, long long pairs, hipStream_t stream);
     // offsets[0 .. n] = exclusive scan of recs[p].n_ops on `stream` (cigar_scan_kernel)
     void launch_cigar_scan(const CigarRec *recs, long long *offsets, long long n, hipStream_t stream);
@@ -1051,6 +1061,7 @@ private:
     const Geometry *ran_extend_align_geo_ = nullptr;     // ... and the geometry its fill was taken from (ran_extend_align_geometry)
     long long ran_extend_align_chunks_ = 0;              // ... and the chunks it was cut into (ran_extend_align_chunks)
     const char *ran_result_format_ = "rows";             // of the last alignment call: rows / cigar (describe)
+    int ran_cigar_lanes_ = 0;                            // the lane group the last CIGAR call's encoder ran on: 16 / 64, 0 none (describe)
     long long cigar_d2h_bytes_ = 0;                      // what the last align_cigar_host call copied back
     const CigarSink *cigar_ = nullptr;
     long long cigar_pairs_[2] = {0, 0};                  // pairs the cigar scratch of each slot holds

@@ -27,11 +27,7 @@ void Engine::launch_cigar_args(hipStream_t stream, CigarArgs &a) {
     a.ext_read = sc_.ext_read;
     a.open_ref = sc_.open_ref;
     a.ext_ref = sc_.ext_ref;
-    // Lane group per pair: 16 lanes where an alignment is a few steps of 16 columns (short reads: ~160 columns at 150 x 500),
-    // a wave beyond that (measured).  Debug switch cigar_lanes forces one.
-    int lanes = std::min(R_, F_) <= 256 ? 16 : 64;
-    const long long forced = dbg_.value("cigar_lanes", 0);
-    if (forced == 16 || forced == 64) lanes = (int)forced;
+    const int lanes = take_cigar_lanes();
     const long long per_block = 256 / lanes;
     const dim3 grid((unsigned)((a.n + per_block - 1) / per_block)), block(256);
     if (lanes == 16) hipLaunchKernelGGL(cigar_encode_kernel<16>, grid, block, 0, stream, a);
@@ -80,6 +76,7 @@ void Engine::ensure_cigar_scratch(int slots, long long pairs, hipStream_t stream
 
 void Engine::align_cigar_device(int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int extended, CigarRec *d_recs,
                                 unsigned *d_ops, int ops_stride, hipStream_t stream) {
+    ran_cigar_lanes_ = 0;                   // (a refused call reports no encoder)
     if (extended != 0 && extended != 1) throw std::runtime_error("extended must be 0 (M) or 1 (= / X)");
     if (ops_stride < 1) throw std::runtime_error("ops_stride must be >= 1");
     if (!d_recs || !d_ops) throw std::runtime_error("null result buffer");
@@ -100,6 +97,7 @@ void Engine::align_cigar_device(int opt, long long n, const uint8_t *d_reads, co
 
 bool Engine::align_cigar_host(int opt, int n, const char *const *reads, const char *const *refs, int extended, CigarRec *recs,
                               unsigned *ops, long long ops_cap, long long *offsets, long long *ops_needed, int threads) {
+    ran_cigar_lanes_ = 0;
     if (extended != 0 && extended != 1) throw std::runtime_error("extended must be 0 (M) or 1 (= / X)");
     if (!recs || !offsets || !ops_needed || (!ops && ops_cap > 0)) throw std::runtime_error("null result buffer");
     if (n < 0 || ops_cap < 0) throw std::runtime_error("negative size");

@@ -165,7 +165,7 @@ std::string Engine::describe(int opt, long long n) const {
                                    ran_geometry(ran_extend_align_geo_) + "\", \"extend_align_scratch_bytes\": " +
                                    std::to_string((long long)(d_ptr_.bytes() + d_ends_.bytes() + d_extend_align_recs_.bytes())) +
                                    ", \"extend_band_align\": " + std::to_string(extend_band_align()) + ", \"ran_extend_align_chunks\": " +
-                                   std::to_string(ran_extend_align_chunks_));
+                                   std::to_string(ran_extend_align_chunks_) + ", \"ran_cigar_lanes\": " + std::to_string(ran_cigar_lanes_));
     if (ran_score_sym_affine_)         // only where the last score call ran the int16 symmetric affine SW kernel
         out.insert(out.size() - 1, std::string(", \"ran_score_sym_affine\": \"") + ran_score_sym_affine_ + "\", \"ran_score_sym_affine_frame\": \"" +
                                        ran_score_sym_affine_frame_ + "\", \"ran_score_sym_affine_scores\": \"" + ran_score_sym_affine_scores_ + "\"");

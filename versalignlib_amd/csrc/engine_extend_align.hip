@@ -150,10 +150,7 @@ void Engine::launch_extend_align_cigar(hipStream_t stream, CigarArgs &a) {
     a.ext_read = sc_.ext_read;
     a.open_ref = sc_.open_ref;
     a.ext_ref = sc_.ext_ref;
-    // the lane group of launch_cigar_args
-    int lanes = std::min(R_, F_) <= 256 ? 16 : 64;
-    const long long forced = dbg_.value("cigar_lanes", 0);
-    if (forced == 16 || forced == 64) lanes = (int)forced;
+    const int lanes = take_cigar_lanes();
     const long long per_block = 256 / lanes;
     const long long blocks = (a.n + per_block - 1) / per_block;
     if (blocks > 0x7FFFFFFFll) throw std::runtime_error("batch too large for one launch");
@@ -232,6 +229,7 @@ void Engine::align_extend_device(int opt, long long n, const uint8_t *d_reads, c
     ran_extend_align_ = "none";
     ran_extend_align_geo_ = nullptr;
     ran_extend_align_chunks_ = 0;
+    ran_cigar_lanes_ = 0;
     if (extended != 0 && extended != 1) throw std::runtime_error("extended must be 0 (M) or 1 (= / X)");
     if (ops_stride < 1) throw std::runtime_error("ops_stride must be >= 1");
     if (!d_recs || !d_ops) throw std::runtime_error("null result buffer");
@@ -257,6 +255,7 @@ bool Engine::align_extend_host(int opt, int n, const char *const *reads, const c
     ran_extend_align_ = "none";
     ran_extend_align_geo_ = nullptr;
     ran_extend_align_chunks_ = 0;
+    ran_cigar_lanes_ = 0;
     if (extended != 0 && extended != 1) throw std::runtime_error("extended must be 0 (M) or 1 (= / X)");
     if (!recs || !offsets || !ops_needed || (!ops && ops_cap > 0)) throw std::runtime_error("null result buffer");
     if (n < 0 || ops_cap < 0) throw std::runtime_error("negative size");

@@ -85,10 +85,7 @@ void Engine::launch_span_cigar_args(hipStream_t stream, SpanCigarArgs &a) {
     a.ext_read = sc_.ext_read;
     a.open_ref = sc_.open_ref;
     a.ext_ref = sc_.ext_ref;
-    // the lane group of launch_cigar_args, for the shape that is walked
-    int lanes = std::min(R_, F_) <= 256 ? 16 : 64;
-    const long long forced = dbg_.value("cigar_lanes", 0);
-    if (forced == 16 || forced == 64) lanes = (int)forced;
+    const int lanes = take_cigar_lanes();          // for the shape that is walked; the parent reports it (span_cigar_chunk)
     const long long per_block = 256 / lanes;
     const long long blocks = (a.n + per_block - 1) / per_block;
     if (blocks > 0x7FFFFFFFll) throw std::runtime_error("batch too large for one launch");
@@ -118,10 +115,12 @@ void Engine::span_cigar_chunk(int c, int opt, long long n, const uint8_t *d_read
     if (n > x.cap) throw std::runtime_error("spanned CIGARs: chunk larger than its scratch");
     score_placed_device(opt, n, d_reads, d_refs, x.fwd.get(), stream);
     launch_span_reverse(n, d_reads, d_refs, x.fwd.get(), x.rev_reads.get(), x.rev_refs.get(), child.ref_length(), stream);
+    child.ran_cigar_lanes_ = 0;
     {
         ScopedSink<CigarSink> scoped(child.cigar_, &sink);
         (void)child.align_device(opt, n, x.rev_reads.get(), x.rev_refs.get(), x.rows.get(), x.idx.get(), stream);
     }
+    ran_cigar_lanes_ = child.ran_cigar_lanes_;          // the width the child's encoder ran on
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ran_span_cigar_ = std::string(ran_placed_) + "/" + child.ran_align_fill();
 }
@@ -129,6 +128,7 @@ void Engine::span_cigar_chunk(int c, int opt, long long n, const uint8_t *d_read
 void Engine::align_span_device(int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int extended, CigarRec *d_recs, unsigned *d_ops,
                                int ops_stride, hipStream_t stream) {
     ran_span_cigar_ = "none";
+    ran_cigar_lanes_ = 0;
     if (extended != 0 && extended != 1) throw std::runtime_error("extended must be 0 (M) or 1 (= / X)");
     if (ops_stride < 1) throw std::runtime_error("ops_stride must be >= 1");
     if (!d_recs || !d_ops) throw std::runtime_error("null result buffer");
@@ -156,6 +156,7 @@ void Engine::align_span_device(int opt, long long n, const uint8_t *d_reads, con
 bool Engine::align_span_host(int opt, int n, const char *const *reads, const char *const *refs, int extended, CigarRec *recs, unsigned *ops,
                              long long ops_cap, long long *offsets, long long *ops_needed, int threads) {
     ran_span_cigar_ = "none";
+    ran_cigar_lanes_ = 0;
     if (extended != 0 && extended != 1) throw std::runtime_error("extended must be 0 (M) or 1 (= / X)");
     if (!recs || !offsets || !ops_needed || (!ops && ops_cap > 0)) throw std::runtime_error("null result buffer");
     if (n < 0 || ops_cap < 0) throw std::runtime_error("negative size");
