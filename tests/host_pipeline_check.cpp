@@ -6,7 +6,8 @@
 // What it drives: scattered heap blocks of odd lengths in, pair-major staging out (gather); staging into a flat
 // sink and into an Alignment-shaped array of operator new[] rows (scatter); chunk sizes around the serial / parallel
 // thresholds; thread counts that make the pool resize; thousands of back-to-back tiny jobs (a worker that wakes up
-// late must never touch a finished job); an exception thrown by one part.
+// late must never touch a finished job); an exception thrown by one part; and the packed results of the compact format
+// (PackedLayout, OpsBudget, HostPacker::unpack_packed) against a serial restatement, into arrays of exactly the call's sizes.
 #include "host_pipeline.h"
 
 #include <stdio.h>
@@ -165,9 +166,98 @@ void packing(int R, int F, long long n, int threads) {
     }
 }
 
+// ---- packed results of the compact format: PackedLayout, OpsBudget and HostPacker::unpack_packed ----
+struct Rec {                    // valign_hip_aln in shape
+    int read_begin, read_end, ref_begin, ref_end, score;
+    unsigned n_ops;
+};
+constexpr size_t kExtraBytes = 20;          // an extension record
+constexpr uint32_t kUntouched = 0xA5A5A5A5u;
+
+// One chunk as the device would pack it, in a buffer of exactly layout.bytes(): `cnt` records whose n_ops sum to `total`
+struct Chunk {
+    valign::PackedLayout layout;
+    std::vector<uint32_t> h;                // (words: the ops behind the records are read as uint32_t)
+    std::vector<Rec> recs;
+    std::vector<uint8_t> extra;
+    std::vector<uint32_t> ops;
+    Chunk(long long cnt, long long total, bool with_extra, bool with_ops, uint64_t seed)
+        : layout(cnt, with_extra ? kExtraBytes : 0, total, with_ops), h(layout.bytes() / 4), recs((size_t)cnt), extra(with_extra ? kExtraBytes * (size_t)cnt : 0),
+          ops((size_t)total) {
+        for (long long i = 0; i < cnt; ++i) {
+            const int v = (int)mix(seed + (uint64_t)i);
+            recs[(size_t)i] = Rec{v, v + 1, v + 2, v + 3, v + 4, (unsigned)(total / cnt + (i < total % cnt ? 1 : 0))};
+        }
+        for (size_t k = 0; k < extra.size(); ++k) extra[k] = (uint8_t)mix(seed * 3 + k);
+        for (size_t k = 0; k < ops.size(); ++k) ops[k] = ((uint32_t)seed * 7u + (uint32_t)k * 2654435761u) | 1u;       // (never the sentinel)
+        uint8_t *b = reinterpret_cast<uint8_t *>(h.data());
+        if (cnt) memcpy(b, recs.data(), sizeof(Rec) * (size_t)cnt);
+        if (!extra.empty()) memcpy(b + sizeof(Rec) * (size_t)cnt, extra.data(), extra.size());
+        if (with_ops && total) memcpy(b + sizeof(Rec) * (size_t)cnt + extra.size(), ops.data(), 4 * (size_t)total);
+    }
+};
+
+void packed_layout() {
+    const valign::PackedLayout a(7, 0, 100, true), b(7, kExtraBytes, 100, true), c(7, kExtraBytes, 100, false), none;
+    expect(a.rec_bytes == 7 * 24 && a.extra_bytes == 0 && a.ops_at() == 168 && a.bytes() == 168 + 400, "layout: records + ops");
+    expect(b.rec_bytes == 168 && b.extra_bytes == 140 && b.ops_at() == 308 && b.bytes() == 308 + 400, "layout: records + extra records + ops");
+    expect(c.ops_at() == 308 && c.bytes() == 308 && !c.with_ops && c.total == 100, "layout: the ops left out");
+    expect(none.bytes() == 0 && none.cnt == 0, "layout: empty");
+    valign::OpsBudget budget{10};
+    expect(budget.add(4) && budget.add(6) && budget.fits() && budget.total == 10, "budget: exactly the cap fits");
+    expect(budget.add(0) && !budget.add(1) && !budget.add(0) && !budget.fits() && budget.total == 11, "budget: once passed, nothing fits again");
+    valign::OpsBudget zero{0};
+    expect(zero.add(0) && !zero.add(1), "budget: a cap of 0 holds a call without ops");
+}
+
+// Two consecutive chunks of `cnt` pairs and `total` ops each into arrays of exactly the call's sizes, against a serial restatement.
+// ops_from: the first chunk that carries no ops (2: both carry theirs) -- what the engines do once the running total passes ops_cap
+void unpack_case(valign::HostPacker &packer, long long cnt, long long total, int threads, bool with_extra, int ops_from) {
+    const std::string what = "unpack cnt=" + std::to_string(cnt) + " total=" + std::to_string(total) + " threads=" + std::to_string(threads) +
+                             (with_extra ? " extra" : "") + " ops_from=" + std::to_string(ops_from);
+    const long long n = 2 * cnt;
+    std::vector<Rec> recs((size_t)n), exp_recs((size_t)n);
+    std::vector<long long> offsets((size_t)n + 1, -7), exp_offsets((size_t)n + 1, -7);
+    std::vector<uint32_t> ops((size_t)(2 * total), kUntouched), exp_ops((size_t)(2 * total), kUntouched);
+    std::vector<uint8_t> extra(with_extra ? kExtraBytes * (size_t)n : 0, 0xEE), exp_extra(extra);
+    memset(recs.data(), 0xEE, sizeof(Rec) * recs.size());
+    offsets[0] = exp_offsets[0] = 0;                    // (the entry points set it before the first chunk)
+    for (int c = 0; c < 2; ++c) {
+        const long long begin = c * cnt;
+        const Chunk chunk(cnt, total, with_extra, c < ops_from, (uint64_t)(cnt * 31 + total * 17 + c));
+        expect(chunk.layout.bytes() == 24 * (size_t)cnt + (with_extra ? 20 * (size_t)cnt : 0) + (c < ops_from ? 4 * (size_t)total : 0), what + ": layout bytes");
+        packer.unpack_packed(chunk.layout, reinterpret_cast<const uint8_t *>(chunk.h.data()), begin, recs.data(),
+                             with_extra ? extra.data() + kExtraBytes * (size_t)begin : nullptr, ops.data(), offsets.data(), threads);
+        // the same, serially
+        for (long long i = 0; i < cnt; ++i) {
+            exp_recs[(size_t)(begin + i)] = chunk.recs[(size_t)i];
+            exp_offsets[(size_t)(begin + i + 1)] = exp_offsets[(size_t)(begin + i)] + chunk.recs[(size_t)i].n_ops;
+        }
+        for (size_t k = 0; k < chunk.extra.size(); ++k) exp_extra[kExtraBytes * (size_t)begin + k] = chunk.extra[k];
+        if (c < ops_from)
+            for (long long k = 0; k < total; ++k) exp_ops[(size_t)(exp_offsets[(size_t)begin] + k)] = chunk.ops[(size_t)k];
+    }
+    expect(memcmp(recs.data(), exp_recs.data(), sizeof(Rec) * recs.size()) == 0, what + ": records");
+    expect(offsets == exp_offsets && offsets[(size_t)n] == 2 * total && offsets[(size_t)cnt] == total, what + ": offsets");
+    expect(extra == exp_extra, what + ": extra records");
+    expect(ops == exp_ops, what + ": ops");
+    bool untouched = true;                              // stated on its own: nothing at or behind the first chunk without ops is written
+    for (long long k = (long long)ops_from * total; k < 2 * total; ++k) untouched = untouched && ops[(size_t)k] == kUntouched;
+    expect(untouched, what + ": ops of a chunk without ops are left alone");
+}
+
 }  // namespace
 
 int main() {
+    packed_layout();
+    for (int th : {1, 4, 16}) {
+        valign::HostPacker packer(1, 1);
+        for (long long cnt : {1ll, 4095ll, 4096ll, 4097ll})         // either side of the records' serial threshold
+            for (long long total : {0ll, 65535ll, 65536ll, 65537ll})        // ... and of the ops'
+                for (bool with_extra : {false, true})
+                    for (int ops_from : {2, 1, 0}) unpack_case(packer, cnt, total, th, with_extra, ops_from);
+    }
+
     {   // every byte value, scalar == vector == definition
         uint8_t all[256 + 64], a[160], b[160];
         for (int c = 0; c < 256 + 64; ++c) all[c] = (uint8_t)c;

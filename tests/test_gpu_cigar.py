@@ -276,12 +276,13 @@ def test_ops_stride_overflow_is_per_pair():
     eng.close()
 
 
-def _raw_host(eng, opt, reads, refs, cap, extended=1, sentinel=None):
+def _raw_host(eng, opt, reads, refs, cap, extended=1, sentinel=None, ops_len=None):
+    """ops_len: entries of the ops buffer where that is more than the ops_cap the call is told"""
     n = reads.shape[0]
     rp = (reads.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(reads.shape[1])).astype(np.uint64)
     fp = (refs.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(refs.shape[1])).astype(np.uint64)
     recs = np.zeros(max(n, 1), dtype=hipkernel.aln_dtype())
-    ops = np.zeros(max(cap, 1), np.uint32)
+    ops = np.zeros(max(cap, 1) if ops_len is None else ops_len, np.uint32)
     offsets = np.zeros(n + 1, np.int64)
     if sentinel is not None:
         recs.view(np.int32)[:] = sentinel
@@ -324,6 +325,31 @@ def test_host_entry_point_contract():
     assert "ops_stride" in hipkernel._err()
     assert L.valign_hip_align_cigar_device(eng._h, 0, 1, d_reads.data_ptr(), d_refs.data_ptr(), 0, None, one.data_ptr(), 4, None) != 0
     assert L.valign_hip_align_cigar_device(eng._h, 0, 1, d_reads.data_ptr(), d_refs.data_ptr(), 3, one.data_ptr(), one.data_ptr(), 4, None) != 0
+    eng.close()
+
+
+def test_ops_cap_crossed_between_chunks(monkeypatch):
+    """Three chunks of 1 024, 1 024 and 452 pairs on the chunk pipeline, ops_cap passed at a chunk border, one op before it and
+    in the last chunk: the return code, the exact need, complete records and offsets, nothing written at or behind ops_cap, only
+    the ops of the chunks that still fitted copied back, and the same engine serves the exact retry."""
+    debug_switches(monkeypatch, align_chunk_bytes=4096)              # the floor: 1 024 pairs a chunk
+    R, F, n, untouched = 150, 500, 2500, -3
+    reads, refs = _pairs(n, R, F, 43)
+    sc, _ = _scorings(False)
+    eng = hipkernel.Engine(R, F, sc)
+    recs, ops, offsets = eng.align_cigar_host(host.SW, reads, refs, extended=True, threads=4)
+    total, d = int(offsets[n]), eng.describe(0, n)
+    # beyond the direct call: the walks ran as kernels of their own, and three op totals crossed
+    assert d["ran_align_fill"] not in ("none", "fused_tag") and d["cigar_d2h_bytes"] == 24 * n + 4 * total + 8 * 3, d
+    for cap, copied in ((int(offsets[1024]), int(offsets[1024])), (int(offsets[1024]) - 1, 0), (int(offsets[2048]), int(offsets[2048]))):
+        assert 0 < cap < total
+        rc, recs2, ops2, offsets2, needed = _raw_host(eng, host.SW, reads, refs, cap, sentinel=untouched, ops_len=total)
+        assert rc != 0 and needed == total and "ops_cap" in hipkernel._err(), cap
+        assert np.array_equal(recs2, recs) and np.array_equal(offsets2, offsets), cap
+        assert (ops2.view(np.int32)[cap:] == untouched).all(), cap
+        assert eng.describe(0, n)["cigar_d2h_bytes"] == 24 * n + 4 * copied + 8 * 3, cap
+        rc, recs3, ops3, offsets3, needed = _raw_host(eng, host.SW, reads, refs, total, sentinel=untouched)
+        assert rc == 0 and needed == total and np.array_equal(ops3, ops) and np.array_equal(offsets3, offsets) and np.array_equal(recs3, recs), cap
     eng.close()
 
 

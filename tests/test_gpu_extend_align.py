@@ -278,6 +278,47 @@ def test_host_equals_device(monkeypatch, chunks):
         eng.close()
 
 
+def _host_raw(eng, reads, refs, cap, ops_len, bonus, with_extend, threads=2):
+    """valign_hip_align_extend_host as it stands: an ops buffer of ops_len entries and an ops_cap of `cap`, both marked"""
+    n = len(reads)
+    rp = (reads.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(reads.shape[1])).astype(np.uint64)
+    fp = (refs.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(refs.shape[1])).astype(np.uint64)
+    recs = np.zeros(n, dtype=hipkernel.aln_dtype())
+    ext = np.zeros(n, dtype=hipkernel.extend_dtype()) if with_extend else None
+    ops = np.full(max(ops_len, 1), 0xDEADBEEF, np.uint32)
+    offsets = np.full(n + 1, -7, np.int64)
+    needed = ctypes.c_longlong(-7)
+    rc = hipkernel.lib().valign_hip_align_extend_host(eng._h, 0, n, rp.ctypes.data, fp.ctypes.data, bonus, 1, recs.ctypes.data, ops.ctypes.data, cap,
+                                                      offsets.ctypes.data, ctypes.byref(needed), ext.ctypes.data if with_extend else None, threads)
+    return rc, recs, ops, offsets, needed.value, ext
+
+
+@pytest.mark.parametrize("with_extend", [True, False])
+def test_ops_cap_crossed_between_chunks(monkeypatch, with_extend):
+    """Three chunks of 1 024, 1 024 and 452 pairs with ops_cap passed at a chunk border, one op before it and in the last chunk: the
+    return code, the exact need, complete records, offsets and extension records, nothing written at or behind ops_cap, only the
+    ops of the chunks that still fitted copied back, and the same engine serves the exact retry."""
+    debug_switches(monkeypatch, align_chunk_bytes=4096)              # the floor: 1 024 pairs a chunk
+    R, F, n = 33, 70, 2500
+    reads, refs = _batch(n, R, F, seed=8)
+    eng = hipkernel.Engine(R, F, _scoring("affsym"))
+    recs, ops, offsets, ext = eng.align_extend_host(0, reads, refs, end_bonus=6, extended=True, with_extend=with_extend, threads=4)
+    total, fixed = int(offsets[n]), (24 + (20 if with_extend else 0)) * n + 8 * 3
+    d = eng.describe(0, n)
+    assert d["ran_extend_align_chunks"] == 3 and d["cigar_d2h_bytes"] == fixed + 4 * total, d
+    for cap, copied in ((int(offsets[1024]), int(offsets[1024])), (int(offsets[1024]) - 1, 0), (int(offsets[2048]), int(offsets[2048]))):
+        assert 0 < cap < total
+        rc, recs2, ops2, offsets2, needed, ext2 = _host_raw(eng, reads, refs, cap, total, 6, with_extend)
+        assert rc != 0 and needed == total and "ops_cap" in hipkernel._err(), cap
+        assert np.array_equal(recs2, recs) and np.array_equal(offsets2, offsets) and (ext2 is None if ext is None else np.array_equal(ext2, ext)), cap
+        assert (ops2[cap:] == 0xDEADBEEF).all(), cap
+        assert eng.describe(0, n)["cigar_d2h_bytes"] == fixed + 4 * copied, cap
+        rc, recs3, ops3, offsets3, needed, ext3 = _host_raw(eng, reads, refs, total, total, 6, with_extend)
+        assert rc == 0 and needed == total and np.array_equal(ops3, ops) and np.array_equal(offsets3, offsets) and np.array_equal(recs3, recs), cap
+        assert ext3 is None if ext is None else np.array_equal(ext3, ext), cap
+    eng.close()
+
+
 # ---- 8. refusals ----
 def test_refusals():
     R, F = 33, 70

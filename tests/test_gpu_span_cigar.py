@@ -202,12 +202,13 @@ def test_wide_forward_sweep_returns_the_same_records():
 
 
 # ---- 7. host entry ----
-def _host_raw(eng, reads, refs, cap, extended=0, threads=2, opt=0):
+def _host_raw(eng, reads, refs, cap, extended=0, threads=2, opt=0, ops_len=None):
+    """ops_len: entries of the ops buffer where that is more than the ops_cap the call is told"""
     n = len(reads)
     rp = (reads.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(reads.shape[1] if n else 0)).astype(np.uint64)
     fp = (refs.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(refs.shape[1] if n else 0)).astype(np.uint64)
     recs = np.zeros(n, dtype=hipkernel.aln_dtype())
-    ops = np.full(max(cap, 1), 0xDEADBEEF, np.uint32)
+    ops = np.full(max(cap, 1) if ops_len is None else ops_len, 0xDEADBEEF, np.uint32)
     offsets = np.full(n + 1, -7, np.int64)
     needed = ctypes.c_longlong(-7)
     rc = hipkernel.lib().valign_hip_align_span_host(eng._h, opt, n, rp.ctypes.data, fp.ctypes.data, extended, recs.ctypes.data, ops.ctypes.data,
@@ -256,6 +257,29 @@ def test_host_pipeline_of_three_chunks(monkeypatch):
     assert d["cigar_d2h_bytes"] == 24 * n + 4 * int(offsets[n]) + 8 * 3, (d["cigar_d2h_bytes"], int(offsets[n]))
     exp = span_cigar_ref.expected(reads[1000:1064], refs[1000:1064], sc_.scoring("affsym"), affine=True)       # (across the first chunk border)
     _check(recs[1000:1064], ops[1000:1064], exp, "pairs 1000 - 1063")
+
+
+def test_ops_cap_crossed_between_chunks(monkeypatch):
+    """The three chunks above with ops_cap passed at a chunk border, one op before it and in the last chunk: the return code, the
+    exact need, complete records and offsets, nothing written at or behind ops_cap, only the ops of the chunks that still fitted
+    copied back, and the same engine serves the exact retry."""
+    debug_switches(monkeypatch, align_chunk_bytes=4096)              # the floor: 1 024 pairs a chunk
+    R, F, n = 33, 70, 2500
+    reads, refs = sc_.pairs(n, R, F, 13)
+    eng = hipkernel.Engine(R, F, sc_.scoring("affsym"))
+    recs, ops, offsets = eng.align_span_host(0, reads, refs, threads=4)
+    total = int(offsets[n])
+    assert eng.describe(0, n)["cigar_d2h_bytes"] == 24 * n + 4 * total + 8 * 3
+    for cap, copied in ((int(offsets[1024]), int(offsets[1024])), (int(offsets[1024]) - 1, 0), (int(offsets[2048]), int(offsets[2048]))):
+        assert 0 < cap < total
+        rc, recs2, ops2, offsets2, needed = _host_raw(eng, reads, refs, cap, ops_len=total)
+        assert rc != 0 and needed == total and "ops_cap" in hipkernel._err(), cap
+        assert np.array_equal(recs2, recs) and np.array_equal(offsets2, offsets), cap
+        assert (ops2[cap:] == 0xDEADBEEF).all(), cap
+        assert eng.describe(0, n)["cigar_d2h_bytes"] == 24 * n + 4 * copied + 8 * 3, cap
+        rc, recs3, ops3, offsets3, needed = _host_raw(eng, reads, refs, total)
+        assert rc == 0 and needed == total and np.array_equal(ops3, ops) and np.array_equal(offsets3, offsets) and np.array_equal(recs3, recs), cap
+    eng.close()
 
 
 # ---- 8. refusals ----

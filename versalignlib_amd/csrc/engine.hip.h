@@ -769,12 +769,20 @@ private:
         const PlacedRec *fwd = nullptr;     // not null (the child engine of a spanned CIGAR call): the rows are those of the reversed
         int fwd_ref_length = 0;             // prefixes -- the backward encoder places them with these forward records of an R x fwd_ref_length pair
     };
+    // sets an engine's sink for the time of an alignment call and clears it when the call leaves, however it leaves
+    struct ScopedSink {
+        const CigarSink *&slot;
+        ScopedSink(const CigarSink *&s, const CigarSink *value) : slot(s) { slot = value; }
+        ~ScopedSink() { slot = nullptr; }
+    };
     // encode `cnt` pairs from pair `begin` of the call on `stream`: rows / idx / ends are those of pair `begin`
     void launch_cigar(hipStream_t stream, const uint8_t *rows, const short *idx, const EndCell *ends, long long begin, long long cnt);
-    void launch_cigar_args(hipStream_t stream, CigarArgs &a);
-    // The encoders' lane group per pair, for all three launch sites (here, engine_span_cigar.hip, engine_extend_align.hip): 16 lanes
-    // where an alignment is a few steps of 16 columns (short reads: ~160 columns at 150 x 500), a wave beyond that (DESIGN 3:
-    // measured).  Debug switch cigar_lanes forces one.  The answer is noted for describe() ("ran_cigar_lanes").
+    // cigar_encode_kernel over rows of `pitch` bytes (R + F behind an alignment's walk, R + F + 1 behind an extension's); any pass:
+    // the caller fills what this leaves open
+    void launch_cigar_args(hipStream_t stream, CigarArgs &a, int pitch);
+    // The encoders' lane group per pair, for every encoder launch (launch_encoder is the only caller): 16 lanes where an
+    // alignment is a few steps of 16 columns (short reads: ~160 columns at 150 x 500), a wave beyond that (measured).
+    // Debug switch cigar_lanes forces one.  The answer is noted for describe() ("ran_cigar_lanes").
     int take_cigar_lanes() {
         int lanes = std::min(R_, F_) <= 256 ? 16 : 64;
         const long long forced = dbg_.value("cigar_lanes", 0);
@@ -782,9 +790,77 @@ private:
         ran_cigar_lanes_ = lanes;
         return lanes;
     }
+    // the scoring fields CigarArgs and SpanCigarArgs carry under these names (ints, and the gap form beside them)
+    template <class A>
+    void put_cigar_scoring(A &a) const {
+        a.affine = sc_.affine ? 1 : 0;
+        a.match = sc_.match;
+        a.mismatch = sc_.mismatch;
+        a.gap_read = sc_.gap_read;
+        a.gap_ref = sc_.gap_ref;
+        a.open_read = sc_.open_read;
+        a.ext_read = sc_.ext_read;
+        a.open_ref = sc_.open_ref;
+        a.ext_ref = sc_.ext_ref;
+    }
+    // The one encoder launch: `a` with its rows, sinks, count and pitch set; the scoring, the lane group (k16 / k64: the kernel's
+    // two instances) and the grid are decided here.  `what` names the launch in an error.
+    template <class A>
+    void launch_encoder(hipStream_t stream, A &a, void (*k16)(const A), void (*k64)(const A), const char *what) {
+        put_cigar_scoring(a);
+        const int lanes = take_cigar_lanes();
+        const long long per_block = 256 / lanes;
+        const long long blocks = (a.n + per_block - 1) / per_block;
+        if (blocks > 0x7FFFFFFFll) throw std::runtime_error("batch too large for one launch");
+        hipLaunchKernelGGL(lanes == 16 ? k16 : k64, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+        hip_check(hipGetLastError(), what);
+    }
     void ensure_cigar_scratch(int slots, long long pairs, hipStream_t stream);
     // offsets[0 .. n] = exclusive scan of recs[p].n_ops on `stream` (cigar_scan_kernel)
     void launch_cigar_scan(const CigarRec *recs, long long *offsets, long long n, hipStream_t stream);
+
+    // ---- packed delivery (engine_cigar.hip): what the three *_host calls of the compact format do with a chunk, once ----
+    // The chunk's count-pass records and scanned offsets on the device, and records + extra records + ops as they cross PCIe
+    struct CigarPack {
+        DeviceBuffer<CigarRec> recs;
+        DeviceBuffer<long long> offsets;
+        DeviceBuffer<uint8_t> out;
+        PinnedBuffer<uint8_t> h_out;
+    };
+    // the argument checks of the entry points, before anything else is looked at (texts: include/valign_hip.h)
+    static void check_packed_device_args(int extended, int ops_stride, const void *d_recs, const void *d_ops);
+    static void check_packed_host_args(int extended, int n, const void *recs, const void *ops, long long ops_cap, const long long *offsets, const long long *ops_needed);
+    // pairs of one chunk of a host call before the caller's own bound: chunk_bytes of inputs + results, in whole rounds, at least 1024
+    long long packed_chunk_pairs(size_t chunk_bytes) const {
+        return std::max<long long>(whole_rounds((long long)(chunk_bytes / ((size_t)3 * (R_ + F_) + 8))), 1024);
+    }
+    // gather and H2D of the caller's BYTES on `stream`: the chunk lies in d_reads_ / d_refs_[slot].  Not stage_chunk, which sends
+    // 4-bit classes under host_packing: alignments report the caller's bytes.
+    void stage_raw_chunk(int slot, hipStream_t stream, const char *const *reads, const char *const *refs, long long cnt, int threads);
+    // behind a chunk's count pass (records only, into pack.recs) on `stream`: the scan and the op total on its way to *h_total_slot
+    void finish_count_pass(CigarPack &pack, long long cnt, long long *h_total_slot, hipStream_t stream);
+    // With the chunk's total known: the packed buffers grown to `layout`, the emit pass where the ops still fit --
+    // fill_and_launch(ops, recs_out) launches the encoder at pack.offsets, which also copies pack.recs to recs_out --, d_extra (null:
+    // none) between them, and ONE copy to pack.h_out on `stream`.  Records alone are copied straight from pack.recs.
+    using EmitLaunch = std::function<void(unsigned *ops, CigarRec *recs_out)>;
+    void emit_packed(CigarPack &pack, const PackedLayout &layout, const EmitLaunch &fill_and_launch, const void *d_extra, hipStream_t stream);
+    // what every emit pass's args share: A = CigarArgs / SpanCigarArgs
+    template <class A>
+    A emit_args(const CigarPack &pack, const uint8_t *rows, const short *idx, long long cnt, int extended, unsigned *ops, CigarRec *recs_out) const {
+        A a{};
+        a.rows = rows;
+        a.idx = idx;
+        a.ops = ops;
+        a.offsets = pack.offsets.get();
+        a.recs_in = pack.recs.get();
+        a.recs_out = recs_out;
+        a.n = cnt;
+        a.extended = extended;
+        return a;
+    }
+    // pack.h_out (its copy waited for) -> the caller's arrays (HostPacker::unpack_packed), timed as the drain phase
+    void drain_packed(const CigarPack &pack, const PackedLayout &layout, long long begin, CigarRec *recs, void *extra, unsigned *ops, long long *offsets,
+                      int threads);
 
     // gather / scatter between the caller's scattered blocks and the staging: host_pipeline.h (host-only, sanitizer-tested)
     template <typename Sink>
@@ -836,16 +912,13 @@ private:
 
     // ---- spanned CIGARs (engine_span_cigar.hip) ----
     // One context for host-pointer calls and one for device-resident calls: the reversed prefixes, the forward records and the
-    // child's rows / idx of one chunk; host path: the count pass's records, the scanned offsets, records + ops as they cross PCIe
+    // child's rows / idx of one chunk; host path: the chunk's pack and its op total
     struct SpanCigarCtx {
         long long cap = 0;                     // pairs the buffers hold
         DeviceBuffer<uint8_t> rev_reads, rev_refs, rows;
         DeviceBuffer<PlacedRec> fwd;
         DeviceBuffer<short> idx;
-        DeviceBuffer<CigarRec> recs;
-        DeviceBuffer<long long> offsets;
-        DeviceBuffer<uint8_t> out;
-        PinnedBuffer<uint8_t> h_out;
+        CigarPack pack;
         PinnedBuffer<long long> h_total;
         size_t bytes() const { return rev_reads.bytes() + rev_refs.bytes() + rows.bytes() + fwd.bytes() + idx.bytes(); }
     };
@@ -855,7 +928,8 @@ private:
     void ensure_span_cigar_scratch(int c, long long pairs, bool host, hipStream_t stream);
     // one chunk, all of it on `stream`: forward sweep, reversal, the child's alignment with `sink` behind its walk
     void span_cigar_chunk(int c, int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, const CigarSink &sink, hipStream_t stream);
-    // (of the child) encode `cnt` pairs from pair `begin` of the call behind their walk, or, with filled args, any pass
+    // (of the child) encode `cnt` pairs from pair `begin` of the call behind their walk, or, with filled args, any pass:
+    // span_cigar_encode_kernel through launch_encoder
     void launch_span_cigar(hipStream_t stream, const uint8_t *rows, const short *idx, long long begin, long long cnt);
     void launch_span_cigar_args(hipStream_t stream, SpanCigarArgs &a);
 
@@ -889,8 +963,6 @@ private:
     // one chunk, all of it on `stream`: fill, walk, encoder (records at recs, ops at ops where not null)
     void extend_align_chunk(const LaunchPlan &plan, const ExtendAlignChoice &choice, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int end_bonus,
                             int extended, CigarRec *recs, unsigned *ops, int ops_stride, ExtendRec *d_extend, int slot, hipStream_t stream);
-    // the encoder over the walk's rows (any pass: the caller fills what launch_cigar_args leaves open)
-    void launch_extend_align_cigar(hipStream_t stream, CigarArgs &a);
     // the scratch of a chunk of `pairs` pairs: the walk's rows, the pointer scratch and end cells and, on the Band route, the
     // boundary rows, partial records and trimmed lengths in the strip scratch extension scores use
     void ensure_extend_align_scratch(const LaunchPlan &plan, const ExtendAlignChoice &choice, long long pairs, hipStream_t stream);
@@ -1093,14 +1165,11 @@ private:
     DeviceBuffer<uint8_t> d_rows_[kSlots];
     DeviceBuffer<short> d_idx_[kSlots];
     DeviceBuffer<uint8_t> d_packed_rows_[kSlots];                // the chunk's rows without their all-zero leading columns
-    // compact result format: the rows the walks write (never copied out), per chunk parity; host path: count-pass records,
-    // scanned offsets, the packed records + ops as they cross PCIe
+    // compact result format: the rows the walks write (never copied out), per chunk parity; host path: each parity's pack and
+    // the two op totals
     DeviceBuffer<uint8_t> d_cig_rows_[2];
     DeviceBuffer<short> d_cig_idx_[2];
-    DeviceBuffer<CigarRec> d_cig_recs_[2];
-    DeviceBuffer<long long> d_cig_offsets_[2];
-    DeviceBuffer<uint8_t> d_cig_out_[2];
-    PinnedBuffer<uint8_t> h_cig_out_[2];
+    CigarPack cig_pack_[2];
     PinnedBuffer<long long> h_cig_total_;
     DeviceBuffer<ExtendRec> d_extend_align_recs_;                // extension alignments, host path: the chunk's extension records before they join the packed copy
     DeviceBuffer<int> d_min_start_;                              // per slot: first column of the chunk's rows that holds a string

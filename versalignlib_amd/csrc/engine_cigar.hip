@@ -1,38 +1,18 @@
 // engine_cigar.hip -- Engine: the compact result format (include/valign_hip.h: valign_hip_aln records + 32-bit CIGAR ops).
 // The alignment paths of engine_align.hip run unchanged into an engine-owned rows scratch; cigar_encode_kernel
 // (cigar_kernels.hip.h) reads each part's rows behind its walk.  The rows never cross PCIe.
+// Also here, once, for align_cigar_host and for the host calls of engine_span_cigar.hip and engine_extend_align.hip: the
+// packed delivery of a chunk -- argument checks, raw staging, scan and op total, the emit pass, ONE copy back, unpacking (its
+// pure half: PackedLayout, OpsBudget and HostPacker::unpack_packed of host_pipeline.h) -- and the one launch of cigar_encode_kernel,
+// at the caller's row pitch.
 #define VALIGN_TU_CIGAR 1
 #include "engine.hip.h"
 
 namespace valign {
 
-namespace {
-// clears Engine::cigar_ when the call leaves, however it leaves
-template <class T>
-struct ScopedSink {
-    const T *&slot;
-    ScopedSink(const T *&s, const T *value) : slot(s) { slot = value; }
-    ~ScopedSink() { slot = nullptr; }
-};
-}  // namespace
-
-void Engine::launch_cigar_args(hipStream_t stream, CigarArgs &a) {
-    a.AL = R_ + F_;
-    a.affine = sc_.affine ? 1 : 0;
-    a.match = sc_.match;
-    a.mismatch = sc_.mismatch;
-    a.gap_read = sc_.gap_read;
-    a.gap_ref = sc_.gap_ref;
-    a.open_read = sc_.open_read;
-    a.ext_read = sc_.ext_read;
-    a.open_ref = sc_.open_ref;
-    a.ext_ref = sc_.ext_ref;
-    const int lanes = take_cigar_lanes();
-    const long long per_block = 256 / lanes;
-    const dim3 grid((unsigned)((a.n + per_block - 1) / per_block)), block(256);
-    if (lanes == 16) hipLaunchKernelGGL(cigar_encode_kernel<16>, grid, block, 0, stream, a);
-    else hipLaunchKernelGGL(cigar_encode_kernel<64>, grid, block, 0, stream, a);
-    hip_check(hipGetLastError(), "hipLaunchKernel(cigar_encode_kernel)");
+void Engine::launch_cigar_args(hipStream_t stream, CigarArgs &a, int pitch) {
+    a.AL = pitch;
+    launch_encoder(stream, a, cigar_encode_kernel<16>, cigar_encode_kernel<64>, "hipLaunchKernel(cigar_encode_kernel)");
 }
 
 void Engine::launch_cigar(hipStream_t stream, const uint8_t *rows, const short *idx, const EndCell *ends, long long begin, long long cnt) {
@@ -50,7 +30,7 @@ void Engine::launch_cigar(hipStream_t stream, const uint8_t *rows, const short *
     a.ops_stride = cigar_->ops_stride;
     a.n = cnt;
     a.extended = cigar_->extended;
-    launch_cigar_args(stream, a);
+    launch_cigar_args(stream, a, R_ + F_);
 }
 
 void Engine::launch_cigar_scan(const CigarRec *recs, long long *offsets, long long n, hipStream_t stream) {
@@ -67,19 +47,73 @@ void Engine::ensure_cigar_scratch(int slots, long long pairs, hipStream_t stream
         cigar_pairs_[s] = 0;
         d_cig_rows_[s].reserve((size_t)pairs * 2 * AL + 64, "alignment rows (compact results)");
         d_cig_idx_[s].reserve(sizeof(short) * 4 * (size_t)pairs, "alignment coordinates (compact results)");
-        d_cig_recs_[s].reserve(sizeof(CigarRec) * (size_t)pairs, "alignment records");
-        d_cig_offsets_[s].reserve(sizeof(long long) * ((size_t)pairs + 1), "op offsets");
+        cig_pack_[s].recs.reserve(sizeof(CigarRec) * (size_t)pairs, "alignment records");
+        cig_pack_[s].offsets.reserve(sizeof(long long) * ((size_t)pairs + 1), "op offsets");
         cigar_pairs_[s] = pairs;
     }
     h_cig_total_.reserve(sizeof(long long) * 2, "op totals");
 }
 
-void Engine::align_cigar_device(int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int extended, CigarRec *d_recs,
-                                unsigned *d_ops, int ops_stride, hipStream_t stream) {
-    ran_cigar_lanes_ = 0;                   // (a refused call reports no encoder)
+// ---- packed delivery: the steps of a chunk that align_cigar_host, align_span_host and align_extend_host share ----
+
+void Engine::check_packed_device_args(int extended, int ops_stride, const void *d_recs, const void *d_ops) {
     if (extended != 0 && extended != 1) throw std::runtime_error("extended must be 0 (M) or 1 (= / X)");
     if (ops_stride < 1) throw std::runtime_error("ops_stride must be >= 1");
     if (!d_recs || !d_ops) throw std::runtime_error("null result buffer");
+}
+
+void Engine::check_packed_host_args(int extended, int n, const void *recs, const void *ops, long long ops_cap, const long long *offsets,
+                                    const long long *ops_needed) {
+    if (extended != 0 && extended != 1) throw std::runtime_error("extended must be 0 (M) or 1 (= / X)");
+    if (!recs || !offsets || !ops_needed || (!ops && ops_cap > 0)) throw std::runtime_error("null result buffer");
+    if (n < 0 || ops_cap < 0) throw std::runtime_error("negative size");
+}
+
+void Engine::stage_raw_chunk(int slot, hipStream_t stream, const char *const *reads, const char *const *refs, long long cnt, int threads) {
+    uint8_t *h_reads = h_reads_[slot].get(), *h_refs = h_refs_[slot].get();
+    auto t0 = std::chrono::steady_clock::now();
+    gather(reads, refs, cnt, h_reads, h_refs, threads);
+    host_stats_.gather_ms += ms_between(t0, std::chrono::steady_clock::now());
+    hip_check(hipMemcpyAsync(d_reads_[slot].get(), h_reads, (size_t)cnt * R_, hipMemcpyHostToDevice, stream), "H2D reads");
+    hip_check(hipMemcpyAsync(d_refs_[slot].get(), h_refs, (size_t)cnt * F_, hipMemcpyHostToDevice, stream), "H2D refs");
+}
+
+void Engine::finish_count_pass(CigarPack &pack, long long cnt, long long *h_total_slot, hipStream_t stream) {
+    launch_cigar_scan(pack.recs.get(), pack.offsets.get(), cnt, stream);
+    hip_check(hipMemcpyAsync(h_total_slot, pack.offsets.get() + cnt, sizeof(long long), hipMemcpyDeviceToHost, stream), "D2H op total");
+}
+
+void Engine::emit_packed(CigarPack &pack, const PackedLayout &layout, const EmitLaunch &fill_and_launch, const void *d_extra, hipStream_t stream) {
+    const size_t bytes = layout.bytes();
+    if (bytes > pack.h_out.bytes()) {                     // (the last copy out of it was waited for before the pack was reused)
+        pack.h_out.reserve(bytes + bytes / 4, "packed alignment results");
+        pack.out.reserve(bytes + bytes / 4, "packed alignment results");
+    }
+    uint8_t *out = pack.out.get();
+    const uint8_t *src = reinterpret_cast<const uint8_t *>(pack.recs.get());
+    if (layout.with_ops) {                              // emit pass: the ops at their offsets, the records in front
+        fill_and_launch(reinterpret_cast<unsigned *>(out + layout.ops_at()), reinterpret_cast<CigarRec *>(out));
+        src = out;
+    } else if (d_extra) {
+        hip_check(hipMemcpyAsync(out, pack.recs.get(), layout.rec_bytes, hipMemcpyDeviceToDevice, stream), "D2D records");
+        src = out;
+    }
+    if (d_extra) hip_check(hipMemcpyAsync(out + layout.rec_bytes, d_extra, layout.extra_bytes, hipMemcpyDeviceToDevice, stream), "D2D extra records");
+    hip_check(hipMemcpyAsync(pack.h_out.get(), src, bytes, hipMemcpyDeviceToHost, stream), "D2H records + ops");
+    cigar_d2h_bytes_ += (long long)(bytes + sizeof(long long));
+}
+
+void Engine::drain_packed(const CigarPack &pack, const PackedLayout &layout, long long begin, CigarRec *recs, void *extra, unsigned *ops, long long *offsets,
+                          int threads) {
+    auto t0 = std::chrono::steady_clock::now();
+    packer_.unpack_packed(layout, pack.h_out.get(), begin, recs, extra, ops, offsets, threads);
+    host_stats_.drain_ms += ms_between(t0, std::chrono::steady_clock::now());
+}
+
+void Engine::align_cigar_device(int opt, long long n, const uint8_t *d_reads, const uint8_t *d_refs, int extended, CigarRec *d_recs,
+                                unsigned *d_ops, int ops_stride, hipStream_t stream) {
+    ran_cigar_lanes_ = 0;                   // (a refused call reports no encoder)
+    check_packed_device_args(extended, ops_stride, d_recs, d_ops);
     const int alg = opt & 0xF;
     if (alg > 1 || n <= 0) return;
     hip_check(hipSetDevice(device_), "hipSetDevice");
@@ -90,17 +124,18 @@ void Engine::align_cigar_device(int opt, long long n, const uint8_t *d_reads, co
     for (long long begin = 0; begin < n; begin += chunk) {
         const long long cnt = std::min(chunk, n - begin);
         const CigarSink sink{d_recs + begin, d_ops + (size_t)begin * ops_stride, ops_stride, extended};
-        ScopedSink<CigarSink> scoped(cigar_, &sink);
+        ScopedSink scoped(cigar_, &sink);
         align_device(opt, cnt, d_reads + (size_t)begin * R_, d_refs + (size_t)begin * F_, d_cig_rows_[0].get(), d_cig_idx_[0].get(), stream);
     }
 }
 
+// Host pointers in, packed results out, on the two-slot pipeline of align_host: the fill of chunk c + 1 (kernels stream) beside
+// the emit pass and the copy back of chunk c (copy_out stream) and the drain of chunk c - 1.  The steps inside a chunk are the
+// shared ones above; this schedule is this call's own.
 bool Engine::align_cigar_host(int opt, int n, const char *const *reads, const char *const *refs, int extended, CigarRec *recs,
                               unsigned *ops, long long ops_cap, long long *offsets, long long *ops_needed, int threads) {
     ran_cigar_lanes_ = 0;
-    if (extended != 0 && extended != 1) throw std::runtime_error("extended must be 0 (M) or 1 (= / X)");
-    if (!recs || !offsets || !ops_needed || (!ops && ops_cap > 0)) throw std::runtime_error("null result buffer");
-    if (n < 0 || ops_cap < 0) throw std::runtime_error("negative size");
+    check_packed_host_args(extended, n, recs, ops, ops_cap, offsets, ops_needed);
     const int alg = opt & 0xF;
     if (alg > 1) return true;                       // (the same silent no-op as every entry point)
     offsets[0] = 0;
@@ -113,15 +148,12 @@ bool Engine::align_cigar_host(int opt, int n, const char *const *reads, const ch
     ran_align_geo_ = nullptr;
     ran_result_format_ = "cigar";           // (before the refusals: a refused call must not report the format of an earlier one)
     const int AL = R_ + F_;
-    const size_t per_pair = (size_t)3 * AL + 8;                 // (the chunks of align_host: same launches, same rounds)
     const RouteFacts facts = route_facts(true);
     const AlignRoute route = valign::align_route(rule_inputs(), alg, facts);       // (refusals leave here)
     const bool by_strips = strip_chunks(route, facts);
+    // (the chunks of align_host: same launches, same rounds)
     const size_t chunk_bytes = by_strips && !dbg_.on("align_chunk_bytes") ? std::max<size_t>(align_chunk_bytes_, 384u << 20) : align_chunk_bytes_;
-    long long chunk = (long long)(chunk_bytes / per_pair);
-    chunk = whole_rounds(chunk);
-    chunk = std::max<long long>(chunk, 1024);
-    chunk = std::min<long long>(chunk, n);
+    const long long chunk = std::min<long long>(packed_chunk_pairs(chunk_bytes), n);
     reset_pipeline();
     ensure_staging(chunk);
     threads = std::min(std::max(threads, 1), 64);
@@ -141,10 +173,11 @@ bool Engine::align_cigar_host(int opt, int n, const char *const *reads, const ch
         }
     } quiesce{this};
     struct Pending {
-        long long begin = 0, cnt = 0, total = 0;
-        bool active = false, with_ops = false;
+        long long begin = 0, cnt = 0;
+        bool active = false;
+        PackedLayout layout;
     } pend[2];
-    long long total_ops = 0;
+    OpsBudget budget{ops_cap};
     // Chunk in slot s: its records and scanned offsets are on the device and its op total is on its way.  Size the packed
     // output, emit the ops beside the records (copy_out stream: beside the next chunk's fill) and start ONE copy back.
     auto emit = [&](int s) {
@@ -152,55 +185,21 @@ bool Engine::align_cigar_host(int opt, int n, const char *const *reads, const ch
         auto t0 = std::chrono::steady_clock::now();
         hip_check(hipEventSynchronize(kernels_done_[s].get()), "hipEventSynchronize");
         host_stats_.wait_ms += ms_between(t0, std::chrono::steady_clock::now());
-        p.total = h_cig_total_.get()[s];
-        total_ops += p.total;
-        p.with_ops = total_ops <= ops_cap;
-        const size_t rec_bytes = sizeof(CigarRec) * (size_t)p.cnt, bytes = rec_bytes + (p.with_ops ? sizeof(unsigned) * (size_t)p.total : 0);
-        if (bytes > h_cig_out_[s].bytes()) {                     // (the slot's last copy was drained before the slot was reused)
-            h_cig_out_[s].reserve(bytes + bytes / 4, "packed alignment results");
-            d_cig_out_[s].reserve(bytes + bytes / 4, "packed alignment results");
-        }
-        const uint8_t *src = reinterpret_cast<const uint8_t *>(d_cig_recs_[s].get());
-        if (p.with_ops) {
-            CigarArgs a{};
-            a.rows = d_cig_rows_[s].get();
-            a.idx = d_cig_idx_[s].get();
-            a.ops = reinterpret_cast<unsigned *>(d_cig_out_[s].get() + rec_bytes);
-            a.offsets = d_cig_offsets_[s].get();
-            a.recs_in = d_cig_recs_[s].get();
-            a.recs_out = reinterpret_cast<CigarRec *>(d_cig_out_[s].get());
-            a.n = p.cnt;
-            a.extended = extended;
-            launch_cigar_args(copy_out, a);
-            src = d_cig_out_[s].get();
-        }
-        hip_check(hipMemcpyAsync(h_cig_out_[s].get(), src, bytes, hipMemcpyDeviceToHost, copy_out), "D2H records + ops");
+        const long long total = h_cig_total_.get()[s];
+        p.layout = PackedLayout(p.cnt, 0, total, budget.add(total));
+        emit_packed(cig_pack_[s], p.layout, [&](unsigned *d_ops, CigarRec *recs_out) {
+            CigarArgs a = emit_args<CigarArgs>(cig_pack_[s], d_cig_rows_[s].get(), d_cig_idx_[s].get(), p.cnt, extended, d_ops, recs_out);
+            launch_cigar_args(copy_out, a, AL);
+        }, nullptr, copy_out);
         hip_check(hipEventRecord(slot_done_[s].get(), copy_out), "hipEventRecord");
-        cigar_d2h_bytes_ += (long long)(bytes + sizeof(long long));
     };
     auto drain = [&](int s) {
         Pending &p = pend[s];
         if (!p.active) return;
         auto t0 = std::chrono::steady_clock::now();
         hip_check(hipEventSynchronize(slot_done_[s].get()), "hipEventSynchronize");
-        auto t1 = std::chrono::steady_clock::now();
-        const uint8_t *h = h_cig_out_[s].get();
-        const CigarRec *h_recs = reinterpret_cast<const CigarRec *>(h);
-        for_ranges(threads, p.cnt, 4096, [&](int, long long lo, long long hi) {
-            memcpy(recs + p.begin + lo, h_recs + lo, sizeof(CigarRec) * (size_t)(hi - lo));
-        });
-        long long at = offsets[p.begin];
-        for (long long i = 0; i < p.cnt; ++i) {                  // offsets follow from n_ops: rebased on the host
-            at += h_recs[i].n_ops;
-            offsets[p.begin + i + 1] = at;
-        }
-        if (p.with_ops && p.total > 0) {
-            unsigned *to = ops + offsets[p.begin];
-            const unsigned *from = reinterpret_cast<const unsigned *>(h + sizeof(CigarRec) * (size_t)p.cnt);
-            for_ranges(threads, p.total, 1 << 16, [&](int, long long lo, long long hi) { memcpy(to + lo, from + lo, sizeof(unsigned) * (size_t)(hi - lo)); });
-        }
-        host_stats_.wait_ms += ms_between(t0, t1);
-        host_stats_.drain_ms += ms_between(t1, std::chrono::steady_clock::now());
+        host_stats_.wait_ms += ms_between(t0, std::chrono::steady_clock::now());
+        drain_packed(cig_pack_[s], p.layout, p.begin, recs, nullptr, ops, offsets, threads);
         p.active = false;
     };
     long long chunk_no = 0;
@@ -208,28 +207,23 @@ bool Engine::align_cigar_host(int opt, int n, const char *const *reads, const ch
         const int s = (int)(chunk_no & 1);
         const long long cnt = std::min<long long>(chunk, n - begin);
         drain(s);                                    // chunk c - 2: its rows, inputs and staging are free after this
-        uint8_t *h_reads = h_reads_[s].get(), *h_refs = h_refs_[s].get(), *d_reads = d_reads_[s].get(), *d_refs = d_refs_[s].get();
-        auto t0 = std::chrono::steady_clock::now();
-        gather(reads + begin, refs + begin, cnt, h_reads, h_refs, threads);
-        host_stats_.gather_ms += ms_between(t0, std::chrono::steady_clock::now());
-        hip_check(hipMemcpyAsync(d_reads, h_reads, (size_t)cnt * R_, hipMemcpyHostToDevice, copy_in), "H2D reads");
-        hip_check(hipMemcpyAsync(d_refs, h_refs, (size_t)cnt * F_, hipMemcpyHostToDevice, copy_in), "H2D refs");
+        stage_raw_chunk(s, copy_in, reads + begin, refs + begin, cnt, threads);
         hip_check(hipEventRecord(in_done_[s].get(), copy_in), "hipEventRecord");
         hip_check(hipStreamWaitEvent(kernels, in_done_[s].get(), 0), "hipStreamWaitEvent");
+        const uint8_t *d_reads = d_reads_[s].get(), *d_refs = d_refs_[s].get();
         // records only: the ops wait for the chunk's scan.  The walk (and the encoder behind it) of this chunk runs on the
         // helper stream beside the fill of the next one, as in align_host.
-        const CigarSink sink{d_cig_recs_[s].get(), nullptr, 1, extended};
+        const CigarSink sink{cig_pack_[s].recs.get(), nullptr, 1, extended};
         bool chained = false;
         {
-            ScopedSink<CigarSink> scoped(cigar_, &sink);
+            ScopedSink scoped(cigar_, &sink);
             if (!(small && route == AlignRoute::Fused && align_fused(alg, cnt, d_reads, d_refs, d_cig_rows_[s].get(), d_cig_idx_[s].get(), kernels))) {
                 const WalkChain chain{s, chunk, nullptr, nullptr};
                 chained = align_device(opt, cnt, d_reads, d_refs, d_cig_rows_[s].get(), d_cig_idx_[s].get(), kernels, &chain);
             }
         }
         hipStream_t tail = chained ? trace_stream_.get() : kernels;
-        launch_cigar_scan(d_cig_recs_[s].get(), d_cig_offsets_[s].get(), cnt, tail);
-        hip_check(hipMemcpyAsync(h_cig_total_.get() + s, d_cig_offsets_[s].get() + cnt, sizeof(long long), hipMemcpyDeviceToHost, tail), "D2H op total");
+        finish_count_pass(cig_pack_[s], cnt, h_cig_total_.get() + s, tail);
         hip_check(hipEventRecord(kernels_done_[s].get(), tail), "hipEventRecord");
         pend[s].begin = begin;
         pend[s].cnt = cnt;
@@ -241,8 +235,9 @@ bool Engine::align_cigar_host(int opt, int n, const char *const *reads, const ch
     drain(last ^ 1);
     drain(last);
     quiesce.armed = false;
-    *ops_needed = total_ops;
-    return total_ops <= ops_cap;
+    *ops_needed = budget.total;
+    return budget.fits();
 }
 
 }  // namespace valign
+

@@ -2,13 +2,14 @@
 // from the anchor before read[0] and ref[0] to the end cell the end-bonus rule picks, as a valign_hip_aln record and CIGAR ops, and
 // the pair's extension record where asked for.  extend_align_choice (cell_rules.h) decides what is refused; a chunk runs
 // align_extend_fill_kernel (extend_align_kernels.hip.h) into the pointer scratch alignments use, extend_walk_kernel into the CIGAR
-// rows scratch at a row pitch of R + F + 1, and cigar_encode_kernel behind it.  extend_walk_kernel (not a template) is defined in
-// this translation unit.
+// rows scratch at a row pitch of R + F + 1, and cigar_encode_kernel behind it (launch_cigar_args of engine_cigar.hip, at that pitch).
+// extend_walk_kernel (not a template) is defined in this translation unit.
 // Where the rule answers Band (extend_band_align = 1 under a band with extend_band = 1) a chunk is extend_band_align_chunk: the
 // lengths pre-pass and the boundary rows of banded extension scores (extend_band_sweep, engine_extend.hip), one launch of
 // align_extend_band_fill_kernel per strip into the same pointer scratch, extend_band_ends_kernel, extend_band_walk_kernel and the
 // encoder (extend_band_align_kernels.hip.h; its two fill instances and the two other kernels are defined here).  Chunk sizes, the
-// scratch and both entry points are shared: only the chunk body differs.
+// scratch and both entry points are shared: only the chunk body differs.  The host entry delivers through the packed path of
+// engine_cigar.hip, the extension records between the records and the ops.
 #define VALIGN_TU_EXTEND_ALIGN 1
 #include "engine.hip.h"
 #include "extend_band_align_kernels.hip.h"
@@ -134,30 +135,9 @@ void Engine::extend_band_align_chunk(const ExtendAlignChoice &choice, long long 
     a.ops_stride = ops_stride;
     a.n = n;
     a.extended = extended;
-    launch_extend_align_cigar(stream, a);
+    launch_cigar_args(stream, a, t.pitch);
     ran_extend_align_ = ran_placed_name(kPlacedRouteBand);
     align_ptr_bytes_per_pair_ = choice.wave_ptr_bytes / 2;
-}
-
-void Engine::launch_extend_align_cigar(hipStream_t stream, CigarArgs &a) {
-    a.AL = R_ + F_ + 1;                 // the walk's row pitch
-    a.affine = sc_.affine ? 1 : 0;
-    a.match = sc_.match;
-    a.mismatch = sc_.mismatch;
-    a.gap_read = sc_.gap_read;
-    a.gap_ref = sc_.gap_ref;
-    a.open_read = sc_.open_read;
-    a.ext_read = sc_.ext_read;
-    a.open_ref = sc_.open_ref;
-    a.ext_ref = sc_.ext_ref;
-    const int lanes = take_cigar_lanes();
-    const long long per_block = 256 / lanes;
-    const long long blocks = (a.n + per_block - 1) / per_block;
-    if (blocks > 0x7FFFFFFFll) throw std::runtime_error("batch too large for one launch");
-    const dim3 grid((unsigned)blocks), block(256);
-    if (lanes == 16) hipLaunchKernelGGL(cigar_encode_kernel<16>, grid, block, 0, stream, a);
-    else hipLaunchKernelGGL(cigar_encode_kernel<64>, grid, block, 0, stream, a);
-    hip_check(hipGetLastError(), "hipLaunchKernel(cigar_encode_kernel)");
 }
 
 void Engine::extend_align_chunk(const LaunchPlan &plan, const ExtendAlignChoice &choice, long long n, const uint8_t *d_reads, const uint8_t *d_refs,
@@ -219,7 +199,7 @@ void Engine::extend_align_chunk(const LaunchPlan &plan, const ExtendAlignChoice 
     a.ops_stride = ops_stride;
     a.n = n;
     a.extended = extended;
-    launch_extend_align_cigar(stream, a);
+    launch_cigar_args(stream, a, t.pitch);
     ran_extend_align_ = ran_placed_name(PlacedRoute::Rows);
     align_ptr_bytes_per_pair_ = choice.wave_ptr_bytes / ppw;           // (the call's own, as on the Band route: not the last other alignment's)
 }
@@ -230,9 +210,7 @@ void Engine::align_extend_device(int opt, long long n, const uint8_t *d_reads, c
     ran_extend_align_geo_ = nullptr;
     ran_extend_align_chunks_ = 0;
     ran_cigar_lanes_ = 0;
-    if (extended != 0 && extended != 1) throw std::runtime_error("extended must be 0 (M) or 1 (= / X)");
-    if (ops_stride < 1) throw std::runtime_error("ops_stride must be >= 1");
-    if (!d_recs || !d_ops) throw std::runtime_error("null result buffer");
+    check_packed_device_args(extended, ops_stride, d_recs, d_ops);
     const int alg = opt & 0xF;
     if (alg > 1 || n <= 0) return;          // reference: unsupported mode is a silent no-op
     ExtendAlignChoice choice;
@@ -247,18 +225,17 @@ void Engine::align_extend_device(int opt, long long n, const uint8_t *d_reads, c
                            d_recs + begin, d_ops + (size_t)begin * ops_stride, ops_stride, d_extend ? d_extend + begin : nullptr, 0, stream);
 }
 
-// Host pointers in, packed results out.  Chunk after chunk on streams_[0], each waited for: gather, H2D, the chunk above with a
-// records-only sink (count pass), the scan of n_ops, the op total to the host, the emit pass at the scanned offsets beside the
-// records (and, where asked for, the extension records between them), ONE copy back.
+// Host pointers in, packed results out.  Chunk after chunk on streams_[0], each waited for: the raw staging, the chunk above with
+// a records-only sink (count pass), then the packed delivery of engine_cigar.hip -- scan, op total, emit pass at the scanned
+// offsets beside the records (and, where asked for, the extension records between them), ONE copy back, unpacking -- with the
+// encoder at the walk's row pitch as the emit pass.
 bool Engine::align_extend_host(int opt, int n, const char *const *reads, const char *const *refs, int end_bonus, int extended, CigarRec *recs,
                                unsigned *ops, long long ops_cap, long long *offsets, long long *ops_needed, ExtendRec *extend, int threads) {
     ran_extend_align_ = "none";
     ran_extend_align_geo_ = nullptr;
     ran_extend_align_chunks_ = 0;
     ran_cigar_lanes_ = 0;
-    if (extended != 0 && extended != 1) throw std::runtime_error("extended must be 0 (M) or 1 (= / X)");
-    if (!recs || !offsets || !ops_needed || (!ops && ops_cap > 0)) throw std::runtime_error("null result buffer");
-    if (n < 0 || ops_cap < 0) throw std::runtime_error("negative size");
+    check_packed_host_args(extended, n, recs, ops, ops_cap, offsets, ops_needed);
     const int alg = opt & 0xF;
     if (alg > 1) return true;                       // (the same silent no-op as every entry point)
     offsets[0] = 0;
@@ -270,9 +247,9 @@ bool Engine::align_extend_host(int opt, int n, const char *const *reads, const c
     const LaunchPlan &plan = extend_align_plan_for(alg, choice);        // (refusals leave here, before anything is staged)
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ran_result_format_ = "cigar";
-    const size_t per_pair = (size_t)3 * (R_ + F_) + 8;         // (the chunks of align_cigar_host)
-    long long chunk = std::max<long long>(whole_rounds((long long)(align_chunk_bytes_ / per_pair)), 1024);
-    chunk = std::min<long long>(chunk, extend_align_chunk_pairs(plan, choice, n, (size_t)std::max<long long>(1, dbg_.value("cigar_rows_mb", 512)) << 20));
+    // (the chunks of align_cigar_host, inside the bounds of the pointer and rows scratch)
+    long long chunk = std::min<long long>(packed_chunk_pairs(align_chunk_bytes_),
+                                          extend_align_chunk_pairs(plan, choice, n, (size_t)std::max<long long>(1, dbg_.value("cigar_rows_mb", 512)) << 20));
     if (choice.route == kPlacedRouteBand && chunk < n) chunk = std::max<long long>(2, chunk / 2 * 2);       // whole waves
     reset_pipeline();
     ensure_staging(chunk);
@@ -280,6 +257,8 @@ bool Engine::align_extend_host(int opt, int n, const char *const *reads, const c
     hipStream_t st = streams_[0].get();
     ensure_extend_align_scratch(plan, choice, chunk, st);
     if (extend) d_extend_align_recs_.reserve(sizeof(ExtendRec) * (size_t)chunk, "extension records");
+    ExtendRec *d_extend = extend ? d_extend_align_recs_.get() : nullptr;
+    CigarPack &pack = cig_pack_[0];
     host_stats_ = HostStats{};
     struct Quiesce {            // an error part-way leaves nothing in flight
         hipStream_t st;
@@ -288,73 +267,31 @@ bool Engine::align_extend_host(int opt, int n, const char *const *reads, const c
             if (armed) (void)hipStreamSynchronize(st);
         }
     } quiesce{st};
-    long long total_ops = 0;
-    for (long long begin = 0; begin < n; begin += chunk) {
-        const long long cnt = std::min<long long>(chunk, n - begin);
-        uint8_t *h_reads = h_reads_[0].get(), *h_refs = h_refs_[0].get(), *d_reads = d_reads_[0].get(), *d_refs = d_refs_[0].get();
+    auto wait = [&] {
         auto t0 = std::chrono::steady_clock::now();
-        gather(reads + begin, refs + begin, cnt, h_reads, h_refs, threads);
-        host_stats_.gather_ms += ms_between(t0, std::chrono::steady_clock::now());
-        hip_check(hipMemcpyAsync(d_reads, h_reads, (size_t)cnt * R_, hipMemcpyHostToDevice, st), "H2D reads");
-        hip_check(hipMemcpyAsync(d_refs, h_refs, (size_t)cnt * F_, hipMemcpyHostToDevice, st), "H2D refs");
-        // records only: the ops wait for the chunk's scan
-        extend_align_chunk(plan, choice, cnt, d_reads, d_refs, end_bonus, extended, d_cig_recs_[0].get(), nullptr, 1,
-                           extend ? d_extend_align_recs_.get() : nullptr, 0, st);
-        launch_cigar_scan(d_cig_recs_[0].get(), d_cig_offsets_[0].get(), cnt, st);
-        hip_check(hipMemcpyAsync(h_cig_total_.get(), d_cig_offsets_[0].get() + cnt, sizeof(long long), hipMemcpyDeviceToHost, st), "D2H op total");
-        t0 = std::chrono::steady_clock::now();
         hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
         host_stats_.wait_ms += ms_between(t0, std::chrono::steady_clock::now());
+    };
+    OpsBudget budget{ops_cap};
+    for (long long begin = 0; begin < n; begin += chunk) {
+        const long long cnt = std::min<long long>(chunk, n - begin);
+        stage_raw_chunk(0, st, reads + begin, refs + begin, cnt, threads);
+        // records only: the ops wait for the chunk's scan
+        extend_align_chunk(plan, choice, cnt, d_reads_[0].get(), d_refs_[0].get(), end_bonus, extended, pack.recs.get(), nullptr, 1, d_extend, 0, st);
+        finish_count_pass(pack, cnt, h_cig_total_.get(), st);
+        wait();
         const long long total = h_cig_total_.get()[0];
-        total_ops += total;
-        const bool with_ops = total_ops <= ops_cap;
-        const size_t rec_bytes = sizeof(CigarRec) * (size_t)cnt, ext_bytes = extend ? sizeof(ExtendRec) * (size_t)cnt : 0;
-        const size_t bytes = rec_bytes + ext_bytes + (with_ops ? sizeof(unsigned) * (size_t)total : 0);
-        if (bytes > h_cig_out_[0].bytes()) {                     // (the last copy out of it was waited for)
-            h_cig_out_[0].reserve(bytes + bytes / 4, "packed alignment results");
-            d_cig_out_[0].reserve(bytes + bytes / 4, "packed alignment results");
-        }
-        uint8_t *out = d_cig_out_[0].get();
-        if (with_ops) {                             // emit pass: the ops at their offsets, the records in front
-            CigarArgs a{};
-            a.rows = d_cig_rows_[0].get();
-            a.idx = d_cig_idx_[0].get();
-            a.ops = reinterpret_cast<unsigned *>(out + rec_bytes + ext_bytes);
-            a.offsets = d_cig_offsets_[0].get();
-            a.recs_in = d_cig_recs_[0].get();
-            a.recs_out = reinterpret_cast<CigarRec *>(out);
-            a.n = cnt;
-            a.extended = extended;
-            launch_extend_align_cigar(st, a);
-        } else {
-            hip_check(hipMemcpyAsync(out, d_cig_recs_[0].get(), rec_bytes, hipMemcpyDeviceToDevice, st), "D2D records");
-        }
-        if (extend) hip_check(hipMemcpyAsync(out + rec_bytes, d_extend_align_recs_.get(), ext_bytes, hipMemcpyDeviceToDevice, st), "D2D extension records");
-        hip_check(hipMemcpyAsync(h_cig_out_[0].get(), out, bytes, hipMemcpyDeviceToHost, st), "D2H records + ops");
-        cigar_d2h_bytes_ += (long long)(bytes + sizeof(long long));
-        t0 = std::chrono::steady_clock::now();
-        hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
-        auto t1 = std::chrono::steady_clock::now();
-        const uint8_t *h = h_cig_out_[0].get();
-        const CigarRec *h_recs = reinterpret_cast<const CigarRec *>(h);
-        for_ranges(threads, cnt, 4096, [&](int, long long lo, long long hi) { memcpy(recs + begin + lo, h_recs + lo, sizeof(CigarRec) * (size_t)(hi - lo)); });
-        if (extend) memcpy(extend + begin, h + rec_bytes, ext_bytes);
-        long long at = offsets[begin];
-        for (long long i = 0; i < cnt; ++i) {                    // offsets follow from n_ops: rebased on the host
-            at += h_recs[i].n_ops;
-            offsets[begin + i + 1] = at;
-        }
-        if (with_ops && total > 0) {
-            unsigned *to = ops + offsets[begin];
-            const unsigned *from = reinterpret_cast<const unsigned *>(h + rec_bytes + ext_bytes);
-            for_ranges(threads, total, 1 << 16, [&](int, long long lo, long long hi) { memcpy(to + lo, from + lo, sizeof(unsigned) * (size_t)(hi - lo)); });
-        }
-        host_stats_.wait_ms += ms_between(t0, t1);
-        host_stats_.drain_ms += ms_between(t1, std::chrono::steady_clock::now());
+        const PackedLayout layout(cnt, extend ? sizeof(ExtendRec) : 0, total, budget.add(total));
+        emit_packed(pack, layout, [&](unsigned *d_ops, CigarRec *recs_out) {
+            CigarArgs a = emit_args<CigarArgs>(pack, d_cig_rows_[0].get(), d_cig_idx_[0].get(), cnt, extended, d_ops, recs_out);
+            launch_cigar_args(st, a, R_ + F_ + 1);      // the walk's row pitch
+        }, d_extend, st);
+        wait();
+        drain_packed(pack, layout, begin, recs, extend ? extend + begin : nullptr, ops, offsets, threads);
     }
     quiesce.armed = false;
-    *ops_needed = total_ops;
-    return total_ops <= ops_cap;
+    *ops_needed = budget.total;
+    return budget.fits();
 }
 
 }  // namespace valign

@@ -619,6 +619,15 @@ VALIGN_EXPORT int valign_hip_align_host(valign_hip_engine *e, int opt, int n, co
 
 static_assert(sizeof(valign_hip_aln) == sizeof(valign::CigarRec) && sizeof(valign_hip_aln) == 24, "valign_hip_aln is the encoder's record");
 
+// the return code of a *_host call of the compact format: 2, and the need in the message, where the call ran and ops_cap was too small
+static int packed_result(int rc, bool fits, const long long *ops_needed) {
+    if (rc == 0 && !fits) {
+        g_last_error = "ops_cap is too small: the call needs " + std::to_string(*ops_needed) + " ops";
+        return 2;
+    }
+    return rc;
+}
+
 VALIGN_EXPORT int valign_hip_align_cigar_device(valign_hip_engine *e, int opt, long long n, const void *d_reads, const void *d_refs,
                                                 int extended, void *d_recs, void *d_ops, int ops_stride, void *hip_stream) {
     if (!e) {
@@ -642,11 +651,7 @@ VALIGN_EXPORT int valign_hip_align_cigar_host(valign_hip_engine *e, int opt, int
     const int rc = flat_guard([&] {
         fits = e->impl->align_cigar_host(opt, n, reads, refs, extended, (valign::CigarRec *)recs, ops, ops_cap, offsets, ops_needed, threads);
     });
-    if (rc == 0 && !fits) {
-        g_last_error = "ops_cap is too small: the call needs " + std::to_string(*ops_needed) + " ops";
-        return 2;
-    }
-    return rc;
+    return packed_result(rc, fits, ops_needed);
 }
 
 static_assert(sizeof(valign_hip_placed) == sizeof(valign::PlacedRec) && sizeof(valign_hip_placed) == 12, "valign_hip_placed is the kernels' record");
@@ -717,11 +722,7 @@ VALIGN_EXPORT int valign_hip_align_span_host(valign_hip_engine *e, int opt, int 
     const int rc = flat_guard([&] {
         fits = e->impl->align_span_host(opt, n, reads, refs, extended, (valign::CigarRec *)recs, ops, ops_cap, offsets, ops_needed, threads);
     });
-    if (rc == 0 && !fits) {
-        g_last_error = "ops_cap is too small: the call needs " + std::to_string(*ops_needed) + " ops";
-        return 2;
-    }
-    return rc;
+    return packed_result(rc, fits, ops_needed);
 }
 
 static_assert(sizeof(valign_hip_subopt) == sizeof(valign::SuboptRec) && sizeof(valign_hip_subopt) == 20, "valign_hip_subopt is the kernels' record");
@@ -793,11 +794,7 @@ VALIGN_EXPORT int valign_hip_align_extend_host(valign_hip_engine *e, int opt, in
         fits = e->impl->align_extend_host(opt, n, reads, refs, end_bonus, extended, (valign::CigarRec *)recs, ops, ops_cap, offsets, ops_needed,
                                           (valign::ExtendRec *)extend, threads);
     });
-    if (rc == 0 && !fits) {
-        g_last_error = "ops_cap is too small: the call needs " + std::to_string(*ops_needed) + " ops";
-        return 2;
-    }
-    return rc;
+    return packed_result(rc, fits, ops_needed);
 }
 
 VALIGN_EXPORT int valign_hip_describe(valign_hip_engine *e, int opt, long long n, char *buf, int cap) {

@@ -1,7 +1,8 @@
 // host_pipeline.h -- the host-only half of libHIPKernel.so's host-pointer path: the persistent worker pool and the
 // gather / scatter between the caller's scattered heap blocks (what the plugin ABI hands over: N `char *`, one per
 // sequence, src/util/versalignUtil.cpp:24-31; 2N operator new[] result rows, include/AlignmentKernel.h:20-23) and the
-// contiguous pair-major staging buffers the device works on.  The reference's precedent is the OpenCL backend's
+// contiguous pair-major staging buffers the device works on -- and, for the compact result format, the layout of a packed
+// chunk and its way into the caller's records, offsets and ops.  The reference's precedent is the OpenCL backend's
 // gather / collect loops (src/Kernels/OpenCL/OpenCLKernel.cpp:57-66, 613-645: one memcpy per sequence, an OpenMP copy
 // back); nothing of them is reused.
 //
@@ -187,6 +188,33 @@ struct FlatSink {
     FlatSink operator+(long long k) const { return FlatSink{rows + (size_t)k * 2 * AL, idx + 4 * k, AL}; }
 };
 
+// ---- packed results of the compact format (valign_hip_align_cigar_host and the calls that follow its contract) ----
+// One chunk as it crosses PCIe in ONE copy: [cnt records][cnt extra records][the chunk's ops].  The records are
+// valign_hip_aln (24 bytes, n_ops last), the ops 32-bit; extra records (extension records today) are opaque bytes here.
+// The ops are absent (with_ops false) from the chunk on whose total the call passes the caller's ops_cap.
+struct PackedLayout {
+    static constexpr size_t kRecordBytes = 24;
+    long long cnt = 0, total = 0;               // pairs and ops of the chunk
+    bool with_ops = false;
+    size_t rec_bytes = 0, extra_bytes = 0;
+    PackedLayout() = default;
+    PackedLayout(long long cnt_, size_t extra_record_bytes, long long total_ops, bool with_ops_)
+        : cnt(cnt_), total(total_ops), with_ops(with_ops_), rec_bytes(kRecordBytes * (size_t)cnt_), extra_bytes(extra_record_bytes * (size_t)cnt_) {}
+    size_t ops_at() const { return rec_bytes + extra_bytes; }
+    size_t bytes() const { return ops_at() + (with_ops ? sizeof(uint32_t) * (size_t)total : 0); }
+};
+
+// The caller's ops buffer against the running op total of a call: a chunk's ops are emitted and copied only while the
+// total up to and including that chunk fits, so none are once it has passed ops_cap (records and offsets still are)
+struct OpsBudget {
+    long long cap, total = 0;
+    bool add(long long chunk_total) {
+        total += chunk_total;
+        return fits();
+    }
+    bool fits() const { return total <= cap; }
+};
+
 // Gather / scatter of one engine: fixed (read_length, ref_length), a pool that is resized when the caller's
 // num_threads changes.  Threads write disjoint pair ranges; nothing else is shared.
 class HostPacker {
@@ -236,6 +264,29 @@ public:
                 pack_classes((const uint8_t *)refs[i], F, dst_refs + (size_t)i * PF);
             }
         });
+    }
+
+    // One packed chunk (`h`, laid out as `L`) -> the caller's arrays; the chunk's first pair is pair `begin` of the call.
+    // Records to recs + begin, extra records to `extra` (the chunk's own destination; null: none asked for), then
+    // offsets[begin + 1 .. begin + cnt] rebased from n_ops on offsets[begin] -- chunks arrive in order --, then the ops to
+    // ops + offsets[begin] where the chunk carries them.  Rec: the 24-byte record, which ends in n_ops.
+    template <class Rec>
+    void unpack_packed(const PackedLayout &L, const uint8_t *h, long long begin, Rec *recs, void *extra, uint32_t *ops, long long *offsets,
+                       int threads) {
+        static_assert(sizeof(Rec) == PackedLayout::kRecordBytes, "the packed record is valign_hip_aln");
+        const Rec *h_recs = reinterpret_cast<const Rec *>(h);
+        for_ranges(threads, L.cnt, 4096, [&](int, long long lo, long long hi) { memcpy(recs + begin + lo, h_recs + lo, sizeof(Rec) * (size_t)(hi - lo)); });
+        if (extra && L.extra_bytes) memcpy(extra, h + L.rec_bytes, L.extra_bytes);
+        long long at = offsets[begin];
+        for (long long i = 0; i < L.cnt; ++i) {
+            at += h_recs[i].n_ops;
+            offsets[begin + i + 1] = at;
+        }
+        if (L.with_ops && L.total > 0) {
+            uint32_t *to = ops + offsets[begin];
+            const uint32_t *from = reinterpret_cast<const uint32_t *>(h + L.ops_at());
+            for_ranges(threads, L.total, 1 << 16, [&](int, long long lo, long long hi) { memcpy(to + lo, from + lo, sizeof(uint32_t) * (size_t)(hi - lo)); });
+        }
     }
 
     // result rows are copied by one thread below 768 KB (waking the pool costs what copying that much does): 2,048 pairs of

@@ -398,10 +398,10 @@ class Engine:
             raise HipKernelError(_err())
         return recs, ops
 
-    def align_cigar_host(self, opt, reads, refs, extended=False, threads=1, ops_cap=None):
-        """Host-pointer path of the compact result format: -> recs (structured, aln_dtype()) [n], ops uint32
-        [offsets[n]], offsets int64 [n + 1]; pair p's ops are ops[offsets[p]:offsets[p + 1]].  `ops` is sized from a guess
-        (`ops_cap`, default 16 per pair) and the call repeated once with the exact size where that was too small."""
+    def _packed_host(self, call, opt, reads, refs, extended, threads, ops_cap, before=(), after=()):
+        """What the three *_host calls of the compact format share: the pointer arrays, `ops` sized from a guess (`ops_cap`,
+        default 16 per pair) and the single retry with the exact size.  `call` is the library's entry point; `before` and
+        `after` are the arguments it takes in front of `extended` (an int here) and behind `ops_needed`.  -> recs, ops, offsets."""
         import numpy as np
         n = reads.shape[0]
         assert reads.dtype == np.uint8 and refs.dtype == np.uint8 and reads.flags.c_contiguous and refs.flags.c_contiguous
@@ -414,15 +414,20 @@ class Engine:
         for _ in range(2):
             ops = np.zeros(max(cap, 1), dtype=np.uint32)
             needed = ctypes.c_longlong(0)
-            rc = lib().valign_hip_align_cigar_host(self._h, int(opt), n, rp.ctypes.data, fp.ctypes.data,
-                                                   1 if extended else 0, recs.ctypes.data, ops.ctypes.data, cap,
-                                                   offsets.ctypes.data, ctypes.byref(needed), int(threads))
+            rc = call(self._h, int(opt), n, rp.ctypes.data, fp.ctypes.data, *before, extended, recs.ctypes.data,
+                      ops.ctypes.data, cap, offsets.ctypes.data, ctypes.byref(needed), *after, int(threads))
             if rc == 0:
                 return recs, ops[:int(offsets[n])], offsets
             if needed.value <= cap:
                 break
             cap = needed.value
         raise HipKernelError(_err())
+
+    def align_cigar_host(self, opt, reads, refs, extended=False, threads=1, ops_cap=None):
+        """Host-pointer path of the compact result format: -> recs (structured, aln_dtype()) [n], ops uint32
+        [offsets[n]], offsets int64 [n + 1]; pair p's ops are ops[offsets[p]:offsets[p + 1]].  `ops` is sized from a guess
+        (`ops_cap`, default 16 per pair) and the call repeated once with the exact size where that was too small."""
+        return self._packed_host(lib().valign_hip_align_cigar_host, opt, reads, refs, 1 if extended else 0, threads, ops_cap)
 
     def score_placed_device(self, opt, reads, refs, out=None, stream=None):
         """Placed Smith-Waterman scores: -> int32 CUDA [n, 3] (score, read_end, ref_end -- `out.cpu().numpy().view(
@@ -521,27 +526,7 @@ class Engine:
         """Host-pointer path of the spanned CIGARs: -> recs (structured, aln_dtype()) [n], ops uint32 [offsets[n]], offsets
         int64 [n + 1], as align_cigar_host returns them.  `ops` is sized from a guess (`ops_cap`, default 16 per pair) and the
         call repeated once with the exact size where that was too small."""
-        import numpy as np
-        n = reads.shape[0]
-        assert reads.dtype == np.uint8 and refs.dtype == np.uint8 and reads.flags.c_contiguous and refs.flags.c_contiguous
-        assert tuple(reads.shape) == (n, self.read_length) and tuple(refs.shape) == (n, self.ref_length)
-        rp = (reads.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(self.read_length)).astype(np.uint64)
-        fp = (refs.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(self.ref_length)).astype(np.uint64)
-        recs = np.zeros(n, dtype=aln_dtype())
-        offsets = np.zeros(n + 1, dtype=np.int64)
-        cap = 16 * n if ops_cap is None else int(ops_cap)
-        for _ in range(2):
-            ops = np.zeros(max(cap, 1), dtype=np.uint32)
-            needed = ctypes.c_longlong(0)
-            rc = lib().valign_hip_align_span_host(self._h, int(opt), n, rp.ctypes.data, fp.ctypes.data, int(extended),
-                                                  recs.ctypes.data, ops.ctypes.data, cap, offsets.ctypes.data,
-                                                  ctypes.byref(needed), int(threads))
-            if rc == 0:
-                return recs, ops[:int(offsets[n])], offsets
-            if needed.value <= cap:
-                break
-            cap = needed.value
-        raise HipKernelError(_err())
+        return self._packed_host(lib().valign_hip_align_span_host, opt, reads, refs, int(extended), threads, ops_cap)
 
     def score_subopt_device(self, opt, reads, refs, mask, out=None, stream=None):
         """Suboptimal Smith-Waterman scores: -> int32 CUDA [n, 5] (score, read_end, ref_end, score2, ref_end2 --
@@ -649,28 +634,9 @@ class Engine:
         with_extend (else None).  `ops` is sized from a guess (`ops_cap`, default 16 per pair) and the call repeated once
         with the exact size where that was too small."""
         import numpy as np
-        n = reads.shape[0]
-        assert reads.dtype == np.uint8 and refs.dtype == np.uint8 and reads.flags.c_contiguous and refs.flags.c_contiguous
-        assert tuple(reads.shape) == (n, self.read_length) and tuple(refs.shape) == (n, self.ref_length)
-        rp = (reads.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(self.read_length)).astype(np.uint64)
-        fp = (refs.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(self.ref_length)).astype(np.uint64)
-        recs = np.zeros(n, dtype=aln_dtype())
-        extend = np.zeros(n, dtype=extend_dtype()) if with_extend else None
-        offsets = np.zeros(n + 1, dtype=np.int64)
-        cap = 16 * n if ops_cap is None else int(ops_cap)
-        for _ in range(2):
-            ops = np.zeros(max(cap, 1), dtype=np.uint32)
-            needed = ctypes.c_longlong(0)
-            rc = lib().valign_hip_align_extend_host(self._h, int(opt), n, rp.ctypes.data, fp.ctypes.data, int(end_bonus),
-                                                    1 if extended else 0, recs.ctypes.data, ops.ctypes.data, cap,
-                                                    offsets.ctypes.data, ctypes.byref(needed),
-                                                    extend.ctypes.data if extend is not None else None, int(threads))
-            if rc == 0:
-                return recs, ops[:int(offsets[n])], offsets, extend
-            if needed.value <= cap:
-                break
-            cap = needed.value
-        raise HipKernelError(_err())
+        extend = np.zeros(reads.shape[0], dtype=extend_dtype()) if with_extend else None
+        return self._packed_host(lib().valign_hip_align_extend_host, opt, reads, refs, 1 if extended else 0, threads, ops_cap, before=(int(end_bonus),),
+                                 after=(extend.ctypes.data if extend is not None else None,)) + (extend,)
 
     def describe(self, opt=0, n=0):
         buf = ctypes.create_string_buffer(8192)
