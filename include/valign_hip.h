@@ -783,6 +783,50 @@ int valign_hip_align_extend_host(valign_hip_engine *e, int opt, int n, const cha
  * into.  tests/extend_band_align_ref.py restates the definition in numpy.                                                      */
 int valign_hip_set_extend_band_align(valign_hip_engine *e, int on);
 
+/* Extension Z-drop: rows stop counting at the first row that drops (key extend_zdrop; flat API only).  The three sentences above
+ * that say "NOT BUILT: Z-drop" are qualified here: under this key a row-wise Z-drop is built, on the int32 strip sweep, as the
+ * extend_band section qualified the sentence before it.  X-drop stays unbuilt.
+ *   Z = 0 (default): every call runs or is refused exactly as stated above.
+ *   0 < Z <= 2^30: valign_hip_score_extend_* and valign_hip_align_extend_* apply the rule below.  Only these calls read the key.
+ *     Values outside [0, 2^30] are refused with "extend_zdrop must be in [0, 2^30]".
+ * DEFINITION.  The matrix X, the trimmed lengths Rp / Fp, the recurrence and the tie rules are exactly those of extension scores;
+ * under extend_band = 1 with band_width > 0 the present cells are those of banded extension scores.  No cell value changes: only
+ * which rows count changes.
+ *   row maxima ... for row i, 0 <= i < Rp, m_i is the maximum of X(i, j) over the present candidates -1 <= j < Fp -- the border
+ *                  column counts -- and c_i the smallest such column.  A row with no present candidate is skipped: it neither
+ *                  updates anything nor drops (under a band such rows are a suffix).
+ *   running best . (M, Mi, Mj) starts at the anchor (0, -1, -1).  Rows are taken in order.  m_i > M: (M, Mi, Mj) = (m_i, i, c_i).
+ *                  Otherwise, with di = i - Mi and dj = c_i - Mj, pen = (di - dj) * |ext_ref| if di > dj, else (dj - di) *
+ *                  |ext_read| (linear gaps: |gap_ref|, |gap_read|), and the row DROPS iff M - m_i - pen > Z.
+ *   drop row ..... T is the first dropping row, Rp if none drops.
+ *   record ....... score = M, read_end = Mi + 1, ref_end = Mj + 1 as they stand at T -- three zeros when M = 0.  This is the
+ *                  row-major first maximum over the rows < T, because border values are never positive.  T == Rp: gscore / gref_end
+ *                  as without the key, the band's unreached closed form included.  T < Rp: the read end is unreached, gscore =
+ *                  VALIGN_HIP_EXTEND_UNREACHED and gref_end = 0.  Rp = 0 is five zeros.
+ *   alignments ... the extension record is the one above; the end-bonus rule then never picks the read end of a dropped pair (as for
+ *                  the band's unreached read end), and the alignment is that of the pair cut to its first T rows.
+ *   limits ....... Z >= 2^29 never drops and gives the record of Z = 0 bit for bit.  Nothing overflows on int32 cells: within
+ *                  extend_int32_ok / extend_band_int32_ok every cell lies in [-2^28, 2^28], so 0 <= M - m_i <= 2^29; |di - dj| <= R + F
+ *                  <= 32767 and a price is at most 32768, so 0 <= pen < 2^30; M - m_i - pen lies in (-2^30, 2^29] and Z <= 2^30.
+ * This follows BWA's ksw_extend rule with this library's rows as read positions.  There is no floor at zero and the row range does
+ * not shrink as ksw_extend's does; parity with BWA's numbers is not claimed.
+ * ROUTES under Z > 0 (versalignlib_amd/csrc/extend_zdrop.h: extend_zdrop_choice, extend_zdrop_align_choice).  opt & 0xF == 1 and
+ * traceback_policy = 1 are refused first, with their texts.
+ *   scores, band_width > 0: as without the key -- "band" under extend_band = 1, with its refusals; the band's refusal without it.
+ *   scores, band_width == 0: the int32 strip sweep ("ran_extend": "wide") whatever extend_wide, the read length and score_width 0 /
+ *     32 say; refused with texts that begin "extend_zdrop:" for score_width = 16 and where the int32 bound of extend_wide fails.
+ *     KNOWN: the int16 register sweep has no Z-drop form, so a 150-row read under the key fills 150 of its strip's 512 rows.
+ *   alignments: only on the banded route (band_width > 0, extend_band = 1, extend_band_align = 1); every other call is refused with
+ *     one "extend_zdrop:" text, which says that a band of 2 * max(read_length, ref_length) is the unbanded alignment.
+ * COST.  A wave sweeps two pairs, a launch 512 rows of every pair.  A strip below the drop rows of both pairs of a wave returns
+ * before its set-up; a strip that holds a drop row still runs to its end (no in-strip stop).
+ * NOT BUILT: a Z-drop form of the int16 register sweep; an in-strip stop; an anti-diagonal (ksw_extz-style) rule, which a
+ * strip-after-strip sweep cannot evaluate in order; X-drop.
+ * valign_hip_describe: "extend_zdrop" is the key; "ran_extend_zdrop" the Z the last extension call ran under, or 0;
+ * "extend_zdrop_skipped_waves" the waves that skipped a strip in the last such call (of a host call: in its last chunk).
+ * "ran_extend" / "ran_extend_align" keep "wide" / "band".  tests/extend_zdrop_ref.py restates the definition in numpy.          */
+int valign_hip_set_extend_zdrop(valign_hip_engine *e, int Z);
+
 /* Page-lock a host range and map it for the device (hipHostRegister behind a C symbol, so that an FFI caller needs no
  * HIP binding).  valign_hip_align_host into result buffers that lie inside a registered range -- or inside memory the
  * caller page-locked itself -- skips the library's pinned staging and its host-side copy: the device's copy engine

@@ -12,7 +12,9 @@ strips, scorings, extended, ops_stride, trace_checkpoints, pointer_scratch_cap_m
 cases for the extension scores (a third of them extend_wide = 1 cases -- long reads, scorings out of int16, score_width = 32; score_extend_device / _host against tests/extend_ref.py: random shapes up to 200 x 300, the four gap
 forms at several scales, the engine's own or a forced geometry, planted extensions, ragged tails and interior junk); `--kind extend_band` draws nothing but cases for the banded extension scores
 (extend_band = 1 under a band, against tests/extend_band_ref.py: random shapes of one to four 512-row strips, random bands from
-w = 0 to the unbanded limit, the four gap forms, score_width 0 / 32, extend_wide 0 / 1, ragged tails); `--kind extend_band_align`
+w = 0 to the unbanded limit, the four gap forms, score_width 0 / 32, extend_wide 0 / 1, ragged tails); `--kind extend_zdrop` draws
+the same cases with a random Z of extend_zdrop, a third of them without the band (against tests/extend_zdrop_ref.py: records and
+the count of skipped waves); `--kind extend_band_align`
 draws the same shapes and bands for banded extension alignments (extend_band_align = 1: align_extend_device / _host against
 tests/extend_band_align_ref.py, from the best cell, from the read end and at bonus 20, extended, ops_stride, pointer_scratch_cap_mb);
 `--kind extend_align`
@@ -41,6 +43,7 @@ import extend_align_ref                                            # noqa: E402
 import extend_band_ref                                             # noqa: E402
 import extend_band_align_ref                                       # noqa: E402
 import extend_ref                                                  # noqa: E402
+import extend_zdrop_ref                                            # noqa: E402
 import placed_band_ref                                             # noqa: E402
 import placed_ref                                                  # noqa: E402
 import span_cigar_ref                                              # noqa: E402
@@ -420,8 +423,25 @@ def run_extend_band(c):
     """one banded extension-score case: the device entry (and, for some, the host entry) against tests/extend_band_ref.py, all five
     fields.  The references are the reads with a few bases inserted -- fewer than w for some pairs, more than w + 8 for others --
     and ragged tails."""
+    return run_extend_zdrop(dict(c, Z=0, banded=True))
+
+
+def draw_extend_zdrop(rng):
+    """--kind extend_zdrop: draw_extend_band's cases with a random Z -- small, of the scale of a read's score, never dropping -- and,
+    for a third, without the band (the unbanded int32 sweep, whatever the read length)"""
+    c = draw_extend_band(rng)
+    c.update(Z=int(rng.choice([1, int(rng.integers(1, 40)), int(rng.integers(1, 400)), int(rng.integers(1, 4 * c["R"] + 2)), 1 << 29, 1 << 30])),
+             banded=bool(rng.random() < 0.67))
+    return c
+
+
+def run_extend_zdrop(c):
+    """one extension-score case under extend_zdrop = Z (Z = 0: a case of --kind extend_band): the device entry (and, for some, the
+    host entry) against tests/extend_zdrop_ref.py -- all five fields and, on the device entry, the count of skipped waves.  Half of
+    the pairs carry a run of A against C behind a random prefix, so that rows drop."""
     rng = np.random.default_rng(c["seed"])
     R, F, n, w = c["R"], c["F"], c["n"], c["band_width"] // 2
+    Z, band_width = c["Z"], c["band_width"] if c["banded"] else 0
     bases = np.frombuffer(b"ACGT", np.uint8)
     reads, refs = bases[rng.integers(0, 4, (n, R))], bases[rng.integers(0, 4, (n, F))]
     for p in range(n):
@@ -429,6 +449,10 @@ def run_extend_band(c):
         pos = int(rng.integers(0, max(1, min(R, F))))
         row = np.concatenate([reads[p, :pos], bases[rng.integers(0, 4, d)], reads[p, pos:]])[:F]
         refs[p, :len(row)] = row
+        if Z and p % 4 < 2:
+            a, g = int(rng.integers(0, R)), int(rng.integers(1, 40))
+            reads[p, a:a + g] = ord("A")
+            refs[p, a:a + g] = ord("C")
         if rng.random() < 0.3:
             reads[p, int(rng.integers(0, R + 1)):] = rng.choice([0, ord("N")])
         if rng.random() < 0.3:
@@ -436,24 +460,33 @@ def run_extend_band(c):
         if rng.random() < 0.2:
             refs[p, int(rng.integers(0, F))] = rng.choice([0, ord("N"), 0x80, 0xFF])
     sc = hipkernel.Scoring.make(*c["scoring"])
-    exp = extend_band_ref.extend(reads, refs, sc, c["band_width"], affine=c["affine"], chunk=64 if R <= 200 else 4)
+    chunk = 64 if R <= 200 else 4
+    if Z:
+        exp, T = extend_zdrop_ref.extend(reads, refs, sc, Z, band_width, affine=c["affine"], chunk=chunk)
+        skipped = extend_zdrop_ref.skipped_waves(T, extend_ref.trimmed_lengths(reads), extend_ref.trimmed_lengths(refs), R, band_width)
+    else:
+        exp, skipped = extend_band_ref.extend(reads, refs, sc, band_width, affine=c["affine"], chunk=chunk), 0
+    route = "band" if band_width else "wide"
     eng = hipkernel.Engine(R, F, sc)
     try:
-        eng.set_band_width(c["band_width"])
-        eng.set_extend_band(1)
+        eng.set_band_width(band_width)
+        eng.set_extend_band(1 if band_width else 0)
         eng.set_score_width(c["width"])
         eng.set_extend_wide(c["wide"])
+        eng.set_extend_zdrop(Z)
         got = eng.score_extend_device(0, torch.from_numpy(reads).cuda(), torch.from_numpy(refs).cuda())
         torch.cuda.synchronize()
-        ran = eng.describe(0, n)["ran_extend"]
-        if ran != "band":
-            return "score_extend_device ran %s" % ran
+        d = eng.describe(0, n)
+        if d["ran_extend"] != route or d["ran_extend_zdrop"] != Z:
+            return "score_extend_device ran %s under Z = %d" % (d["ran_extend"], d["ran_extend_zdrop"])
         if not np.array_equal(got.cpu().numpy().astype(np.int64), exp):
-            return "score_extend_device differs (band)"
+            return "score_extend_device differs (%s, Z = %d)" % (route, Z)
+        if d["extend_zdrop_skipped_waves"] != skipped:
+            return "skipped waves: %d, expected %d" % (d["extend_zdrop_skipped_waves"], skipped)
         if c["host"]:
             h = eng.score_extend_host(0, reads, refs, threads=c["threads"])
             if not np.array_equal(np.stack([h[k] for k in hipkernel.extend_dtype().names], axis=1).astype(np.int64), exp):
-                return "score_extend_host differs (band)"
+                return "score_extend_host differs (%s, Z = %d)" % (route, Z)
         return None
     finally:
         eng.close()
@@ -638,7 +671,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--first", type=int, default=0)
     ap.add_argument("--verbose", action="store_true")
-    ap.add_argument("--kind", choices=["subopt", "sequence", "span_cigar", "extend", "extend_band", "extend_align", "extend_band_align"], default=None,
+    ap.add_argument("--kind", choices=["subopt", "sequence", "span_cigar", "extend", "extend_band", "extend_zdrop", "extend_align", "extend_band_align"], default=None,
                     help="draw cases of this kind only (default: the mix); sequence: one engine through tests/engine_sequences.py's sequences "
                          "(fifteen keys, extend_band and extend_band_align among them; nine families of calls, the banded extension routes included)")
     a = ap.parse_args()
@@ -649,7 +682,7 @@ def main():
     i = done = 0
     while time.time() - t0 < a.seconds:
         own = {"span_cigar": (draw_span_cigar, run_span_cigar), "extend": (draw_extend, run_extend), "extend_band": (draw_extend_band, run_extend_band), "extend_align": (draw_extend_align, run_extend_align),
-               "extend_band_align": (draw_extend_band_align, run_extend_band_align)}.get(a.kind)
+               "extend_band_align": (draw_extend_band_align, run_extend_band_align), "extend_zdrop": (draw_extend_zdrop, run_extend_zdrop)}.get(a.kind)
         c = own[0](rng) if own else draw(rng, a.kind)
         if i >= a.first:
             if a.verbose:

@@ -74,6 +74,10 @@ g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/extend_band_align_plan_check
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/extend_band_align_rules_check.cpp" -o "$OUT/extend_band_align_rules_asan"
 "$OUT/extend_band_align_rules_asan"
 
+echo "== extend_zdrop.h (the choices under extend_zdrop, the drop step, the scan's combine, the skip condition) under AddressSanitizer + UBSan"
+g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/extend_zdrop_rules_check.cpp" -o "$OUT/extend_zdrop_rules_asan"
+"$OUT/extend_zdrop_rules_asan"
+
 echo "== base_classes.h (the byte classifier of the kernels' set-up) under AddressSanitizer + UBSan"
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/base_classes_check.cpp" -o "$OUT/base_classes_asan"
 "$OUT/base_classes_asan"

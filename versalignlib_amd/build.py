@@ -31,7 +31,7 @@ HIP_KERNEL_PART = "kernel_part.hip"          # compiled once per part (kernel_in
 HIP_KERNEL_PARTS = 6
 # every header (a unit is rebuilt when its own source or any header changes; the kernel parts only look at KERNEL_PART_DEPS)
 HIP_HEADERS = ["kernel_instances.hip.h", "placed_kernels.hip.h", "dp_kernels.hip.h", "trace_kernels.hip.h", "long_kernels.hip.h", "strip_kernels.hip.h",
-               "engine.hip.h", "base_classes.h", "cell_constants.h", "lane_map.h", "cell_rules.h", "align_parts.h", "ckpt_plan.h", "strip_plan.h", "long_plan.h", "hip_handles.h", "host_runtime.hip.h", "host_pipeline.h", "band_kernels.hip.h", "band_window.h", "pack_kernels.hip.h", "ragged_kernels.hip.h", "cigar_kernels.hip.h", "span_kernels.hip.h", "span_cigar_kernels.hip.h", "placed_wide_kernels.hip.h", "subopt_kernels.hip.h", "extend_kernels.hip.h", "extend_wide_kernels.hip.h", "extend_band_plan.h", "extend_align_kernels.hip.h", "extend_band_align_plan.h", "extend_band_align_kernels.hip.h"]
+               "engine.hip.h", "base_classes.h", "cell_constants.h", "lane_map.h", "cell_rules.h", "align_parts.h", "ckpt_plan.h", "strip_plan.h", "long_plan.h", "hip_handles.h", "host_runtime.hip.h", "host_pipeline.h", "band_kernels.hip.h", "band_window.h", "pack_kernels.hip.h", "ragged_kernels.hip.h", "cigar_kernels.hip.h", "span_kernels.hip.h", "span_cigar_kernels.hip.h", "placed_wide_kernels.hip.h", "subopt_kernels.hip.h", "extend_kernels.hip.h", "extend_wide_kernels.hip.h", "extend_band_plan.h", "extend_align_kernels.hip.h", "extend_band_align_plan.h", "extend_band_align_kernels.hip.h", "extend_zdrop.h"]
 OBJ = os.path.join(PKG, "build")             # intermediate objects (git-ignored)
 HOST_SOURCES = ["valign_host.cpp"]
 

@@ -54,6 +54,7 @@
 
 #include "align_parts.h"
 #include "cell_rules.h"
+#include "extend_zdrop.h"
 #include "hip_handles.h"
 #include "host_pipeline.h"
 #include "kernel_instances.hip.h"
@@ -307,6 +308,14 @@ public:
         extend_band_align_ = on == 1;
     }
     int extend_band_align() const { return extend_band_align_ ? 1 : 0; }
+    // Z-drop of extension scores and alignments (opt-in; include/valign_hip.h has the definition, extend_zdrop.h the rule): Z > 0 =
+    // valign_hip_score_extend_* and valign_hip_align_extend_* stop counting rows at the first row that drops under Z, on the int32
+    // strip sweep's ZDROP instances; 0 = every row counts (default).  No other call reads it.
+    void set_extend_zdrop(int Z) {
+        if (!extend_zdrop_key_ok(Z)) throw std::runtime_error(kExtendZdropKeyRange);
+        extend_zdrop_ = Z;
+    }
+    int extend_zdrop() const { return extend_zdrop_; }
     // Checkpointed traceback of long-read alignments (opt-in; ckpt_plan.h): 1 = calls that take the plain row strips (unbanded,
     // int16 cells, traceback_policy 0; both algorithms, linear and affine gaps) keep one boundary row per strip and ONE strip's
     // pointer region instead of every pointer, and re-fill strip after strip along the walk -- identical results, a scratch that
@@ -677,6 +686,10 @@ private:
     // its banded form without a record sink: the plan, the LDS, the scratch binding and the lengths pre-pass that banded extension
     // alignments share with the scores (engine_extend_align.hip launches its own fill and closes the chunk itself)
     PlacedSweep extend_band_sweep() const;
+    // extend_zdrop > 0: the counter of skipped waves, zeroed on the call's stream when an extension call starts (engine_extend.hip);
+    // read back by describe() ("extend_zdrop_skipped_waves"; waits for the device)
+    void start_extend_zdrop(hipStream_t stream);
+    long long extend_zdrop_skipped_waves() const;
     // Chunk after chunk of what the scratch cap holds: strip after strip through two boundary row sets that ping-pong, the per-pair
     // scratch merged on the way, then the description's records.  The scratch is the engine's, shared by every description.
     void score_placed_strips(const PlacedSweep &sweep, long long n, const uint8_t *d_reads, const uint8_t *d_refs, hipStream_t stream);
@@ -1056,6 +1069,8 @@ private:
     bool extend_wide_ = false;
     bool extend_band_ = false;
     bool extend_band_align_ = false;
+    int extend_zdrop_ = 0;
+    int ran_extend_zdrop_ = 0;                           // the Z the last extension call ran under, 0 without the key (describe)
     bool trace_checkpoints_ = false;
     int score_width_ = 0;
     int ragged_ = 0, force_g_ = 0, force_k_ = 0;
@@ -1191,6 +1206,7 @@ private:
     DeviceBuffer<int> d_band_fill_;
     RaggedCtx rag_[kSlots + 1];                                  // one per pipeline slot, the last for device-resident batches
     DeviceBuffer<unsigned> d_form_seen_;                         // the 8 x 19 kernel's two form words (ScoreArgs::form_seen)
+    DeviceBuffer<unsigned> d_zdrop_skipped_;                     // extend_zdrop > 0, its last call: the waves that skipped a strip
     DeviceBuffer<uint8_t> d_read_class_;                         // length -> class tables of the length-sorted batches
     DeviceBuffer<uint16_t> d_ref_class_;
 };

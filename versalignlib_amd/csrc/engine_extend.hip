@@ -5,7 +5,10 @@
 // itself -- no scratch, one launch per call -- or, where the rule answers Wide (extend_wide = 1), hands score_placed_strips
 // (engine_placed.hip) the description of the int32 extension sweep (extend_wide_kernels.hip.h): a length pre-pass per chunk, one
 // launch per strip, a record kernel.  Where it answers Band (extend_band = 1 under a band) the same description carries the sweep's
-// BANDED instances.  The host-pointer path is record_pipeline (engine_score.hip), 20-byte records on the way back.
+// BANDED instances.  The rule is asked through extend_zdrop_choice (extend_zdrop.h), which wraps extend_choice(in, alg, facts, G, K):
+// under extend_zdrop > 0 the strip sweep or nothing, and the
+// description carries the sweep's ZDROP instances, a drop row per pair behind the trimmed lengths and the counter of skipped waves.
+// The host-pointer path is record_pipeline (engine_score.hip), 20-byte records on the way back.
 // extend_wide_lengths_kernel and extend_wide_records_kernel (not templates) are defined in this translation unit.
 #define VALIGN_TU_EXTEND 1
 #include "engine.hip.h"
@@ -20,7 +23,7 @@ const LaunchPlan &Engine::extend_plan_for(int alg, int &gaps, PlacedRoute &route
     const PlacedFacts facts = placed_facts();
     RuleInputs in = rule_inputs();
     in.no_f16 = true;                   // int16 cells: the gap form is one of the four integer ones
-    const PlacedChoice choice = extend_choice(in, alg, facts, base.geo ? base.geo->G : 0, base.geo ? base.geo->K : 0);
+    const PlacedChoice choice = extend_zdrop_choice(in, alg, facts, base.geo ? base.geo->G : 0, base.geo ? base.geo->K : 0, extend_zdrop_);
     if (choice.route == PlacedRoute::Refused) throw std::runtime_error(choice.reason);
     route = choice.route;
     if (route == PlacedRoute::Wide || route == kPlacedRouteBand) return base;        // (nothing launches on the plan)
@@ -36,11 +39,13 @@ void Engine::score_extend_device(int opt, long long n, const uint8_t *d_reads, c
     if (alg > 1 || n <= 0) return;          // reference: unsupported mode is a silent no-op
     ran_extend_ = "none";
     ran_extend_geo_ = nullptr;
+    ran_extend_zdrop_ = 0;
     int gaps = 0;
     PlacedRoute route = PlacedRoute::Refused;
     const LaunchPlan &plan = extend_plan_for(alg, gaps, route);
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (route == PlacedRoute::Wide || route == kPlacedRouteBand) {
+        start_extend_zdrop(stream);
         score_placed_strips(extend_wide_sweep(d_extend, route == kPlacedRouteBand), n, d_reads, d_refs, stream);
         ran_extend_ = ran_placed_name(route);
         return;
@@ -76,31 +81,58 @@ void Engine::score_extend_device(int opt, long long n, const uint8_t *d_reads, c
 // read end.
 Engine::PlacedSweep Engine::extend_wide_sweep(ExtendRec *d_extend, bool banded) const {
     constexpr int K = kExtendWideK;
-    const void *fn = banded ? (sc_.affine ? (const void *)&score_extend_wide_kernel<K, true, true> : (const void *)&score_extend_wide_kernel<K, false, true>)
-                            : (sc_.affine ? (const void *)&score_extend_wide_kernel<K, true> : (const void *)&score_extend_wide_kernel<K, false>);
+    const bool zdrop = extend_zdrop_on(extend_zdrop_);
+    const void *plain = banded ? (sc_.affine ? (const void *)&score_extend_wide_kernel<K, true, true> : (const void *)&score_extend_wide_kernel<K, false, true>)
+                               : (sc_.affine ? (const void *)&score_extend_wide_kernel<K, true> : (const void *)&score_extend_wide_kernel<K, false>);
+    const void *dropping = banded ? (sc_.affine ? (const void *)&score_extend_wide_kernel<K, true, true, false, true> : (const void *)&score_extend_wide_kernel<K, false, true, false, true>)
+                                  : (sc_.affine ? (const void *)&score_extend_wide_kernel<K, true, false, false, true> : (const void *)&score_extend_wide_kernel<K, false, false, false, true>);
+    const void *fn = zdrop ? dropping : plain;
     PlacedSweep sweep{fn, WaveLds{StripLds<K>::kRing, 0, StripLds<K>::kTotal}, strip_plan(R_, F_, K, StripMode{kAlgSW, sc_.affine, false, true, false, false}, kNoBand),
                       false, "extension-score boundary rows (int32)", "hipLaunchKernel(score_extend_wide_kernel)"};
-    sweep.pair_bytes = sizeof(ExtendRec) + 2 * sizeof(int);
+    // (ZDROP: a drop row per pair behind the lengths, Z in the band's pad -- the sweep has no padding rows above the read -- and the
+    // counter of skipped waves where the walk state of the checkpointed strips travels)
+    sweep.pair_bytes = sizeof(ExtendRec) + 2 * sizeof(int) + (zdrop ? sizeof(int) : 0);
     const int band_half = banded ? extend_band_half(placed_facts().band_width, R_, F_) : -1;
     if (banded) sweep.plan.band = BandShape{band_half, kExtendBandBlockRows, kExtendBandColAlign, 0};
-    sweep.bind = [](StripArgs &a, long long pairs) {
+    if (zdrop) sweep.plan.band.pad = extend_zdrop_;
+    const WalkState *skipped = zdrop ? reinterpret_cast<const WalkState *>(d_zdrop_skipped_.get()) : nullptr;
+    sweep.bind = [skipped](StripArgs &a, long long pairs) {
         a.ptr = reinterpret_cast<unsigned *>(a.ends);
         a.first_bad = reinterpret_cast<const int *>(a.ptr + (size_t)kExtendWideRecDwords * pairs);
         a.ends = nullptr;
+        a.walk = skipped;
     };
     const int R = R_, F = F_;
     sweep.open = [R, F](const StripArgs &a, long long, hipStream_t stream) {
         hipLaunchKernelGGL(extend_wide_lengths_kernel, dim3((unsigned)a.n), dim3(kWave), 0, stream, a.reads, a.refs, a.n, R, F, const_cast<int *>(a.first_bad));
         hip_check(hipGetLastError(), "hipLaunchKernel(extend_wide_lengths_kernel)");
     };
-    sweep.close = [d_extend, band_half](const StripArgs &a, long long begin, hipStream_t stream) {
-        hipLaunchKernelGGL(extend_wide_records_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, stream, (const int *)a.ptr, a.first_bad, d_extend + begin, a.n, band_half);
+    sweep.close = [d_extend, band_half, zdrop](const StripArgs &a, long long begin, hipStream_t stream) {
+        hipLaunchKernelGGL(extend_wide_records_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, stream, (const int *)a.ptr, a.first_bad, d_extend + begin, a.n, band_half,
+                           zdrop ? extend_drop_rows(a) : nullptr);
         hip_check(hipGetLastError(), "hipLaunchKernel(extend_wide_records_kernel)");
     };
     return sweep;
 }
 
 Engine::PlacedSweep Engine::extend_band_sweep() const { return extend_wide_sweep(nullptr, true); }
+
+// An extension call on the strip sweep starts: what describe() reports of the key, and the counter at zero on the call's stream
+void Engine::start_extend_zdrop(hipStream_t stream) {
+    ran_extend_zdrop_ = extend_zdrop_;
+    if (!extend_zdrop_on(extend_zdrop_)) return;
+    if (!d_zdrop_skipped_.get()) d_zdrop_skipped_.reserve(sizeof(unsigned), "extend_zdrop skipped waves");
+    hip_check(hipMemsetAsync(d_zdrop_skipped_.get(), 0, sizeof(unsigned), stream), "hipMemsetAsync(extend_zdrop skipped waves)");
+}
+
+long long Engine::extend_zdrop_skipped_waves() const {
+    if (!extend_zdrop_on(ran_extend_zdrop_)) return 0;
+    unsigned waves = 0;
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    hip_check(hipMemcpy(&waves, d_zdrop_skipped_.get(), sizeof waves, hipMemcpyDeviceToHost), "hipMemcpy(extend_zdrop skipped waves)");
+    return waves;
+}
 
 // Host pointers in, host records out: record_pipeline, 20 bytes per pair on the way back.
 void Engine::score_extend_host(int opt, int n, const char *const *reads, const char *const *refs, ExtendRec *extend, int threads) {
@@ -109,6 +141,7 @@ void Engine::score_extend_host(int opt, int n, const char *const *reads, const c
     hip_check(hipSetDevice(device_), "hipSetDevice");
     ran_extend_ = "none";
     ran_extend_geo_ = nullptr;
+    ran_extend_zdrop_ = 0;
     int gaps = 0;
     PlacedRoute route = PlacedRoute::Refused;
     (void)extend_plan_for(alg, gaps, route);          // (refusals leave here, before anything is staged)

@@ -10,6 +10,8 @@
 // encoder (extend_band_align_kernels.hip.h; its two fill instances and the two other kernels are defined here).  Chunk sizes, the
 // scratch and both entry points are shared: only the chunk body differs.  The host entry delivers through the packed path of
 // engine_cigar.hip, the extension records between the records and the ops.
+// Under extend_zdrop > 0 the rule is extend_zdrop_align_choice (extend_zdrop.h), which wraps extend_align_choice(...): the Band route
+// or nothing, its fill the ZDROP instance, the ends kernel with the chunk's drop rows.
 #define VALIGN_TU_EXTEND_ALIGN 1
 #include "engine.hip.h"
 #include "extend_band_align_kernels.hip.h"
@@ -21,13 +23,13 @@ const LaunchPlan &Engine::extend_align_plan_for(int alg, ExtendAlignChoice &choi
     const PlacedFacts facts = placed_facts();
     RuleInputs in = rule_inputs();
     in.no_f16 = true;                   // int16 cells
-    choice = extend_align_choice(in, alg, facts, base.geo ? base.geo->G : 0, base.geo ? base.geo->K : 0);
+    choice = extend_zdrop_align_choice(in, alg, facts, base.geo ? base.geo->G : 0, base.geo ? base.geo->K : 0, extend_zdrop_);
     if (choice.route == PlacedRoute::Refused) throw std::runtime_error(choice.reason);
     if (choice.route == kPlacedRouteBand) return base;                  // (nothing launches on the plan)
     if (base.geo->extend_align(sc_.affine ? 1 : 0)) return base;
     if (!fallback_plan_.geo) fallback_plan_ = choose_plan(R_, F_, 0, 0, false, true);
     if (fallback_plan_.long_mode || !fallback_plan_.geo->extend_align(sc_.affine ? 1 : 0)) throw std::runtime_error("no extension-alignment kernel for this mode");
-    choice = extend_align_choice(in, alg, facts, fallback_plan_.geo->G, fallback_plan_.geo->K);
+    choice = extend_zdrop_align_choice(in, alg, facts, fallback_plan_.geo->G, fallback_plan_.geo->K, extend_zdrop_);
     return fallback_plan_;
 }
 
@@ -91,7 +93,10 @@ void Engine::extend_band_align_chunk(const ExtendAlignChoice &choice, long long 
         (size_t)n * 2 * ((size_t)R_ + F_ + 1) > d_cig_rows_[slot].bytes() || (size_t)waves * bytes_per_pp > d_placed_rows_.bytes() ||
         sweep.pair_bytes * (size_t)n > d_placed_ends_.bytes())
         throw std::runtime_error("extension alignments: chunk larger than its scratch");
-    const void *fn = sc_.affine ? (const void *)align_extend_band_fill_kernel<K, true> : (const void *)align_extend_band_fill_kernel<K, false>;
+    const bool zdrop = extend_zdrop_on(extend_zdrop_);
+    const void *plain = sc_.affine ? (const void *)align_extend_band_fill_kernel<K, true> : (const void *)align_extend_band_fill_kernel<K, false>;
+    const void *dropping = sc_.affine ? (const void *)align_extend_band_fill_zdrop_kernel<K, true> : (const void *)align_extend_band_fill_zdrop_kernel<K, false>;
+    const void *fn = zdrop ? dropping : plain;
     raise_block_lds(fn, sweep.lds.total);
     const size_t f_rows = plan.f_rows_at(waves), slot_dwords = plan.row_sets * f_rows;
     StripArgs first{};
@@ -108,7 +113,7 @@ void Engine::extend_band_align_chunk(const ExtendAlignChoice &choice, long long 
         hip_check(hipLaunchKernel(fn, dim3((unsigned)waves), dim3(kWave), kargs, (size_t)sweep.lds.total, stream), "hipLaunchKernel(align_extend_band_fill_kernel)");
     }
     hipLaunchKernelGGL(extend_band_ends_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const int *)first.ptr, first.first_bad, d_extend, d_ends_.get(), n,
-                       choice.band_half, end_bonus);
+                       choice.band_half, end_bonus, zdrop ? extend_drop_rows(first) : nullptr);
     hip_check(hipGetLastError(), "hipLaunchKernel(extend_band_ends_kernel)");
     ExtendWalkArgs t{};
     t.reads = d_reads;
@@ -210,12 +215,14 @@ void Engine::align_extend_device(int opt, long long n, const uint8_t *d_reads, c
     ran_extend_align_geo_ = nullptr;
     ran_extend_align_chunks_ = 0;
     ran_cigar_lanes_ = 0;
+    ran_extend_zdrop_ = 0;
     check_packed_device_args(extended, ops_stride, d_recs, d_ops);
     const int alg = opt & 0xF;
     if (alg > 1 || n <= 0) return;          // reference: unsupported mode is a silent no-op
     ExtendAlignChoice choice;
     const LaunchPlan &plan = extend_align_plan_for(alg, choice);        // (refusals leave here, before anything is launched)
     hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (choice.route == kPlacedRouteBand) start_extend_zdrop(stream);
     ran_result_format_ = "cigar";
     const size_t rows_cap = (size_t)std::max<long long>(1, dbg_.value("cigar_rows_mb", 512)) << 20;
     const long long chunk = extend_align_chunk_pairs(plan, choice, n, rows_cap);
@@ -235,6 +242,7 @@ bool Engine::align_extend_host(int opt, int n, const char *const *reads, const c
     ran_extend_align_geo_ = nullptr;
     ran_extend_align_chunks_ = 0;
     ran_cigar_lanes_ = 0;
+    ran_extend_zdrop_ = 0;
     check_packed_host_args(extended, n, recs, ops, ops_cap, offsets, ops_needed);
     const int alg = opt & 0xF;
     if (alg > 1) return true;                       // (the same silent no-op as every entry point)
@@ -255,6 +263,7 @@ bool Engine::align_extend_host(int opt, int n, const char *const *reads, const c
     ensure_staging(chunk);
     threads = std::min(std::max(threads, 1), 64);
     hipStream_t st = streams_[0].get();
+    if (choice.route == kPlacedRouteBand) start_extend_zdrop(st);
     ensure_extend_align_scratch(plan, choice, chunk, st);
     if (extend) d_extend_align_recs_.reserve(sizeof(ExtendRec) * (size_t)chunk, "extension records");
     ExtendRec *d_extend = extend ? d_extend_align_recs_.get() : nullptr;

@@ -29,7 +29,9 @@
 //   SHORT LAST BLOCK  a strip's steps need not be a multiple of 8: the last block's codes are moved up so that step t lies at
 //     2 * (7 - (t & 7)) as in every other block.
 //   REGIONS  are sized for the engine's F; a wave whose larger Fp is smaller writes the first blocks only, a strip below both Rp
-//     or with an empty window writes none -- no walk reads there: a path never moves right or down.
+//     or with an empty window writes none -- no walk reads there: a path never moves right or down.  Under extend_zdrop a strip
+//     that a wave skips (both pairs dropped above it) writes no block either: the walk starts above T, from the best cell among the
+//     rows before it -- a dropped pair's read end is unreached and never chosen -- and only moves up and left, so it never reads one.
 //   DON'T-CARE BITS  steps outside a lane's window leave the codes of no cell; they are stored and never read.
 #pragma once
 
@@ -41,18 +43,22 @@ namespace valign {
 // The fill: the sweep's kernel with BANDED and PTRS (two instances: linear and affine gaps at K = 8)
 template <int K, bool AFFINE>
 constexpr auto align_extend_band_fill_kernel = &score_extend_wide_kernel<K, AFFINE, true, true>;
+// ... and under extend_zdrop (extend_zdrop.h): the same with ZDROP
+template <int K, bool AFFINE>
+constexpr auto align_extend_band_fill_zdrop_kernel = &score_extend_wide_kernel<K, AFFINE, true, true, true>;
 
 #ifdef VALIGN_TU_EXTEND_ALIGN      // not templates: defined once, in engine_extend_align.hip
 // One lane per pair.  partial / lens: what the strips and extend_wide_lengths_kernel left (extend_wide_kernels.hip.h).
+// drop_rows (null: the key extend_zdrop is off): the read end of a pair that dropped is unreached, and so never chosen.
 __global__ void __launch_bounds__(256)
-extend_band_ends_kernel(const int *partial, const int *lens, ExtendRec *extend, EndCell *ends, long long n, int band_half, int end_bonus) {
+extend_band_ends_kernel(const int *partial, const int *lens, ExtendRec *extend, EndCell *ends, long long n, int band_half, int end_bonus, const int *drop_rows) {
     const long long pair = (long long)blockIdx.x * 256 + threadIdx.x;
     if (pair >= n) return;
     const int *rec = partial + kExtendWideRecDwords * pair;
     const int Rp = lens[2 * pair];
     const bool empty = Rp == 0;
     // the strip that holds row Rp - 1 may have returned before it wrote the pair: the unreached read end in closed form
-    const bool unreached = extend_band_unreached(Rp, lens[2 * pair + 1], band_half);
+    const bool unreached = extend_band_unreached(Rp, lens[2 * pair + 1], band_half) || (drop_rows && extend_zdrop_unreached(drop_rows[pair], Rp));
     ExtendRec r;
     r.score = empty ? 0 : rec[0];
     r.read_end = empty ? 0 : rec[1];

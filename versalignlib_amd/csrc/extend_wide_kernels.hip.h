@@ -29,6 +29,7 @@
 // A short read fills a fraction of its one 512-row strip (as on the placed int32 sweep): the int16 register sweep is the route for
 // those wherever the rule lets it run.  Z-drop, a band around the anchor's diagonal and an end bonus are not built.
 // (Since then the band IS built, on this strip sweep: the BANDED instances, below.  Z-drop and an end bonus remain unbuilt.)
+// (And since then a row-wise Z-drop IS built: the ZDROP instances, further below.)
 //
 // BANDED (key extend_band; the band is extend_band_plan.h's, StripArgs.band.half its w): the same sweep over the present cells
 // only.  A lane's 8 rows are one block of the band, so a lane is wholly inside or wholly outside its window at any step and the
@@ -51,11 +52,26 @@
 //     later strip never reads rec[0] uninitialised.
 //   UNREACHED READ END  the lane that holds row Rp - 1 writes (INT32_MIN, 0) when the row had no candidate; where that strip
 //     returned early nobody writes the pair, and extend_wide_records_kernel puts the closed form (extend_band_unreached) there.
+//
+// ZDROP (key extend_zdrop; the rule, its step, its combine and the skip condition are extend_zdrop.h's): no cell changes, only which
+// rows count.  The row maxima rb / fc the sweep keeps in registers are all the rule reads, so everything happens at the two ends:
+//   * per pair one more int of state behind the trimmed lengths: the drop row T (kExtendZdropNone: not dropped).  The three
+//     scratch arrays -- records, lengths, drop rows -- lie one behind the other, each sized for the same pair count, which is how
+//     the kernel finds the third from the two pointers it is given.  The running best is the partial record's first three ints.
+//   * entry: behind the early returns above, a strip > 0 whose two pairs both dropped above it returns before its set-up and one
+//     lane counts the wave (StripArgs.walk carries the engine's counter dword; StripArgs.band.pad carries Z: this sweep has no
+//     padding rows above the read).  Strip 0 always runs and starts the state.
+//   * epilogue, in the place of the value -> row -> column reduction: each lane's rows in order, an exclusive prefix arg-max over
+//     the lanes seeded with the carried running best (wave shuffles: the maxima never leave the wave), each lane's walk to its first
+//     dropping row, a wave minimum for T; the lane that holds T writes the running best just before it and T, without a drop lane
+//     63 writes the inclusive total.  A pair that entered the strip dropped writes nothing.
+// The closing kernels make the read end of a dropped pair unreached (T < Rp).
 #pragma once
 
 #include "extend_band_align_plan.h"
 #include "extend_band_plan.h"
 #include "extend_kernels.hip.h"
+#include "extend_zdrop.h"
 #include "strip_kernels.hip.h"
 
 namespace valign {
@@ -64,12 +80,22 @@ constexpr int kExtendWideK = 8;                 // rows per lane: the K of the p
 constexpr int kExtendWideRecDwords = 5;         // a partial record: ExtendRec's five ints
 static_assert(sizeof(ExtendRec) == 4 * kExtendWideRecDwords, "the partial record is an ExtendRec");
 
+// ZDROP: the drop rows of a chunk lie behind its trimmed lengths as those lie behind its partial records, all three sized for the same
+// pair count -- (first_bad - ptr) / 5 pairs
+__host__ __device__ inline int *extend_drop_rows(const StripArgs &a) {
+    const long long slots = (a.first_bad - reinterpret_cast<const int *>(a.ptr)) / kExtendWideRecDwords;
+    return const_cast<int *>(a.first_bad) + 2 * slots;
+}
+
 // StripArgs of this sweep: ptr = the partial records (n x 5 dwords), first_bad = the trimmed lengths (n x 2: Rp, Fp); ends unused.
 // PTRS (BANDED only; extend_band_align_kernels.hip.h names the instances and has the codes): the sweep also derives every cell's
 // back pointer and streams the codes to StripArgs.ends, taken as the dwords of the chunk's pointer regions in the layout of
 // extend_band_align_plan.h.  Everything PTRS adds stands under `if constexpr (PTRS)`: the score instances compile to the
 // instructions they had without it.
-template <int K, bool AFFINE, bool BANDED = false, bool PTRS = false>
+// ZDROP (above) is the last parameter and false by default; everything it adds stands under `if constexpr (ZDROP)`, so the six
+// instances of the parameter list as it stood -- template <int K, bool AFFINE, bool BANDED = false, bool PTRS = false> -- compile to
+// the instructions they had.
+template <int K, bool AFFINE, bool BANDED = false, bool PTRS = false, bool ZDROP = false>
 __global__ void __launch_bounds__(64)
 score_extend_wide_kernel(const StripArgs args) {
     static_assert(!BANDED || K == kExtendBandBlockRows, "a lane's rows are one block of the band");
@@ -102,6 +128,23 @@ score_extend_wide_kernel(const StripArgs args) {
     const ExtendBandStrip win = extend_band_strip(args.strip, F, bw);
     if (BANDED && args.strip > 0 && win.empty) return;
     const int t_begin = BANDED ? win.t_begin : 0;
+    // ZDROP: the drop rows lie behind the lengths as the lengths lie behind the records; both pairs dropped above the strip: skipped
+    int *drop_rows = nullptr;
+    int T_in[2] = {kExtendZdropNone, kExtendZdropNone};
+    if constexpr (ZDROP) {
+        drop_rows = extend_drop_rows(args);
+        if (args.strip > 0) {
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                const long long pair = first_pair + half < args.n ? first_pair + half : first_pair;
+                T_in[half] = __builtin_amdgcn_readfirstlane(drop_rows[pair]);
+            }
+            if (extend_zdrop_strip_skipped(args.strip, T_in[0], T_in[1])) {
+                if (lane == 0) atomicAdd(reinterpret_cast<unsigned *>(const_cast<WalkState *>(args.walk)), 1u);
+                return;
+            }
+        }
+    }
 
     WaveTables w;
     if (!strip_ring_setup<K>(args.reads, args.n, R, F, args.match, args.mismatch, row0, w)) return;
@@ -335,6 +378,67 @@ score_extend_wide_kernel(const StripArgs args) {
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
         const long long pair = w.pair0 + half;
+        if constexpr (ZDROP) {
+            if (pair >= args.n || T_in[half] < row0) continue;        // no such pair, or it entered the strip dropped: nothing is written
+            int *rec = partial + kExtendWideRecDwords * pair;
+            const int Z = args.band.pad;
+            const int price_ref = extend_zdrop_price(AFFINE ? e_ref : g_ref), price_read = extend_zdrop_price(AFFINE ? e_read : g_read);
+            // the carried running best (read by every lane before any lane writes it)
+            ExtendZdropBest seed = extend_zdrop_anchor();
+            if (args.strip > 0) seed = extend_zdrop_from_record(rec[0], rec[1], rec[2]);
+            const int first_row = row0 + l * K;
+            // 1. the lane's rows in order: rows of the read that have a candidate
+            ExtendZdropBest mine = extend_zdrop_no_row();
+#pragma unroll
+            for (int q = 0; q < K; ++q)
+                if (first_row + q < Rp[half] && rb[half][q] != (int)0x80000000)
+                    mine = extend_zdrop_combine(mine, ExtendZdropBest{rb[half][q], first_row + q, fc[half][q] - l});
+            // 2. the exclusive prefix over the lanes, seeded
+            ExtendZdropBest run = mine;
+#pragma unroll
+            for (int dd = 1; dd < G; dd <<= 1) {
+                const ExtendZdropBest before{__shfl_up(run.m, dd, kWave), __shfl_up(run.i, dd, kWave), __shfl_up(run.j, dd, kWave)};
+                if (l >= dd) run = extend_zdrop_combine(before, run);
+            }
+            const ExtendZdropBest upto{__shfl_up(run.m, 1, kWave), __shfl_up(run.i, 1, kWave), __shfl_up(run.j, 1, kWave)};
+            ExtendZdropBest best = l == 0 ? seed : extend_zdrop_combine(seed, upto);
+            // 3. the lane's walk: its first dropping row; the running best stays as it was just before that row
+            int T = kExtendZdropNone;
+#pragma unroll
+            for (int q = 0; q < K; ++q) {
+                if (T == kExtendZdropNone && first_row + q < Rp[half] && rb[half][q] != (int)0x80000000 &&
+                    extend_zdrop_step(best, first_row + q, rb[half][q], fc[half][q] - l, Z, price_ref, price_read))
+                    T = first_row + q;
+            }
+            int T_wave = T;
+#pragma unroll
+            for (int dd = G / 2; dd >= 1; dd >>= 1) {
+                const int other = __shfl_xor(T_wave, dd, kWave);
+                T_wave = other < T_wave ? other : T_wave;
+            }
+            // 4. the running best just before T, from the lane that holds T; without a drop the inclusive total, from the last lane
+            if (T_wave != kExtendZdropNone ? T == T_wave : l == G - 1) {
+                rec[0] = best.m;
+                rec[1] = best.i + 1;                      // half-open ends; the anchor is three zeros
+                rec[2] = best.j + 1;
+                drop_rows[pair] = T_wave;
+            }
+            // 5. the read-end score, as without the key (the closing kernel makes it unreached where T < Rp)
+            const int last_row = Rp[half] - 1 - row0;
+            if (last_row >= 0 && last_row < geo::kRows && last_row / K == l) {
+                int gs = 0, gt = 0;
+#pragma unroll
+                for (int q = 0; q < K; ++q) {
+                    if (q == last_row % K) {
+                        gs = rb[half][q];
+                        gt = fc[half][q];
+                    }
+                }
+                rec[3] = gs;
+                rec[4] = gt - l + 1;
+            }
+            continue;
+        }
         int bv = 0, bq = 0, bcol = 0;
 #pragma unroll
         for (int q = 0; q < K; ++q) {
@@ -414,9 +518,9 @@ extend_wide_lengths_kernel(const uint8_t *reads, const uint8_t *refs, long long 
 }
 
 // The merged partial records -> the call's records; a read without an ACGT byte is five zeros (no strip wrote its read-end score)
-// band_half < 0: the unbanded sweep.
+// band_half < 0: the unbanded sweep.  drop_rows (null: the key extend_zdrop is off): the read end of a pair that dropped is unreached.
 __global__ void __launch_bounds__(256)
-extend_wide_records_kernel(const int *partial, const int *lens, ExtendRec *extend, long long n, int band_half) {
+extend_wide_records_kernel(const int *partial, const int *lens, ExtendRec *extend, long long n, int band_half, const int *drop_rows) {
     const long long pair = (long long)blockIdx.x * 256 + threadIdx.x;
     if (pair >= n) return;
     const int *rec = partial + kExtendWideRecDwords * pair;
@@ -427,7 +531,8 @@ extend_wide_records_kernel(const int *partial, const int *lens, ExtendRec *exten
     r.ref_end = empty ? 0 : rec[2];
     // band_half >= 0 (the banded sweep): an unreached read end in closed form -- the strip that holds row Rp - 1 may have
     // returned before it wrote the pair
-    const bool unreached = band_half >= 0 && extend_band_unreached(lens[2 * pair], lens[2 * pair + 1], band_half);
+    const bool unreached = (band_half >= 0 && extend_band_unreached(lens[2 * pair], lens[2 * pair + 1], band_half)) ||
+                           (drop_rows && extend_zdrop_unreached(drop_rows[pair], lens[2 * pair]));
     r.gscore = empty ? 0 : (unreached ? VALIGN_HIP_EXTEND_UNREACHED : rec[3]);
     r.gref_end = empty || unreached ? 0 : rec[4];
     extend[pair] = r;

@@ -508,6 +508,14 @@ VALIGN_EXPORT int valign_hip_set_extend_band_align(valign_hip_engine *e, int on)
     return flat_guard([&] { e->impl->set_extend_band_align(on); });
 }
 
+VALIGN_EXPORT int valign_hip_set_extend_zdrop(valign_hip_engine *e, int Z) {
+    if (!e) {
+        g_last_error = "null engine";
+        return 1;
+    }
+    return flat_guard([&] { e->impl->set_extend_zdrop(Z); });
+}
+
 VALIGN_EXPORT int valign_hip_set_trace_checkpoints(valign_hip_engine *e, int on) {
     if (!e) {
         g_last_error = "null engine";
