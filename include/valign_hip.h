@@ -827,6 +827,35 @@ int valign_hip_set_extend_band_align(valign_hip_engine *e, int on);
  * "ran_extend" / "ran_extend_align" keep "wide" / "band".  tests/extend_zdrop_ref.py restates the definition in numpy.          */
 int valign_hip_set_extend_zdrop(valign_hip_engine *e, int Z);
 
+/* Extension Z-drop on the int16 register sweep (key extend_zdrop_rows; flat API only).  The sentences of the section above that say
+ * "KNOWN: the int16 register sweep has no Z-drop form" and "NOT BUILT: a Z-drop form of the int16 register sweep" are qualified
+ * here: under this key that form is built, for scores and for unbanded alignments.  The rule, the record and the limits are those
+ * of extend_zdrop, word for word; only where the call runs changes.
+ *   on = 0 (default): every call runs or is refused exactly as stated above, "ran_extend": "wide" for unbanded calls under Z > 0 and
+ *     both "extend_zdrop:" texts included.
+ *   on = 1: read by valign_hip_score_extend_* and valign_hip_align_extend_* only, and only where extend_zdrop > 0 and band_width == 0.
+ *     Z = 0 under the key is the call without either key.  Other values are refused with "extend_zdrop_rows must be 0 or 1".
+ * ROUTES under on = 1, Z > 0, band_width == 0 (versalignlib_amd/csrc/extend_zdrop.h: extend_zdrop_rows_choice,
+ * extend_zdrop_rows_align_choice).  opt & 0xF == 1 and traceback_policy = 1 are refused first, with their texts.
+ *   scores: where the call without extend_zdrop runs the register sweep it runs there ("ran_extend": "rows"), score_width = 16
+ *     included; everything else answers as under extend_zdrop alone -- "wide", or its refusals: score_width = 32, cells that leave
+ *     int16 and reads of more than 1,024 rows run "wide".
+ *   alignments: where the call without extend_zdrop runs the register sweep it runs there ("ran_extend_align": "rows"): unbanded
+ *     Z-dropped extension alignments.  Every other unbanded call is refused with one "extend_zdrop:" text, which says that the int32
+ *     route of unbanded extension alignments has no Z-drop form.  The banded route answers as above.
+ * HOW.  The register sweep ends with every row's maximum and first column in registers, so the drop row is decided after the last
+ * step: each lane combines its rows, an exclusive prefix arg-max runs over the lanes of the pair's group, each lane replays its rows
+ * from its prefix, and T is the smallest row any lane answers (extend_zdrop.h states why that is the serial rule's T).  No cell, no
+ * back pointer and no step of the sweep changes; every cell is still swept (no in-sweep stop).  An alignment's walk starts in the
+ * best cell before T, from where it only moves up and left; the read end is picked only where nothing dropped.
+ *   limits ....... the register route runs only where every cell stays inside int16, so 0 <= M - m_i <= 65535; 0 <= pen < 2^30 as
+ *                  above; M - m_i - pen lies in (-2^30, 2^16) and Z <= 2^30: int32 throughout.
+ * NOT BUILT: an in-sweep stop; a Z-drop form of the int32 route of unbanded extension alignments; X-drop.
+ * valign_hip_describe: "extend_zdrop_rows" is the key.  On this route "ran_extend" / "ran_extend_align" are "rows" with the
+ * geometry beside them, "ran_extend_zdrop" is Z and "extend_zdrop_skipped_waves" is 0 -- the route has no strips.
+ * tests/extend_zdrop_ref.py (band_width = 0) restates the records, tests/extend_align_ref.py on the reads cut at T the alignments. */
+int valign_hip_set_extend_zdrop_rows(valign_hip_engine *e, int on);
+
 /* Page-lock a host range and map it for the device (hipHostRegister behind a C symbol, so that an FFI caller needs no
  * HIP binding).  valign_hip_align_host into result buffers that lie inside a registered range -- or inside memory the
  * caller page-locked itself -- skips the library's pinned staging and its host-side copy: the device's copy engine

@@ -13,7 +13,10 @@ scoring and band take turns, round after round; every call is timed with events 
 per leg the median and the minimum over all rounds are printed, then a JSON summary.  The prediction (profiles/
 r31_extend_zdrop.txt) for the dropping legs is the Z = 0 time of the same inputs x the share of the sweep's steps in the strips that
 run, which the tool prints from the count of skipped waves.  --short: 150 x 500, 65,536 pairs, unbanded under Z = 400 against the
-register sweep without the key."""
+register sweep without the key.  --rows: the same shape and pairs under the key extend_zdrop_rows -- the register sweep with both
+keys off (the baseline), Z = 2^29 and Z = 400 on the register sweep's ZDROP instances, the same two on today's "wide" route (the key
+off), and baseline, Z = 2^29 and Z = 400 for align_extend_device (end_bonus -1); Z = 400 runs on pairs whose homology ends at row 40
+(A against C from there: the drop falls near row 140).  The legs of a scoring take turns, round after round."""
 import argparse
 import json
 import statistics
@@ -47,6 +50,60 @@ def _engine(hipkernel, rows, cols, sc, band, Z, align):
     return eng
 
 
+def rows_legs(args, torch, hipkernel):
+    rows, cols, n, end = 150, 500, 65536, 40
+    reads, refs = _batch(rows, cols, n)
+    cut, cut_refs = reads.copy(), refs.copy()
+    cut[:, end:] = ord("A")
+    cut_refs[:, end:] = ord("C")
+    inputs = {"whole": (torch.from_numpy(reads).cuda(), torch.from_numpy(refs).cuda()), "ends": (torch.from_numpy(cut).cuda(), torch.from_numpy(cut_refs).cuda())}
+    summary = {}
+    for name, sc in _scorings(LIN, AFF):
+        legs = {}
+        #            inputs   Z      extend_zdrop_rows  alignments
+        for leg_key in (("whole", 0, 0, False), ("whole", NEVER, 1, False), ("ends", 0, 0, False), ("ends", 400, 1, False), ("whole", NEVER, 0, False), ("ends", 400, 0, False),
+                        ("whole", 0, 0, True), ("whole", NEVER, 1, True), ("ends", 0, 0, True), ("ends", 400, 1, True)):
+            what, Z, key, align = leg_key
+            eng = hipkernel.Engine(rows, cols, sc)
+            eng.set_extend_zdrop(Z)
+            eng.set_extend_zdrop_rows(key)
+            rd, rf = inputs[what]
+            leg = {"eng": eng, "medians": [], "mins": []}
+            if align:
+                leg["out"] = eng.align_extend_device(0, rd, rf, end_bonus=-1, ops_stride=64)
+                leg["call"] = lambda e=eng, a=rd, b=rf, o=leg["out"]: e.align_extend_device(0, a, b, end_bonus=-1, ops_stride=64, out=o)
+            else:
+                leg["out"] = torch.empty((n, 5), dtype=torch.int32, device="cuda")
+                leg["call"] = lambda e=eng, a=rd, b=rf, o=leg["out"]: e.score_extend_device(0, a, b, out=o)
+            legs[leg_key] = leg
+        for _ in range(args.rounds):
+            for leg in legs.values():
+                med, best = _timed(leg["call"], args.reps)
+                leg["medians"].append(med)
+                leg["mins"].append(best)
+        rec = {}
+        for (what, Z, key, align), leg in legs.items():
+            d = leg["eng"].describe(0, n)
+            ext = (leg["out"][2] if align else leg["out"]).to(torch.int64)
+            rec[what, Z, key, align] = {"ms_median": round(statistics.median(leg["medians"]), 4), "ms_min": round(min(leg["mins"]), 4),
+                                        "round_medians": [round(m, 4) for m in leg["medians"]], "ran": d["ran_extend_align" if align else "ran_extend"],
+                                        "geometry": d["ran_extend_align_geometry" if align else "ran_extend_geometry"],
+                                        "dropped": int((ext[:, 3] == hipkernel.EXTEND_UNREACHED).sum()), "read_end_median": int(ext[:, 1].median())}
+            leg["eng"].close()
+        for align in (False, True):
+            for what, Z in (("whole", NEVER), ("ends", 400)):
+                base, on = rec[what, 0, 0, align], rec[what, Z, 1, align]
+                line = "%-7s 150 x 500 %-10s %-5s Z = 0 %8.4f ms (min %8.4f, %s %s) | Z = %-9d rows %8.4f ms (min %8.4f, %s) x %.4f, %d dropped, read_end median %d" % (
+                    name, "alignments" if align else "scores", what, base["ms_median"], base["ms_min"], base["ran"], base["geometry"], Z, on["ms_median"], on["ms_min"], on["ran"],
+                    on["ms_median"] / base["ms_median"], on["dropped"], on["read_end_median"])
+                if not align:
+                    wide = rec[what, Z, 0, False]
+                    line += " | key off %8.4f ms (min %8.4f, %s): rows %.2f x faster" % (wide["ms_median"], wide["ms_min"], wide["ran"], wide["ms_median"] / on["ms_median"])
+                print(line, flush=True)
+        summary[name] = {"%s/%d/%d/%s" % (k[0], k[1], k[2], "align" if k[3] else "scores"): v for k, v in rec.items()}
+    print(json.dumps({"tool": "extend_zdrop_bench", "mode": "rows", "shape": [rows, cols, n], "summary": summary}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -54,9 +111,12 @@ def main():
     ap.add_argument("--pairs", type=int, default=4096)
     ap.add_argument("--align", action="store_true", help="banded extension alignments in the place of the scores")
     ap.add_argument("--short", action="store_true", help="150 x 500 under the key against the register sweep without it")
+    ap.add_argument("--rows", action="store_true", help="150 x 500 under extend_zdrop_rows: scores and alignments against the register sweep without the keys and against the wide route")
     args = ap.parse_args()
     import torch
     from versalignlib_amd import hipkernel
+    if args.rows:
+        return rows_legs(args, torch, hipkernel)
     if args.short:
         rows, cols, n = 150, 500, 65536
         reads, refs = _batch(rows, cols, n)

@@ -14,7 +14,9 @@ forms at several scales, the engine's own or a forced geometry, planted extensio
 (extend_band = 1 under a band, against tests/extend_band_ref.py: random shapes of one to four 512-row strips, random bands from
 w = 0 to the unbanded limit, the four gap forms, score_width 0 / 32, extend_wide 0 / 1, ragged tails); `--kind extend_zdrop` draws
 the same cases with a random Z of extend_zdrop, a third of them without the band (against tests/extend_zdrop_ref.py: records and
-the count of skipped waves); `--kind extend_band_align`
+the count of skipped waves); `--kind extend_zdrop_rows` draws the register-sweep cases of `--kind extend` under extend_zdrop_rows = 1
+with a random Z, as scores or as alignments (against tests/extend_zdrop_ref.py with band_width = 0, and tests/extend_align_ref.py on
+the reads cut at the drop rows); `--kind extend_band_align`
 draws the same shapes and bands for banded extension alignments (extend_band_align = 1: align_extend_device / _host against
 tests/extend_band_align_ref.py, from the best cell, from the read end and at bonus 20, extended, ops_stride, pointer_scratch_cap_mb);
 `--kind extend_align`
@@ -492,6 +494,86 @@ def run_extend_zdrop(c):
         eng.close()
 
 
+def draw_extend_zdrop_rows(rng):
+    """--kind extend_zdrop_rows: draw_extend's register-sweep cases -- shapes up to the register limit, the four gap forms, the
+    engine's own or a forced full geometry -- under extend_zdrop_rows = 1 with a random Z, as scores or, for half, as alignments with
+    an end bonus"""
+    c = None
+    while c is None or c.get("wide"):
+        c = draw_extend(rng)
+    top = c["scoring"][0] * min(c["R"], c["F"])
+    c.update(n=min(c["n"], 60), Z=int(rng.choice([1, 2, int(rng.integers(1, 40)), int(rng.integers(1, 400)), int(rng.integers(1, 4 * top + 2)), 1 << 29, 1 << 30])),
+             align=bool(rng.random() < 0.5), bonus=int(rng.choice([-1, 0, int(rng.integers(0, top + 2)), 2 ** 31 - 1])), extended=bool(rng.random() < 0.5))
+    return c
+
+
+def run_extend_zdrop_rows(c):
+    """one case of the register sweep's ZDROP instances: records (device, for some the host entry too) against
+    tests/extend_zdrop_ref.py with band_width = 0, or alignments -- records, ops, extension records -- against
+    tests/extend_align_ref.py on the reads cut at the reference's drop rows, a dropped pair from its best cell.  Half of the pairs
+    carry a run of A against C, so that rows drop."""
+    rng = np.random.default_rng(c["seed"])
+    R, F, n, Z = c["R"], c["F"], c["n"], c["Z"]
+    bases = np.frombuffer(b"ACGT", np.uint8)
+    reads, refs = bases[rng.integers(0, 4, (n, R))], bases[rng.integers(0, 4, (n, F))]
+    for p in range(n):
+        if p % 3 < 2:
+            L, shift = int(rng.integers(1, min(R, F) + 1)), (int(rng.integers(0, 3)) if p % 3 == 1 else 0)
+            span = min(L, F - shift)
+            if span > 0:
+                refs[p, shift:shift + span] = reads[p, :span]
+        if p % 4 < 2:
+            a, g = int(rng.integers(0, R)), int(rng.integers(1, 40))
+            reads[p, a:a + g] = ord("A")
+            refs[p, a:a + g] = ord("C")
+        if rng.random() < 0.3:
+            reads[p, int(rng.integers(0, R + 1)):] = rng.choice([0, ord("N")])
+        if rng.random() < 0.3:
+            refs[p, int(rng.integers(0, F + 1)):] = rng.choice([0, ord("N")])
+    sc = hipkernel.Scoring.make(*c["scoring"])
+    exp, T = extend_zdrop_ref.extend(reads, refs, sc, Z, 0, affine=c["affine"], chunk=64)
+    eng = hipkernel.Engine(R, F, sc, group_lanes=c["geometry"][0], rows_per_lane=c["geometry"][1])
+    try:
+        eng.set_extend_zdrop(Z)
+        eng.set_extend_zdrop_rows(1)
+        d_reads, d_refs = torch.from_numpy(reads).cuda(), torch.from_numpy(refs).cuda()
+        if not c["align"]:
+            got = eng.score_extend_device(0, d_reads, d_refs)
+            torch.cuda.synchronize()
+            d = eng.describe(0, n)
+            if d["ran_extend"] != "rows" or d["ran_extend_zdrop"] != Z or d["extend_zdrop_skipped_waves"] != 0:
+                return "score_extend_device ran %s under Z = %d" % (d["ran_extend"], d["ran_extend_zdrop"])
+            if not np.array_equal(got.cpu().numpy().astype(np.int64), exp):
+                return "score_extend_device differs (rows, Z = %d)" % Z
+            if c["host"]:
+                h = eng.score_extend_host(0, reads, refs, threads=c["threads"])
+                if not np.array_equal(np.stack([h[k] for k in hipkernel.extend_dtype().names], axis=1).astype(np.int64), exp):
+                    return "score_extend_host differs (rows, Z = %d)" % Z
+            return None
+        Rp = extend_ref.trimmed_lengths(reads)
+        best, chosen = extend_align_ref.align(extend_zdrop_ref.cut_reads(reads, T), refs, sc, c["affine"], end_bonus=(-1, c["bonus"]), extended=c["extended"])
+        dropped = T < Rp
+        exp_recs = np.where(dropped[:, None], best[0], chosen[0])
+        exp_ops = [best[1][k] if dropped[k] else chosen[1][k] for k in range(n)]
+        stride = max([len(o) for o in exp_ops] + [1]) + 1
+        recs, ops, ext = eng.align_extend_device(0, d_reads, d_refs, end_bonus=c["bonus"], extended=c["extended"], ops_stride=stride)
+        torch.cuda.synchronize()
+        d = eng.describe(0, n)
+        if d["ran_extend_align"] != "rows" or d["ran_extend_zdrop"] != Z:
+            return "align_extend_device ran %s under Z = %d" % (d["ran_extend_align"], d["ran_extend_zdrop"])
+        if not np.array_equal(recs.cpu().numpy().astype(np.int64), exp_recs):
+            return "align_extend_device: records differ (Z = %d)" % Z
+        got_ops = ops.cpu().numpy().view(np.uint32)
+        for k, want in enumerate(exp_ops):
+            if got_ops[k, :len(want)].tolist() != want:
+                return "align_extend_device: ops of pair %d differ (Z = %d)" % (k, Z)
+        if not np.array_equal(ext.cpu().numpy().astype(np.int64), exp):
+            return "align_extend_device: extension records differ (Z = %d)" % Z
+        return None
+    finally:
+        eng.close()
+
+
 def draw_extend_align(rng):
     """--kind extend_align: draw_extend's register-sweep cases (shape, scoring inside the signed int16 bound, the engine's own or a
     forced full geometry) with an end bonus -- none, zero, small, of the scale of the scores, or "always the read end" --, extended,
@@ -671,7 +753,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--first", type=int, default=0)
     ap.add_argument("--verbose", action="store_true")
-    ap.add_argument("--kind", choices=["subopt", "sequence", "span_cigar", "extend", "extend_band", "extend_zdrop", "extend_align", "extend_band_align"], default=None,
+    ap.add_argument("--kind", choices=["subopt", "sequence", "span_cigar", "extend", "extend_band", "extend_zdrop", "extend_zdrop_rows", "extend_align", "extend_band_align"], default=None,
                     help="draw cases of this kind only (default: the mix); sequence: one engine through tests/engine_sequences.py's sequences "
                          "(fifteen keys, extend_band and extend_band_align among them; nine families of calls, the banded extension routes included)")
     a = ap.parse_args()
@@ -682,7 +764,8 @@ def main():
     i = done = 0
     while time.time() - t0 < a.seconds:
         own = {"span_cigar": (draw_span_cigar, run_span_cigar), "extend": (draw_extend, run_extend), "extend_band": (draw_extend_band, run_extend_band), "extend_align": (draw_extend_align, run_extend_align),
-               "extend_band_align": (draw_extend_band_align, run_extend_band_align), "extend_zdrop": (draw_extend_zdrop, run_extend_zdrop)}.get(a.kind)
+               "extend_band_align": (draw_extend_band_align, run_extend_band_align), "extend_zdrop": (draw_extend_zdrop, run_extend_zdrop),
+               "extend_zdrop_rows": (draw_extend_zdrop_rows, run_extend_zdrop_rows)}.get(a.kind)
         c = own[0](rng) if own else draw(rng, a.kind)
         if i >= a.first:
             if a.verbose:

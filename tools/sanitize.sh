@@ -78,6 +78,10 @@ echo "== extend_zdrop.h (the choices under extend_zdrop, the drop step, the scan
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/extend_zdrop_rules_check.cpp" -o "$OUT/extend_zdrop_rules_asan"
 "$OUT/extend_zdrop_rules_asan"
 
+echo "== extend_zdrop.h (extend_zdrop_rows: the lane form of the drop rule against the serial loop, the choices under the key) under AddressSanitizer + UBSan"
+g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/extend_zdrop_rows_rules_check.cpp" -o "$OUT/extend_zdrop_rows_rules_asan"
+"$OUT/extend_zdrop_rows_rules_asan"
+
 echo "== base_classes.h (the byte classifier of the kernels' set-up) under AddressSanitizer + UBSan"
 g++ -std=c++17 $SAN -Wall -Werror -I"$CS" "$R/tests/base_classes_check.cpp" -o "$OUT/base_classes_asan"
 "$OUT/base_classes_asan"

@@ -75,7 +75,7 @@ def build_host(force=False):
     return HOST_LIB
 
 
-KERNEL_PART_DEPS = ["kernel_part.hip", "kernel_instances.hip.h", "placed_kernels.hip.h", "extend_kernels.hip.h", "extend_align_kernels.hip.h", "dp_kernels.hip.h", "base_classes.h", "cell_constants.h", "lane_map.h", "trace_kernels.hip.h", "band_window.h", "ckpt_plan.h", "strip_plan.h", "cell_rules.h", "extend_band_plan.h", "extend_band_align_plan.h"]
+KERNEL_PART_DEPS = ["kernel_part.hip", "kernel_instances.hip.h", "placed_kernels.hip.h", "extend_kernels.hip.h", "extend_align_kernels.hip.h", "dp_kernels.hip.h", "base_classes.h", "cell_constants.h", "lane_map.h", "trace_kernels.hip.h", "band_window.h", "ckpt_plan.h", "strip_plan.h", "cell_rules.h", "extend_band_plan.h", "extend_band_align_plan.h", "extend_zdrop.h"]
 
 
 def build_hip(force=False, extra_flags=(), jobs=None):

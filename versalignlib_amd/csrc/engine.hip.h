@@ -92,6 +92,8 @@ struct Geometry {
     const void *(*subopt)(int track, int gaps);      // suboptimal-score kernels: the full geometries', nullptr elsewhere
     const void *(*extend)(int gaps);                 // extension-score kernels (extend_kernels.hip.h): the full geometries', nullptr elsewhere
     const void *(*extend_align)(int affine);         // extension-alignment fills (extend_align_kernels.hip.h): the full geometries', nullptr elsewhere
+    const void *(*extend_zdrop)(int gaps);           // ... and the ZDROP forms of both (key extend_zdrop_rows): wherever the plain form exists
+    const void *(*extend_align_zdrop)(int affine);
 };
 
 template <int G, int K>
@@ -119,14 +121,16 @@ constexpr void set_fast_kernels(Geometry &g) {
 
 template <int G, int K>
 constexpr Geometry fast_geometry() {
-    Geometry g{G, K, false, &wave_lds<G, K>, {}, {}, &placed_kernel<G, K, false>, &subopt_kernel<G, K, false>, &extend_kernel<G, K, false>, &extend_align_kernel<G, K, false>};
+    Geometry g{G, K, false, &wave_lds<G, K>, {}, {}, &placed_kernel<G, K, false>, &subopt_kernel<G, K, false>, &extend_kernel<G, K, false>, &extend_align_kernel<G, K, false>,
+               &extend_zdrop_kernel<G, K, false>, &extend_align_zdrop_kernel<G, K, false>};
     set_fast_kernels<G, K>(g);
     return g;
 }
 
 template <int G, int K>
 constexpr Geometry full_geometry() {
-    Geometry g{G, K, true, &wave_lds<G, K>, {}, {}, &placed_kernel<G, K, true>, &subopt_kernel<G, K, true>, &extend_kernel<G, K, true>, &extend_align_kernel<G, K, true>};
+    Geometry g{G, K, true, &wave_lds<G, K>, {}, {}, &placed_kernel<G, K, true>, &subopt_kernel<G, K, true>, &extend_kernel<G, K, true>, &extend_align_kernel<G, K, true>,
+               &extend_zdrop_kernel<G, K, true>, &extend_align_zdrop_kernel<G, K, true>};
     set_fast_kernels<G, K>(g);
     g.fill[0][kFillLinear] = (const void *)&align_fill_kernel<G, K, kAlgSW, false>;
     g.fill[0][kFillLinearSym] = (const void *)&align_fill_kernel<G, K, kAlgSW, true>;
@@ -316,6 +320,15 @@ public:
         extend_zdrop_ = Z;
     }
     int extend_zdrop() const { return extend_zdrop_; }
+    // The Z-drop on the int16 register sweep (opt-in; include/valign_hip.h has the definition, extend_zdrop.h the routes and the
+    // rule's lane form): 1 = unbanded extension calls under extend_zdrop > 0 run the register sweep's ZDROP instances wherever the
+    // call without extend_zdrop runs the register sweep; 0 = they run as extend_zdrop alone says (default).  Read by
+    // valign_hip_score_extend_* and valign_hip_align_extend_* only, and only where extend_zdrop > 0 and band_width = 0.
+    void set_extend_zdrop_rows(int on) {
+        if (!extend_zdrop_rows_key_ok(on)) throw std::runtime_error(kExtendZdropRowsKeyRange);
+        extend_zdrop_rows_ = on == 1;
+    }
+    int extend_zdrop_rows() const { return extend_zdrop_rows_ ? 1 : 0; }
     // Checkpointed traceback of long-read alignments (opt-in; ckpt_plan.h): 1 = calls that take the plain row strips (unbanded,
     // int16 cells, traceback_policy 0; both algorithms, linear and affine gaps) keep one boundary row per strip and ONE strip's
     // pointer region instead of every pointer, and re-fill strip after strip along the walk -- identical results, a scratch that
@@ -1070,6 +1083,8 @@ private:
     bool extend_band_ = false;
     bool extend_band_align_ = false;
     int extend_zdrop_ = 0;
+    bool extend_zdrop_rows_ = false;
+    bool ran_extend_zdrop_rows_ = false;                 // the last extension call under Z > 0 ran the register sweep: no strips, no skipped waves
     int ran_extend_zdrop_ = 0;                           // the Z the last extension call ran under, 0 without the key (describe)
     bool trace_checkpoints_ = false;
     int score_width_ = 0;

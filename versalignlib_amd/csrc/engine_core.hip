@@ -168,7 +168,8 @@ std::string Engine::describe(int opt, long long n) const {
                                    std::to_string(ran_extend_align_chunks_) + ", \"ran_cigar_lanes\": " + std::to_string(ran_cigar_lanes_));
     // the Z-drop of extension calls (engine_extend.hip): the key, the Z the last extension call ran under, the waves that skipped a strip in it
     out.insert(out.size() - 1, ", \"extend_zdrop\": " + std::to_string(extend_zdrop()) + ", \"ran_extend_zdrop\": " + std::to_string(ran_extend_zdrop_) +
-                                   ", \"extend_zdrop_skipped_waves\": " + std::to_string(extend_zdrop_skipped_waves()));
+                                   ", \"extend_zdrop_skipped_waves\": " + std::to_string(extend_zdrop_skipped_waves()) +
+                                   ", \"extend_zdrop_rows\": " + std::to_string(extend_zdrop_rows()));
     if (ran_score_sym_affine_)         // only where the last score call ran the int16 symmetric affine SW kernel
         out.insert(out.size() - 1, std::string(", \"ran_score_sym_affine\": \"") + ran_score_sym_affine_ + "\", \"ran_score_sym_affine_frame\": \"" +
                                        ran_score_sym_affine_frame_ + "\", \"ran_score_sym_affine_scores\": \"" + ran_score_sym_affine_scores_ + "\"");

@@ -8,6 +8,9 @@
 // BANDED instances.  The rule is asked through extend_zdrop_choice (extend_zdrop.h), which wraps extend_choice(in, alg, facts, G, K):
 // under extend_zdrop > 0 the strip sweep or nothing, and the
 // description carries the sweep's ZDROP instances, a drop row per pair behind the trimmed lengths and the counter of skipped waves.
+// Under extend_zdrop_rows = 1 the rule is extend_zdrop_rows_choice, which wraps extend_zdrop_choice(in, alg, facts, G, K, Z): an
+// unbanded call under Z > 0 that would run the register sweep without Z runs its ZDROP instance (Geometry::extend_zdrop) on the
+// same plan, LDS and launch -- the drop is decided in the kernel's epilogue, nothing else changes.
 // The host-pointer path is record_pipeline (engine_score.hip), 20-byte records on the way back.
 // extend_wide_lengths_kernel and extend_wide_records_kernel (not templates) are defined in this translation unit.
 #define VALIGN_TU_EXTEND 1
@@ -23,14 +26,15 @@ const LaunchPlan &Engine::extend_plan_for(int alg, int &gaps, PlacedRoute &route
     const PlacedFacts facts = placed_facts();
     RuleInputs in = rule_inputs();
     in.no_f16 = true;                   // int16 cells: the gap form is one of the four integer ones
-    const PlacedChoice choice = extend_zdrop_choice(in, alg, facts, base.geo ? base.geo->G : 0, base.geo ? base.geo->K : 0, extend_zdrop_);
+    const PlacedChoice choice = extend_zdrop_rows_choice(in, alg, facts, base.geo ? base.geo->G : 0, base.geo ? base.geo->K : 0, extend_zdrop_, extend_zdrop_rows_);
     if (choice.route == PlacedRoute::Refused) throw std::runtime_error(choice.reason);
     route = choice.route;
     if (route == PlacedRoute::Wide || route == kPlacedRouteBand) return base;        // (nothing launches on the plan)
     gaps = score_gap_form(in, kAlgSW, R_, F_, base.geo->G * base.geo->K);
-    if (base.geo->extend(gaps)) return base;
+    // (a geometry carries the ZDROP form of an instance exactly where it carries the plain one)
+    if (base.geo->extend(gaps) && base.geo->extend_zdrop(gaps)) return base;
     if (!fallback_plan_.geo) fallback_plan_ = choose_plan(R_, F_, 0, 0, false, true);
-    if (fallback_plan_.long_mode || !fallback_plan_.geo->extend(gaps)) throw std::runtime_error("no extension-score kernel for this mode");
+    if (fallback_plan_.long_mode || !fallback_plan_.geo->extend(gaps) || !fallback_plan_.geo->extend_zdrop(gaps)) throw std::runtime_error("no extension-score kernel for this mode");
     return fallback_plan_;
 }
 
@@ -40,6 +44,7 @@ void Engine::score_extend_device(int opt, long long n, const uint8_t *d_reads, c
     ran_extend_ = "none";
     ran_extend_geo_ = nullptr;
     ran_extend_zdrop_ = 0;
+    ran_extend_zdrop_rows_ = false;
     int gaps = 0;
     PlacedRoute route = PlacedRoute::Refused;
     const LaunchPlan &plan = extend_plan_for(alg, gaps, route);
@@ -59,7 +64,12 @@ void Engine::score_extend_device(int opt, long long n, const uint8_t *d_reads, c
     a.F = F_;
     put_lds(a, plan.lds);
     put_scoring(a);
-    const void *fn = plan.geo->extend(gaps);
+    // keys extend_zdrop > 0 and extend_zdrop_rows = 1 (the route is Rows, so no band is set): the ZDROP instance
+    const bool dropping = extend_zdrop_rows_ && extend_zdrop_on(extend_zdrop_);
+    a.Z = dropping ? extend_zdrop_ : 0;
+    ran_extend_zdrop_ = a.Z;
+    ran_extend_zdrop_rows_ = dropping;
+    const void *fn = dropping ? plan.geo->extend_zdrop(gaps) : plan.geo->extend(gaps);
     ran_extend_geo_ = plan.geo;
     const long long ppb = (long long)plan.pairs_per_wave * plan.waves_per_block;
     const long long blocks = (n + ppb - 1) / ppb;
@@ -120,13 +130,14 @@ Engine::PlacedSweep Engine::extend_band_sweep() const { return extend_wide_sweep
 // An extension call on the strip sweep starts: what describe() reports of the key, and the counter at zero on the call's stream
 void Engine::start_extend_zdrop(hipStream_t stream) {
     ran_extend_zdrop_ = extend_zdrop_;
+    ran_extend_zdrop_rows_ = false;
     if (!extend_zdrop_on(extend_zdrop_)) return;
     if (!d_zdrop_skipped_.get()) d_zdrop_skipped_.reserve(sizeof(unsigned), "extend_zdrop skipped waves");
     hip_check(hipMemsetAsync(d_zdrop_skipped_.get(), 0, sizeof(unsigned), stream), "hipMemsetAsync(extend_zdrop skipped waves)");
 }
 
 long long Engine::extend_zdrop_skipped_waves() const {
-    if (!extend_zdrop_on(ran_extend_zdrop_)) return 0;
+    if (!extend_zdrop_on(ran_extend_zdrop_) || ran_extend_zdrop_rows_) return 0;       // (the register sweep has no strips)
     unsigned waves = 0;
     hip_check(hipSetDevice(device_), "hipSetDevice");
     hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");

@@ -11,7 +11,9 @@
 // scratch and both entry points are shared: only the chunk body differs.  The host entry delivers through the packed path of
 // engine_cigar.hip, the extension records between the records and the ops.
 // Under extend_zdrop > 0 the rule is extend_zdrop_align_choice (extend_zdrop.h), which wraps extend_align_choice(...): the Band route
-// or nothing, its fill the ZDROP instance, the ends kernel with the chunk's drop rows.
+// or nothing, its fill the ZDROP instance, the ends kernel with the chunk's drop rows.  Under extend_zdrop_rows = 1 the rule is
+// extend_zdrop_rows_align_choice, which wraps extend_zdrop_align_choice(in, alg, facts, G, K, Z): an unbanded call on the register
+// route runs the fill's ZDROP instance (Geometry::extend_align_zdrop) -- same plan, scratch, walk and encoder.
 #define VALIGN_TU_EXTEND_ALIGN 1
 #include "engine.hip.h"
 #include "extend_band_align_kernels.hip.h"
@@ -23,13 +25,13 @@ const LaunchPlan &Engine::extend_align_plan_for(int alg, ExtendAlignChoice &choi
     const PlacedFacts facts = placed_facts();
     RuleInputs in = rule_inputs();
     in.no_f16 = true;                   // int16 cells
-    choice = extend_zdrop_align_choice(in, alg, facts, base.geo ? base.geo->G : 0, base.geo ? base.geo->K : 0, extend_zdrop_);
+    choice = extend_zdrop_rows_align_choice(in, alg, facts, base.geo ? base.geo->G : 0, base.geo ? base.geo->K : 0, extend_zdrop_, extend_zdrop_rows_);
     if (choice.route == PlacedRoute::Refused) throw std::runtime_error(choice.reason);
     if (choice.route == kPlacedRouteBand) return base;                  // (nothing launches on the plan)
-    if (base.geo->extend_align(sc_.affine ? 1 : 0)) return base;
+    if (base.geo->extend_align(sc_.affine ? 1 : 0) && base.geo->extend_align_zdrop(sc_.affine ? 1 : 0)) return base;
     if (!fallback_plan_.geo) fallback_plan_ = choose_plan(R_, F_, 0, 0, false, true);
     if (fallback_plan_.long_mode || !fallback_plan_.geo->extend_align(sc_.affine ? 1 : 0)) throw std::runtime_error("no extension-alignment kernel for this mode");
-    choice = extend_zdrop_align_choice(in, alg, facts, fallback_plan_.geo->G, fallback_plan_.geo->K, extend_zdrop_);
+    choice = extend_zdrop_rows_align_choice(in, alg, facts, fallback_plan_.geo->G, fallback_plan_.geo->K, extend_zdrop_, extend_zdrop_rows_);
     return fallback_plan_;
 }
 
@@ -171,7 +173,12 @@ void Engine::extend_align_chunk(const LaunchPlan &plan, const ExtendAlignChoice 
     f.end_bonus = end_bonus;
     put_lds(f, plan.lds);
     put_scoring(f);
-    const void *fn = plan.geo->extend_align(sc_.affine ? 1 : 0);
+    // keys extend_zdrop > 0 and extend_zdrop_rows = 1 (the route is Rows: without the second key the rule refused the call)
+    const bool dropping = extend_zdrop_rows_ && extend_zdrop_on(extend_zdrop_);
+    f.Z = dropping ? extend_zdrop_ : 0;
+    ran_extend_zdrop_ = f.Z;
+    ran_extend_zdrop_rows_ = dropping;
+    const void *fn = dropping ? plan.geo->extend_align_zdrop(sc_.affine ? 1 : 0) : plan.geo->extend_align(sc_.affine ? 1 : 0);
     ran_extend_align_geo_ = plan.geo;
     const int block_lds = plan.lds.total * plan.waves_per_block;
     raise_block_lds(fn, block_lds);
@@ -216,6 +223,7 @@ void Engine::align_extend_device(int opt, long long n, const uint8_t *d_reads, c
     ran_extend_align_chunks_ = 0;
     ran_cigar_lanes_ = 0;
     ran_extend_zdrop_ = 0;
+    ran_extend_zdrop_rows_ = false;
     check_packed_device_args(extended, ops_stride, d_recs, d_ops);
     const int alg = opt & 0xF;
     if (alg > 1 || n <= 0) return;          // reference: unsupported mode is a silent no-op
@@ -243,6 +251,7 @@ bool Engine::align_extend_host(int opt, int n, const char *const *reads, const c
     ran_extend_align_chunks_ = 0;
     ran_cigar_lanes_ = 0;
     ran_extend_zdrop_ = 0;
+    ran_extend_zdrop_rows_ = false;
     check_packed_host_args(extended, n, recs, ops, ops_cap, offsets, ops_needed);
     const int alg = opt & 0xF;
     if (alg > 1) return true;                       // (the same silent no-op as every entry point)

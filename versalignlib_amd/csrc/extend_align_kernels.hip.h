@@ -41,12 +41,16 @@ struct ExtendAlignArgs {
     short match, mismatch;
     short gap_read, gap_ref;
     short open_read, ext_read, open_ref, ext_ref;
+    int Z;                    // the ZDROP instances: extend_zdrop (> 0)
 };
 
 // a - b modulo 2^16 in each half: zero exactly where the two cells are equal, whatever their signs
 __device__ __forceinline__ s16x2 pk_sub_wrap(s16x2 a, s16x2 b) { return (s16x2)((u16x2)a - (u16x2)b); }
 
-template <int G, int K, bool AFFINE>
+// ZDROP (keys extend_zdrop > 0 and extend_zdrop_rows = 1): the same sweep and pointer stream; the epilogue takes the record from
+// extend_zdrop_rows_record (extend_kernels.hip.h) -- the walk starts in the best cell before the drop row T, from where it only
+// moves up and left, and the end-bonus rule picks the read end only where nothing dropped.
+template <int G, int K, bool AFFINE, bool ZDROP = false>
 __global__ void __launch_bounds__(256)
 align_extend_fill_kernel(const ExtendAlignArgs args) {
     using geo = Geo<G, K>;
@@ -240,6 +244,25 @@ align_extend_fill_kernel(const ExtendAlignArgs args) {
     for (; t < steady_end; ++t) step(std::false_type{}, t);
     for (; t < steps; ++t) step(std::true_type{}, t);
 
+    if constexpr (ZDROP) {
+        const int price_ref = extend_zdrop_price(AFFINE ? args.ext_ref : args.gap_ref), price_read = extend_zdrop_price(AFFINE ? args.ext_read : args.gap_read);
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            int T;
+            const ExtendRec rec = extend_zdrop_rows_record<G, K>(rb, fc, half, lane, l, Rp[half], args.Z, price_ref, price_read, T);
+            const long long pair = w.pair0 + 2 * grp + half;
+            if (l != 0 || pair >= args.n) continue;
+            if (args.extend) args.extend[pair] = rec;
+            const int last_row = Rp[half] - 1;
+            EndCell start{-1, -1, 0, 0};                                 // the empty alignment: M == 0 ends in the anchor
+            if (last_row >= 0 && !extend_zdrop_unreached(T, Rp[half]) && args.end_bonus >= 0 && (long long)rec.gscore + args.end_bonus >= (long long)rec.score)
+                start = EndCell{(short)last_row, (short)(rec.gref_end - 1), (short)rec.gscore, 0};
+            else if (rec.score > 0)
+                start = EndCell{(short)(rec.read_end - 1), (short)(rec.ref_end - 1), (short)rec.score, 0};
+            args.ends[pair] = start;
+        }
+        return;
+    }
     // ---- the best cell > 0 of each pair (write_end_cells: into the wave's LDS table; no pad rows above the read) ----
     FillArgs fa{};
     fa.n = args.n;
@@ -457,6 +480,22 @@ const void *extend_align_kernel(int affine) {
         fill[1] = (const void *)&align_extend_fill_kernel<G, K, true>;
     }
     return affine == 0 || affine == 1 ? fill[affine] : nullptr;
+}
+#endif
+
+// ... and their ZDROP forms: 12 more, on the same six geometries
+template <int G, int K, bool FULL>
+const void *extend_align_zdrop_kernel(int affine);
+
+#ifdef VALIGN_KERNEL_PART_TU
+template <int G, int K, bool FULL>
+const void *extend_align_zdrop_kernel(int affine) {
+    const void *dropping[2] = {};
+    if constexpr (FULL) {
+        dropping[0] = (const void *)&align_extend_fill_kernel<G, K, false, true>;
+        dropping[1] = (const void *)&align_extend_fill_kernel<G, K, true, true>;
+    }
+    return affine == 0 || affine == 1 ? dropping[affine] : nullptr;
 }
 #endif
 

@@ -23,6 +23,7 @@
 #pragma once
 
 #include "cell_rules.h"
+#include "extend_zdrop.h"
 #include "trace_kernels.hip.h"
 
 namespace valign {
@@ -41,12 +42,70 @@ struct ExtendArgs {
     short match, mismatch;
     short gap_read, gap_ref;
     short open_read, ext_read, open_ref, ext_ref;
+    int Z;                    // the ZDROP instances: extend_zdrop (> 0)
 };
 
 // a - b, saturating: the sign is that of the exact difference for any two int16 values
 __device__ __forceinline__ s16x2 pk_sub_sat(s16x2 a, s16x2 b) { return __builtin_elementwise_sub_sat(a, b); }
 
-template <int G, int K, int GAPS>
+// ZDROP (keys extend_zdrop > 0 and extend_zdrop_rows = 1; extend_zdrop.h has the rule, its lane form and why the minimum of the
+// lanes' answers is the serial drop row): the record of one half of the packed registers, decided in the epilogue from rb / fc --
+// the sweep itself does not change.  Every lane of the wave takes part (shuffles); every lane of the group returns the pair's
+// record and T, the first dropping row, Rp where none drops.  Steps: unpack to (m, c = fc - l); the lane's combine; an inclusive
+// scan over the group by __shfl_up, shifted by one lane and seeded with the anchor; the lane's replay; the minimum by an xor
+// butterfly; the record from the lane that holds T (extend_zdrop_record_lane), which is also the lane of row Rp - 1 where T == Rp.
+template <int G, int K>
+__device__ __forceinline__ ExtendRec extend_zdrop_rows_record(const s16x2 (&rb)[K], const s16x2 (&fc)[K], int half, int lane, int l, int Rp, int Z,
+                                                              int price_ref, int price_read, int &T_pair) {
+    int m[K], c[K];
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+        m[q] = half ? rb[q].y : rb[q].x;
+        c[q] = (half ? fc[q].y : fc[q].x) - l;         // step -> column: the border column is -1
+    }
+    const int first_row = l * K;
+    ExtendZdropBest run = extend_zdrop_lane_best(m, c, K, first_row, Rp);
+#pragma unroll
+    for (int dd = 1; dd < G; dd <<= 1) {
+        const ExtendZdropBest before{__shfl_up(run.m, dd, kWave), __shfl_up(run.i, dd, kWave), __shfl_up(run.j, dd, kWave)};
+        if (l >= dd) run = extend_zdrop_combine(before, run);
+    }
+    const ExtendZdropBest upto{__shfl_up(run.m, 1, kWave), __shfl_up(run.i, 1, kWave), __shfl_up(run.j, 1, kWave)};
+    const ExtendZdropBest prefix = l == 0 ? extend_zdrop_anchor() : extend_zdrop_combine(extend_zdrop_anchor(), upto);
+    const ExtendZdropLane mine = extend_zdrop_replay_lane(m, c, K, first_row, Rp, kExtendZdropNone, prefix, Z, price_ref, price_read);
+    int T = mine.T;
+#pragma unroll
+    for (int dd = G / 2; dd >= 1; dd >>= 1) {
+        const int other = __shfl_xor(T, dd, kWave);
+        T = other < T ? other : T;
+    }
+    T = T < Rp ? T : Rp;
+    // row Rp - 1's own entry, in the lane that holds it
+    const int last_q = Rp > 0 ? (Rp - 1) % K : -1;
+    int gs = 0, ge = 0;
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+        if (q == last_q) {
+            gs = m[q];
+            ge = c[q] + 1;                              // half-open: the border column is 0
+        }
+    }
+    const int src = lane - l + (Rp > 0 ? extend_zdrop_record_lane(T, Rp, K) : 0);
+    ExtendRec rec;
+    rec.score = __shfl(mine.best.m, src, kWave);
+    rec.read_end = __shfl(mine.best.i, src, kWave) + 1;       // half-open ends; the anchor is three zeros
+    rec.ref_end = __shfl(mine.best.j, src, kWave) + 1;
+    rec.gscore = __shfl(gs, src, kWave);
+    rec.gref_end = __shfl(ge, src, kWave);
+    if (extend_zdrop_unreached(T, Rp)) {
+        rec.gscore = kExtendZdropUnreached;
+        rec.gref_end = 0;
+    }
+    T_pair = T;
+    return rec;
+}
+
+template <int G, int K, int GAPS, bool ZDROP = false>
 __global__ void __launch_bounds__(256)
 score_extend_kernel(const ExtendArgs args) {
     static_assert(GAPS == kGapLinear || GAPS == kGapSym || GAPS == kGapAffine || GAPS == kGapAffineSym, "extension scores run on int16 cells");
@@ -246,6 +305,18 @@ score_extend_kernel(const ExtendArgs args) {
     for (; t < steady_end; ++t) step(std::false_type{}, t, S0);
     for (; t < steps; ++t) step(std::true_type{}, t, S0);
 
+    if constexpr (ZDROP) {
+        // ---- the records under the rule: the group leader writes the five numbers the epilogue helper hands every lane ----
+        const int price_ref = extend_zdrop_price(AFFINE ? args.ext_ref : args.gap_ref), price_read = extend_zdrop_price(AFFINE ? args.ext_read : args.gap_read);
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            int T;
+            const ExtendRec rec = extend_zdrop_rows_record<G, K>(rb, fc, half, lane, l, Rp[half], args.Z, price_ref, price_read, T);
+            const long long pair = w.pair0 + 2 * grp + half;
+            if (l == 0 && pair < args.n) args.extend[pair] = rec;
+        }
+        return;
+    }
     // ---- the best cell > 0 of each pair (write_end_cells: into the wave's LDS table; no pad rows above the read) ----
     FillArgs fa{};
     fa.n = args.n;
@@ -302,6 +373,24 @@ const void *extend_kernel(int gaps) {
         ext[kGapAffineSym] = (const void *)&score_extend_kernel<G, K, kGapAffineSym>;
     }
     return gaps >= 0 && gaps < 4 ? ext[gaps] : nullptr;
+}
+#endif
+
+// ... and their ZDROP forms (keys extend_zdrop > 0 and extend_zdrop_rows = 1): 24 more, on the same six geometries
+template <int G, int K, bool FULL>
+const void *extend_zdrop_kernel(int gaps);
+
+#ifdef VALIGN_KERNEL_PART_TU
+template <int G, int K, bool FULL>
+const void *extend_zdrop_kernel(int gaps) {
+    const void *dropping[4] = {};
+    if constexpr (FULL) {
+        dropping[kGapLinear] = (const void *)&score_extend_kernel<G, K, kGapLinear, true>;
+        dropping[kGapSym] = (const void *)&score_extend_kernel<G, K, kGapSym, true>;
+        dropping[kGapAffine] = (const void *)&score_extend_kernel<G, K, kGapAffine, true>;
+        dropping[kGapAffineSym] = (const void *)&score_extend_kernel<G, K, kGapAffineSym, true>;
+    }
+    return gaps >= 0 && gaps < 4 ? dropping[gaps] : nullptr;
 }
 #endif
 

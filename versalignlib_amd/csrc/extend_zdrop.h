@@ -2,7 +2,9 @@
 // tests/extend_zdrop_ref.py restates it): what a call under the key is -- refused, or the int32 strip sweep with or without a band
 // -- and the row-wise drop rule itself: the step of the running best, the associative combine of the prefix arg-max the sweep's
 // epilogue scans with, and when a strip is skipped.  Integers in, integers out; no HIP: one definition for the engine, the kernel
-// (extend_wide_kernels.hip.h, ZDROP) and the CPU check (tests/extend_zdrop_rules_check.cpp).
+// (extend_wide_kernels.hip.h, ZDROP) and the CPU check (tests/extend_zdrop_rules_check.cpp).  Below them, for the key
+// extend_zdrop_rows: the rule's lane form for the int16 register sweep (extend_kernels.hip.h / extend_align_kernels.hip.h, ZDROP) and
+// the two choices that wrap the older ones (tests/extend_zdrop_rows_rules_check.cpp).
 //
 // The rule is BWA's ksw_extend one with this library's rows as read positions: per row the maximum m_i over the present candidates
 // and its first column c_i; the running best (M, Mi, Mj) starts at the anchor (0, -1, -1) and moves to a row only with a strictly
@@ -97,6 +99,83 @@ inline ExtendAlignChoice extend_zdrop_align_choice(const RuleInputs &in, int alg
     ExtendAlignChoice c;
     c.reason = kExtendZdropAlign;
     return c;
+}
+
+// ---- key extend_zdrop_rows: the rule on the int16 register sweep (score_extend_kernel / align_extend_fill_kernel, ZDROP) ----
+// The register sweep ends with every row's maximum and first column in registers -- a group of G lanes, lane l holding rows
+// l K .. l K + K - 1 of one pair -- so the drop is decided in the epilogue; no cell, pointer or step changes.
+//
+// THE LANE FORM.  1. each lane combines its rows below Rp (extend_zdrop_combine, strict); 2. an exclusive prefix over the group's
+// lanes, seeded with the anchor; 3. each lane replays its rows from its prefix (extend_zdrop_replay_lane); 4. T is the minimum
+// of the lanes' answers.  Why the minimum is the serial rule's T: the prefix of a lane is the arg-max over ALL rows above the
+// lane's first, which is the serial running best there only if no row above dropped.  So every lane whose rows lie at or above
+// the true first drop holds the serial running best and replays the serial loop: the lane of the true T answers T, the lanes above
+// it answer nothing.  A lane below the true T may hold a prefix the serial loop never reached, but whatever it answers is one of
+// its own rows, all greater than T.  The record is the replay of lane T / K stopped at T; where nothing drops (T == Rp) the
+// inclusive best of the last lane with a row below Rp.
+//
+// RANGE.  The register route runs only where every cell stays inside int16 (extend_int16_ok), so after sign-extension M - m lies
+// in [0, 65535]; pen < 2^30 by the argument above; M - m - pen lies in (-2^30, 2^16) and is compared with Z <= 2^30 in int32.
+constexpr int kExtendZdropUnreached = (int)0x80000000;        // gscore of a dropped pair: VALIGN_HIP_EXTEND_UNREACHED (include/valign_hip.h)
+constexpr const char *kExtendZdropRowsKeyRange = "extend_zdrop_rows must be 0 or 1";
+inline bool extend_zdrop_rows_key_ok(long long on) { return on == 0 || on == 1; }
+
+struct ExtendZdropLane {
+    int T;                      // the lane's first dropping row below Rp and below the stop row, kExtendZdropNone where none drops
+    ExtendZdropBest best;       // the running best as it stands at min(T, stop_row): no row from there on has moved it
+};
+// One lane's replay: its K row entries (m[q], c[q]) are rows first_row + q; rows at or beyond Rp or stop_row count for nothing.
+__host__ __device__ inline ExtendZdropLane extend_zdrop_replay_lane(const int *m, const int *c, int K, int first_row, int Rp, int stop_row,
+                                                                    const ExtendZdropBest &prefix, int Z, int price_ref, int price_read) {
+    ExtendZdropLane out{kExtendZdropNone, prefix};
+    for (int q = 0; q < K; ++q) {
+        const int row = first_row + q;
+        if (out.T == kExtendZdropNone && row < Rp && row < stop_row && extend_zdrop_step(out.best, row, m[q], c[q], Z, price_ref, price_read)) out.T = row;
+    }
+    return out;
+}
+// ... and step 1 of the lane form: the combine of the lane's rows below Rp ("no row" where it has none)
+__host__ __device__ inline ExtendZdropBest extend_zdrop_lane_best(const int *m, const int *c, int K, int first_row, int Rp) {
+    ExtendZdropBest mine = extend_zdrop_no_row();
+    for (int q = 0; q < K; ++q)
+        if (first_row + q < Rp) mine = extend_zdrop_combine(mine, ExtendZdropBest{m[q], first_row + q, c[q]});
+    return mine;
+}
+// The lane whose replay is the record: T / K of a dropped pair, the last lane with a row below Rp otherwise (Rp > 0)
+__host__ __device__ inline int extend_zdrop_record_lane(int T, int Rp, int K) { return (T < Rp ? T : Rp - 1) / K; }
+
+constexpr const char *kExtendZdropRowsAlign = "extend_zdrop: the int32 route of unbanded extension alignments has no Z-drop form (extend_zdrop_rows = 1 runs Z-dropped "
+                                              "unbanded extension alignments on the int16 register sweep only; this call's shape, scoring or keys leave it)";
+
+// Extension scores under the key.  Read only where Z > 0 and no band is set: where plain extend_choice answers the register route
+// the call is Rows (score_width = 16 included); everything else is extend_zdrop_choice's answer.  rows_key = false, Z == 0 or a
+// band: exactly extend_zdrop_choice.
+inline PlacedChoice extend_zdrop_rows_choice(const RuleInputs &in, int alg, const PlacedFacts &f, int G, int K, int Z, bool rows_key) {
+    if (rows_key && extend_zdrop_on(Z) && f.band_width == 0) {
+        const PlacedChoice plain = extend_choice(in, alg, f, G, K);
+        if (plain.route == PlacedRoute::Rows) return plain;
+    }
+    return extend_zdrop_choice(in, alg, f, G, K, Z);
+}
+// ... does the call run the register sweep's ZDROP instances?
+inline bool extend_zdrop_rows_runs(const PlacedChoice &c, const PlacedFacts &f, int Z, bool rows_key) {
+    return rows_key && extend_zdrop_on(Z) && f.band_width == 0 && c.route == PlacedRoute::Rows;
+}
+
+// Extension alignments under the key.  Read only where Z > 0 and no band is set: Rows wherever plain extend_align_choice answers
+// the register route; every other unbanded call the mode bit or the policy does not refuse first is refused with
+// kExtendZdropRowsAlign.  rows_key = false, Z == 0 or a band: exactly extend_zdrop_align_choice.
+inline ExtendAlignChoice extend_zdrop_rows_align_choice(const RuleInputs &in, int alg, const PlacedFacts &f, int G, int K, int Z, bool rows_key) {
+    const ExtendAlignChoice today = extend_zdrop_align_choice(in, alg, f, G, K, Z);
+    if (!rows_key || !extend_zdrop_on(Z) || alg != kAlgSW || in.sse_policy || f.band_width > 0) return today;
+    const ExtendAlignChoice plain = extend_align_choice(in, alg, f, G, K);
+    if (plain.route == PlacedRoute::Rows) return plain;
+    ExtendAlignChoice c;
+    c.reason = kExtendZdropRowsAlign;
+    return c;
+}
+inline bool extend_zdrop_rows_runs(const ExtendAlignChoice &c, const PlacedFacts &f, int Z, bool rows_key) {
+    return rows_key && extend_zdrop_on(Z) && f.band_width == 0 && c.route == PlacedRoute::Rows;
 }
 
 }  // namespace valign

@@ -516,6 +516,14 @@ VALIGN_EXPORT int valign_hip_set_extend_zdrop(valign_hip_engine *e, int Z) {
     return flat_guard([&] { e->impl->set_extend_zdrop(Z); });
 }
 
+VALIGN_EXPORT int valign_hip_set_extend_zdrop_rows(valign_hip_engine *e, int on) {
+    if (!e) {
+        g_last_error = "null engine";
+        return 1;
+    }
+    return flat_guard([&] { e->impl->set_extend_zdrop_rows(on); });
+}
+
 VALIGN_EXPORT int valign_hip_set_trace_checkpoints(valign_hip_engine *e, int on) {
     if (!e) {
         g_last_error = "null engine";

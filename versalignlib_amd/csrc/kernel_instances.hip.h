@@ -96,7 +96,9 @@
 // The extension-score kernels (extend_kernels.hip.h: extend_kernel<G, K, FULL>, score_extend_kernel): the four gap forms on the six
 // full geometries, 24 instances
 #define VALIGN_EXTEND_KERNELS(PREFIX, G, K, FULL) PREFIX const void *extend_kernel<G, K, FULL>(int);
+// ... and their ZDROP forms (extend_zdrop_kernel<G, K, FULL>: keys extend_zdrop > 0 and extend_zdrop_rows = 1), 24 more
+#define VALIGN_EXTEND_ZDROP_KERNELS(PREFIX, G, K, FULL) PREFIX const void *extend_zdrop_kernel<G, K, FULL>(int); PREFIX const void *extend_align_zdrop_kernel<G, K, FULL>(int);
 
 // The extension-alignment fills (extend_align_kernels.hip.h: extend_align_kernel<G, K, FULL>, align_extend_fill_kernel): linear and
-// affine gaps on the six full geometries, 12 instances
+// affine gaps on the six full geometries, 12 instances (and 12 ZDROP forms: extend_align_zdrop_kernel<G, K, FULL>, above)
 #define VALIGN_EXTEND_ALIGN_KERNELS(PREFIX, G, K, FULL) PREFIX const void *extend_align_kernel<G, K, FULL>(int);

@@ -14,8 +14,8 @@
 
 namespace valign {
 
-#define VALIGN_DEFINE_FULL(G, K) VALIGN_FAST_KERNELS(template, G, K) VALIGN_FALLBACK_KERNELS(template, G, K) VALIGN_PLACED_KERNELS(template, G, K, true) VALIGN_SUBOPT_KERNELS(template, G, K, true) VALIGN_EXTEND_KERNELS(template, G, K, true) VALIGN_EXTEND_ALIGN_KERNELS(template, G, K, true)
-#define VALIGN_DEFINE_FAST(G, K) VALIGN_FAST_KERNELS(template, G, K) VALIGN_PLACED_KERNELS(template, G, K, false) VALIGN_SUBOPT_KERNELS(template, G, K, false) VALIGN_EXTEND_KERNELS(template, G, K, false) VALIGN_EXTEND_ALIGN_KERNELS(template, G, K, false)
+#define VALIGN_DEFINE_FULL(G, K) VALIGN_FAST_KERNELS(template, G, K) VALIGN_FALLBACK_KERNELS(template, G, K) VALIGN_PLACED_KERNELS(template, G, K, true) VALIGN_SUBOPT_KERNELS(template, G, K, true) VALIGN_EXTEND_KERNELS(template, G, K, true) VALIGN_EXTEND_ALIGN_KERNELS(template, G, K, true) VALIGN_EXTEND_ZDROP_KERNELS(template, G, K, true)
+#define VALIGN_DEFINE_FAST(G, K) VALIGN_FAST_KERNELS(template, G, K) VALIGN_PLACED_KERNELS(template, G, K, false) VALIGN_SUBOPT_KERNELS(template, G, K, false) VALIGN_EXTEND_KERNELS(template, G, K, false) VALIGN_EXTEND_ALIGN_KERNELS(template, G, K, false) VALIGN_EXTEND_ZDROP_KERNELS(template, G, K, false)
 #if VALIGN_PART == 0
 VALIGN_PART0(VALIGN_DEFINE_FULL, VALIGN_DEFINE_FAST)
 #elif VALIGN_PART == 1

@@ -91,6 +91,7 @@ def lib():
         L.valign_hip_set_extend_wide.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_extend_band.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_extend_zdrop.argtypes = [vp, ctypes.c_int]
+        L.valign_hip_set_extend_zdrop_rows.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_extend_band_align.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_trace_checkpoints.argtypes = [vp, ctypes.c_int]
         L.valign_hip_set_pointer_scratch_cap_mb.argtypes = [vp, ctypes.c_longlong]
@@ -135,7 +136,7 @@ EXTEND_UNREACHED = -(1 << 31)           # VALIGN_HIP_EXTEND_UNREACHED: gscore of
 EXPORTED_SYMBOLS = (
     "spawn_alignment_kernel", "set_parameters", "set_logger", "delete_alignment_kernel",
     "valign_hip_device_count", "valign_hip_shard_range", "valign_hip_engine_create", "valign_hip_engine_destroy",
-    "valign_hip_set_traceback_policy", "valign_hip_set_pointer_scratch_cap_mb", "valign_hip_set_host_packing", "valign_hip_set_half_float_cells", "valign_hip_host_register", "valign_hip_host_unregister", "valign_hip_set_band_width", "valign_hip_set_band_alignments", "valign_hip_set_band_nw", "valign_hip_set_band_placed", "valign_hip_set_placed_wide", "valign_hip_set_extend_wide", "valign_hip_set_extend_band", "valign_hip_set_extend_band_align", "valign_hip_set_extend_zdrop", "valign_hip_set_trace_checkpoints", "valign_hip_set_score_width", "valign_hip_set_ragged_batching", "valign_hip_score_device", "valign_hip_align_device", "valign_hip_score_host", "valign_hip_align_host", "valign_hip_align_cigar_device", "valign_hip_align_cigar_host", "valign_hip_score_placed_device", "valign_hip_score_placed_host", "valign_hip_score_span_device", "valign_hip_score_span_host", "valign_hip_align_span_device", "valign_hip_align_span_host", "valign_hip_score_subopt_device", "valign_hip_score_subopt_host", "valign_hip_score_extend_device", "valign_hip_score_extend_host", "valign_hip_align_extend_device", "valign_hip_align_extend_host", "valign_hip_describe",
+    "valign_hip_set_traceback_policy", "valign_hip_set_pointer_scratch_cap_mb", "valign_hip_set_host_packing", "valign_hip_set_half_float_cells", "valign_hip_host_register", "valign_hip_host_unregister", "valign_hip_set_band_width", "valign_hip_set_band_alignments", "valign_hip_set_band_nw", "valign_hip_set_band_placed", "valign_hip_set_placed_wide", "valign_hip_set_extend_wide", "valign_hip_set_extend_band", "valign_hip_set_extend_band_align", "valign_hip_set_extend_zdrop", "valign_hip_set_extend_zdrop_rows", "valign_hip_set_trace_checkpoints", "valign_hip_set_score_width", "valign_hip_set_ragged_batching", "valign_hip_score_device", "valign_hip_align_device", "valign_hip_score_host", "valign_hip_align_host", "valign_hip_align_cigar_device", "valign_hip_align_cigar_host", "valign_hip_score_placed_device", "valign_hip_score_placed_host", "valign_hip_score_span_device", "valign_hip_score_span_host", "valign_hip_align_span_device", "valign_hip_align_span_host", "valign_hip_score_subopt_device", "valign_hip_score_subopt_host", "valign_hip_score_extend_device", "valign_hip_score_extend_host", "valign_hip_align_extend_device", "valign_hip_align_extend_host", "valign_hip_describe",
     "valign_hip_last_error",
 )
 
@@ -292,6 +293,15 @@ class Engine:
         if not -(1 << 31) <= int(Z) < (1 << 31):
             raise HipKernelError("extend_zdrop must be in [0, 2^30]")
         if lib().valign_hip_set_extend_zdrop(self._h, int(Z)) != 0:
+            raise HipKernelError(_err())
+
+    def set_extend_zdrop_rows(self, on):
+        """1: under extend_zdrop > 0 and without a band, score_extend_* and align_extend_* calls that would run the int16 register
+        sweep without extend_zdrop run its ZDROP instances -- the drop row is decided in the sweep's epilogue from the row maxima it
+        already holds (describe: ran_extend / ran_extend_align "rows", ran_extend_zdrop Z, no skipped waves; score_width = 16
+        runs; unbanded alignments exist); every other call answers as extend_zdrop alone says, unbanded alignments off the register
+        route with a text of their own.  0 (default): as extend_zdrop alone says.  include/valign_hip.h has the definition."""
+        if lib().valign_hip_set_extend_zdrop_rows(self._h, int(on)) != 0:
             raise HipKernelError(_err())
 
     def set_extend_band_align(self, on):
